@@ -12,12 +12,18 @@ Default (what the driver runs):  --config 2
            only cross-rank step is the one-off 255-sample hand-over to the
            right-hand neighbour over RCCL (setup, untimed).  The data path has no
            collective -> weak scaling (per-GPU work fixed) for `value`.
-  Beside `value`, the same JSON line carries `stream_2p30`: the north-star's
-  2^30-sample stream cut into N contiguous shards of 2^30/N samples per rank
-  (strong scaling; every shard is far past the 256 MiB Infinity Cache, so its FIR
-  fraction is the HBM-resident figure).
+  A plain run does only what `value` needs: set-up, the untimed settle + W warm-up
+  steps, the K timed steps, the outputs (--dump-outputs) and the result line.
+  --full adds everything else, as before: the host-pointer leg (`host_vec`), the
+  self-check against the fused chain node, the kernel timer (`roofline`, `ranks`),
+  the fused chain's own timed loop (`fused_chain`), the copy ceiling, the CPU
+  baseline and `stream_2p30`: the north-star's 2^30-sample stream cut into N
+  contiguous shards of 2^30/N samples per rank (strong scaling; every shard is far
+  past the 256 MiB Infinity Cache, so its FIR fraction is the HBM-resident figure).
+  --dump-outputs DIR: after the timed steps, what the last timed step handed its
+  caller, as DIR/<name>.npy (float32 re / im pairs; see dump_outputs()).
 
-Other BASELINE configs (same contract, one JSON line each, each with roofline + cpu_baseline at N = 1):
+Other BASELINE configs (--full only; same contract, one JSON line each, each with roofline + cpu_baseline at N = 1):
   --config 1   the reference's own CPU case on the GPU: PRBS7 -> BPSK -> 63-tap RRC x4 -> mixer, 2^20 samples per step,
                one launch; cpu_baseline = the whole config through the oracle
   --config 3   mixer -> 127-tap LPF -> decimate-by-8 -> FM demod, 2^26 samples per rank,
@@ -30,7 +36,7 @@ Other BASELINE configs (same contract, one JSON line each, each with roofline + 
                reported separately from the compute (`transfer`).
   --backend gloo --n-log2 K   rehearsal aid: CPU-side messages, ranks may share a GPU, smaller shards.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
         N > 1 without RANK in the environment: this process only spawns N rank processes
         (child processes, never exec; it has not touched the GPU) and relays rank 0's line.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -657,9 +663,33 @@ def rank_report(ctx, kernel_ms):
             "kernel_ms_max": round(max(per), 5)}
 
 
-def fir_chain_pass(ctx, n, first_index, steps, warmup, algo="auto", stride=TIMER_STRIDE):
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: all files of all ranks together stay below this
+
+
+def dump_outputs(ctx, out_dir, arrays):
+    """--dump-outputs: each device array of `arrays` (name -> tensor) as out_dir/<name>.npy, complex as float32 (m, 2)
+    re / im rows (N > 1: every rank r writes <name>_rank<r>.npy).  Each array gets an equal share of DUMP_BYTES; one larger
+    than its share is written as a fixed sample of its rows (drawn from a generator seeded with SEED, in index order),
+    so that two runs with the same arguments write the same rows."""
+    torch = ctx.torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // (len(arrays) * ctx.world)
+    for name, t in arrays.items():
+        a = torch.view_as_real(t) if t.is_complex() else t
+        row_bytes = a[:1].numel() * 4
+        if a.shape[0] * row_bytes > share:
+            rows = share // row_bytes - 32     # (room for the .npy header)
+            idx = np.sort(np.random.default_rng(SEED).choice(a.shape[0], rows, replace=False))
+            a = a[torch.from_numpy(idx).to(a.device)]
+        suffix = "_rank%d" % ctx.rank if ctx.world > 1 else ""
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a.float().cpu().numpy())
+
+
+def fir_chain_pass(ctx, n, first_index, steps, warmup, algo="auto", stride=TIMER_STRIDE, full=True, dump_dir=None):
     """The metric's chain, node by node, over this rank's shard [first_index, first_index + n) of the
-    stream: 255-tap BatchFirNode -> MixerNode -> DecimateNode.  Returns timings + the nodes' facts."""
+    stream: 255-tap BatchFirNode -> MixerNode -> DecimateNode.  Returns timings + the nodes' facts.
+    full=False: only the settle, the warm-up and the timed steps (no self-check, no kernel timer, no fused chain,
+    no copy ceiling).  dump_dir: what the last timed step produced goes there (dump_outputs)."""
     import comms_rs_amd as c
     from comms_rs_amd.sharding import halo_exchange, shard_mixer_phase, state_from_halo
 
@@ -698,34 +728,35 @@ def fir_chain_pass(ctx, n, first_index, steps, warmup, algo="auto", stride=TIMER
         mixer.run_dev(y.data_ptr(), n, y.data_ptr(), s)
         dec.run_dev(y.data_ptr(), n, 8, z.data_ptr(), s)
 
-    # ---- self-check of the first step (fail loudly): the node-by-node chain (FFT overlap-save
-    # FIR, then mixer, then decimate) against the fused chain node, an independent time-domain
-    # kernel, on the same shard.  (Parity with the reference's arithmetic is the job of tests/
-    # and smoke(); nothing on this path touches the CPU checker.)
-    step()
-    chk = c.ChainNode(MIX_DPHASE, mix_phase, taps, DEC_RATE, False, device=ctx.local_rank, mixer_after_fir=True)
-    if h is not None:
-        chk.set_fir_state(state_from_halo(h))
-    zc = torch.empty_like(z)
-    chk.run_dev(x.data_ptr(), n, zc.data_ptr(), s)
-    torch.cuda.synchronize()
-    bound = 2e-5 * float(np.sum(np.abs(taps)))
-    err = float((z - zc).abs().max())
-    ok = err <= bound
-    if ok and rank > 0 and ctx.args.variant != "scatter":
-        # the shard boundary itself: a fresh chain run over [prefix | first outputs] with no hand-over at
-        # all must agree, past its start-up transient, with what the halo-primed nodes produced
-        P, M = 512, 4096
-        xb = torch.empty(P + M, dtype=torch.complex64, device=ctx.dev)
-        c.synth_iq_dev(xb.data_ptr(), P + M, first_index - P, SEED, device=ctx.local_rank, stream=s)
-        zb = torch.empty((P + M) // DEC_RATE, dtype=torch.complex64, device=ctx.dev)
-        c.ChainNode(MIX_DPHASE, shard_mixer_phase(0.0, MIX_DPHASE, first_index - P), taps, DEC_RATE, False,
-                    device=ctx.local_rank, mixer_after_fir=True).run_dev(xb.data_ptr(), P + M, zb.data_ptr(), s)
+    if full:
+        # ---- self-check of the first step (fail loudly): the node-by-node chain (FFT overlap-save
+        # FIR, then mixer, then decimate) against the fused chain node, an independent time-domain
+        # kernel, on the same shard.  (Parity with the reference's arithmetic is the job of tests/
+        # and smoke(); nothing on this path touches the CPU checker.)
+        step()
+        chk = c.ChainNode(MIX_DPHASE, mix_phase, taps, DEC_RATE, False, device=ctx.local_rank, mixer_after_fir=True)
+        if h is not None:
+            chk.set_fir_state(state_from_halo(h))
+        zc = torch.empty_like(z)
+        chk.run_dev(x.data_ptr(), n, zc.data_ptr(), s)
         torch.cuda.synchronize()
-        err = max(err, float((zb[P // DEC_RATE:] - z[:M // DEC_RATE]).abs().max()))
+        bound = 2e-5 * float(np.sum(np.abs(taps)))
+        err = float((z - zc).abs().max())
         ok = err <= bound
-    ctx.all_ok(ok, "chain vs fused chain / shard boundary differ by %g (bound %g)" % (err, bound))
-    del chk, zc
+        if ok and rank > 0 and ctx.args.variant != "scatter":
+            # the shard boundary itself: a fresh chain run over [prefix | first outputs] with no hand-over at
+            # all must agree, past its start-up transient, with what the halo-primed nodes produced
+            P, M = 512, 4096
+            xb = torch.empty(P + M, dtype=torch.complex64, device=ctx.dev)
+            c.synth_iq_dev(xb.data_ptr(), P + M, first_index - P, SEED, device=ctx.local_rank, stream=s)
+            zb = torch.empty((P + M) // DEC_RATE, dtype=torch.complex64, device=ctx.dev)
+            c.ChainNode(MIX_DPHASE, shard_mixer_phase(0.0, MIX_DPHASE, first_index - P), taps, DEC_RATE, False,
+                        device=ctx.local_rank, mixer_after_fir=True).run_dev(xb.data_ptr(), P + M, zb.data_ptr(), s)
+            torch.cuda.synchronize()
+            err = max(err, float((zb[P // DEC_RATE:] - z[:M // DEC_RATE]).abs().max()))
+            ok = err <= bound
+        ctx.all_ok(ok, "chain vs fused chain / shard boundary differ by %g (bound %g)" % (err, bound))
+        del chk, zc
 
     # Clock settling in front of the W warm-up steps (short batches only): a burst of launches runs its first ~2 ms at boost clocks, the
     # next ~20 ms up to 40 % slower, then settles (profiles/r05_config3_poly8_launch_order.txt, r03_config5_kernel_trace.txt).  The
@@ -739,10 +770,21 @@ def fir_chain_pass(ctx, n, first_index, steps, warmup, algo="auto", stride=TIMER
                 step()
             torch.cuda.synchronize()
             settle_steps += 20
+    # The settling runs for a time, not a number of steps: the oscillator starts over behind it (host state, no GPU idle), so
+    # the last timed step's outputs depend on W + K alone (--dump-outputs compares runs output for output; the FIR state is
+    # the batch's own tail after any step)
+    mixer.phase = mix_phase
     for _ in range(warmup):
         step()
-    timer = c.KernelTimer(max(steps, 1), device=ctx.local_rank, stamps="both", stride=stride).attach(fir)
+    timer = c.KernelTimer(max(steps, 1), device=ctx.local_rank, stamps="both", stride=stride).attach(fir) if full else None
     elapsed = ctx.timed(step, steps, 0)
+    if dump_dir is not None:
+        dump_outputs(ctx, dump_dir, {"chain_out": z, "mixer_out": y})
+    if not full:
+        res = {"elapsed": elapsed, "algo": fir.kernel_for(n), "transfer": transfer, "settle_steps": settle_steps}
+        del x, y, z, fir, mixer
+        torch.cuda.empty_cache()
+        return res
     kms, sms = kernel_times(timer)
     timer.close()
     ctx.collect(z, transfer)
@@ -852,24 +894,25 @@ def run_config2(ctx):
     # device buffers allocated and released again) the same pageable copies run at half the rate (FIR node 5.2 -> 2.8
     # Gsamples/s on one box, `profiles/r05_host_pipeline.txt`), which says something about that process state, not about
     # the path.  It touches the GPU for a few milliseconds: the legs below are not affected.
-    host_vec = host_vec_leg(ctx, min(n, N_SAMPLES)) if (ctx.rank == 0 and not args.no_host_vec) else None
+    # (a plain run: the headline alone; the host-pointer and stream legs are part of --full)
+    full = args.full
+    host_vec = host_vec_leg(ctx, min(n, N_SAMPLES)) if (full and ctx.rank == 0 and not args.no_host_vec) else None
     stream = None
-    if args.stream_log2 and not args.head_first:
+    if full and args.stream_log2 and not args.head_first:
         stream = stream_leg()
-    head = fir_chain_pass(ctx, n, ctx.rank * n, args.steps, args.warmup, args.algo)
-    if args.stream_log2 and args.head_first:
+    head = fir_chain_pass(ctx, n, ctx.rank * n, args.steps, args.warmup, args.algo, full=full, dump_dir=args.dump_outputs)
+    if full and args.stream_log2 and args.head_first:
         stream = stream_leg()
     if ctx.rank != 0:
         return None
-    kernel_ms, algo = head["kernel_ms"], head["algo"]
+    algo = head["algo"]
     total = float(world) * n * args.steps
-    achieved = FIR_BYTES_PER_SAMPLE * n / (kernel_ms * 1e-3) / 1e9
     out = {
         "metric": "Msamples/s Complex<f32> through 255-tap FIR->mix->decimate chain",
         "value": round(total / head["elapsed"] / 1e6, 1),
         "unit": "Msamples/s",
         "n_gpus": world,
-        "world_size_seen": head["ranks"]["world_size_seen"],
+        "world_size_seen": ctx.world_size_seen(),
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(head["elapsed"] / args.steps * 1e3, 4),
@@ -884,9 +927,24 @@ def run_config2(ctx):
                    "samples_per_gpu_per_step": n, "n_taps": N_TAPS, "dec_rate": DEC_RATE,
                    "fir_kernel": algo, "sharding": "contiguous stream shards, one-off RCCL halo",
                    "variant": args.variant, "backend": args.backend,
-                   "leg_order": "headline first" if (args.head_first or not args.stream_log2) else
+                   "leg_order": "headline only (--full: the other legs and figures)" if not full else
+                                "headline first" if (args.head_first or not args.stream_log2) else
                                 "2^%d-sample stream leg first (clock warm-up), then the headline" % args.stream_log2,
                    "settle": "%d untimed steps (%g ms) in front of the W warm-up steps: the chip's start-up clock transient" % (head["settle_steps"], args.settle_ms)},
+        "full": full,
+    }
+    if args.dump_outputs:
+        out["dump_outputs"] = {"chain_out": "DecimateNode output of the last timed step (N > 1: one file per rank)",
+                               "mixer_out": "MixerNode output of that step (FIR -> mixer, in place), a seeded sample of its "
+                                            "rows when larger than its share of %d bytes" % DUMP_BYTES}
+    if args.n_log2:
+        out["rehearsal"] = "per-GPU size overridden (--n-log2): not a BASELINE-config number"
+    if not full:
+        out["box"] = box_info(ctx.torch, ctx.local_rank)
+        return out
+    kernel_ms = head["kernel_ms"]
+    achieved = FIR_BYTES_PER_SAMPLE * n / (kernel_ms * 1e-3) / 1e9
+    out.update({
         "roofline": {"bound": "hbm", "kernel": algo, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": pmc_traffic(algo, n),
@@ -897,7 +955,7 @@ def run_config2(ctx):
                      "algorithmic_bytes_per_launch": FIR_BYTES_PER_SAMPLE * n, "ceiling": head["ceiling"]},
         "ranks": head["ranks"],
         "box": box_info(ctx.torch, ctx.local_rank),
-    }
+    })
     fused_ms = head["fused_elapsed"] / args.steps * 1e3
     fused_bytes = 9.0 * n   # 8 B read + 8/8 B written per input sample
     out["fused_chain"] = {"value": round(total / head["fused_elapsed"] / 1e6, 1), "unit": "Msamples/s",
@@ -933,8 +991,6 @@ def run_config2(ctx):
             out["stream_2p30"]["transfer"] = st["transfer"]
     if head["transfer"]:
         out["transfer"] = head["transfer"]
-    if args.n_log2:
-        out["rehearsal"] = "per-GPU size overridden (--n-log2): not a BASELINE-config number"
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(n)
     return out
@@ -1440,7 +1496,20 @@ def main():
                          "the timed loop, and exit: a seconds-long first use of an N-GPU node")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous of the N ranks only (gloo on the CPU), no GPU work: checks the launcher")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: host-pointer and 2^30-sample stream legs, self-check, kernel timer / "
+                         "roofline, fused chain, CPU baseline; and configs 1, 3, 4, 5 and --variant scatter")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="config 2: write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and args.config != 2:
+        ap.error("--config %d is part of --full (a plain run times the config 2 headline only)" % args.config)
+    if not args.full and args.variant != "inplace":
+        ap.error("--variant %s is part of --full (a plain run times the config 2 headline only)" % args.variant)
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs covers the config 2 headline chain only")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     if args.launch_check:

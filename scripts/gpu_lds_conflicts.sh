@@ -9,10 +9,10 @@ while IFS= read -r cmd; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $OUT/p$i -o pmc -- $cmd > $OUT/p$i.log 2>&1 || { echo "pass $i failed: $cmd"; tail -3 $OUT/p$i.log; }
 done <<'CMDS'
-python3 bench.py --no-cpu-baseline --stream-log2 0 --steps 20 --warmup 5
-python3 bench.py --config 1 --no-cpu-baseline --steps 20 --warmup 5
-python3 bench.py --config 3 --no-cpu-baseline --steps 10 --warmup 2
-python3 bench.py --config 5 --no-cpu-baseline --steps 10 --warmup 2
+python3 bench.py --full --no-cpu-baseline --stream-log2 0 --steps 20 --warmup 5
+python3 bench.py --full --config 1 --no-cpu-baseline --steps 20 --warmup 5
+python3 bench.py --full --config 3 --no-cpu-baseline --steps 10 --warmup 2
+python3 bench.py --full --config 5 --no-cpu-baseline --steps 10 --warmup 2
 python3 scripts/bench_fft.py 6 8 10 11 12 13 14 15 17 20 22
 python3 scripts/bench_fir.py 511 24 20
 python3 scripts/bench_fir.py 32 22 20

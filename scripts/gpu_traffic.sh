@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/traffic; mkdir -p $OUT
 for cnt in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 400 rocprofv3 --pmc $cnt --output-format csv -d $OUT/$cnt -o pmc -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --stream-log2 0 > $OUT/$cnt.log 2>&1 || { echo "$cnt pass failed"; tail -3 $OUT/$cnt.log; }
+  timeout -k 10 400 rocprofv3 --pmc $cnt --output-format csv -d $OUT/$cnt -o pmc -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --stream-log2 0 > $OUT/$cnt.log 2>&1 || { echo "$cnt pass failed"; tail -3 $OUT/$cnt.log; }
 done
 python3 - <<PY
 import csv, glob, json, collections
@@ -25,7 +25,7 @@ if key:
     d = {"kernel": k.split("::")[-1].split("<")[0], "n_samples": 1 << 24,
          "fetch_size_bytes_raw": fetch, "write_size_bytes": write,
          "hbm_bytes_per_launch": 2.0 * fetch + write,
-         "note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over bench.py --steps 50; "
+         "note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over bench.py --full --steps 50; "
                  "counters are KiB; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports half the bytes of a "
                  "wide coalesced streaming read); algorithmic bytes per launch = 268435456"}
     json.dump(d, open("$OUT/pmc_traffic.json", "w"), indent=1)
