@@ -4,13 +4,16 @@
 // reference nodes in series -- MixerNode -> BatchFirNode -> DecimateNode
 // [-> FMDemodNode] (BASELINE config 3; examples/fm_radio.rs:146-148 order with a
 // mixer in front) or BatchFirNode -> MixerNode -> DecimateNode (the BASELINE
-// metric's chain).  Up to 257 taps it is ONE launch: 8 B read per input sample and
-// 8/R (or 4/R) B written, instead of 16 + 16 + 9 + 1.5 B for the four nodes --
-//   * fir_decim_kernel (fir_decim.hip): time domain, computes only the kept outputs;
-//     used when taps/rate is small enough to beat the FFT (rates 2,3,4,5,6,8,10,12,16);
-//   * fir_os1024_kernel<.., MODE> (fir.hip): the 1024-point overlap-save kernel with
-//     the extra stages fused in registers, for everything else.
-// Longer filters run the four device kernels back to back through HBM temporaries.
+// metric's chain).  plan_chain picks one kind per chain when it is created:
+//   Series      mixer, FIR, decimator [, FM demod]: four launches through HBM temporaries
+//   SeriesPost  FIR, then mixer + decimator in one pass over the kept samples [, FM demod]
+//   Os1024      fir_os1024_kernel<.., MODE> (fir.hip): 1024-point overlap-save, the extra stages fused in registers
+//   Decim       fir_decim_kernel (fir_decim.hip): time domain, computes only the kept outputs
+//   DecimAny    fir_decim_any_kernel (fir_decim_any.hip): the same at any rate
+//   Poly8       fir_poly8_kernel (fir_poly8.hip): polyphase branches in the frequency domain
+//   Os4096Dec   fir_os4096_kernel (fir.hip), mixer and decimator in its store stage
+//   Os16kDec    fir_os16k_kernel (fir.hip), the same
+// Decim and DecimAny hand a call to fir_poly8_kernel where it is the faster form for that batch.
 #include <cmath>
 #include <vector>
 
@@ -27,34 +30,52 @@ __global__ __launch_bounds__(256) void chain_raw_hist_kernel(const float2* __res
     hist_advance(old_hist, in, n, new_hist, HL);
 }
 
+enum class ChainKind : uint8_t { Series, SeriesPost, Os1024, Decim, DecimAny, Poly8, Os4096Dec, Os16kDec };  // (the map above)
+
+// one fused launch (+ the demodulator's own, if fm_separate)
+static bool is_fused(ChainKind k) { return k != ChainKind::Series && k != ChainKind::SeriesPost; }
+// the kernel converts raw i16 / u8 IQ in its load stage; the other kinds get one conversion pass first
+static bool reads_wire_format(ChainKind k) {
+    return k == ChainKind::Decim || k == ChainKind::DecimAny || k == ChainKind::Poly8 || k == ChainKind::Os4096Dec;
+}
+// the mixer runs in front of the FIR node, whose history then holds mixed samples: the raw ones are kept beside it
+static bool has_raw_history(ChainKind k) { return k == ChainKind::Series; }
+// the kernel takes the FM demodulator's state (d_prev, ping-pong) as arguments
+static bool has_fm_prev(ChainKind k) {
+    return k == ChainKind::Os1024 || k == ChainKind::Decim || k == ChainKind::DecimAny || k == ChainKind::Poly8;
+}
+
+struct ChainPlan {
+    ChainKind kind = ChainKind::Series;
+    bool fm_separate = false;     // the FM demodulator runs as its own launch (behind the fused one, or last of the series)
+    bool taps_modulated = false;  // the mixer in front is folded into the taps
+    int32_t mode = 0;             // COMMS_CHAIN_* bits of the fused launch
+};
+
 struct comms_chain : Handle {
-    bool fused = false;
-    bool decim = false;  // fused on the time-domain decimating kernel
-    bool decim_any = false;  // ... on its any-rate form (fir_decim_any.hip; a mixer in front is folded into the taps)
-    bool poly8 = false;      // COMMS_CHAIN_POLYPHASE: always the polyphase frequency-domain kernel (fir_poly8.hip)
-    bool fm_separate = false;  // fused mixer / FIR / decimate launch, FM demod as its own (small) kernel behind it
-    bool os_dec = false;       // fused: the 4096-point overlap-save kernel with mixer and decimator in its store stage (258 ... 1537 taps)
-    bool os_dec16 = false;     // ... the 16384-point kernel (1538 ... 4097 taps; Complex<f32> input: raw formats take the conversion pass)
-    bool pre_as_post = false;  // series of launches, mixer in front folded into the taps: runs as the mixer-behind form
-    int mode = 0;
-    // fused path state
+    ChainKind kind = ChainKind::Series;
+    bool fm_separate = false;  // (ChainPlan)
+    int32_t mode = 0;
+    bool time_domain = false;  // COMMS_CHAIN_TIME_DOMAIN: Decim / DecimAny never hand a call to the polyphase kernel
+    bool ran_poly8 = false;    // Decim / DecimAny: the last call ran fir_poly8_kernel (comms_chain_is_fused)
+    size_t rate = 1;
+    bool fm_demod = false;
     comms_fir_t* fir = nullptr;
+    // fused kinds: oscillator phase and FM demod state
     uint64_t turns = 0, frac = 0;
     float2* d_prev[2] = {nullptr, nullptr};
     int cur = 0;
-    // unfused path
+    // series kinds
     comms_mixer_t* mixer = nullptr;
-    comms_fmdemod_t* fm = nullptr;
-    size_t rate = 1;
+    comms_fmdemod_t* fm = nullptr;  // (and fm_separate)
     double dphase = 0.0;  // wrapped, as the mixer steps it
-    bool fm_demod = false, mixer_after = false;
     Scratch t1, t2, t3;
-    float2* raw_hist[2] = {nullptr, nullptr};  // unfused + mixer first: last n_eff raw inputs, time order
+    float2* raw_hist[2] = {nullptr, nullptr};  // has_raw_history: last n_eff raw inputs, time order
     int raw_cur = 0;
     std::vector<comms_c32> pending_raw;        // a user state not yet mixed into the FIR node's history
     int in_fmt = COMMS_IQ_C32;                 // wire format of d_in (comms_chain_set_input_format)
     float in_scale = 1.0f;
-    Scratch t0;                                // converted input, for the paths that read Complex<f32> only
+    Scratch t0;                                // converted input, for the kinds that read Complex<f32> only
 };
 
 // four-kernel path with the mixer in front: the FIR node keeps MIXED samples, so a raw user history is
@@ -95,6 +116,128 @@ static void free_chain(comms_chain* h) {
     delete h;
 }
 
+// Which kind runs this chain, decided once from the filter (the user's taps), the rate and the COMMS_CHAIN_* flags.
+// Rules in order of precedence: forced and long polyphase, any-rate, the fused and time-domain forms, the long
+// overlap-save decimating forms, the series.
+static ChainPlan plan_chain(const comms_fir* fir, size_t rate, int32_t flags) {
+    const bool fm = (flags & COMMS_CHAIN_FM_DEMOD) != 0;
+    const bool after = (flags & COMMS_CHAIN_MIXER_AFTER_FIR) != 0;
+    const size_t n_taps = static_cast<size_t>(fir->n_eff);
+    const uint32_t r32 = static_cast<uint32_t>(rate);
+    ChainPlan p;
+    const int32_t poly_mode = (after ? COMMS_CHAIN_POST : COMMS_CHAIN_PRE) | COMMS_CHAIN_DEC | (fm ? COMMS_CHAIN_FM : 0);
+    const bool force_poly8 = (flags & COMMS_CHAIN_POLYPHASE) && !(flags & COMMS_CHAIN_UNFUSED) &&
+                             comms_fir_poly8_supported(fir, r32, poly_mode, static_cast<size_t>(1) << 26) != 0;
+    // Filters too long for the other fusions (258 ... 513 taps; until round 5 these chains ran as overlap-save FIR + mixer-decimator
+    // [+ demodulator]: 80 us at 2^24 samples and rate 8): the polyphase kernel with five to eight halo rows, where it takes every
+    // call of the filter (asked with the shortest batch); the demodulator in the kernel where it has one (rates 8 and 4, 505
+    // taps), as its own launch over the kept samples otherwise.
+    bool poly_long = false, poly_long_fm = false;
+    if (n_taps > 257 && !force_poly8 && !(flags & (COMMS_CHAIN_UNFUSED | COMMS_CHAIN_TIME_DOMAIN | COMMS_CHAIN_FREQ_DOMAIN))) {
+        poly_long_fm = fm && comms_fir_poly8_supported(fir, r32, poly_mode, rate) == 2;
+        poly_long = poly_long_fm || comms_fir_poly8_supported(fir, r32, poly_mode & ~COMMS_CHAIN_FM, rate) == 2;
+    }
+    if (force_poly8 || poly_long) {
+        p.kind = ChainKind::Poly8;
+        p.fm_separate = poly_long && fm && !poly_long_fm;
+        p.mode = p.fm_separate ? (poly_mode & ~COMMS_CHAIN_FM) : poly_mode;
+        return p;
+    }
+    const bool can_fuse_nofm = !(flags & COMMS_CHAIN_UNFUSED) && n_taps <= 257 && rate <= (1u << 20);
+    // FM chains on the overlap-save path: mixer / FIR / decimate as the one fused launch, the demodulator as its
+    // own kernel over the n / rate decimated samples.  That beats demodulating inside the overlap-save kernel at
+    // every rate (2^24 samples, 127 taps: /2 85.8 against 95.9 us, /3 68 against 83, /8 60 against 82 -- the fused
+    // form needs `rate` more halo samples per segment and an atan2 per output in a kernel short of issue slots) and
+    // has no limit on taps + rate; COMMS_CHAIN_FM_SEPARATE=0 brings the in-kernel form back for comparison.
+    static const int fm_sep = diag_knob("COMMS_CHAIN_FM_SEPARATE", 1);
+    const bool can_fuse = can_fuse_nofm && (!fm || (!fm_sep && rate <= 64 && n_taps + rate <= 257));
+    const bool can_hybrid = fm && can_fuse_nofm && !can_fuse;
+    // the time-domain kernel against what would run otherwise: an overlap-save fusion, or the four kernels in
+    // series, which it beats up to many more MACs per input sample
+    const int decim_ok = rate <= 16 ? comms_fir_decim_supported_for(fir, r32, fm ? 1 : 0, can_fuse || can_hybrid ? 1 : 0) : 0;
+    // (rate 4 with a long filter: too many MACs for the time-domain kernel, but its chain kind is the one that reaches the polyphase
+    // frequency-domain kernel, which takes every call from 64 taps -- fir_poly8.hip)
+    const bool poly_pref = decim_ok >= 1 && !(flags & COMMS_CHAIN_TIME_DOMAIN) &&
+                           comms_fir_poly8_supported(fir, r32, COMMS_CHAIN_DEC | (fm ? COMMS_CHAIN_FM : 0), static_cast<size_t>(1) << 26) == 2;
+    // FM chains where that kernel runs without its demodulator (rates 12 ... 64; rate 4 beyond 249 taps): mixer / FIR / decimate on
+    // it and the demodulator as its own small launch over the n / rate kept samples, where the kernel takes EVERY call of this
+    // filter (asked with the shortest batch) -- rate 4, 255 taps, 2^24 samples: ~50 us against 70 for the overlap-save launch +
+    // demodulator (up to 249 taps the demodulator runs in the kernel: poly_pref above)
+    const bool poly_sep = fm && rate != 8 && !poly_pref && !(flags & (COMMS_CHAIN_TIME_DOMAIN | COMMS_CHAIN_FREQ_DOMAIN | COMMS_CHAIN_UNFUSED)) &&
+                          comms_fir_poly8_supported(fir, r32, COMMS_CHAIN_DEC, rate) == 2;
+    const bool can_decim = !(flags & (COMMS_CHAIN_UNFUSED | COMMS_CHAIN_FREQ_DOMAIN)) &&
+                           (decim_ok == 2 || poly_pref || (poly_sep && decim_ok >= 1) || (decim_ok == 1 && (flags & COMMS_CHAIN_TIME_DOMAIN)));
+    // Rates the per-rate kernel is not built for (17 and up; 11 / 13 / 15 with complex taps): the any-rate kernel (half
+    // a wave per output).  Against the overlap-save launch it replaces (58-61 us at 2^24 samples whatever the rate): 255
+    // taps 60 us at rate 17, 53 at 20, 39 at 32, 30 at 100, 11 at 1000; 127 taps 49 at 17; 63 taps 45 at 17
+    // (profiles/r03_bench_chain_rates.txt) -- so from rate 17; taps up to 512, where the alternative is four kernels in
+    // series.  COMMS_CHAIN_TIME_DOMAIN forces it wherever it can run.
+    static const int any_min_rate = diag_knob("COMMS_ANY_MIN_RATE", 17);
+    const size_t any_from = static_cast<size_t>(any_min_rate);
+    const bool can_any = !can_decim && !(flags & (COMMS_CHAIN_UNFUSED | COMMS_CHAIN_FREQ_DOMAIN)) &&
+                         comms_fir_decim_any_supported(fir, r32) && ((flags & COMMS_CHAIN_TIME_DOMAIN) || rate >= any_from);
+    if (can_any) {
+        // mixer in front: sum_k h[k] x[n-k] e^{i phi(n-k)} = e^{i phi(n)} sum_k (h[k] e^{-i k dphi}) x[n-k] -- the kernel
+        // filters the RAW samples with modulated (complex) taps and mixes the kept outputs (the roundings fall
+        // elsewhere than in the reference's order, inside the parity tolerance: test_chain_any_rate)
+        p.kind = ChainKind::DecimAny;
+        p.taps_modulated = !after;
+        p.fm_separate = poly_sep;
+        p.mode = COMMS_CHAIN_POST | COMMS_CHAIN_DEC | (fm && !poly_sep ? COMMS_CHAIN_FM : 0);
+        return p;
+    }
+    if (can_fuse || can_decim || can_hybrid) {
+        p.kind = can_decim ? ChainKind::Decim : ChainKind::Os1024;
+        p.fm_separate = (!can_decim && !can_fuse) || (can_decim && poly_sep);
+        p.mode = (after ? COMMS_CHAIN_POST : COMMS_CHAIN_PRE) | COMMS_CHAIN_DEC | (fm && !p.fm_separate ? COMMS_CHAIN_FM : 0);
+        return p;
+    }
+    // 258 ... 1537 taps at the rates the polyphase kernel does not run: the 4096-point overlap-save kernel keeps, mixes and stores
+    // every rate-th output itself (one launch instead of FIR + mixer-decimator; 383 taps at rate 5, 2^24 samples: 96 -> ~60 us);
+    // FM demod follows as its own launch over the kept samples
+    const uint32_t rate32 = static_cast<uint32_t>(rate < (1u << 21) ? rate : 0);
+    const bool os_ok = !(flags & (COMMS_CHAIN_UNFUSED | COMMS_CHAIN_TIME_DOMAIN));
+    const bool os_dec16 = os_ok && comms_fir_os16k_decim_supported(fir, rate32) != 0;  // (1538 ... 4097 taps: the 16384-point kernel)
+    const bool os_dec = os_dec16 || (os_ok && comms_fir_os4096_decim_supported(fir, rate32) != 0);
+    // Mixer in front of a long filter: sum_k h[k] x[n-k] e^{i phi_(n-k)} = e^{i phi_n} sum_k (h[k] e^{-i k dphi}) x[n-k],
+    // so the chain runs as FIR (modulated taps, raw samples) -> mixer + decimator in one pass over the kept
+    // samples, instead of a full-rate mixer pass in front of the FIR (511 taps / 16 at 2^24: 135 -> 95 us).  The
+    // roundings fall elsewhere than in the reference's order (inside the parity tolerance); COMMS_CHAIN_UNFUSED
+    // keeps the literal four nodes.
+    p.taps_modulated = !after && !(flags & COMMS_CHAIN_UNFUSED);
+    p.fm_separate = fm;
+    if (os_dec) {
+        p.kind = os_dec16 ? ChainKind::Os16kDec : ChainKind::Os4096Dec;
+        p.mode = COMMS_CHAIN_POST | COMMS_CHAIN_DEC;
+    } else {
+        p.kind = after || p.taps_modulated ? ChainKind::SeriesPost : ChainKind::Series;
+    }
+    return p;
+}
+
+// h[k] e^{-i k dphase}: the taps with the mixer in front folded in (plan_chain)
+static std::vector<comms_c32> modulated_taps(const comms_c32* taps, size_t n_taps, double dphase) {
+    std::vector<comms_c32> mod(n_taps);
+    for (size_t k = 0; k < n_taps; ++k) {
+        const double ang = -dphase * static_cast<double>(k);
+        const double cr = std::cos(ang), ci = std::sin(ang);
+        const double tr = taps[k].re, ti = taps[k].im;
+        mod[k].re = static_cast<float>(tr * cr - ti * ci);
+        mod[k].im = static_cast<float>(tr * ci + ti * cr);
+    }
+    return mod;
+}
+
+// two zeroed device buffers (a ping-pong state)
+static comms_status_t alloc_state_pair(float2* (&buf)[2], size_t bytes) {
+    for (float2*& b : buf) {
+        hipError_t e = hipMalloc(&b, bytes);
+        if (e == hipSuccess) e = zero_device(b, bytes);
+        if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "chain state alloc: %s", hipGetErrorString(e));
+    }
+    return COMMS_OK;
+}
+
 extern "C" {
 
 comms_status_t comms_chain_create_ex(double dphase, double phase, const comms_c32* taps, size_t n_taps,
@@ -113,173 +256,34 @@ comms_status_t comms_chain_create_ex(double dphase, double phase, const comms_c3
     h->rate = rate;
     h->dphase = mix_wrap_dphase(dphase);
     h->fm_demod = (flags & COMMS_CHAIN_FM_DEMOD) != 0;
-    h->mixer_after = (flags & COMMS_CHAIN_MIXER_AFTER_FIR) != 0;
-    st = comms_fir_create(taps, n_taps, nullptr, 0, device, &h->fir);
-    const bool can_fuse_nofm = !(flags & COMMS_CHAIN_UNFUSED) && n_taps <= 257 && rate <= (1u << 20);
-    // FM chains on the overlap-save path: mixer / FIR / decimate as the one fused launch, the demodulator as its
-    // own kernel over the n / rate decimated samples.  That beats demodulating inside the overlap-save kernel at
-    // every rate (2^24 samples, 127 taps: /2 85.8 against 95.9 us, /3 68 against 83, /8 60 against 82 -- the fused
-    // form needs `rate` more halo samples per segment and an atan2 per output in a kernel short of issue slots) and
-    // has no limit on taps + rate; COMMS_CHAIN_FM_SEPARATE=0 brings the in-kernel form back for comparison.
-    static const int fm_sep = diag_knob("COMMS_CHAIN_FM_SEPARATE", 1);
-    const bool can_fuse = can_fuse_nofm && (!h->fm_demod || (!fm_sep && rate <= 64 && n_taps + rate <= 257));
-    const bool can_hybrid = h->fm_demod && can_fuse_nofm && !can_fuse;
-    // the time-domain kernel against what would run otherwise: an overlap-save fusion, or the four kernels in
-    // series, which it beats up to many more MACs per input sample
-    const int decim_ok = st == COMMS_OK && rate <= 16
-                             ? comms_fir_decim_supported_for(h->fir, static_cast<uint32_t>(rate), h->fm_demod ? 1 : 0,
-                                                             can_fuse || can_hybrid ? 1 : 0)
-                             : 0;
-    // (rate 4 with a long filter: too many MACs for the time-domain kernel, but its chain kind is the one that reaches the polyphase
-    // frequency-domain kernel, which takes every call from 64 taps -- fir_poly8.hip)
-    const bool poly_pref = decim_ok >= 1 && !(flags & COMMS_CHAIN_TIME_DOMAIN) &&
-                           comms_fir_poly8_supported(h->fir, static_cast<uint32_t>(rate), COMMS_CHAIN_DEC | (h->fm_demod ? COMMS_CHAIN_FM : 0),
-                                                     static_cast<size_t>(1) << 26) == 2;
-    // FM chains where that kernel runs without its demodulator (rates 12 ... 64; rate 4 beyond 249 taps): mixer / FIR / decimate on
-    // it and the demodulator as its own small launch over the n / rate kept samples, where the kernel takes EVERY call of this
-    // filter (asked with the shortest batch) -- rate 4, 255 taps, 2^24 samples: ~50 us against 70 for the overlap-save launch +
-    // demodulator (up to 249 taps the demodulator runs in the kernel: poly_pref above)
-    const bool poly_sep = h->fm_demod && st == COMMS_OK && rate != 8 && !poly_pref && !(flags & (COMMS_CHAIN_TIME_DOMAIN | COMMS_CHAIN_FREQ_DOMAIN | COMMS_CHAIN_UNFUSED)) &&
-                          comms_fir_poly8_supported(h->fir, static_cast<uint32_t>(rate), COMMS_CHAIN_DEC, rate) == 2;
-    const bool can_decim = !(flags & (COMMS_CHAIN_UNFUSED | COMMS_CHAIN_FREQ_DOMAIN)) &&
-                           (decim_ok == 2 || poly_pref || (poly_sep && decim_ok >= 1) || (decim_ok == 1 && (flags & COMMS_CHAIN_TIME_DOMAIN)));
-    // Rates the per-rate kernel is not built for (17 and up; 11 / 13 / 15 with complex taps): the any-rate kernel (half
-    // a wave per output).  Against the overlap-save launch it replaces (58-61 us at 2^24 samples whatever the rate): 255
-    // taps 60 us at rate 17, 53 at 20, 39 at 32, 30 at 100, 11 at 1000; 127 taps 49 at 17; 63 taps 45 at 17
-    // (profiles/r03_bench_chain_rates.txt) -- so from rate 17; taps up to 512, where the alternative is four kernels in
-    // series.  COMMS_CHAIN_TIME_DOMAIN forces it wherever it can run.
-    static const int any_min_rate = diag_knob("COMMS_ANY_MIN_RATE", 17);
-    const size_t any_from = static_cast<size_t>(any_min_rate);
-    const bool can_any = st == COMMS_OK && !can_decim && !(flags & (COMMS_CHAIN_UNFUSED | COMMS_CHAIN_FREQ_DOMAIN)) &&
-                         comms_fir_decim_any_supported(h->fir, static_cast<uint32_t>(rate)) &&
-                         ((flags & COMMS_CHAIN_TIME_DOMAIN) || rate >= any_from);
-    const int32_t poly_mode = (h->mixer_after ? COMMS_CHAIN_POST : COMMS_CHAIN_PRE) | COMMS_CHAIN_DEC | (h->fm_demod ? COMMS_CHAIN_FM : 0);
-    const bool force_poly8 = st == COMMS_OK && (flags & COMMS_CHAIN_POLYPHASE) && !(flags & COMMS_CHAIN_UNFUSED) &&
-                             comms_fir_poly8_supported(h->fir, static_cast<uint32_t>(rate), poly_mode, static_cast<size_t>(1) << 26) != 0;
-    // Filters too long for the other fusions (258 ... 513 taps; until round 5 these chains ran as overlap-save FIR + mixer-decimator
-    // [+ demodulator]: 80 us at 2^24 samples and rate 8): the polyphase kernel with five to eight halo rows, where it takes every
-    // call of the filter (asked with the shortest batch); the demodulator in the kernel where it has one (rates 8 and 4, 505
-    // taps), as its own launch over the kept samples otherwise.
-    bool poly_long = false, poly_long_fm = false;
-    if (st == COMMS_OK && n_taps > 257 && !force_poly8 &&
-        !(flags & (COMMS_CHAIN_UNFUSED | COMMS_CHAIN_TIME_DOMAIN | COMMS_CHAIN_FREQ_DOMAIN))) {
-        poly_long_fm = h->fm_demod && comms_fir_poly8_supported(h->fir, static_cast<uint32_t>(rate), poly_mode, rate) == 2;
-        poly_long = poly_long_fm || comms_fir_poly8_supported(h->fir, static_cast<uint32_t>(rate), poly_mode & ~COMMS_CHAIN_FM, rate) == 2;
-    }
-    if (force_poly8 || poly_long) {
-        h->fused = true;
-        h->poly8 = true;
-        h->mode = poly_long && !poly_long_fm ? (poly_mode & ~COMMS_CHAIN_FM) : poly_mode;
-        h->fm_separate = poly_long && h->fm_demod && !poly_long_fm;
-        if (h->fm_separate) st = comms_fmdemod_create(device, &h->fm);
-        h->frac = mix_to_turns(mix_wrap_dphase(dphase));
-        h->turns = mix_to_turns(phase);
-        for (int i = 0; i < 2 && st == COMMS_OK; ++i) {
-            hipError_t e = hipMalloc(&h->d_prev[i], sizeof(float2));
-            if (e == hipSuccess) e = zero_device(h->d_prev[i], sizeof(float2));
-            if (e != hipSuccess) st = fail(COMMS_ERR_DEVICE, "chain state alloc: %s", hipGetErrorString(e));
-        }
-        if (st != COMMS_OK) {
-            free_chain(h);
-            return st;
-        }
-        *out = h;
-        return COMMS_OK;
-    }
-    if (can_any && !h->mixer_after) {
-        // mixer in front: sum_k h[k] x[n-k] e^{i phi(n-k)} = e^{i phi(n)} sum_k (h[k] e^{-i k dphi}) x[n-k] -- the kernel
-        // filters the RAW samples with modulated (complex) taps and mixes the kept outputs (the roundings fall
-        // elsewhere than in the reference's order, inside the parity tolerance: test_chain_any_rate)
-        std::vector<comms_c32> mod(n_taps);
-        for (size_t k = 0; k < n_taps; ++k) {
-            const double ang = -h->dphase * static_cast<double>(k);
-            const double cr = std::cos(ang), ci = std::sin(ang);
-            const double tr = taps[k].re, ti = taps[k].im;
-            mod[k].re = static_cast<float>(tr * cr - ti * ci);
-            mod[k].im = static_cast<float>(tr * ci + ti * cr);
-        }
-        comms_fir_destroy(h->fir);
-        h->fir = nullptr;
-        st = comms_fir_create(mod.data(), n_taps, nullptr, 0, device, &h->fir);
-    }
-    if (st == COMMS_OK && can_any) {
-        h->fused = true;
-        h->decim_any = true;
-        h->fm_separate = poly_sep;
-        h->mode = COMMS_CHAIN_POST | COMMS_CHAIN_DEC | (h->fm_demod && !poly_sep ? COMMS_CHAIN_FM : 0);
-        if (h->fm_separate) st = comms_fmdemod_create(device, &h->fm);
-        h->frac = mix_to_turns(mix_wrap_dphase(dphase));
-        h->turns = mix_to_turns(phase);
-        for (int i = 0; i < 2 && st == COMMS_OK; ++i) {
-            hipError_t e = hipMalloc(&h->d_prev[i], sizeof(float2));
-            if (e == hipSuccess) e = zero_device(h->d_prev[i], sizeof(float2));
-            if (e != hipSuccess) st = fail(COMMS_ERR_DEVICE, "chain state alloc: %s", hipGetErrorString(e));
-        }
-    } else if (st == COMMS_OK && (can_fuse || can_decim || can_hybrid)) {
-        h->fused = true;
-        h->decim = can_decim;
-        h->fm_separate = (!can_decim && !can_fuse) || (can_decim && poly_sep);
-        h->mode = (h->mixer_after ? COMMS_CHAIN_POST : COMMS_CHAIN_PRE) | COMMS_CHAIN_DEC |
-                  (h->fm_demod && !h->fm_separate ? COMMS_CHAIN_FM : 0);
-        if (h->fm_separate) st = comms_fmdemod_create(device, &h->fm);
-        h->frac = mix_to_turns(mix_wrap_dphase(dphase));
-        h->turns = mix_to_turns(phase);
-        for (int i = 0; i < 2 && st == COMMS_OK; ++i) {
-            hipError_t e = hipMalloc(&h->d_prev[i], sizeof(float2));
-            if (e == hipSuccess) e = zero_device(h->d_prev[i], sizeof(float2));
-            if (e != hipSuccess) st = fail(COMMS_ERR_DEVICE, "chain state alloc: %s", hipGetErrorString(e));
-        }
-    } else if (st == COMMS_OK) {
-        // 258 ... 1537 taps at the rates the polyphase kernel does not run: the 4096-point overlap-save kernel keeps, mixes and stores
-        // every rate-th output itself (one launch instead of FIR + mixer-decimator; 383 taps at rate 5, 2^24 samples: 96 -> ~60 us);
-        // FM demod follows as its own launch over the kept samples
-        const uint32_t rate32 = static_cast<uint32_t>(rate < (1u << 21) ? rate : 0);
-        const bool os_ok = !(flags & (COMMS_CHAIN_UNFUSED | COMMS_CHAIN_TIME_DOMAIN));
-        const bool os_dec16 = os_ok && comms_fir_os16k_decim_supported(h->fir, rate32) != 0;  // (1538 ... 4097 taps: the 16384-point kernel)
-        const bool os_dec = os_dec16 || (os_ok && comms_fir_os4096_decim_supported(h->fir, rate32) != 0);
-        if (!h->mixer_after && !(flags & COMMS_CHAIN_UNFUSED)) {
-            // Mixer in front of a long filter: sum_k h[k] x[n-k] e^{i phi_(n-k)} = e^{i phi_n} sum_k (h[k] e^{-i k dphi}) x[n-k],
-            // so the chain runs as FIR (modulated taps, raw samples) -> mixer + decimator in one pass over the kept
-            // samples, instead of a full-rate mixer pass in front of the FIR (511 taps / 16 at 2^24: 135 -> 95 us).  The
-            // roundings fall elsewhere than in the reference's order (inside the parity tolerance); COMMS_CHAIN_UNFUSED
-            // keeps the literal four nodes.
-            std::vector<comms_c32> mod(n_taps);
-            for (size_t k = 0; k < n_taps; ++k) {
-                const double ang = -h->dphase * static_cast<double>(k);
-                const double cr = std::cos(ang), ci = std::sin(ang);
-                const double tr = taps[k].re, ti = taps[k].im;
-                mod[k].re = static_cast<float>(tr * cr - ti * ci);
-                mod[k].im = static_cast<float>(tr * ci + ti * cr);
-            }
+    h->time_domain = (flags & COMMS_CHAIN_TIME_DOMAIN) != 0;
+    st = [&]() -> comms_status_t {
+        COMMS_TRY(comms_fir_create(taps, n_taps, nullptr, 0, device, &h->fir));
+        const ChainPlan p = plan_chain(h->fir, rate, flags);
+        h->kind = p.kind;
+        h->fm_separate = p.fm_separate;
+        h->mode = p.mode;
+        if (p.taps_modulated) {
+            const std::vector<comms_c32> mod = modulated_taps(taps, n_taps, h->dphase);
             comms_fir_destroy(h->fir);
             h->fir = nullptr;
-            st = comms_fir_create(mod.data(), n_taps, nullptr, 0, device, &h->fir);
-            h->pre_as_post = st == COMMS_OK;
+            COMMS_TRY(comms_fir_create(mod.data(), n_taps, nullptr, 0, device, &h->fir));
         }
-        if (st == COMMS_OK && os_dec) {
-            h->fused = true;
-            h->os_dec = !os_dec16;
-            h->os_dec16 = os_dec16;
-            h->fm_separate = h->fm_demod;
-            h->mode = COMMS_CHAIN_POST | COMMS_CHAIN_DEC;
-            h->frac = mix_to_turns(mix_wrap_dphase(dphase));
+        if (is_fused(p.kind)) {
+            h->frac = mix_to_turns(h->dphase);
             h->turns = mix_to_turns(phase);
-        } else if (st == COMMS_OK) {
-            st = comms_mixer_create(dphase, phase, device, &h->mixer);
+        } else {
+            COMMS_TRY(comms_mixer_create(dphase, phase, device, &h->mixer));
         }
-        if (st == COMMS_OK && h->fm_demod) st = comms_fmdemod_create(device, &h->fm);
-        for (int i = 0; i < 2 && st == COMMS_OK && !h->mixer_after && !h->pre_as_post && !h->os_dec && !h->os_dec16; ++i) {
-            const size_t bytes = static_cast<size_t>(h->fir->n_eff) * sizeof(float2);
-            hipError_t e = hipMalloc(&h->raw_hist[i], bytes);
-            if (e == hipSuccess) e = zero_device(h->raw_hist[i], bytes);
-            if (e != hipSuccess) st = fail(COMMS_ERR_DEVICE, "chain state alloc: %s", hipGetErrorString(e));
-        }
-    }
+        if (p.fm_separate) COMMS_TRY(comms_fmdemod_create(device, &h->fm));
+        if (has_fm_prev(p.kind)) COMMS_TRY(alloc_state_pair(h->d_prev, sizeof(float2)));
+        if (has_raw_history(p.kind)) COMMS_TRY(alloc_state_pair(h->raw_hist, static_cast<size_t>(h->fir->n_eff) * sizeof(float2)));
+        return COMMS_OK;
+    }();
     if (st != COMMS_OK) {
         free_chain(h);
         return st;
     }
-    if (h->fir) h->fir->no_poly8 = (flags & COMMS_CHAIN_TIME_DOMAIN) != 0;
     *out = h;
     return COMMS_OK;
 }
@@ -292,7 +296,14 @@ comms_status_t comms_chain_create(double dphase, double phase, const comms_c32* 
 
 comms_status_t comms_chain_is_fused(const comms_chain_t* h, int32_t* out_fused) {
     COMMS_ARG(h && out_fused, "NULL argument");
-    *out_fused = h->fused ? (h->poly8 || ((h->decim || h->decim_any) && h->fir && h->fir->last_poly8) ? 4 : h->decim_any ? 3 : h->decim ? 2 : 1) : 0;
+    switch (h->kind) {
+        case ChainKind::Series:
+        case ChainKind::SeriesPost: *out_fused = 0; break;
+        case ChainKind::Decim: *out_fused = h->ran_poly8 ? 4 : 2; break;
+        case ChainKind::DecimAny: *out_fused = h->ran_poly8 ? 4 : 3; break;
+        case ChainKind::Poly8: *out_fused = 4; break;
+        default: *out_fused = 1; break;  // the overlap-save kernels
+    }
     return COMMS_OK;
 }
 
@@ -304,7 +315,7 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
     COMMS_ARG(n % h->rate == 0, "n (%zu) must be a multiple of the decimation rate %zu", n, h->rate);
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
-    const size_t in_elem = h->in_fmt == COMMS_IQ_I16 ? 4 : h->in_fmt == COMMS_IQ_U8 ? 2 : 8;
+    const size_t in_elem = in_elem_bytes(h->in_fmt);
     COMMS_ARG(!ranges_overlap(d_in, n * in_elem, d_out,
                               (n / h->rate) * (h->fm_demod ? sizeof(float) : sizeof(comms_c32))),
               "the chain cannot run in place");
@@ -312,9 +323,8 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
     hipStream_t hs = nullptr;
     COMMS_TRY(h->enter(stream, &hs));  // the stages' state (history, prev) advances in stream order
     void* s = static_cast<void*>(hs);
-    if (h->in_fmt != COMMS_IQ_C32 && !(h->fused && (h->decim || h->decim_any || h->poly8 || h->os_dec))) {
-        // only the time-domain kernel reads wire formats in its load stage; everything else gets one
-        // conversion pass first (same arithmetic, iqformat.hip)
+    if (h->in_fmt != COMMS_IQ_C32 && !reads_wire_format(h->kind)) {
+        // the kernels of the other kinds read Complex<f32>: one conversion pass first (same arithmetic, iqformat.hip)
         COMMS_TRY(h->t0.reserve(n * sizeof(comms_c32)));
         comms_c32* c = static_cast<comms_c32*>(h->t0.p);
         if (h->in_fmt == COMMS_IQ_I16)
@@ -324,27 +334,42 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
         d_in = c;
     }
     const size_t n_dec = n / h->rate;
-    if (h->fused) {
+    const uint32_t rate = static_cast<uint32_t>(h->rate);
+    if (is_fused(h->kind)) {
         void* stage_out = d_out;
         if (h->fm_separate) {  // decimated filter output to scratch, the demodulator reads it
             COMMS_TRY(h->t3.reserve(n_dec * sizeof(comms_c32)));
             stage_out = h->t3.p;
         }
-        if (h->os_dec)
-            COMMS_TRY(comms_fir_run_os4096_decim_dev(h->fir, d_in, n, stage_out, h->turns, h->frac, static_cast<uint32_t>(h->rate), s));
-        else if (h->os_dec16)
-            COMMS_TRY(comms_fir_run_os16k_decim_dev(h->fir, d_in, n, stage_out, h->turns, h->frac, static_cast<uint32_t>(h->rate), s));
-        else if (h->poly8)
-            COMMS_TRY(comms_fir_run_poly8_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, static_cast<uint32_t>(h->rate), h->d_prev[h->cur], h->d_prev[h->cur ^ 1], s));
-        else if (h->decim_any)
-            COMMS_TRY(comms_fir_run_decim_any_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, static_cast<uint32_t>(h->rate),
-                                                  h->d_prev[h->cur], h->d_prev[h->cur ^ 1], s));
-        else if (h->decim)
-            COMMS_TRY(comms_fir_run_decim_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, static_cast<uint32_t>(h->rate),
-                                              h->d_prev[h->cur], h->d_prev[h->cur ^ 1], s));
-        else
-            COMMS_TRY(comms_fir_run_fused_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, static_cast<uint32_t>(h->rate),
-                                              h->d_prev[h->cur], h->d_prev[h->cur ^ 1], s));
+        float2* prev = h->d_prev[h->cur];
+        float2* prev_new = h->d_prev[h->cur ^ 1];
+        switch (h->kind) {
+            case ChainKind::Os4096Dec:
+                COMMS_TRY(comms_fir_run_os4096_decim_dev(h->fir, d_in, n, stage_out, h->turns, h->frac, rate, s));
+                break;
+            case ChainKind::Os16kDec:
+                COMMS_TRY(comms_fir_run_os16k_decim_dev(h->fir, d_in, n, stage_out, h->turns, h->frac, rate, s));
+                break;
+            case ChainKind::Decim:
+            case ChainKind::DecimAny:
+                // long filters on long batches: the polyphase frequency-domain kernel, where it is the faster form (fir_poly8.hip)
+                if (h->time_domain || comms_fir_poly8_supported(h->fir, rate, h->mode, n) != 2) {
+                    h->ran_poly8 = false;
+                    if (h->kind == ChainKind::Decim)
+                        COMMS_TRY(comms_fir_run_decim_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
+                    else
+                        COMMS_TRY(comms_fir_run_decim_any_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
+                    break;
+                }
+                [[fallthrough]];
+            case ChainKind::Poly8:
+                COMMS_TRY(comms_fir_run_poly8_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
+                h->ran_poly8 = true;
+                break;
+            default:
+                COMMS_TRY(comms_fir_run_fused_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
+                break;
+        }
         h->turns += static_cast<uint64_t>(n) * h->frac;
         if (h->fm_separate)
             return comms_fmdemod_run_dev(h->fm, static_cast<const comms_c32*>(stage_out), n_dec, static_cast<float*>(d_out), s);
@@ -353,20 +378,17 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
     }
     COMMS_TRY(h->t1.reserve(n * sizeof(comms_c32)));
     comms_c32* a = static_cast<comms_c32*>(h->t1.p);
-    if (h->mixer_after || h->pre_as_post) {  // FIR, then mixer + decimate in one pass over the kept samples only
-        COMMS_TRY(comms_fir_run_dev(h->fir, d_in, n, a, s));
-        comms_c32* dst = static_cast<comms_c32*>(d_out);
-        if (h->fm_demod) {
-            COMMS_TRY(h->t3.reserve(n_dec * sizeof(comms_c32)));
-            dst = static_cast<comms_c32*>(h->t3.p);
-        }
-        COMMS_TRY(comms_mixer_run_decim_dev(h->mixer, a, n, h->rate, dst, s));
-        if (!h->fm_demod) return COMMS_OK;
-        return comms_fmdemod_run_dev(h->fm, dst, n_dec, static_cast<float*>(d_out), s);
+    comms_c32* dec = static_cast<comms_c32*>(d_out);  // the decimated samples: the output, or the demodulator's input
+    if (h->fm_demod) {
+        COMMS_TRY(h->t3.reserve(n_dec * sizeof(comms_c32)));
+        dec = static_cast<comms_c32*>(h->t3.p);
     }
-    COMMS_TRY(h->t2.reserve(n * sizeof(comms_c32)));
-    comms_c32* b = static_cast<comms_c32*>(h->t2.p);
-    {
+    if (h->kind == ChainKind::SeriesPost) {  // FIR, then mixer + decimate in one pass over the kept samples only
+        COMMS_TRY(comms_fir_run_dev(h->fir, d_in, n, a, s));
+        COMMS_TRY(comms_mixer_run_decim_dev(h->mixer, a, n, h->rate, dec, s));
+    } else {
+        COMMS_TRY(h->t2.reserve(n * sizeof(comms_c32)));
+        comms_c32* b = static_cast<comms_c32*>(h->t2.p);
         COMMS_TRY(chain_flush_raw_state(h));
         COMMS_TRY(comms_mixer_run_dev(h->mixer, d_in, n, a, s));
         COMMS_TRY(comms_fir_run_dev(h->fir, a, n, b, s));
@@ -374,13 +396,10 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
                                                              h->raw_hist[h->raw_cur ^ 1], h->fir->n_eff);
         COMMS_TRY(launch_ok("chain_raw_hist_kernel"));
         h->raw_cur ^= 1;
+        COMMS_TRY(comms_decimate_run_dev(b, n, sizeof(comms_c32), h->rate, dec, nullptr, h->device, s));
     }
-    if (!h->fm_demod)
-        return comms_decimate_run_dev(b, n, sizeof(comms_c32), h->rate, d_out, nullptr, h->device, s);
-    COMMS_TRY(h->t3.reserve(n_dec * sizeof(comms_c32)));
-    comms_c32* c = static_cast<comms_c32*>(h->t3.p);
-    COMMS_TRY(comms_decimate_run_dev(b, n, sizeof(comms_c32), h->rate, c, nullptr, h->device, s));
-    return comms_fmdemod_run_dev(h->fm, c, n_dec, static_cast<float*>(d_out), s);
+    if (!h->fm_demod) return COMMS_OK;
+    return comms_fmdemod_run_dev(h->fm, dec, n_dec, static_cast<float*>(d_out), s);
 }
 
 comms_status_t comms_chain_run(comms_chain_t* h, const comms_c32* in, size_t n, void* out) {
@@ -390,7 +409,7 @@ comms_status_t comms_chain_run(comms_chain_t* h, const comms_c32* in, size_t n, 
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
     const size_t out_bytes = (n / h->rate) * (h->fm_demod ? sizeof(float) : sizeof(comms_c32));
-    const size_t in_elem = h->in_fmt == COMMS_IQ_I16 ? 4 : h->in_fmt == COMMS_IQ_U8 ? 2 : 8;
+    const size_t in_elem = in_elem_bytes(h->in_fmt);
     // (chunks of whole groups of `rate` samples: DecimateNode restarts its index with every batch, src/util/resample_node.rs:53-65,
     // and a chunk that starts on a multiple of the rate keeps the batch's indexing)
     const size_t out_elem = h->fm_demod ? sizeof(float) : sizeof(comms_c32);
@@ -410,7 +429,7 @@ comms_status_t comms_chain_set_input_format(comms_chain_t* h, int32_t format, fl
     COMMS_ARG(format != COMMS_IQ_I16 || std::isfinite(scale), "scale must be finite");
     h->in_fmt = format;
     h->in_scale = format == COMMS_IQ_I16 ? scale : 1.0f;
-    if (h->fused && (h->decim || h->decim_any || h->poly8 || h->os_dec)) COMMS_TRY(comms_fir_set_input_format(h->fir, format, scale));
+    if (reads_wire_format(h->kind)) COMMS_TRY(comms_fir_set_input_format(h->fir, format, scale));
     return COMMS_OK;
 }
 
@@ -424,7 +443,7 @@ comms_status_t comms_chain_set_fir_state(comms_chain_t* h, const comms_c32* stat
     COMMS_ARG(state || !n_state, "state is NULL");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    if (h->fused || h->mixer_after || h->pre_as_post) return comms_fir_set_state(h->fir, state, n_state);
+    if (!has_raw_history(h->kind)) return comms_fir_set_state(h->fir, state, n_state);
     COMMS_ARG(n_state == static_cast<size_t>(h->fir->n_eff), "state must hold exactly the %d effective taps", h->fir->n_eff);
     {
         std::vector<float2> ring(n_state);
@@ -439,7 +458,7 @@ comms_status_t comms_chain_get_fir_state(comms_chain_t* h, comms_c32* state, siz
     COMMS_ARG(h && state, "NULL argument");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    if (h->fused || h->mixer_after || h->pre_as_post) return comms_fir_get_state(h->fir, state, n_state);
+    if (!has_raw_history(h->kind)) return comms_fir_get_state(h->fir, state, n_state);
     const size_t N = static_cast<size_t>(h->fir->n_eff);
     COMMS_ARG(n_state <= N, "n_state %zu exceeds the %zu effective taps", n_state, N);
     std::vector<float2> ring(N);
@@ -454,7 +473,7 @@ comms_status_t comms_chain_get_fir_state(comms_chain_t* h, comms_c32* state, siz
 // Oscillator phase of the next input sample (radians, as comms_mixer_get_phase).
 comms_status_t comms_chain_get_phase(comms_chain_t* h, double* out_phase) {
     COMMS_ARG(h && out_phase, "NULL argument");
-    if (!h->fused) return comms_mixer_get_phase(h->mixer, out_phase);
+    if (!is_fused(h->kind)) return comms_mixer_get_phase(h->mixer, out_phase);
     *out_phase = static_cast<double>(h->turns >> 11) * (kMixT * 0x1.0p-53);
     return COMMS_OK;
 }
@@ -462,7 +481,7 @@ comms_status_t comms_chain_get_phase(comms_chain_t* h, double* out_phase) {
 comms_status_t comms_chain_set_phase(comms_chain_t* h, double phase) {
     COMMS_ARG(h != nullptr, "handle is NULL");
     COMMS_ARG(std::isfinite(phase), "phase must be finite");
-    if (!h->fused) return comms_mixer_set_phase(h->mixer, phase);
+    if (!is_fused(h->kind)) return comms_mixer_set_phase(h->mixer, phase);
     h->turns = mix_to_turns(phase);
     return COMMS_OK;
 }
@@ -472,7 +491,7 @@ comms_status_t comms_chain_set_phase(comms_chain_t* h, double phase) {
 comms_status_t comms_chain_get_fm_prev(comms_chain_t* h, comms_c32* out_prev) {
     COMMS_ARG(h && out_prev, "NULL argument");
     COMMS_ARG(h->fm_demod, "this chain has no FM demodulator");
-    if (!h->fused || h->fm_separate) return comms_fmdemod_get_prev(h->fm, out_prev);
+    if (h->fm_separate) return comms_fmdemod_get_prev(h->fm, out_prev);
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
     COMMS_HIP_TRY(hipMemcpy(out_prev, h->d_prev[h->cur], sizeof(float2), hipMemcpyDeviceToHost));
@@ -482,7 +501,7 @@ comms_status_t comms_chain_get_fm_prev(comms_chain_t* h, comms_c32* out_prev) {
 comms_status_t comms_chain_set_fm_prev(comms_chain_t* h, const comms_c32* prev) {
     COMMS_ARG(h && prev, "NULL argument");
     COMMS_ARG(h->fm_demod, "this chain has no FM demodulator");
-    if (!h->fused || h->fm_separate) return comms_fmdemod_set_prev(h->fm, prev);
+    if (h->fm_separate) return comms_fmdemod_set_prev(h->fm, prev);
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
     COMMS_HIP_TRY(hipMemcpy(h->d_prev[h->cur], prev, sizeof(float2), hipMemcpyHostToDevice));

@@ -2091,7 +2091,7 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
     const void* d_in = d_in_any;  // n samples in the handle's input format
-    const size_t in_elem = h->in_fmt == COMMS_IQ_I16 ? 4 : h->in_fmt == COMMS_IQ_U8 ? 2 : 8;
+    const size_t in_elem = in_elem_bytes(h->in_fmt);
     COMMS_ARG(!ranges_overlap(d_in, n * in_elem, d_out, n * 8), "FIR cannot run in place");
     COMMS_ARG((reinterpret_cast<uintptr_t>(d_in) & (in_elem - 1)) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0,
               "device pointers must be aligned to one sample");
@@ -2114,12 +2114,7 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
         const int nrows = (DTILE + h->NP) / 8;
         const size_t lds = static_cast<size_t>(nrows) * DROW * sizeof(float2) + static_cast<size_t>(h->NP) * sizeof(float2);
         h->tic(s);
-        if (h->in_fmt == COMMS_IQ_I16)
-            launch_direct_in(h, InI16{static_cast<const short2*>(d_in), h->in_scale}, hist, o, n, nh, blocks, lds, s);
-        else if (h->in_fmt == COMMS_IQ_U8)
-            launch_direct_in(h, InU8{static_cast<const uchar2*>(d_in)}, hist, o, n, nh, blocks, lds, s);
-        else
-            launch_direct_in(h, in, hist, o, n, nh, blocks, lds, s);
+        with_input_view(h, d_in, in, [&](auto v) { launch_direct_in(h, v, hist, o, n, nh, blocks, lds, s); });
         h->toc(s);
         COMMS_TRY(launch_ok("fir_direct_kernel"));
     } else if (algo == COMMS_FIR_OS1024) {
@@ -2135,20 +2130,10 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
         else
             h->tic(s);
         const KStamp ks = pl.dyn ? h->next_stamp() : KStamp{nullptr, nullptr};
-        if (pl.dyn) {
-            if (h->in_fmt == COMMS_IQ_I16)
-                COMMS_TRY(launch_dyn_hr(pl.hr, s, InI16{static_cast<const short2*>(d_in), h->in_scale}, h, o, n, tb, nh, ea, eb, ks));
-            else if (h->in_fmt == COMMS_IQ_U8)
-                COMMS_TRY(launch_dyn_hr(pl.hr, s, InU8{static_cast<const uchar2*>(d_in)}, h, o, n, tb, nh, ea, eb, ks));
-            else
-                COMMS_TRY(launch_dyn_hr(pl.hr, s, in, h, o, n, tb, nh, ea, eb, ks));
-        } else if (h->in_fmt == COMMS_IQ_I16) {
-            COMMS_TRY(launch_fixed_hr(pl.hr, pl.wpb, runs, s, InI16{static_cast<const short2*>(d_in), h->in_scale}, hist, h->n_eff, o, n, nseg, tb, nh, ea, eb));
-        } else if (h->in_fmt == COMMS_IQ_U8) {
-            COMMS_TRY(launch_fixed_hr(pl.hr, pl.wpb, runs, s, InU8{static_cast<const uchar2*>(d_in)}, hist, h->n_eff, o, n, nseg, tb, nh, ea, eb));
-        } else {
-            COMMS_TRY(launch_fixed_hr(pl.hr, pl.wpb, runs, s, in, hist, h->n_eff, o, n, nseg, tb, nh, ea, eb));
-        }
+        COMMS_TRY(with_input_view(h, d_in, in, [&](auto v) {
+            return pl.dyn ? launch_dyn_hr(pl.hr, s, v, h, o, n, tb, nh, ea, eb, ks)
+                          : launch_fixed_hr(pl.hr, pl.wpb, runs, s, v, hist, h->n_eff, o, n, nseg, tb, nh, ea, eb);
+        }));
         if (!own_stamps) h->toc(s);
         COMMS_TRY(launch_ok("fir_os1024_kernel"));
     } else if (algo == COMMS_FIR_OS16K) {
@@ -2166,12 +2151,7 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
                        reinterpret_cast<const cf*>(h->d_xt[2]), reinterpret_cast<const cf*>(h->d_xt[3]),
                        reinterpret_cast<const cf*>(h->d_xh[pt])};
             const int dl = pt * X_PART, acc = pt ? 1 : 0;
-            if (h->in_fmt == COMMS_IQ_I16)
-                launch_os16k_hr(hr, blocks, lds, s, InI16{static_cast<const short2*>(d_in), h->in_scale}, hist, h->n_eff, o, n, nseg, tb, nh, dl, acc, ks, h->d_err);
-            else if (h->in_fmt == COMMS_IQ_U8)
-                launch_os16k_hr(hr, blocks, lds, s, InU8{static_cast<const uchar2*>(d_in)}, hist, h->n_eff, o, n, nseg, tb, nh, dl, acc, ks, h->d_err);
-            else
-                launch_os16k_hr(hr, blocks, lds, s, in, hist, h->n_eff, o, n, nseg, tb, nh, dl, acc, ks, h->d_err);
+            with_input_view(h, d_in, in, [&](auto v) { launch_os16k_hr(hr, blocks, lds, s, v, hist, h->n_eff, o, n, nseg, tb, nh, dl, acc, ks, h->d_err); });
         }
         h->toc(s);
         COMMS_TRY(launch_ok("fir_os16k_kernel"));
@@ -2200,15 +2180,10 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
                 fir_os4096_kernel<4><<<dim3(blocks), dim3(256), 0, s>>>(in, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
             else if (wps == 2)
                 fir_os4096_kernel<2><<<dim3(blocks), dim3(256), 0, s>>>(in, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
-            else if (h->in_fmt == COMMS_IQ_I16)
-                fir_os4096_kernel<3, InI16><<<dim3(blocks), dim3(256), 0, s>>>(InI16{static_cast<const short2*>(d_in), h->in_scale}, hist, h->n_eff, o, n,
-                                                                              h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
-            else if (h->in_fmt == COMMS_IQ_U8)
-                fir_os4096_kernel<3, InU8><<<dim3(blocks), dim3(256), 0, s>>>(InU8{static_cast<const uchar2*>(d_in)}, hist, h->n_eff, o, n, h->hblk, nseg,
-                                                                             tb, nh, dl, acc, il, OsDec{});
             else
-                fir_os4096_kernel<3, InC32Split><<<dim3(blocks), dim3(256), 0, s>>>(InC32Split{reinterpret_cast<const float*>(in)}, hist, h->n_eff, o, n,
-                                                                                   h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
+                with_input_view(h, d_in, InC32Split{reinterpret_cast<const float*>(in)}, [&](auto v) {
+                    fir_os4096_kernel<3, decltype(v)><<<dim3(blocks), dim3(256), 0, s>>>(v, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
+                });
         }
         h->toc(s);
         COMMS_TRY(launch_ok("fir_os4096_kernel"));
@@ -2222,7 +2197,7 @@ comms_status_t comms_fir_run(comms_fir_t* h, const comms_c32* in, size_t n, comm
     COMMS_ARG((in && out) || !n, "NULL host pointer");
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
-    const size_t in_elem = h->in_fmt == COMMS_IQ_I16 ? 4 : h->in_fmt == COMMS_IQ_U8 ? 2 : 8;
+    const size_t in_elem = in_elem_bytes(h->in_fmt);
     // (long batches go through the chunked host pipeline, common.hpp: the history streams across the chunks as across calls)
     COMMS_TRY(h->run_host_units(in, n * in_elem, in_elem, out, n * sizeof(comms_c32), sizeof(comms_c32), [&](void* d_in, void* d_out, size_t ib, size_t) {
         return comms_fir_run_dev(h, static_cast<const comms_c32*>(d_in), ib / in_elem, static_cast<comms_c32*>(d_out), COMMS_STREAM_HANDLE);
@@ -2412,7 +2387,6 @@ comms_status_t comms_fir_run_os16k_decim_dev(comms_fir_t* h, const comms_c32* d_
     h->toc(s);
     COMMS_TRY(launch_ok("fir_os16k_kernel (decimating)"));
     h->cur ^= 1;
-    h->last_poly8 = false;
     return COMMS_OK;
 }
 
@@ -2425,7 +2399,7 @@ comms_status_t comms_fir_run_os4096_decim_dev(comms_fir_t* h, const void* d_in, 
     COMMS_TRY(fir_check_sticky(h));
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
-    const size_t in_elem = h->in_fmt == COMMS_IQ_I16 ? 4 : h->in_fmt == COMMS_IQ_U8 ? 2 : 8;
+    const size_t in_elem = in_elem_bytes(h->in_fmt);
     COMMS_ARG(!ranges_overlap(d_in, n * in_elem, d_out, (n / rate) * 8), "the decimating chain cannot run in place");
     COMMS_ARG((reinterpret_cast<uintptr_t>(d_in) & (in_elem - 1)) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0,
               "device pointers must be aligned to one sample");
@@ -2455,19 +2429,12 @@ comms_status_t comms_fir_run_os4096_decim_dev(comms_fir_t* h, const void* d_in, 
     }
     OsTables tb{reinterpret_cast<const cf*>(h->d_tw1), reinterpret_cast<const cf*>(h->d_tw2), reinterpret_cast<const cf*>(h->d_hparts[0])};
     h->tic(s);
-    if (h->in_fmt == COMMS_IQ_I16)
-        fir_os4096_kernel<3, InI16, true><<<dim3(blocks), dim3(256), 0, s>>>(InI16{static_cast<const short2*>(d_in), h->in_scale}, hist, h->n_eff, o, n,
-                                                                            h->hblk, nseg, tb, nh, 0, 0, 1, dc);
-    else if (h->in_fmt == COMMS_IQ_U8)
-        fir_os4096_kernel<3, InU8, true><<<dim3(blocks), dim3(256), 0, s>>>(InU8{static_cast<const uchar2*>(d_in)}, hist, h->n_eff, o, n, h->hblk, nseg,
-                                                                           tb, nh, 0, 0, 1, dc);
-    else
-        fir_os4096_kernel<3, InC32Split, true><<<dim3(blocks), dim3(256), 0, s>>>(InC32Split{static_cast<const float*>(d_in)}, hist, h->n_eff, o, n,
-                                                                                 h->hblk, nseg, tb, nh, 0, 0, 1, dc);
+    with_input_view(h, d_in, InC32Split{static_cast<const float*>(d_in)}, [&](auto v) {
+        fir_os4096_kernel<3, decltype(v), true><<<dim3(blocks), dim3(256), 0, s>>>(v, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, 0, 0, 1, dc);
+    });
     h->toc(s);
     COMMS_TRY(launch_ok("fir_os4096_kernel (decimating)"));
     h->cur ^= 1;
-    h->last_poly8 = false;
     return COMMS_OK;
 }
 

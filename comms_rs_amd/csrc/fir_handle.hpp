@@ -200,8 +200,6 @@ struct comms_fir : comms::Handle {
     float2* d_p8 = nullptr;     // polyphase frequency-domain chain kernel (fir_poly8.hip): branch spectra + twiddle tables ...
     bool p8_pre = false;        //   ... built for this mixer order and (mixer first: folded into the taps) increment
     uint64_t p8_frac = 0;
-    bool no_poly8 = false;      // COMMS_CHAIN_TIME_DOMAIN: the time-domain kernel on every call
-    bool last_poly8 = false;    // the last decimating chain launch of this handle ran fir_poly8_kernel (comms_chain_is_fused)
     // direct form
     int NP = 0;          // taps padded to a multiple of 8
     float2* d_taps_pad = nullptr;
@@ -232,6 +230,18 @@ struct comms_fir : comms::Handle {
 };
 
 namespace comms {
+// Bytes of one IQ sample in a COMMS_IQ_* format
+inline size_t in_elem_bytes(int fmt) { return fmt == COMMS_IQ_I16 ? 4 : fmt == COMMS_IQ_U8 ? 2 : 8; }
+
+// f(view) with the device view of d_in that the handle's input format needs: InI16 / InU8 over the raw samples, or
+// `c32`, the Complex<f32> view the launch wants (a pointer, InC32Split, ...)
+template <class C32, class F>
+auto with_input_view(const comms_fir* h, const void* d_in, C32 c32, F&& f) {
+    if (h->in_fmt == COMMS_IQ_I16) return f(InI16{static_cast<const short2*>(d_in), h->in_scale});
+    if (h->in_fmt == COMMS_IQ_U8) return f(InU8{static_cast<const uchar2*>(d_in)});
+    return f(c32);
+}
+
 // A launch of the 16384-point kernel whose LDS waits ran out has raised the handle's error word (fir_os16k_kernel):
 // its outputs are wrong, and so is everything the handle would compute from the state it left.  Checked on entry to
 // every run / state entry of the handle (all of them, round 5) and, by the host-pointer entries, once more AFTER the

@@ -602,7 +602,7 @@ int32_t comms_fir_poly8_supported(const comms_fir_t* h, uint32_t rate, int32_t m
     if (!(mode & COMMS_CHAIN_DEC) || !poly8_halo_rows(h->n_eff, fm) || (fm && kind > 2)) return 0;  // (FM demod: rates 8 and 4)
     if (kind >= 3 && (n >> 2) > 0xFFFFFFFFull) return 0;  // (its output index arithmetic is 32 bits wide)
     static const int knob = diag_knob("COMMS_POLY8", 1);          // 0: never, 1: where it wins, 2: wherever it can run
-    if (!knob || h->no_poly8) return 0;
+    if (!knob) return 0;
     if (knob == 2) return 2;
     // Against the time-domain kernels (scripts/sweep_poly8.py, profiles/r05_sweep_poly8.txt: taps x batch length, with and
     // without FM demod): its time does not depend on the taps -- ahead from 64 taps at every batch length (255 taps: 47 -> 29 us
@@ -644,7 +644,7 @@ comms_status_t comms_fir_run_poly8_dev(comms_fir_t* h, const void* d_in, size_t 
     COMMS_TRY(fir_check_sticky(h));
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
-    const size_t in_elem = h->in_fmt == COMMS_IQ_I16 ? 4 : h->in_fmt == COMMS_IQ_U8 ? 2 : 8;
+    const size_t in_elem = in_elem_bytes(h->in_fmt);
     COMMS_ARG(!ranges_overlap(d_in, n * in_elem, d_out, (n / rate) * (fm ? 4 : 8)), "the decimating chain cannot run in place");
     COMMS_ARG((reinterpret_cast<uintptr_t>(d_in) & (in_elem - 1)) == 0, "input must be aligned to one IQ sample");
     hipStream_t s = nullptr;
@@ -672,16 +672,9 @@ comms_status_t comms_fir_run_poly8_dev(comms_fir_t* h, const void* d_in, size_t 
     }
     P8Fm fmx{static_cast<const float2*>(fm_prev), static_cast<float2*>(fm_prev_new)};
     const int nph = kind == 2 || kind == 4 ? 2 : 1;
-    comms_status_t st;
-    if (h->in_fmt == COMMS_IQ_I16)
-        st = poly8_launch_in(hr, fm, nph, h, s, InI16{static_cast<const short2*>(d_in), h->in_scale}, d_out, n, tb, mx, fmx);
-    else if (h->in_fmt == COMMS_IQ_U8)
-        st = poly8_launch_in(hr, fm, nph, h, s, InU8{static_cast<const uchar2*>(d_in)}, d_out, n, tb, mx, fmx);
-    else
-        st = poly8_launch_in(hr, fm, nph, h, s, static_cast<const float2*>(d_in), d_out, n, tb, mx, fmx);
-    COMMS_TRY(st);
+    COMMS_TRY(with_input_view(h, d_in, static_cast<const float2*>(d_in),
+                              [&](auto in) { return poly8_launch_in(hr, fm, nph, h, s, in, d_out, n, tb, mx, fmx); }));
     h->cur ^= 1;
-    h->last_poly8 = true;
     return COMMS_OK;
 }
 
