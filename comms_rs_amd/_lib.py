@@ -16,6 +16,8 @@ CSRC = os.path.join(_HERE, "csrc")
 COMMS_OK, COMMS_ERR_ARG, COMMS_ERR_DEVICE = 0, 1, 2
 FIR_AUTO, FIR_DIRECT, FIR_OVERLAP_SAVE, FIR_OS1024, FIR_OS4096, FIR_OS16K, FIR_OS1024_FIXED = 0, 1, 2, 3, 4, 5, 6
 IQ_C32, IQ_I16, IQ_U8 = 0, 1, 2
+SYM_C32, SYM_BITS = 0, 1        # comms_pulse_set_input_format
+BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 STREAM_HANDLE = C.c_void_p(-1).value  # COMMS_STREAM_HANDLE: the handle's own stream
 
 
@@ -110,6 +112,7 @@ _PROTOS = {
     "comms_pulse_set_mixer": [_vp, _f64, _f64],
     "comms_pulse_get_phase": [_vp, C.POINTER(_f64)],
     "comms_pulse_set_output_format": [_vp, _i32, C.c_float],
+    "comms_pulse_set_input_format": [_vp, _i32, _i32, _vp],
     "comms_pulse_destroy": [_vp],
     "comms_mixer_create": [_f64, _f64, _i32, _pp],
     "comms_mixer_run": [_vp, _vp, _sz, _vp],
@@ -169,6 +172,22 @@ _PROTOS = {
     "comms_iq_u8_to_c32_dev": [_vp, _sz, _vp, _i32, _vp],
     "comms_iq_real_to_c32_dev": [_vp, _sz, _vp, _i32, _vp],
     "comms_iq_c32_re_dev": [_vp, _sz, _vp, _i32, _vp],
+    "comms_bpsk_byte_mod": [_vp, _sz, _vp, _i32],
+    "comms_qpsk_byte_mod": [_vp, _sz, _vp, _i32],
+    "comms_bpsk_bit_mod": [_vp, _sz, _vp, _i32],
+    "comms_qpsk_bit_mod": [_vp, _sz, _vp, _i32],
+    "comms_bpsk_byte_mod_dev": [_vp, _sz, _vp, _i32, _vp],
+    "comms_qpsk_byte_mod_dev": [_vp, _sz, _vp, _i32, _vp],
+    "comms_bpsk_bit_mod_dev": [_vp, _sz, _vp, _i32, _vp],
+    "comms_qpsk_bit_mod_dev": [_vp, _sz, _vp, _i32, _vp],
+    "comms_prns_create": [_u64, _u64, _i32, _i32, _pp],
+    "comms_prns_run": [_vp, _sz, _i32, _vp],
+    "comms_prns_run_dev": [_vp, _sz, _i32, _vp, _vp],
+    "comms_prns_get_state": [_vp, C.POINTER(_u64)],
+    "comms_prns_set_state": [_vp, _u64],
+    "comms_prns_skip": [_vp, _u64],
+    "comms_prns_set_timer": [_vp, _vp],
+    "comms_prns_destroy": [_vp],
     "comms_frequency_offset_estimate": [_vp, _sz, C.POINTER(_f64), _i32],
     "comms_psk_phase_estimate": [_vp, _sz, _u32, C.POINTER(_f64), _i32],
     "comms_qam_phase_estimate": [_vp, _sz, C.POINTER(_f64), _i32],

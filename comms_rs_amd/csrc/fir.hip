@@ -1320,46 +1320,48 @@ __device__ __forceinline__ void pulse_rotor_at(uint64_t turns, double& c, double
     sincos(static_cast<double>(turns >> 11) * (kTwoPiF * 0x1.0p-53), &s, &c);
 }
 
+// Packed-bit symbols (comms_pulse_set_input_format, COMMS_SYM_BITS): symbol i = c[v], v = stream bits
+// K i ... K i + K - 1 (the first one the LSB; stream bit j = bit j%8 of byte j/8).  The constellation travels with
+// the view in the kernel arguments and is selected without indexing (no scratch); everything downstream of the
+// view -- history, window, taps, mixer, stores -- is the c32 path's, so the outputs are bit-identical to it.
+template <int K>
+struct InBits {
+    const uint8_t* p;
+    float2 c[1 << K];
+    __device__ __forceinline__ float2 operator[](size_t i) const {
+        const size_t b = i * K;
+        const unsigned v = (static_cast<unsigned>(p[b >> 3]) >> (b & 7)) & ((1u << K) - 1);
+        if constexpr (K == 1) {
+            return v ? c[1] : c[0];
+        } else {
+            const float2 lo = (v & 1u) ? c[1] : c[0], hi = (v & 1u) ? c[3] : c[2];
+            return (v & 2u) ? hi : lo;
+        }
+    }
+};
+
 __global__ __launch_bounds__(256) void pulse_kernel(const float2* __restrict__ sym,
                                                     const float2* __restrict__ hist, int hist_len,
                                                     const float2* __restrict__ taps, int n_taps,
                                                     int sps, float2* __restrict__ out,
                                                     size_t n_sym, float2* __restrict__ new_hist, PulseMix mx) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    hist_advance(hist, sym, n_sym, new_hist, hist_len);
-    float2* tp = reinterpret_cast<float2*>(smem);
-    for (int k = threadIdx.x; k < n_taps; k += 256) tp[k] = taps[k];
-    __syncthreads();
-    const size_t n_out = n_sym * static_cast<size_t>(sps);
-    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-    double rc = 1.0, rs = 0.0;
-    if (mx.on) pulse_rotor_at(mx.turns0 + (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) * mx.frac, rc, rs);
-    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n_out;
-         i += stride) {
-        const size_t m = i / sps;
-        const int p = static_cast<int>(i - m * sps);
-        float2 acc = make_float2(0.f, 0.f);
-        long long s = static_cast<long long>(m);
-        for (int k = p; k < n_taps; k += sps, --s) {
-            const float2 x = stream_at(sym, hist, hist_len, s, n_sym);
-            const float2 h = tp[k];
-            acc.x = __builtin_fmaf(h.x, x.x, acc.x);
-            acc.x = __builtin_fmaf(-h.y, x.y, acc.x);
-            acc.y = __builtin_fmaf(h.x, x.y, acc.y);
-            acc.y = __builtin_fmaf(h.y, x.x, acc.y);
-        }
-        if (mx.on) {  // Mixer::mix arithmetic: f64 product rounded once (src/mixer.rs:77-78)
-            const double yr = acc.x, yi = acc.y;
-            acc = make_float2(static_cast<float>(yr * rc - yi * rs), static_cast<float>(yr * rs + yi * rc));
-            const double nc = rc * mx.sweep_c - rs * mx.sweep_s;
-            rs = rc * mx.sweep_s + rs * mx.sweep_c;
-            rc = nc;
-        }
-        if (mx.out_i16)
-            reinterpret_cast<short2*>(out)[i] = c32_as_i16(acc, mx.out_scale);
-        else
-            out[i] = acc;
-    }
+#define PULSE_GENERIC_BODY
+#define PULSE_SYM sym
+#include "pulse_body.inc"
+#undef PULSE_SYM
+#undef PULSE_GENERIC_BODY
+}
+template <class In>
+__global__ __launch_bounds__(256) void pulse_in_kernel(const In sym,
+                                                       const float2* __restrict__ hist, int hist_len,
+                                                       const float2* __restrict__ taps, int n_taps,
+                                                       int sps, float2* __restrict__ out,
+                                                       size_t n_sym, float2* __restrict__ new_hist, PulseMix mx) {
+#define PULSE_GENERIC_BODY
+#define PULSE_SYM sym
+#include "pulse_body.inc"
+#undef PULSE_SYM
+#undef PULSE_GENERIC_BODY
 }
 
 // Polyphase pulse shaper for the usual sam_per_sym (2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 32):
@@ -1388,128 +1390,17 @@ struct PulseArgs {
 
 template <int SPS, bool REAL, bool MIX>
 __global__ __launch_bounds__(256) void pulse_poly_kernel(const PulseArgs a) {
-    constexpr int SPSP = SPS + (SPS & 1);
-    // outputs leave through a per-wave LDS block, CW phases at a time (CW * 2 KiB per workgroup)
-    constexpr int CW = SPS <= 8 ? SPS : SPS % 8 == 0 ? 8 : SPS % 6 == 0 ? 6 : SPS % 5 == 0 ? 5 : SPS % 4 == 0 ? 4 : SPS % 3 == 0 ? 3 : SPS % 2 == 0 ? 2 : 1;
-    __shared__ cf sh[256 + PP_JMAX];
-    __shared__ __attribute__((aligned(16))) cf xch[256 * CW];
-    const int tid = threadIdx.x;
-    const int halo = a.J - 1;
-    const size_t ntiles = (a.n_sym + 255) / 256;
-    kstamp_begin(a.ks);
-    hist_advance(a.hist, a.sym, a.n_sym, a.new_hist, a.hist_len);
-    double rc = 1.0, rs = 0.0;  // rotor of this lane's first output of the current tile
-    if (MIX) pulse_rotor_at(a.mx.turns0 + (static_cast<uint64_t>(blockIdx.x) * 256 + tid) * SPS * a.mx.frac, rc, rs);
-    // the next tile's symbols are requested before this tile's taps run and land in LDS at the top of the next step: a
-    // tile's own work is short, and without this every step began with an exposed round trip to HBM
-    cf nx0 = cf{0.f, 0.f}, nx1 = cf{0.f, 0.f};  // window elements tid and 256 + tid (the latter: tid < halo <= 127)
-    auto fetch = [&](size_t t) {
-        const long long w0 = static_cast<long long>(t) * 256 - halo;
-        nx0 = to_cf(stream_at(a.sym, a.hist, a.hist_len, w0 + tid, a.n_sym));
-        if (tid < halo) nx1 = to_cf(stream_at(a.sym, a.hist, a.hist_len, w0 + 256 + tid, a.n_sym));
-    };
-    if (blockIdx.x < ntiles) fetch(blockIdx.x);
-    for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const long long m0 = static_cast<long long>(t) * 256;
-        __syncthreads();
-        sh[tid] = nx0;
-        if (tid < halo) sh[256 + tid] = nx1;
-        __syncthreads();
-        if (t + gridDim.x < ntiles) fetch(t + gridDim.x);
-        cf acc[SPS];
-#pragma unroll
-        for (int p = 0; p < SPS; ++p) acc[p] = cf{0.f, 0.f};
-        const cf* sp = sh + halo + tid;
-        for (int j0 = 0; j0 < a.J; j0 += PP_JB) {
-            cf sv[PP_JB];
-            v2f tr[PP_JB * SPSP / 2], ti[PP_JB * SPSP / 2];
-#pragma unroll
-            for (int i = 0; i < PP_JB * SPSP / 2; ++i) {
-                tr[i] = v2f{a.are[j0 * SPSP + 2 * i], a.are[j0 * SPSP + 2 * i + 1]};
-                if (!REAL) ti[i] = v2f{a.aim[j0 * SPSP + 2 * i], a.aim[j0 * SPSP + 2 * i + 1]};
-            }
-#pragma unroll
-            for (int jj = 0; jj < PP_JB; ++jj) sv[jj] = sp[-(j0 + jj)];
-#pragma unroll
-            for (int jj = 0; jj < PP_JB; ++jj)
-#pragma unroll
-                for (int p = 0; p < SPS; ++p) {
-                    const int e = jj * SPSP + p;
-                    mac_tap<REAL>(acc[p], sv[jj], tr[e >> 1], ti[e >> 1], (e & 1) != 0);
-                }
-        }
-        if (MIX) {
-            const cf r0 = cf{static_cast<float>(rc), static_cast<float>(rs)};
-#pragma unroll
-            for (int p = 0; p < SPS; ++p) acc[p] = cmulf(acc[p], p ? cmulf(r0, to_cf(a.step[p])) : r0);
-            const double nc = rc * a.mx.sweep_c - rs * a.mx.sweep_s;
-            rs = rc * a.mx.sweep_s + rs * a.mx.sweep_c;
-            rc = nc;
-        }
-        {
-            // A lane's SPS outputs are one run of SPS * 8 B, so a plain store instruction covers a wave's 64 SPS outputs in
-            // pieces of 16 B at a stride of SPS * 8 B.  Through the wave's own LDS block instead, CW <= 8 phases at a time:
-            // instruction i writes elements 64 i ... 64 i + 63 of the block [64 symbols][CW], i.e. whole lines for SPS <= 8
-            // and runs of CW * 8 B above (63 taps x 4, 2^26 outputs: 183 -> 134 us; 127 taps x 8, 2^24: 48.8 -> 29.7 us).
-            cf* ex = xch + (tid & ~63) * CW;
-            const int lane = tid & 63;
-            const size_t mw = static_cast<size_t>(m0) + (tid & ~63);                      // the wave's first symbol
-            const unsigned nel = mw < a.n_sym ? static_cast<unsigned>(a.n_sym - mw < 64 ? a.n_sym - mw : 64) * CW : 0u;  // valid elements per chunk
-#pragma unroll
-            for (int c = 0; c < SPS / CW; ++c) {
-                if (c) {  // the previous chunk has been read
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                }
-#pragma unroll
-                for (int p = 0; p < CW; ++p) ex[lane * CW + p] = acc[c * CW + p];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (a.mx.out_i16) {  // the transmit chain straight into the IQOutput wire format: 4 B per output
-                    constexpr int W = CW % 4 == 0 ? 4 : CW % 2 == 0 ? 2 : 1;  // outputs per lane and store
-                    short2* o = reinterpret_cast<short2*>(a.out) + mw * SPS + c * CW;
-#pragma unroll
-                    for (int i = 0; i < CW / W; ++i) {
-                        const unsigned e = (static_cast<unsigned>(i) * 64u + lane) * W;
-                        if (e < nel) {  // (nel is a multiple of CW, hence of W)
-                            short2 q[W];
-#pragma unroll
-                            for (int w = 0; w < W; ++w) q[w] = c32_as_i16(to_f2(ex[e + w]), a.mx.out_scale);
-                            short2* dp = o + (e / CW) * SPS + e % CW;
-                            if constexpr (W == 4) {
-                                u32x4 qv;
-                                __builtin_memcpy(&qv, q, 16);
-                                store_b128_dword_aligned(dp, qv);
-                            } else if constexpr (W == 2) {
-                                __builtin_memcpy(dp, q, 8);
-                            } else {
-                                dp[0] = q[0];
-                            }
-                        }
-                    }
-                } else {
-                    constexpr int W = CW % 2 == 0 ? 2 : 1;
-                    float2* o = a.out + mw * SPS + c * CW;
-#pragma unroll
-                    for (int i = 0; i < CW / W; ++i) {
-                        const unsigned e = (static_cast<unsigned>(i) * 64u + lane) * W;
-                        if (e < nel) {
-                            float2* dp = o + (e / CW) * SPS + e % CW;
-                            if constexpr (W == 2) {
-                                const cf u0 = ex[e], u1 = ex[e + 1];
-                                float2 q[2] = {to_f2(u0), to_f2(u1)};
-                                __builtin_memcpy(dp, q, 16);
-                            } else {
-                                dp[0] = to_f2(ex[e]);
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    }
-    kstamp_end(a.ks);
+#define PULSE_SYM a.sym
+#include "pulse_body.inc"
+#undef PULSE_SYM
+}
+// the same kernel over another symbol input (InBits: comms_pulse_set_input_format); `in` travels next to the
+// arguments block (PulseArgs 3440 B + InBits<2> 40 B, within the 4 KiB kernel-argument limit)
+template <int SPS, bool REAL, bool MIX, class In>
+__global__ __launch_bounds__(256) void pulse_poly_in_kernel(const PulseArgs a, const In in) {
+#define PULSE_SYM in
+#include "pulse_body.inc"
+#undef PULSE_SYM
 }
 
 }  // namespace comms
@@ -2461,17 +2352,29 @@ struct comms_pulse : Handle {
     uint64_t turns = 0, frac = 0;
     bool out_i16 = false;  // comms_pulse_set_output_format
     float out_scale = 1.0f;
+    int in_bits = 0;       // comms_pulse_set_input_format: 0 = Complex<f32> symbols, else bits per symbol (1, 2)
+    float2 cons[4] = {};   //   ... and the constellation
 };
 
+// f(view) with the device view of d_sym that the handle's input format needs: the Complex<f32> pointer, or the
+// packed bits with the constellation (InBits)
+template <class F>
+static auto with_pulse_input(const comms_pulse* h, const void* d_sym, F&& f) {
+    if (h->in_bits == 1) return f(comms::InBits<1>{static_cast<const uint8_t*>(d_sym), {h->cons[0], h->cons[1]}});
+    if (h->in_bits == 2)
+        return f(comms::InBits<2>{static_cast<const uint8_t*>(d_sym), {h->cons[0], h->cons[1], h->cons[2], h->cons[3]}});
+    return f(static_cast<const float2*>(d_sym));
+}
+
 // Launches pulse_poly_kernel if (sps, taps) fit it; false -> the caller runs the generic kernel.
-template <int SPS>
-static bool pulse_poly_try(comms_pulse* h, const float2* sym, size_t n_sym, float2* out, hipStream_t s) {
+template <int SPS, class In>
+static bool pulse_poly_try(comms_pulse* h, In sym, size_t n_sym, float2* out, hipStream_t s) {
     constexpr int SPSP = SPS + (SPS & 1);
     int J = (h->n_taps + SPS - 1) / SPS;
     J = (J + comms::PP_JB - 1) / comms::PP_JB * comms::PP_JB;
     if (J > comms::PP_JMAX || J * SPSP > comms::PP_AMAX) return false;
     comms::PulseArgs a{};
-    a.sym = sym;
+    if constexpr (std::is_same<In, const float2*>::value) a.sym = sym;
     a.hist = h->d_hist[h->cur];
     a.new_hist = h->d_hist[h->cur ^ 1];
     a.out = out;
@@ -2508,10 +2411,17 @@ static bool pulse_poly_try(comms_pulse* h, const float2* sym, size_t n_sym, floa
     a.ks = h->next_stamp();
 #define COMMS_PULSE_GO(REAL, MIX)                                                                                            \
     do {                                                                                                                     \
-        if (ea)                                                                                                              \
-            hipExtLaunchKernelGGL((comms::pulse_poly_kernel<SPS, REAL, MIX>), dim3(blocks), dim3(256), 0u, s, ea, eb, 0u, a); \
-        else                                                                                                                 \
-            comms::pulse_poly_kernel<SPS, REAL, MIX><<<dim3(blocks), dim3(256), 0, s>>>(a);                                  \
+        if constexpr (std::is_same<In, const float2*>::value) {                                                              \
+            if (ea)                                                                                                          \
+                hipExtLaunchKernelGGL((comms::pulse_poly_kernel<SPS, REAL, MIX>), dim3(blocks), dim3(256), 0u, s, ea, eb, 0u, a); \
+            else                                                                                                             \
+                comms::pulse_poly_kernel<SPS, REAL, MIX><<<dim3(blocks), dim3(256), 0, s>>>(a);                              \
+        } else {                                                                                                             \
+            if (ea)                                                                                                          \
+                hipExtLaunchKernelGGL((comms::pulse_poly_in_kernel<SPS, REAL, MIX, In>), dim3(blocks), dim3(256), 0u, s, ea, eb, 0u, a, sym); \
+            else                                                                                                             \
+                comms::pulse_poly_in_kernel<SPS, REAL, MIX, In><<<dim3(blocks), dim3(256), 0, s>>>(a, sym);                  \
+        }                                                                                                                    \
     } while (0)
     if (h->mix) {
         if (h->real_taps) COMMS_PULSE_GO(true, true); else COMMS_PULSE_GO(false, true);
@@ -2521,7 +2431,8 @@ static bool pulse_poly_try(comms_pulse* h, const float2* sym, size_t n_sym, floa
 #undef COMMS_PULSE_GO
     return true;
 }
-static bool pulse_poly_launch(comms_pulse* h, const float2* sym, size_t n_sym, float2* out, hipStream_t s) {
+template <class In>
+static bool pulse_poly_launch(comms_pulse* h, In sym, size_t n_sym, float2* out, hipStream_t s) {
     static const bool off = diag_knob("COMMS_PULSE_GENERIC", 0) != 0;
     if (off) return false;
     switch (h->sps) {
@@ -2595,11 +2506,12 @@ comms_status_t comms_pulse_run_dev(comms_pulse_t* h, const comms_c32* d_sym, siz
     if (!n_sym) return COMMS_OK;
     COMMS_ARG(n_sym <= SIZE_MAX / 8 / h->sps, "n_sym * sam_per_sym overflows");
     const size_t n_out = n_sym * h->sps;
-    COMMS_ARG(!ranges_overlap(d_sym, n_sym * 8, d_out, n_out * (h->out_i16 ? 4 : 8)), "pulse shaping cannot run in place");
+    const size_t in_bytes = h->in_bits ? (n_sym * h->in_bits + 7) / 8 : n_sym * 8;  // COMMS_SYM_BITS: packed bits
+    COMMS_ARG(!ranges_overlap(d_sym, in_bytes, d_out, n_out * (h->out_i16 ? 4 : 8)), "pulse shaping cannot run in place");
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
-    const float2* sym = reinterpret_cast<const float2*>(d_sym);
-    if (!pulse_poly_launch(h, sym, n_sym, reinterpret_cast<float2*>(d_out), s)) {
+    const bool poly = with_pulse_input(h, d_sym, [&](auto sym) { return pulse_poly_launch(h, sym, n_sym, reinterpret_cast<float2*>(d_out), s); });
+    if (!poly) {
         h->tic(s);
         size_t blocks = (n_out + 255) / 256;
         if (blocks > 8u * kNumCU) blocks = 8u * kNumCU;
@@ -2612,9 +2524,16 @@ comms_status_t comms_pulse_run_dev(comms_pulse_t* h, const comms_c32* d_sym, siz
             mx.frac = h->frac;
             mix_host_rotor(static_cast<uint64_t>(blocks) * 256u * h->frac, mx.sweep_c, mx.sweep_s);
         }
-        pulse_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(256), h->n_taps * sizeof(float2), s>>>(
-            sym, h->d_hist[h->cur], h->hist_len, h->d_taps, h->n_taps, h->sps,
-            reinterpret_cast<float2*>(d_out), n_sym, h->d_hist[h->cur ^ 1], mx);
+        with_pulse_input(h, d_sym, [&](auto sym) {
+            if constexpr (std::is_same<decltype(sym), const float2*>::value)
+                pulse_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(256), h->n_taps * sizeof(float2), s>>>(
+                    sym, h->d_hist[h->cur], h->hist_len, h->d_taps, h->n_taps, h->sps,
+                    reinterpret_cast<float2*>(d_out), n_sym, h->d_hist[h->cur ^ 1], mx);
+            else
+                pulse_in_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(256), h->n_taps * sizeof(float2), s>>>(
+                    sym, h->d_hist[h->cur], h->hist_len, h->d_taps, h->n_taps, h->sps,
+                    reinterpret_cast<float2*>(d_out), n_sym, h->d_hist[h->cur ^ 1], mx);
+        });
         h->toc(s);
     }
     COMMS_TRY(launch_ok("pulse kernel"));  // (workgroup 0 of the same launch advanced the history)
@@ -2646,6 +2565,26 @@ comms_status_t comms_pulse_set_output_format(comms_pulse_t* h, int32_t format, f
     return COMMS_OK;
 }
 
+// Symbols from packed bits (COMMS_SYM_BITS): the transmit front end PRNS -> BPSK / QPSK -> pulse shaping in one
+// launch, 1/8 or 1/4 B read per symbol instead of 8.  The node's history keeps the mapped Complex<f32> symbols.
+comms_status_t comms_pulse_set_input_format(comms_pulse_t* h, int32_t format, int32_t bits_per_sym, const comms_c32* constellation) {
+    COMMS_ARG(h != nullptr, "handle is NULL");
+    COMMS_ARG(format == COMMS_SYM_C32 || format == COMMS_SYM_BITS, "the pulse node reads COMMS_SYM_C32 or COMMS_SYM_BITS (got format %d)", format);
+    if (format == COMMS_SYM_C32) {
+        h->in_bits = 0;
+        return COMMS_OK;
+    }
+    COMMS_ARG(bits_per_sym == 1 || bits_per_sym == 2, "bits_per_sym must be 1 or 2 (got %d)", bits_per_sym);
+    // digital.rs: bpsk_bit_mod (:6-14), qpsk_bit_mod (:24-36)
+    static const float2 kBpsk[2] = {{1.f, 0.f}, {-1.f, 0.f}};
+    static const float2 kQpsk[4] = {{1.f, 1.f}, {-1.f, 1.f}, {1.f, -1.f}, {-1.f, -1.f}};
+    const int m = 1 << bits_per_sym;
+    for (int v = 0; v < m; ++v)
+        h->cons[v] = constellation ? make_float2(constellation[v].re, constellation[v].im) : bits_per_sym == 1 ? kBpsk[v] : kQpsk[v];
+    h->in_bits = bits_per_sym;
+    return COMMS_OK;
+}
+
 comms_status_t comms_pulse_get_phase(const comms_pulse_t* h, double* out_phase) {
     COMMS_ARG(h && out_phase, "NULL argument");
     COMMS_ARG(h->mix, "no mixer is fused into this pulse node");
@@ -2660,6 +2599,13 @@ comms_status_t comms_pulse_run(comms_pulse_t* h, const comms_c32* sym, size_t n_
     COMMS_TRY(use_device(h->device));
     if (!n_sym) return COMMS_OK;
     const size_t out_sym = static_cast<size_t>(h->sps) * (h->out_i16 ? 4 : sizeof(comms_c32));  // output bytes per symbol
+    if (h->in_bits) {  // packed bits: chunks of whole input bytes (8 / bits_per_sym symbols each), the remainder last
+        COMMS_ARG(n_sym <= SIZE_MAX / 8 / out_sym, "n_sym * sam_per_sym overflows");
+        const size_t per_byte = 8 / h->in_bits;
+        return h->run_host_units(sym, (n_sym * h->in_bits + 7) / 8, 1, out, n_sym * out_sym, per_byte * out_sym, [&](void* d_in, void* d_out, size_t, size_t ob) {
+            return comms_pulse_run_dev(h, static_cast<const comms_c32*>(d_in), ob / out_sym, static_cast<comms_c32*>(d_out), COMMS_STREAM_HANDLE);
+        });
+    }
     return h->run_host_units(sym, n_sym * sizeof(comms_c32), sizeof(comms_c32), out, n_sym * out_sym, out_sym, [&](void* d_in, void* d_out, size_t ib, size_t) {
         return comms_pulse_run_dev(h, static_cast<const comms_c32*>(d_in), ib / sizeof(comms_c32), static_cast<comms_c32*>(d_out), COMMS_STREAM_HANDLE);
     });

@@ -6,6 +6,7 @@
 //       back it is `(scale * x) as i16` (examples/single_thread_bpsk.rs:40-44: 8192.0 * x as i16;
 //       Rust `as`: truncate toward zero, saturate, NaN -> 0);
 //   u8 pairs from an RTL-SDR -- examples/fm_radio.rs:82-90: (x as f32 - 127.5) / 127.5.
+// And the digital modulators of src/modulation/digital.rs: bits -> Complex<i16> symbols (bpsk/qpsk _bit_mod, _byte_mod).
 #include "common.hpp"
 #include "fir_handle.hpp"
 
@@ -57,6 +58,38 @@ __global__ __launch_bounds__(256) void c32_re_kernel(const float2* __restrict__ 
         reinterpret_cast<float2*>(out)[i] = make_float2(v.x, v.z);
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) out[n - 1] = in[n - 1].x;
+}
+
+// Digital modulation (src/modulation/digital.rs): bits -> Complex<i16> symbols, elementwise.  A symbol is one
+// (re, im) pair of i16 = 4 B; a lane writes the 8 (BPSK) or 4 (QPSK) symbols of its byte as 16-byte stores.
+// Out-of-range values of the *_bit_mod forms give (0,0) (the reference returns None; the host entries refuse them).
+__device__ __forceinline__ unsigned bpsk_c16(unsigned b) {  // 0 -> (1,0), 1 -> (-1,0) as the dword {re, im}
+    return b == 0u ? 0x00000001u : b == 1u ? 0x0000FFFFu : 0u;
+}
+__device__ __forceinline__ unsigned qpsk_c16(unsigned v) {  // 0 (1,1), 1 (-1,1), 2 (1,-1), 3 (-1,-1)
+    const unsigned re = (v & 1u) ? 0xFFFFu : 0x0001u, im = (v & 2u) ? 0xFFFF0000u : 0x00010000u;
+    return v < 4u ? (re | im) : 0u;
+}
+__global__ __launch_bounds__(256) void bpsk_byte_kernel(const uint8_t* __restrict__ in, uint4* __restrict__ out, size_t n) {
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const unsigned b = in[i];
+        out[2 * i] = make_uint4(bpsk_c16(b & 1u), bpsk_c16((b >> 1) & 1u), bpsk_c16((b >> 2) & 1u), bpsk_c16((b >> 3) & 1u));
+        out[2 * i + 1] = make_uint4(bpsk_c16((b >> 4) & 1u), bpsk_c16((b >> 5) & 1u), bpsk_c16((b >> 6) & 1u), bpsk_c16(b >> 7));
+    }
+}
+__global__ __launch_bounds__(256) void qpsk_byte_kernel(const uint8_t* __restrict__ in, uint4* __restrict__ out, size_t n) {
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const unsigned b = in[i];
+        out[i] = make_uint4(qpsk_c16(b & 3u), qpsk_c16((b >> 2) & 3u), qpsk_c16((b >> 4) & 3u), qpsk_c16(b >> 6));
+    }
+}
+template <bool QPSK>
+__global__ __launch_bounds__(256) void psk_bit_kernel(const uint8_t* __restrict__ in, unsigned* __restrict__ out, size_t n) {
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[i] = QPSK ? qpsk_c16(in[i]) : bpsk_c16(in[i]);
 }
 
 static unsigned conv_grid(size_t n) {
@@ -157,6 +190,76 @@ comms_status_t comms_iq_u8_to_c32(const uint8_t* in, size_t n, comms_c32* out, i
     if (!n) return use_device(device);
     return via_device(in, n, 2, out, 8, device, [&](void* a, void* b, size_t m, void* st) {
         return comms_iq_u8_to_c32_dev(static_cast<const uint8_t*>(a), m, static_cast<comms_c32*>(b), device, st);
+    });
+}
+
+// ---- digital modulation
+static comms_status_t psk_dev_args(const uint8_t* d_in, size_t n, const comms_c16* d_out, size_t per, int32_t device) {
+    COMMS_ARG((d_in && d_out) || !n, "NULL device pointer");
+    COMMS_ARG(n <= SIZE_MAX / 32, "n too large");
+    COMMS_ARG((reinterpret_cast<uintptr_t>(d_out) & (per > 1 ? 15 : 3)) == 0,
+              per > 1 ? "d_out must be 16-byte aligned" : "d_out must be aligned to one Complex<i16>");
+    COMMS_ARG(!ranges_overlap(d_in, n, d_out, n * per * 4), "modulation cannot run in place");
+    return use_device(device);
+}
+comms_status_t comms_bpsk_byte_mod_dev(const uint8_t* d_in, size_t n, comms_c16* d_out, int32_t device, void* stream) {
+    COMMS_TRY(psk_dev_args(d_in, n, d_out, 8, device));
+    if (!n) return COMMS_OK;
+    bpsk_byte_kernel<<<dim3(conv_grid(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(d_in, reinterpret_cast<uint4*>(d_out), n);
+    return launch_ok("bpsk_byte_kernel");
+}
+comms_status_t comms_qpsk_byte_mod_dev(const uint8_t* d_in, size_t n, comms_c16* d_out, int32_t device, void* stream) {
+    COMMS_TRY(psk_dev_args(d_in, n, d_out, 4, device));
+    if (!n) return COMMS_OK;
+    qpsk_byte_kernel<<<dim3(conv_grid(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(d_in, reinterpret_cast<uint4*>(d_out), n);
+    return launch_ok("qpsk_byte_kernel");
+}
+comms_status_t comms_bpsk_bit_mod_dev(const uint8_t* d_in, size_t n, comms_c16* d_out, int32_t device, void* stream) {
+    COMMS_TRY(psk_dev_args(d_in, n, d_out, 1, device));
+    if (!n) return COMMS_OK;
+    psk_bit_kernel<false><<<dim3(conv_grid(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(d_in, reinterpret_cast<unsigned*>(d_out), n);
+    return launch_ok("psk_bit_kernel");
+}
+comms_status_t comms_qpsk_bit_mod_dev(const uint8_t* d_in, size_t n, comms_c16* d_out, int32_t device, void* stream) {
+    COMMS_TRY(psk_dev_args(d_in, n, d_out, 1, device));
+    if (!n) return COMMS_OK;
+    psk_bit_kernel<true><<<dim3(conv_grid(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(d_in, reinterpret_cast<unsigned*>(d_out), n);
+    return launch_ok("psk_bit_kernel");
+}
+comms_status_t comms_bpsk_byte_mod(const uint8_t* in, size_t n, comms_c16* out, int32_t device) {
+    COMMS_ARG((in && out) || !n, "NULL host pointer");
+    if (!n) return use_device(device);
+    return via_device(in, n, 1, out, 32, device, [&](void* a, void* b, size_t m, void* st) {
+        return comms_bpsk_byte_mod_dev(static_cast<const uint8_t*>(a), m, static_cast<comms_c16*>(b), device, st);
+    });
+}
+comms_status_t comms_qpsk_byte_mod(const uint8_t* in, size_t n, comms_c16* out, int32_t device) {
+    COMMS_ARG((in && out) || !n, "NULL host pointer");
+    if (!n) return use_device(device);
+    return via_device(in, n, 1, out, 16, device, [&](void* a, void* b, size_t m, void* st) {
+        return comms_qpsk_byte_mod_dev(static_cast<const uint8_t*>(a), m, static_cast<comms_c16*>(b), device, st);
+    });
+}
+// the reference returns None for a value the table does not hold: refused here before anything runs
+static comms_status_t psk_bit_check(const uint8_t* in, size_t n, unsigned top, const char* what) {
+    for (size_t i = 0; i < n; ++i)
+        COMMS_ARG(in[i] <= top, "%s: value %u at index %zu is not a symbol (the reference returns None)", what, in[i], i);
+    return COMMS_OK;
+}
+comms_status_t comms_bpsk_bit_mod(const uint8_t* in, size_t n, comms_c16* out, int32_t device) {
+    COMMS_ARG((in && out) || !n, "NULL host pointer");
+    COMMS_TRY(psk_bit_check(in, n, 1, "bpsk_bit_mod"));
+    if (!n) return use_device(device);
+    return via_device(in, n, 1, out, 4, device, [&](void* a, void* b, size_t m, void* st) {
+        return comms_bpsk_bit_mod_dev(static_cast<const uint8_t*>(a), m, static_cast<comms_c16*>(b), device, st);
+    });
+}
+comms_status_t comms_qpsk_bit_mod(const uint8_t* in, size_t n, comms_c16* out, int32_t device) {
+    COMMS_ARG((in && out) || !n, "NULL host pointer");
+    COMMS_TRY(psk_bit_check(in, n, 3, "qpsk_bit_mod"));
+    if (!n) return use_device(device);
+    return via_device(in, n, 1, out, 4, device, [&](void* a, void* b, size_t m, void* st) {
+        return comms_qpsk_bit_mod_dev(static_cast<const uint8_t*>(a), m, static_cast<comms_c16*>(b), device, st);
     });
 }
 

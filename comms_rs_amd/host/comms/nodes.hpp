@@ -11,6 +11,7 @@
 //   FMDemodNode::new()                            src/modulation/analog_node.rs:43
 //   TimingEstimatorNode::new(n, d, alpha)         src/demodulation/timing_estimator.rs:123
 //   NcoNode::new(dphase, phase) (block form)      src/demodulation/nco.rs:118
+//   PrnsNode::new(poly_mask, state)               src/prns.rs:93-137
 // Messages are host vectors (std::vector<Complex>), moved through the channels by
 // value as in the reference; every run() goes H2D -> kernel -> D2H through the C
 // ABI.  The *Dev variants at the bottom keep messages device-resident
@@ -379,6 +380,59 @@ public:
 private:
     comms_pulse_t* h_ = nullptr;
     size_t sps_;
+};
+
+// ---------------------------------------------------------------- PRNS source
+// A source node (no input): run() returns the next bit of the LFSR (prns.rs:131-133), as the reference.  The bits are
+// generated on the device kBlock at a time and handed out one per run(); state() is the register before the NEXT bit
+// run() returns (the handle itself has already advanced past the block -- comms_prns_skip makes that exact and
+// host-only).  width = 8, 16, 32 or 64 (PrnsNode<u8/u16/u32/u64>).
+class PrnsNode : public DeriveNode<PrnsNode> {
+public:
+    NodeSender<uint8_t> output;
+    static constexpr size_t kBlock = 4096;
+
+    PrnsNode(uint64_t poly_mask, uint64_t state, int width = 8, int device = 0) : start_(state) {
+        throw_on(comms_prns_create(poly_mask, state, width, device, &h_), "PrnsNode::new");
+    }
+    PrnsNode(PrnsNode&& o) noexcept
+        : output(std::move(o.output)), h_(o.h_), buf_(std::move(o.buf_)), pos_(o.pos_), start_(o.start_) { o.h_ = nullptr; }
+    ~PrnsNode() { comms_prns_destroy(h_); }
+
+    Result<uint8_t> run() {
+        if (pos_ == buf_.size()) {
+            uint64_t s = 0;
+            comms_status_t st = comms_prns_get_state(h_, &s);
+            buf_.resize(kBlock);
+            if (st == COMMS_OK) st = comms_prns_run(h_, kBlock, COMMS_BITS_U8, buf_.data());
+            if (st != COMMS_OK) {
+                buf_.clear();
+                pos_ = 0;
+                return to_node_error(st);
+            }
+            start_ = s;
+            pos_ = 0;
+        }
+        return buf_[pos_++];
+    }
+    // the register before the next bit run() returns (PrnGen's `state`)
+    uint64_t state() {
+        uint64_t ahead = 0, s = 0;
+        throw_on(comms_prns_get_state(h_, &ahead), "PrnsNode::state");
+        throw_on(comms_prns_set_state(h_, start_), "PrnsNode::state");
+        throw_on(comms_prns_skip(h_, pos_), "PrnsNode::state");
+        throw_on(comms_prns_get_state(h_, &s), "PrnsNode::state");
+        throw_on(comms_prns_set_state(h_, ahead), "PrnsNode::state");
+        return s;
+    }
+    auto receivers() { return std::tie(); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_prns_t* h_ = nullptr;
+    std::vector<uint8_t> buf_;
+    size_t pos_ = 0;
+    uint64_t start_ = 0;  // register at buf_[0]
 };
 
 // ---------------------------------------------------------------- mixer

@@ -202,8 +202,49 @@ class PulseNode(_Handle):
         self._out_i16 = fmt == "i16"
         return self
 
+    _in_bits = 0
+
+    def set_input_format(self, fmt, bits_per_sym=1, constellation=None):
+        """"bits": run_bits() takes packed bits (LSB first, bits_per_sym = 1 or 2 per symbol) and the kernel maps
+        value v to constellation[v] (2**bits_per_sym points; None = digital.rs's bpsk_bit_mod / qpsk_bit_mod tables);
+        "c32" restores the default, run() on complex symbols.  The history carries across a switch."""
+        if fmt == "c32":
+            check(lib().comms_pulse_set_input_format(self._h, _lib.SYM_C32, 0, None))
+            self._in_bits = 0
+            return self
+        if fmt != "bits":
+            raise ValueError("input format must be 'c32' or 'bits' (got %r)" % (fmt,))
+        cons = None
+        if constellation is not None:
+            cons = _as_c64(constellation).ravel()
+            if cons.size != 1 << int(bits_per_sym):
+                raise ValueError("the constellation holds 2**bits_per_sym points")
+        check(lib().comms_pulse_set_input_format(self._h, _lib.SYM_BITS, int(bits_per_sym), None if cons is None else _ptr(cons)))
+        self._cons = cons  # (kept alive while the call copies it)
+        self._in_bits = int(bits_per_sym)
+        return self
+
+    def _out_array(self, n_sym):
+        if self._out_i16:
+            return np.empty((n_sym * self.sam_per_sym, 2), np.int16)
+        return np.empty(n_sym * self.sam_per_sym, np.complex64)
+
+    def run_bits(self, packed, n_sym):
+        """n_sym symbols from packed bits (uint8, LSB first; ceil(n_sym * bits_per_sym / 8) bytes) -> samples."""
+        if not self._in_bits:
+            raise ValueError("run_bits needs set_input_format('bits', ...)")
+        n_sym = int(n_sym)
+        b = np.ascontiguousarray(packed, dtype=np.uint8).ravel()
+        if b.size < (n_sym * self._in_bits + 7) // 8:
+            raise ValueError("packed holds fewer than n_sym * bits_per_sym bits")
+        out = self._out_array(n_sym)
+        check(lib().comms_pulse_run(self._h, _ptr(b), n_sym, _ptr(out)))
+        return out
+
     def run(self, sym):
         """One symbol (scalar) -> sam_per_sym samples, or a batch of symbols."""
+        if self._in_bits:
+            raise ValueError("the node reads packed bits (set_input_format): use run_bits")
         s = _as_c64(np.atleast_1d(sym))
         if self._out_i16:
             out = np.empty((s.size * self.sam_per_sym, 2), np.int16)
@@ -710,6 +751,74 @@ def iq_u8_to_c32(x, device=0):
     out = np.empty(x.shape[0], np.complex64)
     check(lib().comms_iq_u8_to_c32(_ptr(x), x.shape[0], _ptr(out), device))
     return out
+
+
+# ------------------------------------------------------------------ digital modulation (digital.rs)
+def _psk(fn, x, per, device):
+    x = np.ascontiguousarray(x, dtype=np.uint8).ravel()
+    out = np.empty((x.size * per, 2), np.int16)
+    check(getattr(lib(), fn)(_ptr(x), x.size, _ptr(out), device))
+    return out
+
+
+def bpsk_byte_mod(x, device=0):
+    """digital.rs:17-21 over a byte array: int16 (8n, 2) Complex<i16> symbols, bit i of a byte -> symbol i."""
+    return _psk("comms_bpsk_byte_mod", x, 8, device)
+
+
+def qpsk_byte_mod(x, device=0):
+    """digital.rs:39-44 over a byte array: int16 (4n, 2), (byte >> 2i) & 3 -> symbol i."""
+    return _psk("comms_qpsk_byte_mod", x, 4, device)
+
+
+def bpsk_bit_mod(x, device=0):
+    """digital.rs:6-14 over values 0 / 1 (anything else: CommsError, as the reference's None)."""
+    return _psk("comms_bpsk_bit_mod", x, 1, device)
+
+
+def qpsk_bit_mod(x, device=0):
+    """digital.rs:24-36 over values 0..3 (anything else: CommsError, as the reference's None)."""
+    return _psk("comms_qpsk_bit_mod", x, 1, device)
+
+
+# ------------------------------------------------------------------ PRNS source
+class PrnsNode(_Handle):
+    """PrnsNode::new(poly_mask, state) (prns.rs:93-137) on an unsigned register of `width` = 8, 16, 32 or 64 bits:
+    run() returns the next bit, as the reference; run_batch(n) the next n bits (uint8 0/1 per bit, or packed LSB
+    first with packed=True), generated on the device.  `state` and skip(n) never wait for the device."""
+    _destroy = "comms_prns_destroy"
+
+    def __init__(self, poly_mask, state, width=8, device=0):
+        super().__init__()
+        self.width = int(width)
+        check(lib().comms_prns_create(int(poly_mask), int(state), self.width, device, C.byref(self._h)))
+
+    def run(self):
+        return int(self.run_batch(1)[0])
+
+    def run_batch(self, n, packed=False):
+        n = int(n)
+        out = np.empty((n + 7) // 8 if packed else n, np.uint8)
+        check(lib().comms_prns_run(self._h, n, _lib.BITS_PACKED if packed else _lib.BITS_U8, _ptr(out)))
+        return out
+
+    def run_dev(self, n, out_ptr, packed=False, stream=0):
+        check(lib().comms_prns_run_dev(self._h, int(n), _lib.BITS_PACKED if packed else _lib.BITS_U8, out_ptr, stream))
+
+    @property
+    def state(self):
+        v = C.c_uint64()
+        check(lib().comms_prns_get_state(self._h, C.byref(v)))
+        return v.value
+
+    @state.setter
+    def state(self, value):
+        check(lib().comms_prns_set_state(self._h, int(value)))
+
+    def skip(self, n):
+        """Jump ahead n bits (any n < 2**64): shard r of a stream starts at skip(r * n)."""
+        check(lib().comms_prns_skip(self._h, int(n)))
+        return self
 
 
 # ------------------------------------------------------------------ block estimators
