@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 COMMS_OK, COMMS_ERR_ARG, COMMS_ERR_DEVICE = 0, 1, 2
 FIR_AUTO, FIR_DIRECT, FIR_OVERLAP_SAVE, FIR_OS1024, FIR_OS4096, FIR_OS16K, FIR_OS1024_FIXED = 0, 1, 2, 3, 4, 5, 6
 IQ_C32, IQ_I16, IQ_U8 = 0, 1, 2
-SYM_C32, SYM_BITS = 0, 1        # comms_pulse_set_input_format
+SYM_C32, SYM_BITS = 0, 1        # comms_pulse_set_input_format, comms_chain_set_output_format
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 STREAM_HANDLE = C.c_void_p(-1).value  # COMMS_STREAM_HANDLE: the handle's own stream
 
@@ -73,6 +73,7 @@ _PROTOS = {
     "comms_fir_set_timer": [_vp, _vp],
     "comms_fir_set_input_format": [_vp, _i32, C.c_float],
     "comms_chain_set_input_format": [_vp, _i32, C.c_float],
+    "comms_chain_set_output_format": [_vp, _i32, _i32, _vp],
     "comms_mixer_set_timer": [_vp, _vp],
     "comms_pulse_set_timer": [_vp, _vp],
     "comms_fmdemod_set_timer": [_vp, _vp],
@@ -180,6 +181,10 @@ _PROTOS = {
     "comms_qpsk_byte_mod_dev": [_vp, _sz, _vp, _i32, _vp],
     "comms_bpsk_bit_mod_dev": [_vp, _sz, _vp, _i32, _vp],
     "comms_qpsk_bit_mod_dev": [_vp, _sz, _vp, _i32, _vp],
+    "comms_sym_to_bits": [_vp, _sz, _i32, _vp, _vp, _i32],
+    "comms_sym_to_bits_dev": [_vp, _sz, _i32, _vp, _vp, _i32, _vp],
+    "comms_bit_errors": [_vp, _vp, _u64, C.POINTER(_u64), _i32],
+    "comms_bit_errors_dev": [_vp, _vp, _u64, C.POINTER(_u64), _i32, _vp],
     "comms_prns_create": [_u64, _u64, _i32, _i32, _pp],
     "comms_prns_run": [_vp, _sz, _i32, _vp],
     "comms_prns_run_dev": [_vp, _sz, _i32, _vp, _vp],

@@ -76,7 +76,15 @@ struct comms_chain : Handle {
     int in_fmt = COMMS_IQ_C32;                 // wire format of d_in (comms_chain_set_input_format)
     float in_scale = 1.0f;
     Scratch t0;                                // converted input, for the kinds that read Complex<f32> only
+    int out_bits = 0;                          // COMMS_SYM_BITS output: bits per symbol (0: Complex<f32> / FM angles)
+    SymTable out_sym{};                        // ... and the decision table (comms_chain_set_output_format)
 };
+
+// bytes of a call's output of n_dec decimated samples
+static size_t chain_out_bytes(const comms_chain* h, size_t n_dec) {
+    if (h->out_bits) return (n_dec * static_cast<size_t>(h->out_bits) + 7) / 8;
+    return n_dec * (h->fm_demod ? sizeof(float) : sizeof(comms_c32));
+}
 
 // four-kernel path with the mixer in front: the FIR node keeps MIXED samples, so a raw user history is
 // mixed with the phases the oscillator had at samples -1, -2, ... (Mixer::mix arithmetic: f64 product
@@ -316,9 +324,8 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
     const size_t in_elem = in_elem_bytes(h->in_fmt);
-    COMMS_ARG(!ranges_overlap(d_in, n * in_elem, d_out,
-                              (n / h->rate) * (h->fm_demod ? sizeof(float) : sizeof(comms_c32))),
-              "the chain cannot run in place");
+    COMMS_ARG(!ranges_overlap(d_in, n * in_elem, d_out, chain_out_bytes(h, n / h->rate)), "the chain cannot run in place");
+    COMMS_ARG(!h->out_bits || (reinterpret_cast<uintptr_t>(d_out) & 3) == 0, "bits output (COMMS_SYM_BITS) must be 4-byte aligned");
     COMMS_ARG((reinterpret_cast<uintptr_t>(d_in) & (in_elem - 1)) == 0, "input must be aligned to one IQ sample");
     hipStream_t hs = nullptr;
     COMMS_TRY(h->enter(stream, &hs));  // the stages' state (history, prev) advances in stream order
@@ -337,10 +344,14 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
     const uint32_t rate = static_cast<uint32_t>(h->rate);
     if (is_fused(h->kind)) {
         void* stage_out = d_out;
-        if (h->fm_separate) {  // decimated filter output to scratch, the demodulator reads it
+        // decimated filter output to scratch: the demodulator reads it, or (bits output of a kernel without the fused
+        // decision stage) the decision pass
+        const bool via_t3 = h->fm_separate || h->out_bits;
+        if (via_t3) {
             COMMS_TRY(h->t3.reserve(n_dec * sizeof(comms_c32)));
             stage_out = h->t3.p;
         }
+        bool decided = false;  // the launch wrote the bits itself
         float2* prev = h->d_prev[h->cur];
         float2* prev_new = h->d_prev[h->cur ^ 1];
         switch (h->kind) {
@@ -355,7 +366,10 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
                 // long filters on long batches: the polyphase frequency-domain kernel, where it is the faster form (fir_poly8.hip)
                 if (h->time_domain || comms_fir_poly8_supported(h->fir, rate, h->mode, n) != 2) {
                     h->ran_poly8 = false;
-                    if (h->kind == ChainKind::Decim)
+                    if (h->kind == ChainKind::Decim && h->out_bits) {  // the decision in fir_decim_kernel's store stage
+                        COMMS_TRY(comms_fir_run_decim_bits_dev(h->fir, d_in, n, d_out, h->mode, h->turns, h->frac, rate, &h->out_sym, stage_out, s));
+                        decided = true;
+                    } else if (h->kind == ChainKind::Decim)
                         COMMS_TRY(comms_fir_run_decim_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
                     else
                         COMMS_TRY(comms_fir_run_decim_any_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
@@ -371,6 +385,8 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
                 break;
         }
         h->turns += static_cast<uint64_t>(n) * h->frac;
+        if (h->out_bits && !decided)
+            return sym_to_bits_launch(static_cast<const comms_c32*>(stage_out), n_dec, h->out_sym, static_cast<uint8_t*>(d_out), hs);
         if (h->fm_separate)
             return comms_fmdemod_run_dev(h->fm, static_cast<const comms_c32*>(stage_out), n_dec, static_cast<float*>(d_out), s);
         if (h->fm_demod) h->cur ^= 1;
@@ -378,8 +394,8 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
     }
     COMMS_TRY(h->t1.reserve(n * sizeof(comms_c32)));
     comms_c32* a = static_cast<comms_c32*>(h->t1.p);
-    comms_c32* dec = static_cast<comms_c32*>(d_out);  // the decimated samples: the output, or the demodulator's input
-    if (h->fm_demod) {
+    comms_c32* dec = static_cast<comms_c32*>(d_out);  // the decimated samples: the output, or the demodulator's / decision's input
+    if (h->fm_demod || h->out_bits) {
         COMMS_TRY(h->t3.reserve(n_dec * sizeof(comms_c32)));
         dec = static_cast<comms_c32*>(h->t3.p);
     }
@@ -398,6 +414,7 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
         h->raw_cur ^= 1;
         COMMS_TRY(comms_decimate_run_dev(b, n, sizeof(comms_c32), h->rate, dec, nullptr, h->device, s));
     }
+    if (h->out_bits) return sym_to_bits_launch(dec, n_dec, h->out_sym, static_cast<uint8_t*>(d_out), hs);
     if (!h->fm_demod) return COMMS_OK;
     return comms_fmdemod_run_dev(h->fm, dec, n_dec, static_cast<float*>(d_out), s);
 }
@@ -408,12 +425,14 @@ comms_status_t comms_chain_run(comms_chain_t* h, const comms_c32* in, size_t n, 
     COMMS_ARG(n % h->rate == 0, "n (%zu) must be a multiple of the decimation rate %zu", n, h->rate);
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
-    const size_t out_bytes = (n / h->rate) * (h->fm_demod ? sizeof(float) : sizeof(comms_c32));
+    const size_t out_bytes = chain_out_bytes(h, n / h->rate);
     const size_t in_elem = in_elem_bytes(h->in_fmt);
     // (chunks of whole groups of `rate` samples: DecimateNode restarts its index with every batch, src/util/resample_node.rs:53-65,
-    // and a chunk that starts on a multiple of the rate keeps the batch's indexing)
-    const size_t out_elem = h->fm_demod ? sizeof(float) : sizeof(comms_c32);
-    COMMS_TRY(h->run_host_units(in, n * in_elem, h->rate * in_elem, out, out_bytes, out_elem, [&](void* d_in, void* d_out, size_t ib, size_t) {
+    // and a chunk that starts on a multiple of the rate keeps the batch's indexing; bits output: of 32 / k groups, one whole
+    // 32-bit word of bits, so that every chunk but the last starts on a word of the output)
+    const size_t out_elem = h->out_bits ? 4 : h->fm_demod ? sizeof(float) : sizeof(comms_c32);
+    const size_t unit = h->out_bits ? h->rate * static_cast<size_t>(32 / h->out_bits) : h->rate;
+    COMMS_TRY(h->run_host_units(in, n * in_elem, unit * in_elem, out, out_bytes, out_elem, [&](void* d_in, void* d_out, size_t ib, size_t) {
         return comms_chain_run_dev(h, static_cast<const comms_c32*>(d_in), ib / in_elem, d_out, COMMS_STREAM_HANDLE);
     }));
     // (a long filter runs the 16384-point FIR kernel inside the series of launches: its failure is this call's)
@@ -430,6 +449,23 @@ comms_status_t comms_chain_set_input_format(comms_chain_t* h, int32_t format, fl
     h->in_fmt = format;
     h->in_scale = format == COMMS_IQ_I16 ? scale : 1.0f;
     if (reads_wire_format(h->kind)) COMMS_TRY(comms_fir_set_input_format(h->fir, format, scale));
+    return COMMS_OK;
+}
+
+// Hard-decision bits instead of Complex<f32> (the receive end: matched filter, symbol-rate sampler, decision).  Stateless:
+// history, phase and the checkpoint hooks are the same whichever format a call writes.
+comms_status_t comms_chain_set_output_format(comms_chain_t* h, int32_t format, int32_t bits_per_sym, const comms_c32* constellation) {
+    COMMS_ARG(h != nullptr, "handle is NULL");
+    COMMS_ARG(format == COMMS_SYM_C32 || format == COMMS_SYM_BITS, "the chain writes COMMS_SYM_C32 or COMMS_SYM_BITS (got format %d)", format);
+    if (format == COMMS_SYM_C32) {
+        h->out_bits = 0;
+        return COMMS_OK;
+    }
+    COMMS_ARG(!h->fm_demod, "a chain with FM demod writes angles: no bits output");
+    SymTable t;
+    COMMS_TRY(sym_table(bits_per_sym, constellation, &t));
+    h->out_sym = t;
+    h->out_bits = bits_per_sym;
     return COMMS_OK;
 }
 

@@ -45,6 +45,12 @@ extern "C" COMMS_INTERNAL int32_t comms_fir_decim_supported_for(const comms_fir_
 extern "C" COMMS_INTERNAL comms_status_t comms_fir_run_decim_dev(comms_fir_t* h, const void* d_in, size_t n, void* d_out,
                                                   int32_t mode, uint64_t turns0, uint64_t frac, uint32_t rate,
                                                   const void* fm_prev, void* fm_prev_new, void* stream);
+// ... the same with hard-decision bits out of its store stage (comms_chain_set_output_format; no FM demod): ceil(n/rate * k / 8)
+// bytes at d_out (4-byte aligned).  A call the wave-private form takes (it has no decision stage) writes its Complex<f32>
+// outputs to c32_scratch (n/rate of them) and the decision pass follows, so that the bits are always those of the c32 form.
+extern "C" COMMS_INTERNAL comms_status_t comms_fir_run_decim_bits_dev(comms_fir_t* h, const void* d_in, size_t n, void* d_out,
+                                                  int32_t mode, uint64_t turns0, uint64_t frac, uint32_t rate,
+                                                  const void* sym_table, void* c32_scratch, void* stream);
 
 // ... and on the any-rate time-domain kernel (fir_decim_any.hip): mixer behind the FIR only
 extern "C" COMMS_INTERNAL int32_t comms_fir_decim_any_supported(const comms_fir_t* h, uint32_t rate);
@@ -240,6 +246,54 @@ __device__ __forceinline__ void kstamp_end(const KStamp& k) {
 }
 
 namespace comms {
+
+// ---- hard decisions (receive side: comms_chain_set_output_format, comms_sym_to_bits) ---------------------------------
+// The contract of include/comms_hip.h: nearest point by d_i = dx*dx + dy*dy, every operation rounded on its own (no FMA),
+// i scanned ascending and replaced on a strictly smaller d only -- ties to the lowest index, NaN to index 0.
+struct SymTable {
+    float2 c[4];  // 2^k points (k = 1: c[0], c[1])
+    int k;        // bits per symbol, 1 or 2
+};
+__device__ __forceinline__ float sym_dist(float2 y, float2 c) {
+    const float dx = __fsub_rn(y.x, c.x), dy = __fsub_rn(y.y, c.y);
+    return __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+}
+template <int K>
+__device__ __forceinline__ unsigned sym_decide(float2 y, const float2 (&c)[4]) {
+    unsigned v = 0;
+    float best = sym_dist(y, c[0]);
+#pragma unroll
+    for (int i = 1; i < (1 << K); ++i) {
+        const float d = sym_dist(y, c[i]);
+        if (d < best) {
+            best = d;
+            v = static_cast<unsigned>(i);
+        }
+    }
+    return v;
+}
+// 32 stream bits made by the lanes of one group (lane l holds `bits` = its `nb` bits at stream offset nb * (l % G),
+// G = 32 / nb lanes per group, groups aligned in the wave): OR-ed across the group, the sum lands in every lane of it
+template <int G>
+__device__ __forceinline__ unsigned bits_gather(unsigned bits) {
+#pragma unroll
+    for (int s = G / 2; s >= 1; s >>= 1) bits |= static_cast<unsigned>(__shfl_xor(static_cast<int>(bits), s));
+    return bits;
+}
+// One packed 32-bit word at byte offset `byte` of an output of `n_bytes` bytes: whole when it fits, otherwise only the
+// bytes before the end (the caller zeroed the bits past the last symbol) -- no byte past the end is written.
+__device__ __forceinline__ void bits_store_word(uint8_t* out, size_t byte, size_t n_bytes, unsigned word) {
+    if (byte + 4 <= n_bytes) {
+        *reinterpret_cast<unsigned*>(out + byte) = word;
+    } else {
+        for (int i = 0; i < 3; ++i)
+            if (byte + i < n_bytes) out[byte + i] = static_cast<uint8_t>(word >> (8 * i));
+    }
+}
+// COMMS_SYM_BITS table of a receiver: the caller's points, or digital.rs's (the pulse node's defaults)
+COMMS_INTERNAL comms_status_t sym_table(int32_t bits_per_sym, const comms_c32* constellation, SymTable* out);
+// n_sym symbols (device) -> packed bits (device, 4-byte aligned), the pass behind the chain kinds without a fused store stage
+COMMS_INTERNAL comms_status_t sym_to_bits_launch(const comms_c32* d_sym, size_t n_sym, const SymTable& t, uint8_t* d_out, hipStream_t s);
 
 // Base of every node handle: device + own stream + scratch for host-pointer runs.
 // Streams of handles and host-graph nodes come from a per-device pool and go back to it instead of being destroyed

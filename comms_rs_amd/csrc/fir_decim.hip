@@ -21,6 +21,7 @@
 #include <hip/hip_ext.h>
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -115,6 +116,12 @@ struct DecimArgs {
     long long n_chunks;            // runs
     float2 step_h[4];              // e^{i * 64 (i - HR) * dphi}, halo row i
 };
+// fir_decim_kernel with hard-decision bits out of its store stage (comms_chain_set_output_format): the same arguments
+// with the constellation behind them, so that the other instantiations keep their kernel-argument layout
+struct DecimBitsArgs : DecimArgs {
+    SymTable sym;
+};
+static_assert(sizeof(DecimBitsArgs) <= 4096, "kernel arguments beyond 4 KiB");
 
 constexpr double kTwoPiD = 2.0 * 3.14159265358979323846264338327950288;
 
@@ -150,9 +157,11 @@ __device__ __forceinline__ void lds_barrier() {  // (kept light: nothing global 
 
 // PRE: the mixer sits in front of the FIR (samples are mixed on their way into LDS); otherwise it
 // follows the FIR (or is absent).
-template <int R, int OPL, bool REAL, bool PRE, int TILE = DC_TILE, int CHX = 0>
-__global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::template waves_per_simd<PRE>())) void fir_decim_kernel(const DecimArgs a) {
+// A = DecimBitsArgs: hard-decision bits instead of Complex<f32> outputs (no FM demod in that form).
+template <int R, int OPL, bool REAL, bool PRE, int TILE = DC_TILE, int CHX = 0, class A = DecimArgs>
+__global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::template waves_per_simd<PRE>())) void fir_decim_kernel(const A a) {
     using G = DcGeom<R, OPL, TILE>;
+    constexpr bool kBits = !std::is_same<A, DecimArgs>::value;
     constexpr int PR = G::PR, S = G::S, WG = G::WG, HROWS = G::HROWS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     cf* sh = reinterpret_cast<cf*>(smem);  // [PR][S]
@@ -452,6 +461,28 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
             if (l == 63) sh_y[w] = y[OPL - 1];
         }
         lds_barrier();  // sh_y visible; every lane is done reading the staged tile
+        if constexpr (kBits) {
+            // hard decisions of the values the c32 form stores, packed LSB first: output j is stream bits k j ... k j + k - 1.
+            // A tile starts on a 64-byte boundary (512 outputs), so groups of 32 / (OPL k) lanes make whole 32-bit words:
+            // OR-ed across the group, stored by its first lane (16 B per wave and tile at k = 1, 32 at k = 2).  Outputs past
+            // the end add zero bits; the last word stops at the last byte.
+            const long long n_out = static_cast<long long>(a.n_out);
+            const size_t n_bytes = (static_cast<size_t>(n_out) * static_cast<size_t>(a.sym.k) + 7) / 8;
+            uint8_t* o = static_cast<uint8_t*>(a.out);
+            auto emit = [&](auto kc) __attribute__((always_inline)) {
+                constexpr int K = decltype(kc)::value, GL = 32 / (OPL * K);
+                unsigned bits = 0;
+#pragma unroll
+                for (int c = 0; c < OPL; ++c)
+                    if (j0 + c < n_out) bits |= sym_decide<K>(y[c], a.sym.c) << (K * c);
+                bits = bits_gather<GL>(bits << (OPL * K * (l % GL)));
+                if (l % GL == 0 && j0 < n_out) bits_store_word(o, static_cast<size_t>(j0) * K / 8, n_bytes, bits);
+            };
+            if (a.sym.k == 1)
+                emit(std::integral_constant<int, 1>{});
+            else
+                emit(std::integral_constant<int, 2>{});
+        } else
         if (fm) {
             float2 p0 = make_float2(__shfl_up(y[OPL - 1].x, 1), __shfl_up(y[OPL - 1].y, 1));
             if (l == 0 && w > 0) p0 = sh_y[w - 1];
@@ -773,8 +804,8 @@ static comms_status_t launch_decim_wave_v(const DecimArgs& a, hipStream_t s) {
     return launch_ok("fir_decim_wave_kernel");
 }
 
-template <int R, int OPL, bool REAL, bool PRE, int TILE = DC_TILE, int CHX = 0>
-static comms_status_t launch_decim_v(const DecimArgs& a, hipStream_t s) {
+template <int R, int OPL, bool REAL, bool PRE, int TILE = DC_TILE, int CHX = 0, class A = DecimArgs>
+static comms_status_t launch_decim_v(const A& a, hipStream_t s) {
     using G = DcGeom<R, OPL, TILE>;
     constexpr size_t lds = G::LDS;
     // persistent grid: one workgroup per slot of the chip; tile b, b + slots, ... (or a contiguous run) each
@@ -782,9 +813,9 @@ static comms_status_t launch_decim_v(const DecimArgs& a, hipStream_t s) {
     const unsigned blocks = static_cast<unsigned>(a.n_tiles < slots ? a.n_tiles : slots);
     static DeviceOnce attr_once;
     if (attr_once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_decim_kernel<R, OPL, REAL, PRE, TILE, CHX>),
+        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_decim_kernel<R, OPL, REAL, PRE, TILE, CHX, A>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    DecimArgs b = a;
+    A b = a;
     if (a.interleave) {
         // a workgroup's next tile is `blocks` tiles on: the per-step rotor of its tile-wide phase follows the grid
         const uint64_t ts = static_cast<uint64_t>(TILE) - ((a.mode & COMMS_CHAIN_FM) ? 1 : 0);
@@ -793,9 +824,9 @@ static comms_status_t launch_decim_v(const DecimArgs& a, hipStream_t s) {
     hipEvent_t ea = g_decim_ev_start, eb = g_decim_ev_stop;
     g_decim_ev_start = g_decim_ev_stop = nullptr;
     if (ea)
-        hipExtLaunchKernelGGL((fir_decim_kernel<R, OPL, REAL, PRE, TILE, CHX>), dim3(blocks), dim3(G::WG), static_cast<uint32_t>(lds), s, ea, eb, 0u, b);
+        hipExtLaunchKernelGGL((fir_decim_kernel<R, OPL, REAL, PRE, TILE, CHX, A>), dim3(blocks), dim3(G::WG), static_cast<uint32_t>(lds), s, ea, eb, 0u, b);
     else
-        fir_decim_kernel<R, OPL, REAL, PRE, TILE, CHX><<<dim3(blocks), dim3(G::WG), lds, s>>>(b);
+        fir_decim_kernel<R, OPL, REAL, PRE, TILE, CHX, A><<<dim3(blocks), dim3(G::WG), lds, s>>>(b);
     return launch_ok("fir_decim_kernel");
 }
 
@@ -857,6 +888,19 @@ static comms_status_t launch_decim_real(const DecimArgs& a, hipStream_t s) {
     return (a.mode & COMMS_CHAIN_PRE) ? launch_decim_v<R, 2, true, true>(a, s) : launch_decim_v<R, 2, true, false>(a, s);
 }
 
+// the bits form: two outputs per lane, 512-output tiles, every rate of the switch below (11 / 13 / 15: real taps only)
+template <int R>
+static comms_status_t launch_decim_bits(const DecimBitsArgs& a, bool real, hipStream_t s) {
+    const bool pre = (a.mode & COMMS_CHAIN_PRE) != 0;
+    if constexpr (R != 11 && R != 13 && R != 15) {
+        if (!real)
+            return pre ? launch_decim_v<R, 2, false, true, DC_TILE, 0, DecimBitsArgs>(a, s)
+                       : launch_decim_v<R, 2, false, false, DC_TILE, 0, DecimBitsArgs>(a, s);
+    }
+    return pre ? launch_decim_v<R, 2, true, true, DC_TILE, 0, DecimBitsArgs>(a, s)
+               : launch_decim_v<R, 2, true, false, DC_TILE, 0, DecimBitsArgs>(a, s);
+}
+
 }  // namespace comms
 
 using namespace comms;
@@ -904,9 +948,12 @@ int32_t comms_fir_decim_supported(const comms_fir_t* h, uint32_t rate) {
     return comms_fir_decim_supported_for(h, rate, 0, 1);
 }
 
-comms_status_t comms_fir_run_decim_dev(comms_fir_t* h, const void* d_in, size_t n, void* d_out, int32_t mode,
-                                       uint64_t turns0, uint64_t frac, uint32_t rate, const void* fm_prev,
-                                       void* fm_prev_new, void* stream) {
+// bits: hard-decision output (comms_fir_run_decim_bits_dev), or NULL for Complex<f32> / FM
+// (and c32_scratch: n / rate Complex<f32>, 16-byte aligned, where the wave-private kernel writes a call it takes -- it has no
+// decision stage -- before the decision pass turns them into bits)
+static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void* d_out, int32_t mode, uint64_t turns0,
+                                uint64_t frac, uint32_t rate, const void* fm_prev, void* fm_prev_new, const SymTable* bits,
+                                void* c32_scratch, void* stream) {
     COMMS_ARG(h != nullptr, "handle is NULL");
     COMMS_ARG((d_in && d_out) || !n, "NULL device pointer");
     COMMS_ARG(comms_fir_decim_supported(h, rate) != 0,
@@ -917,15 +964,17 @@ comms_status_t comms_fir_run_decim_dev(comms_fir_t* h, const void* d_in, size_t 
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
     const size_t in_elem = in_elem_bytes(h->in_fmt);
-    COMMS_ARG(!ranges_overlap(d_in, n * in_elem, d_out, (n / rate) * ((mode & COMMS_CHAIN_FM) ? 4 : 8)),
-              "the decimating chain cannot run in place");
+    const size_t out_bytes = bits ? ((n / rate) * static_cast<size_t>(bits->k) + 7) / 8 : (n / rate) * ((mode & COMMS_CHAIN_FM) ? 4 : 8);
+    COMMS_ARG(!ranges_overlap(d_in, n * in_elem, d_out, out_bytes), "the decimating chain cannot run in place");
+    COMMS_ARG(!bits || !(mode & COMMS_CHAIN_FM), "no bits output with FM demod");
+    COMMS_ARG(!bits || (reinterpret_cast<uintptr_t>(d_out) & 3) == 0, "bits output must be 4-byte aligned");
     COMMS_ARG((reinterpret_cast<uintptr_t>(d_in) & (in_elem - 1)) == 0, "input must be aligned to one IQ sample");
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
     const bool real = h->real_taps;
     const int R = static_cast<int>(rate), N = h->n_eff;
-    const int opl = (R <= 8 && R % 2 == 0) ? decim_opl(real, (N + R - 1) / R) : 2;  // (four outputs per lane: even R up to 8)
-    const int tile = decim_tile(real, R, opl);
+    const int opl = !bits && (R <= 8 && R % 2 == 0) ? decim_opl(real, (N + R - 1) / R) : 2;  // (four outputs per lane: even R up to 8)
+    const int tile = bits ? DC_TILE : decim_tile(real, R, opl);
     const int PR = opl * R, WG = tile / opl;
     DecimArgs a{};
     a.in = d_in;
@@ -1012,14 +1061,16 @@ comms_status_t comms_fir_run_decim_dev(comms_fir_t* h, const void* d_in, size_t 
     // samples, 15 / 31 / 47 / 63 real taps: rate 2 41.1 / 50.4 / 55.3 / 61.8 -> 35.1 / 47.0 / 51.6 / 59.2 us, rate 4 level up to 47 taps,
     // 35.1 -> 32.3 at 63 (scripts/time_rate2.py)
     static const int wave_r24 = diag_knob("COMMS_DECIM_WAVE_R24", 1);
-    if (wave_knob && (R == 8 || (wave_r24 && (R == 2 || R == 4))) && h->in_fmt == COMMS_IQ_C32 && opl == 2 && tile == DC_TILE && a.hlq * PR <= 128 &&
-        (reinterpret_cast<uintptr_t>(d_out) & 15) == 0) {  // (its stores are 8 / 16 bytes per lane)
+    void* wave_out = bits ? c32_scratch : d_out;
+    if (wave_out && wave_knob && (R == 8 || (wave_r24 && (R == 2 || R == 4))) && h->in_fmt == COMMS_IQ_C32 && opl == 2 && tile == DC_TILE && a.hlq * PR <= 128 &&
+        (reinterpret_cast<uintptr_t>(wave_out) & 15) == 0) {  // (its stores are 8 / 16 bytes per lane)
         constexpr int HR = 2;
         const long long tiles = static_cast<long long>((a.n_out + 127) / 128);
         const long long waves = 16 * static_cast<long long>(kNumCU);  // single-wave workgroups, 10240 B of LDS each
         const long long nt = (tiles + waves - 1) / waves;
         const bool balanced = tiles >= waves && nt * waves * 100 <= tiles * 104;
         if (balanced || wave_knob == 2) {
+            a.out = wave_out;
             a.nt_chunk = static_cast<int>(nt < 1 ? 1 : nt);
             static const int ntc_div = diag_knob("COMMS_DECIM_WAVE_SPLIT", COMMS_DECIM_WAVE_SPLIT_DEFAULT);  // runs per wave (trial)
             if (ntc_div > 1 && a.nt_chunk % ntc_div == 0) a.nt_chunk /= ntc_div;
@@ -1057,8 +1108,25 @@ comms_status_t comms_fir_run_decim_dev(comms_fir_t* h, const void* d_in, size_t 
 #undef COMMS_DW
             COMMS_TRY(st);
             h->cur ^= 1;
+            if (bits) return sym_to_bits_launch(static_cast<const comms_c32*>(wave_out), a.n_out, *bits, static_cast<uint8_t*>(d_out), s);
             return COMMS_OK;
         }
+    }
+    if (bits) {
+        DecimBitsArgs b;
+        static_cast<DecimArgs&>(b) = a;
+        b.sym = *bits;
+        switch (R) {
+#define COMMS_DB(RV) \
+    case RV: st = launch_decim_bits<RV>(b, real, s); break;
+            COMMS_DB(2) COMMS_DB(3) COMMS_DB(4) COMMS_DB(5) COMMS_DB(6) COMMS_DB(7) COMMS_DB(8) COMMS_DB(9) COMMS_DB(10)
+            COMMS_DB(11) COMMS_DB(12) COMMS_DB(13) COMMS_DB(14) COMMS_DB(15) COMMS_DB(16)
+#undef COMMS_DB
+            default: return fail(COMMS_ERR_ARG, "no decimating kernel for rate %d", R);
+        }
+        COMMS_TRY(st);
+        h->cur ^= 1;
+        return COMMS_OK;
     }
     switch (R) {
         case 2: st = launch_decim<2>(a, real, opl, tile, s); break;
@@ -1081,6 +1149,20 @@ comms_status_t comms_fir_run_decim_dev(comms_fir_t* h, const void* d_in, size_t 
     COMMS_TRY(st);
     h->cur ^= 1;
     return COMMS_OK;
+}
+
+comms_status_t comms_fir_run_decim_dev(comms_fir_t* h, const void* d_in, size_t n, void* d_out, int32_t mode,
+                                       uint64_t turns0, uint64_t frac, uint32_t rate, const void* fm_prev,
+                                       void* fm_prev_new, void* stream) {
+    return run_decim(h, d_in, n, d_out, mode, turns0, frac, rate, fm_prev, fm_prev_new, nullptr, nullptr, stream);
+}
+
+comms_status_t comms_fir_run_decim_bits_dev(comms_fir_t* h, const void* d_in, size_t n, void* d_out, int32_t mode,
+                                            uint64_t turns0, uint64_t frac, uint32_t rate, const void* sym_table,
+                                            void* c32_scratch, void* stream) {
+    COMMS_ARG(sym_table != nullptr, "NULL constellation table");
+    return run_decim(h, d_in, n, d_out, mode, turns0, frac, rate, nullptr, nullptr, static_cast<const SymTable*>(sym_table),
+                     c32_scratch, stream);
 }
 
 }  // extern "C"

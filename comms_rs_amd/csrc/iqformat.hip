@@ -92,6 +92,74 @@ __global__ __launch_bounds__(256) void psk_bit_kernel(const uint8_t* __restrict_
         out[i] = QPSK ? qpsk_c16(in[i]) : bpsk_c16(in[i]);
 }
 
+// Hard decisions (comms_sym_to_bits; the pass behind the chain kinds without a fused store stage): Complex<f32> symbols ->
+// packed bits, LSB first, by the rule of common.hpp's sym_decide.  8 B in, k/8 B out per symbol: a lane decides two
+// consecutive symbols (one 16-byte load where the input allows it), groups of 32 / 2k lanes OR their bits into one 32-bit
+// word, stored by the group's first lane.  Symbols past n add zero bits; the last word stops at the last byte.
+template <int K>
+__global__ __launch_bounds__(256) void sym_to_bits_kernel(const float2* __restrict__ sym, size_t n, const SymTable t,
+                                                          uint8_t* __restrict__ out) {
+    constexpr int GL = 32 / (2 * K);
+    const size_t n_bytes = (n * K + 7) / 8;
+    const size_t n_lanes = (((n + 1) / 2) + 63) & ~static_cast<size_t>(63);  // whole waves: every lane of one takes part in the OR
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    const bool wide = (reinterpret_cast<uintptr_t>(sym) & 15) == 0;
+    const int l = threadIdx.x & 63;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n_lanes; i += stride) {
+        const size_t j = 2 * i;
+        unsigned bits = 0;
+        if (j + 1 < n) {
+            float2 y0, y1;
+            if (wide) {
+                const float4 q = reinterpret_cast<const float4*>(sym)[i];
+                y0 = make_float2(q.x, q.y);
+                y1 = make_float2(q.z, q.w);
+            } else {
+                y0 = sym[j];
+                y1 = sym[j + 1];
+            }
+            bits = sym_decide<K>(y0, t.c) | (sym_decide<K>(y1, t.c) << K);
+        } else if (j < n) {
+            bits = sym_decide<K>(sym[j], t.c);
+        }
+        bits = bits_gather<GL>(bits << (2 * K * (l % GL)));
+        if (l % GL == 0 && j < n) bits_store_word(out, j * K / 8, n_bytes, bits);
+    }
+}
+
+// popcount(a XOR b) over the first n_bits stream bits: 16-byte words where both inputs allow it, bytes otherwise, the
+// partial last byte masked; a wave reduction, one 64-bit atomic add per workgroup
+__global__ __launch_bounds__(256) void bit_errors_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n_bits,
+                                                         unsigned long long* __restrict__ count) {
+    const size_t n_full = static_cast<size_t>(n_bits / 8);
+    const unsigned rb = static_cast<unsigned>(n_bits % 8);
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    unsigned long long acc = 0;
+    size_t done = 0;
+    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0) {
+        const uint4* a4 = reinterpret_cast<const uint4*>(a);
+        const uint4* b4 = reinterpret_cast<const uint4*>(b);
+        const size_t nw = n_full / 16;
+        for (size_t i = tid; i < nw; i += stride) {
+            const uint4 x = a4[i], y = b4[i];
+            acc += __popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w);
+        }
+        done = nw * 16;
+    }
+    for (size_t i = done + tid; i < n_full; i += stride) acc += __popc(static_cast<unsigned>(a[i] ^ b[i]));
+    if (rb && tid == 0) acc += __popc(static_cast<unsigned>(a[n_full] ^ b[n_full]) & ((1u << rb) - 1u));
+#pragma unroll
+    for (int sft = 32; sft >= 1; sft >>= 1) acc += __shfl_xor(acc, sft);
+    __shared__ unsigned long long part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long sum = part[0] + part[1] + part[2] + part[3];
+        if (sum) atomicAdd(count, sum);
+    }
+}
+
 static unsigned conv_grid(size_t n) {
     size_t b = (n + 255) / 256;
     if (b > 8u * kNumCU) b = 8u * kNumCU;
@@ -107,6 +175,30 @@ static comms_status_t via_device(const void* in, size_t n, size_t in_e, void* ou
     COMMS_TRY(thread_handle(device, &h));
     return h->run_host_units(in, n * in_e, in_e, out, n * out_e, out_e,
                              [&](void* d_in, void* d_out, size_t ib, size_t) { return run(d_in, d_out, ib / in_e, h->stream); });
+}
+
+// digital.rs: bpsk_bit_mod (:6-14), qpsk_bit_mod (:24-36) -- the pulse node's COMMS_SYM_BITS defaults
+comms_status_t sym_table(int32_t bits_per_sym, const comms_c32* constellation, SymTable* out) {
+    COMMS_ARG(bits_per_sym == 1 || bits_per_sym == 2, "bits_per_sym must be 1 or 2 (got %d)", bits_per_sym);
+    static const float2 kBpsk[2] = {{1.f, 0.f}, {-1.f, 0.f}};
+    static const float2 kQpsk[4] = {{1.f, 1.f}, {-1.f, 1.f}, {1.f, -1.f}, {-1.f, -1.f}};
+    SymTable t{};
+    t.k = bits_per_sym;
+    for (int v = 0; v < (1 << bits_per_sym); ++v)
+        t.c[v] = constellation ? make_float2(constellation[v].re, constellation[v].im) : bits_per_sym == 1 ? kBpsk[v] : kQpsk[v];
+    *out = t;
+    return COMMS_OK;
+}
+
+comms_status_t sym_to_bits_launch(const comms_c32* d_sym, size_t n_sym, const SymTable& t, uint8_t* d_out, hipStream_t s) {
+    if (!n_sym) return COMMS_OK;
+    const float2* in = reinterpret_cast<const float2*>(d_sym);
+    const unsigned grid = conv_grid((n_sym + 1) / 2);
+    if (t.k == 1)
+        sym_to_bits_kernel<1><<<dim3(grid), dim3(256), 0, s>>>(in, n_sym, t, d_out);
+    else
+        sym_to_bits_kernel<2><<<dim3(grid), dim3(256), 0, s>>>(in, n_sym, t, d_out);
+    return launch_ok("sym_to_bits_kernel");
 }
 
 }  // namespace comms
@@ -191,6 +283,76 @@ comms_status_t comms_iq_u8_to_c32(const uint8_t* in, size_t n, comms_c32* out, i
     return via_device(in, n, 2, out, 8, device, [&](void* a, void* b, size_t m, void* st) {
         return comms_iq_u8_to_c32_dev(static_cast<const uint8_t*>(a), m, static_cast<comms_c32*>(b), device, st);
     });
+}
+
+// ---- hard decisions and bit errors
+comms_status_t comms_sym_to_bits_dev(const comms_c32* d_sym, size_t n_sym, int32_t bits_per_sym, const comms_c32* constellation,
+                                     uint8_t* d_out, int32_t device, void* stream) {
+    COMMS_ARG((d_sym && d_out) || !n_sym, "NULL device pointer");
+    COMMS_ARG(n_sym <= SIZE_MAX / 16, "n_sym too large");
+    SymTable t;
+    COMMS_TRY(sym_table(bits_per_sym, constellation, &t));
+    COMMS_ARG((reinterpret_cast<uintptr_t>(d_sym) & 7) == 0, "symbols must be 8-byte aligned");
+    COMMS_ARG((reinterpret_cast<uintptr_t>(d_out) & 3) == 0, "d_out must be 4-byte aligned");
+    COMMS_ARG(!ranges_overlap(d_sym, n_sym * 8, d_out, (n_sym * bits_per_sym + 7) / 8), "the decision cannot run in place");
+    COMMS_TRY(use_device(device));
+    return sym_to_bits_launch(d_sym, n_sym, t, d_out, reinterpret_cast<hipStream_t>(stream));
+}
+comms_status_t comms_sym_to_bits(const comms_c32* sym, size_t n_sym, int32_t bits_per_sym, const comms_c32* constellation,
+                                 uint8_t* out, int32_t device) {
+    COMMS_ARG((sym && out) || !n_sym, "NULL host pointer");
+    COMMS_ARG(n_sym <= SIZE_MAX / 16, "n_sym too large");
+    SymTable t;
+    COMMS_TRY(sym_table(bits_per_sym, constellation, &t));
+    COMMS_TRY(use_device(device));
+    if (!n_sym) return COMMS_OK;
+    Handle* h = nullptr;
+    COMMS_TRY(thread_handle(device, &h));
+    // chunks of 32 / k symbols = one whole output word each (the last chunk takes the rest)
+    const size_t per_word = static_cast<size_t>(32 / bits_per_sym);
+    return h->run_host_units(sym, n_sym * 8, per_word * 8, out, (n_sym * bits_per_sym + 7) / 8, 4,
+                             [&](void* d_in, void* d_out, size_t ib, size_t) {
+                                 return sym_to_bits_launch(static_cast<const comms_c32*>(d_in), ib / 8, t, static_cast<uint8_t*>(d_out), h->stream);
+                             });
+}
+
+comms_status_t comms_bit_errors_dev(const uint8_t* d_a, const uint8_t* d_b, uint64_t n_bits, uint64_t* out_errors, int32_t device,
+                                    void* stream) {
+    COMMS_ARG(out_errors != nullptr && ((d_a && d_b) || !n_bits), "NULL argument");
+    COMMS_ARG(device >= 0 && device < 64, "device index out of range");
+    COMMS_TRY(use_device(device));
+    *out_errors = 0;
+    if (!n_bits) return COMMS_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // per-thread, per-device counter, allocated once (every call ends with a stream sync, as the block estimators)
+    static thread_local unsigned long long* tl_count[64] = {};
+    if (!tl_count[device]) COMMS_HIP_TRY(hipMalloc(&tl_count[device], sizeof(unsigned long long)));
+    unsigned long long* d_count = tl_count[device];
+    COMMS_HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+    const uint64_t n_bytes = (n_bits + 7) / 8;
+    bit_errors_kernel<<<dim3(conv_grid(static_cast<size_t>((n_bytes + 15) / 16))), dim3(256), 0, s>>>(d_a, d_b, n_bits, d_count);
+    COMMS_TRY(launch_ok("bit_errors_kernel"));
+    unsigned long long count = 0;
+    hipError_t e = hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "bit error count copy-back: %s", hipGetErrorString(e));
+    *out_errors = count;
+    return COMMS_OK;
+}
+comms_status_t comms_bit_errors(const uint8_t* a, const uint8_t* b, uint64_t n_bits, uint64_t* out_errors, int32_t device) {
+    COMMS_ARG(out_errors != nullptr && ((a && b) || !n_bits), "NULL argument");
+    COMMS_TRY(use_device(device));
+    *out_errors = 0;
+    if (!n_bits) return COMMS_OK;
+    Handle* h = nullptr;
+    COMMS_TRY(thread_handle(device, &h));
+    const size_t n_bytes = static_cast<size_t>((n_bits + 7) / 8);
+    const size_t off = (n_bytes + 255) & ~static_cast<size_t>(255);  // b behind a, both 16-byte aligned
+    COMMS_TRY(h->in_scratch.reserve(2 * off));
+    uint8_t* d = static_cast<uint8_t*>(h->in_scratch.p);
+    COMMS_HIP_TRY(hipMemcpyAsync(d, a, n_bytes, hipMemcpyHostToDevice, h->stream));
+    COMMS_HIP_TRY(hipMemcpyAsync(d + off, b, n_bytes, hipMemcpyHostToDevice, h->stream));
+    return comms_bit_errors_dev(d, d + off, n_bits, out_errors, device, h->stream);
 }
 
 // ---- digital modulation

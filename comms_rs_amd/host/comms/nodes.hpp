@@ -435,6 +435,93 @@ private:
     uint64_t start_ = 0;  // register at buf_[0]
 };
 
+// ---------------------------------------------------------------- a digital link from bits to bits (additional nodes)
+// Transmit: packed bits (LSB first, bits_per_sym = 1 or 2 per symbol, whole bytes per message) -> constellation -> pulse
+// shaping -> mixer -> (scale * y) as i16, one launch per message (comms_pulse_set_input_format / _set_output_format).
+class PulseBitsNode : public DeriveNode<PulseBitsNode> {
+public:
+    NodeReceiver<std::vector<uint8_t>> input;
+    NodeSender<std::vector<Complex16>> output;
+    PulseBitsNode(const std::vector<Complex32>& taps, size_t sam_per_sym, int bits_per_sym, double dphase, float scale,
+                  const std::vector<Complex32>& constellation = {}, int device = 0)
+        : sps_(sam_per_sym), k_(bits_per_sym) {
+        throw_on(comms_pulse_create(c32(taps.data()), taps.size(), sam_per_sym, device, &h_), "PulseBitsNode::new");
+        try {
+            throw_on(comms_pulse_set_mixer(h_, dphase, 0.0), "PulseBitsNode::new");
+            throw_on(comms_pulse_set_input_format(h_, COMMS_SYM_BITS, bits_per_sym, constellation.empty() ? nullptr : c32(constellation.data())),
+                     "PulseBitsNode::new");
+            throw_on(comms_pulse_set_output_format(h_, COMMS_IQ_I16, scale), "PulseBitsNode::new");
+        } catch (...) {
+            comms_pulse_destroy(h_);
+            throw;
+        }
+    }
+    PulseBitsNode(PulseBitsNode&& o) noexcept
+        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sps_(o.sps_), k_(o.k_) { o.h_ = nullptr; }
+    ~PulseBitsNode() { comms_pulse_destroy(h_); }
+    Result<std::vector<Complex16>> run(const std::vector<uint8_t>& packed) {
+        const size_t n_sym = packed.size() * 8 / static_cast<size_t>(k_);
+        std::vector<Complex16> out(n_sym * sps_);
+        comms_status_t st = comms_pulse_run(h_, reinterpret_cast<const comms_c32*>(packed.data()), n_sym, c32_as(out.data()));
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    static comms_c32* c32_as(Complex16* p) { return reinterpret_cast<comms_c32*>(p); }
+    comms_pulse_t* h_ = nullptr;
+    size_t sps_;
+    int k_;
+};
+
+// Receive: i16 samples -> mixer -> matched FIR -> keep every rate-th -> hard decisions -> packed bits (LSB first), one chain
+// (comms_chain_set_input_format / _set_output_format): ceil(n / rate * bits_per_sym / 8) bytes per message, each message
+// from bit 0 of its first byte -- whole bytes when n is a multiple of 8 * rate / bits_per_sym.
+class ChainBitsNode : public DeriveNode<ChainBitsNode> {
+public:
+    NodeReceiver<std::vector<Complex16>> input;
+    NodeSender<std::vector<uint8_t>> output;
+    ChainBitsNode(double dphase, double phase, const std::vector<Complex32>& taps, size_t rate, int bits_per_sym, float in_scale,
+                  const std::vector<Complex32>& constellation = {}, bool mixer_after_fir = false, int device = 0)
+        : rate_(rate), k_(bits_per_sym) {
+        throw_on(comms_chain_create_ex(dphase, phase, c32(taps.data()), taps.size(), rate, mixer_after_fir ? COMMS_CHAIN_MIXER_AFTER_FIR : 0,
+                                       device, &h_),
+                 "ChainBitsNode::new");
+        try {
+            throw_on(comms_chain_set_input_format(h_, COMMS_IQ_I16, in_scale), "ChainBitsNode::new");
+            throw_on(comms_chain_set_output_format(h_, COMMS_SYM_BITS, bits_per_sym, constellation.empty() ? nullptr : c32(constellation.data())),
+                     "ChainBitsNode::new");
+        } catch (...) {
+            comms_chain_destroy(h_);
+            throw;
+        }
+    }
+    ChainBitsNode(ChainBitsNode&& o) noexcept
+        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), rate_(o.rate_), k_(o.k_) { o.h_ = nullptr; }
+    ~ChainBitsNode() { comms_chain_destroy(h_); }
+    Result<std::vector<uint8_t>> run(const std::vector<Complex16>& in) {
+        if (rate_ == 0 || in.size() % rate_) return NodeError::DataError;
+        std::vector<uint8_t> out((in.size() / rate_ * static_cast<size_t>(k_) + 7) / 8);
+        comms_status_t st = comms_chain_run(h_, reinterpret_cast<const comms_c32*>(in.data()), in.size(), out.data());
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    int fused_kind() const {  // as ChainNodeDev::fused_kind
+        int32_t f = 0;
+        comms_chain_is_fused(h_, &f);
+        return f;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_chain_t* h_ = nullptr;
+    size_t rate_;
+    int k_;
+};
+
 // ---------------------------------------------------------------- mixer
 class MixerNode : public DeriveNode<MixerNode> {
 public:

@@ -650,9 +650,37 @@ class ChainNode(_Handle):
         self._fmt = fmt
         return self
 
+    _out_bits = 0
+
+    def set_output_format(self, fmt, bits_per_sym=1, constellation=None):
+        """"bits": run() returns hard decisions of the decimated samples as packed bits (np.uint8, LSB first,
+        ceil(n / rate * bits_per_sym / 8) bytes; the inverse of PulseNode.set_input_format("bits", ...)), nearest of
+        the 2**bits_per_sym points of `constellation` (None = digital.rs's tables; see comms_sym_to_bits for the rule);
+        "c32" restores the default.  No FM chains.  History and phase carry across a switch."""
+        if fmt == "c32":
+            check(lib().comms_chain_set_output_format(self._h, _lib.SYM_C32, 0, None))
+            self._out_bits = 0
+            return self
+        if fmt != "bits":
+            raise ValueError("output format must be 'c32' or 'bits' (got %r)" % (fmt,))
+        cons = _constellation(constellation, bits_per_sym)
+        check(lib().comms_chain_set_output_format(self._h, _lib.SYM_BITS, int(bits_per_sym), None if cons is None else _ptr(cons)))
+        self._out_bits = int(bits_per_sym)
+        return self
+
+    def out_bytes(self, n):
+        """Bytes of run's output for n input samples."""
+        n_dec = int(n) // self.rate
+        if self._out_bits:
+            return (n_dec * self._out_bits + 7) // 8
+        return n_dec * (4 if self.fm_demod else 8)
+
     def run(self, x):
         x, n = _as_input(x, self._fmt)
-        out = np.empty(n // self.rate, np.float32 if self.fm_demod else np.complex64)
+        if self._out_bits:
+            out = np.empty(self.out_bytes(n), np.uint8)
+        else:
+            out = np.empty(n // self.rate, np.float32 if self.fm_demod else np.complex64)
         check(lib().comms_chain_run(self._h, _ptr(x), n, _ptr(out)))
         return out
 
@@ -779,6 +807,50 @@ def bpsk_bit_mod(x, device=0):
 def qpsk_bit_mod(x, device=0):
     """digital.rs:24-36 over values 0..3 (anything else: CommsError, as the reference's None)."""
     return _psk("comms_qpsk_bit_mod", x, 1, device)
+
+
+# ------------------------------------------------------------------ hard decisions, bit errors
+def _constellation(constellation, bits_per_sym):
+    if constellation is None:
+        return None
+    cons = _as_c64(constellation).ravel()
+    if cons.size != 1 << int(bits_per_sym):
+        raise ValueError("the constellation holds 2**bits_per_sym points")
+    return cons
+
+
+def sym_to_bits(sym, bits_per_sym, constellation=None, device=0):
+    """Complex<f32> symbols -> packed hard-decision bits (np.uint8, LSB first, ceil(n * bits_per_sym / 8) bytes):
+    nearest of the 2**bits_per_sym points of `constellation` (None = digital.rs's tables), by comms_sym_to_bits's rule."""
+    s = _as_c64(sym).ravel()
+    cons = _constellation(constellation, bits_per_sym)
+    out = np.empty((s.size * int(bits_per_sym) + 7) // 8, np.uint8)
+    check(lib().comms_sym_to_bits(_ptr(s), s.size, int(bits_per_sym), None if cons is None else _ptr(cons), _ptr(out), device))
+    return out
+
+
+def sym_to_bits_dev(sym_ptr, n_sym, bits_per_sym, out_ptr, constellation=None, device=0, stream=0):
+    cons = _constellation(constellation, bits_per_sym)
+    check(lib().comms_sym_to_bits_dev(sym_ptr, int(n_sym), int(bits_per_sym), None if cons is None else _ptr(cons), out_ptr,
+                                      device, stream))
+
+
+def bit_errors(a, b, n_bits, device=0):
+    """popcount(a XOR b) over the first n_bits stream bits (LSB first) of two packed byte arrays, counted on the device."""
+    a = np.ascontiguousarray(a, dtype=np.uint8).ravel()
+    b = np.ascontiguousarray(b, dtype=np.uint8).ravel()
+    n_bits = int(n_bits)
+    if min(a.size, b.size) * 8 < n_bits:
+        raise ValueError("the arrays hold fewer than n_bits bits")
+    out = C.c_uint64()
+    check(lib().comms_bit_errors(_ptr(a), _ptr(b), n_bits, C.byref(out), device))
+    return out.value
+
+
+def bit_errors_dev(a_ptr, b_ptr, n_bits, device=0, stream=0):
+    out = C.c_uint64()
+    check(lib().comms_bit_errors_dev(a_ptr, b_ptr, int(n_bits), C.byref(out), device, stream))
+    return out.value
 
 
 # ------------------------------------------------------------------ PRNS source
