@@ -156,10 +156,9 @@ static ChainPlan plan_chain(const comms_fir* fir, size_t rate, int32_t flags) {
     // own kernel over the n / rate decimated samples.  That beats demodulating inside the overlap-save kernel at
     // every rate (2^24 samples, 127 taps: /2 85.8 against 95.9 us, /3 68 against 83, /8 60 against 82 -- the fused
     // form needs `rate` more halo samples per segment and an atan2 per output in a kernel short of issue slots) and
-    // has no limit on taps + rate; COMMS_CHAIN_FM_SEPARATE=0 brings the in-kernel form back for comparison.
-    static const int fm_sep = diag_knob("COMMS_CHAIN_FM_SEPARATE", 1);
-    const bool can_fuse = can_fuse_nofm && (!fm || (!fm_sep && rate <= 64 && n_taps + rate <= 257));
-    const bool can_hybrid = fm && can_fuse_nofm && !can_fuse;
+    // has no limit on taps + rate.
+    const bool can_fuse = can_fuse_nofm && !fm;
+    const bool can_hybrid = can_fuse_nofm && fm;
     // the time-domain kernel against what would run otherwise: an overlap-save fusion, or the four kernels in
     // series, which it beats up to many more MACs per input sample
     const int decim_ok = rate <= 16 ? comms_fir_decim_supported_for(fir, r32, fm ? 1 : 0, can_fuse || can_hybrid ? 1 : 0) : 0;

@@ -227,8 +227,8 @@ __device__ __forceinline__ cf os_table_rotor(unsigned u, const cf* sc) {
     return cmulf(tq, cf{cs, sn});
 }
 
-template <int WPS, class In = const float2*, bool DEC = false>
-__global__ __launch_bounds__(256, WPS) void fir_os4096_kernel(In in,
+template <class In = const float2*, bool DEC = false>
+__global__ __launch_bounds__(256, 3) void fir_os4096_kernel(In in,
                                                             const float2* __restrict__ hist,
                                                             int hist_len, float2* __restrict__ out,
                                                             size_t n, int hblk, size_t nseg,
@@ -405,14 +405,15 @@ struct WTables {
 
 // Optional stages fused around the 1024-point overlap-save FIR (comms_chain_*):
 //   MODE bit 0: mixer BEFORE the FIR (on load)      bit 1: mixer AFTER the FIR
-//   MODE bit 2: keep every `rate`-th output          bit 3: FM demod of the kept outputs
+//   MODE bit 2: keep every `rate`-th output
+// (FM chains run the demodulator as its own launch over the kept outputs: chain.hip, plan_chain)
 // The mixer rotor of sample i (relative to this call) is rot(turns0 + i*frac); a lane
 // evaluates it once per run with an f64 sincos, advances it per segment with one f64
 // rotor, and reaches the 16 rows of a segment with the wave-uniform f32 rotors
 // step_a[a] = e^{i*64a*dphi}.
 constexpr int CH_STAMP = 16;  // diagnostic: per-phase cycle stamps into fm_prev_new (scripts/stamp_fir.py)
 constexpr int CH_TRACE = 32;  // diagnostic: per-wave start / set-up / end times, production geometry (scripts/trace_fir.py)
-constexpr int CH_PRE = COMMS_CHAIN_PRE, CH_POST = COMMS_CHAIN_POST, CH_DEC = COMMS_CHAIN_DEC, CH_FM = COMMS_CHAIN_FM;
+constexpr int CH_PRE = COMMS_CHAIN_PRE, CH_POST = COMMS_CHAIN_POST, CH_DEC = COMMS_CHAIN_DEC;
 struct ChainArgs {
     uint64_t turns0, frac;
     double seg_c, seg_s;      // e^{i*768*dphi}
@@ -420,8 +421,8 @@ struct ChainArgs {
     unsigned rate;            // decimation rate (>= 1)
     unsigned q_a[16], r_a[16];  // (64*(a-4)) / rate and % rate for a = 4..15
     unsigned q_seg, r_seg;      // 768 / rate and 768 % rate
-    const float2* fm_prev;    // FM.prev before this call
-    float2* fm_prev_new;      //   ... and after it (ping-pong)
+    const float2* fm_prev;    // (unused: FM chains demodulate in a launch of their own)
+    float2* fm_prev_new;      // diagnostic modes (CH_STAMP, CH_TRACE): where the stamps go
 };
 constexpr double kTwoPiF = 2.0 * 3.14159265358979323846264338327950288;
 
@@ -722,16 +723,6 @@ __global__ __launch_bounds__(64 * WPB, MINW) void fir_os1024_kernel(In in,
 #pragma unroll
                 for (int a = 4; a < 16; ++a)
                     v[R16_POS(a)] = cmulf(v[R16_POS(a)], cmulf(rot, to_cf(ch.step_a[a])));
-                // FM demod of row 4 reaches back into the tail of row 3 (valid outputs of the previous
-                // segment's span, recomputed here): they must carry the mixer rotation too
-                if (MODE & CH_FM) v[R16_POS(3)] = cmulf(v[R16_POS(3)], cmulf(rot, to_cf(ch.step_a[3])));
-            }
-            // FM needs y[idx - rate]: lane l - rate of the same row, or the tail of row a-1
-            const int src = (l - static_cast<int>(ch.rate)) & 63;
-            float2 sh_prev = make_float2(0.f, 0.f);
-            if (MODE & CH_FM) {
-                const float2 y3 = to_f2(v[R16_POS(3)]);
-                sh_prev = make_float2(__shfl(y3.x, src), __shfl(y3.y, src));
             }
             // idx = nb + 64(a-4) + l; kept when idx % rate == 0, written at idx / rate
             // (nb + l) / rate and % rate: one 64-bit division per run, then per-segment increments
@@ -756,24 +747,7 @@ __global__ __launch_bounds__(64 * WPB, MINW) void fir_os1024_kernel(In in,
                     ++q;
                 }
                 const size_t idx = nb + 64 * (a - 4) + l;
-                float2 sh_cur = make_float2(0.f, 0.f);
-                if (MODE & CH_FM) {
-                    const float2 ya = to_f2(v[R16_POS(a)]);
-                    sh_cur = make_float2(__shfl(ya.x, src), __shfl(ya.y, src));
-                }
-                const float2 p_row = l >= static_cast<int>(ch.rate) ? sh_cur : sh_prev;
-                sh_prev = sh_cur;
-                if (r == 0 && idx < n) {
-                    const float2 y = to_f2(v[R16_POS(a)]);
-                    if (MODE & CH_FM) {
-                        float2 p = p_row;
-                        if (idx == 0) p = ch.fm_prev[0];
-                        reinterpret_cast<float*>(out)[q] = fm_step(y, p);
-                        if (idx + ch.rate >= n) ch.fm_prev_new[0] = y;  // last kept sample of the call
-                    } else {
-                        out[q] = y;
-                    }
-                }
+                if (r == 0 && idx < n) out[q] = to_f2(v[R16_POS(a)]);
             }
         }
         OS_STAMP(9)  // R16 + stores retired
@@ -798,10 +772,9 @@ __global__ __launch_bounds__(64 * WPB, MINW) void fir_os1024_kernel(In in,
 // (history) and its partial last one take the guarded path after the loop.
 // (Loading the NEXT segment's rows into spare registers before transforming this one -- the wait
 // then sits after the 16 - HR stores as a counted vmcnt -- was measured too: 3 us SLOWER at 2^24,
-// the 32 register moves per segment cost more than the covered latency.)
-#ifndef COMMS_OS1024_PREFETCH
-#define COMMS_OS1024_PREFETCH 0  // trial (round 5, second form): measured level or slower, see the loop
-#endif
+// the 32 register moves per segment cost more than the covered latency.  So was a second form with two register sets
+// taking turns, no moves: 255 taps 2^22 19.5 -> 20.8 us, 2^24 50.0 -> 52.1, 2^26 206.3 -> 206.5 -- this kernel's four
+// waves per SIMD already cover each other's loads; NOTES.md, round 5.)
 template <int HR, bool TRACE, class In = const float2*>
 __global__ __launch_bounds__(1024, 4) void fir_os1024_dyn_kernel(In in,
                                                                  const float2* __restrict__ hist, int hist_len,
@@ -857,23 +830,14 @@ __global__ __launch_bounds__(1024, 4) void fir_os1024_dyn_kernel(In in,
         for (int a = 0; a < 16; ++a) r[a] = to_cf(in[p + 64 * a]);
     };
     auto nostamp = [](int) {};
-#ifndef COMMS_OS1024_REG_TW
-#define COMMS_OS1024_REG_TW 1
-#endif
-    // The lane's column of the stage-2 twiddle table (bit 0) in registers instead of 30 LDS reads per segment: the tables are
+    // The lane's column of the stage-2 twiddle table in registers instead of 30 LDS reads per segment: the tables are
     // read-only, but the compiler must reload them for every segment; the kernel has 64 VGPRs to spare at its sixteen waves per
     // CU.  Same values, same arithmetic.  Three builds alternating launch by launch (scripts/build_variant.sh, ab_libs.py; 255
-    // taps): 2^22 samples 19.2 -> 18.8 us, 2^24 50.0 -> 49.3, 2^26 199.2 -> 198.7; with the stage-1 column as well (bit 1: 124
-    // VGPRs) 18.2 / 49.5 / 198.0 -- no better where it matters, not used.
+    // taps): 2^22 samples 19.2 -> 18.8 us, 2^24 50.0 -> 49.3, 2^26 199.2 -> 198.7; with the stage-1 column as well (124
+    // VGPRs) 18.2 / 49.5 / 198.0 -- no better where it matters, not used (t1r stays unset: os1024_core_rt<.., 1> never reads it).
     cf t1r[16], t2r[16];
-    if (COMMS_OS1024_REG_TW & 1) {
 #pragma unroll
-        for (int k = 1; k < 16; ++k) t2r[k] = tw2[k * 4 + (l >> 4)];
-    }
-    if (COMMS_OS1024_REG_TW & 2) {
-#pragma unroll
-        for (int k = 1; k < 16; ++k) t1r[k] = tw1[k * 64 + l];
-    }
+    for (int k = 1; k < 16; ++k) t2r[k] = tw2[k * 4 + (l >> 4)];
 
     size_t count = 0;
     cf v[16];
@@ -894,7 +858,7 @@ __global__ __launch_bounds__(1024, 4) void fir_os1024_dyn_kernel(In in,
             load_rows(in, nb, l, n, nw);
 #pragma unroll
             for (int a = HR; a < 16; ++a) v[a] = nw[a - HR];
-            os1024_core_rt<64, COMMS_OS1024_REG_TW>(v, lds, tw1, hsp, tw2, l, nostamp, -1, t1r, t2r);
+            os1024_core_rt<64, 1>(v, lds, tw1, hsp, tw2, l, nostamp, -1, t1r, t2r);
 #pragma unroll
             for (int a = HR; a < 16; ++a) {
                 const size_t i = nb + 64 * (a - HR) + l;
@@ -903,48 +867,17 @@ __global__ __launch_bounds__(1024, 4) void fir_os1024_dyn_kernel(In in,
             ++count;
         }
     }
-#if COMMS_OS1024_PREFETCH
-    // TRIAL, not the product (-DCOMMS_OS1024_PREFETCH=1; scripts/build_variant.sh + ab_libs.py).  Two register sets taking
-    // turns (the kernel needs ~64 of the 128 VGPRs its sixteen waves per CU may have): the NEXT segment's rows are requested
-    // before this one is transformed, so a wave's own load latency leaves its critical path; those loads are OLDER than this
-    // segment's twelve stores in the in-order vmcnt queue, so the wait for them leaves the stores in flight; no register
-    // moves (round 1's attempt kept one set and moved the prefetched rows into it: 3 us slower).  Measured, the two builds
-    // alternating launch by launch: 255 taps 2^22 19.5 -> 20.8 us, 2^24 50.0 -> 52.1, 2^26 206.3 -> 206.5, 2^28 801 -> 805; 127
-    // taps 2^24 47.6 -> 49.2.  The same reordering is worth 9 % on fir_poly8_kernel, whose waves are short of work while they
-    // wait; this kernel's four waves per SIMD already cover each other's loads -- what bounds it is what the memory system
-    // gives its 1.33x-overlapped read stream and its write stream together (NOTES.md).
-    cf w[16];
-    auto finish = [&](size_t sg, cf (&r)[16]) {
-        os1024_core_rt<64, COMMS_OS1024_REG_TW>(r, lds, tw1, hsp, tw2, l, nostamp, -1, t1r, t2r);
-        float2* o = out + sg * WVK + l;
-#pragma unroll
-        for (int a = HR; a < 16; ++a) o[64 * (a - HR)] = to_f2(r[R16_POS(a)]);
-        ++count;
-    };
-    size_t seg = draw();
-    if (seg < hi) fetch(seg, v);
-    while (seg < hi) {
-        const size_t s1 = draw();
-        if (s1 < hi) fetch(s1, w);
-        finish(seg, v);
-        if (!(s1 < hi)) break;
-        seg = draw();
-        if (seg < hi) fetch(seg, v);
-        finish(s1, w);
-    }
-#else
     size_t seg = draw();
     while (seg < hi) {
         fetch(seg, v);
         const size_t seg_next = draw();  // the ticket's LDS round trip hides behind the loads
-        os1024_core_rt<64, COMMS_OS1024_REG_TW>(v, lds, tw1, hsp, tw2, l, nostamp, -1, t1r, t2r);
+        os1024_core_rt<64, 1>(v, lds, tw1, hsp, tw2, l, nostamp, -1, t1r, t2r);
         float2* o = out + seg * WVK + l;
 #pragma unroll
         for (int a = HR; a < 16; ++a) o[64 * (a - HR)] = to_f2(v[R16_POS(a)]);
         seg = seg_next;
         ++count;
     }
-#endif
 
     if (TRACE) trace.write(trace_buf, blockIdx.x * 16 + wave, l, count);
     kstamp_end(ks);
@@ -961,9 +894,6 @@ __global__ __launch_bounds__(1024, 4) void fir_os1024_dyn_kernel(In in,
 // tables + counters = 158 KiB, one workgroup per CU.
 constexpr int X_BUF = 1090;    // per-wave slice buffer (>= 1088; 2180 dwords = 4 mod 64 banks)
 constexpr size_t X_LDS_BYTES = (1024 + 64 + 16 * X_BUF) * sizeof(float2) + 32 * sizeof(unsigned) + 3 * sizeof(unsigned long long);  // tables, slices, counters, aux
-#ifndef COMMS_OS16K_CARRY
-#define COMMS_OS16K_CARRY 1  // the four halo rows of a segment stay in registers from the previous one
-#endif
 
 struct XTables {
     const cf* tw1;   // [16][64]   W1024^{lane*k}          (per-wave 1024-point transform)
@@ -1037,11 +967,9 @@ __device__ __forceinline__ bool x_wait_all16(const unsigned* cnt, unsigned targe
 }
 // at a wave's end: report what any wait of the workgroup gave up on
 __device__ __forceinline__ void x_report(const unsigned long long* aux) {
-#ifndef COMMS_OS16K_NO_ERR
     const unsigned code = static_cast<unsigned>(aux[2]);
     unsigned* err = reinterpret_cast<unsigned*>(aux[1]);
     if (code && err && (threadIdx.x & 63) == 0) __hip_atomic_fetch_or(err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#endif
 }
 
 // diagnostic build: phase times of the first X_TRACE_SEGS segments of every wave (scripts/trace_os16k.py), s_memtime at
@@ -1080,9 +1008,7 @@ __global__ __launch_bounds__(1024, 4) void fir_os16k_kernel(In in,
                                                             std::conditional_t<DEC, OsDec, OsNoDec> dec = {}) {
     // err: the handle's sticky error word.  fault (diagnostic build, else 0): workgroup 0's wave 3 withholds one
     // signal, so that the waits above run out and the error path can be tested.
-#ifndef COMMS_OS16K_NO_STAMP
     kstamp_begin(ks);
-#endif
     // HR = halo rows of 1024 samples (1 ... 4: up to 1025 / 2049 / 3073 / 4097 taps): a segment keeps 16 - HR rows.
     // (A compile-time value: as a kernel argument the row loops turned into chains of uniform branches and the
     // kernel lost 11 % -- 591 -> 658 us at 2^27 samples, 4097 taps.)
@@ -1150,7 +1076,6 @@ __global__ __launch_bounds__(1024, 4) void fir_os16k_kernel(In in,
     // The new rows of a segment are requested one phase ahead -- between the slice work and the inverse stage 1 of the
     // segment before, where the registers are free -- so their HBM latency runs behind the workgroup's second
     // wait instead of in front of an idle CU.
-    const int R0 = COMMS_OS16K_CARRY ? hr : 0;  // first row that is fetched per segment
     cf v[16], rows[16];
     auto fetch_rows = [&](size_t sg, int first) {
         const long long base = static_cast<long long>(sg * xv) - 1024 * hr - delay;
@@ -1195,12 +1120,10 @@ __global__ __launch_bounds__(1024, 4) void fir_os16k_kernel(In in,
             X_MARK(1);
         }
 #endif
-#if COMMS_OS16K_CARRY
         // the next segment's halo = this segment's last hr rows (HBM would see them again otherwise: the XCD streams
         // 7 MiB per segment time through a 4 MiB L2)
 #pragma unroll
         for (int a = 0; a < HR; ++a) rows[a] = rows[16 - HR + a];
-#endif
         radix16<-1>(v);
         X_MARK_AFTER(8, v[R16_POS(15)].x);
 #pragma unroll
@@ -1231,7 +1154,7 @@ __global__ __launch_bounds__(1024, 4) void fir_os16k_kernel(In in,
         X_MARK(4);
         // (unconditional -- the last segment fetches itself again -- so that `rows` is redefined on every path
         // and its registers are free during the slice work)
-        fetch_rows(seg + 1 < seg_hi ? seg + 1 : seg, R0);
+        fetch_rows(seg + 1 < seg_hi ? seg + 1 : seg, hr);  // (rows 0 ... hr - 1: carried above)
         // ---- inverse stage 1: thread tid gathers point tid of every slice, radix-16 back to the rows
         X_MARK(5);
         if (!x_wait_all16(slice_out, done + 1, l, gave_up)) break;
@@ -1297,9 +1220,7 @@ __global__ __launch_bounds__(1024, 4) void fir_os16k_kernel(In in,
         X_MARK(7);
     }
     x_report(aux);
-#ifndef COMMS_OS16K_NO_STAMP
     kstamp_end(KStamp{nullptr, reinterpret_cast<unsigned long long*>(aux[0])});
-#endif
 }
 
 // ---------------------------------------------------------------- pulse shaping (polyphase)
@@ -1409,8 +1330,6 @@ using namespace comms;
 
 // ================================================================= FIR handle (struct comms_fir: fir_handle.hpp)
 static void free_fir(comms_fir* h) {
-    h->conv.release();
-    if (h->d_qt) (void)hipFree(h->d_qt);
     if (h->d_any_taps) (void)hipFree(h->d_any_taps);
     if (h->d_p8) (void)hipFree(h->d_p8);
     (void)use_device(h->device);
@@ -1897,24 +1816,6 @@ comms_status_t comms_fir_get_algo(const comms_fir_t* h, size_t n, int32_t* out_a
 
 }  // extern "C"
 
-// Wire-format input for the kernels that read Complex<f32> only: one conversion pass (iqformat.hip's
-// kernels) into a handle-owned buffer on the same stream.  The direct, ticketed 1024-point and
-// decimating-chain kernels convert in their load stage instead and never come here.
-static comms_status_t fir_converted_input(comms_fir* h, const void* d_in, size_t n, hipStream_t s, const float2** out) {
-    if (h->in_fmt == COMMS_IQ_C32) {
-        *out = static_cast<const float2*>(d_in);
-        return COMMS_OK;
-    }
-    COMMS_TRY(h->conv.reserve(n * sizeof(float2)));
-    comms_c32* tmp = static_cast<comms_c32*>(h->conv.p);
-    if (h->in_fmt == COMMS_IQ_I16)
-        COMMS_TRY(comms_iq_i16_to_c32_dev(static_cast<const int16_t*>(d_in), n, h->in_scale, tmp, h->device, s));
-    else
-        COMMS_TRY(comms_iq_u8_to_c32_dev(static_cast<const uint8_t*>(d_in), n, tmp, h->device, s));
-    *out = static_cast<const float2*>(h->conv.p);
-    return COMMS_OK;
-}
-
 template <int HR, class In>
 static comms_status_t launch_dyn_in(hipStream_t s, In in, comms_fir* h, float2* o, size_t n, const WTables& tb, float2* nh,
                                     hipEvent_t ea, hipEvent_t eb, KStamp ks) {
@@ -1993,12 +1894,8 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
     const float2* hist = h->d_hist[h->cur];
     float2* nh = h->d_hist[h->cur ^ 1];  // the kernel's workgroup 0 advances the history into it
     const int algo = fir_pick(h, n);
-    // kernels whose load stages read raw IQ (the 4096-point one in its default three-workgroups-per-CU build)
-    static const int os4096_wps = tune_int("COMMS_OS4096_WPS", 3);
-    const bool fused_fmt = algo == COMMS_FIR_DIRECT || algo == COMMS_FIR_OS1024 || algo == COMMS_FIR_OS16K ||
-                           (algo == COMMS_FIR_OS4096 && os4096_wps == 3);
-    const float2* in = nullptr;  // Complex<f32> view of the input (the conversion pass, where the kernel needs one)
-    if (!fused_fmt || h->in_fmt == COMMS_IQ_C32) COMMS_TRY(fir_converted_input(h, d_in, n, s, &in));
+    // Complex<f32> input, or null: every kernel here reads raw i16 / u8 IQ in its load stage (with_input_view)
+    const float2* in = h->in_fmt == COMMS_IQ_C32 ? static_cast<const float2*>(d_in) : nullptr;
     if (algo == COMMS_FIR_DIRECT) {
         COMMS_TRY(fir_prepare_direct(h));
         const unsigned blocks = static_cast<unsigned>((n + DTILE - 1) / DTILE);
@@ -2050,13 +1947,12 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
         COMMS_TRY(fir_prepare_os(h));
         const size_t V = OSF - 256 * static_cast<size_t>(h->hblk);
         const size_t nseg = (n + V - 1) / V;
-        // persistent grid: WPS workgroups per CU (one wave of each per SIMD), segments dealt round-robin.
-        // Three workgroups per CU with the samples read as 4-byte loads (InC32Split, or the raw i16 / u8 views): with
-        // 8-byte loads the kernel's load stage needs ~200 VGPRs, which at three workgroups (budget 170) spilled 24
-        // registers and cost 4-21 %, while two workgroups leave the CU short of waves; with 4-byte loads it fits in 130
-        // (511 taps at 2^24: 86.8 us spilling, 69.7 at two workgroups, 66.6 now; 2049 taps: 107.5 / 105.7 / 97.5).
-        // COMMS_OS4096_WPS=2 / 4 select the 8-byte-load builds (raw input then takes a conversion pass).
-        const int wps = os4096_wps;
+        // persistent grid: three workgroups per CU (one wave of each per SIMD), segments dealt round-robin, the samples
+        // read as 4-byte loads (InC32Split, or the raw i16 / u8 views): with 8-byte loads the kernel's load stage needs
+        // ~200 VGPRs, which at three workgroups (budget 170) spilled 24 registers and cost 4-21 %, while two workgroups
+        // leave the CU short of waves; with 4-byte loads it fits in 130 (511 taps at 2^24: 86.8 us spilling, 69.7 at two
+        // workgroups, 66.6 now; 2049 taps: 107.5 / 105.7 / 97.5).
+        const int wps = 3;
         // segments b, b + G, ... per workgroup (the chip sweeps the stream as one window: 2-4 % faster at 2^24 ...
         // 2^26 than a contiguous run per workgroup, 1 % at 2^28); 0 restores the runs
         static const int il = tune_int("COMMS_OS4096_INTERLEAVE", 1);
@@ -2067,14 +1963,9 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
             OsTables tb{reinterpret_cast<const cf*>(h->d_tw1), reinterpret_cast<const cf*>(h->d_tw2),
                         reinterpret_cast<const cf*>(h->d_hparts[pt])};
             const int dl = pt * OS_PART, acc = pt ? 1 : 0;
-            if (wps == 4)
-                fir_os4096_kernel<4><<<dim3(blocks), dim3(256), 0, s>>>(in, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
-            else if (wps == 2)
-                fir_os4096_kernel<2><<<dim3(blocks), dim3(256), 0, s>>>(in, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
-            else
-                with_input_view(h, d_in, InC32Split{reinterpret_cast<const float*>(in)}, [&](auto v) {
-                    fir_os4096_kernel<3, decltype(v)><<<dim3(blocks), dim3(256), 0, s>>>(v, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
-                });
+            with_input_view(h, d_in, InC32Split{reinterpret_cast<const float*>(in)}, [&](auto v) {
+                fir_os4096_kernel<decltype(v)><<<dim3(blocks), dim3(256), 0, s>>>(v, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
+            });
         }
         h->toc(s);
         COMMS_TRY(launch_ok("fir_os4096_kernel"));
@@ -2145,12 +2036,10 @@ comms_status_t comms_fir_run_fused_dev(comms_fir_t* h, const comms_c32* d_in, si
     COMMS_ARG((d_in && d_out) || !n, "NULL device pointer");
     COMMS_ARG(h->n_eff <= 257, "the fused chain kernel supports at most 257 taps");
     COMMS_ARG(rate >= 1 && n % rate == 0, "n must be a multiple of the decimation rate");
-    COMMS_ARG(!(mode & CH_FM) || (rate <= 64 && h->n_eff + static_cast<int>(rate) <= 257),
-              "fused FM demod needs rate <= 64 and taps + rate <= 257");
     COMMS_TRY(fir_check_sticky(h));
     COMMS_TRY(use_device(h->device));
     if (!n) return COMMS_OK;
-    COMMS_ARG(!ranges_overlap(d_in, n * 8, d_out, (n / rate) * ((mode & CH_FM) ? 4 : 8)), "the fused chain cannot run in place");
+    COMMS_ARG(!ranges_overlap(d_in, n * 8, d_out, (n / rate) * 8), "the fused chain cannot run in place");
     COMMS_TRY(fir_prepare_os1024(h));
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
@@ -2173,7 +2062,6 @@ comms_status_t comms_fir_run_fused_dev(comms_fir_t* h, const comms_c32* d_in, si
     ch.rate = rate;
     ch.q_seg = WV / rate;
     ch.r_seg = WV % rate;
-    ch.fm_prev = static_cast<const float2*>(fm_prev);
     ch.fm_prev_new = static_cast<float2*>(fm_prev_new);
     const size_t nseg = (n + WV - 1) / WV;
     static const int wpb = tune_int("COMMS_OS1024_WPB", 16);
@@ -2184,14 +2072,8 @@ comms_status_t comms_fir_run_fused_dev(comms_fir_t* h, const comms_c32* d_in, si
         case CH_PRE | CH_DEC:
             COMMS_TRY(launch_os1024<CH_PRE | CH_DEC>(wpb, runs, s, in, hist, h->n_eff, o, n, nseg, tb, nh, ch));
             break;
-        case CH_PRE | CH_DEC | CH_FM:
-            COMMS_TRY(launch_os1024<CH_PRE | CH_DEC | CH_FM>(wpb, runs, s, in, hist, h->n_eff, o, n, nseg, tb, nh, ch));
-            break;
         case CH_POST | CH_DEC:
             COMMS_TRY(launch_os1024<CH_POST | CH_DEC>(wpb, runs, s, in, hist, h->n_eff, o, n, nseg, tb, nh, ch));
-            break;
-        case CH_POST | CH_DEC | CH_FM:
-            COMMS_TRY(launch_os1024<CH_POST | CH_DEC | CH_FM>(wpb, runs, s, in, hist, h->n_eff, o, n, nseg, tb, nh, ch));
             break;
         case CH_TRACE:  // diagnostic build: production geometry, per-wave times into fm_prev_new
             if (os1024_dynamic_mode() != 0)
@@ -2321,7 +2203,7 @@ comms_status_t comms_fir_run_os4096_decim_dev(comms_fir_t* h, const void* d_in, 
     OsTables tb{reinterpret_cast<const cf*>(h->d_tw1), reinterpret_cast<const cf*>(h->d_tw2), reinterpret_cast<const cf*>(h->d_hparts[0])};
     h->tic(s);
     with_input_view(h, d_in, InC32Split{static_cast<const float*>(d_in)}, [&](auto v) {
-        fir_os4096_kernel<3, decltype(v), true><<<dim3(blocks), dim3(256), 0, s>>>(v, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, 0, 0, 1, dc);
+        fir_os4096_kernel<decltype(v), true><<<dim3(blocks), dim3(256), 0, s>>>(v, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, 0, 0, 1, dc);
     });
     h->toc(s);
     COMMS_TRY(launch_ok("fir_os4096_kernel (decimating)"));

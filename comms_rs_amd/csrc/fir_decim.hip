@@ -22,52 +22,39 @@
 
 #include <cmath>
 #include <type_traits>
-#include <vector>
 
 #include "common.hpp"
 #include "fft_radix.hpp"
 #include "fir_handle.hpp"
 #include "sgpr_mac.hpp"
 
-#ifndef COMMS_DECIM_PREFETCH
-#define COMMS_DECIM_PREFETCH 0
-#endif
-#ifndef COMMS_DECIM_TILE_DEFAULT
-#define COMMS_DECIM_TILE_DEFAULT 0
-#endif
 #ifndef COMMS_DECIM_NOMAC_DEFAULT
 #define COMMS_DECIM_NOMAC_DEFAULT 0
 #endif
 #ifndef COMMS_DECIM_WAVE_DEFAULT
 #define COMMS_DECIM_WAVE_DEFAULT 1
 #endif
-#ifndef COMMS_DECIM_WAVE_NT_DEFAULT
-#define COMMS_DECIM_WAVE_NT_DEFAULT -1
-#endif
-#ifndef COMMS_DECIM_WAVE_SPLIT_DEFAULT
-#define COMMS_DECIM_WAVE_SPLIT_DEFAULT 1
-#endif
-#ifndef COMMS_DECIM_WAVE_WPB_DEFAULT
-#define COMMS_DECIM_WAVE_WPB_DEFAULT 1
-#endif
 
 namespace comms {
 
-constexpr int DC_TILE = 512;        // outputs per tile (DcGeom<.., TILE>: 1024 in the diagnostic build's wide variant)
+constexpr int DC_TILE = 512;        // outputs per tile
 constexpr int DC_NMAX = 257;        // taps (kernel-argument budget)
-constexpr int DC_AMAX = 384;        // padded tap array: OPL*R*nd + (OPL-1)*R + pair slack (worst: R = 12, OPL = 4: 376)
+// DecimArgs' array sizes.  Both are larger than two outputs per lane need (DcGeom checks the tap array): they were sized
+// for a four-outputs-per-lane form, since retired, and stay so that the fields behind them keep their offsets.
+constexpr int DC_AMAX = 384;
 constexpr int DC_RMAX = 16;
 constexpr int DC_OPLMAX = 4;
 
-// A lane owns OPL consecutive outputs (2 or 4), a workgroup of 512 / OPL lanes one tile of 512.  Every LDS
-// read of the filter loop feeds OPL MACs: at OPL = 2 the loop issues one ds_read_b64 per two packed FMAs and
-// the LDS array is as busy as the vector ALU (the two do not overlap perfectly: ~10 cycles per MAC and SIMD
-// measured against 4.9 for the FMA alone); OPL = 4 halves the LDS traffic for the same FMAs, at half the
-// waves per CU (the staged inputs of a tile bound how many outputs can be resident).
-template <int R, int OPL, int TILE = DC_TILE>
+// A lane owns OPL = 2 consecutive outputs, a workgroup of 256 lanes one tile of 512.  Every LDS read of the filter
+// loop feeds two MACs: the loop issues one ds_read_b64 per two packed FMAs and the LDS array is as busy as the vector
+// ALU (the two do not overlap perfectly: ~10 cycles per MAC and SIMD measured against 4.9 for the FMA alone).  (Four
+// outputs per lane -- half the LDS traffic for the same FMAs, at half the waves per CU -- was measured slower wherever
+// this kernel is chosen: NOTES.md, round 2.)
+template <int R>
 struct DcGeom {
+    static constexpr int OPL = 2;                                  // outputs per lane
     static constexpr int PR = OPL * R;                             // phases
-    static constexpr int WG = TILE / OPL;                          // lanes per workgroup
+    static constexpr int WG = DC_TILE / OPL;                       // lanes per workgroup
     static constexpr int HLQ_MAX = (DC_NMAX - 1 + PR - 1) / PR;    // halo in phase-array elements
     static constexpr int HROWS = (HLQ_MAX * PR + WG - 1) / WG;     // halo rows of WG samples
     // phase-array stride: odd, so that a staging row (one ds_write_b64 per lane, sixteen lanes at a time over sixteen 8-byte bank
@@ -76,14 +63,14 @@ struct DcGeom {
     static constexpr int SB = WG + HLQ_MAX + 1;
     static constexpr int S = (PR == 4 || PR == 8) ? (SB + 15 - ((SB + 15 - 16 / PR) % 16)) : (SB | 1);
     static constexpr size_t LDS = static_cast<size_t>(PR) * S * sizeof(float2);
-    static constexpr int WGPC = (R <= 8 ? 4 : R <= 12 ? 3 : 2) * DC_TILE / TILE;  // workgroups per CU that fit in LDS
+    static constexpr int WGPC = R <= 8 ? 4 : R <= 12 ? 3 : 2;     // workgroups per CU that fit in LDS
     static constexpr int WAVES_PER_SIMD = (WGPC * WG / 64 + 3) / 4;  // __launch_bounds__' second argument: sets the VGPR budget
     // ... with the mixer in front (PRE: row rotors in registers) rate 12 does not fit three workgroups' budget of 168 VGPRs (148
     // bytes of scratch per lane): two -- 2^24 samples, 31 / 63 / 127 / 255 taps: 33.6 / 35.3 / 38.9 / 46.5 -> 27.9 / 30.1 / 36.3 / 46.0 us
     // (scripts/ab_pre_rates.py).  Rate 11 (92 bytes) gains as much on short filters and loses it on long ones (255 taps: 46.5 ->
     // 50.0 us): it stays at three.
     template <bool PRE>
-    static constexpr int wgpc() { return PRE && R == 12 ? 2 * DC_TILE / TILE : WGPC; }
+    static constexpr int wgpc() { return PRE && R == 12 ? 2 : WGPC; }
     template <bool PRE>
     static constexpr int waves_per_simd() { return (wgpc<PRE>() * WG / 64 + 3) / 4; }
     static_assert(PR * (HLQ_MAX + 1) + (OPL - 1) * R + 4 <= DC_AMAX, "tap table too small");
@@ -106,7 +93,8 @@ struct DecimArgs {
     float2 step[DC_OPLMAX * DC_RMAX];  // e^{i * WG m * dphi}, staging row m
     float are[DC_AMAX];            // A[m] = Re h[m - (PR-1)], zero outside [0, N)
     float aim[DC_AMAX];
-    const float* qt;               // OPL = 4: the taps of one LDS read stored together, Q[m][c] = A[m + R c] (device memory)
+    uint64_t : 64;                 // (a retired form's tap-table pointer: the slot stays so that the fields behind it, and
+                                   // DecimBitsArgs::sym, keep their offsets -- see interleave)
     unsigned long long* stamps;    // diagnostic (scripts/stamp_decim.py): per-wave cycles per phase, or NULL
     int interleave;                // tile t of workgroup b: b + i gridDim.x instead of a contiguous run (kept behind the tap
                                    // arrays: their offsets decide how many scalar-cache lines a 64-byte tap load touches)
@@ -134,21 +122,6 @@ __device__ __forceinline__ void rotor_step(double& c, double& s, double sc, doub
     c = nc;
 }
 
-// A sample of the input stream, read once by this launch (the tile's halo a second time).  COMMS_DECIM_NT=1 (trial
-// build): Complex<f32> rows as nontemporal loads.
-#ifndef COMMS_DECIM_NT
-#define COMMS_DECIM_NT 0
-#endif
-template <class In>
-__device__ __forceinline__ float2 ld_once(In in, size_t i) { return in[i]; }
-#if COMMS_DECIM_NT
-__device__ __forceinline__ float2 ld_once(const float2* in, size_t i) {
-    typedef float nt_f2 __attribute__((ext_vector_type(2)));
-    const nt_f2 q = __builtin_nontemporal_load(reinterpret_cast<const nt_f2*>(in) + i);
-    return make_float2(q.x, q.y);
-}
-#endif
-
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, which would
 // stall on the next tile's global loads that are deliberately left in flight across it.
 __device__ __forceinline__ void lds_barrier() {  // (kept light: nothing global is shared between waves here)
@@ -158,11 +131,11 @@ __device__ __forceinline__ void lds_barrier() {  // (kept light: nothing global 
 // PRE: the mixer sits in front of the FIR (samples are mixed on their way into LDS); otherwise it
 // follows the FIR (or is absent).
 // A = DecimBitsArgs: hard-decision bits instead of Complex<f32> outputs (no FM demod in that form).
-template <int R, int OPL, bool REAL, bool PRE, int TILE = DC_TILE, int CHX = 0, class A = DecimArgs>
-__global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::template waves_per_simd<PRE>())) void fir_decim_kernel(const A a) {
-    using G = DcGeom<R, OPL, TILE>;
+template <int R, bool REAL, bool PRE, class A = DecimArgs>
+__global__ __launch_bounds__((DcGeom<R>::WG), (DcGeom<R>::template waves_per_simd<PRE>())) void fir_decim_kernel(const A a) {
+    using G = DcGeom<R>;
     constexpr bool kBits = !std::is_same<A, DecimArgs>::value;
-    constexpr int PR = G::PR, S = G::S, WG = G::WG, HROWS = G::HROWS;
+    constexpr int OPL = G::OPL, PR = G::PR, S = G::S, WG = G::WG, HROWS = G::HROWS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     cf* sh = reinterpret_cast<cf*>(smem);  // [PR][S]
     __shared__ float2 sh_y[WG / 64];
@@ -178,7 +151,7 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
     const bool post = !PRE && (a.mode & COMMS_CHAIN_POST) != 0;
     const bool fm = (a.mode & COMMS_CHAIN_FM) != 0;
     const int ovl = fm ? 1 : 0;           // FM tiles recompute the previous tile's last output
-    const long long ts = TILE - ovl;      // stored outputs per tile
+    const long long ts = DC_TILE - ovl;   // stored outputs per tile
     const int hl = a.hlq * PR;            // halo samples staged to the left of the tile
 
     // tiles of a workgroup: a contiguous run, or (a.interleave) every gridDim.x-th tile, so that the chip
@@ -193,12 +166,8 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
     // outputs after the filter -- the filter is linear), and a part that never changes,
     // lrow[m] = e^{i (tid + WG m) dphi} (f32, set up once): one multiply per staged sample.
     //   mixer after the FIR: ro = rot(R (jb + OPL tid)) is this lane's first output's rotor.
-    // (prefetching build: the row rotors are re-made from the lane's l0 / h0 and the wave-uniform steps for every tile --
-    // two packed operations per staged row -- instead of living in 2 (PR + HROWS) registers through the filter loop,
-    // where the next tile's rows now wait; the products are the same f32 operations either way)
-    constexpr bool kRowRotorsPerTile = COMMS_DECIM_PREFETCH != 0;
-    constexpr int NROW = PRE && !kRowRotorsPerTile ? PR : 1;
-    cf lrow[NROW], lhalo[kRowRotorsPerTile ? 1 : HROWS];
+    constexpr int NROW = PRE ? PR : 1;
+    cf lrow[NROW], lhalo[HROWS];
     double tt_c = 1.0, tt_s = 0.0, ro_c = 1.0, ro_s = 0.0;
     {
         const long long jb0 = static_cast<long long>(t0) * ts - ovl;
@@ -211,7 +180,7 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
 #pragma unroll
             for (int m = 0; m < NROW; ++m) lrow[m] = m ? cmulf(l0, to_cf(a.step[m])) : l0;
 #pragma unroll
-            for (int m = 0; m < (kRowRotorsPerTile ? 1 : HROWS); ++m) lhalo[m] = m ? cmulf(h0, to_cf(a.step[m])) : h0;
+            for (int m = 0; m < HROWS; ++m) lhalo[m] = m ? cmulf(h0, to_cf(a.step[m])) : h0;
             rotor_at(a.turns0 + static_cast<uint64_t>(R * jb0) * a.frac, tt_c, tt_s);
         }
         if (post) rotor_at(a.turns0 + static_cast<uint64_t>(R * (jb0 + OPL * tid)) * a.frac, ro_c, ro_s);
@@ -242,9 +211,9 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
         if (ib - hl >= 0 && static_cast<size_t>(ib) + static_cast<size_t>(WG) * PR <= a.n) {  // interior tile: no edge handling
             const size_t base = static_cast<size_t>(ib) + static_cast<unsigned>(tid);
 #pragma unroll
-            for (int m = 0; m < PR; ++m) x[m] = to_cf(ld_once(in, base + WG * m));
+            for (int m = 0; m < PR; ++m) x[m] = to_cf(in[base + WG * m]);
 #pragma unroll
-            for (int m = 0; m < HROWS; ++m) xh[m] = slot_h[m] >= 0 ? to_cf(ld_once(in, base - hl + WG * m)) : cf{0.f, 0.f};
+            for (int m = 0; m < HROWS; ++m) xh[m] = slot_h[m] >= 0 ? to_cf(in[base - hl + WG * m]) : cf{0.f, 0.f};
         } else {
 #pragma unroll
             for (int m = 0; m < PR; ++m) x[m] = to_cf(stream_at(in, a.hist, a.hist_len, ib + tid + WG * m, a.n));
@@ -274,30 +243,16 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
     }
     if (a.stamps) st_prev = __builtin_amdgcn_s_memtime();
 
-#if COMMS_DECIM_PREFETCH
-    load_tile(t0);
-#endif
     for (size_t t = t0; t < t1; t += tstep) {
         const long long jb = static_cast<long long>(t) * ts - ovl;  // first output computed by this tile
         // ---- stage the tile: PR rows of new samples, then the halo
-#if !COMMS_DECIM_PREFETCH
         load_tile(t);
-#endif
         DC_STAMP(0)  // global loads landed
         if (pre) {
-            if constexpr (kRowRotorsPerTile) {
-                cf l0 = lrow[0], h0 = lhalo[0];
-                asm volatile("" : "+v"(l0), "+v"(h0));  // (opaque per tile: keeps the row rotors from being hoisted back out of the loop)
 #pragma unroll
-                for (int m = 0; m < PR; ++m) x[m] = cmulf(x[m], m ? cmulf(l0, to_cf(a.step[m])) : l0);
+            for (int m = 0; m < PR; ++m) x[m] = cmulf(x[m], lrow[m < NROW ? m : 0]);
 #pragma unroll
-                for (int m = 0; m < HROWS; ++m) xh[m] = cmulf(xh[m], m ? cmulf(h0, to_cf(a.step[m])) : h0);
-            } else {
-#pragma unroll
-                for (int m = 0; m < PR; ++m) x[m] = cmulf(x[m], lrow[m < NROW ? m : 0]);
-#pragma unroll
-                for (int m = 0; m < HROWS; ++m) xh[m] = cmulf(xh[m], lhalo[m < (kRowRotorsPerTile ? 1 : HROWS) ? m : 0]);
-            }
+            for (int m = 0; m < HROWS; ++m) xh[m] = cmulf(xh[m], lhalo[m]);
         }
 #pragma unroll
         for (int m = 0; m < PR; ++m) sh[kLinearSlots ? slot[0] + (WG / PR) * m : slot[m < NSLOT ? m : 0]] = x[m];
@@ -307,9 +262,6 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
         DC_STAMP(1)  // mixer + LDS writes
         lds_barrier();
         DC_STAMP(2)
-#if COMMS_DECIM_PREFETCH
-        if (t + tstep < t1) load_tile(t + tstep);  // the next tile's rows travel while this tile's taps run
-#endif
 
         // ---- outputs j = jb + OPL tid + c:  y_c = sum_k h[k] u[R j - k]
         // tile sample index of u[R j - k] is PR (tid + hlq) + (R c - k) = PR (tid + hlq - d) + p with
@@ -323,53 +275,9 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
 #pragma unroll
         for (int c = 0; c < OPL; ++c) acc[c] = cf{0.f, 0.f};
         const cf* up = sh + tid + a.hlq;
-        if constexpr (OPL == 4) {
-            // Four outputs per lane: the taps of the four outputs that one LDS read feeds, A[m + R c] (c = 0..3), sit
-            // together in a device-resident table, so a chunk of four reads needs ONE s_load_dwordx16 and 8 SGPR
-            // pairs (the sliding window of the two-output form would need 14 and spill).  Real taps only.
-            static_assert(REAL, "the four-output form is built for real taps");
-            typedef const __attribute__((address_space(4))) float* cptr;  // constant address space: scalar loads
-            const cptr qt = (cptr)(a.qt);
-            constexpr int CH4 = PR % 16 == 0 ? 8 : 4, NCH4 = PR / CH4;  // reads per chunk (8: two s_load_dwordx16, 32 MACs of cover)
-            static_assert(PR % CH4 == 0 && NCH4 % 2 == 0, "chunks must pair up inside a block (even R)");
-            cf ua[CH4], ub[CH4];
-            v2f ra[2 * CH4], rb[2 * CH4];
-            auto fetch4 = [&](int d, int g, cf (&u)[CH4], v2f (&tr)[2 * CH4]) {
-                const int m0 = PR * d + g * CH4;
-#pragma unroll
-                for (int i = 0; i < 2 * CH4; ++i) tr[i] = v2f{qt[4 * m0 + 2 * i], qt[4 * m0 + 2 * i + 1]};
-#pragma unroll
-                for (int i = 0; i < CH4; ++i) u[i] = up[(PR - 1 - (g * CH4 + i)) * S - d];
-            };
-            auto landed4 = [&](cf (&u)[CH4], v2f (&tr)[2 * CH4]) { asm volatile("" ::"v"(u[CH4 - 1]), "s"(tr[2 * CH4 - 1])); };
-            auto macs4 = [&](const cf (&u)[CH4], const v2f (&tr)[2 * CH4]) {
-#pragma unroll
-                for (int i = 0; i < CH4; ++i) {
-                    mac_s_lo(acc[0], u[i], tr[2 * i]);
-                    mac_s_hi(acc[1], u[i], tr[2 * i]);
-                    mac_s_lo(acc[2], u[i], tr[2 * i + 1]);
-                    mac_s_hi(acc[3], u[i], tr[2 * i + 1]);
-                }
-            };
-            fetch4(0, 0, ua, ra);
-            for (int d = 0; d < a.nd; ++d) {
-#pragma unroll
-                for (int g = 0; g < NCH4; g += 2) {
-                    landed4(ua, ra);
-                    fetch4(d, g + 1, ub, rb);
-                    macs4(ua, ra);
-                    landed4(ub, rb);
-                    if (g + 2 < NCH4)
-                        fetch4(d, g + 2, ua, ra);
-                    else if (d + 1 < a.nd)
-                        fetch4(d + 1, 0, ua, ra);
-                    macs4(ub, rb);
-                }
-            }
-        } else {
-        constexpr int CH = CHX ? CHX : OPL == 2 ? ((R <= 10 || R % 2) ? R : R / 2) : (R <= 4 ? R : R % 4 == 0 ? R / 2 : R <= 6 ? R : R / 2);  // taps per chunk (odd rates: whole blocks of R)
+        constexpr int CH = (R <= 10 || R % 2) ? R : R / 2;  // taps per chunk (odd rates: whole blocks of R)
         constexpr int NCH = PR / CH;
-        static_assert(PR % CH == 0 && (NCH == 1 || NCH % 2 == 0), "chunks must pair up inside a block (or be whole blocks)");
+        static_assert(PR % CH == 0 && NCH % 2 == 0, "chunks must pair up inside a block");
         constexpr int NP = ((CH & 1) + CH + (OPL - 1) * R + 1) / 2;  // SGPR pairs (A[2i], A[2i+1]) covering the chunk's taps of all OPL outputs (an odd chunk may start in a pair's hi half)
         cf ua[CH], ub[CH];
         v2f ra[NP], rb[NP], ia[NP], ib_[NP];
@@ -400,21 +308,6 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
             }
         };
         fetch(0, 0, ua, ra, ia);
-        if constexpr (NCH == 1) {  // whole blocks as chunks (diagnostic variant): blocks pair up, an odd last one runs alone
-            int d = 0;
-            for (; d + 1 < a.nd; d += 2) {
-                landed(ua, ra, ia);
-                fetch(d + 1, 0, ub, rb, ib_);
-                macs(0, ua, ra, ia);
-                landed(ub, rb, ib_);
-                if (d + 2 < a.nd) fetch(d + 2, 0, ua, ra, ia);
-                macs(0, ub, rb, ib_);
-            }
-            if (d < a.nd) {
-                landed(ua, ra, ia);
-                macs(0, ua, ra, ia);
-            }
-        } else
         for (int d = 0; d < a.nd; ++d) {
 #pragma unroll
             for (int g = 0; g < NCH; g += 2) {
@@ -428,8 +321,6 @@ __global__ __launch_bounds__((DcGeom<R, OPL, TILE>::WG), (DcGeom<R, OPL, TILE>::
                     fetch(d + 1, 0, ua, ra, ia);
                 macs(g + 1, ub, rb, ib_);
             }
-        }
-
         }
 
         // ---- epilogue: mixer after the FIR, FM demod, stores
@@ -549,8 +440,9 @@ struct DwGeom {
 };
 
 
-template <int R, bool REAL, bool PRE, int HR, int WPB, int AUX>
-__global__ __launch_bounds__(64 * WPB, 4) void fir_decim_wave_kernel(const DecimArgs a) {
+// AUX: 0, or 6 -- nontemporal loads (2) and stores (4), for batches past what the Infinity Cache holds (run_decim)
+template <int R, bool REAL, bool PRE, int HR, int AUX>
+__global__ __launch_bounds__(64, 4) void fir_decim_wave_kernel(const DecimArgs a) {
     using G = DwGeom<R, HR>;
     constexpr int PR = G::PR, S = G::S, RPE = G::RPE, SCAP = G::SCAP;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -567,7 +459,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void fir_decim_wave_kernel(const Decim
     // (run k belongs to workgroup k: the sixteen waves that share a CU then work 32 MiB apart.  Giving them sixteen
     // ADJACENT runs instead -- b -> (b % 256) * 16 + b / 256, 2 MiB of the stream per CU -- was measured and is slower,
     // 130.6 against 124.6 us on config 3, as are four-wave workgroups with four adjacent runs: NOTES.md, round 5)
-    const long long wave0 = static_cast<long long>(blockIdx.x) * WPB + w, n_waves = static_cast<long long>(gridDim.x) * WPB;
+    const long long wave0 = static_cast<long long>(blockIdx.x) + w, n_waves = static_cast<long long>(gridDim.x);
 
     // lane constants: LDS slot of the lane's sample of row 0 (row m: + RPE m; halo row i: - SCAP + RPE i), its rotor
     const int wslot = (l % PR) * S + SCAP + l / PR;
@@ -782,123 +674,85 @@ __global__ __launch_bounds__(64 * WPB, 4) void fir_decim_wave_kernel(const Decim
 // around the launch would include the dispatch gap in front of it whenever the launch before it carried no events.
 static thread_local hipEvent_t g_decim_ev_start = nullptr, g_decim_ev_stop = nullptr;
 
-template <int R, bool REAL, bool PRE, int HR, int WPB, int AUX>
+template <int R, bool REAL, bool PRE, int HR, int AUX>
 static comms_status_t launch_decim_wave_v(const DecimArgs& a, hipStream_t s) {
     using G = DwGeom<R, HR>;
     // (single-wave workgroups ask for a sixteenth of the CU's LDS: seventeen would fit at HR = 2, and the dispatcher
     // would then fill some CUs with 17 waves and leave others 15)
-    constexpr size_t lds = WPB == 1 && G::LDS_WAVE < 10240 ? 10240 : G::LDS_WAVE * WPB;
-    const size_t want = (static_cast<size_t>(a.n_chunks) + WPB - 1) / WPB;
+    constexpr size_t lds = G::LDS_WAVE < 10240 ? 10240 : G::LDS_WAVE;
+    const size_t want = static_cast<size_t>(a.n_chunks);
     const size_t slots = (160u * 1024u / lds) * kNumCU;
     const unsigned blocks = static_cast<unsigned>(want < slots ? want : slots);
     static DeviceOnce attr_once;
     if (attr_once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_decim_wave_kernel<R, REAL, PRE, HR, WPB, AUX>),
+        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_decim_wave_kernel<R, REAL, PRE, HR, AUX>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     hipEvent_t ea = g_decim_ev_start, eb = g_decim_ev_stop;
     g_decim_ev_start = g_decim_ev_stop = nullptr;
     if (ea)
-        hipExtLaunchKernelGGL((fir_decim_wave_kernel<R, REAL, PRE, HR, WPB, AUX>), dim3(blocks), dim3(64 * WPB), static_cast<uint32_t>(lds), s, ea, eb, 0u, a);
+        hipExtLaunchKernelGGL((fir_decim_wave_kernel<R, REAL, PRE, HR, AUX>), dim3(blocks), dim3(64), static_cast<uint32_t>(lds), s, ea, eb, 0u, a);
     else
-        fir_decim_wave_kernel<R, REAL, PRE, HR, WPB, AUX><<<dim3(blocks), dim3(64 * WPB), lds, s>>>(a);
+        fir_decim_wave_kernel<R, REAL, PRE, HR, AUX><<<dim3(blocks), dim3(64), lds, s>>>(a);
     return launch_ok("fir_decim_wave_kernel");
 }
 
-template <int R, int OPL, bool REAL, bool PRE, int TILE = DC_TILE, int CHX = 0, class A = DecimArgs>
+// rates 2, 4 and 8 (Complex<f32> input, up to 129 taps: two halo rows); nt: nontemporal loads and stores
+template <int R>
+static comms_status_t launch_decim_wave(const DecimArgs& a, bool real, bool pre, bool nt, hipStream_t s) {
+    if (real) {
+        if (pre) return nt ? launch_decim_wave_v<R, true, true, 2, 6>(a, s) : launch_decim_wave_v<R, true, true, 2, 0>(a, s);
+        return nt ? launch_decim_wave_v<R, true, false, 2, 6>(a, s) : launch_decim_wave_v<R, true, false, 2, 0>(a, s);
+    }
+    if (pre) return nt ? launch_decim_wave_v<R, false, true, 2, 6>(a, s) : launch_decim_wave_v<R, false, true, 2, 0>(a, s);
+    return nt ? launch_decim_wave_v<R, false, false, 2, 6>(a, s) : launch_decim_wave_v<R, false, false, 2, 0>(a, s);
+}
+
+template <int R, bool REAL, bool PRE, class A>
 static comms_status_t launch_decim_v(const A& a, hipStream_t s) {
-    using G = DcGeom<R, OPL, TILE>;
+    using G = DcGeom<R>;
     constexpr size_t lds = G::LDS;
     // persistent grid: one workgroup per slot of the chip; tile b, b + slots, ... (or a contiguous run) each
     const size_t slots = static_cast<size_t>(G::template wgpc<PRE>()) * kNumCU;
     const unsigned blocks = static_cast<unsigned>(a.n_tiles < slots ? a.n_tiles : slots);
     static DeviceOnce attr_once;
     if (attr_once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_decim_kernel<R, OPL, REAL, PRE, TILE, CHX, A>),
+        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_decim_kernel<R, REAL, PRE, A>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     A b = a;
     if (a.interleave) {
         // a workgroup's next tile is `blocks` tiles on: the per-step rotor of its tile-wide phase follows the grid
-        const uint64_t ts = static_cast<uint64_t>(TILE) - ((a.mode & COMMS_CHAIN_FM) ? 1 : 0);
+        const uint64_t ts = static_cast<uint64_t>(DC_TILE) - ((a.mode & COMMS_CHAIN_FM) ? 1 : 0);
         mix_host_rotor(static_cast<uint64_t>(R) * ts * blocks * a.frac, b.tile_c, b.tile_s);
     }
     hipEvent_t ea = g_decim_ev_start, eb = g_decim_ev_stop;
     g_decim_ev_start = g_decim_ev_stop = nullptr;
     if (ea)
-        hipExtLaunchKernelGGL((fir_decim_kernel<R, OPL, REAL, PRE, TILE, CHX, A>), dim3(blocks), dim3(G::WG), static_cast<uint32_t>(lds), s, ea, eb, 0u, b);
+        hipExtLaunchKernelGGL((fir_decim_kernel<R, REAL, PRE, A>), dim3(blocks), dim3(G::WG), static_cast<uint32_t>(lds), s, ea, eb, 0u, b);
     else
-        fir_decim_kernel<R, OPL, REAL, PRE, TILE, CHX, A><<<dim3(blocks), dim3(G::WG), lds, s>>>(b);
+        fir_decim_kernel<R, REAL, PRE, A><<<dim3(blocks), dim3(G::WG), lds, s>>>(b);
     return launch_ok("fir_decim_kernel");
 }
 
-// Outputs per lane.  Two in the product.  Four (half the LDS reads per MAC, half the waves per CU, 28 tap
-// registers per chunk instead of 16) was built and measured: slower wherever the chain kernel is chosen
-// (metric chain 50 -> 60 us, config 3 153 -> 172 us) and ahead only beyond ~100 MACs per input sample
-// (255 taps / 2: 194 -> 148 us), where the overlap-save fusion is used anyway.  The diagnostic build keeps
-// it selectable (COMMS_DECIM_OPL=4) so that the comparison can be repeated.
-static int decim_opl(bool real, int macs_per_input) {
-    (void)macs_per_input;
-#ifdef COMMS_DIAG
-    static const int forced = diag_knob("COMMS_DECIM_OPL", 0);
-    if (real && forced == 4) return 4;
-#else
-    (void)real;
-#endif
-    return 2;
-}
-
-// Tile width (diagnostic build: COMMS_DECIM_TILE=1024 = 512-lane workgroups, two per CU, so that the waves a
-// SIMD holds are in the same phase more often)
-static int decim_tile(bool real, int R, int opl) {
-#ifdef COMMS_DIAG
-    static const int forced = diag_knob("COMMS_DECIM_TILE", COMMS_DECIM_TILE_DEFAULT);
-    if (real && opl == 2 && R == 8 && (forced == 1024 || forced == 256)) return forced;
-#else
-    (void)real; (void)R; (void)opl;
-#endif
-    return DC_TILE;
-}
-
-template <int R>
-static comms_status_t launch_decim(const DecimArgs& a, bool real, int opl, int tile, hipStream_t s) {
-    const bool pre = (a.mode & COMMS_CHAIN_PRE) != 0;
-#ifdef COMMS_DIAG
-    if constexpr (R == 8) {
-        static const int chx = diag_knob("COMMS_DECIM_CH", 0);
-        if (chx == 16 && real && opl == 2 && !pre && tile == DC_TILE) return launch_decim_v<R, 2, true, false, DC_TILE, 16>(a, s);
-        if (tile == 1024) return pre ? launch_decim_v<R, 2, true, true, 1024>(a, s) : launch_decim_v<R, 2, true, false, 1024>(a, s);
-        if (tile == 256) return pre ? launch_decim_v<R, 2, true, true, 256>(a, s) : launch_decim_v<R, 2, true, false, 256>(a, s);
-    }
-#else
-    (void)tile;
-#endif
-    if (!real) return pre ? launch_decim_v<R, 2, false, true>(a, s) : launch_decim_v<R, 2, false, false>(a, s);
-#ifdef COMMS_DIAG
-    if constexpr (R <= 8 && R % 2 == 0) {
-        if (opl == 4) return pre ? launch_decim_v<R, 4, true, true>(a, s) : launch_decim_v<R, 4, true, false>(a, s);
-    }
-#else
-    (void)opl;
-#endif
-    return pre ? launch_decim_v<R, 2, true, true>(a, s) : launch_decim_v<R, 2, true, false>(a, s);
-}
-
-// odd rates above 10 (chunks of R taps): real taps only
-template <int R>
-static comms_status_t launch_decim_real(const DecimArgs& a, hipStream_t s) {
-    return (a.mode & COMMS_CHAIN_PRE) ? launch_decim_v<R, 2, true, true>(a, s) : launch_decim_v<R, 2, true, false>(a, s);
-}
-
-// the bits form: two outputs per lane, 512-output tiles, every rate of the switch below (11 / 13 / 15: real taps only)
-template <int R>
-static comms_status_t launch_decim_bits(const DecimBitsArgs& a, bool real, hipStream_t s) {
+// A = DecimArgs (Complex<f32> / FM outputs) or DecimBitsArgs (hard decisions); 11 / 13 / 15 (chunks of R taps): real taps only
+template <int R, class A>
+static comms_status_t launch_decim(const A& a, bool real, hipStream_t s) {
     const bool pre = (a.mode & COMMS_CHAIN_PRE) != 0;
     if constexpr (R != 11 && R != 13 && R != 15) {
-        if (!real)
-            return pre ? launch_decim_v<R, 2, false, true, DC_TILE, 0, DecimBitsArgs>(a, s)
-                       : launch_decim_v<R, 2, false, false, DC_TILE, 0, DecimBitsArgs>(a, s);
+        if (!real) return pre ? launch_decim_v<R, false, true>(a, s) : launch_decim_v<R, false, false>(a, s);
     }
-    return pre ? launch_decim_v<R, 2, true, true, DC_TILE, 0, DecimBitsArgs>(a, s)
-               : launch_decim_v<R, 2, true, false, DC_TILE, 0, DecimBitsArgs>(a, s);
+    return pre ? launch_decim_v<R, true, true>(a, s) : launch_decim_v<R, true, false>(a, s);
+}
+
+template <class A>
+static comms_status_t launch_decim_rate(const A& a, int R, bool real, hipStream_t s) {
+    switch (R) {
+#define COMMS_DR(RV) \
+    case RV: return launch_decim<RV>(a, real, s);
+        COMMS_DR(2) COMMS_DR(3) COMMS_DR(4) COMMS_DR(5) COMMS_DR(6) COMMS_DR(7) COMMS_DR(8) COMMS_DR(9) COMMS_DR(10)
+        COMMS_DR(11) COMMS_DR(12) COMMS_DR(13) COMMS_DR(14) COMMS_DR(15) COMMS_DR(16)
+#undef COMMS_DR
+        default: return fail(COMMS_ERR_ARG, "no decimating kernel for rate %d", R);
+    }
 }
 
 }  // namespace comms
@@ -973,9 +827,7 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
     COMMS_TRY(h->enter(stream, &s));
     const bool real = h->real_taps;
     const int R = static_cast<int>(rate), N = h->n_eff;
-    const int opl = !bits && (R <= 8 && R % 2 == 0) ? decim_opl(real, (N + R - 1) / R) : 2;  // (four outputs per lane: even R up to 8)
-    const int tile = bits ? DC_TILE : decim_tile(real, R, opl);
-    const int PR = opl * R, WG = tile / opl;
+    const int opl = 2, PR = opl * R, WG = DC_TILE / opl;  // (DcGeom<R>)
     DecimArgs a{};
     a.in = d_in;
     a.fmt = h->in_fmt;
@@ -988,7 +840,7 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
     a.n = n;
     a.n_out = n / rate;
     const bool fm = (mode & COMMS_CHAIN_FM) != 0;
-    const size_t ts = static_cast<size_t>(tile) - (fm ? 1 : 0);
+    const size_t ts = static_cast<size_t>(DC_TILE) - (fm ? 1 : 0);
     a.n_tiles = (a.n_out + ts - 1) / ts;
     a.hist_len = h->n_eff;
     a.hlq = (N - 1 + PR - 1) / PR;
@@ -1016,26 +868,6 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
         a.step[m] = make_float2(static_cast<float>(c), static_cast<float>(sn));
     }
     COMMS_ARG(PR * (a.hlq + 1) + (opl - 1) * R + 4 <= DC_AMAX, "tap table overflow");
-    if (opl == 4) {  // tap quadruples Q[m][c] = A[m + R c], A[m] = h[m - (PR-1)]: built once per rate, device resident
-        if (h->qt_rate != R) {
-            const int rows = PR * (a.hlq + 1);
-            std::vector<float> q(static_cast<size_t>(rows) * 4, 0.f);
-            for (int m = 0; m < rows; ++m)
-                for (int c = 0; c < 4; ++c) {
-                    const int k = m + R * c - (PR - 1);
-                    if (k >= 0 && k < N) q[4 * m + c] = h->taps[k].re;
-                }
-            COMMS_TRY(h->quiesce());
-            h->last_stream = s;  // (quiesce forgot the stream `enter` just recorded: the launch below must stay tracked)
-            h->launched = true;
-            if (h->d_qt) (void)hipFree(h->d_qt);
-            h->d_qt = nullptr;
-            COMMS_HIP_TRY(hipMalloc(&h->d_qt, q.size() * sizeof(float)));
-            COMMS_HIP_TRY(hipMemcpy(h->d_qt, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice));
-            h->qt_rate = R;
-        }
-        a.qt = h->d_qt;
-    }
     for (int m = 0; m < DC_AMAX; ++m) {
         const int k = m - (PR - 1);
         const bool in_range = k >= 0 && k < N;
@@ -1062,7 +894,7 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
     // 35.1 -> 32.3 at 63 (scripts/time_rate2.py)
     static const int wave_r24 = diag_knob("COMMS_DECIM_WAVE_R24", 1);
     void* wave_out = bits ? c32_scratch : d_out;
-    if (wave_out && wave_knob && (R == 8 || (wave_r24 && (R == 2 || R == 4))) && h->in_fmt == COMMS_IQ_C32 && opl == 2 && tile == DC_TILE && a.hlq * PR <= 128 &&
+    if (wave_out && wave_knob && (R == 8 || (wave_r24 && (R == 2 || R == 4))) && h->in_fmt == COMMS_IQ_C32 && a.hlq * PR <= 128 &&
         (reinterpret_cast<uintptr_t>(wave_out) & 15) == 0) {  // (its stores are 8 / 16 bytes per lane)
         constexpr int HR = 2;
         const long long tiles = static_cast<long long>((a.n_out + 127) / 128);
@@ -1072,8 +904,6 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
         if (balanced || wave_knob == 2) {
             a.out = wave_out;
             a.nt_chunk = static_cast<int>(nt < 1 ? 1 : nt);
-            static const int ntc_div = diag_knob("COMMS_DECIM_WAVE_SPLIT", COMMS_DECIM_WAVE_SPLIT_DEFAULT);  // runs per wave (trial)
-            if (ntc_div > 1 && a.nt_chunk % ntc_div == 0) a.nt_chunk /= ntc_div;
             a.n_chunks = (tiles + a.nt_chunk - 1) / a.nt_chunk;
             a.interleave = 0;
             mix_host_rotor(static_cast<uint64_t>(R) * 128u * frac, a.tile_c, a.tile_s);
@@ -1088,24 +918,11 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
             const bool pre = (mode & COMMS_CHAIN_PRE) != 0;
             // nontemporal loads and stores once the batch is past what the 256 MiB Infinity Cache can hold for the next kernel
             // (config 3 at 2^26 samples: 128.3 -> 120.3 us; at 2^24 the re-read input of a benchmark loop would lose its
-            // cache hits); the diagnostic build's COMMS_DECIM_WAVE_NT = 0 / 2 (loads) / 4 (stores) / 6 forces a form
-            static const int nt_knob = diag_knob("COMMS_DECIM_WAVE_NT", COMMS_DECIM_WAVE_NT_DEFAULT);
-            const int nt_loads = nt_knob >= 0 ? nt_knob : (n * sizeof(float2) > (192u << 20) ? 6 : 0);
-#ifdef COMMS_DIAG
-            static const int wpb4 = diag_knob("COMMS_DECIM_WAVE_WPB", COMMS_DECIM_WAVE_WPB_DEFAULT) == 4;
-#define COMMS_DW(REAL_, PRE_, HR_) (wpb4 ? launch_decim_wave_v<8, REAL_, PRE_, HR_, 4, 0>(a, s) : nt_loads == 2 ? launch_decim_wave_v<8, REAL_, PRE_, HR_, 1, 2>(a, s) : nt_loads == 4 ? launch_decim_wave_v<8, REAL_, PRE_, HR_, 1, 4>(a, s) : nt_loads == 6 ? launch_decim_wave_v<8, REAL_, PRE_, HR_, 1, 6>(a, s) : launch_decim_wave_v<8, REAL_, PRE_, HR_, 1, 0>(a, s))
-#else
-#define COMMS_DW(REAL_, PRE_, HR_) (nt_loads ? launch_decim_wave_v<8, REAL_, PRE_, HR_, 1, 6>(a, s) : launch_decim_wave_v<8, REAL_, PRE_, HR_, 1, 0>(a, s))
-#endif
-#define COMMS_DWR(RV, REAL_, PRE_) (nt_loads ? launch_decim_wave_v<RV, REAL_, PRE_, 2, 1, 6>(a, s) : launch_decim_wave_v<RV, REAL_, PRE_, 2, 1, 0>(a, s))
-            if (R == 2)
-                st = real ? (pre ? COMMS_DWR(2, true, true) : COMMS_DWR(2, true, false)) : (pre ? COMMS_DWR(2, false, true) : COMMS_DWR(2, false, false));
-            else if (R == 4)
-                st = real ? (pre ? COMMS_DWR(4, true, true) : COMMS_DWR(4, true, false)) : (pre ? COMMS_DWR(4, false, true) : COMMS_DWR(4, false, false));
-            else
-                st = real ? (pre ? COMMS_DW(true, true, 2) : COMMS_DW(true, false, 2)) : (pre ? COMMS_DW(false, true, 2) : COMMS_DW(false, false, 2));
-#undef COMMS_DWR
-#undef COMMS_DW
+            // cache hits)
+            const bool nt_big = n * sizeof(float2) > (192u << 20);
+            st = R == 2 ? launch_decim_wave<2>(a, real, pre, nt_big, s)
+                 : R == 4 ? launch_decim_wave<4>(a, real, pre, nt_big, s)
+                          : launch_decim_wave<8>(a, real, pre, nt_big, s);
             COMMS_TRY(st);
             h->cur ^= 1;
             if (bits) return sym_to_bits_launch(static_cast<const comms_c32*>(wave_out), a.n_out, *bits, static_cast<uint8_t*>(d_out), s);
@@ -1116,35 +933,9 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
         DecimBitsArgs b;
         static_cast<DecimArgs&>(b) = a;
         b.sym = *bits;
-        switch (R) {
-#define COMMS_DB(RV) \
-    case RV: st = launch_decim_bits<RV>(b, real, s); break;
-            COMMS_DB(2) COMMS_DB(3) COMMS_DB(4) COMMS_DB(5) COMMS_DB(6) COMMS_DB(7) COMMS_DB(8) COMMS_DB(9) COMMS_DB(10)
-            COMMS_DB(11) COMMS_DB(12) COMMS_DB(13) COMMS_DB(14) COMMS_DB(15) COMMS_DB(16)
-#undef COMMS_DB
-            default: return fail(COMMS_ERR_ARG, "no decimating kernel for rate %d", R);
-        }
-        COMMS_TRY(st);
-        h->cur ^= 1;
-        return COMMS_OK;
-    }
-    switch (R) {
-        case 2: st = launch_decim<2>(a, real, opl, tile, s); break;
-        case 3: st = launch_decim<3>(a, real, opl, tile, s); break;
-        case 4: st = launch_decim<4>(a, real, opl, tile, s); break;
-        case 5: st = launch_decim<5>(a, real, opl, tile, s); break;
-        case 6: st = launch_decim<6>(a, real, opl, tile, s); break;
-        case 7: st = launch_decim<7>(a, real, 2, tile, s); break;
-        case 8: st = launch_decim<8>(a, real, opl, tile, s); break;
-        case 9: st = launch_decim<9>(a, real, 2, tile, s); break;
-        case 10: st = launch_decim<10>(a, real, 2, tile, s); break;
-        case 11: st = launch_decim_real<11>(a, s); break;
-        case 12: st = launch_decim<12>(a, real, 2, tile, s); break;
-        case 13: st = launch_decim_real<13>(a, s); break;
-        case 14: st = launch_decim<14>(a, real, 2, tile, s); break;
-        case 15: st = launch_decim_real<15>(a, s); break;
-        case 16: st = launch_decim<16>(a, real, 2, tile, s); break;
-        default: return fail(COMMS_ERR_ARG, "no decimating kernel for rate %d", R);
+        st = launch_decim_rate(b, R, real, s);
+    } else {
+        st = launch_decim_rate(a, R, real, s);
     }
     COMMS_TRY(st);
     h->cur ^= 1;

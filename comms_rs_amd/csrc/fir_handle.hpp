@@ -192,9 +192,6 @@ struct comms_fir : comms::Handle {
     bool os1024_fixed = false;  // COMMS_FIR_OS1024_FIXED: never the ticketed kernel
     int in_fmt = 0;             // COMMS_IQ_C32 / _I16 / _U8: what d_in of the run entries points to
     float in_scale = 1.0f;      // i16 only
-    comms::Scratch conv;        // converted copy, for the kernels that do not read wire formats themselves
-    float* d_qt = nullptr;      // decimating chain kernel, four outputs per lane: tap quadruples for rate qt_rate
-    int qt_rate = 0;
     float2* d_any_taps = nullptr;  // any-rate chain kernel: taps zero-padded to 32 * any_nt
     int any_nt = 0;
     float2* d_p8 = nullptr;     // polyphase frequency-domain chain kernel (fir_poly8.hip): branch spectra + twiddle tables ...

@@ -1,5 +1,5 @@
 """Rate-2 chains (31 / 47 / 63 taps) on the per-rate time-domain kernel, for A/B runs of diagnostic knobs.
-usage: [COMMS_HIP_LIB=...diag.so COMMS_DECIM_OPL=4] python3 scripts/time_rate2.py [rate]"""
+usage: [COMMS_HIP_LIB=...diag.so COMMS_DECIM_WAVE_R24=0] python3 scripts/time_rate2.py [rate]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

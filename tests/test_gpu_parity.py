@@ -1102,35 +1102,6 @@ print("ok")
     assert out.returncode == 0 and "ok" in out.stdout, out.stdout + out.stderr
 
 
-def test_fft_trial_tile_kernel_gives_the_same_transforms():
-    """COMMS_FFT_TILE_DIRECT=1: fft1024x16d_kernel (register-layout loads, last radix-4 across lanes) in place of
-    fft1024x16_kernel on every pass that uses it -- 1024-point batches, pass 2 of 2^16 ... 2^19, both passes of 2^20,
-    the column pass of 2^21 -- forward and inverse, against numpy's f64 FFT.  Read once per process: own process."""
-    import subprocess
-    import sys
-
-    code = r'''
-import sys; sys.path.insert(0, %r)
-import numpy as np, torch, comms_rs_amd as c
-for logn, batch, inverse in ((10, 64, False), (10, 48, True), (16, 4, False), (17, 2, True), (19, 2, False), (20, 3, False), (20, 2, True), (21, 1, False)):
-    n = 1 << logn
-    x = torch.empty(n * batch, dtype=torch.complex64, device="cuda:0")
-    c.synth_iq_dev(x.data_ptr(), n * batch, 0, 190 + logn)
-    y = torch.empty_like(x)
-    c.FFTBatchNode(n, inverse).run_dev(x.data_ptr(), n * batch, y.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    xs = c.synth_iq(n * batch, 0, 190 + logn).astype(np.complex128).reshape(batch, n)
-    want = np.fft.ifft(xs, axis=1) * n if inverse else np.fft.fft(xs, axis=1)
-    got = y.cpu().numpy().astype(np.complex128).reshape(batch, n)
-    d = np.linalg.norm(got - want) / np.linalg.norm(want)
-    assert d <= %r, (logn, d)
-print("ok")
-''' % (ROOT, TOL)
-    env = dict(os.environ, COMMS_FFT_TILE_DIRECT="1", COMMS_HIP_LIB=DIAG_LIB)  # kernel selectors exist in the diagnostic build only
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "ok" in out.stdout, out.stdout + out.stderr
-
-
 def test_fft_bluestein_on_a_padded_length_above_2p20(c):
     """A non-power-of-two length whose chirp-z padding (2^21) runs on the columns / rows / transpose path,
     forward and inverse, against numpy's f64 FFT."""
@@ -1463,36 +1434,6 @@ def test_chain_beyond_257_taps(c, n_taps, rate, after, fm):
         assert np.max(circ(g1.astype(np.float64) - g2.astype(np.float64))) <= 1e-4
     else:
         fir_close(g2, g1, taps, tail)
-
-
-def test_fm_chain_demodulating_inside_the_overlap_save_kernel_still_works():
-    """COMMS_CHAIN_FM_SEPARATE=0 brings back the form that demodulates inside the overlap-save kernel (kept for the
-    comparison recorded in profiles/r02_bench_chain_rates.txt).  The switch is read once per process: own process."""
-    import subprocess
-    import sys
-
-    code = r'''
-import sys; sys.path.insert(0, %r)
-import numpy as np, comms_rs_amd as c, oracle
-rate, n = 5, 768 * 5 * 4
-t = np.arange(n)
-x = np.exp(1j * (0.05 * t + 0.5 * np.sin(2 * np.pi * t / 4096))).astype(np.complex64)
-k = np.arange(63) - 31
-taps = (0.16 * np.sinc(0.16 * k) * np.hamming(63)).astype(np.float32).astype(np.complex64)
-node = c.ChainNode(0.3, 0.1, taps, rate, True, kernel="freq")
-assert node.kernel == "freq"
-ost, om, ofm = oracle.default_state(taps), oracle.Mixer(0.1, 0.3), oracle.FM()
-for a, b in ((0, 768 * rate), (768 * rate, n)):
-    y = oracle.decimate(oracle.batch_fir(om.mix(x[a:b]), taps, ost, norotate=True), rate)
-    w = ofm.demod(y)
-    d = np.abs(node.run(x[a:b]).astype(np.float64) - w); d = np.minimum(d, 2 * np.pi - d)
-    ok = np.minimum(np.abs(y), np.abs(np.concatenate([[1.0], y[:-1]]))) > 0.05
-    assert d[ok].max() <= 1e-4, d[ok].max()
-print("ok")
-''' % ROOT
-    env = dict(os.environ, COMMS_CHAIN_FM_SEPARATE="0", COMMS_HIP_LIB=DIAG_LIB)  # kernel selectors exist in the diagnostic build only
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "ok" in out.stdout, out.stdout + out.stderr
 
 
 @pytest.mark.parametrize("rate", [2, 3, 4, 5, 6, 8, 10, 12, 16])
