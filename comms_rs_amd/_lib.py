@@ -173,6 +173,15 @@ _PROTOS = {
     "comms_iq_u8_to_c32_dev": [_vp, _sz, _vp, _i32, _vp],
     "comms_iq_real_to_c32_dev": [_vp, _sz, _vp, _i32, _vp],
     "comms_iq_c32_re_dev": [_vp, _sz, _vp, _i32, _vp],
+    "comms_rfir_create": [_vp, _sz, _vp, _sz, _sz, _i32, _pp],
+    "comms_rfir_out_len": [_sz, _sz, _psz],
+    "comms_rfir_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_rfir_run": [_vp, _vp, _sz, _vp],
+    "comms_rfir_get_state": [_vp, _vp, _sz],
+    "comms_rfir_set_state": [_vp, _vp, _sz],
+    "comms_rfir_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_rfir_set_timer": [_vp, _vp],
+    "comms_rfir_destroy": [_vp],
     "comms_bpsk_byte_mod": [_vp, _sz, _vp, _i32],
     "comms_qpsk_byte_mod": [_vp, _sz, _vp, _i32],
     "comms_bpsk_bit_mod": [_vp, _sz, _vp, _i32],

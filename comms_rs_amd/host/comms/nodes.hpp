@@ -522,6 +522,43 @@ private:
     int k_;
 };
 
+// Real FIR + decimator over an f32 stream as ONE node (comms_rfir_*; an additional node): the results of the audio stage of
+// examples/fm_radio.rs:98-164 -- Convert2Node -> BatchFirNode<f32> -> Convert3Node -> DecimateNode<f32>(rate) -- for real
+// taps.  Any message length: ceil(n / rate) outputs, the decimator restarting with every message as DecimateNode does.
+class RealFirDecimNode : public DeriveNode<RealFirDecimNode> {
+public:
+    NodeReceiver<std::vector<float>> input;
+    NodeSender<std::vector<float>> output;
+    RealFirDecimNode(const std::vector<float>& taps, size_t rate, const std::optional<std::vector<float>>& state = std::nullopt,
+                     int device = 0)
+        : rate_(rate) {
+        throw_on(comms_rfir_create(taps.data(), taps.size(), state ? state->data() : nullptr, state ? state->size() : 0, rate,
+                                   device, &h_),
+                 "RealFirDecimNode::new");
+    }
+    RealFirDecimNode(RealFirDecimNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), rate_(o.rate_) { o.h_ = nullptr; }
+    ~RealFirDecimNode() { comms_rfir_destroy(h_); }
+    Result<std::vector<float>> run(const std::vector<float>& in) {
+        size_t m = 0;
+        comms_rfir_out_len(in.size(), rate_, &m);
+        std::vector<float> out(m);
+        comms_status_t st = comms_rfir_run(h_, in.data(), in.size(), out.data());
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    std::string kernel(size_t n) const {  // "rfir_decim_kernel<..>", or "series: ..." (the four launches)
+        char name[160] = {0};
+        comms_rfir_get_kernel(h_, n, name, sizeof name);
+        return name;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_rfir_t* h_ = nullptr;
+    size_t rate_;
+};
+
 // ---------------------------------------------------------------- mixer
 class MixerNode : public DeriveNode<MixerNode> {
 public:
@@ -1185,6 +1222,39 @@ public:
 
 private:
     comms_chain_t* h_ = nullptr;
+    size_t rate_;
+    int device_;
+    DevStream st_;
+};
+
+// The real FIR + decimator on device-resident messages (the angles a ChainNodeDev<float> sends never leave the device)
+class RealFirDecimNodeDev : public DeriveNode<RealFirDecimNodeDev> {
+public:
+    NodeReceiver<DeviceBuf<float>> input;
+    NodeSender<DeviceBuf<float>> output;
+    RealFirDecimNodeDev(const std::vector<float>& taps, size_t rate, const std::optional<std::vector<float>>& state = std::nullopt,
+                        int device = 0)
+        : rate_(rate), device_(device), st_(device) {
+        throw_on(comms_rfir_create(taps.data(), taps.size(), state ? state->data() : nullptr, state ? state->size() : 0, rate,
+                                   device, &h_),
+                 "RealFirDecimNodeDev::new");
+    }
+    RealFirDecimNodeDev(RealFirDecimNodeDev&& o) noexcept
+        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), rate_(o.rate_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
+    ~RealFirDecimNodeDev() { comms_rfir_destroy(h_); }
+    Result<DeviceBuf<float>> run(const DeviceBuf<float>& in) {
+        size_t m = 0;
+        comms_rfir_out_len(in.size(), rate_, &m);
+        DeviceBuf<float> out(m, device_);
+        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_rfir_run_dev(h_, in.ptr(), in.size(), out.ptr(), s); });
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_rfir_t* h_ = nullptr;
     size_t rate_;
     int device_;
     DevStream st_;

@@ -723,6 +723,57 @@ class ChainNode(_Handle):
 
 
 # ------------------------------------------------------------------ tap design
+class RealFirDecimNode(_Handle):
+    """Real FIR with decimation (comms_rfir_*): the audio stage of examples/fm_radio.rs:98-164 -- Convert2Node ->
+    BatchFirNode<f32> -> Convert3Node -> DecimateNode<f32>(rate) -- as one node over an f32 stream.  Any batch length:
+    the decimator restarts at sample 0 of every call, the FIR history advances by all samples."""
+    _destroy = "comms_rfir_destroy"
+
+    def __init__(self, taps, rate, state=None, device=0):
+        super().__init__()
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self.rate = int(rate)
+        if state is None:
+            check(lib().comms_rfir_create(_ptr(taps), taps.size, None, 0, self.rate, device, C.byref(self._h)))
+        else:
+            state = np.ascontiguousarray(state, dtype=np.float32)
+            check(lib().comms_rfir_create(_ptr(taps), taps.size, _ptr(state), state.size, self.rate, device, C.byref(self._h)))
+
+    def out_len(self, n):
+        m = C.c_size_t()
+        check(lib().comms_rfir_out_len(n, self.rate, C.byref(m)))
+        return m.value
+
+    def kernel(self, n):
+        """What a batch of n samples is run by: "rfir_decim_kernel<..>", or "series: ..." (the four launches)."""
+        buf = C.create_string_buffer(160)
+        check(lib().comms_rfir_get_kernel(self._h, n, buf, 160))
+        return buf.value.decode()
+
+    def run(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        out = np.empty(self.out_len(x.size), np.float32)
+        check(lib().comms_rfir_run(self._h, _ptr(x), x.size, _ptr(out)))
+        return out
+
+    def run_dev(self, in_ptr, n, out_ptr, stream=0):
+        check(lib().comms_rfir_run_dev(self._h, in_ptr, n, out_ptr, stream))
+
+    def get_state(self, n_state):
+        st = np.empty(n_state, np.float32)
+        check(lib().comms_rfir_get_state(self._h, _ptr(st), n_state))
+        return st
+
+    def set_state(self, state):
+        state = np.ascontiguousarray(state, dtype=np.float32)
+        check(lib().comms_rfir_set_state(self._h, _ptr(state), state.size))
+
+    def set_timer(self, timer):
+        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch (the series: its FIR launch)."""
+        check(lib().comms_rfir_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
 def _taps(fn, n_taps, *args):
     out = np.empty(int(n_taps), np.complex64)
     check(fn(int(n_taps), *args, _ptr(out)))
@@ -1006,7 +1057,8 @@ class KernelTimer:
     def attach(self, node):
         name = {"comms_fir_destroy": "comms_fir_set_timer", "comms_mixer_destroy": "comms_mixer_set_timer",
                 "comms_fmdemod_destroy": "comms_fmdemod_set_timer", "comms_fft_destroy": "comms_fft_set_timer",
-                "comms_chain_destroy": "comms_chain_set_timer", "comms_pulse_destroy": "comms_pulse_set_timer"}[node._destroy]
+                "comms_chain_destroy": "comms_chain_set_timer", "comms_pulse_destroy": "comms_pulse_set_timer",
+                "comms_rfir_destroy": "comms_rfir_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

@@ -462,6 +462,47 @@ impl<T: FloatSample> Default for FMDemodNode<T> {
     fn default() -> Self { Self::new() }   // the reference derives Default (analog_node.rs:18)
 }
 
+/// Real FIR with decimation over an `f32` stream (an additional node): what examples/fm_radio.rs:98-164 wires as
+/// `Convert2Node -> BatchFirNode<f32> -> Convert3Node -> DecimateNode<f32>`, for real taps, as one node.  `state`
+/// as `BatchFirNode::new` takes it (newest first; `zip` truncation); any batch length, `ceil(n / rate)` outputs.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct RealFirDecimNode {
+    pub input: NodeReceiver<Vec<f32>>,
+    h: *mut comms_rfir_t,
+    rate: usize,
+    pub output: NodeSender<Vec<f32>>,
+}
+unsafe impl Send for RealFirDecimNode {}
+impl Drop for RealFirDecimNode {
+    fn drop(&mut self) { unsafe { comms_rfir_destroy(self.h); } }
+}
+impl RealFirDecimNode {
+    pub fn new(taps: Vec<f32>, rate: usize, state: Option<Vec<f32>>) -> Self {
+        let mut h = ptr::null_mut();
+        let (sp, sn) = match &state {
+            Some(s) => (s.as_ptr(), s.len()),
+            None => (ptr::null(), 0),
+        };
+        let st = unsafe { comms_rfir_create(taps.as_ptr(), taps.len(), sp, sn, rate, 0, &mut h) };
+        assert_eq!(st, COMMS_OK, "comms_rfir_create failed");
+        RealFirDecimNode { input: Default::default(), h, rate, output: Default::default() }
+    }
+    pub fn run(&mut self, samples: &[f32]) -> Result<Vec<f32>, NodeError> {
+        let mut m = 0usize;
+        unsafe { comms_rfir_out_len(samples.len(), self.rate, &mut m); }
+        let mut out = vec![0f32; m];
+        let st = unsafe { comms_rfir_run(self.h, samples.as_ptr(), samples.len(), out.as_mut_ptr()) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    /// The checkpoint hook: the last `n` input samples, newest first
+    pub fn state(&mut self, n: usize) -> Result<Vec<f32>, NodeError> {
+        let mut out = vec![0f32; n];
+        let st = unsafe { comms_rfir_get_state(self.h, out.as_mut_ptr(), n) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
 /// fft_node.rs:28-84
 #[derive(Node)]
 #[pass_by_ref]
