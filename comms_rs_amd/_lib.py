@@ -202,6 +202,23 @@ _PROTOS = {
     "comms_prns_skip": [_vp, _u64],
     "comms_prns_set_timer": [_vp, _vp],
     "comms_prns_destroy": [_vp],
+    "comms_noise_create": [_u64, _u64, _i32, _pp],
+    "comms_noise_get_pos": [_vp, C.POINTER(_u64)],
+    "comms_noise_set_pos": [_vp, _u64],
+    "comms_noise_skip": [_vp, _u64],
+    "comms_noise_bits_run": [_vp, _sz, _i32, _vp],
+    "comms_noise_bits_run_dev": [_vp, _sz, _i32, _vp, _vp],
+    "comms_noise_uniform_run": [_vp, _sz, C.c_float, C.c_float, _vp],
+    "comms_noise_uniform_run_dev": [_vp, _sz, C.c_float, C.c_float, _vp, _vp],
+    "comms_noise_normal_run": [_vp, _sz, _f64, _f64, _vp],
+    "comms_noise_normal_run_dev": [_vp, _sz, _f64, _f64, _vp, _vp],
+    "comms_noise_normal_f64_run": [_vp, _sz, _f64, _f64, _vp],
+    "comms_noise_normal_f64_run_dev": [_vp, _sz, _f64, _f64, _vp, _vp],
+    "comms_awgn_run": [_vp, _vp, _sz, C.c_float, _vp],
+    "comms_awgn_run_dev": [_vp, _vp, _sz, C.c_float, _vp, _vp],
+    "comms_awgn_set_input_format": [_vp, _i32, C.c_float],
+    "comms_noise_set_timer": [_vp, _vp],
+    "comms_noise_destroy": [_vp],
     "comms_frequency_offset_estimate": [_vp, _sz, C.POINTER(_f64), _i32],
     "comms_psk_phase_estimate": [_vp, _sz, _u32, C.POINTER(_f64), _i32],
     "comms_qam_phase_estimate": [_vp, _sz, C.POINTER(_f64), _i32],

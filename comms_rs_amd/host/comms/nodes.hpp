@@ -12,6 +12,7 @@
 //   TimingEstimatorNode::new(n, d, alpha)         src/demodulation/timing_estimator.rs:123
 //   NcoNode::new(dphase, phase) (block form)      src/demodulation/nco.rs:118
 //   PrnsNode::new(poly_mask, state)               src/prns.rs:93-137
+//   NormalNode::new(mu, std_dev), UniformNode<T>::new(start, end), random_bit()   src/util/rand_node.rs:60, :124, :150
 // Messages are host vectors (std::vector<Complex>), moved through the channels by
 // value as in the reference; every run() goes H2D -> kernel -> D2H through the C
 // ABI.  The *Dev variants at the bottom keep messages device-resident
@@ -22,8 +23,11 @@
 // reference panics in the same places); there is no CPU fallback.
 #pragma once
 
+#include <cmath>
 #include <complex>
 #include <cstring>
+#include <optional>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -433,6 +437,145 @@ private:
     std::vector<uint8_t> buf_;
     size_t pos_ = 0;
     uint64_t start_ = 0;  // register at buf_[0]
+};
+
+// ---------------------------------------------------------------- random sources (util/rand_node.rs) and the AWGN channel
+// NormalNode::new(mu, std_dev), UniformNode<T>::new(start, end) and random_bit() with the reference's names and argument
+// order.  The reference seeds a host generator from entropy (StdRng::from_entropy, rand_node.rs:61,125); here the values
+// come from the library's counter-based source (comms_noise_*, stream 0 of `seed`), and without a seed one is drawn from
+// std::random_device.  As source nodes they keep the reference's run(): one value per call, handed out of a block drawn
+// in one launch; run_block(n) returns the next n values of the same sequence in (at most) one launch.
+inline uint64_t entropy_seed() {
+    std::random_device rd;
+    return (static_cast<uint64_t>(rd()) << 32) | static_cast<uint64_t>(rd());
+}
+
+// CRTP base: D::draw(handle, n, out) draws n values (n a multiple of D::kGrain) from the stream position
+template <class D, class T>
+class NoiseSourceNode : public DeriveNode<D> {
+public:
+    NodeSender<T> output;
+    static constexpr size_t kBlock = 4096;
+
+    NoiseSourceNode(std::optional<uint64_t> seed, int device, const char* what) : seed_(seed ? *seed : entropy_seed()) {
+        throw_on(comms_noise_create(seed_, 0, device, &h_), what);
+    }
+    NoiseSourceNode(NoiseSourceNode&& o) noexcept
+        : output(std::move(o.output)), h_(o.h_), seed_(o.seed_), buf_(std::move(o.buf_)), pos_(o.pos_) { o.h_ = nullptr; }
+    ~NoiseSourceNode() { comms_noise_destroy(h_); }
+
+    Result<T> run() {
+        if (pos_ == buf_.size()) {
+            comms_status_t st = refill(kBlock);
+            if (st != COMMS_OK) return to_node_error(st);
+        }
+        return buf_[pos_++];
+    }
+    // the next n values of the sequence run() hands out, drawn in one launch (what is left of run()'s block goes first)
+    Result<std::vector<T>> run_block(size_t n) {
+        std::vector<T> out(buf_.begin() + static_cast<std::ptrdiff_t>(pos_), buf_.end());
+        if (out.size() >= n) {
+            out.resize(n);
+            pos_ += n;
+            return out;
+        }
+        const size_t need = n - out.size();
+        comms_status_t st = refill((need + D::kGrain - 1) / D::kGrain * D::kGrain);
+        if (st != COMMS_OK) return to_node_error(st);
+        out.insert(out.end(), buf_.begin(), buf_.begin() + static_cast<std::ptrdiff_t>(need));
+        pos_ = need;
+        return out;
+    }
+    uint64_t seed() const { return seed_; }
+    auto receivers() { return std::tie(); }
+    auto senders() { return std::tie(output); }
+
+protected:
+    comms_noise_t* h_ = nullptr;
+
+private:
+    comms_status_t refill(size_t n) {
+        buf_.resize(n);
+        pos_ = 0;
+        comms_status_t st = static_cast<D&>(*this).draw(n, buf_.data());
+        if (st != COMMS_OK) buf_.clear();
+        return st;
+    }
+    uint64_t seed_;
+    std::vector<T> buf_;
+    size_t pos_ = 0;
+};
+
+class NormalNode : public NoiseSourceNode<NormalNode, double> {
+public:
+    static constexpr size_t kGrain = 1;
+    NormalNode(double mu, double std_dev, std::optional<uint64_t> seed = std::nullopt, int device = 0)
+        : NoiseSourceNode(seed, device, "NormalNode::new"), mu_(mu), sd_(std_dev) {
+        if (!(std_dev >= 0.0) || !std::isfinite(std_dev) || !std::isfinite(mu)) throw std::runtime_error("NormalNode::new: std_dev < 0 or not finite");
+    }
+    comms_status_t draw(size_t n, double* out) { return comms_noise_normal_f64_run(h_, n, mu_, sd_, out); }
+
+private:
+    double mu_, sd_;
+};
+
+template <class T>
+class UniformNode;
+
+// UniformNode<f32>: values in [start, end)
+template <>
+class UniformNode<float> : public NoiseSourceNode<UniformNode<float>, float> {
+public:
+    static constexpr size_t kGrain = 1;
+    UniformNode(float start, float end, std::optional<uint64_t> seed = std::nullopt, int device = 0)
+        : NoiseSourceNode(seed, device, "UniformNode::new"), lo_(start), hi_(end) {
+        if (!(start < end) || !std::isfinite(start) || !std::isfinite(end)) throw std::runtime_error("UniformNode::new: start >= end");  // Uniform::new panics
+    }
+    comms_status_t draw(size_t n, float* out) { return comms_noise_uniform_run(h_, n, lo_, hi_, out); }
+
+private:
+    float lo_, hi_;
+};
+
+// UniformNode<u8> over [0, 2): what random_bit() returns (rand_node.rs:150-152) -- the bit draw of the source
+template <>
+class UniformNode<uint8_t> : public NoiseSourceNode<UniformNode<uint8_t>, uint8_t> {
+public:
+    static constexpr size_t kGrain = 32;  // a bit draw consumes whole 32-bit words
+    UniformNode(uint8_t start, uint8_t end, std::optional<uint64_t> seed = std::nullopt, int device = 0)
+        : NoiseSourceNode(seed, device, "UniformNode::new") {
+        if (start != 0 || end != 2) throw std::runtime_error("UniformNode<u8>::new: only the range [0, 2) of random_bit() is implemented");
+    }
+    comms_status_t draw(size_t n, uint8_t* out) { return comms_noise_bits_run(h_, n, COMMS_BITS_U8, out); }
+};
+
+inline UniformNode<uint8_t> random_bit(std::optional<uint64_t> seed = std::nullopt, int device = 0) {
+    return UniformNode<uint8_t>(0, 2, seed, device);
+}
+
+// AWGN channel (an additional node): out = in + sigma * (z + i z'), one complex standard pair per sample, the pairs of
+// consecutive messages consecutive in the source's stream (comms_awgn_run)
+class AwgnNode : public DeriveNode<AwgnNode> {
+public:
+    NodeReceiver<std::vector<Complex32>> input;
+    NodeSender<std::vector<Complex32>> output;
+    AwgnNode(float sigma, std::optional<uint64_t> seed = std::nullopt, uint64_t stream = 0, int device = 0) : sigma_(sigma) {
+        throw_on(comms_noise_create(seed ? *seed : entropy_seed(), stream, device, &h_), "AwgnNode::new");
+    }
+    AwgnNode(AwgnNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sigma_(o.sigma_) { o.h_ = nullptr; }
+    ~AwgnNode() { comms_noise_destroy(h_); }
+    Result<std::vector<Complex32>> run(const std::vector<Complex32>& in) {
+        std::vector<Complex32> out(in.size());
+        comms_status_t st = comms_awgn_run(h_, in.data(), in.size(), sigma_, c32(out.data()));
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_noise_t* h_ = nullptr;
+    float sigma_;
 };
 
 // ---------------------------------------------------------------- a digital link from bits to bits (additional nodes)
@@ -1256,6 +1399,35 @@ public:
 private:
     comms_rfir_t* h_ = nullptr;
     size_t rate_;
+    int device_;
+    DevStream st_;
+};
+
+// AWGN channel on device-resident messages: wait_ready(in) -> comms_awgn_run_dev on the node's stream -> record_use(in),
+// record_ready(out) -> send(out), the ordering of every *Dev node
+class AwgnNodeDev : public DeriveNode<AwgnNodeDev> {
+public:
+    NodeReceiver<DeviceBuf<Complex32>> input;
+    NodeSender<DeviceBuf<Complex32>> output;
+    AwgnNodeDev(float sigma, std::optional<uint64_t> seed = std::nullopt, uint64_t stream = 0, int device = 0)
+        : sigma_(sigma), device_(device), st_(device) {
+        throw_on(comms_noise_create(seed ? *seed : entropy_seed(), stream, device, &h_), "AwgnNodeDev::new");
+    }
+    AwgnNodeDev(AwgnNodeDev&& o) noexcept
+        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sigma_(o.sigma_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
+    ~AwgnNodeDev() { comms_noise_destroy(h_); }
+    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& in) {
+        DeviceBuf<Complex32> out(in.size(), device_);
+        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_awgn_run_dev(h_, in.ptr(), in.size(), sigma_, c32(out.ptr()), s); });
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_noise_t* h_ = nullptr;
+    float sigma_;
     int device_;
     DevStream st_;
 };

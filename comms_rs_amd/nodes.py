@@ -944,6 +944,85 @@ class PrnsNode(_Handle):
         return self
 
 
+# ------------------------------------------------------------------ seeded noise source / AWGN channel
+class NoiseSource(_Handle):
+    """comms_noise_*: the counter-based source (Philox4x32-10 of (seed, stream); include/comms_hip.h has the contract)
+    behind NormalNode / UniformNode / random_bit (util/rand_node.rs:26-152) and the AWGN channel node.  `pos` is the
+    position in 32-bit stream words, kept on the host: reading, setting and skip(n) never wait for the device."""
+    _destroy = "comms_noise_destroy"
+
+    def __init__(self, seed, stream=0, device=0):
+        super().__init__()
+        self._fmt = "c32"
+        check(lib().comms_noise_create(int(seed), int(stream), device, C.byref(self._h)))
+
+    @property
+    def pos(self):
+        v = C.c_uint64()
+        check(lib().comms_noise_get_pos(self._h, C.byref(v)))
+        return v.value
+
+    @pos.setter
+    def pos(self, value):
+        check(lib().comms_noise_set_pos(self._h, int(value)))
+
+    def skip(self, n_words):
+        check(lib().comms_noise_skip(self._h, int(n_words)))
+        return self
+
+    def set_timer(self, timer):
+        check(lib().comms_noise_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+    def bits(self, n, packed=False):
+        """The next n bits: uint8 0 / 1 per bit, or packed LSB first (the PRNS layout)."""
+        n = int(n)
+        out = np.empty((n + 7) // 8 if packed else n, np.uint8)
+        check(lib().comms_noise_bits_run(self._h, n, _lib.BITS_PACKED if packed else _lib.BITS_U8, _ptr(out)))
+        return out
+
+    def bits_dev(self, n, out_ptr, packed=False, stream=0):
+        check(lib().comms_noise_bits_run_dev(self._h, int(n), _lib.BITS_PACKED if packed else _lib.BITS_U8, out_ptr, stream))
+
+    def uniform(self, n, lo=0.0, hi=1.0):
+        out = np.empty(int(n), np.float32)
+        check(lib().comms_noise_uniform_run(self._h, out.size, lo, hi, _ptr(out)))
+        return out
+
+    def uniform_dev(self, n, out_ptr, lo=0.0, hi=1.0, stream=0):
+        check(lib().comms_noise_uniform_run_dev(self._h, int(n), lo, hi, out_ptr, stream))
+
+    def normal(self, n, mu=0.0, sd=1.0, dtype=np.float32):
+        """mu + sd * z as float32, or with dtype=np.float64 the f64 form (the f32 z widened)."""
+        out = np.empty(int(n), dtype)
+        fn = lib().comms_noise_normal_f64_run if out.dtype == np.float64 else lib().comms_noise_normal_run
+        check(fn(self._h, out.size, float(mu), float(sd), _ptr(out)))
+        return out
+
+    def normal_dev(self, n, out_ptr, mu=0.0, sd=1.0, f64=False, stream=0):
+        fn = lib().comms_noise_normal_f64_run_dev if f64 else lib().comms_noise_normal_run_dev
+        check(fn(self._h, int(n), float(mu), float(sd), out_ptr, stream))
+
+    def set_input_format(self, fmt, scale=1.0):
+        """Input of awgn(): "c32" (default) or "i16" pairs times `scale`, converted in the kernel's load stage."""
+        if fmt not in ("c32", "i16"):
+            raise ValueError("the AWGN node reads 'c32' or 'i16'")
+        check(lib().comms_awgn_set_input_format(self._h, _IQ[fmt][0], scale))
+        self._fmt = fmt
+        return self
+
+    def awgn(self, x, sigma):
+        """x + sigma * (z + i z'), one complex standard pair per sample."""
+        a, n = _as_input(x, self._fmt)
+        out = np.empty(n, np.complex64)
+        check(lib().comms_awgn_run(self._h, _ptr(a), n, sigma, _ptr(out)))
+        return out
+
+    def awgn_dev(self, in_ptr, n, sigma, out_ptr, stream=0):
+        """Device pointers; in_ptr == out_ptr (in place) is allowed with c32 input."""
+        check(lib().comms_awgn_run_dev(self._h, in_ptr, int(n), sigma, out_ptr, stream))
+
+
 # ------------------------------------------------------------------ block estimators
 def frequency_offset_estimate(samples, device=0):
     """frequency_estimator.rs:27-42 on Complex<f64> samples."""
@@ -1058,7 +1137,7 @@ class KernelTimer:
         name = {"comms_fir_destroy": "comms_fir_set_timer", "comms_mixer_destroy": "comms_mixer_set_timer",
                 "comms_fmdemod_destroy": "comms_fmdemod_set_timer", "comms_fft_destroy": "comms_fft_set_timer",
                 "comms_chain_destroy": "comms_chain_set_timer", "comms_pulse_destroy": "comms_pulse_set_timer",
-                "comms_rfir_destroy": "comms_rfir_set_timer"}[node._destroy]
+                "comms_rfir_destroy": "comms_rfir_set_timer", "comms_noise_destroy": "comms_noise_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

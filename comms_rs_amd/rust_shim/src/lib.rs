@@ -26,6 +26,7 @@
 //! | `MixerNode<T>` | mixer.rs:93 | `f32`, `f64` (`MixerSample`) |
 //! | `FFTBatchNode<T>`, `FFTSampleNode<T>`, `FMDemodNode<T>` | fft_node.rs:28,104; analog_node.rs:20 | `f32`, `f64` (`FloatSample`) |
 //! | `DecimateNode<T>`, `UpsampleNode<T>` | resample_node.rs:10,74 | any `Copy + Send` type of 1, 2, 4, 8 or 16 bytes |
+//! | `UniformNode<T>`, `random_bit()`, `NormalNode` | rand_node.rs:26,98,150 | `f32`, and `u8` over `[0, 2)` (`UniformSample`); plus `with_seed` |
 pub mod ffi;
 
 use comms_rs::prelude::*;
@@ -499,6 +500,170 @@ impl RealFirDecimNode {
     pub fn state(&mut self, n: usize) -> Result<Vec<f32>, NodeError> {
         let mut out = vec![0f32; n];
         let st = unsafe { comms_rfir_get_state(self.h, out.as_mut_ptr(), n) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
+/// Sample types `UniformNode<T>` is built for: `f32` (values in `[start, end)`) and `u8` over `[0, 2)`, which is what
+/// `random_bit()` returns (rand_node.rs:150-152).
+pub trait UniformSample: Copy + Send + 'static {
+    #[doc(hidden)] unsafe fn draw(h: *mut comms_noise_t, n: usize, lo: Self, hi: Self, out: *mut Self) -> comms_status_t;
+    #[doc(hidden)] fn range_ok(lo: Self, hi: Self) -> bool;
+    #[doc(hidden)] const GRAIN: usize;
+}
+impl UniformSample for f32 {
+    unsafe fn draw(h: *mut comms_noise_t, n: usize, lo: f32, hi: f32, out: *mut f32) -> comms_status_t { comms_noise_uniform_run(h, n, lo, hi, out) }
+    fn range_ok(lo: f32, hi: f32) -> bool { lo < hi && lo.is_finite() && hi.is_finite() }
+    const GRAIN: usize = 1;
+}
+impl UniformSample for u8 {
+    unsafe fn draw(h: *mut comms_noise_t, n: usize, _lo: u8, _hi: u8, out: *mut u8) -> comms_status_t { comms_noise_bits_run(h, n, COMMS_BITS_U8, out) }
+    fn range_ok(lo: u8, hi: u8) -> bool { lo == 0 && hi == 2 }
+    const GRAIN: usize = 32; // a bit draw consumes whole 32-bit words
+}
+
+/// Seed of a node built without one: the reference seeds from entropy (`StdRng::from_entropy`, rand_node.rs:61,125).
+fn entropy_seed() -> u64 {
+    use std::collections::hash_map::RandomState;
+    use std::hash::{BuildHasher, Hasher};
+    let mut h = RandomState::new().build_hasher(); // keyed from the operating system's entropy, per instance
+    h.write_u64(std::time::SystemTime::now().duration_since(std::time::UNIX_EPOCH).map(|d| d.as_nanos() as u64).unwrap_or(0));
+    h.finish()
+}
+
+const NOISE_BLOCK: usize = 4096; // values drawn per launch behind the per-call `run()`
+
+/// rand_node.rs:26-75.  `new(start, end)` as the reference (seeded from entropy) plus `with_seed`: the values are those
+/// of the library's counter-based source (include/comms_hip.h, "seeded noise source"), stream 0 of the seed.  `run()`
+/// hands out one value per call from a block drawn in one launch; `run_block(n)` returns the next `n` values.
+#[derive(Node)]
+pub struct UniformNode<T>
+where
+    T: UniformSample,
+{
+    h: *mut comms_noise_t,
+    lo: T,
+    hi: T,
+    buf: Vec<T>,
+    pos: usize,
+    pub output: NodeSender<T>,
+}
+unsafe impl<T: UniformSample> Send for UniformNode<T> {}
+impl<T: UniformSample> Drop for UniformNode<T> {
+    fn drop(&mut self) { unsafe { comms_noise_destroy(self.h); } }
+}
+impl<T> UniformNode<T>
+where
+    T: UniformSample,
+{
+    pub fn new(start: T, end: T) -> Self { Self::with_seed(start, end, entropy_seed()) }
+    pub fn with_seed(start: T, end: T, seed: u64) -> Self {
+        assert!(T::range_ok(start, end), "Uniform::new called with `low >= high`"); // rand's own panic
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_noise_create(seed, 0, 0, &mut h) };
+        assert_eq!(st, COMMS_OK, "comms_noise_create failed");
+        UniformNode { h, lo: start, hi: end, buf: Vec::new(), pos: 0, output: Default::default() }
+    }
+    fn refill(&mut self, n: usize, fill: T) -> Result<(), NodeError> {
+        self.buf.clear();
+        self.buf.resize(n, fill);
+        self.pos = 0;
+        let st = unsafe { T::draw(self.h, n, self.lo, self.hi, self.buf.as_mut_ptr()) };
+        if st == COMMS_OK { Ok(()) } else { self.buf.clear(); Err(to_err(st)) }
+    }
+    pub fn run(&mut self) -> Result<T, NodeError> {
+        if self.pos == self.buf.len() { let lo = self.lo; self.refill(NOISE_BLOCK, lo)?; }
+        self.pos += 1;
+        Ok(self.buf[self.pos - 1])
+    }
+    pub fn run_block(&mut self, n: usize) -> Result<Vec<T>, NodeError> {
+        let mut out: Vec<T> = self.buf[self.pos..].to_vec();
+        if out.len() >= n { out.truncate(n); self.pos += n; return Ok(out); }
+        let need = n - out.len();
+        let lo = self.lo;
+        self.refill((need + T::GRAIN - 1) / T::GRAIN * T::GRAIN, lo)?;
+        out.extend_from_slice(&self.buf[..need]);
+        self.pos = need;
+        Ok(out)
+    }
+}
+
+/// rand_node.rs:150-152
+pub fn random_bit() -> UniformNode<u8> { UniformNode::new(0u8, 2u8) }
+pub fn random_bit_with_seed(seed: u64) -> UniformNode<u8> { UniformNode::with_seed(0u8, 2u8, seed) }
+
+/// rand_node.rs:97-139: `f64` messages, `mu + std_dev * z` with the f32 `z` of the source widened.
+#[derive(Node)]
+pub struct NormalNode {
+    h: *mut comms_noise_t,
+    mu: f64,
+    sd: f64,
+    buf: Vec<f64>,
+    pos: usize,
+    pub output: NodeSender<f64>,
+}
+unsafe impl Send for NormalNode {}
+impl Drop for NormalNode {
+    fn drop(&mut self) { unsafe { comms_noise_destroy(self.h); } }
+}
+impl NormalNode {
+    pub fn new(mu: f64, std_dev: f64) -> NormalNode { Self::with_seed(mu, std_dev, entropy_seed()) }
+    pub fn with_seed(mu: f64, std_dev: f64, seed: u64) -> NormalNode {
+        assert!(std_dev >= 0.0 && std_dev.is_finite() && mu.is_finite(), "Normal::new called with `std_dev` < 0"); // rand's own panic
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_noise_create(seed, 0, 0, &mut h) };
+        assert_eq!(st, COMMS_OK, "comms_noise_create failed");
+        NormalNode { h, mu, sd: std_dev, buf: Vec::new(), pos: 0, output: Default::default() }
+    }
+    fn refill(&mut self, n: usize) -> Result<(), NodeError> {
+        self.buf.clear();
+        self.buf.resize(n, 0.0);
+        self.pos = 0;
+        let st = unsafe { comms_noise_normal_f64_run(self.h, n, self.mu, self.sd, self.buf.as_mut_ptr()) };
+        if st == COMMS_OK { Ok(()) } else { self.buf.clear(); Err(to_err(st)) }
+    }
+    pub fn run(&mut self) -> Result<f64, NodeError> {
+        if self.pos == self.buf.len() { self.refill(NOISE_BLOCK)?; }
+        self.pos += 1;
+        Ok(self.buf[self.pos - 1])
+    }
+    pub fn run_block(&mut self, n: usize) -> Result<Vec<f64>, NodeError> {
+        let mut out: Vec<f64> = self.buf[self.pos..].to_vec();
+        if out.len() >= n { out.truncate(n); self.pos += n; return Ok(out); }
+        let need = n - out.len();
+        self.refill(need)?;
+        out.extend_from_slice(&self.buf[..need]);
+        self.pos = need;
+        Ok(out)
+    }
+}
+
+/// AWGN channel (an additional node): `out = in + sigma * (z + i z')`, one complex standard pair per sample, consecutive
+/// across messages (comms_awgn_run).
+#[derive(Node)]
+#[pass_by_ref]
+pub struct AwgnNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    h: *mut comms_noise_t,
+    sigma: f32,
+    pub output: NodeSender<Vec<Complex<f32>>>,
+}
+unsafe impl Send for AwgnNode {}
+impl Drop for AwgnNode {
+    fn drop(&mut self) { unsafe { comms_noise_destroy(self.h); } }
+}
+impl AwgnNode {
+    pub fn new(sigma: f32) -> Self { Self::with_seed(sigma, entropy_seed(), 0) }
+    pub fn with_seed(sigma: f32, seed: u64, stream: u64) -> Self {
+        assert!(sigma >= 0.0 && sigma.is_finite(), "sigma must be finite and >= 0");
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_noise_create(seed, stream, 0, &mut h) };
+        assert_eq!(st, COMMS_OK, "comms_noise_create failed");
+        AwgnNode { input: Default::default(), h, sigma, output: Default::default() }
+    }
+    pub fn run(&mut self, samples: &[Complex<f32>]) -> Result<Vec<Complex<f32>>, NodeError> {
+        let mut out = czeros::<f32>(samples.len());
+        let st = unsafe { comms_awgn_run(self.h, samples.as_ptr() as *const c_void, samples.len(), self.sigma, out.as_mut_ptr()) };
         if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
     }
 }
