@@ -73,18 +73,18 @@ __global__ __launch_bounds__(256) void mixer_kernel(const float2* __restrict__ i
 
 // Mixer::mix::<f64> -- the instantiation the reference's own mixer tests use (src/mixer.rs:160-246, :250-336):
 // the casts to and from f64 are identities, so the output is the f64 product itself.  One double2 (16 B) per lane.
+// Every sample's rotor is evaluated in closed form from its own phase (one f64 sincos per sample; its cost has not been
+// measured, this kernel is in no benchmark): a rotor stepped from sweep to sweep carries the rounding of its steps, which an f64 output shows in its
+// last bits -- a sample then depended on where in the batch it sat, and a long host call cut into chunks (run_host_units)
+// differed from the same call in one piece (tests/test_gpu_host_pipeline.py, mixer_f64).
 __global__ __launch_bounds__(256) void mixer_f64_kernel(const double2* __restrict__ in, double2* __restrict__ out,
-                                                        size_t n, uint64_t turns0, uint64_t frac, double sweep_c,
-                                                        double sweep_s) {
+                                                        size_t n, uint64_t turns0, uint64_t frac) {
     const size_t nthreads = static_cast<size_t>(gridDim.x) * blockDim.x;
-    const size_t gid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (gid >= n) return;
-    double c, s;
-    rotor_at(turns0 + static_cast<uint64_t>(gid) * frac, c, s);
-    for (size_t g = gid; g < n; g += nthreads) {
+    for (size_t g = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; g < n; g += nthreads) {
+        double c, s;
+        rotor_at(turns0 + static_cast<uint64_t>(g) * frac, c, s);
         const double2 x = in[g];
         out[g] = make_double2(x.x * c - x.y * s, x.x * s + x.y * c);
-        rot_step(c, s, sweep_c, sweep_s);
     }
 }
 
@@ -403,11 +403,9 @@ comms_status_t comms_mixer_run_f64_dev(comms_mixer_t* h, const comms_c64* d_in, 
     if (!n) return COMMS_OK;
     hipStream_t s = h->pick(stream);
     unsigned blocks = grid_for(n, 256, 8 * kNumCU);
-    double sc, ss;
-    host_rotor(static_cast<uint64_t>(blocks) * 256u * h->frac, sc, ss);
     h->tic(s);
     mixer_f64_kernel<<<dim3(blocks), dim3(256), 0, s>>>(reinterpret_cast<const double2*>(d_in),
-                                                       reinterpret_cast<double2*>(d_out), n, h->turns, h->frac, sc, ss);
+                                                       reinterpret_cast<double2*>(d_out), n, h->turns, h->frac);
     h->toc(s);
     COMMS_TRY(launch_ok("mixer_f64_kernel"));
     h->turns += static_cast<uint64_t>(n) * h->frac;
