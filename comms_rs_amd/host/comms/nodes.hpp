@@ -95,123 +95,136 @@ private:
     size_t count_ = 0;
 };
 
-// ---------------------------------------------------------------- FIR
-class BatchFirNode : public DeriveNode<BatchFirNode> {
-public:
-    NodeReceiver<std::vector<Complex32>> input;
-    NodeSender<std::vector<Complex32>> output;
-
-    BatchFirNode(const std::vector<Complex32>& taps, const std::optional<std::vector<Complex32>>& state = std::nullopt,
-                 int device = 0) {
-        throw_on(comms_fir_create(c32(taps.data()), taps.size(), state ? c32(state->data()) : nullptr,
-                                  state ? state->size() : 0, device, &h_),
-                 "BatchFirNode::new");
-    }
-    BatchFirNode(BatchFirNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~BatchFirNode() { comms_fir_destroy(h_); }
-
-    Result<std::vector<Complex32>> run(const std::vector<Complex32>& in) {
-        std::vector<Complex32> out(in.size());
-        comms_status_t st = comms_fir_run(h_, c32(in.data()), in.size(), c32(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-    comms_fir_t* handle() const { return h_; }
-
-private:
-    comms_fir_t* h_ = nullptr;
-};
-
-class FirNode : public DeriveNode<FirNode> {
-public:
-    NodeReceiver<Complex32> input;
-    NodeSender<Complex32> output;
-
-    FirNode(const std::vector<Complex32>& taps, const std::optional<std::vector<Complex32>>& state = std::nullopt,
-            int device = 0) {
-        throw_on(comms_fir_create(c32(taps.data()), taps.size(), state ? c32(state->data()) : nullptr,
-                                  state ? state->size() : 0, device, &h_),
-                 "FirNode::new");
-    }
-    FirNode(FirNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FirNode() { comms_fir_destroy(h_); }
-
-    Result<Complex32> run(const Complex32& in) {
-        Complex32 out;
-        comms_status_t st = comms_fir_run(h_, c32(&in), 1, c32(&out));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    // the samples already queued behind the first one, in one launch (DeriveNode::call): the
-    // filter's state runs through the block exactly as through the same samples one by one
-    Result<std::vector<Complex32>> run_block(const std::vector<Complex32>& ins) {
-        std::vector<Complex32> out(ins.size());
-        comms_status_t st = comms_fir_run(h_, c32(ins.data()), ins.size(), c32(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_fir_t* h_ = nullptr;
-};
-
-// ---------------------------------------------------------------- Complex<i16> instantiations
-// FirNode<i16> / BatchFirNode<i16> / PulseNode<i16>: the reference's nodes are generic over the sample type and its own
-// tests run on Complex<i16> (fir_node.rs:259-313, pulse.rs:129-183); wrapping arithmetic (comms_fir_i16_*).
+// ---------------------------------------------------------------- sample types
+// What the C ABI offers per sample type, as the Rust shim's FirSample / MixSample / SpectralSample traits have it: the
+// interleaved {re, im} struct, the handle types and the entry points.  Complex<i16> (wrapping arithmetic) has the FIR and
+// the pulse shaper only.
 using Complex16 = std::complex<int16_t>;
 static_assert(sizeof(Complex16) == sizeof(comms_c16), "Complex<i16> must be interleaved {re, im}");
 inline const comms_c16* c16(const Complex16* p) { return reinterpret_cast<const comms_c16*>(p); }
 inline comms_c16* c16(Complex16* p) { return reinterpret_cast<comms_c16*>(p); }
 
-class BatchFirNodeI16 : public DeriveNode<BatchFirNodeI16> {
+template <class T>
+struct Sample;
+template <>
+struct Sample<Complex32> {
+    using Abi = comms_c32;
+    using Real = float;
+    using Fir = comms_fir_t;
+    using Pulse = comms_pulse_t;
+    using Fft = comms_fft_t;
+    using Fm = comms_fmdemod_t;
+    static constexpr auto fir_create = comms_fir_create;
+    static constexpr auto fir_run = comms_fir_run;
+    static constexpr auto fir_destroy = comms_fir_destroy;
+    static constexpr auto pulse_create = comms_pulse_create;
+    static constexpr auto pulse_run = comms_pulse_run;
+    static constexpr auto pulse_destroy = comms_pulse_destroy;
+    static constexpr auto mixer_run = comms_mixer_run;
+    static constexpr auto fft_create = comms_fft_create;
+    static constexpr auto fft_run = comms_fft_run;
+    static constexpr auto fft_destroy = comms_fft_destroy;
+    static constexpr auto fm_create = comms_fmdemod_create;
+    static constexpr auto fm_run = comms_fmdemod_run;
+    static constexpr auto fm_destroy = comms_fmdemod_destroy;
+};
+template <>
+struct Sample<Complex16> {
+    using Abi = comms_c16;
+    using Fir = comms_fir_i16_t;
+    using Pulse = comms_pulse_i16_t;
+    static constexpr auto fir_create = comms_fir_i16_create;
+    static constexpr auto fir_run = comms_fir_i16_run;
+    static constexpr auto fir_destroy = comms_fir_i16_destroy;
+    static constexpr auto pulse_create = comms_pulse_i16_create;
+    static constexpr auto pulse_run = comms_pulse_i16_run;
+    static constexpr auto pulse_destroy = comms_pulse_i16_destroy;
+};
+template <>
+struct Sample<Complex64> {
+    using Abi = comms_c64;
+    using Real = double;
+    using Fir = comms_fir_f64_t;
+    using Pulse = comms_pulse_f64_t;
+    using Fft = comms_fft_f64_t;
+    using Fm = comms_fmdemod_f64_t;
+    static constexpr auto fir_create = comms_fir_f64_create;
+    static constexpr auto fir_run = comms_fir_f64_run;
+    static constexpr auto fir_destroy = comms_fir_f64_destroy;
+    static constexpr auto pulse_create = comms_pulse_f64_create;
+    static constexpr auto pulse_run = comms_pulse_f64_run;
+    static constexpr auto pulse_destroy = comms_pulse_f64_destroy;
+    static constexpr auto mixer_run = comms_mixer_run_f64;
+    static constexpr auto fft_create = comms_fft_f64_create;
+    static constexpr auto fft_run = comms_fft_f64_run;
+    static constexpr auto fft_destroy = comms_fft_f64_destroy;
+    static constexpr auto fm_create = comms_fmdemod_f64_create;
+    static constexpr auto fm_run = comms_fmdemod_f64_run;
+    static constexpr auto fm_destroy = comms_fmdemod_f64_destroy;
+};
+template <class T>
+const typename Sample<T>::Abi* abi(const T* p) { return reinterpret_cast<const typename Sample<T>::Abi*>(p); }
+template <class T>
+typename Sample<T>::Abi* abi(T* p) { return reinterpret_cast<typename Sample<T>::Abi*>(p); }
+
+// ---------------------------------------------------------------- FIR
+// The node templates below take the public node type D (what DeriveNode wants, and D::kNew names the node when its
+// constructor throws) and the sample type T.  The public names follow each group.
+template <class D, class T>
+class BatchFirNodeOf : public DeriveNode<D> {
+    using S = Sample<T>;
+
 public:
-    NodeReceiver<std::vector<Complex16>> input;
-    NodeSender<std::vector<Complex16>> output;
-    BatchFirNodeI16(const std::vector<Complex16>& taps, const std::optional<std::vector<Complex16>>& state = std::nullopt,
-                    int device = 0) {
-        throw_on(comms_fir_i16_create(c16(taps.data()), taps.size(), state ? c16(state->data()) : nullptr,
-                                      state ? state->size() : 0, device, &h_),
-                 "BatchFirNode<i16>::new");
+    NodeReceiver<std::vector<T>> input;
+    NodeSender<std::vector<T>> output;
+
+    BatchFirNodeOf(const std::vector<T>& taps, const std::optional<std::vector<T>>& state = std::nullopt, int device = 0) {
+        throw_on(S::fir_create(abi(taps.data()), taps.size(), state ? abi(state->data()) : nullptr, state ? state->size() : 0, device, &h_),
+                 D::kNew);
     }
-    BatchFirNodeI16(BatchFirNodeI16&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~BatchFirNodeI16() { comms_fir_i16_destroy(h_); }
-    Result<std::vector<Complex16>> run(const std::vector<Complex16>& in) {
-        std::vector<Complex16> out(in.size());
-        comms_status_t st = comms_fir_i16_run(h_, c16(in.data()), in.size(), c16(out.data()));
+    BatchFirNodeOf(BatchFirNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
+    ~BatchFirNodeOf() { S::fir_destroy(h_); }
+
+    Result<std::vector<T>> run(const std::vector<T>& in) {
+        std::vector<T> out(in.size());
+        comms_status_t st = S::fir_run(h_, abi(in.data()), in.size(), abi(out.data()));
         if (st != COMMS_OK) return to_node_error(st);
         return out;
     }
     auto receivers() { return std::tie(input); }
     auto senders() { return std::tie(output); }
+    typename S::Fir* handle() const { return h_; }
 
 private:
-    comms_fir_i16_t* h_ = nullptr;
+    typename S::Fir* h_ = nullptr;
 };
 
-class FirNodeI16 : public DeriveNode<FirNodeI16> {
+template <class D, class T>
+class FirNodeOf : public DeriveNode<D> {
+    using S = Sample<T>;
+
 public:
-    NodeReceiver<Complex16> input;
-    NodeSender<Complex16> output;
-    FirNodeI16(const std::vector<Complex16>& taps, const std::optional<std::vector<Complex16>>& state = std::nullopt, int device = 0) {
-        throw_on(comms_fir_i16_create(c16(taps.data()), taps.size(), state ? c16(state->data()) : nullptr,
-                                      state ? state->size() : 0, device, &h_),
-                 "FirNode<i16>::new");
+    NodeReceiver<T> input;
+    NodeSender<T> output;
+
+    FirNodeOf(const std::vector<T>& taps, const std::optional<std::vector<T>>& state = std::nullopt, int device = 0) {
+        throw_on(S::fir_create(abi(taps.data()), taps.size(), state ? abi(state->data()) : nullptr, state ? state->size() : 0, device, &h_),
+                 D::kNew);
     }
-    FirNodeI16(FirNodeI16&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FirNodeI16() { comms_fir_i16_destroy(h_); }
-    Result<Complex16> run(const Complex16& in) {
-        Complex16 out;
-        comms_status_t st = comms_fir_i16_run(h_, c16(&in), 1, c16(&out));
+    FirNodeOf(FirNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
+    ~FirNodeOf() { S::fir_destroy(h_); }
+
+    Result<T> run(const T& in) {
+        T out;
+        comms_status_t st = S::fir_run(h_, abi(&in), 1, abi(&out));
         if (st != COMMS_OK) return to_node_error(st);
         return out;
     }
-    Result<std::vector<Complex16>> run_block(const std::vector<Complex16>& ins) {  // queued samples in one launch
-        std::vector<Complex16> out(ins.size());
-        comms_status_t st = comms_fir_i16_run(h_, c16(ins.data()), ins.size(), c16(out.data()));
+    // the samples already queued behind the first one, in one launch (DeriveNode::call): the
+    // filter's state runs through the block exactly as through the same samples one by one
+    Result<std::vector<T>> run_block(const std::vector<T>& ins) {
+        std::vector<T> out(ins.size());
+        comms_status_t st = S::fir_run(h_, abi(ins.data()), ins.size(), abi(out.data()));
         if (st != COMMS_OK) return to_node_error(st);
         return out;
     }
@@ -219,171 +232,98 @@ public:
     auto senders() { return std::tie(output); }
 
 private:
-    comms_fir_i16_t* h_ = nullptr;
-};
-
-class PulseNodeI16 : public DeriveNode<PulseNodeI16> {
-public:
-    NodeReceiver<Complex16> input;
-    NodeSender<std::vector<Complex16>> output;
-    PulseNodeI16(const std::vector<Complex16>& taps, size_t sam_per_sym, int device = 0) : sps_(sam_per_sym) {
-        throw_on(comms_pulse_i16_create(c16(taps.data()), taps.size(), sam_per_sym, device, &h_), "PulseNode<i16>::new");
-    }
-    PulseNodeI16(PulseNodeI16&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sps_(o.sps_) { o.h_ = nullptr; }
-    ~PulseNodeI16() { comms_pulse_i16_destroy(h_); }
-    Result<std::vector<Complex16>> run(const Complex16& sym) {
-        std::vector<Complex16> out(sps_);
-        comms_status_t st = comms_pulse_i16_run(h_, c16(&sym), 1, c16(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    Result<std::vector<std::vector<Complex16>>> run_block(const std::vector<Complex16>& syms) {
-        std::vector<Complex16> flat(syms.size() * sps_);
-        comms_status_t st = comms_pulse_i16_run(h_, c16(syms.data()), syms.size(), c16(flat.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        std::vector<std::vector<Complex16>> out(syms.size());
-        for (size_t i = 0; i < syms.size(); ++i) out[i].assign(flat.begin() + i * sps_, flat.begin() + (i + 1) * sps_);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_pulse_i16_t* h_ = nullptr;
-    size_t sps_;
-};
-
-// ---------------------------------------------------------------- Complex<f64> instantiations
-// FirNode<f64> / BatchFirNode<f64> / PulseNode<f64>: the reference's own doc example of batch_fir (fir.rs:68-86) and its timing
-// estimator (timing_estimator.rs:102-103) run on Complex<f64>; the reference's arithmetic operation for operation, outputs
-// bit-identical to it (comms_fir_f64_*, round 5).
-
-class BatchFirNodeF64 : public DeriveNode<BatchFirNodeF64> {
-public:
-    NodeReceiver<std::vector<Complex64>> input;
-    NodeSender<std::vector<Complex64>> output;
-    BatchFirNodeF64(const std::vector<Complex64>& taps, const std::optional<std::vector<Complex64>>& state = std::nullopt,
-                    int device = 0) {
-        throw_on(comms_fir_f64_create(c64(taps.data()), taps.size(), state ? c64(state->data()) : nullptr,
-                                      state ? state->size() : 0, device, &h_),
-                 "BatchFirNode<f64>::new");
-    }
-    BatchFirNodeF64(BatchFirNodeF64&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~BatchFirNodeF64() { comms_fir_f64_destroy(h_); }
-    Result<std::vector<Complex64>> run(const std::vector<Complex64>& in) {
-        std::vector<Complex64> out(in.size());
-        comms_status_t st = comms_fir_f64_run(h_, c64(in.data()), in.size(), c64(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_fir_f64_t* h_ = nullptr;
-};
-
-class FirNodeF64 : public DeriveNode<FirNodeF64> {
-public:
-    NodeReceiver<Complex64> input;
-    NodeSender<Complex64> output;
-    FirNodeF64(const std::vector<Complex64>& taps, const std::optional<std::vector<Complex64>>& state = std::nullopt, int device = 0) {
-        throw_on(comms_fir_f64_create(c64(taps.data()), taps.size(), state ? c64(state->data()) : nullptr,
-                                      state ? state->size() : 0, device, &h_),
-                 "FirNode<f64>::new");
-    }
-    FirNodeF64(FirNodeF64&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FirNodeF64() { comms_fir_f64_destroy(h_); }
-    Result<Complex64> run(const Complex64& in) {
-        Complex64 out;
-        comms_status_t st = comms_fir_f64_run(h_, c64(&in), 1, c64(&out));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    Result<std::vector<Complex64>> run_block(const std::vector<Complex64>& ins) {  // queued samples in one launch
-        std::vector<Complex64> out(ins.size());
-        comms_status_t st = comms_fir_f64_run(h_, c64(ins.data()), ins.size(), c64(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_fir_f64_t* h_ = nullptr;
-};
-
-class PulseNodeF64 : public DeriveNode<PulseNodeF64> {
-public:
-    NodeReceiver<Complex64> input;
-    NodeSender<std::vector<Complex64>> output;
-    PulseNodeF64(const std::vector<Complex64>& taps, size_t sam_per_sym, int device = 0) : sps_(sam_per_sym) {
-        throw_on(comms_pulse_f64_create(c64(taps.data()), taps.size(), sam_per_sym, device, &h_), "PulseNode<f64>::new");
-    }
-    PulseNodeF64(PulseNodeF64&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sps_(o.sps_) { o.h_ = nullptr; }
-    ~PulseNodeF64() { comms_pulse_f64_destroy(h_); }
-    Result<std::vector<Complex64>> run(const Complex64& sym) {
-        std::vector<Complex64> out(sps_);
-        comms_status_t st = comms_pulse_f64_run(h_, c64(&sym), 1, c64(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    Result<std::vector<std::vector<Complex64>>> run_block(const std::vector<Complex64>& syms) {
-        std::vector<Complex64> flat(syms.size() * sps_);
-        comms_status_t st = comms_pulse_f64_run(h_, c64(syms.data()), syms.size(), c64(flat.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        std::vector<std::vector<Complex64>> out(syms.size());
-        for (size_t i = 0; i < syms.size(); ++i) out[i].assign(flat.begin() + i * sps_, flat.begin() + (i + 1) * sps_);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_pulse_f64_t* h_ = nullptr;
-    size_t sps_;
+    typename S::Fir* h_ = nullptr;
 };
 
 // ---------------------------------------------------------------- pulse shaping
-class PulseNode : public DeriveNode<PulseNode> {
+template <class D, class T>
+class PulseNodeOf : public DeriveNode<D> {
+    using S = Sample<T>;
+
 public:
-    NodeReceiver<Complex32> input;
-    NodeSender<std::vector<Complex32>> output;
+    NodeReceiver<T> input;
+    NodeSender<std::vector<T>> output;
 
-    PulseNode(const std::vector<Complex32>& taps, size_t sam_per_sym, int device = 0) : sps_(sam_per_sym) {
-        throw_on(comms_pulse_create(c32(taps.data()), taps.size(), sam_per_sym, device, &h_), "PulseNode::new");
+    PulseNodeOf(const std::vector<T>& taps, size_t sam_per_sym, int device = 0) : sps_(sam_per_sym) {
+        throw_on(S::pulse_create(abi(taps.data()), taps.size(), sam_per_sym, device, &h_), D::kNew);
     }
-    PulseNode(PulseNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sps_(o.sps_) { o.h_ = nullptr; }
-    ~PulseNode() { comms_pulse_destroy(h_); }
+    PulseNodeOf(PulseNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sps_(o.sps_) { o.h_ = nullptr; }
+    ~PulseNodeOf() { S::pulse_destroy(h_); }
 
-    // transmit chain in one launch: the MixerNode::new(dphase, phase) that follows is fused in
-    PulseNode& with_mixer(double dphase, std::optional<double> phase = std::nullopt) {
-        throw_on(comms_pulse_set_mixer(h_, dphase, phase.value_or(0.0)), "PulseNode::with_mixer");
-        return *this;
-    }
-
-    // (the i16 store stage, comms_pulse_set_output_format, is offered on the device-resident node below)
-    Result<std::vector<Complex32>> run(const Complex32& sym) {
-        std::vector<Complex32> out(sps_);
-        comms_status_t st = comms_pulse_run(h_, c32(&sym), 1, c32(out.data()));
+    Result<std::vector<T>> run(const T& sym) {
+        std::vector<T> out(sps_);
+        comms_status_t st = S::pulse_run(h_, abi(&sym), 1, abi(out.data()));
         if (st != COMMS_OK) return to_node_error(st);
         return out;
     }
     // queued symbols in one launch; still one Vec of sam_per_sym samples per symbol downstream
-    Result<std::vector<std::vector<Complex32>>> run_block(const std::vector<Complex32>& syms) {
-        std::vector<Complex32> flat(syms.size() * sps_);
-        comms_status_t st = comms_pulse_run(h_, c32(syms.data()), syms.size(), c32(flat.data()));
+    Result<std::vector<std::vector<T>>> run_block(const std::vector<T>& syms) {
+        std::vector<T> flat(syms.size() * sps_);
+        comms_status_t st = S::pulse_run(h_, abi(syms.data()), syms.size(), abi(flat.data()));
         if (st != COMMS_OK) return to_node_error(st);
-        std::vector<std::vector<Complex32>> out(syms.size());
+        std::vector<std::vector<T>> out(syms.size());
         for (size_t i = 0; i < syms.size(); ++i) out[i].assign(flat.begin() + i * sps_, flat.begin() + (i + 1) * sps_);
         return out;
     }
     auto receivers() { return std::tie(input); }
     auto senders() { return std::tie(output); }
 
+protected:
+    typename S::Pulse* h_ = nullptr;
+
 private:
-    comms_pulse_t* h_ = nullptr;
     size_t sps_;
+};
+
+// f32: every BASELINE config, the tuned kernels (comms_fir_*, comms_pulse_*)
+struct BatchFirNode : BatchFirNodeOf<BatchFirNode, Complex32> {
+    using BatchFirNodeOf::BatchFirNodeOf;
+    static constexpr const char* kNew = "BatchFirNode::new";
+};
+struct FirNode : FirNodeOf<FirNode, Complex32> {
+    using FirNodeOf::FirNodeOf;
+    static constexpr const char* kNew = "FirNode::new";
+};
+struct PulseNode : PulseNodeOf<PulseNode, Complex32> {
+    using PulseNodeOf::PulseNodeOf;
+    static constexpr const char* kNew = "PulseNode::new";
+    // transmit chain in one launch: the MixerNode::new(dphase, phase) that follows is fused in
+    // (the i16 store stage, comms_pulse_set_output_format, is offered on the device-resident node below)
+    PulseNode& with_mixer(double dphase, std::optional<double> phase = std::nullopt) {
+        throw_on(comms_pulse_set_mixer(h_, dphase, phase.value_or(0.0)), "PulseNode::with_mixer");
+        return *this;
+    }
+};
+
+// Complex<i16>: the reference's nodes are generic over the sample type and its own tests run on Complex<i16>
+// (fir_node.rs:259-313, pulse.rs:129-183); wrapping arithmetic (comms_fir_i16_*, comms_pulse_i16_*)
+struct BatchFirNodeI16 : BatchFirNodeOf<BatchFirNodeI16, Complex16> {
+    using BatchFirNodeOf::BatchFirNodeOf;
+    static constexpr const char* kNew = "BatchFirNode<i16>::new";
+};
+struct FirNodeI16 : FirNodeOf<FirNodeI16, Complex16> {
+    using FirNodeOf::FirNodeOf;
+    static constexpr const char* kNew = "FirNode<i16>::new";
+};
+struct PulseNodeI16 : PulseNodeOf<PulseNodeI16, Complex16> {
+    using PulseNodeOf::PulseNodeOf;
+    static constexpr const char* kNew = "PulseNode<i16>::new";
+};
+
+// Complex<f64>: the reference's own doc example of batch_fir (fir.rs:68-86) and its timing estimator
+// (timing_estimator.rs:102-103) run on Complex<f64>; the reference's arithmetic operation for operation, outputs
+// bit-identical to it (comms_fir_f64_*, comms_pulse_f64_*)
+struct BatchFirNodeF64 : BatchFirNodeOf<BatchFirNodeF64, Complex64> {
+    using BatchFirNodeOf::BatchFirNodeOf;
+    static constexpr const char* kNew = "BatchFirNode<f64>::new";
+};
+struct FirNodeF64 : FirNodeOf<FirNodeF64, Complex64> {
+    using FirNodeOf::FirNodeOf;
+    static constexpr const char* kNew = "FirNode<f64>::new";
+};
+struct PulseNodeF64 : PulseNodeOf<PulseNodeF64, Complex64> {
+    using PulseNodeOf::PulseNodeOf;
+    static constexpr const char* kNew = "PulseNode<f64>::new";
 };
 
 // ---------------------------------------------------------------- PRNS source
@@ -703,27 +643,28 @@ private:
 };
 
 // ---------------------------------------------------------------- mixer
-class MixerNode : public DeriveNode<MixerNode> {
+template <class D, class T>
+class MixerNodeOf : public DeriveNode<D> {
 public:
-    NodeReceiver<Complex32> input;
-    NodeSender<Complex32> output;
+    NodeReceiver<T> input;
+    NodeSender<T> output;
 
     // NB (dphase, phase): the node's order, not Mixer::new's (mixer.rs:128 vs :43)
-    explicit MixerNode(double dphase, std::optional<double> phase = std::nullopt, int device = 0) {
-        throw_on(comms_mixer_create(dphase, phase.value_or(0.0), device, &h_), "MixerNode::new");
+    explicit MixerNodeOf(double dphase, std::optional<double> phase = std::nullopt, int device = 0) {
+        throw_on(comms_mixer_create(dphase, phase.value_or(0.0), device, &h_), D::kNew);
     }
-    MixerNode(MixerNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~MixerNode() { comms_mixer_destroy(h_); }
+    MixerNodeOf(MixerNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
+    ~MixerNodeOf() { comms_mixer_destroy(h_); }
 
-    Result<Complex32> run(const Complex32& in) {
-        Complex32 out;
-        comms_status_t st = comms_mixer_run(h_, c32(&in), 1, c32(&out));
+    Result<T> run(const T& in) {
+        T out;
+        comms_status_t st = Sample<T>::mixer_run(h_, abi(&in), 1, abi(&out));
         if (st != COMMS_OK) return to_node_error(st);
         return out;
     }
-    Result<std::vector<Complex32>> run_block(const std::vector<Complex32>& ins) {  // see FirNode::run_block
-        std::vector<Complex32> out(ins.size());
-        comms_status_t st = comms_mixer_run(h_, c32(ins.data()), ins.size(), c32(out.data()));
+    Result<std::vector<T>> run_block(const std::vector<T>& ins) {  // see FirNodeOf::run_block
+        std::vector<T> out(ins.size());
+        comms_status_t st = Sample<T>::mixer_run(h_, abi(ins.data()), ins.size(), abi(out.data()));
         if (st != COMMS_OK) return to_node_error(st);
         return out;
     }
@@ -734,35 +675,14 @@ private:
     comms_mixer_t* h_ = nullptr;
 };
 
+struct MixerNode : MixerNodeOf<MixerNode, Complex32> {
+    using MixerNodeOf::MixerNodeOf;
+    static constexpr const char* kNew = "MixerNode::new";
+};
 // MixerNode<f64> (src/mixer.rs:93-148 with T = f64, the type of the reference's own mixer tests :160-336)
-class MixerNode64 : public DeriveNode<MixerNode64> {
-public:
-    NodeReceiver<Complex64> input;
-    NodeSender<Complex64> output;
-
-    explicit MixerNode64(double dphase, std::optional<double> phase = std::nullopt, int device = 0) {
-        throw_on(comms_mixer_create(dphase, phase.value_or(0.0), device, &h_), "MixerNode<f64>::new");
-    }
-    MixerNode64(MixerNode64&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~MixerNode64() { comms_mixer_destroy(h_); }
-
-    Result<Complex64> run(const Complex64& in) {
-        Complex64 out;
-        comms_status_t st = comms_mixer_run_f64(h_, c64(&in), 1, c64(&out));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    Result<std::vector<Complex64>> run_block(const std::vector<Complex64>& ins) {  // see FirNode::run_block
-        std::vector<Complex64> out(ins.size());
-        comms_status_t st = comms_mixer_run_f64(h_, c64(ins.data()), ins.size(), c64(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_mixer_t* h_ = nullptr;
+struct MixerNode64 : MixerNodeOf<MixerNode64, Complex64> {
+    using MixerNodeOf::MixerNodeOf;
+    static constexpr const char* kNew = "MixerNode<f64>::new";
 };
 
 // The reference has no batch mixer node; this one mixes a whole Vec per message.
@@ -847,18 +767,21 @@ private:
 };
 
 // ---------------------------------------------------------------- FM demod
-class FMDemodNode : public DeriveNode<FMDemodNode> {
+template <class D, class T>
+class FMDemodNodeOf : public DeriveNode<D> {
+    using S = Sample<T>;
+
 public:
-    NodeReceiver<std::vector<Complex32>> input;
-    NodeSender<std::vector<float>> output;
+    NodeReceiver<std::vector<T>> input;
+    NodeSender<std::vector<typename S::Real>> output;
 
-    explicit FMDemodNode(int device = 0) { throw_on(comms_fmdemod_create(device, &h_), "FMDemodNode::new"); }
-    FMDemodNode(FMDemodNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FMDemodNode() { comms_fmdemod_destroy(h_); }
+    explicit FMDemodNodeOf(int device = 0) { throw_on(S::fm_create(device, &h_), D::kNew); }
+    FMDemodNodeOf(FMDemodNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
+    ~FMDemodNodeOf() { S::fm_destroy(h_); }
 
-    Result<std::vector<float>> run(const std::vector<Complex32>& samples) {
-        std::vector<float> out(samples.size());
-        comms_status_t st = comms_fmdemod_run(h_, c32(samples.data()), samples.size(), out.data());
+    Result<std::vector<typename S::Real>> run(const std::vector<T>& samples) {
+        std::vector<typename S::Real> out(samples.size());
+        comms_status_t st = S::fm_run(h_, abi(samples.data()), samples.size(), out.data());
         if (st != COMMS_OK) return to_node_error(st);
         return out;
     }
@@ -866,25 +789,28 @@ public:
     auto senders() { return std::tie(output); }
 
 private:
-    comms_fmdemod_t* h_ = nullptr;
+    typename S::Fm* h_ = nullptr;
 };
 
 // ---------------------------------------------------------------- FFT
-class FFTBatchNode : public DeriveNode<FFTBatchNode> {
+template <class D, class T>
+class FFTBatchNodeOf : public DeriveNode<D> {
+    using S = Sample<T>;
+
 public:
-    NodeReceiver<std::vector<Complex32>> input;
-    NodeSender<std::vector<Complex32>> output;
+    NodeReceiver<std::vector<T>> input;
+    NodeSender<std::vector<T>> output;
 
-    FFTBatchNode(size_t fft_size, bool ifft, int device = 0) {
-        throw_on(comms_fft_create(fft_size, ifft ? 1 : 0, device, &h_), "FFTBatchNode::new");
+    FFTBatchNodeOf(size_t fft_size, bool ifft, int device = 0) {
+        throw_on(S::fft_create(fft_size, ifft ? 1 : 0, device, &h_), D::kNew);
     }
-    FFTBatchNode(FFTBatchNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FFTBatchNode() { comms_fft_destroy(h_); }
+    FFTBatchNodeOf(FFTBatchNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
+    ~FFTBatchNodeOf() { S::fft_destroy(h_); }
 
-    Result<std::vector<Complex32>> run(const std::vector<Complex32>& data) {
-        std::vector<Complex32> out(data.size());
+    Result<std::vector<T>> run(const std::vector<T>& data) {
+        std::vector<T> out(data.size());
         // a wrong length panics inside rustfft in the reference; here it is DataError
-        comms_status_t st = comms_fft_run(h_, c32(data.data()), data.size(), c32(out.data()));
+        comms_status_t st = S::fft_run(h_, abi(data.data()), data.size(), abi(out.data()));
         if (st != COMMS_OK) return to_node_error(st);
         return out;
     }
@@ -892,55 +818,26 @@ public:
     auto senders() { return std::tie(output); }
 
 private:
-    comms_fft_t* h_ = nullptr;
+    typename S::Fft* h_ = nullptr;
 };
 
+struct FMDemodNode : FMDemodNodeOf<FMDemodNode, Complex32> {
+    using FMDemodNodeOf::FMDemodNodeOf;
+    static constexpr const char* kNew = "FMDemodNode::new";
+};
+struct FFTBatchNode : FFTBatchNodeOf<FFTBatchNode, Complex32> {
+    using FFTBatchNodeOf::FFTBatchNodeOf;
+    static constexpr const char* kNew = "FFTBatchNode::new";
+};
 // FFTBatchNode<f64> (the instantiation of the reference's doc examples, fft_node.rs:24) and FMDemodNode<f64>
 // (analog_node.rs:20 with T = f64): plain FP64 kernels, correct to f64 rounding (comms_fft_f64_*, comms_fmdemod_f64_*)
-class FFTBatchNodeF64 : public DeriveNode<FFTBatchNodeF64> {
-public:
-    NodeReceiver<std::vector<Complex64>> input;
-    NodeSender<std::vector<Complex64>> output;
-
-    FFTBatchNodeF64(size_t fft_size, bool ifft, int device = 0) {
-        throw_on(comms_fft_f64_create(fft_size, ifft ? 1 : 0, device, &h_), "FFTBatchNode<f64>::new");
-    }
-    FFTBatchNodeF64(FFTBatchNodeF64&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FFTBatchNodeF64() { comms_fft_f64_destroy(h_); }
-
-    Result<std::vector<Complex64>> run(const std::vector<Complex64>& data) {
-        std::vector<Complex64> out(data.size());
-        comms_status_t st = comms_fft_f64_run(h_, c64(data.data()), data.size(), c64(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_fft_f64_t* h_ = nullptr;
+struct FFTBatchNodeF64 : FFTBatchNodeOf<FFTBatchNodeF64, Complex64> {
+    using FFTBatchNodeOf::FFTBatchNodeOf;
+    static constexpr const char* kNew = "FFTBatchNode<f64>::new";
 };
-
-class FMDemodNodeF64 : public DeriveNode<FMDemodNodeF64> {
-public:
-    NodeReceiver<std::vector<Complex64>> input;
-    NodeSender<std::vector<double>> output;
-
-    explicit FMDemodNodeF64(int device = 0) { throw_on(comms_fmdemod_f64_create(device, &h_), "FMDemodNode<f64>::new"); }
-    FMDemodNodeF64(FMDemodNodeF64&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FMDemodNodeF64() { comms_fmdemod_f64_destroy(h_); }
-
-    Result<std::vector<double>> run(const std::vector<Complex64>& samples) {
-        std::vector<double> out(samples.size());
-        comms_status_t st = comms_fmdemod_f64_run(h_, c64(samples.data()), samples.size(), out.data());
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_fmdemod_f64_t* h_ = nullptr;
+struct FMDemodNodeF64 : FMDemodNodeOf<FMDemodNodeF64, Complex64> {
+    using FMDemodNodeOf::FMDemodNodeOf;
+    static constexpr const char* kNew = "FMDemodNode<f64>::new";
 };
 
 // #[aggregate]: run returns Some(vec) every fft_size pushes, None otherwise

@@ -257,121 +257,109 @@ class PulseNode(_Handle):
         check(lib().comms_pulse_run_dev(self._h, sym_ptr, n_sym, out_ptr, stream))
 
 
-# ------------------------------------------------------------------ Complex<i16> instantiations
+# ------------------------------------------------------------------ Complex<i16> and Complex<f64> instantiations
 def _as_c16(a):
     a = np.ascontiguousarray(a, dtype=np.int16)
     return a.reshape(-1, 2)
 
 
-class BatchFirNodeI16(_Handle):
-    """BatchFirNode<i16>::new(taps, state) / run (fir_node.rs:193-220) on Complex<i16> = int16 (n, 2) arrays,
-    wrapping arithmetic.  A single sample (shape (2,)) in gives a single sample out: FirNode<i16>."""
-    _destroy = "comms_fir_i16_destroy"
+def _as_c128(a):
+    return np.ascontiguousarray(np.atleast_1d(a), dtype=np.complex128)
+
+
+class _Exact(_Handle):
+    """The nodes whose outputs are bit-identical to the reference's, over `comms_{fir,pulse}_{i16,f64}_*`.  A subclass names
+    its ABI prefix `_abi`, the function `_arr` that makes a contiguous array of its sample type, and that type as the numpy
+    `_dtype` and `_shape` of ONE sample: int16 (2,) for Complex<i16>, complex128 () for Complex<f64>."""
+    _abi = _arr = _dtype = _shape = None
+
+    def _call(self, name, *args):
+        check(getattr(lib(), self._abi + name)(*args))
+
+    def _n(self, a):
+        """Samples in an array that _arr made."""
+        return len(a.reshape((-1,) + self._shape))
+
+    def _out(self, n):
+        return np.empty((n,) + self._shape, self._dtype)
+
+    def run_dev(self, in_ptr, n, out_ptr, stream=0):
+        self._call("run_dev", self._h, in_ptr, n, out_ptr, stream)
+
+
+class _ExactFir(_Exact):
+    """BatchFirNode<T>::new(taps, state) / run (fir_node.rs:193-220).  A single sample in gives a single sample out: FirNode<T>."""
 
     def __init__(self, taps, state=None, device=0):
         super().__init__()
-        taps = _as_c16(taps)
+        taps = self._arr(taps)
         if state is None:
-            check(lib().comms_fir_i16_create(_ptr(taps), taps.shape[0], None, 0, device, C.byref(self._h)))
+            self._call("create", _ptr(taps), self._n(taps), None, 0, device, C.byref(self._h))
         else:
-            state = _as_c16(state)
-            check(lib().comms_fir_i16_create(_ptr(taps), taps.shape[0], _ptr(state), state.shape[0], device, C.byref(self._h)))
+            state = self._arr(state)
+            self._call("create", _ptr(taps), self._n(taps), _ptr(state), self._n(state), device, C.byref(self._h))
 
     def run(self, x):
-        single = np.ndim(x) == 1 and np.size(x) == 2
-        x = _as_c16(x)
+        single = np.shape(x) == self._shape
+        x = self._arr(x)
         out = np.empty_like(x)
-        check(lib().comms_fir_i16_run(self._h, _ptr(x), x.shape[0], _ptr(out)))
+        self._call("run", self._h, _ptr(x), self._n(x), _ptr(out))
         return out[0] if single else out
 
-    def run_dev(self, in_ptr, n, out_ptr, stream=0):
-        check(lib().comms_fir_i16_run_dev(self._h, in_ptr, n, out_ptr, stream))
-
     def state(self, n_state):
-        st = np.empty((int(n_state), 2), np.int16)
-        check(lib().comms_fir_i16_get_state(self._h, _ptr(st), int(n_state)))
+        st = self._out(int(n_state))
+        self._call("get_state", self._h, _ptr(st), int(n_state))
         return st
 
 
-FirNodeI16 = BatchFirNodeI16
+class _ExactPulse(_Exact):
+    """PulseNode<T>::new(taps, sam_per_sym) / run (pulse.rs:71-92)."""
 
-
-class BatchFirNodeF64(_Handle):
-    """BatchFirNode<f64>::new(taps, state) / run (fir_node.rs:193-220) on Complex<f64> = numpy complex128: the reference's
-    arithmetic operation for operation, bit-identical outputs (comms_fir_f64_*).  A scalar in gives a scalar out: FirNode<f64>."""
-    _destroy = "comms_fir_f64_destroy"
-
-    def __init__(self, taps, state=None, device=0):
+    def __init__(self, taps, sam_per_sym, device=0):
         super().__init__()
-        taps = np.ascontiguousarray(taps, dtype=np.complex128).ravel()
-        if state is None:
-            check(lib().comms_fir_f64_create(_ptr(taps), taps.size, None, 0, device, C.byref(self._h)))
-        else:
-            state = np.ascontiguousarray(state, dtype=np.complex128).ravel()
-            check(lib().comms_fir_f64_create(_ptr(taps), taps.size, _ptr(state), state.size, device, C.byref(self._h)))
+        taps = self._arr(taps)
+        self.sam_per_sym = int(sam_per_sym)
+        self._call("create", _ptr(taps), self._n(taps), self.sam_per_sym, device, C.byref(self._h))
 
-    def run(self, x):
-        scalar = np.ndim(x) == 0
-        x = np.ascontiguousarray(np.atleast_1d(x), dtype=np.complex128)
-        out = np.empty_like(x)
-        check(lib().comms_fir_f64_run(self._h, _ptr(x), x.size, _ptr(out)))
-        return out[0] if scalar else out
+    def run(self, sym):
+        s = self._arr(sym)
+        out = self._out(self._n(s) * self.sam_per_sym)
+        self._call("run", self._h, _ptr(s), self._n(s), _ptr(out))
+        return out
 
-    def run_dev(self, in_ptr, n, out_ptr, stream=0):
-        check(lib().comms_fir_f64_run_dev(self._h, in_ptr, n, out_ptr, stream))
 
-    def state(self, n_state):
-        st = np.empty(int(n_state), np.complex128)
-        check(lib().comms_fir_f64_get_state(self._h, _ptr(st), int(n_state)))
-        return st
+class BatchFirNodeI16(_ExactFir):
+    """BatchFirNode<i16> on Complex<i16> = int16 (n, 2) arrays, wrapping arithmetic.  A single sample has shape (2,)."""
+    _abi, _arr, _dtype, _shape = "comms_fir_i16_", staticmethod(_as_c16), np.int16, (2,)
+    _destroy = _abi + "destroy"
+
+
+class BatchFirNodeF64(_ExactFir):
+    """BatchFirNode<f64> on Complex<f64> = numpy complex128: the reference's arithmetic operation for operation.  A single
+    sample is a scalar."""
+    _abi, _arr, _dtype, _shape = "comms_fir_f64_", staticmethod(_as_c128), np.complex128, ()
+    _destroy = _abi + "destroy"
 
     def set_state(self, state):
-        st = np.ascontiguousarray(state, dtype=np.complex128).ravel()
-        check(lib().comms_fir_f64_set_state(self._h, _ptr(st), st.size))
+        st = self._arr(state)
+        self._call("set_state", self._h, _ptr(st), st.size)
         return self
 
 
+FirNodeI16 = BatchFirNodeI16
 FirNodeF64 = BatchFirNodeF64
 
 
-class PulseNodeF64(_Handle):
-    """PulseNode<f64>::new(taps, sam_per_sym) / run (pulse.rs:71-92) on Complex<f64>, bit-identical to the reference."""
-    _destroy = "comms_pulse_f64_destroy"
-
-    def __init__(self, taps, sam_per_sym, device=0):
-        super().__init__()
-        taps = np.ascontiguousarray(taps, dtype=np.complex128).ravel()
-        self.sam_per_sym = int(sam_per_sym)
-        check(lib().comms_pulse_f64_create(_ptr(taps), taps.size, self.sam_per_sym, device, C.byref(self._h)))
-
-    def run(self, sym):
-        s = np.ascontiguousarray(np.atleast_1d(sym), dtype=np.complex128)
-        out = np.empty(s.size * self.sam_per_sym, np.complex128)
-        check(lib().comms_pulse_f64_run(self._h, _ptr(s), s.size, _ptr(out)))
-        return out
-
-    def run_dev(self, sym_ptr, n_sym, out_ptr, stream=0):
-        check(lib().comms_pulse_f64_run_dev(self._h, sym_ptr, n_sym, out_ptr, stream))
+class PulseNodeI16(_ExactPulse):
+    """PulseNode<i16> on Complex<i16>."""
+    _abi, _arr, _dtype, _shape = "comms_pulse_i16_", staticmethod(_as_c16), np.int16, (2,)
+    _destroy = _abi + "destroy"
 
 
-class PulseNodeI16(_Handle):
-    """PulseNode<i16>::new(taps, sam_per_sym) / run (pulse.rs:71-92) on Complex<i16>."""
-    _destroy = "comms_pulse_i16_destroy"
-
-    def __init__(self, taps, sam_per_sym, device=0):
-        super().__init__()
-        taps = _as_c16(taps)
-        self.sam_per_sym = int(sam_per_sym)
-        check(lib().comms_pulse_i16_create(_ptr(taps), taps.shape[0], self.sam_per_sym, device, C.byref(self._h)))
-
-    def run(self, sym):
-        s = _as_c16(sym)
-        out = np.empty((s.shape[0] * self.sam_per_sym, 2), np.int16)
-        check(lib().comms_pulse_i16_run(self._h, _ptr(s), s.shape[0], _ptr(out)))
-        return out
-
-    def run_dev(self, sym_ptr, n_sym, out_ptr, stream=0):
-        check(lib().comms_pulse_i16_run_dev(self._h, sym_ptr, n_sym, out_ptr, stream))
+class PulseNodeF64(_ExactPulse):
+    """PulseNode<f64> on Complex<f64>, bit-identical to the reference."""
+    _abi, _arr, _dtype, _shape = "comms_pulse_f64_", staticmethod(_as_c128), np.complex128, ()
+    _destroy = _abi + "destroy"
 
 
 # ------------------------------------------------------------------ mixer

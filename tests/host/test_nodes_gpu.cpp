@@ -21,6 +21,26 @@
 using namespace comms;
 using C = Complex32;
 
+// every public node name keeps the message types of its `input` / `output` fields, whatever template it is built from
+template <class N, class In, class Out>
+constexpr bool kIo = std::is_same_v<decltype(N::input), NodeReceiver<In>> && std::is_same_v<decltype(N::output), NodeSender<Out>>;
+static_assert(kIo<BatchFirNode, std::vector<Complex32>, std::vector<Complex32>>);
+static_assert(kIo<FirNode, Complex32, Complex32>);
+static_assert(kIo<PulseNode, Complex32, std::vector<Complex32>>);
+static_assert(kIo<BatchFirNodeI16, std::vector<Complex16>, std::vector<Complex16>>);
+static_assert(kIo<FirNodeI16, Complex16, Complex16>);
+static_assert(kIo<PulseNodeI16, Complex16, std::vector<Complex16>>);
+static_assert(kIo<BatchFirNodeF64, std::vector<Complex64>, std::vector<Complex64>>);
+static_assert(kIo<FirNodeF64, Complex64, Complex64>);
+static_assert(kIo<PulseNodeF64, Complex64, std::vector<Complex64>>);
+static_assert(kIo<MixerNode, Complex32, Complex32>);
+static_assert(kIo<MixerNode64, Complex64, Complex64>);
+static_assert(kIo<FMDemodNode, std::vector<Complex32>, std::vector<float>>);
+static_assert(kIo<FMDemodNodeF64, std::vector<Complex64>, std::vector<double>>);
+static_assert(kIo<FFTBatchNode, std::vector<Complex32>, std::vector<Complex32>>);
+static_assert(kIo<FFTBatchNodeF64, std::vector<Complex64>, std::vector<Complex64>>);
+static_assert(std::is_same_v<decltype(std::declval<const BatchFirNode&>().handle()), comms_fir_t*>);
+
 static int g_fail = 0;
 #define CHECK(cond)                                                                       \
     do {                                                                                  \

@@ -133,3 +133,23 @@ def test_fir_f64_device_entry_and_errors(c):
     assert e.value.code == c.COMMS_ERR_ARG
     h = C.c_void_p()
     assert lib().comms_fir_f64_create(None, 0, None, 0, 0, C.byref(h)) == c.COMMS_ERR_ARG   # the reference panics on an empty state
+
+
+def test_fir_f64_set_state_round_trip(c):
+    """set_state(s) is what state() then reports, bit for bit, and the filter goes on from it as the oracle does."""
+    rng = np.random.default_rng(11)
+    taps = rand_c128(rng, 5, 0.3)
+    s = rand_c128(rng, 5)
+    x = rand_c128(rng, 7)
+    node = c.BatchFirNodeF64(taps)
+    node.run(rand_c128(rng, 3))                      # some history of its own first
+    assert node.set_state(s) is node
+    assert np.array_equal(bits(node.state(5)), bits(s))
+    ost = s.copy()
+    want = oracle.batch_fir(x, taps, ost)
+    assert np.array_equal(bits(node.run(x)), bits(want))
+    assert np.array_equal(bits(node.state(5)), bits(ost))
+    for bad in (s[:4], np.concatenate([s, s[:1]])):  # exactly the effective taps, no fewer and no more
+        with pytest.raises(c.CommsError) as e:
+            node.set_state(bad)
+        assert e.value.code == c.COMMS_ERR_ARG

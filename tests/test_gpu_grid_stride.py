@@ -1,6 +1,6 @@
 """The second-tier kernels past the point where their grid stops growing.
 
-fir_f64_kernel, fir_i16_kernel, fmdemod_f64_kernel, the wire-format converters of iqformat.hip and estimator_kernel all launch
+fir_exact_kernel<double2>, fir_exact_kernel<short2>, fmdemod_f64_kernel, the wire-format converters of iqformat.hip and estimator_kernel all launch
 min(ceil(n / 256), 8 * kNumCU) workgroups of 256 lanes and walk the rest of the batch in grid-stride rounds.  Below T work
 items there is one round and the `r * stride` / `i += stride` arithmetic never runs; the estimator's four-accumulator main
 loop needs more than 3 T terms to run at all.  Every test here sits on or beyond T and compares EVERY output with the oracle:
@@ -19,8 +19,8 @@ import pytest
 import oracle
 from test_estimators import psk_stream, qam16_stream
 
-# The grid cap: 8 * kNumCU workgroups (kNumCU = 256, csrc/common.hpp) of 256 lanes -- run_f64_dev (fir_f64.hip), run_int_dev
-# (fir_int.hip), comms_fmdemod_f64_run_dev (fft_f64.hip), conv_grid (iqformat.hip), estimate (estimators.hip).
+# The grid cap: 8 * kNumCU workgroups (kNumCU = 256, csrc/common.hpp) of 256 lanes -- run_dev<V> (fir_exact.hip, both sample
+# types), comms_fmdemod_f64_run_dev (fft_f64.hip), conv_grid (iqformat.hip), estimate (estimators.hip).
 T = 8 * 256 * 256
 SIZES = (T - 1, T, T + 1, 2 * T + 3, 3 * T + 1)   # one round to the brim, one lane into the second, three and four rounds
 HEAD = 1077                                        # a short first call: the seam to the long call is no multiple of 256

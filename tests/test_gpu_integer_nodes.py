@@ -82,3 +82,47 @@ def test_pulse_i16_vs_oracle(c, n_taps, sps):
     assert np.array_equal(np.concatenate(got), np.concatenate(want))
     with pytest.raises(c.CommsError):
         c.PulseNodeI16(taps, 0)
+
+
+@pytest.mark.parametrize("kind", ["i16", "f64"])
+def test_exact_fir_and_pulse_refuse_bad_arguments_alike(c, kind):
+    """Complex<i16> and Complex<f64> share one set of argument checks: each bad call comes back COMMS_ERR_ARG for both, refused
+    on the host before any kernel starts; an empty message is fine, NULL pointers and all."""
+    import ctypes as C
+
+    import torch
+    from comms_rs_amd._lib import lib
+
+    n, n_taps = 8, 3
+    if kind == "i16":
+        fir_cls, pulse_cls, taps, half = c.BatchFirNodeI16, c.PulseNodeI16, np.ones((n_taps, 2), np.int16), 2
+        dev = lambda: torch.zeros((n + 1, 2), dtype=torch.int16, device="cuda:0")
+    else:
+        fir_cls, pulse_cls, taps, half = c.BatchFirNodeF64, c.PulseNodeF64, np.ones(n_taps, np.complex128), 8
+        dev = lambda: torch.zeros(n + 1, dtype=torch.complex128, device="cuda:0")
+    fir_create = getattr(lib(), "comms_fir_%s_create" % kind)
+    pulse_create = getattr(lib(), "comms_pulse_%s_create" % kind)
+    xd, yd = dev(), dev()
+    fir, pulse = fir_cls(taps), pulse_cls(taps, 1)
+
+    def refused(f, *args):
+        with pytest.raises(c.CommsError) as e:
+            f(*args)
+        assert e.value.code == c.COMMS_ERR_ARG, e.value
+
+    for node in (fir, pulse):
+        refused(node.run_dev, xd.data_ptr(), n, xd.data_ptr(), 0)           # in place
+        refused(node.run_dev, xd.data_ptr() + half, n, yd.data_ptr(), 0)    # input half a sample off
+        refused(node.run_dev, xd.data_ptr(), n, yd.data_ptr() + half, 0)    # output half a sample off
+        node.run_dev(None, 0, None, 0)                                      # n = 0: nothing to do
+        assert getattr(lib(), node._abi + "run")(node._h, None, 0, None) == c.COMMS_OK
+    refused(fir.state, n_taps + 1)                                          # more state than the filter has
+    h = C.c_void_p()
+    tp = taps.ctypes.data_as(C.c_void_p)
+    assert fir_create(None, 0, None, 0, 0, C.byref(h)) == c.COMMS_ERR_ARG and not h
+    assert fir_create(tp, 0, None, 0, 0, C.byref(h)) == c.COMMS_ERR_ARG and not h
+    assert pulse_create(tp, 0, 1, 0, C.byref(h)) == c.COMMS_ERR_ARG and not h
+    for sps in (0, 65537):
+        assert pulse_create(tp, n_taps, sps, 0, C.byref(h)) == c.COMMS_ERR_ARG and not h, sps
+    torch.cuda.synchronize()
+    assert not xd.cpu().numpy().any() and not yd.cpu().numpy().any()        # and nothing was written
