@@ -18,6 +18,7 @@ FIR_AUTO, FIR_DIRECT, FIR_OVERLAP_SAVE, FIR_OS1024, FIR_OS4096, FIR_OS16K, FIR_O
 IQ_C32, IQ_I16, IQ_U8 = 0, 1, 2
 SYM_C32, SYM_BITS = 0, 1        # comms_pulse_set_input_format, comms_chain_set_output_format
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
+RESAMPLE_F32, RESAMPLE_C32 = 4, 8  # comms_resample_create: bytes per sample
 STREAM_HANDLE = C.c_void_p(-1).value  # COMMS_STREAM_HANDLE: the handle's own stream
 
 
@@ -182,6 +183,16 @@ _PROTOS = {
     "comms_rfir_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_rfir_set_timer": [_vp, _vp],
     "comms_rfir_destroy": [_vp],
+    "comms_resample_create": [_vp, _sz, _sz, _sz, _i32, _i32, _pp],
+    "comms_resample_out_len": [_sz, _sz, _sz, _psz],
+    "comms_resample_state_len": [_sz, _sz, _psz],
+    "comms_resample_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_resample_run": [_vp, _vp, _sz, _vp],
+    "comms_resample_get_state": [_vp, _vp, _sz],
+    "comms_resample_set_state": [_vp, _vp, _sz],
+    "comms_resample_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_resample_set_timer": [_vp, _vp],
+    "comms_resample_destroy": [_vp],
     "comms_bpsk_byte_mod": [_vp, _sz, _vp, _i32],
     "comms_qpsk_byte_mod": [_vp, _sz, _vp, _i32],
     "comms_bpsk_bit_mod": [_vp, _sz, _vp, _i32],

@@ -642,6 +642,51 @@ private:
     size_t rate_;
 };
 
+// Rational resampler by up / down as ONE node (comms_resample_*; an additional node): the results of
+// UpsampleNode(up) -> BatchFirNode(Complex(taps, 0)) -> DecimateNode(down) for real taps, over float or Complex32
+// messages.  Any message length: ceil(n up / down) outputs, the decimator restarting with every message.
+template <class T>
+struct ResampleElem;
+template <>
+struct ResampleElem<float> {
+    static constexpr int32_t value = COMMS_RESAMPLE_F32;
+};
+template <>
+struct ResampleElem<Complex32> {
+    static constexpr int32_t value = COMMS_RESAMPLE_C32;
+};
+
+template <class T>
+class ResampleNode : public DeriveNode<ResampleNode<T>> {
+public:
+    NodeReceiver<std::vector<T>> input;
+    NodeSender<std::vector<T>> output;
+    ResampleNode(const std::vector<float>& taps, size_t up, size_t down, int device = 0) : up_(up), down_(down) {
+        throw_on(comms_resample_create(taps.data(), taps.size(), up, down, ResampleElem<T>::value, device, &h_), "ResampleNode::new");
+    }
+    ResampleNode(ResampleNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), up_(o.up_), down_(o.down_) { o.h_ = nullptr; }
+    ~ResampleNode() { comms_resample_destroy(h_); }
+    Result<std::vector<T>> run(const std::vector<T>& in) {
+        size_t m = 0;
+        if (comms_resample_out_len(in.size(), up_, down_, &m) != COMMS_OK) return NodeError::DataError;
+        std::vector<T> out(m);
+        comms_status_t st = comms_resample_run(h_, in.data(), in.size(), out.data());
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    std::string kernel(size_t n) const {  // "resample_kernel<..> ...", or "series: ..." (the launches)
+        char name[200] = {0};
+        comms_resample_get_kernel(h_, n, name, sizeof name);
+        return name;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_resample_t* h_ = nullptr;
+    size_t up_, down_;
+};
+
 // ---------------------------------------------------------------- mixer
 template <class D, class T>
 class MixerNodeOf : public DeriveNode<D> {
@@ -1296,6 +1341,39 @@ public:
 private:
     comms_rfir_t* h_ = nullptr;
     size_t rate_;
+    int device_;
+    DevStream st_;
+};
+
+// The rational resampler on device-resident messages
+template <class T>
+class ResampleNodeDev : public DeriveNode<ResampleNodeDev<T>> {
+public:
+    NodeReceiver<DeviceBuf<T>> input;
+    NodeSender<DeviceBuf<T>> output;
+    ResampleNodeDev(const std::vector<float>& taps, size_t up, size_t down, int device = 0)
+        : up_(up), down_(down), device_(device), st_(device) {
+        throw_on(comms_resample_create(taps.data(), taps.size(), up, down, ResampleElem<T>::value, device, &h_), "ResampleNodeDev::new");
+    }
+    ResampleNodeDev(ResampleNodeDev&& o) noexcept
+        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), up_(o.up_), down_(o.down_), device_(o.device_), st_(std::move(o.st_)) {
+        o.h_ = nullptr;
+    }
+    ~ResampleNodeDev() { comms_resample_destroy(h_); }
+    Result<DeviceBuf<T>> run(const DeviceBuf<T>& in) {
+        size_t m = 0;
+        if (comms_resample_out_len(in.size(), up_, down_, &m) != COMMS_OK) return NodeError::DataError;
+        DeviceBuf<T> out(m, device_);
+        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_resample_run_dev(h_, in.ptr(), in.size(), out.ptr(), s); });
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_resample_t* h_ = nullptr;
+    size_t up_, down_;
     int device_;
     DevStream st_;
 };

@@ -762,6 +762,64 @@ class RealFirDecimNode(_Handle):
         return self
 
 
+class ResampleNode(_Handle):
+    """Rational resampler by up / down (comms_resample_*): UpsampleNode(up) -> BatchFirNode(Complex(taps, 0)) ->
+    DecimateNode(down) as one node over an f32 or Complex<f32> stream, which forms only the products with input samples.
+    Any batch length: ceil(n up / down) outputs per call, the decimator restarts at sample 0 of every call and the
+    history -- (len(taps) - 1) // up INPUT samples -- advances by all samples."""
+    _destroy = "comms_resample_destroy"
+
+    def __init__(self, taps, up, down, dtype=np.float32, device=0):
+        super().__init__()
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.complex64)):
+            raise TypeError("ResampleNode takes float32 or complex64 samples, not %s" % self.dtype)
+        self.up, self.down, self.n_taps = int(up), int(down), taps.size
+        check(lib().comms_resample_create(_ptr(taps), taps.size, self.up, self.down, self.dtype.itemsize, device, C.byref(self._h)))
+
+    def out_len(self, n):
+        m = C.c_size_t()
+        check(lib().comms_resample_out_len(n, self.up, self.down, C.byref(m)))
+        return m.value
+
+    def state_len(self):
+        m = C.c_size_t()
+        check(lib().comms_resample_state_len(self.n_taps, self.up, C.byref(m)))
+        return m.value
+
+    def kernel(self, n):
+        """What a batch of n samples is run by: "resample_kernel<..> tile=.. lds=..", or "series: ..." (the launches)."""
+        buf = C.create_string_buffer(200)
+        check(lib().comms_resample_get_kernel(self._h, n, buf, 200))
+        return buf.value.decode()
+
+    def run(self, x):
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        out = np.empty(self.out_len(x.size), self.dtype)
+        check(lib().comms_resample_run(self._h, _ptr(x), x.size, _ptr(out)))
+        return out
+
+    def run_dev(self, in_ptr, n, out_ptr, stream=0):
+        check(lib().comms_resample_run_dev(self._h, in_ptr, n, out_ptr, stream))
+
+    def get_state(self, n_state=None):
+        """The last n_state input samples (default: all state_len() of them), newest first."""
+        n_state = self.state_len() if n_state is None else int(n_state)
+        st = np.empty(n_state, self.dtype)
+        check(lib().comms_resample_get_state(self._h, _ptr(st), n_state))
+        return st
+
+    def set_state(self, state):
+        state = np.ascontiguousarray(state, dtype=self.dtype)
+        check(lib().comms_resample_set_state(self._h, _ptr(state), state.size))
+
+    def set_timer(self, timer):
+        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch (the series: its FIR launch)."""
+        check(lib().comms_resample_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
 def _taps(fn, n_taps, *args):
     out = np.empty(int(n_taps), np.complex64)
     check(fn(int(n_taps), *args, _ptr(out)))
@@ -1125,7 +1183,8 @@ class KernelTimer:
         name = {"comms_fir_destroy": "comms_fir_set_timer", "comms_mixer_destroy": "comms_mixer_set_timer",
                 "comms_fmdemod_destroy": "comms_fmdemod_set_timer", "comms_fft_destroy": "comms_fft_set_timer",
                 "comms_chain_destroy": "comms_chain_set_timer", "comms_pulse_destroy": "comms_pulse_set_timer",
-                "comms_rfir_destroy": "comms_rfir_set_timer", "comms_noise_destroy": "comms_noise_set_timer"}[node._destroy]
+                "comms_rfir_destroy": "comms_rfir_set_timer", "comms_noise_destroy": "comms_noise_set_timer",
+                "comms_resample_destroy": "comms_resample_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

@@ -504,6 +504,64 @@ impl RealFirDecimNode {
     }
 }
 
+/// Sample types of the rational resampler: `f32` and `Complex<f32>`.
+pub trait ResampleSample: Copy + Send + Zero + 'static {
+    #[doc(hidden)] const ELEM: i32;
+}
+impl ResampleSample for f32 { const ELEM: i32 = COMMS_RESAMPLE_F32; }
+impl ResampleSample for Complex<f32> { const ELEM: i32 = COMMS_RESAMPLE_C32; }
+
+/// Rational resampler by `up / down` (an additional node): what the reference wires as
+/// `UpsampleNode(up) -> BatchFirNode(Complex(taps, 0)) -> DecimateNode(down)`, for real taps, as one node that forms
+/// only the products with input samples.  Any batch length, `ceil(n * up / down)` outputs per call; the state is
+/// `(taps.len() - 1) / up` input samples.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct ResampleNode<T>
+where
+    T: ResampleSample,
+{
+    pub input: NodeReceiver<Vec<T>>,
+    h: *mut comms_resample_t,
+    up: usize,
+    down: usize,
+    pub output: NodeSender<Vec<T>>,
+}
+unsafe impl<T: ResampleSample> Send for ResampleNode<T> {}
+impl<T: ResampleSample> Drop for ResampleNode<T> {
+    fn drop(&mut self) { unsafe { comms_resample_destroy(self.h); } }
+}
+impl<T> ResampleNode<T>
+where
+    T: ResampleSample,
+{
+    pub fn new(taps: Vec<f32>, up: usize, down: usize) -> Self {
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_resample_create(taps.as_ptr(), taps.len(), up, down, T::ELEM, 0, &mut h) };
+        assert_eq!(st, COMMS_OK, "comms_resample_create failed");
+        ResampleNode { input: Default::default(), h, up, down, output: Default::default() }
+    }
+    pub fn run(&mut self, samples: &[T]) -> Result<Vec<T>, NodeError> {
+        let mut m = 0usize;
+        let st = unsafe { comms_resample_out_len(samples.len(), self.up, self.down, &mut m) };
+        if st != COMMS_OK { return Err(to_err(st)); }
+        let mut out = vec![T::zero(); m];
+        let st = unsafe { comms_resample_run(self.h, samples.as_ptr() as *const c_void, samples.len(), out.as_mut_ptr() as *mut c_void) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    /// The checkpoint hook: the last `n` input samples, newest first
+    pub fn state(&mut self, n: usize) -> Result<Vec<T>, NodeError> {
+        let mut out = vec![T::zero(); n];
+        let st = unsafe { comms_resample_get_state(self.h, out.as_mut_ptr() as *mut c_void, n) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    /// Checkpoint restore / the halo in front of a stream shard: exactly `(taps.len() - 1) / up` samples, newest first
+    pub fn set_state(&mut self, state: &[T]) -> Result<(), NodeError> {
+        let st = unsafe { comms_resample_set_state(self.h, state.as_ptr() as *const c_void, state.len()) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+}
+
 /// Sample types `UniformNode<T>` is built for: `f32` (values in `[start, end)`) and `u8` over `[0, 2)`, which is what
 /// `random_bit()` returns (rand_node.rs:150-152).
 pub trait UniformSample: Copy + Send + 'static {
