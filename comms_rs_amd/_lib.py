@@ -19,6 +19,7 @@ IQ_C32, IQ_I16, IQ_U8 = 0, 1, 2
 SYM_C32, SYM_BITS = 0, 1        # comms_pulse_set_input_format, comms_chain_set_output_format
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 RESAMPLE_F32, RESAMPLE_C32 = 4, 8  # comms_resample_create: bytes per sample
+CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR = 0, 1  # comms_channelizer_create: layout
 STREAM_HANDLE = C.c_void_p(-1).value  # COMMS_STREAM_HANDLE: the handle's own stream
 
 
@@ -193,6 +194,18 @@ _PROTOS = {
     "comms_resample_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_resample_set_timer": [_vp, _vp],
     "comms_resample_destroy": [_vp],
+    "comms_channelizer_create": [_vp, _sz, _sz, _sz, _i32, _i32, _pp],
+    "comms_channelizer_out_len": [_sz, _sz, _psz],
+    "comms_channelizer_state_len": [_sz, _psz],
+    "comms_channelizer_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_channelizer_run": [_vp, _vp, _sz, _vp],
+    "comms_channelizer_get_state": [_vp, _vp, _sz],
+    "comms_channelizer_set_state": [_vp, _vp, _sz],
+    "comms_channelizer_get_phase": [_vp, C.POINTER(C.c_uint64)],
+    "comms_channelizer_set_phase": [_vp, _u64],
+    "comms_channelizer_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_channelizer_set_timer": [_vp, _vp],
+    "comms_channelizer_destroy": [_vp],
     "comms_bpsk_byte_mod": [_vp, _sz, _vp, _i32],
     "comms_qpsk_byte_mod": [_vp, _sz, _vp, _i32],
     "comms_bpsk_bit_mod": [_vp, _sz, _vp, _i32],

@@ -687,6 +687,46 @@ private:
     size_t up_, down_;
 };
 
+// Polyphase channelizer as ONE node (comms_channelizer_*; an additional node): the results of M chains
+// MixerNode(0, -2 pi k / M) -> BatchFirNode(Complex(taps, 0)) -> DecimateNode(down) over one Complex32 stream.  Any message
+// length: ceil(n / down) frames.  One sender carries a message's frames x M outputs in the node's layout
+// (COMMS_CHANNELIZER_CHANNEL_MAJOR: channel k is out[k frames .. (k + 1) frames)); connect it to as many receivers as there
+// are consumers.
+class ChannelizerNode : public DeriveNode<ChannelizerNode> {
+public:
+    NodeReceiver<std::vector<Complex32>> input;
+    NodeSender<std::vector<Complex32>> output;
+    ChannelizerNode(const std::vector<float>& taps, size_t channels, size_t down, int32_t layout = COMMS_CHANNELIZER_CHANNEL_MAJOR, int device = 0)
+        : channels_(channels), down_(down) {
+        throw_on(comms_channelizer_create(taps.data(), taps.size(), channels, down, layout, device, &h_), "ChannelizerNode::new");
+    }
+    ChannelizerNode(ChannelizerNode&& o) noexcept
+        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), channels_(o.channels_), down_(o.down_) {
+        o.h_ = nullptr;
+    }
+    ~ChannelizerNode() { comms_channelizer_destroy(h_); }
+    Result<std::vector<Complex32>> run(const std::vector<Complex32>& in) {
+        size_t frames = 0;
+        if (comms_channelizer_out_len(in.size(), down_, &frames) != COMMS_OK) return NodeError::DataError;
+        std::vector<Complex32> out(frames * channels_);
+        comms_status_t st = comms_channelizer_run(h_, reinterpret_cast<const comms_c32*>(in.data()), in.size(), reinterpret_cast<comms_c32*>(out.data()));
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    size_t channels() const { return channels_; }
+    std::string kernel(size_t n) const {  // "channelizer_kernel<..> ...", or "series: ..." (the launches)
+        char name[240] = {0};
+        comms_channelizer_get_kernel(h_, n, name, sizeof name);
+        return name;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_channelizer_t* h_ = nullptr;
+    size_t channels_, down_;
+};
+
 // ---------------------------------------------------------------- mixer
 template <class D, class T>
 class MixerNodeOf : public DeriveNode<D> {
@@ -1374,6 +1414,41 @@ public:
 private:
     comms_resample_t* h_ = nullptr;
     size_t up_, down_;
+    int device_;
+    DevStream st_;
+};
+
+// The channelizer on device-resident messages: channel k of a channel-major message is a contiguous device stream
+class ChannelizerNodeDev : public DeriveNode<ChannelizerNodeDev> {
+public:
+    NodeReceiver<DeviceBuf<Complex32>> input;
+    NodeSender<DeviceBuf<Complex32>> output;
+    ChannelizerNodeDev(const std::vector<float>& taps, size_t channels, size_t down, int32_t layout = COMMS_CHANNELIZER_CHANNEL_MAJOR, int device = 0)
+        : channels_(channels), down_(down), device_(device), st_(device) {
+        throw_on(comms_channelizer_create(taps.data(), taps.size(), channels, down, layout, device, &h_), "ChannelizerNodeDev::new");
+    }
+    ChannelizerNodeDev(ChannelizerNodeDev&& o) noexcept
+        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), channels_(o.channels_), down_(o.down_), device_(o.device_),
+          st_(std::move(o.st_)) {
+        o.h_ = nullptr;
+    }
+    ~ChannelizerNodeDev() { comms_channelizer_destroy(h_); }
+    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& in) {
+        size_t frames = 0;
+        if (comms_channelizer_out_len(in.size(), down_, &frames) != COMMS_OK) return NodeError::DataError;
+        DeviceBuf<Complex32> out(frames * channels_, device_);
+        comms_status_t st = st_.run(in, out, [&](void* s) {
+            return comms_channelizer_run_dev(h_, reinterpret_cast<const comms_c32*>(in.ptr()), in.size(), reinterpret_cast<comms_c32*>(out.ptr()), s);
+        });
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    comms_channelizer_t* h_ = nullptr;
+    size_t channels_, down_;
     int device_;
     DevStream st_;
 };

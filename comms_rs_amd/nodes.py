@@ -820,6 +820,85 @@ class ResampleNode(_Handle):
         return self
 
 
+class ChannelizerNode(_Handle):
+    """Polyphase channelizer (comms_channelizer_*): M chains MixerNode(0, -2 pi k / M) -> BatchFirNode(Complex(taps, 0)) ->
+    DecimateNode(down), k = 0 .. M-1, over one Complex<f32> stream as one node -- a polyphase filter bank that reads every
+    sample once and spends len(taps) multiply-adds per frame (one output of each channel).  Any batch length: ceil(n / down)
+    frames per call, returned as an array [channels][frames] (layout "channel", each row a contiguous stream) or
+    [frames][channels] (layout "frame").  State: the last len(taps) - 1 input samples and the stream index mod M."""
+    _destroy = "comms_channelizer_destroy"
+    LAYOUTS = {"channel": 0, "frame": 1, 0: 0, 1: 1}
+
+    def __init__(self, taps, channels, down, layout="channel", device=0):
+        super().__init__()
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        if layout not in self.LAYOUTS:
+            raise ValueError("layout is 'channel' or 'frame', not %r" % (layout,))
+        self.layout = self.LAYOUTS[layout]
+        self.channels, self.down, self.n_taps = int(channels), int(down), taps.size
+        check(lib().comms_channelizer_create(_ptr(taps), taps.size, self.channels, self.down, self.layout, device, C.byref(self._h)))
+
+    def out_len(self, n):
+        """Frames of a call of n samples; the call writes out_len(n) * channels outputs."""
+        m = C.c_size_t()
+        check(lib().comms_channelizer_out_len(n, self.down, C.byref(m)))
+        return m.value
+
+    def state_len(self):
+        m = C.c_size_t()
+        check(lib().comms_channelizer_state_len(self.n_taps, C.byref(m)))
+        return m.value
+
+    def kernel(self, n):
+        """What a batch of n samples is run by: "channelizer_kernel<..> ...", or "series: ..." (the launches)."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_channelizer_get_kernel(self._h, n, buf, 240))
+        return buf.value.decode()
+
+    def shape(self, n):
+        frames = self.out_len(n)
+        return (frames, self.channels) if self.layout else (self.channels, frames)
+
+    def run(self, x):
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        out = np.empty(self.shape(x.size), np.complex64)
+        check(lib().comms_channelizer_run(self._h, _ptr(x), x.size, _ptr(out)))
+        return out
+
+    def run_dev(self, in_ptr, n, out_ptr, stream=0):
+        check(lib().comms_channelizer_run_dev(self._h, in_ptr, n, out_ptr, stream))
+
+    def get_state(self, n_state=None):
+        """The last n_state input samples (default: all state_len() of them), newest first."""
+        n_state = self.state_len() if n_state is None else int(n_state)
+        st = np.empty(n_state, np.complex64)
+        check(lib().comms_channelizer_get_state(self._h, _ptr(st), n_state))
+        return st
+
+    def set_state(self, state):
+        state = np.ascontiguousarray(state, dtype=np.complex64)
+        check(lib().comms_channelizer_set_state(self._h, _ptr(state), state.size))
+
+    state = property(get_state, set_state)
+
+    def get_phase(self):
+        """The stream index of the next input sample, mod channels."""
+        t = C.c_uint64()
+        check(lib().comms_channelizer_get_phase(self._h, C.byref(t)))
+        return t.value
+
+    def set_phase(self, t):
+        """Any stream index t >= 0 (reduced mod channels): where a shard starts."""
+        check(lib().comms_channelizer_set_phase(self._h, int(t)))
+
+    phase = property(get_phase, set_phase)
+
+    def set_timer(self, timer):
+        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch (the series: channel 0's FIR launch)."""
+        check(lib().comms_channelizer_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
 def _taps(fn, n_taps, *args):
     out = np.empty(int(n_taps), np.complex64)
     check(fn(int(n_taps), *args, _ptr(out)))
@@ -1184,7 +1263,8 @@ class KernelTimer:
                 "comms_fmdemod_destroy": "comms_fmdemod_set_timer", "comms_fft_destroy": "comms_fft_set_timer",
                 "comms_chain_destroy": "comms_chain_set_timer", "comms_pulse_destroy": "comms_pulse_set_timer",
                 "comms_rfir_destroy": "comms_rfir_set_timer", "comms_noise_destroy": "comms_noise_set_timer",
-                "comms_resample_destroy": "comms_resample_set_timer"}[node._destroy]
+                "comms_resample_destroy": "comms_resample_set_timer",
+                "comms_channelizer_destroy": "comms_channelizer_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

@@ -562,6 +562,67 @@ where
     }
 }
 
+/// Polyphase channelizer (an additional node): what the reference wires as `channels` chains
+/// `MixerNode::new(0, -2 pi k / M) -> BatchFirNode(Complex(taps, 0)) -> DecimateNode(down)` on one source, as one node
+/// that reads every sample once.  Any batch length, `ceil(n / down)` frames per call; the output carries a call's
+/// `frames * channels` samples channel-major (`out[k * frames + j]`) unless built with `new_frame_major`.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct ChannelizerNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    h: *mut comms_channelizer_t,
+    channels: usize,
+    down: usize,
+    pub output: NodeSender<Vec<Complex<f32>>>,
+}
+unsafe impl Send for ChannelizerNode {}
+impl Drop for ChannelizerNode {
+    fn drop(&mut self) { unsafe { comms_channelizer_destroy(self.h); } }
+}
+impl ChannelizerNode {
+    fn with_layout(taps: Vec<f32>, channels: usize, down: usize, layout: i32) -> Self {
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_channelizer_create(taps.as_ptr(), taps.len(), channels, down, layout, 0, &mut h) };
+        assert_eq!(st, COMMS_OK, "comms_channelizer_create failed");
+        ChannelizerNode { input: Default::default(), h, channels, down, output: Default::default() }
+    }
+    pub fn new(taps: Vec<f32>, channels: usize, down: usize) -> Self {
+        Self::with_layout(taps, channels, down, COMMS_CHANNELIZER_CHANNEL_MAJOR)
+    }
+    pub fn new_frame_major(taps: Vec<f32>, channels: usize, down: usize) -> Self {
+        Self::with_layout(taps, channels, down, COMMS_CHANNELIZER_FRAME_MAJOR)
+    }
+    pub fn run(&mut self, samples: &[Complex<f32>]) -> Result<Vec<Complex<f32>>, NodeError> {
+        let mut frames = 0usize;
+        let st = unsafe { comms_channelizer_out_len(samples.len(), self.down, &mut frames) };
+        if st != COMMS_OK { return Err(to_err(st)); }
+        let mut out = vec![Complex::<f32>::zero(); frames * self.channels];
+        let st = unsafe { comms_channelizer_run(self.h, samples.as_ptr(), samples.len(), out.as_mut_ptr()) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    /// The checkpoint hooks: the last `n` input samples, newest first, and the stream index mod `channels`
+    pub fn state(&mut self, n: usize) -> Result<Vec<Complex<f32>>, NodeError> {
+        let mut out = vec![Complex::<f32>::zero(); n];
+        let st = unsafe { comms_channelizer_get_state(self.h, out.as_mut_ptr(), n) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    /// Exactly `taps.len() - 1` samples, newest first
+    pub fn set_state(&mut self, state: &[Complex<f32>]) -> Result<(), NodeError> {
+        let st = unsafe { comms_channelizer_set_state(self.h, state.as_ptr(), state.len()) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    pub fn phase(&mut self) -> Result<u64, NodeError> {
+        let mut t = 0u64;
+        let st = unsafe { comms_channelizer_get_phase(self.h, &mut t) };
+        if st == COMMS_OK { Ok(t) } else { Err(to_err(st)) }
+    }
+    /// Any stream index `t`; the node reduces it mod `channels`
+    pub fn set_phase(&mut self, t: u64) -> Result<(), NodeError> {
+        let st = unsafe { comms_channelizer_set_phase(self.h, t) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+}
+
 /// Sample types `UniformNode<T>` is built for: `f32` (values in `[start, end)`) and `u8` over `[0, 2)`, which is what
 /// `random_bit()` returns (rand_node.rs:150-152).
 pub trait UniformSample: Copy + Send + 'static {
