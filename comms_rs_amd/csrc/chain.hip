@@ -40,7 +40,7 @@ static bool reads_wire_format(ChainKind k) {
 }
 // the mixer runs in front of the FIR node, whose history then holds mixed samples: the raw ones are kept beside it
 static bool has_raw_history(ChainKind k) { return k == ChainKind::Series; }
-// the kernel takes the FM demodulator's state (d_prev, ping-pong) as arguments
+// the kernel takes the FM demodulator's state (fm_prev) as arguments
 static bool has_fm_prev(ChainKind k) {
     return k == ChainKind::Os1024 || k == ChainKind::Decim || k == ChainKind::DecimAny || k == ChainKind::Poly8;
 }
@@ -63,15 +63,13 @@ struct comms_chain : Handle {
     comms_fir_t* fir = nullptr;
     // fused kinds: oscillator phase and FM demod state
     uint64_t turns = 0, frac = 0;
-    float2* d_prev[2] = {nullptr, nullptr};
-    int cur = 0;
+    History fm_prev;  // has_fm_prev: FM.prev, one sample
     // series kinds
     comms_mixer_t* mixer = nullptr;
     comms_fmdemod_t* fm = nullptr;  // (and fm_separate)
     double dphase = 0.0;  // wrapped, as the mixer steps it
     Scratch t1, t2, t3;
-    float2* raw_hist[2] = {nullptr, nullptr};  // has_raw_history: last n_eff raw inputs, time order
-    int raw_cur = 0;
+    History raw_hist;                          // has_raw_history: last n_eff raw inputs
     std::vector<comms_c32> pending_raw;        // a user state not yet mixed into the FIR node's history
     int in_fmt = COMMS_IQ_C32;                 // wire format of d_in (comms_chain_set_input_format)
     float in_scale = 1.0f;
@@ -112,10 +110,8 @@ static void free_chain(comms_chain* h) {
     if (h->fir) comms_fir_destroy(h->fir);
     if (h->fm) comms_fmdemod_destroy(h->fm);
     (void)use_device(h->device);
-    if (h->d_prev[0]) (void)hipFree(h->d_prev[0]);
-    if (h->d_prev[1]) (void)hipFree(h->d_prev[1]);
-    if (h->raw_hist[0]) (void)hipFree(h->raw_hist[0]);
-    if (h->raw_hist[1]) (void)hipFree(h->raw_hist[1]);
+    h->fm_prev.release();
+    h->raw_hist.release();
     h->t1.release();
     h->t2.release();
     h->t3.release();
@@ -235,16 +231,6 @@ static std::vector<comms_c32> modulated_taps(const comms_c32* taps, size_t n_tap
     return mod;
 }
 
-// two zeroed device buffers (a ping-pong state)
-static comms_status_t alloc_state_pair(float2* (&buf)[2], size_t bytes) {
-    for (float2*& b : buf) {
-        hipError_t e = hipMalloc(&b, bytes);
-        if (e == hipSuccess) e = zero_device(b, bytes);
-        if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "chain state alloc: %s", hipGetErrorString(e));
-    }
-    return COMMS_OK;
-}
-
 extern "C" {
 
 comms_status_t comms_chain_create_ex(double dphase, double phase, const comms_c32* taps, size_t n_taps,
@@ -253,18 +239,13 @@ comms_status_t comms_chain_create_ex(double dphase, double phase, const comms_c3
     *out = nullptr;
     COMMS_ARG(rate >= 1, "rate must be >= 1");
     COMMS_ARG(std::isfinite(dphase) && std::isfinite(phase), "dphase/phase must be finite");
-    comms_chain* h = new (std::nothrow) comms_chain;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    comms_chain* h = nullptr;
+    COMMS_TRY(make_handle(device, &h));
     h->rate = rate;
     h->dphase = mix_wrap_dphase(dphase);
     h->fm_demod = (flags & COMMS_CHAIN_FM_DEMOD) != 0;
     h->time_domain = (flags & COMMS_CHAIN_TIME_DOMAIN) != 0;
-    st = [&]() -> comms_status_t {
+    const comms_status_t st = [&]() -> comms_status_t {
         COMMS_TRY(comms_fir_create(taps, n_taps, nullptr, 0, device, &h->fir));
         const ChainPlan p = plan_chain(h->fir, rate, flags);
         h->kind = p.kind;
@@ -283,8 +264,9 @@ comms_status_t comms_chain_create_ex(double dphase, double phase, const comms_c3
             COMMS_TRY(comms_mixer_create(dphase, phase, device, &h->mixer));
         }
         if (p.fm_separate) COMMS_TRY(comms_fmdemod_create(device, &h->fm));
-        if (has_fm_prev(p.kind)) COMMS_TRY(alloc_state_pair(h->d_prev, sizeof(float2)));
-        if (has_raw_history(p.kind)) COMMS_TRY(alloc_state_pair(h->raw_hist, static_cast<size_t>(h->fir->n_eff) * sizeof(float2)));
+        hipError_t e = has_fm_prev(p.kind) ? h->fm_prev.alloc(1, sizeof(float2)) : hipSuccess;
+        if (e == hipSuccess && has_raw_history(p.kind)) e = h->raw_hist.alloc(static_cast<size_t>(h->fir->n_eff), sizeof(float2));
+        if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "chain state alloc: %s", hipGetErrorString(e));
         return COMMS_OK;
     }();
     if (st != COMMS_OK) {
@@ -351,8 +333,8 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
             stage_out = h->t3.p;
         }
         bool decided = false;  // the launch wrote the bits itself
-        float2* prev = h->d_prev[h->cur];
-        float2* prev_new = h->d_prev[h->cur ^ 1];
+        float2* prev = h->fm_prev.cur<float2>();
+        float2* prev_new = h->fm_prev.next<float2>();
         switch (h->kind) {
             case ChainKind::Os4096Dec:
                 COMMS_TRY(comms_fir_run_os4096_decim_dev(h->fir, d_in, n, stage_out, h->turns, h->frac, rate, s));
@@ -388,7 +370,7 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
             return sym_to_bits_launch(static_cast<const comms_c32*>(stage_out), n_dec, h->out_sym, static_cast<uint8_t*>(d_out), hs);
         if (h->fm_separate)
             return comms_fmdemod_run_dev(h->fm, static_cast<const comms_c32*>(stage_out), n_dec, static_cast<float*>(d_out), s);
-        if (h->fm_demod) h->cur ^= 1;
+        if (h->fm_demod) h->fm_prev.flip();
         return COMMS_OK;
     }
     COMMS_TRY(h->t1.reserve(n * sizeof(comms_c32)));
@@ -407,10 +389,10 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
         COMMS_TRY(chain_flush_raw_state(h));
         COMMS_TRY(comms_mixer_run_dev(h->mixer, d_in, n, a, s));
         COMMS_TRY(comms_fir_run_dev(h->fir, a, n, b, s));
-        chain_raw_hist_kernel<<<dim3(1), dim3(256), 0, hs>>>(h->raw_hist[h->raw_cur], reinterpret_cast<const float2*>(d_in), n,
-                                                             h->raw_hist[h->raw_cur ^ 1], h->fir->n_eff);
+        chain_raw_hist_kernel<<<dim3(1), dim3(256), 0, hs>>>(h->raw_hist.cur<float2>(), reinterpret_cast<const float2*>(d_in), n,
+                                                             h->raw_hist.next<float2>(), h->fir->n_eff);
         COMMS_TRY(launch_ok("chain_raw_hist_kernel"));
-        h->raw_cur ^= 1;
+        h->raw_hist.flip();
         COMMS_TRY(comms_decimate_run_dev(b, n, sizeof(comms_c32), h->rate, dec, nullptr, h->device, s));
     }
     if (h->out_bits) return sym_to_bits_launch(dec, n_dec, h->out_sym, static_cast<uint8_t*>(d_out), hs);
@@ -480,11 +462,7 @@ comms_status_t comms_chain_set_fir_state(comms_chain_t* h, const comms_c32* stat
     COMMS_TRY(h->quiesce());
     if (!has_raw_history(h->kind)) return comms_fir_set_state(h->fir, state, n_state);
     COMMS_ARG(n_state == static_cast<size_t>(h->fir->n_eff), "state must hold exactly the %d effective taps", h->fir->n_eff);
-    {
-        std::vector<float2> ring(n_state);
-        for (size_t k = 0; k < n_state; ++k) ring[n_state - 1 - k] = make_float2(state[k].re, state[k].im);
-        COMMS_HIP_TRY(hipMemcpy(h->raw_hist[h->raw_cur], ring.data(), n_state * sizeof(float2), hipMemcpyHostToDevice));
-    }
+    COMMS_HIP_TRY(h->raw_hist.upload(state, n_state));
     h->pending_raw.assign(state, state + n_state);  // mixed into the FIR node's history at the next run
     return COMMS_OK;
 }
@@ -496,12 +474,7 @@ comms_status_t comms_chain_get_fir_state(comms_chain_t* h, comms_c32* state, siz
     if (!has_raw_history(h->kind)) return comms_fir_get_state(h->fir, state, n_state);
     const size_t N = static_cast<size_t>(h->fir->n_eff);
     COMMS_ARG(n_state <= N, "n_state %zu exceeds the %zu effective taps", n_state, N);
-    std::vector<float2> ring(N);
-    COMMS_HIP_TRY(hipMemcpy(ring.data(), h->raw_hist[h->raw_cur], N * sizeof(float2), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_state; ++k) {
-        state[k].re = ring[N - 1 - k].x;
-        state[k].im = ring[N - 1 - k].y;
-    }
+    COMMS_HIP_TRY(h->raw_hist.download(state, n_state));
     return COMMS_OK;
 }
 
@@ -529,7 +502,7 @@ comms_status_t comms_chain_get_fm_prev(comms_chain_t* h, comms_c32* out_prev) {
     if (h->fm_separate) return comms_fmdemod_get_prev(h->fm, out_prev);
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(hipMemcpy(out_prev, h->d_prev[h->cur], sizeof(float2), hipMemcpyDeviceToHost));
+    COMMS_HIP_TRY(h->fm_prev.download(out_prev, 1));
     return COMMS_OK;
 }
 
@@ -539,7 +512,7 @@ comms_status_t comms_chain_set_fm_prev(comms_chain_t* h, const comms_c32* prev) 
     if (h->fm_separate) return comms_fmdemod_set_prev(h->fm, prev);
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(hipMemcpy(h->d_prev[h->cur], prev, sizeof(float2), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(h->fm_prev.upload(prev, 1));
     return COMMS_OK;
 }
 

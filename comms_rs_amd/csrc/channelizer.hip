@@ -263,8 +263,7 @@ struct comms_channelizer : Handle {
     unsigned max_grid = 1;
     float* d_tab = nullptr;
     float2* d_tw = nullptr;
-    float2* d_hist[2] = {nullptr, nullptr};  // last H samples, time order, ping-pong
-    int cur = 0;
+    History hist;            // last H samples
     // the series: one chain per channel (made on first use), the padded stream and the chains' outputs
     std::vector<float> taps;
     std::vector<comms_chain_t*> chains;
@@ -318,8 +317,7 @@ void free_channelizer(comms_channelizer* h) {
         if (c) (void)comms_chain_destroy(c);
     if (h->d_tab) (void)hipFree(h->d_tab);
     if (h->d_tw) (void)hipFree(h->d_tw);
-    if (h->d_hist[0]) (void)hipFree(h->d_hist[0]);
-    if (h->d_hist[1]) (void)hipFree(h->d_hist[1]);
+    h->hist.release();
     h->ext.release();
     h->tmp.release();
     h->fini();
@@ -372,7 +370,7 @@ comms_status_t run_series(comms_channelizer* h, const float2* d_in, size_t n, fl
     float2* ext = static_cast<float2*>(h->ext.p);
     float2* tmp = static_cast<float2*>(h->tmp.p);
     const unsigned blocks = static_cast<unsigned>(std::min<size_t>((total + 255) / 256, static_cast<size_t>(kNumCU) * 8));
-    chz_prep_kernel<<<dim3(blocks), dim3(256), 0, s>>>(d_in, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], ext, n, total, P, static_cast<int>(H));
+    chz_prep_kernel<<<dim3(blocks), dim3(256), 0, s>>>(d_in, h->hist.cur<float2>(), h->hist.next<float2>(), ext, n, total, P, static_cast<int>(H));
     COMMS_TRY(launch_ok("chz_prep_kernel"));
     const uint64_t t0 = (h->r + M - P % M) % M;  // (t - P) mod M: the stream index of ext[0]
     for (size_t k = 0; k < M; ++k) {
@@ -426,13 +424,8 @@ comms_status_t comms_channelizer_create(const float* taps, size_t n_taps, size_t
     const bool series = !in_kernel_range(channels, n_taps, D);
     COMMS_ARG(!series || channels <= CHZ_MAX_SERIES_M, "%zu channels: outside the kernel's range the node runs one chain per channel, at most %zu",
               channels, CHZ_MAX_SERIES_M);
-    comms_channelizer* h = new (std::nothrow) comms_channelizer;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    comms_channelizer* h = nullptr;
+    COMMS_TRY(make_handle(device, &h));
     h->n_taps = n_taps;
     h->M = channels;
     h->D = D;
@@ -440,19 +433,13 @@ comms_status_t comms_channelizer_create(const float* taps, size_t n_taps, size_t
     h->layout = layout;
     h->series = series;
     h->taps.assign(taps, taps + n_taps);
-    const size_t hist_bytes = (h->H ? h->H : 1) * sizeof(float2);
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(reinterpret_cast<void**>(&h->d_hist[i]), hist_bytes);
-        if (e == hipSuccess) e = zero_device(h->d_hist[i], hist_bytes);
-    }
+    hipError_t e = h->hist.alloc(h->H, sizeof(float2));
     if (e == hipSuccess && !series) {
         const size_t M = channels;
         while ((static_cast<size_t>(1) << h->lgM) < M) ++h->lgM;
         h->Q = static_cast<int>((n_taps + M - 1) / M);
         plan_tile(h);
-        const size_t per_cu = std::min<size_t>(8, (160 * 1024) / (h->lds < 1024 ? 1024 : h->lds));
-        h->max_grid = static_cast<unsigned>(kNumCU * (per_cu < 1 ? 1 : per_cu));
+        h->max_grid = resident_workgroups(h->lds);
         const int cap = diag_knob("COMMS_CHANNELIZER_GRID", 0);  // sweeps: fewer workgroups
         if (cap > 0 && static_cast<unsigned>(cap) < h->max_grid) h->max_grid = static_cast<unsigned>(cap);
         std::vector<float> tab(static_cast<size_t>(h->Q) * M, 0.0f);
@@ -472,7 +459,7 @@ comms_status_t comms_channelizer_create(const float* taps, size_t n_taps, size_t
         return fail(COMMS_ERR_DEVICE, "channelizer alloc: %s", hipGetErrorString(e));
     }
     if (series) {
-        st = ensure_chains(h);
+        const comms_status_t st = ensure_chains(h);
         if (st != COMMS_OK) {
             free_channelizer(h);
             return st;
@@ -501,8 +488,8 @@ comms_status_t comms_channelizer_run_dev(comms_channelizer_t* h, const comms_c32
     } else {
         ChzArgs a{};
         a.in = in;
-        a.hist = h->d_hist[h->cur];
-        a.new_hist = h->d_hist[h->cur ^ 1];
+        a.hist = h->hist.cur<float2>();
+        a.new_hist = h->hist.next<float2>();
         a.out = out;
         a.taps = h->d_tab;
         a.tw = h->d_tw;
@@ -527,7 +514,7 @@ comms_status_t comms_channelizer_run_dev(comms_channelizer_t* h, const comms_c32
         h->toc(s);
         COMMS_TRY(st);
     }
-    h->cur ^= 1;
+    h->hist.flip();
     h->r = (h->r + n % h->M) % h->M;
     return COMMS_OK;
 }
@@ -551,10 +538,7 @@ comms_status_t comms_channelizer_get_state(comms_channelizer_t* h, comms_c32* st
     COMMS_ARG(state != nullptr || !n_state, "state is NULL");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());  // the history is advanced by the launches, on whatever stream they ran
-    if (!n_state) return COMMS_OK;
-    std::vector<comms_c32> ring(h->H);
-    COMMS_HIP_TRY(hipMemcpy(ring.data(), h->d_hist[h->cur], ring.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t q = 0; q < n_state; ++q) state[q] = ring[h->H - 1 - q];
+    COMMS_HIP_TRY(h->hist.download(state, n_state));
     return COMMS_OK;
 }
 
@@ -564,10 +548,7 @@ comms_status_t comms_channelizer_set_state(comms_channelizer_t* h, const comms_c
     COMMS_ARG(state != nullptr || !n_state, "state is NULL");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());  // no pending launch may still read the buffer that is overwritten
-    if (!n_state) return COMMS_OK;
-    std::vector<comms_c32> ring(h->H);
-    for (size_t q = 0; q < n_state; ++q) ring[h->H - 1 - q] = state[q];
-    COMMS_HIP_TRY(hipMemcpy(h->d_hist[h->cur], ring.data(), ring.size() * 8, hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(h->hist.upload(state, n_state));
     return COMMS_OK;
 }
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/comms_hip.h"
+#include "history_order.hpp"
 
 // fused-chain stage bits shared by fir.hip and chain.hip (internal)
 #define COMMS_CHAIN_PRE 1  /* mixer before the FIR */
@@ -200,6 +201,53 @@ inline hipError_t zero_device(void* p, size_t bytes) {
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     return e;
 }
+
+// The sample history every stateful node carries from one launch to the next: the last `len` samples in time order
+// (the "ring" of history_order.hpp), twice.  A launch reads cur() and writes the advanced history to next() -- all
+// `len` entries of it, so next() never needs a defined content -- and the host calls flip() once the launch is queued.
+// upload / download exchange the reference's newest-first state with cur(); they are synchronous and do NOT wait for
+// the node's stream: the caller quiesces its handle first.
+struct History {
+    void* buf[2] = {nullptr, nullptr};
+    size_t len = 0, elem = 0;  // samples kept, bytes per sample
+    int idx = 0;
+    // both buffers zero-filled (at least one sample each: an empty history still hands the kernels a valid address)
+    hipError_t alloc(size_t n_elems, size_t elem_bytes) {
+        len = n_elems;
+        elem = elem_bytes;
+        const size_t bytes = (len ? len : 1) * elem;
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+            e = hipMalloc(&buf[i], bytes);
+            if (e == hipSuccess) e = zero_device(buf[i], bytes);
+        }
+        return e;
+    }
+    void release() {
+        for (void*& b : buf) {
+            if (b) (void)hipFree(b);
+            b = nullptr;
+        }
+    }
+    template <class T = void>
+    T* cur() const { return static_cast<T*>(buf[idx]); }
+    template <class T = void>
+    T* next() const { return static_cast<T*>(buf[idx ^ 1]); }
+    void flip() { idx ^= 1; }
+    // state (newest first; entries beyond `len` ignored, missing ones zero) -> cur()
+    hipError_t upload(const void* state, size_t n_state) {
+        std::vector<char> ring(len * elem);
+        state_to_ring(ring.data(), len, state, n_state, elem);
+        return len ? hipMemcpy(buf[idx], ring.data(), ring.size(), hipMemcpyHostToDevice) : hipSuccess;
+    }
+    // cur() -> its newest min(len, n_state) samples, newest first
+    hipError_t download(void* state, size_t n_state) const {
+        std::vector<char> ring(len * elem);
+        hipError_t e = len ? hipMemcpy(ring.data(), buf[idx], ring.size(), hipMemcpyDeviceToHost) : hipSuccess;
+        if (e == hipSuccess) ring_to_state(state, n_state, ring.data(), len, elem);
+        return e;
+    }
+};
 
 // calls moving at most this many bytes each way take the zero-copy route (COMMS_ZERO_COPY_BYTES)
 size_t zero_copy_limit();
@@ -560,6 +608,20 @@ struct Handle {
     }
 };
 
+// What every *_create starts with: a handle of its own stream on `device`, or the error and no handle
+template <class H>
+comms_status_t make_handle(int32_t device, H** out) {
+    H* h = new (std::nothrow) H;
+    COMMS_ARG(h != nullptr, "out of host memory");
+    const comms_status_t st = h->init(device);
+    if (st != COMMS_OK) {
+        delete h;
+        return st;
+    }
+    *out = h;
+    return COMMS_OK;
+}
+
 // Handle-less host-pointer entry points (resampling, IQ formats, estimators) borrow a per-thread,
 // per-device handle (stream + staging), created on first use and kept for the thread's life:
 // no hipMalloc / hipFree -- which also synchronise the device -- per call.  The handles END with their thread
@@ -602,6 +664,12 @@ inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 }
 
 constexpr int kNumCU = 256;  // MI355X: 8 XCD x 32 CU
+// Grid cap of a persistent kernel that uses `lds` bytes per workgroup: the workgroups the chip holds at once, at most
+// eight per CU and as many as fit the CU's 160 KiB of LDS (a kernel below 1 KiB counts as 1 KiB)
+inline unsigned resident_workgroups(size_t lds) {
+    const size_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : lds);
+    return static_cast<unsigned>(kNumCU * (per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu));
+}
 
 // Mixer phase bookkeeping shared by the mixer node and the fused chain: phases are
 // 64-bit fixed-point fractions ("turns") of T = fl(2*pi), the constant the reference

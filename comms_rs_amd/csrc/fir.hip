@@ -1345,8 +1345,7 @@ static void free_fir(comms_fir* h) {
         if (q) (void)hipFree(q);
     for (float2* q : h->d_xt)
         if (q) (void)hipFree(q);
-    if (h->d_hist[0]) (void)hipFree(h->d_hist[0]);
-    if (h->d_hist[1]) (void)hipFree(h->d_hist[1]);
+    h->hist.release();
     if (h->err_host) (void)hipHostFree(h->err_host);
     h->fini();
     delete h;
@@ -1702,15 +1701,6 @@ static int fir_pick(const comms_fir* h, size_t n) {
 }
 
 
-static comms_status_t fir_upload_state(comms_fir* h, const comms_c32* state, size_t n_state) {
-    // reference layout: state[0] newest ... -> device ring is time-ordered (oldest first)
-    std::vector<float2> ring(h->n_eff, make_float2(0.f, 0.f));
-    for (int k = 0; k < h->n_eff && static_cast<size_t>(k) < n_state; ++k)
-        ring[h->n_eff - 1 - k] = make_float2(state[k].re, state[k].im);
-    COMMS_HIP_TRY(hipMemcpy(h->d_hist[h->cur], ring.data(), ring.size() * sizeof(float2), hipMemcpyHostToDevice));
-    return COMMS_OK;
-}
-
 extern "C" {
 
 comms_status_t comms_fir_create(const comms_c32* taps, size_t n_taps, const comms_c32* state,
@@ -1722,32 +1712,18 @@ comms_status_t comms_fir_create(const comms_c32* taps, size_t n_taps, const comm
     size_t n_eff = n_taps;
     if (state && n_state < n_eff) n_eff = n_state;  // zip(taps, state), fir.rs:53
     COMMS_ARG(n_eff <= (1u << 20), "too many taps (%zu)", n_eff);
-    comms_fir* h = new (std::nothrow) comms_fir;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    comms_fir* h = nullptr;
+    COMMS_TRY(make_handle(device, &h));
     h->n_eff = static_cast<int>(n_eff);
     h->taps.assign(taps, taps + n_eff);
     h->real_taps = true;
     for (size_t k = 0; k < n_eff; ++k)
         if (taps[k].im != 0.0f) h->real_taps = false;
-    for (int i = 0; i < 2; ++i) {
-        hipError_t e = hipMalloc(&h->d_hist[i], n_eff * sizeof(float2));
-        if (e == hipSuccess) e = zero_device(h->d_hist[i], n_eff * sizeof(float2));
-        if (e != hipSuccess) {
-            free_fir(h);
-            return fail(COMMS_ERR_DEVICE, "FIR history alloc: %s", hipGetErrorString(e));
-        }
-    }
-    if (state) {
-        st = fir_upload_state(h, state, n_state);
-        if (st != COMMS_OK) {
-            free_fir(h);
-            return st;
-        }
+    hipError_t e = h->hist.alloc(n_eff, sizeof(float2));
+    if (e == hipSuccess && state) e = h->hist.upload(state, n_state);
+    if (e != hipSuccess) {
+        free_fir(h);
+        return fail(COMMS_ERR_DEVICE, "FIR history alloc: %s", hipGetErrorString(e));
     }
     *out = h;
     return COMMS_OK;
@@ -1819,7 +1795,7 @@ comms_status_t comms_fir_get_algo(const comms_fir_t* h, size_t n, int32_t* out_a
 template <int HR, class In>
 static comms_status_t launch_dyn_in(hipStream_t s, In in, comms_fir* h, float2* o, size_t n, const WTables& tb, float2* nh,
                                     hipEvent_t ea, hipEvent_t eb, KStamp ks) {
-    return launch_os1024_dyn<HR, false, In>(s, in, h->d_hist[h->cur], h->n_eff, o, n, tb, nh, nullptr, ea, eb, ks);
+    return launch_os1024_dyn<HR, false, In>(s, in, h->hist.cur<float2>(), h->n_eff, o, n, tb, nh, nullptr, ea, eb, ks);
 }
 template <class In>
 static comms_status_t launch_dyn_hr(int hr, hipStream_t s, In in, comms_fir* h, float2* o, size_t n, const WTables& tb,
@@ -1891,8 +1867,8 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
     float2* o = reinterpret_cast<float2*>(d_out);
-    const float2* hist = h->d_hist[h->cur];
-    float2* nh = h->d_hist[h->cur ^ 1];  // the kernel's workgroup 0 advances the history into it
+    const float2* hist = h->hist.cur<float2>();
+    float2* nh = h->hist.next<float2>();  // the kernel's workgroup 0 advances the history into it
     const int algo = fir_pick(h, n);
     // Complex<f32> input, or null: every kernel here reads raw i16 / u8 IQ in its load stage (with_input_view)
     const float2* in = h->in_fmt == COMMS_IQ_C32 ? static_cast<const float2*>(d_in) : nullptr;
@@ -1970,7 +1946,7 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
         h->toc(s);
         COMMS_TRY(launch_ok("fir_os4096_kernel"));
     }
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 
@@ -1995,12 +1971,7 @@ comms_status_t comms_fir_get_state(comms_fir_t* h, comms_c32* state, size_t n_st
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());  // the history is advanced by the launches, on whatever stream they ran
     COMMS_TRY(fir_check_sticky(h));
-    std::vector<float2> ring(h->n_eff);
-    COMMS_HIP_TRY(hipMemcpy(ring.data(), h->d_hist[h->cur], ring.size() * sizeof(float2), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_state; ++k) {
-        state[k].re = ring[h->n_eff - 1 - k].x;
-        state[k].im = ring[h->n_eff - 1 - k].y;
-    }
+    COMMS_HIP_TRY(h->hist.download(state, n_state));
     return COMMS_OK;
 }
 
@@ -2010,7 +1981,8 @@ comms_status_t comms_fir_set_state(comms_fir_t* h, const comms_c32* state, size_
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());  // no pending launch may still read the buffer that is overwritten
     COMMS_TRY(fir_check_sticky(h));
-    return fir_upload_state(h, state, n_state);
+    COMMS_HIP_TRY(h->hist.upload(state, n_state));
+    return COMMS_OK;
 }
 
 comms_status_t comms_fir_set_timer(comms_fir_t* h, comms_timer_t* t) {
@@ -2045,8 +2017,8 @@ comms_status_t comms_fir_run_fused_dev(comms_fir_t* h, const comms_c32* d_in, si
     COMMS_TRY(h->enter(stream, &s));
     const float2* in = reinterpret_cast<const float2*>(d_in);
     float2* o = reinterpret_cast<float2*>(d_out);
-    const float2* hist = h->d_hist[h->cur];
-    float2* nh = h->d_hist[h->cur ^ 1];
+    const float2* hist = h->hist.cur<float2>();
+    float2* nh = h->hist.next<float2>();
     ChainArgs ch{};
     ch.turns0 = turns0;
     ch.frac = frac;
@@ -2089,7 +2061,7 @@ comms_status_t comms_fir_run_fused_dev(comms_fir_t* h, const comms_c32* d_in, si
     }
     h->toc(s);
     COMMS_TRY(launch_ok("fir_os1024_kernel (fused)"));
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 
@@ -2121,8 +2093,8 @@ comms_status_t comms_fir_run_os16k_decim_dev(comms_fir_t* h, const comms_c32* d_
     COMMS_TRY(h->enter(stream, &s));
     const float2* in = reinterpret_cast<const float2*>(d_in);
     float2* o = reinterpret_cast<float2*>(d_out);
-    const float2* hist = h->d_hist[h->cur];
-    float2* nh = h->d_hist[h->cur ^ 1];
+    const float2* hist = h->hist.cur<float2>();
+    float2* nh = h->hist.next<float2>();
     const int hr = h->n_eff <= 2049 ? 2 : h->n_eff <= 3073 ? 3 : 4;
     const size_t xv = static_cast<size_t>(16 - hr) * 1024;
     const size_t nseg = (n + xv - 1) / xv;
@@ -2159,7 +2131,7 @@ comms_status_t comms_fir_run_os16k_decim_dev(comms_fir_t* h, const comms_c32* d_
     }
     h->toc(s);
     COMMS_TRY(launch_ok("fir_os16k_kernel (decimating)"));
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 
@@ -2180,8 +2152,8 @@ comms_status_t comms_fir_run_os4096_decim_dev(comms_fir_t* h, const void* d_in, 
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
     float2* o = reinterpret_cast<float2*>(d_out);
-    const float2* hist = h->d_hist[h->cur];
-    float2* nh = h->d_hist[h->cur ^ 1];
+    const float2* hist = h->hist.cur<float2>();
+    float2* nh = h->hist.next<float2>();
     const size_t V = OSF - 256 * static_cast<size_t>(h->hblk);
     const size_t nseg = (n + V - 1) / V;
     const size_t slots = static_cast<size_t>(3) * kNumCU;
@@ -2207,7 +2179,7 @@ comms_status_t comms_fir_run_os4096_decim_dev(comms_fir_t* h, const void* d_in, 
     });
     h->toc(s);
     COMMS_TRY(launch_ok("fir_os4096_kernel (decimating)"));
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 
@@ -2225,8 +2197,7 @@ struct comms_pulse : Handle {
     int sps = 1;
     int hist_len = 0;  // symbols of history kept: ceil(n_taps / sps)
     float2* d_taps = nullptr;
-    float2* d_hist[2] = {nullptr, nullptr};
-    int cur = 0;
+    History hist;
     std::vector<comms_c32> taps;  // host copy (kernel-argument taps of the polyphase kernel)
     bool real_taps = false;
     // fused output mixer (comms_pulse_set_mixer): phase of the next output, step per output
@@ -2257,8 +2228,8 @@ static bool pulse_poly_try(comms_pulse* h, In sym, size_t n_sym, float2* out, hi
     if (J > comms::PP_JMAX || J * SPSP > comms::PP_AMAX) return false;
     comms::PulseArgs a{};
     if constexpr (std::is_same<In, const float2*>::value) a.sym = sym;
-    a.hist = h->d_hist[h->cur];
-    a.new_hist = h->d_hist[h->cur ^ 1];
+    a.hist = h->hist.cur<float2>();
+    a.new_hist = h->hist.next<float2>();
     a.out = out;
     a.n_sym = n_sym;
     a.hist_len = h->hist_len;
@@ -2336,8 +2307,7 @@ static bool pulse_poly_launch(comms_pulse* h, In sym, size_t n_sym, float2* out,
 static void free_pulse(comms_pulse* h) {
     (void)use_device(h->device);
     if (h->d_taps) (void)hipFree(h->d_taps);
-    if (h->d_hist[0]) (void)hipFree(h->d_hist[0]);
-    if (h->d_hist[1]) (void)hipFree(h->d_hist[1]);
+    h->hist.release();
     h->fini();
     delete h;
 }
@@ -2352,13 +2322,8 @@ comms_status_t comms_pulse_create(const comms_c32* taps, size_t n_taps, size_t s
     COMMS_ARG(sam_per_sym >= 1, "sam_per_sym must be >= 1 (0 underflows in the reference, pulse.rs:88)");
     COMMS_ARG(n_taps <= 8192, "pulse shaping supports at most 8192 taps (got %zu)", n_taps);
     COMMS_ARG(sam_per_sym <= (1u << 20), "sam_per_sym too large");
-    comms_pulse* h = new (std::nothrow) comms_pulse;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    comms_pulse* h = nullptr;
+    COMMS_TRY(make_handle(device, &h));
     h->n_taps = static_cast<int>(n_taps);
     h->sps = static_cast<int>(sam_per_sym);
     h->hist_len = static_cast<int>((n_taps + sam_per_sym - 1) / sam_per_sym);
@@ -2368,10 +2333,7 @@ comms_status_t comms_pulse_create(const comms_c32* taps, size_t n_taps, size_t s
         if (taps[k].im != 0.0f) h->real_taps = false;
     hipError_t e = hipMalloc(&h->d_taps, n_taps * sizeof(float2));
     if (e == hipSuccess) e = hipMemcpy(h->d_taps, taps, n_taps * sizeof(float2), hipMemcpyHostToDevice);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(&h->d_hist[i], h->hist_len * sizeof(float2));
-        if (e == hipSuccess) e = zero_device(h->d_hist[i], h->hist_len * sizeof(float2));
-    }
+    if (e == hipSuccess) e = h->hist.alloc(h->hist_len, sizeof(float2));
     if (e != hipSuccess) {
         free_pulse(h);
         return fail(COMMS_ERR_DEVICE, "pulse alloc: %s", hipGetErrorString(e));
@@ -2409,17 +2371,17 @@ comms_status_t comms_pulse_run_dev(comms_pulse_t* h, const comms_c32* d_sym, siz
         with_pulse_input(h, d_sym, [&](auto sym) {
             if constexpr (std::is_same<decltype(sym), const float2*>::value)
                 pulse_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(256), h->n_taps * sizeof(float2), s>>>(
-                    sym, h->d_hist[h->cur], h->hist_len, h->d_taps, h->n_taps, h->sps,
-                    reinterpret_cast<float2*>(d_out), n_sym, h->d_hist[h->cur ^ 1], mx);
+                    sym, h->hist.cur<float2>(), h->hist_len, h->d_taps, h->n_taps, h->sps,
+                    reinterpret_cast<float2*>(d_out), n_sym, h->hist.next<float2>(), mx);
             else
                 pulse_in_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(256), h->n_taps * sizeof(float2), s>>>(
-                    sym, h->d_hist[h->cur], h->hist_len, h->d_taps, h->n_taps, h->sps,
-                    reinterpret_cast<float2*>(d_out), n_sym, h->d_hist[h->cur ^ 1], mx);
+                    sym, h->hist.cur<float2>(), h->hist_len, h->d_taps, h->n_taps, h->sps,
+                    reinterpret_cast<float2*>(d_out), n_sym, h->hist.next<float2>(), mx);
         });
         h->toc(s);
     }
     COMMS_TRY(launch_ok("pulse kernel"));  // (workgroup 0 of the same launch advanced the history)
-    h->cur ^= 1;
+    h->hist.flip();
     if (h->mix) h->turns += static_cast<uint64_t>(n_out) * h->frac;
     return COMMS_OK;
 }

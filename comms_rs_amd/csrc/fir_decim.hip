@@ -832,8 +832,8 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
     a.in = d_in;
     a.fmt = h->in_fmt;
     a.in_scale = h->in_scale;
-    a.hist = h->d_hist[h->cur];
-    a.new_hist = h->d_hist[h->cur ^ 1];
+    a.hist = h->hist.cur<float2>();
+    a.new_hist = h->hist.next<float2>();
     a.out = d_out;
     a.fm_prev = static_cast<const float2*>(fm_prev);
     a.fm_prev_new = static_cast<float2*>(fm_prev_new);
@@ -924,7 +924,7 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
                  : R == 4 ? launch_decim_wave<4>(a, real, pre, nt_big, s)
                           : launch_decim_wave<8>(a, real, pre, nt_big, s);
             COMMS_TRY(st);
-            h->cur ^= 1;
+            h->hist.flip();
             if (bits) return sym_to_bits_launch(static_cast<const comms_c32*>(wave_out), a.n_out, *bits, static_cast<uint8_t*>(d_out), s);
             return COMMS_OK;
         }
@@ -938,7 +938,7 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
         st = launch_decim_rate(a, R, real, s);
     }
     COMMS_TRY(st);
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 

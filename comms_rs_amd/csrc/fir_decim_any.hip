@@ -342,8 +342,8 @@ comms_status_t comms_fir_run_decim_any_dev(comms_fir_t* h, const void* d_in, siz
     a.in = d_in;
     a.fmt = h->in_fmt;
     a.in_scale = h->in_scale;
-    a.hist = h->d_hist[h->cur];
-    a.new_hist = h->d_hist[h->cur ^ 1];
+    a.hist = h->hist.cur<float2>();
+    a.new_hist = h->hist.next<float2>();
     a.out = d_out;
     a.fm_prev = static_cast<const float2*>(fm_prev);
     a.fm_prev_new = static_cast<float2*>(fm_prev_new);
@@ -388,7 +388,7 @@ comms_status_t comms_fir_run_decim_any_dev(comms_fir_t* h, const void* d_in, siz
     }
     h->toc(s);
     COMMS_TRY(st);
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 

@@ -113,8 +113,7 @@ struct ExactFir : Handle {
     int sps = 1;
     int hist_len = 0;   // samples (FIR: n_eff) or symbols (pulse: ceil(n_taps / sps)) of history
     V* d_taps = nullptr;
-    V* d_hist[2] = {nullptr, nullptr};
-    int cur = 0;
+    History hist;
 };
 
 }  // namespace comms
@@ -135,39 +134,22 @@ template <class V>
 void free_exact(ExactFir<V>* h) {
     (void)use_device(h->device);
     if (h->d_taps) (void)hipFree(h->d_taps);
-    if (h->d_hist[0]) (void)hipFree(h->d_hist[0]);
-    if (h->d_hist[1]) (void)hipFree(h->d_hist[1]);
+    h->hist.release();
     h->fini();
-}
-
-template <class V>
-void ring_from_state(std::vector<V>& ring, const CxOf<V>* state, size_t n_state) {
-    // device history is time-ordered (oldest first); the reference's state is newest first
-    const size_t hl = ring.size();
-    for (size_t k = 0; k < hl && k < n_state; ++k) ring[hl - 1 - k] = Exact<V>::make(state[k].re, state[k].im);
 }
 
 template <class V, class H>
 comms_status_t create(const CxOf<V>* taps, size_t n_eff, int sps, size_t hist_len, const CxOf<V>* state, size_t n_state,
                       int32_t device, H** out) {
-    H* h = new (std::nothrow) H;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    H* h = nullptr;
+    COMMS_TRY(make_handle(device, &h));
     h->n_eff = static_cast<int>(n_eff);
     h->sps = sps;
     h->hist_len = static_cast<int>(hist_len);
-    std::vector<V> ring(hist_len, Exact<V>::make(0, 0));
-    ring_from_state(ring, state, n_state);
     hipError_t e = hipMalloc(&h->d_taps, n_eff * sizeof(V));
     if (e == hipSuccess) e = hipMemcpy(h->d_taps, taps, n_eff * sizeof(V), hipMemcpyHostToDevice);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(&h->d_hist[i], (hist_len ? hist_len : 1) * sizeof(V));
-        if (e == hipSuccess && hist_len) e = hipMemcpy(h->d_hist[i], ring.data(), hist_len * sizeof(V), hipMemcpyHostToDevice);
-    }
+    if (e == hipSuccess) e = h->hist.alloc(hist_len, sizeof(V));
+    if (e == hipSuccess && n_state) e = h->hist.upload(state, n_state);
     if (e != hipSuccess) {
         free_exact<V>(h);
         delete h;
@@ -217,11 +199,11 @@ comms_status_t run_dev(ExactFir<V>* h, const CxOf<V>* d_in, size_t n, CxOf<V>* d
     if (blocks > 8u * kNumCU) blocks = 8u * kNumCU;
     h->tic(s);
     fir_exact_kernel<V><<<dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s>>>(
-        reinterpret_cast<const V*>(d_in), h->d_hist[h->cur], h->hist_len, h->d_taps, h->n_eff, h->sps,
-        reinterpret_cast<V*>(d_out), n, h->d_hist[h->cur ^ 1]);
+        reinterpret_cast<const V*>(d_in), h->hist.template cur<V>(), h->hist_len, h->d_taps, h->n_eff, h->sps,
+        reinterpret_cast<V*>(d_out), n, h->hist.template next<V>());
     h->toc(s);
     COMMS_TRY(launch_ok(Exact<V>::kKernel));
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 
@@ -243,12 +225,7 @@ comms_status_t get_state(ExactFir<V>* h, CxOf<V>* state, size_t n_state) {
     COMMS_ARG(n_state <= static_cast<size_t>(h->hist_len), "n_state %zu exceeds the %d effective taps", n_state, h->hist_len);
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    std::vector<V> ring(h->hist_len);
-    COMMS_HIP_TRY(hipMemcpy(ring.data(), h->d_hist[h->cur], ring.size() * sizeof(V), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_state; ++k) {
-        state[k].re = ring[h->hist_len - 1 - k].x;
-        state[k].im = ring[h->hist_len - 1 - k].y;
-    }
+    COMMS_HIP_TRY(h->hist.download(state, n_state));
     return COMMS_OK;
 }
 
@@ -258,9 +235,7 @@ comms_status_t set_state(ExactFir<V>* h, const CxOf<V>* state, size_t n_state) {
     COMMS_ARG(n_state == static_cast<size_t>(h->hist_len), "state must hold exactly the %d effective taps", h->hist_len);
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());  // no pending launch may still read the buffer that is overwritten
-    std::vector<V> ring(h->hist_len, Exact<V>::make(0, 0));
-    ring_from_state(ring, state, n_state);
-    COMMS_HIP_TRY(hipMemcpy(h->d_hist[h->cur], ring.data(), ring.size() * sizeof(V), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(h->hist.upload(state, n_state));
     return COMMS_OK;
 }
 

@@ -1,5 +1,6 @@
-// fir_handle.hpp -- the FIR node handle and the stream helpers shared by fir.hip and
-// fir_decim.hip.
+// fir_handle.hpp -- the FIR node handle (struct comms_fir; its sample history is a comms::History, common.hpp) and the
+// device helpers -- input views, buffer-addressed rows, hist_advance, stream_at, the FM demod steps -- shared by the files
+// that launch on that handle: fir.hip, fir_decim.hip, fir_decim_any.hip, fir_poly8.hip and chain.hip.
 #pragma once
 
 #include <vector>
@@ -220,9 +221,7 @@ struct comms_fir : comms::Handle {
     float2* d_tw1 = nullptr;
     float2* d_tw2 = nullptr;
     float2* d_hdev = nullptr;
-    // history: last n_eff input samples, time order, ping-pong
-    float2* d_hist[2] = {nullptr, nullptr};
-    int cur = 0;
+    comms::History hist;  // last n_eff input samples
     std::vector<comms_c32> taps;  // effective taps (host copy)
 };
 

@@ -540,10 +540,10 @@ comms_status_t poly8_launch_w(comms_fir* h, hipStream_t s, In in, void* out, siz
     const KStamp ks = h->next_stamp();
     if (ea)
         hipExtLaunchKernelGGL((fir_poly8_kernel<HR, FM, In, WPB, NPH>), grid, dim3(64 * WPB), static_cast<uint32_t>(lds), s, ea, eb, 0u, in,
-                              h->d_hist[h->cur], h->n_eff, out, n, tb, h->d_hist[h->cur ^ 1], chunk_log2, mx, fmx, ks);
+                              h->hist.cur<float2>(), h->n_eff, out, n, tb, h->hist.next<float2>(), chunk_log2, mx, fmx, ks);
     else
-        fir_poly8_kernel<HR, FM, In, WPB, NPH><<<grid, dim3(64 * WPB), lds, s>>>(in, h->d_hist[h->cur], h->n_eff, out, n, tb,
-                                                                                h->d_hist[h->cur ^ 1], chunk_log2, mx, fmx, ks);
+        fir_poly8_kernel<HR, FM, In, WPB, NPH><<<grid, dim3(64 * WPB), lds, s>>>(in, h->hist.cur<float2>(), h->n_eff, out, n, tb,
+                                                                                h->hist.next<float2>(), chunk_log2, mx, fmx, ks);
     return launch_ok("fir_poly8_kernel");
 }
 
@@ -674,7 +674,7 @@ comms_status_t comms_fir_run_poly8_dev(comms_fir_t* h, const void* d_in, size_t 
     const int nph = kind == 2 || kind == 4 ? 2 : 1;
     COMMS_TRY(with_input_view(h, d_in, static_cast<const float2*>(d_in),
                               [&](auto in) { return poly8_launch_in(hr, fm, nph, h, s, in, d_out, n, tb, mx, fmx); }));
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 

@@ -200,8 +200,7 @@ struct comms_resample : Handle {
     size_t lds = 0;
     unsigned max_grid = 1;
     float* d_tab = nullptr;
-    void* d_hist[2] = {nullptr, nullptr};  // last Q samples, time order, ping-pong
-    int cur = 0;
+    History hist;                   // last Q samples
     // the series: the complex FIR node carries the state (of the UPSAMPLED stream); two scratch streams of n up samples
     comms_fir_t* fir = nullptr;
     Scratch sa, sb;
@@ -235,8 +234,7 @@ void free_resample(comms_resample* h) {
     (void)use_device(h->device);
     if (h->fir) (void)comms_fir_destroy(h->fir);
     if (h->d_tab) (void)hipFree(h->d_tab);
-    if (h->d_hist[0]) (void)hipFree(h->d_hist[0]);
-    if (h->d_hist[1]) (void)hipFree(h->d_hist[1]);
+    h->hist.release();
     h->sa.release();
     h->sb.release();
     h->fini();
@@ -308,13 +306,8 @@ comms_status_t comms_resample_create(const float* taps, size_t n_taps, size_t up
     COMMS_ARG(elem == COMMS_RESAMPLE_F32 || elem == COMMS_RESAMPLE_C32, "elem must be COMMS_RESAMPLE_F32 (4) or COMMS_RESAMPLE_C32 (8), got %d", elem);
     COMMS_ARG(up <= 0x7fffffffu && down <= 0x7fffffffu, "rates %zu / %zu are out of range", up, down);
     COMMS_ARG(n_taps <= (1u << 20), "too many taps (%zu)", n_taps);
-    comms_resample* h = new (std::nothrow) comms_resample;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    comms_resample* h = nullptr;
+    COMMS_TRY(make_handle(device, &h));
     h->elem = elem;
     h->n_taps = n_taps;
     h->up = up < 1 ? 1 : up;
@@ -326,7 +319,7 @@ comms_status_t comms_resample_create(const float* taps, size_t n_taps, size_t up
     if (h->series) {
         std::vector<comms_c32> ct(n_taps);
         for (size_t k = 0; k < n_taps; ++k) ct[k] = comms_c32{taps[k], 0.0f};
-        st = comms_fir_create(ct.data(), n_taps, nullptr, 0, device, &h->fir);
+        const comms_status_t st = comms_fir_create(ct.data(), n_taps, nullptr, 0, device, &h->fir);
         if (st != COMMS_OK) {
             free_resample(h);
             return st;
@@ -343,18 +336,13 @@ comms_status_t comms_resample_create(const float* taps, size_t n_taps, size_t up
         return fail(COMMS_ERR_DEVICE, "resample: no tile fits (up %zu, down %zu, %zu taps)", L, M, n_taps);
     }
     h->WG = h->TO >= 256 ? 256 : h->TO < 64 ? 64 : h->TO;
-    const size_t per_cu = std::min<size_t>(8, (160 * 1024) / (h->lds < 1024 ? 1024 : h->lds));
-    h->max_grid = static_cast<unsigned>(kNumCU * (per_cu < 1 ? 1 : per_cu));
+    h->max_grid = resident_workgroups(h->lds);
     std::vector<float> tab(tab_floats, 0.0f);
     for (size_t p = 0; p < L; ++p)
         for (size_t q = 0; p + L * q < n_taps; ++q) tab[p * h->RS + q] = taps[p + L * q];
-    const size_t hist_bytes = (h->Q ? h->Q : 1) * static_cast<size_t>(elem);
     hipError_t e = hipMalloc(&h->d_tab, tab.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(&h->d_hist[i], hist_bytes);
-        if (e == hipSuccess) e = zero_device(h->d_hist[i], hist_bytes);
-    }
+    if (e == hipSuccess) e = h->hist.alloc(h->Q, static_cast<size_t>(elem));
     if (e != hipSuccess) {
         free_resample(h);
         return fail(COMMS_ERR_DEVICE, "resample alloc: %s", hipGetErrorString(e));
@@ -381,8 +369,8 @@ comms_status_t comms_resample_run_dev(comms_resample_t* h, const void* d_in, siz
     const unsigned grid = tiles < h->max_grid ? static_cast<unsigned>(tiles) : h->max_grid;
     RsArgs a{};
     a.in = d_in;
-    a.hist = h->d_hist[h->cur];
-    a.new_hist = h->d_hist[h->cur ^ 1];
+    a.hist = h->hist.cur();
+    a.new_hist = h->hist.next();
     a.out = d_out;
     a.taps = h->d_tab;
     a.n = n;
@@ -409,7 +397,7 @@ comms_status_t comms_resample_run_dev(comms_resample_t* h, const void* d_in, siz
         st = h->tab_lds ? launch_resample<float2, true>(a, grid, h->WG, h->lds, s) : launch_resample<float2, false>(a, grid, h->WG, h->lds, s);
     h->toc(s);
     COMMS_TRY(st);
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 
@@ -449,9 +437,7 @@ comms_status_t comms_resample_get_state(comms_resample_t* h, void* state, size_t
         }
         return COMMS_OK;
     }
-    std::vector<char> ring(h->Q * E);
-    COMMS_HIP_TRY(hipMemcpy(ring.data(), h->d_hist[h->cur], ring.size(), hipMemcpyDeviceToHost));
-    for (size_t q = 0; q < n_state; ++q) std::memcpy(static_cast<char*>(state) + q * E, ring.data() + (h->Q - 1 - q) * E, E);
+    COMMS_HIP_TRY(h->hist.download(state, n_state));
     return COMMS_OK;
 }
 
@@ -468,10 +454,7 @@ comms_status_t comms_resample_set_state(comms_resample_t* h, const void* state, 
             cs[h->up - 1 + h->up * q] = E == 8 ? static_cast<const comms_c32*>(state)[q] : comms_c32{static_cast<const float*>(state)[q], 0.0f};
         return comms_fir_set_state(h->fir, cs.data(), cs.size());
     }
-    if (!n_state) return COMMS_OK;
-    std::vector<char> ring(h->Q * E);
-    for (size_t q = 0; q < n_state; ++q) std::memcpy(ring.data() + (h->Q - 1 - q) * E, static_cast<const char*>(state) + q * E, E);
-    COMMS_HIP_TRY(hipMemcpy(h->d_hist[h->cur], ring.data(), ring.size(), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(h->hist.upload(state, n_state));
     return COMMS_OK;
 }
 

@@ -158,8 +158,7 @@ struct comms_rfir : Handle {
     int OUT = 1, WG = 256, MP = 8, stride = 0;
     size_t lds = 0;
     float* d_tab = nullptr;
-    float* d_hist[2] = {nullptr, nullptr};  // last n_eff samples, time order, ping-pong
-    int cur = 0;
+    History hist;      // last n_eff samples
     // the series: the complex FIR node carries the state; two Complex<f32> scratch streams
     comms_fir_t* fir = nullptr;
     Scratch sa, sb;
@@ -196,18 +195,11 @@ int plan_stride(int R, int len) {
     return best;
 }
 
-void ring_from_state(std::vector<float>& ring, const float* state, size_t n_state) {
-    // device history is time-ordered (oldest first); the reference's state is newest first
-    const size_t hl = ring.size();
-    for (size_t k = 0; k < hl && k < n_state; ++k) ring[hl - 1 - k] = state[k];
-}
-
 void free_rfir(comms_rfir* h) {
     (void)use_device(h->device);
     if (h->fir) (void)comms_fir_destroy(h->fir);
     if (h->d_tab) (void)hipFree(h->d_tab);
-    if (h->d_hist[0]) (void)hipFree(h->d_hist[0]);
-    if (h->d_hist[1]) (void)hipFree(h->d_hist[1]);
+    h->hist.release();
     h->sa.release();
     h->sb.release();
     h->fini();
@@ -260,13 +252,8 @@ comms_status_t comms_rfir_create(const float* taps, size_t n_taps, const float* 
     size_t n_eff = n_taps;
     if (state && n_state < n_eff) n_eff = n_state;  // zip(taps, state), fir.rs:53
     COMMS_ARG(n_eff <= (1u << 20), "too many taps (%zu)", n_eff);
-    comms_rfir* h = new (std::nothrow) comms_rfir;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    comms_rfir* h = nullptr;
+    COMMS_TRY(make_handle(device, &h));
     h->n_eff = static_cast<int>(n_eff);
     h->rate = rate < 1 ? 1 : static_cast<int>(rate);
     h->series = h->n_eff > RF_MAX_TAPS || h->rate > RF_MAX_RATE;
@@ -274,7 +261,7 @@ comms_status_t comms_rfir_create(const float* taps, size_t n_taps, const float* 
         std::vector<comms_c32> ct(n_eff), cs(state ? n_eff : 0);
         for (size_t k = 0; k < n_eff; ++k) ct[k] = comms_c32{taps[k], 0.0f};
         for (size_t k = 0; k < cs.size(); ++k) cs[k] = comms_c32{state[k], 0.0f};
-        st = comms_fir_create(ct.data(), n_eff, state ? cs.data() : nullptr, cs.size(), device, &h->fir);
+        const comms_status_t st = comms_fir_create(ct.data(), n_eff, state ? cs.data() : nullptr, cs.size(), device, &h->fir);
         if (st != COMMS_OK) {
             free_rfir(h);
             return st;
@@ -297,15 +284,11 @@ comms_status_t comms_rfir_create(const float* taps, size_t n_taps, const float* 
             const long long k = static_cast<long long>(R) * m - r;
             if (k >= 0 && k < N) tab[static_cast<size_t>(r) * h->MP + m] = taps[k];
         }
-    std::vector<float> ring(n_eff, 0.0f);
-    if (state) ring_from_state(ring, state, n_state);
     hipError_t e = h->lds <= 64 * 1024 ? hipSuccess : hipErrorInvalidValue;
     if (e == hipSuccess) e = hipMalloc(&h->d_tab, tab.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(&h->d_hist[i], n_eff * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(h->d_hist[i], ring.data(), n_eff * sizeof(float), hipMemcpyHostToDevice);
-    }
+    if (e == hipSuccess) e = h->hist.alloc(n_eff, sizeof(float));
+    if (e == hipSuccess && state) e = h->hist.upload(state, n_state);
     if (e != hipSuccess) {
         free_rfir(h);
         return fail(COMMS_ERR_DEVICE, "real FIR alloc: %s", hipGetErrorString(e));
@@ -328,8 +311,8 @@ comms_status_t comms_rfir_run_dev(comms_rfir_t* h, const float* d_in, size_t n, 
     if (h->series) return run_series(h, d_in, n, d_out, s);
     RfArgs a{};
     a.in = d_in;
-    a.hist = h->d_hist[h->cur];
-    a.new_hist = h->d_hist[h->cur ^ 1];
+    a.hist = h->hist.cur<float>();
+    a.new_hist = h->hist.next<float>();
     a.out = d_out;
     a.taps = h->d_tab;
     a.n = n;
@@ -352,7 +335,7 @@ comms_status_t comms_rfir_run_dev(comms_rfir_t* h, const float* d_in, size_t n, 
     }
     h->toc(s);
     COMMS_TRY(st);
-    h->cur ^= 1;
+    h->hist.flip();
     return COMMS_OK;
 }
 
@@ -374,15 +357,14 @@ comms_status_t comms_rfir_get_state(comms_rfir_t* h, float* state, size_t n_stat
     COMMS_ARG(n_state <= static_cast<size_t>(h->n_eff), "n_state %zu exceeds the %d effective taps", n_state, h->n_eff);
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());  // the history is advanced by the launches, on whatever stream they ran
+    if (!n_state) return COMMS_OK;  // (an empty read: the series' inner getter takes no empty buffer)
     if (h->series) {
         std::vector<comms_c32> cs(n_state);
         COMMS_TRY(comms_fir_get_state(h->fir, cs.data(), n_state));
         for (size_t k = 0; k < n_state; ++k) state[k] = cs[k].re;
         return COMMS_OK;
     }
-    std::vector<float> ring(h->n_eff);
-    COMMS_HIP_TRY(hipMemcpy(ring.data(), h->d_hist[h->cur], ring.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_state; ++k) state[k] = ring[h->n_eff - 1 - k];
+    COMMS_HIP_TRY(h->hist.download(state, n_state));
     return COMMS_OK;
 }
 
@@ -396,9 +378,7 @@ comms_status_t comms_rfir_set_state(comms_rfir_t* h, const float* state, size_t 
         for (size_t k = 0; k < n_state; ++k) cs[k] = comms_c32{state[k], 0.0f};
         return comms_fir_set_state(h->fir, cs.data(), n_state);
     }
-    std::vector<float> ring(h->n_eff, 0.0f);
-    ring_from_state(ring, state, n_state);
-    COMMS_HIP_TRY(hipMemcpy(h->d_hist[h->cur], ring.data(), ring.size() * sizeof(float), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(h->hist.upload(state, n_state));
     return COMMS_OK;
 }
 

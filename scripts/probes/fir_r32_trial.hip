@@ -285,9 +285,9 @@ comms_status_t r32_launch(comms_fir* h, hipStream_t s, In in, float2* o, size_t 
     const cf* tw = reinterpret_cast<const cf*>(h->d_r32);
     if (ea)
         hipExtLaunchKernelGGL((fir_os1024_r32_kernel<HR, In>), grid, dim3(64 * R32_WPB), static_cast<uint32_t>(R32_LDS_BYTES), s, ea, eb, 0u, in,
-                              h->d_hist[h->cur], h->n_eff, o, n, tw, tw + 1024, nh, chunk_log2, ks);
+                              h->hist.cur<float2>(), h->n_eff, o, n, tw, tw + 1024, nh, chunk_log2, ks);
     else
-        fir_os1024_r32_kernel<HR, In><<<grid, dim3(64 * R32_WPB), R32_LDS_BYTES, s>>>(in, h->d_hist[h->cur], h->n_eff, o, n, tw, tw + 1024, nh,
+        fir_os1024_r32_kernel<HR, In><<<grid, dim3(64 * R32_WPB), R32_LDS_BYTES, s>>>(in, h->hist.cur<float2>(), h->n_eff, o, n, tw, tw + 1024, nh,
                                                                              chunk_log2, ks);
     return launch_ok("fir_os1024_r32_kernel");
 }
@@ -307,7 +307,7 @@ comms_status_t r32_launch_hr(int hr, comms_fir* h, hipStream_t s, In in, float2*
 
 namespace comms {
 
-// The launch fir.hip makes in place of fir_os1024_dyn_kernel (same arguments; the caller has entered the stream and flips h->cur)
+// The launch fir.hip makes in place of fir_os1024_dyn_kernel (same arguments; the caller has entered the stream and flips h->hist)
 comms_status_t fir_os1024_r32_run(comms_fir* h, hipStream_t s, const void* d_in, float2* o, size_t n, float2* nh, int hr,
                                   unsigned chunk_log2, hipEvent_t ea, hipEvent_t eb, KStamp ks) {
     COMMS_TRY(r32_prepare(h));
