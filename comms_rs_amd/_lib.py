@@ -206,6 +206,21 @@ _PROTOS = {
     "comms_channelizer_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_channelizer_set_timer": [_vp, _vp],
     "comms_channelizer_destroy": [_vp],
+    "comms_symsync_create": [_vp, _sz, _sz, _sz, _i32, _pp],
+    "comms_symsync_out_len": [_sz, _sz, _psz],
+    "comms_symsync_state_len": [_sz, _sz, _psz],
+    "comms_symsync_set_timing": [_vp, _f64],
+    "comms_symsync_get_timing": [_vp, C.POINTER(_u32)],
+    "comms_symsync_set_rotation": [_vp, _f64, _f64],
+    "comms_symsync_get_phase": [_vp, C.POINTER(_f64)],
+    "comms_symsync_set_output_format": [_vp, _i32, _i32, _vp],
+    "comms_symsync_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_symsync_run": [_vp, _vp, _sz, _vp],
+    "comms_symsync_get_state": [_vp, _vp, _sz],
+    "comms_symsync_set_state": [_vp, _vp, _sz],
+    "comms_symsync_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_symsync_set_timer": [_vp, _vp],
+    "comms_symsync_destroy": [_vp],
     "comms_bpsk_byte_mod": [_vp, _sz, _vp, _i32],
     "comms_qpsk_byte_mod": [_vp, _sz, _vp, _i32],
     "comms_bpsk_bit_mod": [_vp, _sz, _vp, _i32],

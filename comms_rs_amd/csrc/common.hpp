@@ -663,6 +663,34 @@ inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     return pa < pb + nb && pb < pa + na;
 }
 
+// Stride (in elements, >= len) of R phase arrays that a staging row scatters over: sample s goes to [s mod R][s div R].
+// The LDS serves a row `lanes` lanes at a time over as many element-wide banks (32 for a ds_write_b32, 16 for a
+// ds_write_b64); a group holds consecutive samples, i.e. up to R phases x ~lanes / R consecutive elements, at banks
+// (phase * stride + element) mod lanes.  Two lanes on a bank cost nothing (the instruction takes its cycles anyway), more
+// do: count the lanes beyond two per bank over every alignment of the group and take the residue with the fewest.
+inline int plan_stride(int R, int len, int lanes = 32) {
+    int best = len, best_cost = -1;
+    for (int c = 0; c < lanes; ++c) {
+        const int stride = len + c;
+        int cost = 0;
+        for (int s0 = 0; s0 < R * lanes; s0 += lanes) {  // every phase alignment of a group (period R groups)
+            int banks[32] = {0};
+            for (int l = 0; l < lanes; ++l) {
+                const int s = s0 + l;
+                ++banks[((s % R) * stride + s / R) & (lanes - 1)];
+            }
+            int worst = 0;
+            for (int b = 0; b < lanes; ++b) worst = banks[b] > worst ? banks[b] : worst;
+            cost += worst > 2 ? worst - 2 : 0;
+        }
+        if (best_cost < 0 || cost < best_cost) {
+            best_cost = cost;
+            best = stride;
+        }
+    }
+    return best;
+}
+
 constexpr int kNumCU = 256;  // MI355X: 8 XCD x 32 CU
 // Grid cap of a persistent kernel that uses `lds` bytes per workgroup: the workgroups the chip holds at once, at most
 // eight per CU and as many as fit the CU's 160 KiB of LDS (a kernel below 1 KiB counts as 1 KiB)
@@ -686,6 +714,16 @@ inline void mix_host_rotor(uint64_t turns, double& c, double& s) {
     double ang = static_cast<double>(turns >> 11) * (kMixT * 0x1.0p-53);
     c = cos(ang);
     s = sin(ang);
+}
+// The mixer's device arithmetic (pointwise.hip's kernels, the symbol synchroniser's store stage): the rotor of a phase in
+// turns, and Mixer::mix of one sample -- (xr + i xi) * (c + i s) in num-complex's form, f64, then `as f32`
+__device__ inline void mix_rotor_at(uint64_t turns, double& c, double& s) {
+    double ang = static_cast<double>(turns >> 11) * (kMixT * 0x1.0p-53);
+    sincos(ang, &s, &c);
+}
+__device__ inline float2 mix_one(float2 x, double c, double s) {
+    double xr = static_cast<double>(x.x), xi = static_cast<double>(x.y);
+    return make_float2(static_cast<float>(xr * c - xi * s), static_cast<float>(xr * s + xi * c));
 }
 // Mixer::new (src/mixer.rs:43-51): dphase wrapped into [0, 2pi)
 inline double mix_wrap_dphase(double dphase) {

@@ -18,17 +18,9 @@ namespace comms {
 // in closed form: turns(n) = turns0 + n*frac (mod 2^64).  A thread evaluates
 // its first rotor with one f64 sincos and then steps it by a constant rotor
 // (f64 complex multiply) per grid sweep.
-constexpr double kT = 2.0 * 3.14159265358979323846264338327950288;
+// (mix_rotor_at and mix_one, the rotor of a phase and one sample's product, are in common.hpp: symsync.hip rotates with them too)
+constexpr double kT = kMixT;
 
-__device__ inline void rotor_at(uint64_t turns, double& c, double& s) {
-    double ang = static_cast<double>(turns >> 11) * (kT * 0x1.0p-53);
-    sincos(ang, &s, &c);
-}
-__device__ inline float2 mix1(float2 x, double c, double s) {
-    double xr = static_cast<double>(x.x), xi = static_cast<double>(x.y);
-    // (xr + i xi) * (c + i s), num-complex form, f64, then `as f32`
-    return make_float2(static_cast<float>(xr * c - xi * s), static_cast<float>(xr * s + xi * c));
-}
 __device__ inline void rot_step(double& c, double& s, double sc, double ss) {
     double nc = c * sc - s * ss;
     double ns = c * ss + s * sc;
@@ -47,18 +39,18 @@ __global__ __launch_bounds__(256) void mixer_kernel(const float2* __restrict__ i
     const size_t ngroups = n / VEC;
     if (gid < ngroups) {
         double c0, s0;
-        rotor_at(turns0 + static_cast<uint64_t>(gid * VEC) * frac, c0, s0);
+        mix_rotor_at(turns0 + static_cast<uint64_t>(gid * VEC) * frac, c0, s0);
         double c1 = c0, s1 = s0;
         if (VEC == 2) rot_step(c1, s1, d_c, d_s);
         for (size_t g = gid; g < ngroups; g += nthreads) {
             if (VEC == 2) {
                 float4 x = reinterpret_cast<const float4*>(in)[g];
-                float2 a = mix1(make_float2(x.x, x.y), c0, s0);
-                float2 b = mix1(make_float2(x.z, x.w), c1, s1);
+                float2 a = mix_one(make_float2(x.x, x.y), c0, s0);
+                float2 b = mix_one(make_float2(x.z, x.w), c1, s1);
                 reinterpret_cast<float4*>(out)[g] = make_float4(a.x, a.y, b.x, b.y);
                 rot_step(c1, s1, sweep_c, sweep_s);
             } else {
-                out[g] = mix1(in[g], c0, s0);
+                out[g] = mix_one(in[g], c0, s0);
             }
             rot_step(c0, s0, sweep_c, sweep_s);
         }
@@ -66,8 +58,8 @@ __global__ __launch_bounds__(256) void mixer_kernel(const float2* __restrict__ i
     // odd tail (VEC == 2 only): one thread, exact evaluation
     if (VEC == 2 && gid == 0 && (n & 1)) {
         double c, s;
-        rotor_at(turns0 + static_cast<uint64_t>(n - 1) * frac, c, s);
-        out[n - 1] = mix1(in[n - 1], c, s);
+        mix_rotor_at(turns0 + static_cast<uint64_t>(n - 1) * frac, c, s);
+        out[n - 1] = mix_one(in[n - 1], c, s);
     }
 }
 
@@ -82,7 +74,7 @@ __global__ __launch_bounds__(256) void mixer_f64_kernel(const double2* __restric
     const size_t nthreads = static_cast<size_t>(gridDim.x) * blockDim.x;
     for (size_t g = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; g < n; g += nthreads) {
         double c, s;
-        rotor_at(turns0 + static_cast<uint64_t>(g) * frac, c, s);
+        mix_rotor_at(turns0 + static_cast<uint64_t>(g) * frac, c, s);
         const double2 x = in[g];
         out[g] = make_double2(x.x * c - x.y * s, x.x * s + x.y * c);
     }
@@ -98,9 +90,9 @@ __global__ __launch_bounds__(256) void mix_decimate_kernel(const float2* __restr
     const size_t gid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (gid >= n_out) return;
     double c0, s0;
-    rotor_at(turns0 + static_cast<uint64_t>(gid * rate) * frac, c0, s0);
+    mix_rotor_at(turns0 + static_cast<uint64_t>(gid * rate) * frac, c0, s0);
     for (size_t j = gid; j < n_out; j += nthreads) {
-        out[j] = mix1(in[j * rate], c0, s0);
+        out[j] = mix_one(in[j * rate], c0, s0);
         rot_step(c0, s0, sweep_c, sweep_s);
     }
 }

@@ -168,33 +168,7 @@ namespace {
 
 constexpr int RF_MAX_TAPS = 257, RF_MAX_RATE = 64;
 
-// Stride of the phase arrays, >= len.  A staging row is a ds_write_b32 served 32 lanes at a time over 32 banks; the 32
-// lanes hold consecutive samples, i.e. up to R phases x ~32 / R consecutive elements, at banks (phase * stride +
-// element) mod 32.  Two lanes on a bank cost nothing (the instruction takes its four cycles anyway), more do: count the
-// lanes beyond two per bank over every alignment of the group and take the residue with the fewest.
-int plan_stride(int R, int len) {
-    int best = len, best_cost = -1;
-    for (int c = 0; c < 32; ++c) {
-        const int stride = len + c;
-        int cost = 0;
-        for (int s0 = 0; s0 < R * 32; s0 += 32) {  // every phase alignment of a 32-lane group (period R groups)
-            int banks[32] = {0};
-            for (int l = 0; l < 32; ++l) {
-                const int s = s0 + l;
-                ++banks[((s % R) * stride + s / R) & 31];
-            }
-            int worst = 0;
-            for (int b = 0; b < 32; ++b) worst = banks[b] > worst ? banks[b] : worst;
-            cost += worst > 2 ? worst - 2 : 0;
-        }
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = stride;
-        }
-    }
-    return best;
-}
-
+// (the stride of the phase arrays: plan_stride, common.hpp)
 void free_rfir(comms_rfir* h) {
     (void)use_device(h->device);
     if (h->fir) (void)comms_fir_destroy(h->fir);

@@ -727,6 +727,90 @@ private:
     size_t channels_, down_;
 };
 
+// Symbol synchroniser as ONE node (comms_symsync_*; an additional node): matched filter with a fractional delay, symbol-rate
+// sampler, rotation and -- with set_output_bits -- hard decision, the results of UpsampleNode(phases) -> BatchFirNode(Complex(
+// taps, 0)) -> skip mu -> DecimateNode(phases sps) -> MixerNode.  Messages are multiples of sps samples and give n / sps
+// symbols (Complex32), or their packed bits (uint8_t, SymbolSyncNode<uint8_t>).
+// A second channel, `update`, carries what a block-rate loop (TimingEstimatorNode, a phase estimator) decides between
+// blocks: every update queued when a block arrives is applied before it, in order, and the node never waits for one -- the
+// channel may stay unconnected.  A NaN field leaves that setting as it is.  dphase is fixed at construction: an update
+// carries no increment, and a phase update is applied with the constructor's.
+struct SymbolSyncUpdate {
+    double tau;    // comms_symsync_set_timing: the sampling instant in input samples
+    double phase;  // comms_symsync_set_rotation(dphase, phase): rotor phase of the next output
+};
+namespace detail {
+class SymbolSyncCore {
+public:
+    SymbolSyncCore(const std::vector<float>& taps, size_t phases, size_t sps, double dphase, int bits_per_sym, int device, const char* who)
+        : sps_(sps < 1 ? 1 : sps), dphase_(dphase), bits_(bits_per_sym) {
+        throw_on(comms_symsync_create(taps.data(), taps.size(), phases, sps, device, &h_), who);
+        comms_status_t st = comms_symsync_set_rotation(h_, dphase, 0.0);
+        if (st == COMMS_OK && bits_) st = comms_symsync_set_output_format(h_, COMMS_SYM_BITS, bits_, nullptr);
+        if (st != COMMS_OK) {
+            comms_symsync_destroy(h_);
+            throw_on(st, who);
+        }
+    }
+    SymbolSyncCore(SymbolSyncCore&& o) noexcept : h_(o.h_), sps_(o.sps_), dphase_(o.dphase_), bits_(o.bits_) { o.h_ = nullptr; }
+    ~SymbolSyncCore() { comms_symsync_destroy(h_); }
+    comms_status_t drain(NodeReceiver<SymbolSyncUpdate>& update) {
+        while (update) {
+            const std::optional<SymbolSyncUpdate> u = update->try_recv();
+            if (!u) break;
+            comms_status_t st = COMMS_OK;
+            if (!std::isnan(u->tau)) st = comms_symsync_set_timing(h_, u->tau);
+            if (st == COMMS_OK && !std::isnan(u->phase)) st = comms_symsync_set_rotation(h_, dphase_, u->phase);
+            if (st != COMMS_OK) return st;
+        }
+        return COMMS_OK;
+    }
+    // elements of a message's output: symbols, or bytes of packed bits
+    size_t out_len(size_t n) const {
+        const size_t n_sym = n / sps_;
+        return bits_ ? (n_sym * static_cast<size_t>(bits_) + 7) / 8 : n_sym;
+    }
+    comms_symsync_t* h() const { return h_; }
+
+private:
+    comms_symsync_t* h_ = nullptr;
+    size_t sps_;
+    double dphase_;
+    int bits_;
+};
+}  // namespace detail
+
+template <class Out = Complex32>
+class SymbolSyncNode : public DeriveNode<SymbolSyncNode<Out>> {
+    static_assert(std::is_same_v<Out, Complex32> || std::is_same_v<Out, uint8_t>, "symbols (Complex32) or packed bits (uint8_t)");
+
+public:
+    NodeReceiver<std::vector<Complex32>> input;
+    NodeReceiver<SymbolSyncUpdate> update;  // optional; drained before each block
+    NodeSender<std::vector<Out>> output;
+    SymbolSyncNode(const std::vector<float>& taps, size_t phases, size_t sps, double dphase = 0.0, int bits_per_sym = 2, int device = 0)
+        : core_(taps, phases, sps, dphase, std::is_same_v<Out, uint8_t> ? bits_per_sym : 0, device, "SymbolSyncNode::new") {}
+    SymbolSyncNode(SymbolSyncNode&&) noexcept = default;
+    Result<std::vector<Out>> run(const std::vector<Complex32>& in) {
+        comms_status_t st = core_.drain(update);
+        if (st != COMMS_OK) return to_node_error(st);
+        std::vector<Out> out(core_.out_len(in.size()));
+        st = comms_symsync_run(core_.h(), reinterpret_cast<const comms_c32*>(in.data()), in.size(), out.data());
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    std::string kernel(size_t n) const {  // "symsync_kernel<..> ..."
+        char name[240] = {0};
+        comms_symsync_get_kernel(core_.h(), n, name, sizeof name);
+        return name;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    detail::SymbolSyncCore core_;
+};
+
 // ---------------------------------------------------------------- mixer
 template <class D, class T>
 class MixerNodeOf : public DeriveNode<D> {
@@ -1449,6 +1533,38 @@ public:
 private:
     comms_channelizer_t* h_ = nullptr;
     size_t channels_, down_;
+    int device_;
+    DevStream st_;
+};
+
+// The symbol synchroniser on device-resident messages (`update` as SymbolSyncNode's: host values, drained before each block)
+template <class Out = Complex32>
+class SymbolSyncNodeDev : public DeriveNode<SymbolSyncNodeDev<Out>> {
+    static_assert(std::is_same_v<Out, Complex32> || std::is_same_v<Out, uint8_t>, "symbols (Complex32) or packed bits (uint8_t)");
+
+public:
+    NodeReceiver<DeviceBuf<Complex32>> input;
+    NodeReceiver<SymbolSyncUpdate> update;
+    NodeSender<DeviceBuf<Out>> output;
+    SymbolSyncNodeDev(const std::vector<float>& taps, size_t phases, size_t sps, double dphase = 0.0, int bits_per_sym = 2, int device = 0)
+        : core_(taps, phases, sps, dphase, std::is_same_v<Out, uint8_t> ? bits_per_sym : 0, device, "SymbolSyncNodeDev::new"),
+          device_(device), st_(device) {}
+    SymbolSyncNodeDev(SymbolSyncNodeDev&&) noexcept = default;
+    Result<DeviceBuf<Out>> run(const DeviceBuf<Complex32>& in) {
+        comms_status_t st = core_.drain(update);
+        if (st != COMMS_OK) return to_node_error(st);
+        DeviceBuf<Out> out(core_.out_len(in.size()), device_);
+        st = st_.run(in, out, [&](void* s) {
+            return comms_symsync_run_dev(core_.h(), reinterpret_cast<const comms_c32*>(in.ptr()), in.size(), out.ptr(), s);
+        });
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    detail::SymbolSyncCore core_;
     int device_;
     DevStream st_;
 };

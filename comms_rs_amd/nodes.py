@@ -899,6 +899,110 @@ class ChannelizerNode(_Handle):
         return self
 
 
+class SymbolSyncNode(_Handle):
+    """Symbol synchroniser (comms_symsync_*): matched filter with a fractional delay, symbol-rate sampler, rotation and
+    (optionally) hard decision over a Complex<f32> stream as one node -- UpsampleNode(phases) -> BatchFirNode(Complex(taps,
+    0)) -> skip mu -> DecimateNode(phases * sps) -> MixerNode -> decision, computing only the kept outputs.  taps are real,
+    designed at `phases` times the input rate (rrc_taps(N, phases * sps, beta)); batches are multiples of sps samples and
+    give n / sps outputs; the history -- (len(taps) - 1) // phases RAW input samples -- does not depend on the timing."""
+    _destroy = "comms_symsync_destroy"
+    _out_bits = 0
+
+    def __init__(self, taps, phases, sps, device=0):
+        super().__init__()
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self.phases, self.sps, self.n_taps = max(int(phases), 1), max(int(sps), 1), taps.size
+        check(lib().comms_symsync_create(_ptr(taps), taps.size, int(phases), int(sps), device, C.byref(self._h)))
+
+    def set_timing(self, tau):
+        """The sampling instant in input samples (positive = later), rounded to 1 / phases and reduced mod sps."""
+        check(lib().comms_symsync_set_timing(self._h, float(tau)))
+
+    def get_timing(self):
+        """mu, in steps of 1 / phases input samples: 0 <= mu < sps * phases."""
+        mu = C.c_uint32()
+        check(lib().comms_symsync_get_timing(self._h, C.byref(mu)))
+        return mu.value
+
+    timing = property(get_timing, set_timing)
+
+    def set_rotation(self, dphase, phase=0.0):
+        """out[k] = y[k] * exp(i (phase + k dphase)), the mixer's convention; the phase carries across calls."""
+        check(lib().comms_symsync_set_rotation(self._h, float(dphase), float(phase)))
+        self._dphase = float(dphase)
+
+    _dphase = 0.0
+
+    def get_rotation(self):
+        """(dphase as given, phase of the next output in [0, 2 pi))."""
+        ph = C.c_double()
+        check(lib().comms_symsync_get_phase(self._h, C.byref(ph)))
+        return self._dphase, ph.value
+
+    rotation = property(get_rotation, lambda self, v: self.set_rotation(*v))
+
+    def set_output(self, bits_per_sym=None, constellation=None):
+        """bits_per_sym 1 or 2: run() returns hard decisions as packed bits (np.uint8, LSB first, ceil(n / sps *
+        bits_per_sym / 8) bytes), nearest of the 2**bits_per_sym points of `constellation` (None = digital.rs's tables; see
+        comms_sym_to_bits for the rule); None restores Complex<f32>.  State, phase and timing carry across a switch."""
+        if bits_per_sym is None:
+            check(lib().comms_symsync_set_output_format(self._h, _lib.SYM_C32, 0, None))
+            self._out_bits = 0
+            return self
+        cons = _constellation(constellation, bits_per_sym)
+        check(lib().comms_symsync_set_output_format(self._h, _lib.SYM_BITS, int(bits_per_sym), None if cons is None else _ptr(cons)))
+        self._out_bits = int(bits_per_sym)
+        return self
+
+    def out_len(self, n):
+        """Symbols of a call of n samples."""
+        m = C.c_size_t()
+        check(lib().comms_symsync_out_len(n, self.sps, C.byref(m)))
+        return m.value
+
+    def out_bytes(self, n):
+        n_sym = self.out_len(n)
+        return (n_sym * self._out_bits + 7) // 8 if self._out_bits else n_sym * 8
+
+    def state_len(self):
+        m = C.c_size_t()
+        check(lib().comms_symsync_state_len(self.n_taps, self.phases, C.byref(m)))
+        return m.value
+
+    def kernel(self, n):
+        """What a batch of n samples is run by: "symsync_kernel<..> tile=.. wg=.. lds=.. tiles=.. grid=.. max_grid=.."."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_symsync_get_kernel(self._h, n, buf, 240))
+        return buf.value.decode()
+
+    def run(self, x):
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        out = np.empty(self.out_bytes(x.size), np.uint8) if self._out_bits else np.empty(self.out_len(x.size), np.complex64)
+        check(lib().comms_symsync_run(self._h, _ptr(x), x.size, _ptr(out)))
+        return out
+
+    def run_dev(self, in_ptr, n, out_ptr, stream=0):
+        check(lib().comms_symsync_run_dev(self._h, in_ptr, n, out_ptr, stream))
+
+    def get_state(self, n_state=None):
+        """The last n_state input samples (default: all state_len() of them), newest first."""
+        n_state = self.state_len() if n_state is None else int(n_state)
+        st = np.empty(n_state, np.complex64)
+        check(lib().comms_symsync_get_state(self._h, _ptr(st), n_state))
+        return st
+
+    def set_state(self, state):
+        state = np.ascontiguousarray(state, dtype=np.complex64)
+        check(lib().comms_symsync_set_state(self._h, _ptr(state), state.size))
+
+    state = property(get_state, set_state)
+
+    def set_timer(self, timer):
+        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch."""
+        check(lib().comms_symsync_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
 def _taps(fn, n_taps, *args):
     out = np.empty(int(n_taps), np.complex64)
     check(fn(int(n_taps), *args, _ptr(out)))
@@ -1264,7 +1368,8 @@ class KernelTimer:
                 "comms_chain_destroy": "comms_chain_set_timer", "comms_pulse_destroy": "comms_pulse_set_timer",
                 "comms_rfir_destroy": "comms_rfir_set_timer", "comms_noise_destroy": "comms_noise_set_timer",
                 "comms_resample_destroy": "comms_resample_set_timer",
-                "comms_channelizer_destroy": "comms_channelizer_set_timer"}[node._destroy]
+                "comms_channelizer_destroy": "comms_channelizer_set_timer",
+                "comms_symsync_destroy": "comms_symsync_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

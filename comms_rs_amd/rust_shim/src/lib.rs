@@ -623,6 +623,131 @@ impl ChannelizerNode {
     }
 }
 
+/// Symbol synchroniser (an additional node): what the reference could only wire as `UpsampleNode(phases) ->
+/// BatchFirNode(Complex(taps, 0)) -> [skip mu] -> DecimateNode(phases * sps) -> MixerNode`, as one node that computes only
+/// the kept outputs.  Batches are multiples of `sps` samples and give `n / sps` symbols; the state is
+/// `(taps.len() - 1) / phases` raw input samples, whatever the timing.  `set_timing` / `set_rotation` are the block-rate
+/// loop's inputs (TimingEstimatorNode, a phase estimator); see include/comms_hip.h for what to feed them.  Packed bits out:
+/// `SymbolSyncBitsNode`.  As the shim's other nodes it exposes no kernel name or timer hook (diagnostics stay in C / Python).
+#[derive(Node)]
+#[pass_by_ref]
+pub struct SymbolSyncNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    h: *mut comms_symsync_t,
+    sps: usize,
+    pub output: NodeSender<Vec<Complex<f32>>>,
+}
+unsafe impl Send for SymbolSyncNode {}
+impl Drop for SymbolSyncNode {
+    fn drop(&mut self) { unsafe { comms_symsync_destroy(self.h); } }
+}
+impl SymbolSyncNode {
+    pub fn new(taps: Vec<f32>, phases: usize, sps: usize) -> Self {
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_symsync_create(taps.as_ptr(), taps.len(), phases, sps, 0, &mut h) };
+        assert_eq!(st, COMMS_OK, "comms_symsync_create failed");
+        SymbolSyncNode { input: Default::default(), h, sps, output: Default::default() }
+    }
+    pub fn run(&mut self, samples: &[Complex<f32>]) -> Result<Vec<Complex<f32>>, NodeError> {
+        let mut m = 0usize;
+        let st = unsafe { comms_symsync_out_len(samples.len(), self.sps, &mut m) };
+        if st != COMMS_OK { return Err(to_err(st)); }
+        let mut out = vec![Complex::<f32>::zero(); m];
+        let st = unsafe { comms_symsync_run(self.h, samples.as_ptr(), samples.len(), out.as_mut_ptr() as *mut c_void) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    /// The sampling instant in input samples (positive = later); holds until changed
+    pub fn set_timing(&mut self, tau: f64) -> Result<(), NodeError> {
+        let st = unsafe { comms_symsync_set_timing(self.h, tau) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    /// mu: the timing in steps of `1 / phases` input samples
+    pub fn timing(&self) -> Result<u32, NodeError> {
+        let mut mu = 0u32;
+        let st = unsafe { comms_symsync_get_timing(self.h, &mut mu) };
+        if st == COMMS_OK { Ok(mu) } else { Err(to_err(st)) }
+    }
+    /// `Mixer::new(phase, dphase)` at symbol rate (NOTE the argument order of the C entry, kept here)
+    pub fn set_rotation(&mut self, dphase: f64, phase: f64) -> Result<(), NodeError> {
+        let st = unsafe { comms_symsync_set_rotation(self.h, dphase, phase) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    /// Rotor phase of the next output, in [0, 2 pi)
+    pub fn phase(&self) -> Result<f64, NodeError> {
+        let mut p = 0f64;
+        let st = unsafe { comms_symsync_get_phase(self.h, &mut p) };
+        if st == COMMS_OK { Ok(p) } else { Err(to_err(st)) }
+    }
+    /// The checkpoint hook: the last `n` input samples, newest first
+    pub fn state(&mut self, n: usize) -> Result<Vec<Complex<f32>>, NodeError> {
+        let mut out = vec![Complex::<f32>::zero(); n];
+        let st = unsafe { comms_symsync_get_state(self.h, out.as_mut_ptr(), n) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    /// Exactly `(taps.len() - 1) / phases` samples, newest first
+    pub fn set_state(&mut self, state: &[Complex<f32>]) -> Result<(), NodeError> {
+        let st = unsafe { comms_symsync_set_state(self.h, state.as_ptr(), state.len()) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+}
+
+/// The symbol synchroniser with hard decisions out (`COMMS_SYM_BITS`): `ceil(n / sps * bits_per_sym / 8)` bytes of packed
+/// bits per batch, LSB first, decided against digital.rs's tables (`bits_per_sym` 1: BPSK, 2: QPSK) in the kernel's store
+/// stage.  Timing, rotation and state as `SymbolSyncNode`.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct SymbolSyncBitsNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    h: *mut comms_symsync_t,
+    sps: usize,
+    bits_per_sym: usize,
+    pub output: NodeSender<Vec<u8>>,
+}
+unsafe impl Send for SymbolSyncBitsNode {}
+impl Drop for SymbolSyncBitsNode {
+    fn drop(&mut self) { unsafe { comms_symsync_destroy(self.h); } }
+}
+impl SymbolSyncBitsNode {
+    pub fn new(taps: Vec<f32>, phases: usize, sps: usize, bits_per_sym: usize) -> Self {
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_symsync_create(taps.as_ptr(), taps.len(), phases, sps, 0, &mut h) };
+        assert_eq!(st, COMMS_OK, "comms_symsync_create failed");
+        let st = unsafe { comms_symsync_set_output_format(h, COMMS_SYM_BITS, bits_per_sym as i32, ptr::null()) };
+        assert_eq!(st, COMMS_OK, "comms_symsync_set_output_format failed (bits_per_sym is 1 or 2)");
+        SymbolSyncBitsNode { input: Default::default(), h, sps, bits_per_sym, output: Default::default() }
+    }
+    pub fn run(&mut self, samples: &[Complex<f32>]) -> Result<Vec<u8>, NodeError> {
+        let mut m = 0usize;
+        let st = unsafe { comms_symsync_out_len(samples.len(), self.sps, &mut m) };
+        if st != COMMS_OK { return Err(to_err(st)); }
+        let mut out = vec![0u8; (m * self.bits_per_sym + 7) / 8];
+        let st = unsafe { comms_symsync_run(self.h, samples.as_ptr(), samples.len(), out.as_mut_ptr() as *mut c_void) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    pub fn set_timing(&mut self, tau: f64) -> Result<(), NodeError> {
+        let st = unsafe { comms_symsync_set_timing(self.h, tau) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    pub fn set_rotation(&mut self, dphase: f64, phase: f64) -> Result<(), NodeError> {
+        let st = unsafe { comms_symsync_set_rotation(self.h, dphase, phase) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    pub fn phase(&self) -> Result<f64, NodeError> {
+        let mut p = 0f64;
+        let st = unsafe { comms_symsync_get_phase(self.h, &mut p) };
+        if st == COMMS_OK { Ok(p) } else { Err(to_err(st)) }
+    }
+    pub fn state(&mut self, n: usize) -> Result<Vec<Complex<f32>>, NodeError> {
+        let mut out = vec![Complex::<f32>::zero(); n];
+        let st = unsafe { comms_symsync_get_state(self.h, out.as_mut_ptr(), n) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    pub fn set_state(&mut self, state: &[Complex<f32>]) -> Result<(), NodeError> {
+        let st = unsafe { comms_symsync_set_state(self.h, state.as_ptr(), state.len()) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+}
+
 /// Sample types `UniformNode<T>` is built for: `f32` (values in `[start, end)`) and `u8` over `[0, 2)`, which is what
 /// `random_bit()` returns (rand_node.rs:150-152).
 pub trait UniformSample: Copy + Send + 'static {
