@@ -12,4 +12,5 @@ from .nodes import (BatchFirNode, BatchFirNodeI16, FirNodeI16, PulseNodeI16, Bat
                     gaussian_taps, iq_c32_to_i16, iq_i16_to_c32, iq_u8_to_c32, real_to_c32_dev, c32_re_dev, rc_taps, rect_taps, rrc_taps,
                     synth_iq, synth_iq_dev, PrnsNode, bpsk_byte_mod, qpsk_byte_mod, bpsk_bit_mod, qpsk_bit_mod,
                     sym_to_bits, sym_to_bits_dev, bit_errors, bit_errors_dev, RealFirDecimNode, NoiseSource, ResampleNode, ChannelizerNode,
-                    SymbolSyncNode)
+                    SymbolSyncNode, SyncEstimatorNode, SyncEstimate, psk_phase_estimate_c32, qam_phase_estimate_c32,
+                    psk_phase_estimate_c32_dev, qam_phase_estimate_c32_dev)

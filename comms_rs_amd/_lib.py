@@ -269,6 +269,16 @@ _PROTOS = {
     "comms_timing_push_dev": [_vp, _vp, _sz, C.POINTER(_f64), _vp],
     "comms_timing_destroy": [_vp],
     "comms_qfilt_taps": [_u32, _f64, _u32, _vp],
+    "comms_syncest_create": [_u32, _u32, _f64, _i32, _pp],
+    "comms_syncest_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_syncest_run": [_vp, _vp, _sz, _vp],
+    "comms_syncest_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_syncest_set_timer": [_vp, _vp],
+    "comms_syncest_destroy": [_vp],
+    "comms_psk_phase_estimate_c32": [_vp, _sz, _u32, C.POINTER(_f64), _i32],
+    "comms_qam_phase_estimate_c32": [_vp, _sz, C.POINTER(_f64), _i32],
+    "comms_psk_phase_estimate_c32_dev": [_vp, _sz, _u32, C.POINTER(_f64), _i32, _vp],
+    "comms_qam_phase_estimate_c32_dev": [_vp, _sz, C.POINTER(_f64), _i32, _vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],

@@ -24,6 +24,7 @@
 #pragma once
 
 #include <cmath>
+#include <limits>
 #include <complex>
 #include <cstring>
 #include <optional>
@@ -1109,6 +1110,66 @@ private:
     comms_timing_t* h_ = nullptr;
 };
 
+// Timing and frequency estimates of a Complex<f32> block from one read of it (comms_syncest_*; an additional node):
+// TimingEstimator::push at (n, d, alpha) and frequency_offset_estimate of the widened samples.  Two outputs per block:
+// `output` carries the whole comms_sync_estimate_t, `update` the SymbolSyncUpdate{tau, NaN} that puts a SymbolSyncNode of
+// (n_taps, phases) -- its sps = n -- on the symbol centres: tau = timing + (n_taps - 1) / (2 phases) (mod n); the NaN leaves
+// the synchroniser's phase alone.  `update` plugs straight into SymbolSyncNode::update.
+struct SyncEstimate {
+    comms_sync_estimate_t estimate;
+    SymbolSyncUpdate update;
+    operator comms_sync_estimate_t() const { return estimate; }
+    operator SymbolSyncUpdate() const { return update; }
+};
+namespace detail {
+class SyncEstimatorCore {
+public:
+    SyncEstimatorCore(uint32_t n, uint32_t d, double alpha, size_t n_taps, size_t phases, int device, const char* who)
+        : n_(n), delay_(n_taps ? static_cast<double>(n_taps - 1) / (2.0 * static_cast<double>(phases < 1 ? 1 : phases)) : 0.0) {
+        throw_on(comms_syncest_create(n, d, alpha, device, &h_), who);
+    }
+    SyncEstimatorCore(SyncEstimatorCore&& o) noexcept : h_(o.h_), n_(o.n_), delay_(o.delay_) { o.h_ = nullptr; }
+    ~SyncEstimatorCore() { comms_syncest_destroy(h_); }
+    SyncEstimate message(const comms_sync_estimate_t& e) const {
+        double tau = std::fmod(e.timing + delay_, static_cast<double>(n_));
+        if (tau < 0) tau += static_cast<double>(n_);
+        return SyncEstimate{e, SymbolSyncUpdate{tau, std::numeric_limits<double>::quiet_NaN()}};
+    }
+    comms_syncest_t* h() const { return h_; }
+
+private:
+    comms_syncest_t* h_ = nullptr;
+    uint32_t n_;
+    double delay_;
+};
+}  // namespace detail
+
+class SyncEstimatorNode : public DeriveNode<SyncEstimatorNode> {
+public:
+    NodeReceiver<std::vector<Complex32>> input;
+    NodeSender<comms_sync_estimate_t> output;
+    NodeSender<SymbolSyncUpdate> update;
+    SyncEstimatorNode(uint32_t n, uint32_t d, double alpha, size_t n_taps, size_t phases, int device = 0)
+        : core_(n, d, alpha, n_taps, phases, device, "SyncEstimatorNode::new") {}
+    SyncEstimatorNode(SyncEstimatorNode&&) noexcept = default;
+    Result<SyncEstimate> run(const std::vector<Complex32>& samples) {
+        comms_sync_estimate_t e{};
+        comms_status_t st = comms_syncest_run(core_.h(), reinterpret_cast<const comms_c32*>(samples.data()), samples.size(), &e);
+        if (st != COMMS_OK) return to_node_error(st);
+        return core_.message(e);
+    }
+    std::string kernel(size_t n) const {  // "syncest_kernel ..."
+        char name[240] = {0};
+        comms_syncest_get_kernel(core_.h(), n, name, sizeof name);
+        return name;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output, update); }
+
+private:
+    detail::SyncEstimatorCore core_;
+};
+
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)
@@ -1567,6 +1628,40 @@ private:
     detail::SymbolSyncCore core_;
     int device_;
     DevStream st_;
+};
+
+// The synchronisation estimator on device-resident messages: the estimates themselves are host values (the call
+// synchronises its stream), so the outputs are SyncEstimatorNode's
+class SyncEstimatorNodeDev : public DeriveNode<SyncEstimatorNodeDev> {
+public:
+    NodeReceiver<DeviceBuf<Complex32>> input;
+    NodeSender<comms_sync_estimate_t> output;
+    NodeSender<SymbolSyncUpdate> update;
+    SyncEstimatorNodeDev(uint32_t n, uint32_t d, double alpha, size_t n_taps, size_t phases, int device = 0)
+        : core_(n, d, alpha, n_taps, phases, device, "SyncEstimatorNodeDev::new"), device_(device) {
+        throw_on(comms_stream_create(device, &s_), "comms_stream_create");
+    }
+    SyncEstimatorNodeDev(SyncEstimatorNodeDev&& o) noexcept
+        : input(std::move(o.input)), output(std::move(o.output)), update(std::move(o.update)), core_(std::move(o.core_)),
+          device_(o.device_), s_(o.s_) { o.s_ = nullptr; }
+    ~SyncEstimatorNodeDev() {
+        if (s_) comms_stream_destroy(device_, s_);   // every run ends synchronised
+    }
+    Result<SyncEstimate> run(const DeviceBuf<Complex32>& in) {
+        if (in.device() != device_) return to_node_error(COMMS_ERR_ARG);
+        comms_sync_estimate_t e{};
+        comms_status_t st = comms_buf_wait_ready(in.raw(), s_);
+        if (st == COMMS_OK) st = comms_syncest_run_dev(core_.h(), reinterpret_cast<const comms_c32*>(in.ptr()), in.size(), &e, s_);
+        if (st != COMMS_OK) return to_node_error(st);
+        return core_.message(e);
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output, update); }
+
+private:
+    detail::SyncEstimatorCore core_;
+    int device_;
+    void* s_ = nullptr;
 };
 
 // AWGN channel on device-resident messages: wait_ready(in) -> comms_awgn_run_dev on the node's stream -> record_use(in),

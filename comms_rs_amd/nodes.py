@@ -1298,6 +1298,86 @@ class TimingEstimatorNode(_Handle):
         return out.value
 
 
+class _SyncEstimateStruct(C.Structure):
+    _fields_ = [("timing", C.c_double), ("freq", C.c_double), ("timing_sum", C.c_double * 2), ("freq_sum", C.c_double * 2)]
+
+
+class SyncEstimate:
+    """comms_sync_estimate_t: timing (samples) and freq (rad / sample) of one block, and the complex sums they are the
+    angles of (to add over blocks or shards before taking the angle)."""
+    __slots__ = ("timing", "freq", "timing_sum", "freq_sum")
+
+    def __init__(self, s):
+        self.timing, self.freq = s.timing, s.freq
+        self.timing_sum = complex(s.timing_sum[0], s.timing_sum[1])
+        self.freq_sum = complex(s.freq_sum[0], s.freq_sum[1])
+
+    def __repr__(self):
+        return "SyncEstimate(timing=%r, freq=%r, timing_sum=%r, freq_sum=%r)" % (self.timing, self.freq, self.timing_sum, self.freq_sum)
+
+
+class SyncEstimatorNode(_Handle):
+    """Timing and frequency estimates of a Complex<f32> block from one read of it (comms_syncest_*): TimingEstimator::push
+    at (n, d, alpha) and frequency_offset_estimate of the widened samples, the timing filter in f32.  What to feed
+    SymbolSyncNode (estimator at n = sps): timing = est.timing + (N - 1) / (2 phases), set_rotation(-est.freq * sps,
+    -phase estimate)."""
+    _destroy = "comms_syncest_destroy"
+
+    def __init__(self, n, d, alpha, device=0):
+        super().__init__()
+        check(lib().comms_syncest_create(int(n), int(d), float(alpha), device, C.byref(self._h)))
+
+    def run(self, samples):
+        x = np.ascontiguousarray(samples, dtype=np.complex64)
+        out = _SyncEstimateStruct()
+        check(lib().comms_syncest_run(self._h, _ptr(x), x.size, C.byref(out)))
+        return SyncEstimate(out)
+
+    def run_dev(self, in_ptr, n, stream=0):
+        out = _SyncEstimateStruct()
+        check(lib().comms_syncest_run_dev(self._h, in_ptr, n, C.byref(out), stream))
+        return SyncEstimate(out)
+
+    def kernel(self, n):
+        """What a block of n samples is run by: "syncest_kernel tile=.. wg=.. taps=.. lds=.. tiles=.. grid=.. max_grid=.."."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_syncest_get_kernel(self._h, n, buf, 240))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch."""
+        check(lib().comms_syncest_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
+def psk_phase_estimate_c32(symbols, m, device=0):
+    """phase_estimator.rs:26-33 on Complex<f32> symbols (widened in the kernel's load)."""
+    x = np.ascontiguousarray(symbols, dtype=np.complex64)
+    out = C.c_double()
+    check(lib().comms_psk_phase_estimate_c32(_ptr(x), x.size, int(m), C.byref(out), device))
+    return out.value
+
+
+def qam_phase_estimate_c32(symbols, device=0):
+    """phase_estimator.rs:58-65 on Complex<f32> symbols."""
+    x = np.ascontiguousarray(symbols, dtype=np.complex64)
+    out = C.c_double()
+    check(lib().comms_qam_phase_estimate_c32(_ptr(x), x.size, C.byref(out), device))
+    return out.value
+
+
+def psk_phase_estimate_c32_dev(in_ptr, n, m, device=0, stream=0):
+    out = C.c_double()
+    check(lib().comms_psk_phase_estimate_c32_dev(in_ptr, n, int(m), C.byref(out), device, stream))
+    return out.value
+
+
+def qam_phase_estimate_c32_dev(in_ptr, n, device=0, stream=0):
+    out = C.c_double()
+    check(lib().comms_qam_phase_estimate_c32_dev(in_ptr, n, C.byref(out), device, stream))
+    return out.value
+
+
 def qfilt_taps(n_taps, alpha, sam_per_sym):
     """util/math.rs:307-342 (f64, real); even n_taps is incremented."""
     out = np.empty(lib().comms_qfilt_len(int(n_taps)), np.float64)
@@ -1369,7 +1449,8 @@ class KernelTimer:
                 "comms_rfir_destroy": "comms_rfir_set_timer", "comms_noise_destroy": "comms_noise_set_timer",
                 "comms_resample_destroy": "comms_resample_set_timer",
                 "comms_channelizer_destroy": "comms_channelizer_set_timer",
-                "comms_symsync_destroy": "comms_symsync_set_timer"}[node._destroy]
+                "comms_symsync_destroy": "comms_symsync_set_timer",
+                "comms_syncest_destroy": "comms_syncest_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

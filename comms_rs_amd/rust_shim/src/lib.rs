@@ -1121,6 +1121,55 @@ impl TimingEstimatorNode {
     }
 }
 
+/// Timing and frequency estimates of a `Complex<f32>` block from one read of it (an additional node, comms_syncest_*):
+/// `TimingEstimator::push` at `(n, d, alpha)` and `frequency_offset_estimate` of the widened samples.  The message is the
+/// whole `comms_sync_estimate_t`; `tau()` turns its timing into what `SymbolSyncNode::set_timing` takes, and
+/// `psk_phase_estimate_c32` / `qam_phase_estimate_c32` cover the symbols (`set_rotation(-freq * sps, -phase)`).
+#[derive(Node)]
+#[pass_by_ref]
+pub struct SyncEstimatorNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    h: *mut comms_syncest_t,
+    n: u32,
+    pub output: NodeSender<comms_sync_estimate_t>,
+}
+handle_node!(SyncEstimatorNode, comms_syncest_destroy);
+impl SyncEstimatorNode {
+    /// `Err(())`: a bad rolloff (the reference's `MathError::InvalidRolloffError`) or a filter beyond the kernel's limits
+    /// (`n <= 256`, `2 n d + 1 <= 1024`).
+    pub fn new(n: u32, d: u32, alpha: f64) -> Result<Self, ()> {
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_syncest_create(n, d, alpha, 0, &mut h) };
+        if st != COMMS_OK { return Err(()); }
+        Ok(SyncEstimatorNode { input: Default::default(), h, n, output: Default::default() })
+    }
+    pub fn run(&mut self, input: &[Complex<f32>]) -> Result<comms_sync_estimate_t, NodeError> {
+        let mut est = comms_sync_estimate_t::default();
+        let st = unsafe { comms_syncest_run(self.h, input.as_ptr(), input.len(), &mut est) };
+        if st == COMMS_OK { Ok(est) } else { Err(to_err(st)) }
+    }
+    /// The `tau` of a `SymbolSyncNode` whose prototype has `n_taps` taps over `phases` phases (its sps = this node's n):
+    /// `timing + (n_taps - 1) / (2 phases)` modulo n.
+    pub fn tau(&self, est: &comms_sync_estimate_t, n_taps: usize, phases: usize) -> f64 {
+        let delay = (n_taps.max(1) - 1) as f64 / (2.0 * phases.max(1) as f64);
+        (est.timing + delay).rem_euclid(self.n as f64)
+    }
+}
+
+/// phase_estimator.rs:26-33 on `Complex<f32>` symbols (widened in the kernel's load).
+pub fn psk_phase_estimate_c32(symbols: &[Complex<f32>], m: u32) -> Result<f64, NodeError> {
+    let mut out = 0.0f64;
+    let st = unsafe { comms_psk_phase_estimate_c32(symbols.as_ptr(), symbols.len(), m, &mut out, 0) };
+    if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+}
+
+/// phase_estimator.rs:58-65 on `Complex<f32>` symbols.
+pub fn qam_phase_estimate_c32(symbols: &[Complex<f32>]) -> Result<f64, NodeError> {
+    let mut out = 0.0f64;
+    let st = unsafe { comms_qam_phase_estimate_c32(symbols.as_ptr(), symbols.len(), &mut out, 0) };
+    if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+}
+
 /// demodulation/nco.rs:118-133 in block form: a vector of phase errors per message.
 #[derive(Node)]
 #[pass_by_ref]
