@@ -13,4 +13,5 @@ from .nodes import (BatchFirNode, BatchFirNodeI16, FirNodeI16, PulseNodeI16, Bat
                     synth_iq, synth_iq_dev, PrnsNode, bpsk_byte_mod, qpsk_byte_mod, bpsk_bit_mod, qpsk_bit_mod,
                     sym_to_bits, sym_to_bits_dev, bit_errors, bit_errors_dev, RealFirDecimNode, NoiseSource, ResampleNode, ChannelizerNode,
                     SymbolSyncNode, SyncEstimatorNode, SyncEstimate, psk_phase_estimate_c32, qam_phase_estimate_c32,
-                    psk_phase_estimate_c32_dev, qam_phase_estimate_c32_dev)
+                    psk_phase_estimate_c32_dev, qam_phase_estimate_c32_dev, FrameSyncNode, FrameDetection,
+                    FRAME_DETECTION_DTYPE)

@@ -279,6 +279,19 @@ _PROTOS = {
     "comms_qam_phase_estimate_c32": [_vp, _sz, C.POINTER(_f64), _i32],
     "comms_psk_phase_estimate_c32_dev": [_vp, _sz, _u32, C.POINTER(_f64), _i32, _vp],
     "comms_qam_phase_estimate_c32_dev": [_vp, _sz, C.POINTER(_f64), _i32, _vp],
+    "comms_framesync_create": [_vp, _sz, _f64, _sz, _i32, _pp],
+    "comms_framesync_run_dev": [_vp, _vp, _sz, _vp, _sz, _psz, _vp],
+    "comms_framesync_run": [_vp, _vp, _sz, _vp, _sz, _psz],
+    "comms_framesync_flush": [_vp, _vp, _sz, _psz],
+    "comms_framesync_state_len": [_sz, _sz, _psz],
+    "comms_framesync_get_state": [_vp, _vp, _sz],
+    "comms_framesync_set_state": [_vp, _vp, _sz],
+    "comms_framesync_get_position": [_vp, C.POINTER(C.c_uint64)],
+    "comms_framesync_set_position": [_vp, C.c_uint64],
+    "comms_framesync_set_threshold": [_vp, _f64],
+    "comms_framesync_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_framesync_set_timer": [_vp, _vp],
+    "comms_framesync_destroy": [_vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],

@@ -1170,6 +1170,67 @@ private:
     detail::SyncEstimatorCore core_;
 };
 
+// Frame synchroniser (comms_framesync_*; an additional node): takes SymbolSyncNode<Complex32>'s symbol output and sends, per
+// block, the detections of a known word that the block decides -- possibly none -- as a vector ordered by stream index.
+// index + word.size() is the first payload symbol, atan2(corr_im, corr_re) the rotation to take out.  A block of n symbols
+// decides n positions, so a word is reported by the block that brings the last symbol of its guard window; flush() ends a
+// stream.  The detections do not depend on how the stream is cut into blocks.
+namespace detail {
+class FrameSyncCore {
+public:
+    FrameSyncCore(const std::vector<Complex32>& word, double threshold, size_t guard, int device, const char* who)
+        : n_word_(word.size()), guard_(guard) {
+        throw_on(comms_framesync_create(reinterpret_cast<const comms_c32*>(word.data()), word.size(), threshold, guard, device, &h_), who);
+    }
+    FrameSyncCore(FrameSyncCore&& o) noexcept : h_(o.h_), n_word_(o.n_word_), guard_(o.guard_) { o.h_ = nullptr; }
+    ~FrameSyncCore() { comms_framesync_destroy(h_); }
+    // no call on n symbols has more detections: they are more than `guard` apart
+    size_t bound(size_t n) const { return (n + guard_) / (guard_ + 1); }
+    Result<std::vector<comms_frame_detection_t>> flush() {
+        size_t found = 0;
+        std::vector<comms_frame_detection_t> out(bound(n_word_ + guard_));  // a flush decides word + guard positions
+        comms_status_t st = comms_framesync_flush(h_, out.data(), out.size(), &found);
+        if (st != COMMS_OK) return to_node_error(st);
+        out.resize(found);
+        return out;
+    }
+    comms_framesync_t* h() const { return h_; }
+
+private:
+    comms_framesync_t* h_ = nullptr;
+    size_t n_word_, guard_;
+};
+}  // namespace detail
+
+class FrameSyncNode : public DeriveNode<FrameSyncNode> {
+public:
+    NodeReceiver<std::vector<Complex32>> input;
+    NodeSender<std::vector<comms_frame_detection_t>> output;
+    FrameSyncNode(const std::vector<Complex32>& word, double threshold, size_t guard, int device = 0)
+        : core_(word, threshold, guard, device, "FrameSyncNode::new") {}
+    FrameSyncNode(FrameSyncNode&&) noexcept = default;
+    Result<std::vector<comms_frame_detection_t>> run(const std::vector<Complex32>& symbols) {
+        std::vector<comms_frame_detection_t> out(core_.bound(symbols.size()));
+        size_t found = 0;
+        comms_status_t st = comms_framesync_run(core_.h(), reinterpret_cast<const comms_c32*>(symbols.data()), symbols.size(), out.data(),
+                                                out.size(), &found);
+        if (st != COMMS_OK) return to_node_error(st);
+        out.resize(found);
+        return out;
+    }
+    Result<std::vector<comms_frame_detection_t>> flush() { return core_.flush(); }
+    std::string kernel(size_t n) const {  // "framesync_kernel ..."
+        char name[240] = {0};
+        comms_framesync_get_kernel(core_.h(), n, name, sizeof name);
+        return name;
+    }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    detail::FrameSyncCore core_;
+};
+
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)
@@ -1660,6 +1721,42 @@ public:
 
 private:
     detail::SyncEstimatorCore core_;
+    int device_;
+    void* s_ = nullptr;
+};
+
+// The frame synchroniser on device-resident messages (SymbolSyncNodeDev<Complex32>'s output): the detections are host
+// values (the call synchronises its stream), so the output is FrameSyncNode's
+class FrameSyncNodeDev : public DeriveNode<FrameSyncNodeDev> {
+public:
+    NodeReceiver<DeviceBuf<Complex32>> input;
+    NodeSender<std::vector<comms_frame_detection_t>> output;
+    FrameSyncNodeDev(const std::vector<Complex32>& word, double threshold, size_t guard, int device = 0)
+        : core_(word, threshold, guard, device, "FrameSyncNodeDev::new"), device_(device) {
+        throw_on(comms_stream_create(device, &s_), "comms_stream_create");
+    }
+    FrameSyncNodeDev(FrameSyncNodeDev&& o) noexcept
+        : input(std::move(o.input)), output(std::move(o.output)), core_(std::move(o.core_)), device_(o.device_), s_(o.s_) { o.s_ = nullptr; }
+    ~FrameSyncNodeDev() {
+        if (s_) comms_stream_destroy(device_, s_);   // every run ends synchronised
+    }
+    Result<std::vector<comms_frame_detection_t>> run(const DeviceBuf<Complex32>& in) {
+        if (in.device() != device_) return to_node_error(COMMS_ERR_ARG);
+        std::vector<comms_frame_detection_t> out(core_.bound(in.size()));
+        size_t found = 0;
+        comms_status_t st = comms_buf_wait_ready(in.raw(), s_);
+        if (st == COMMS_OK)
+            st = comms_framesync_run_dev(core_.h(), reinterpret_cast<const comms_c32*>(in.ptr()), in.size(), out.data(), out.size(), &found, s_);
+        if (st != COMMS_OK) return to_node_error(st);
+        out.resize(found);
+        return out;
+    }
+    Result<std::vector<comms_frame_detection_t>> flush() { return core_.flush(); }
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+
+private:
+    detail::FrameSyncCore core_;
     int device_;
     void* s_ = nullptr;
 };

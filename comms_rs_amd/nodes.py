@@ -1378,6 +1378,124 @@ def qam_phase_estimate_c32_dev(in_ptr, n, device=0, stream=0):
     return out.value
 
 
+class _FrameDetectionStruct(C.Structure):
+    _fields_ = [("index", C.c_uint64), ("corr_re", C.c_float), ("corr_im", C.c_float), ("metric", C.c_float), ("energy", C.c_float)]
+
+
+FRAME_DETECTION_DTYPE = np.dtype([("index", np.uint64), ("corr_re", np.float32), ("corr_im", np.float32), ("metric", np.float32),
+                                  ("energy", np.float32)])
+
+
+class FrameDetection:
+    """comms_frame_detection_t: `index` of the word's first symbol in the stream, the correlation `corr` = c[index] (its angle
+    is the rotation of the received word), the normalised `metric` in [0, 1] and the window's `energy`."""
+    __slots__ = ("index", "corr", "metric", "energy")
+
+    def __init__(self, s):
+        self.index = int(s["index"])
+        self.corr = complex(float(s["corr_re"]), float(s["corr_im"]))
+        self.metric, self.energy = float(s["metric"]), float(s["energy"])
+
+    @property
+    def phase(self):
+        """arg(corr): MixerNode(0, -phase) or SymbolSyncNode.set_rotation(dphase, phase_now - phase) takes it out."""
+        return float(np.arctan2(self.corr.imag, self.corr.real))
+
+    def __eq__(self, other):
+        return isinstance(other, FrameDetection) and (self.index, self.corr, self.metric, self.energy) == (
+            other.index, other.corr, other.metric, other.energy)
+
+    def __repr__(self):
+        return "FrameDetection(index=%d, corr=%r, metric=%r, energy=%r)" % (self.index, self.corr, self.metric, self.energy)
+
+
+class FrameSyncNode(_Handle):
+    """Frame synchroniser (comms_framesync_*): normalised correlation of a Complex<f32> symbol stream (SymbolSyncNode's
+    output) with a known `word`, peak search over +-`guard` positions and the `threshold` in one launch that returns only the
+    detections.  A call on n symbols decides n positions (a word is reported `guard` symbols after its end); flush() ends a
+    stream.  Detections are bit-identical however the stream is cut into calls.  `cap` limits the detections returned (the
+    lowest indices); `found` is the true count of the last call.  With raw=True a call returns the structured array
+    (FRAME_DETECTION_DTYPE) instead of FrameDetection values."""
+    _destroy = "comms_framesync_destroy"
+    found = 0
+
+    def __init__(self, word, threshold, guard, device=0):
+        super().__init__()
+        word = np.ascontiguousarray(word, dtype=np.complex64)
+        self.n_word, self.guard = word.size, int(guard)
+        check(lib().comms_framesync_create(_ptr(word), word.size, float(threshold), int(guard), device, C.byref(self._h)))
+
+    def _cap(self, n, cap):
+        return (n + self.guard) // (self.guard + 1) if cap is None else int(cap)
+
+    def _result(self, out, cap, found, raw):
+        self.found = found.value
+        out = out[: min(self.found, cap)]
+        return out if raw else [FrameDetection(d) for d in out]
+
+    def run(self, symbols, cap=None, raw=False):
+        x = np.ascontiguousarray(symbols, dtype=np.complex64)
+        cap = self._cap(x.size, cap)
+        out, found = np.zeros(cap, FRAME_DETECTION_DTYPE), C.c_size_t()
+        check(lib().comms_framesync_run(self._h, _ptr(x), x.size, _ptr(out) if cap else None, cap, C.byref(found)))
+        return self._result(out, cap, found, raw)
+
+    def run_dev(self, in_ptr, n, cap=None, stream=0, raw=False):
+        cap = self._cap(n, cap)
+        out, found = np.zeros(cap, FRAME_DETECTION_DTYPE), C.c_size_t()
+        check(lib().comms_framesync_run_dev(self._h, in_ptr, n, _ptr(out) if cap else None, cap, C.byref(found), stream))
+        return self._result(out, cap, found, raw)
+
+    def flush(self, cap=None, raw=False):
+        """The positions still undecided, as if n_word + guard zero symbols followed; history zero afterwards, position kept."""
+        cap = self._cap(self.n_word + self.guard, cap)
+        out, found = np.zeros(cap, FRAME_DETECTION_DTYPE), C.c_size_t()
+        check(lib().comms_framesync_flush(self._h, _ptr(out) if cap else None, cap, C.byref(found)))
+        return self._result(out, cap, found, raw)
+
+    def state_len(self):
+        m = C.c_size_t()
+        check(lib().comms_framesync_state_len(self.n_word, self.guard, C.byref(m)))
+        return m.value
+
+    def state(self, n_state=None):
+        """The last n_state symbols (default: all n_word + 2 guard - 1), newest first."""
+        n_state = self.state_len() if n_state is None else int(n_state)
+        st = np.empty(n_state, np.complex64)
+        check(lib().comms_framesync_get_state(self._h, _ptr(st), n_state))
+        return st
+
+    def set_state(self, state):
+        state = np.ascontiguousarray(state, dtype=np.complex64)
+        check(lib().comms_framesync_set_state(self._h, _ptr(state), state.size))
+        return self
+
+    def position(self):
+        """Stream index of the next symbol."""
+        t = C.c_uint64()
+        check(lib().comms_framesync_get_position(self._h, C.byref(t)))
+        return t.value
+
+    def set_position(self, position):
+        check(lib().comms_framesync_set_position(self._h, int(position)))
+        return self
+
+    def set_threshold(self, threshold):
+        check(lib().comms_framesync_set_threshold(self._h, float(threshold)))
+        return self
+
+    def kernel(self, n):
+        """What a call on n symbols is run by: "framesync_kernel tile=.. wg=.. word=.. guard=.. lds=.. tiles=.. grid=.. max_grid=.."."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_framesync_get_kernel(self._h, n, buf, 240))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch."""
+        check(lib().comms_framesync_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
 def qfilt_taps(n_taps, alpha, sam_per_sym):
     """util/math.rs:307-342 (f64, real); even n_taps is incremented."""
     out = np.empty(lib().comms_qfilt_len(int(n_taps)), np.float64)
@@ -1450,7 +1568,8 @@ class KernelTimer:
                 "comms_resample_destroy": "comms_resample_set_timer",
                 "comms_channelizer_destroy": "comms_channelizer_set_timer",
                 "comms_symsync_destroy": "comms_symsync_set_timer",
-                "comms_syncest_destroy": "comms_syncest_set_timer"}[node._destroy]
+                "comms_syncest_destroy": "comms_syncest_set_timer",
+                "comms_framesync_destroy": "comms_framesync_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

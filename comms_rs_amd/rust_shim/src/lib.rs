@@ -1170,6 +1170,66 @@ pub fn qam_phase_estimate_c32(symbols: &[Complex<f32>]) -> Result<f64, NodeError
     if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
 }
 
+/// Frame synchroniser (an additional node, comms_framesync_*): finds a known `word` in the `Complex<f32>` symbol stream that
+/// `SymbolSyncNode` sends and returns, per block, the detections the block decides (possibly none), ordered by stream index.
+/// `index + word.len()` is the first payload symbol and `corr_im.atan2(corr_re)` the rotation to take out
+/// (`MixerNode::new(0.0, Some(-angle))`).  A block of n symbols decides n positions: a word is reported `guard` symbols after
+/// its end; `flush` ends a stream.  The detections do not depend on how the stream is cut into blocks.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct FrameSyncNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    h: *mut comms_framesync_t,
+    n_word: usize,
+    guard: usize,
+    pub output: NodeSender<Vec<comms_frame_detection_t>>,
+}
+handle_node!(FrameSyncNode, comms_framesync_destroy);
+impl FrameSyncNode {
+    /// `Err(())`: a word of fewer than 2 or more than 512 symbols, not finite or without energy, a guard beyond 512 or a
+    /// threshold outside (0, 1].
+    pub fn new(word: &[Complex<f32>], threshold: f64, guard: usize) -> Result<Self, ()> {
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_framesync_create(word.as_ptr(), word.len(), threshold, guard, 0, &mut h) };
+        if st != COMMS_OK { return Err(()); }
+        Ok(FrameSyncNode { input: Default::default(), h, n_word: word.len(), guard, output: Default::default() })
+    }
+    pub fn run(&mut self, input: &[Complex<f32>]) -> Result<Vec<comms_frame_detection_t>, NodeError> {
+        // detections are more than `guard` apart: no call on n symbols has more than ceil(n / (guard + 1))
+        let cap = (input.len() + self.guard) / (self.guard + 1);
+        let mut out = vec![comms_frame_detection_t::default(); cap];
+        let mut found = 0usize;
+        let st = unsafe { comms_framesync_run(self.h, input.as_ptr(), input.len(), out.as_mut_ptr(), cap, &mut found) };
+        if st != COMMS_OK { return Err(to_err(st)); }
+        out.truncate(found);
+        Ok(out)
+    }
+    /// The positions still undecided, as if `word.len() + guard` zero symbols followed; the history is zero afterwards.
+    pub fn flush(&mut self) -> Result<Vec<comms_frame_detection_t>, NodeError> {
+        let cap = (self.n_word + 2 * self.guard) / (self.guard + 1);
+        let mut out = vec![comms_frame_detection_t::default(); cap];
+        let mut found = 0usize;
+        let st = unsafe { comms_framesync_flush(self.h, out.as_mut_ptr(), cap, &mut found) };
+        if st != COMMS_OK { return Err(to_err(st)); }
+        out.truncate(found);
+        Ok(out)
+    }
+    /// Stream index of the next symbol (checkpoints; the first index of a stream shard).
+    pub fn position(&self) -> u64 {
+        let mut t = 0u64;
+        unsafe { comms_framesync_get_position(self.h, &mut t) };
+        t
+    }
+    pub fn set_position(&mut self, position: u64) -> Result<(), NodeError> {
+        let st = unsafe { comms_framesync_set_position(self.h, position) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    pub fn set_threshold(&mut self, threshold: f64) -> Result<(), NodeError> {
+        let st = unsafe { comms_framesync_set_threshold(self.h, threshold) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+}
+
 /// demodulation/nco.rs:118-133 in block form: a vector of phase errors per message.
 #[derive(Node)]
 #[pass_by_ref]
