@@ -13,10 +13,22 @@
 //   NcoNode::new(dphase, phase) (block form)      src/demodulation/nco.rs:118
 //   PrnsNode::new(poly_mask, state)               src/prns.rs:93-137
 //   NormalNode::new(mu, std_dev), UniformNode<T>::new(start, end), random_bit()   src/util/rand_node.rs:60, :124, :150
-// Messages are host vectors (std::vector<Complex>), moved through the channels by
-// value as in the reference; every run() goes H2D -> kernel -> D2H through the C
-// ABI.  The *Dev variants at the bottom keep messages device-resident
-// (DeviceBuf<T>, clone = refcount bump) -- what the roofline numbers use.
+//
+// How the header is built:
+//   Owned<H, Destroy>   the one owner of an opaque comms_*_t*; create<>() runs a *_create entry into it.  No class here
+//                       writes a move constructor or a destructor for a handle: moves are implicit or `= default`.
+//   a description       (FirOp, ChainOp, RealFirDecimOp, SymbolSyncOp ...) states once what is particular to an operation:
+//                       its handle and parameters, prepare(n, m) -- what precedes a launch, m = the output length --, the
+//                       host-pointer entry launch(), the *_run_dev entry launch_dev(), and its extras as public members
+//                       (kernel(n), channels(), fused_kind(), flush(), the `update` channel).
+//   Ports<In, Out>      the `input` / `output` fields with receivers() / senders(), and the teardown order: handle, stream, channels.
+//   HostNode<D, Op>     turns a description into the node on std::vector messages: every run() goes H2D -> kernel -> D2H
+//                       through the C ABI, messages moved through the channels by value as in the reference.
+//   DevNode<D, Op>      turns it into the node on device-resident messages (DeviceBuf<T>, clone = refcount bump) on a stream
+//                       of its own -- what the roofline numbers use.
+// The public node types are thin: a constructor with the reference's parameter list, and the name its errors carry.
+// Sources, per-sample nodes (run_block) and the nodes whose output is a host value have run() bodies of their own over the
+// same descriptions and the same owner.
 //
 // Error convention: comms_status_t 1 -> NodeError::DataError, 2 -> PermanentError.
 // Constructors throw std::runtime_error when a handle cannot be created (the
@@ -27,6 +39,7 @@
 #include <limits>
 #include <complex>
 #include <cstring>
+#include <memory>
 #include <optional>
 #include <random>
 #include <stdexcept>
@@ -54,6 +67,40 @@ inline void throw_on(comms_status_t st, const char* what) {
 }
 inline NodeError to_node_error(comms_status_t st) {
     return st == COMMS_ERR_ARG ? NodeError::DataError : NodeError::PermanentError;
+}
+// what a run() returns: `out` (moved from) when the C call succeeded, its NodeError otherwise
+template <class T>
+Result<T> ok_or(comms_status_t st, T& out) {
+    if (st != COMMS_OK) return to_node_error(st);
+    return std::move(out);
+}
+
+// ---------------------------------------------------------------- handle ownership
+// The owner of an opaque C handle: move-only, released through the handle's comms_*_destroy entry.
+template <auto Destroy>
+struct Destroyer {
+    template <class H>
+    void operator()(H* h) const { Destroy(h); }
+};
+template <class H, auto Destroy>
+using Owned = std::unique_ptr<H, Destroyer<Destroy>>;
+
+// runs a *_create entry (its last argument receives the handle) into the owner O; a failure throws "<who>: <last error>".
+// A constructor that throws after this still releases the handle: the owner is a member by then.
+template <class O, class F, class... A>
+O create(const char* who, F make, A... args) {
+    typename O::pointer h = nullptr;
+    throw_on(make(args..., &h), who);
+    return O(h);
+}
+
+// the *_get_kernel entries: what a handle launches for n samples, as text ("<kernel><..> ...", or "series: ..." for the launches
+// of a fallback)
+template <class F, class H>
+std::string kernel_name(F get_kernel, const H* h, size_t n) {
+    char name[240] = {0};
+    get_kernel(h, n, name, sizeof name);
+    return name;
 }
 
 // ---------------------------------------------------------------- device-resident message
@@ -96,10 +143,122 @@ private:
     size_t count_ = 0;
 };
 
+// ---------------------------------------------------------------- the two shells
+// A description Op has
+//     using In, Out;                                      element types of a message
+//     Op(const char* who, <its parameters>);              creates the handle; `who` names the node in the error
+//     comms_status_t prepare(size_t n, size_t& m);        what precedes the launch of an n-element message; m = its output length
+//     comms_status_t launch(const In*, size_t n, Out*);               the host-pointer entry (synchronous)
+//     comms_status_t launch_dev(const In*, size_t n, Out*, void* s);  the *_run_dev entry on stream s
+// (the three protected), and whatever else is public on the node.  A shell derives from it, so the extras need no forwarding.
+
+// The channel fields of a one-in / one-out node, and how DeriveNode finds them.  First among a node's bases, so it goes last:
+// a node releases its handle before its senders disconnect, and a consumer that sees its channel end finds the producer's
+// device work over.
+template <class In, class Out>
+struct Ports {
+    NodeReceiver<In> input;
+    NodeSender<Out> output;
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output); }
+};
+
+struct SameLength {  // prepare() of the operations that give one output element per input element
+    comms_status_t prepare(size_t n, size_t& m) const {
+        m = n;
+        return COMMS_OK;
+    }
+};
+
+// The node on host vectors.  D is the public node type (what DeriveNode wants).
+template <class D, class Op>
+class HostNode : public DeriveNode<D>, public Ports<std::vector<typename Op::In>, std::vector<typename Op::Out>>, public Op {
+public:
+    template <class... A>
+    explicit HostNode(const char* who, A&&... a) : Op(who, std::forward<A>(a)...) {}
+    HostNode(HostNode&&) = default;  // a node is moved into its thread, never copied
+
+    Result<std::vector<typename Op::Out>> run(const std::vector<typename Op::In>& in) {
+        size_t m = 0;
+        comms_status_t st = Op::prepare(in.size(), m);
+        if (st != COMMS_OK) return to_node_error(st);
+        std::vector<typename Op::Out> out(m);
+        return ok_or(Op::launch(in.data(), in.size(), out.data()), out);
+    }
+};
+
+// Device-resident messages are DeviceBuf<T>: nothing crosses PCIe between nodes and nothing ever synchronises
+// the device.  Every node owns a stream (DevStream); run() is
+//     wait_ready(in)  ->  one asynchronous launch on the node's stream  ->  record_use(in),
+//     record_ready(out)  ->  send(out)
+// so the consumer's stream starts its own launch only after the producer's has finished, while the
+// node threads themselves run ahead of the device.  An edge stays on ONE GPU: the buffer's events
+// belong to its device and the kernels read it directly, so a message whose device is not the node's is a
+// DataError (COMMS_ERR_ARG) -- between GPUs the host copies or sends the samples itself (sharding, below).  Output
+// buffers come from the library's cache (no hipMalloc / hipFree in steady state); a buffer's
+// memory is recycled only after the launches that read it.  to_host() waits for the producer.
+class DevStream {
+public:
+    explicit DevStream(int device) : s_(nullptr, Retire{device}) {
+        void* s = nullptr;
+        throw_on(comms_stream_create(device, &s), "comms_stream_create");
+        s_.reset(s);
+    }
+    // the producer of `in` has finished before anything later on this stream starts (no host wait); no cross-device edges
+    template <class T>
+    comms_status_t wait(const DeviceBuf<T>& in) const {
+        return in.device() != device() ? COMMS_ERR_ARG : comms_buf_wait_ready(in.raw(), get());
+    }
+    // `launch(stream)` is the node's *_run_dev call
+    template <class TI, class TO, class F>
+    comms_status_t submit(const DeviceBuf<TI>& in, DeviceBuf<TO>& out, F&& launch) const {
+        comms_status_t st = out.device() != device() ? COMMS_ERR_ARG : wait(in);
+        if (st == COMMS_OK) st = launch(get());
+        if (st == COMMS_OK) st = comms_buf_record_use(in.raw(), get());
+        if (st == COMMS_OK) st = comms_buf_record_ready(out.raw(), get());
+        return st;
+    }
+    void* get() const { return s_.get(); }
+    int device() const { return s_.get_deleter().device; }
+
+private:
+    struct Retire {
+        int device;
+        void operator()(void* s) const {
+            comms_stream_synchronize(device, s);
+            comms_stream_destroy(device, s);
+        }
+    };
+    std::unique_ptr<void, Retire> s_;
+};
+
+// A description on a stream of its own: the one place where a device node is put together.
+template <class Op>
+struct OnStream : protected DevStream, public Op {  // bases go in reverse order: the handle, whose destroy quiesces this stream, before the stream
+    template <class... A>
+    explicit OnStream(int device, const char* who, A&&... a) : DevStream(device), Op(who, std::forward<A>(a)...) {}
+};
+
+// The node on device-resident messages.
+template <class D, class Op>
+class DevNode : public DeriveNode<D>, public Ports<DeviceBuf<typename Op::In>, DeviceBuf<typename Op::Out>>, public OnStream<Op> {
+public:
+    using OnStream<Op>::OnStream;
+    DevNode(DevNode&&) = default;
+
+    Result<DeviceBuf<typename Op::Out>> run(const DeviceBuf<typename Op::In>& in) {
+        size_t m = 0;
+        comms_status_t st = Op::prepare(in.size(), m);
+        if (st != COMMS_OK) return to_node_error(st);
+        DeviceBuf<typename Op::Out> out(m, this->device());
+        return ok_or(this->submit(in, out, [&](void* s) { return Op::launch_dev(in.ptr(), in.size(), out.ptr(), s); }), out);
+    }
+};
+
 // ---------------------------------------------------------------- sample types
 // What the C ABI offers per sample type, as the Rust shim's FirSample / MixSample / SpectralSample traits have it: the
 // interleaved {re, im} struct, the handle types and the entry points.  Complex<i16> (wrapping arithmetic) has the FIR and
-// the pulse shaper only.
+// the pulse shaper only; the *_run_dev entries are bound where a device-resident node uses them (Complex<f32>).
 using Complex16 = std::complex<int16_t>;
 static_assert(sizeof(Complex16) == sizeof(comms_c16), "Complex<i16> must be interleaved {re, im}");
 inline const comms_c16* c16(const Complex16* p) { return reinterpret_cast<const comms_c16*>(p); }
@@ -117,16 +276,21 @@ struct Sample<Complex32> {
     using Fm = comms_fmdemod_t;
     static constexpr auto fir_create = comms_fir_create;
     static constexpr auto fir_run = comms_fir_run;
+    static constexpr auto fir_run_dev = comms_fir_run_dev;
     static constexpr auto fir_destroy = comms_fir_destroy;
     static constexpr auto pulse_create = comms_pulse_create;
     static constexpr auto pulse_run = comms_pulse_run;
+    static constexpr auto pulse_run_dev = comms_pulse_run_dev;
     static constexpr auto pulse_destroy = comms_pulse_destroy;
     static constexpr auto mixer_run = comms_mixer_run;
+    static constexpr auto mixer_run_dev = comms_mixer_run_dev;
     static constexpr auto fft_create = comms_fft_create;
     static constexpr auto fft_run = comms_fft_run;
+    static constexpr auto fft_run_dev = comms_fft_run_dev;
     static constexpr auto fft_destroy = comms_fft_destroy;
     static constexpr auto fm_create = comms_fmdemod_create;
     static constexpr auto fm_run = comms_fmdemod_run;
+    static constexpr auto fm_run_dev = comms_fmdemod_run_dev;
     static constexpr auto fm_destroy = comms_fmdemod_destroy;
 };
 template <>
@@ -171,109 +335,96 @@ typename Sample<T>::Abi* abi(T* p) { return reinterpret_cast<typename Sample<T>:
 // ---------------------------------------------------------------- FIR
 // The node templates below take the public node type D (what DeriveNode wants, and D::kNew names the node when its
 // constructor throws) and the sample type T.  The public names follow each group.
-template <class D, class T>
-class BatchFirNodeOf : public DeriveNode<D> {
-    using S = Sample<T>;
+template <class T>
+struct FirOp : protected SameLength {
+    using In = T;
+    using Out = T;
+    FirOp(const char* who, const std::vector<T>& taps, const std::optional<std::vector<T>>& state, int device)
+        : h_(create<decltype(h_)>(who, Sample<T>::fir_create, abi(taps.data()), taps.size(), state ? abi(state->data()) : nullptr,
+                                  state ? state->size() : 0, device)) {}
 
-public:
-    NodeReceiver<std::vector<T>> input;
-    NodeSender<std::vector<T>> output;
-
-    BatchFirNodeOf(const std::vector<T>& taps, const std::optional<std::vector<T>>& state = std::nullopt, int device = 0) {
-        throw_on(S::fir_create(abi(taps.data()), taps.size(), state ? abi(state->data()) : nullptr, state ? state->size() : 0, device, &h_),
-                 D::kNew);
-    }
-    BatchFirNodeOf(BatchFirNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~BatchFirNodeOf() { S::fir_destroy(h_); }
-
-    Result<std::vector<T>> run(const std::vector<T>& in) {
-        std::vector<T> out(in.size());
-        comms_status_t st = S::fir_run(h_, abi(in.data()), in.size(), abi(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-    typename S::Fir* handle() const { return h_; }
-
-private:
-    typename S::Fir* h_ = nullptr;
+protected:
+    comms_status_t launch(const T* in, size_t n, T* out) { return Sample<T>::fir_run(h_.get(), abi(in), n, abi(out)); }
+    comms_status_t launch_dev(const T* in, size_t n, T* out, void* s) { return Sample<T>::fir_run_dev(h_.get(), abi(in), n, abi(out), s); }
+    Owned<typename Sample<T>::Fir, Sample<T>::fir_destroy> h_;
 };
 
 template <class D, class T>
-class FirNodeOf : public DeriveNode<D> {
-    using S = Sample<T>;
-
+class BatchFirNodeOf : public HostNode<D, FirOp<T>> {
 public:
-    NodeReceiver<T> input;
-    NodeSender<T> output;
+    BatchFirNodeOf(const std::vector<T>& taps, const std::optional<std::vector<T>>& state = std::nullopt, int device = 0)
+        : BatchFirNodeOf::HostNode(D::kNew, taps, state, device) {}
+    typename Sample<T>::Fir* handle() const { return this->h_.get(); }
+};
 
-    FirNodeOf(const std::vector<T>& taps, const std::optional<std::vector<T>>& state = std::nullopt, int device = 0) {
-        throw_on(S::fir_create(abi(taps.data()), taps.size(), state ? abi(state->data()) : nullptr, state ? state->size() : 0, device, &h_),
-                 D::kNew);
-    }
-    FirNodeOf(FirNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FirNodeOf() { S::fir_destroy(h_); }
+template <class D, class T>
+class FirNodeOf : public DeriveNode<D>, public Ports<T, T>, public FirOp<T> {
+public:
+    FirNodeOf(const std::vector<T>& taps, const std::optional<std::vector<T>>& state = std::nullopt, int device = 0)
+        : FirOp<T>(D::kNew, taps, state, device) {}
 
     Result<T> run(const T& in) {
         T out;
-        comms_status_t st = S::fir_run(h_, abi(&in), 1, abi(&out));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
+        return ok_or(this->launch(&in, 1, &out), out);
     }
     // the samples already queued behind the first one, in one launch (DeriveNode::call): the
     // filter's state runs through the block exactly as through the same samples one by one
     Result<std::vector<T>> run_block(const std::vector<T>& ins) {
         std::vector<T> out(ins.size());
-        comms_status_t st = S::fir_run(h_, abi(ins.data()), ins.size(), abi(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
+        return ok_or(this->launch(ins.data(), ins.size(), out.data()), out);
     }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    typename S::Fir* h_ = nullptr;
 };
 
 // ---------------------------------------------------------------- pulse shaping
-template <class D, class T>
-class PulseNodeOf : public DeriveNode<D> {
-    using S = Sample<T>;
+// T is the sample type of the taps (and of the handle).  A message holds symbols of type T, or -- bits_per_sym 1 or 2 -- packed
+// bits, LSB first, whole bytes; sam_per_sym outputs per symbol.
+template <class T, class I = T, class O = T>
+struct PulseOp {
+    using In = I;
+    using Out = O;
+    PulseOp(const char* who, const std::vector<T>& taps, size_t sam_per_sym, int device, int bits_per_sym = 0)
+        : h_(create<decltype(h_)>(who, Sample<T>::pulse_create, abi(taps.data()), taps.size(), sam_per_sym, device)),
+          sps_(sam_per_sym),
+          k_(bits_per_sym) {}
 
-public:
-    NodeReceiver<T> input;
-    NodeSender<std::vector<T>> output;
-
-    PulseNodeOf(const std::vector<T>& taps, size_t sam_per_sym, int device = 0) : sps_(sam_per_sym) {
-        throw_on(S::pulse_create(abi(taps.data()), taps.size(), sam_per_sym, device, &h_), D::kNew);
+protected:
+    size_t symbols(size_t n) const { return k_ ? n * 8 / static_cast<size_t>(k_) : n; }
+    comms_status_t prepare(size_t n, size_t& m) const {
+        m = symbols(n) * sps_;
+        return COMMS_OK;
     }
-    PulseNodeOf(PulseNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sps_(o.sps_) { o.h_ = nullptr; }
-    ~PulseNodeOf() { S::pulse_destroy(h_); }
+    comms_status_t launch(const In* in, size_t n, Out* out) {
+        return Sample<T>::pulse_run(h_.get(), reinterpret_cast<const typename Sample<T>::Abi*>(in), symbols(n),
+                                    reinterpret_cast<typename Sample<T>::Abi*>(out));
+    }
+    comms_status_t launch_dev(const In* in, size_t n, Out* out, void* s) {
+        return Sample<T>::pulse_run_dev(h_.get(), reinterpret_cast<const typename Sample<T>::Abi*>(in), symbols(n),
+                                        reinterpret_cast<typename Sample<T>::Abi*>(out), s);
+    }
+    Owned<typename Sample<T>::Pulse, Sample<T>::pulse_destroy> h_;
+    size_t sps_;
+    int k_;
+};
+
+template <class D, class T>
+class PulseNodeOf : public DeriveNode<D>, public Ports<T, std::vector<T>>, public PulseOp<T> {
+public:
+    PulseNodeOf(const std::vector<T>& taps, size_t sam_per_sym, int device = 0) : PulseOp<T>(D::kNew, taps, sam_per_sym, device) {}
 
     Result<std::vector<T>> run(const T& sym) {
-        std::vector<T> out(sps_);
-        comms_status_t st = S::pulse_run(h_, abi(&sym), 1, abi(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
+        std::vector<T> out(this->sps_);
+        return ok_or(this->launch(&sym, 1, out.data()), out);
     }
     // queued symbols in one launch; still one Vec of sam_per_sym samples per symbol downstream
     Result<std::vector<std::vector<T>>> run_block(const std::vector<T>& syms) {
-        std::vector<T> flat(syms.size() * sps_);
-        comms_status_t st = S::pulse_run(h_, abi(syms.data()), syms.size(), abi(flat.data()));
+        const size_t sps = this->sps_;
+        std::vector<T> flat(syms.size() * sps);
+        comms_status_t st = this->launch(syms.data(), syms.size(), flat.data());
         if (st != COMMS_OK) return to_node_error(st);
         std::vector<std::vector<T>> out(syms.size());
-        for (size_t i = 0; i < syms.size(); ++i) out[i].assign(flat.begin() + i * sps_, flat.begin() + (i + 1) * sps_);
+        for (size_t i = 0; i < syms.size(); ++i) out[i].assign(flat.begin() + i * sps, flat.begin() + (i + 1) * sps);
         return out;
     }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-protected:
-    typename S::Pulse* h_ = nullptr;
-
-private:
-    size_t sps_;
 };
 
 // f32: every BASELINE config, the tuned kernels (comms_fir_*, comms_pulse_*)
@@ -291,7 +442,22 @@ struct PulseNode : PulseNodeOf<PulseNode, Complex32> {
     // transmit chain in one launch: the MixerNode::new(dphase, phase) that follows is fused in
     // (the i16 store stage, comms_pulse_set_output_format, is offered on the device-resident node below)
     PulseNode& with_mixer(double dphase, std::optional<double> phase = std::nullopt) {
-        throw_on(comms_pulse_set_mixer(h_, dphase, phase.value_or(0.0)), "PulseNode::with_mixer");
+        throw_on(comms_pulse_set_mixer(h_.get(), dphase, phase.value_or(0.0)), "PulseNode::with_mixer");
+        return *this;
+    }
+};
+class BatchFirNodeDev : public DevNode<BatchFirNodeDev, FirOp<Complex32>> {
+public:
+    BatchFirNodeDev(const std::vector<Complex32>& taps, const std::optional<std::vector<Complex32>>& state = std::nullopt, int device = 0)
+        : DevNode(device, "BatchFirNodeDev::new", taps, state, device) {}
+};
+// PulseNode over whole symbol blocks: n symbols in, n * sam_per_sym samples out
+class BatchPulseNodeDev : public DevNode<BatchPulseNodeDev, PulseOp<Complex32>> {
+public:
+    BatchPulseNodeDev(const std::vector<Complex32>& taps, size_t sam_per_sym, int device = 0)
+        : DevNode(device, "BatchPulseNodeDev::new", taps, sam_per_sym, device) {}
+    BatchPulseNodeDev& with_mixer(double dphase, std::optional<double> phase = std::nullopt) {
+        throw_on(comms_pulse_set_mixer(h_.get(), dphase, phase.value_or(0.0)), "BatchPulseNodeDev::with_mixer");
         return *this;
     }
 };
@@ -337,19 +503,15 @@ public:
     NodeSender<uint8_t> output;
     static constexpr size_t kBlock = 4096;
 
-    PrnsNode(uint64_t poly_mask, uint64_t state, int width = 8, int device = 0) : start_(state) {
-        throw_on(comms_prns_create(poly_mask, state, width, device, &h_), "PrnsNode::new");
-    }
-    PrnsNode(PrnsNode&& o) noexcept
-        : output(std::move(o.output)), h_(o.h_), buf_(std::move(o.buf_)), pos_(o.pos_), start_(o.start_) { o.h_ = nullptr; }
-    ~PrnsNode() { comms_prns_destroy(h_); }
+    PrnsNode(uint64_t poly_mask, uint64_t state, int width = 8, int device = 0)
+        : h_(create<decltype(h_)>("PrnsNode::new", comms_prns_create, poly_mask, state, width, device)), start_(state) {}
 
     Result<uint8_t> run() {
         if (pos_ == buf_.size()) {
             uint64_t s = 0;
-            comms_status_t st = comms_prns_get_state(h_, &s);
+            comms_status_t st = comms_prns_get_state(h_.get(), &s);
             buf_.resize(kBlock);
-            if (st == COMMS_OK) st = comms_prns_run(h_, kBlock, COMMS_BITS_U8, buf_.data());
+            if (st == COMMS_OK) st = comms_prns_run(h_.get(), kBlock, COMMS_BITS_U8, buf_.data());
             if (st != COMMS_OK) {
                 buf_.clear();
                 pos_ = 0;
@@ -363,18 +525,18 @@ public:
     // the register before the next bit run() returns (PrnGen's `state`)
     uint64_t state() {
         uint64_t ahead = 0, s = 0;
-        throw_on(comms_prns_get_state(h_, &ahead), "PrnsNode::state");
-        throw_on(comms_prns_set_state(h_, start_), "PrnsNode::state");
-        throw_on(comms_prns_skip(h_, pos_), "PrnsNode::state");
-        throw_on(comms_prns_get_state(h_, &s), "PrnsNode::state");
-        throw_on(comms_prns_set_state(h_, ahead), "PrnsNode::state");
+        throw_on(comms_prns_get_state(h_.get(), &ahead), "PrnsNode::state");
+        throw_on(comms_prns_set_state(h_.get(), start_), "PrnsNode::state");
+        throw_on(comms_prns_skip(h_.get(), pos_), "PrnsNode::state");
+        throw_on(comms_prns_get_state(h_.get(), &s), "PrnsNode::state");
+        throw_on(comms_prns_set_state(h_.get(), ahead), "PrnsNode::state");
         return s;
     }
     auto receivers() { return std::tie(); }
     auto senders() { return std::tie(output); }
 
 private:
-    comms_prns_t* h_ = nullptr;
+    Owned<comms_prns_t, comms_prns_destroy> h_;
     std::vector<uint8_t> buf_;
     size_t pos_ = 0;
     uint64_t start_ = 0;  // register at buf_[0]
@@ -390,20 +552,17 @@ inline uint64_t entropy_seed() {
     std::random_device rd;
     return (static_cast<uint64_t>(rd()) << 32) | static_cast<uint64_t>(rd());
 }
+using NoiseHandle = Owned<comms_noise_t, comms_noise_destroy>;
 
-// CRTP base: D::draw(handle, n, out) draws n values (n a multiple of D::kGrain) from the stream position
+// CRTP base: D::draw(n, out) draws n values (n a multiple of D::kGrain) from the stream position
 template <class D, class T>
 class NoiseSourceNode : public DeriveNode<D> {
 public:
     NodeSender<T> output;
     static constexpr size_t kBlock = 4096;
 
-    NoiseSourceNode(std::optional<uint64_t> seed, int device, const char* what) : seed_(seed ? *seed : entropy_seed()) {
-        throw_on(comms_noise_create(seed_, 0, device, &h_), what);
-    }
-    NoiseSourceNode(NoiseSourceNode&& o) noexcept
-        : output(std::move(o.output)), h_(o.h_), seed_(o.seed_), buf_(std::move(o.buf_)), pos_(o.pos_) { o.h_ = nullptr; }
-    ~NoiseSourceNode() { comms_noise_destroy(h_); }
+    NoiseSourceNode(std::optional<uint64_t> seed, int device, const char* what)
+        : seed_(seed ? *seed : entropy_seed()), h_(create<NoiseHandle>(what, comms_noise_create, seed_, uint64_t(0), device)) {}
 
     Result<T> run() {
         if (pos_ == buf_.size()) {
@@ -431,8 +590,11 @@ public:
     auto receivers() { return std::tie(); }
     auto senders() { return std::tie(output); }
 
+private:
+    uint64_t seed_;  // before h_: the create reads it
+
 protected:
-    comms_noise_t* h_ = nullptr;
+    NoiseHandle h_;
 
 private:
     comms_status_t refill(size_t n) {
@@ -442,7 +604,6 @@ private:
         if (st != COMMS_OK) buf_.clear();
         return st;
     }
-    uint64_t seed_;
     std::vector<T> buf_;
     size_t pos_ = 0;
 };
@@ -454,7 +615,7 @@ public:
         : NoiseSourceNode(seed, device, "NormalNode::new"), mu_(mu), sd_(std_dev) {
         if (!(std_dev >= 0.0) || !std::isfinite(std_dev) || !std::isfinite(mu)) throw std::runtime_error("NormalNode::new: std_dev < 0 or not finite");
     }
-    comms_status_t draw(size_t n, double* out) { return comms_noise_normal_f64_run(h_, n, mu_, sd_, out); }
+    comms_status_t draw(size_t n, double* out) { return comms_noise_normal_f64_run(h_.get(), n, mu_, sd_, out); }
 
 private:
     double mu_, sd_;
@@ -472,7 +633,7 @@ public:
         : NoiseSourceNode(seed, device, "UniformNode::new"), lo_(start), hi_(end) {
         if (!(start < end) || !std::isfinite(start) || !std::isfinite(end)) throw std::runtime_error("UniformNode::new: start >= end");  // Uniform::new panics
     }
-    comms_status_t draw(size_t n, float* out) { return comms_noise_uniform_run(h_, n, lo_, hi_, out); }
+    comms_status_t draw(size_t n, float* out) { return comms_noise_uniform_run(h_.get(), n, lo_, hi_, out); }
 
 private:
     float lo_, hi_;
@@ -487,7 +648,7 @@ public:
         : NoiseSourceNode(seed, device, "UniformNode::new") {
         if (start != 0 || end != 2) throw std::runtime_error("UniformNode<u8>::new: only the range [0, 2) of random_bit() is implemented");
     }
-    comms_status_t draw(size_t n, uint8_t* out) { return comms_noise_bits_run(h_, n, COMMS_BITS_U8, out); }
+    comms_status_t draw(size_t n, uint8_t* out) { return comms_noise_bits_run(h_.get(), n, COMMS_BITS_U8, out); }
 };
 
 inline UniformNode<uint8_t> random_bit(std::optional<uint64_t> seed = std::nullopt, int device = 0) {
@@ -496,151 +657,124 @@ inline UniformNode<uint8_t> random_bit(std::optional<uint64_t> seed = std::nullo
 
 // AWGN channel (an additional node): out = in + sigma * (z + i z'), one complex standard pair per sample, the pairs of
 // consecutive messages consecutive in the source's stream (comms_awgn_run)
-class AwgnNode : public DeriveNode<AwgnNode> {
-public:
-    NodeReceiver<std::vector<Complex32>> input;
-    NodeSender<std::vector<Complex32>> output;
-    AwgnNode(float sigma, std::optional<uint64_t> seed = std::nullopt, uint64_t stream = 0, int device = 0) : sigma_(sigma) {
-        throw_on(comms_noise_create(seed ? *seed : entropy_seed(), stream, device, &h_), "AwgnNode::new");
-    }
-    AwgnNode(AwgnNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sigma_(o.sigma_) { o.h_ = nullptr; }
-    ~AwgnNode() { comms_noise_destroy(h_); }
-    Result<std::vector<Complex32>> run(const std::vector<Complex32>& in) {
-        std::vector<Complex32> out(in.size());
-        comms_status_t st = comms_awgn_run(h_, in.data(), in.size(), sigma_, c32(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
+struct AwgnOp : protected SameLength {
+    using In = Complex32;
+    using Out = Complex32;
+    AwgnOp(const char* who, float sigma, std::optional<uint64_t> seed, uint64_t stream, int device)
+        : h_(create<NoiseHandle>(who, comms_noise_create, seed ? *seed : entropy_seed(), stream, device)), sigma_(sigma) {}
 
-private:
-    comms_noise_t* h_ = nullptr;
+protected:
+    comms_status_t launch(const Complex32* in, size_t n, Complex32* out) { return comms_awgn_run(h_.get(), in, n, sigma_, c32(out)); }
+    comms_status_t launch_dev(const Complex32* in, size_t n, Complex32* out, void* s) {
+        return comms_awgn_run_dev(h_.get(), in, n, sigma_, c32(out), s);
+    }
+    NoiseHandle h_;
     float sigma_;
+};
+class AwgnNode : public HostNode<AwgnNode, AwgnOp> {
+public:
+    AwgnNode(float sigma, std::optional<uint64_t> seed = std::nullopt, uint64_t stream = 0, int device = 0)
+        : HostNode("AwgnNode::new", sigma, seed, stream, device) {}
+};
+class AwgnNodeDev : public DevNode<AwgnNodeDev, AwgnOp> {
+public:
+    AwgnNodeDev(float sigma, std::optional<uint64_t> seed = std::nullopt, uint64_t stream = 0, int device = 0)
+        : DevNode(device, "AwgnNodeDev::new", sigma, seed, stream, device) {}
 };
 
 // ---------------------------------------------------------------- a digital link from bits to bits (additional nodes)
 // Transmit: packed bits (LSB first, bits_per_sym = 1 or 2 per symbol, whole bytes per message) -> constellation -> pulse
 // shaping -> mixer -> (scale * y) as i16, one launch per message (comms_pulse_set_input_format / _set_output_format).
-class PulseBitsNode : public DeriveNode<PulseBitsNode> {
+class PulseBitsNode : public HostNode<PulseBitsNode, PulseOp<Complex32, uint8_t, Complex16>> {
 public:
-    NodeReceiver<std::vector<uint8_t>> input;
-    NodeSender<std::vector<Complex16>> output;
     PulseBitsNode(const std::vector<Complex32>& taps, size_t sam_per_sym, int bits_per_sym, double dphase, float scale,
                   const std::vector<Complex32>& constellation = {}, int device = 0)
-        : sps_(sam_per_sym), k_(bits_per_sym) {
-        throw_on(comms_pulse_create(c32(taps.data()), taps.size(), sam_per_sym, device, &h_), "PulseBitsNode::new");
-        try {
-            throw_on(comms_pulse_set_mixer(h_, dphase, 0.0), "PulseBitsNode::new");
-            throw_on(comms_pulse_set_input_format(h_, COMMS_SYM_BITS, bits_per_sym, constellation.empty() ? nullptr : c32(constellation.data())),
-                     "PulseBitsNode::new");
-            throw_on(comms_pulse_set_output_format(h_, COMMS_IQ_I16, scale), "PulseBitsNode::new");
-        } catch (...) {
-            comms_pulse_destroy(h_);
-            throw;
-        }
+        : HostNode("PulseBitsNode::new", taps, sam_per_sym, device, bits_per_sym) {
+        throw_on(comms_pulse_set_mixer(h_.get(), dphase, 0.0), "PulseBitsNode::new");
+        throw_on(comms_pulse_set_input_format(h_.get(), COMMS_SYM_BITS, bits_per_sym, constellation.empty() ? nullptr : c32(constellation.data())),
+                 "PulseBitsNode::new");
+        throw_on(comms_pulse_set_output_format(h_.get(), COMMS_IQ_I16, scale), "PulseBitsNode::new");
     }
-    PulseBitsNode(PulseBitsNode&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sps_(o.sps_), k_(o.k_) { o.h_ = nullptr; }
-    ~PulseBitsNode() { comms_pulse_destroy(h_); }
-    Result<std::vector<Complex16>> run(const std::vector<uint8_t>& packed) {
-        const size_t n_sym = packed.size() * 8 / static_cast<size_t>(k_);
-        std::vector<Complex16> out(n_sym * sps_);
-        comms_status_t st = comms_pulse_run(h_, reinterpret_cast<const comms_c32*>(packed.data()), n_sym, c32_as(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
+};
 
-private:
-    static comms_c32* c32_as(Complex16* p) { return reinterpret_cast<comms_c32*>(p); }
-    comms_pulse_t* h_ = nullptr;
-    size_t sps_;
+// mixer / FIR / decimate [/ FM demod] as ONE launch (comms_chain_*; additional nodes, the results of the reference nodes in
+// series).  A message is a whole number of decimation periods.  In: Complex32, or what comms_chain_set_input_format names;
+// Out: Complex32, float with FM demod, or -- bits_per_sym 1 or 2 -- the hard decisions as packed bits, LSB first, each message
+// from bit 0 of its first byte.
+template <class I, class O>
+struct ChainOp {
+    using In = I;
+    using Out = O;
+    ChainOp(const char* who, double dphase, double phase, const std::vector<Complex32>& taps, size_t rate, int32_t flags, int device,
+            int bits_per_sym = 0)
+        : h_(create<decltype(h_)>(who, comms_chain_create_ex, dphase, phase, c32(taps.data()), taps.size(), rate, flags, device)),
+          rate_(rate),
+          k_(bits_per_sym) {}
+    int fused_kind() const {  // 0 four kernels, 1 overlap-save fusion, 2 time-domain decimating kernel, 3 its any-rate form, 4 the polyphase
+                              // frequency-domain kernel (what the last call ran on: rates 4, 8, 12 ... 64)
+        int32_t f = 0;
+        comms_chain_is_fused(h_.get(), &f);
+        return f;
+    }
+
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const {
+        if (rate_ == 0 || n % rate_) return COMMS_ERR_ARG;
+        m = k_ ? (n / rate_ * static_cast<size_t>(k_) + 7) / 8 : n / rate_;
+        return COMMS_OK;
+    }
+    comms_status_t launch(const In* in, size_t n, Out* out) { return comms_chain_run(h_.get(), reinterpret_cast<const comms_c32*>(in), n, out); }
+    comms_status_t launch_dev(const In* in, size_t n, Out* out, void* s) {
+        return comms_chain_run_dev(h_.get(), reinterpret_cast<const comms_c32*>(in), n, out, s);
+    }
+    Owned<comms_chain_t, comms_chain_destroy> h_;
+    size_t rate_;
     int k_;
 };
 
 // Receive: i16 samples -> mixer -> matched FIR -> keep every rate-th -> hard decisions -> packed bits (LSB first), one chain
 // (comms_chain_set_input_format / _set_output_format): ceil(n / rate * bits_per_sym / 8) bytes per message, each message
 // from bit 0 of its first byte -- whole bytes when n is a multiple of 8 * rate / bits_per_sym.
-class ChainBitsNode : public DeriveNode<ChainBitsNode> {
+class ChainBitsNode : public HostNode<ChainBitsNode, ChainOp<Complex16, uint8_t>> {
 public:
-    NodeReceiver<std::vector<Complex16>> input;
-    NodeSender<std::vector<uint8_t>> output;
     ChainBitsNode(double dphase, double phase, const std::vector<Complex32>& taps, size_t rate, int bits_per_sym, float in_scale,
                   const std::vector<Complex32>& constellation = {}, bool mixer_after_fir = false, int device = 0)
-        : rate_(rate), k_(bits_per_sym) {
-        throw_on(comms_chain_create_ex(dphase, phase, c32(taps.data()), taps.size(), rate, mixer_after_fir ? COMMS_CHAIN_MIXER_AFTER_FIR : 0,
-                                       device, &h_),
+        : HostNode("ChainBitsNode::new", dphase, phase, taps, rate, mixer_after_fir ? COMMS_CHAIN_MIXER_AFTER_FIR : 0, device, bits_per_sym) {
+        throw_on(comms_chain_set_input_format(h_.get(), COMMS_IQ_I16, in_scale), "ChainBitsNode::new");
+        throw_on(comms_chain_set_output_format(h_.get(), COMMS_SYM_BITS, bits_per_sym, constellation.empty() ? nullptr : c32(constellation.data())),
                  "ChainBitsNode::new");
-        try {
-            throw_on(comms_chain_set_input_format(h_, COMMS_IQ_I16, in_scale), "ChainBitsNode::new");
-            throw_on(comms_chain_set_output_format(h_, COMMS_SYM_BITS, bits_per_sym, constellation.empty() ? nullptr : c32(constellation.data())),
-                     "ChainBitsNode::new");
-        } catch (...) {
-            comms_chain_destroy(h_);
-            throw;
-        }
     }
-    ChainBitsNode(ChainBitsNode&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), rate_(o.rate_), k_(o.k_) { o.h_ = nullptr; }
-    ~ChainBitsNode() { comms_chain_destroy(h_); }
-    Result<std::vector<uint8_t>> run(const std::vector<Complex16>& in) {
-        if (rate_ == 0 || in.size() % rate_) return NodeError::DataError;
-        std::vector<uint8_t> out((in.size() / rate_ * static_cast<size_t>(k_) + 7) / 8);
-        comms_status_t st = comms_chain_run(h_, reinterpret_cast<const comms_c32*>(in.data()), in.size(), out.data());
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    int fused_kind() const {  // as ChainNodeDev::fused_kind
-        int32_t f = 0;
-        comms_chain_is_fused(h_, &f);
-        return f;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_chain_t* h_ = nullptr;
-    size_t rate_;
-    int k_;
 };
 
 // Real FIR + decimator over an f32 stream as ONE node (comms_rfir_*; an additional node): the results of the audio stage of
 // examples/fm_radio.rs:98-164 -- Convert2Node -> BatchFirNode<f32> -> Convert3Node -> DecimateNode<f32>(rate) -- for real
 // taps.  Any message length: ceil(n / rate) outputs, the decimator restarting with every message as DecimateNode does.
-class RealFirDecimNode : public DeriveNode<RealFirDecimNode> {
-public:
-    NodeReceiver<std::vector<float>> input;
-    NodeSender<std::vector<float>> output;
-    RealFirDecimNode(const std::vector<float>& taps, size_t rate, const std::optional<std::vector<float>>& state = std::nullopt,
-                     int device = 0)
-        : rate_(rate) {
-        throw_on(comms_rfir_create(taps.data(), taps.size(), state ? state->data() : nullptr, state ? state->size() : 0, rate,
-                                   device, &h_),
-                 "RealFirDecimNode::new");
-    }
-    RealFirDecimNode(RealFirDecimNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), rate_(o.rate_) { o.h_ = nullptr; }
-    ~RealFirDecimNode() { comms_rfir_destroy(h_); }
-    Result<std::vector<float>> run(const std::vector<float>& in) {
-        size_t m = 0;
-        comms_rfir_out_len(in.size(), rate_, &m);
-        std::vector<float> out(m);
-        comms_status_t st = comms_rfir_run(h_, in.data(), in.size(), out.data());
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    std::string kernel(size_t n) const {  // "rfir_decim_kernel<..>", or "series: ..." (the four launches)
-        char name[160] = {0};
-        comms_rfir_get_kernel(h_, n, name, sizeof name);
-        return name;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
+struct RealFirDecimOp {
+    using In = float;
+    using Out = float;
+    RealFirDecimOp(const char* who, const std::vector<float>& taps, size_t rate, const std::optional<std::vector<float>>& state, int device)
+        : h_(create<decltype(h_)>(who, comms_rfir_create, taps.data(), taps.size(), state ? state->data() : nullptr,
+                                  state ? state->size() : 0, rate, device)),
+          rate_(rate) {}
+    std::string kernel(size_t n) const { return kernel_name(comms_rfir_get_kernel, h_.get(), n); }  // "rfir_decim_kernel<..>", or the four launches
 
-private:
-    comms_rfir_t* h_ = nullptr;
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const { return comms_rfir_out_len(n, rate_, &m); }
+    comms_status_t launch(const float* in, size_t n, float* out) { return comms_rfir_run(h_.get(), in, n, out); }
+    comms_status_t launch_dev(const float* in, size_t n, float* out, void* s) { return comms_rfir_run_dev(h_.get(), in, n, out, s); }
+    Owned<comms_rfir_t, comms_rfir_destroy> h_;
     size_t rate_;
+};
+class RealFirDecimNode : public HostNode<RealFirDecimNode, RealFirDecimOp> {
+public:
+    RealFirDecimNode(const std::vector<float>& taps, size_t rate, const std::optional<std::vector<float>>& state = std::nullopt, int device = 0)
+        : HostNode("RealFirDecimNode::new", taps, rate, state, device) {}
+};
+// on device-resident messages: the angles a ChainNodeDev<float> sends never leave the device
+class RealFirDecimNodeDev : public DevNode<RealFirDecimNodeDev, RealFirDecimOp> {
+public:
+    RealFirDecimNodeDev(const std::vector<float>& taps, size_t rate, const std::optional<std::vector<float>>& state = std::nullopt, int device = 0)
+        : DevNode(device, "RealFirDecimNodeDev::new", taps, rate, state, device) {}
 };
 
 // Rational resampler by up / down as ONE node (comms_resample_*; an additional node): the results of
@@ -658,34 +792,33 @@ struct ResampleElem<Complex32> {
 };
 
 template <class T>
-class ResampleNode : public DeriveNode<ResampleNode<T>> {
-public:
-    NodeReceiver<std::vector<T>> input;
-    NodeSender<std::vector<T>> output;
-    ResampleNode(const std::vector<float>& taps, size_t up, size_t down, int device = 0) : up_(up), down_(down) {
-        throw_on(comms_resample_create(taps.data(), taps.size(), up, down, ResampleElem<T>::value, device, &h_), "ResampleNode::new");
-    }
-    ResampleNode(ResampleNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), up_(o.up_), down_(o.down_) { o.h_ = nullptr; }
-    ~ResampleNode() { comms_resample_destroy(h_); }
-    Result<std::vector<T>> run(const std::vector<T>& in) {
-        size_t m = 0;
-        if (comms_resample_out_len(in.size(), up_, down_, &m) != COMMS_OK) return NodeError::DataError;
-        std::vector<T> out(m);
-        comms_status_t st = comms_resample_run(h_, in.data(), in.size(), out.data());
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    std::string kernel(size_t n) const {  // "resample_kernel<..> ...", or "series: ..." (the launches)
-        char name[200] = {0};
-        comms_resample_get_kernel(h_, n, name, sizeof name);
-        return name;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
+struct ResampleOp {
+    using In = T;
+    using Out = T;
+    ResampleOp(const char* who, const std::vector<float>& taps, size_t up, size_t down, int device)
+        : h_(create<decltype(h_)>(who, comms_resample_create, taps.data(), taps.size(), up, down, ResampleElem<T>::value, device)),
+          up_(up),
+          down_(down) {}
+    std::string kernel(size_t n) const { return kernel_name(comms_resample_get_kernel, h_.get(), n); }  // "resample_kernel<..> ...", or the launches
 
-private:
-    comms_resample_t* h_ = nullptr;
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const { return comms_resample_out_len(n, up_, down_, &m); }
+    comms_status_t launch(const T* in, size_t n, T* out) { return comms_resample_run(h_.get(), in, n, out); }
+    comms_status_t launch_dev(const T* in, size_t n, T* out, void* s) { return comms_resample_run_dev(h_.get(), in, n, out, s); }
+    Owned<comms_resample_t, comms_resample_destroy> h_;
     size_t up_, down_;
+};
+template <class T>
+class ResampleNode : public HostNode<ResampleNode<T>, ResampleOp<T>> {
+public:
+    ResampleNode(const std::vector<float>& taps, size_t up, size_t down, int device = 0)
+        : ResampleNode::HostNode("ResampleNode::new", taps, up, down, device) {}
+};
+template <class T>
+class ResampleNodeDev : public DevNode<ResampleNodeDev<T>, ResampleOp<T>> {
+public:
+    ResampleNodeDev(const std::vector<float>& taps, size_t up, size_t down, int device = 0)
+        : ResampleNodeDev::DevNode(device, "ResampleNodeDev::new", taps, up, down, device) {}
 };
 
 // Polyphase channelizer as ONE node (comms_channelizer_*; an additional node): the results of M chains
@@ -693,39 +826,39 @@ private:
 // length: ceil(n / down) frames.  One sender carries a message's frames x M outputs in the node's layout
 // (COMMS_CHANNELIZER_CHANNEL_MAJOR: channel k is out[k frames .. (k + 1) frames)); connect it to as many receivers as there
 // are consumers.
-class ChannelizerNode : public DeriveNode<ChannelizerNode> {
-public:
-    NodeReceiver<std::vector<Complex32>> input;
-    NodeSender<std::vector<Complex32>> output;
-    ChannelizerNode(const std::vector<float>& taps, size_t channels, size_t down, int32_t layout = COMMS_CHANNELIZER_CHANNEL_MAJOR, int device = 0)
-        : channels_(channels), down_(down) {
-        throw_on(comms_channelizer_create(taps.data(), taps.size(), channels, down, layout, device, &h_), "ChannelizerNode::new");
-    }
-    ChannelizerNode(ChannelizerNode&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), channels_(o.channels_), down_(o.down_) {
-        o.h_ = nullptr;
-    }
-    ~ChannelizerNode() { comms_channelizer_destroy(h_); }
-    Result<std::vector<Complex32>> run(const std::vector<Complex32>& in) {
-        size_t frames = 0;
-        if (comms_channelizer_out_len(in.size(), down_, &frames) != COMMS_OK) return NodeError::DataError;
-        std::vector<Complex32> out(frames * channels_);
-        comms_status_t st = comms_channelizer_run(h_, reinterpret_cast<const comms_c32*>(in.data()), in.size(), reinterpret_cast<comms_c32*>(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
+struct ChannelizerOp {
+    using In = Complex32;
+    using Out = Complex32;
+    ChannelizerOp(const char* who, const std::vector<float>& taps, size_t channels, size_t down, int32_t layout, int device)
+        : h_(create<decltype(h_)>(who, comms_channelizer_create, taps.data(), taps.size(), channels, down, layout, device)),
+          channels_(channels),
+          down_(down) {}
     size_t channels() const { return channels_; }
-    std::string kernel(size_t n) const {  // "channelizer_kernel<..> ...", or "series: ..." (the launches)
-        char name[240] = {0};
-        comms_channelizer_get_kernel(h_, n, name, sizeof name);
-        return name;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
+    std::string kernel(size_t n) const { return kernel_name(comms_channelizer_get_kernel, h_.get(), n); }  // "channelizer_kernel<..> ...", or the launches
 
-private:
-    comms_channelizer_t* h_ = nullptr;
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const {
+        comms_status_t st = comms_channelizer_out_len(n, down_, &m);  // frames
+        m *= channels_;
+        return st;
+    }
+    comms_status_t launch(const Complex32* in, size_t n, Complex32* out) { return comms_channelizer_run(h_.get(), c32(in), n, c32(out)); }
+    comms_status_t launch_dev(const Complex32* in, size_t n, Complex32* out, void* s) {
+        return comms_channelizer_run_dev(h_.get(), c32(in), n, c32(out), s);
+    }
+    Owned<comms_channelizer_t, comms_channelizer_destroy> h_;
     size_t channels_, down_;
+};
+class ChannelizerNode : public HostNode<ChannelizerNode, ChannelizerOp> {
+public:
+    ChannelizerNode(const std::vector<float>& taps, size_t channels, size_t down, int32_t layout = COMMS_CHANNELIZER_CHANNEL_MAJOR, int device = 0)
+        : HostNode("ChannelizerNode::new", taps, channels, down, layout, device) {}
+};
+// on device-resident messages: channel k of a channel-major message is a contiguous device stream
+class ChannelizerNodeDev : public DevNode<ChannelizerNodeDev, ChannelizerOp> {
+public:
+    ChannelizerNodeDev(const std::vector<float>& taps, size_t channels, size_t down, int32_t layout = COMMS_CHANNELIZER_CHANNEL_MAJOR, int device = 0)
+        : DevNode(device, "ChannelizerNodeDev::new", taps, channels, down, layout, device) {}
 };
 
 // Symbol synchroniser as ONE node (comms_symsync_*; an additional node): matched filter with a fractional delay, symbol-rate
@@ -740,109 +873,86 @@ struct SymbolSyncUpdate {
     double tau;    // comms_symsync_set_timing: the sampling instant in input samples
     double phase;  // comms_symsync_set_rotation(dphase, phase): rotor phase of the next output
 };
-namespace detail {
-class SymbolSyncCore {
-public:
-    SymbolSyncCore(const std::vector<float>& taps, size_t phases, size_t sps, double dphase, int bits_per_sym, int device, const char* who)
-        : sps_(sps < 1 ? 1 : sps), dphase_(dphase), bits_(bits_per_sym) {
-        throw_on(comms_symsync_create(taps.data(), taps.size(), phases, sps, device, &h_), who);
-        comms_status_t st = comms_symsync_set_rotation(h_, dphase, 0.0);
-        if (st == COMMS_OK && bits_) st = comms_symsync_set_output_format(h_, COMMS_SYM_BITS, bits_, nullptr);
-        if (st != COMMS_OK) {
-            comms_symsync_destroy(h_);
-            throw_on(st, who);
-        }
+template <class O>
+struct SymbolSyncOp {
+    static_assert(std::is_same_v<O, Complex32> || std::is_same_v<O, uint8_t>, "symbols (Complex32) or packed bits (uint8_t)");
+    using In = Complex32;
+    using Out = O;
+    NodeReceiver<SymbolSyncUpdate> update;  // optional; host values, drained before each block
+
+    SymbolSyncOp(const char* who, const std::vector<float>& taps, size_t phases, size_t sps, double dphase, int bits_per_sym, int device)
+        : h_(create<decltype(h_)>(who, comms_symsync_create, taps.data(), taps.size(), phases, sps, device)),
+          sps_(sps < 1 ? 1 : sps),
+          dphase_(dphase),
+          bits_(std::is_same_v<O, uint8_t> ? bits_per_sym : 0) {
+        throw_on(comms_symsync_set_rotation(h_.get(), dphase, 0.0), who);
+        if (bits_) throw_on(comms_symsync_set_output_format(h_.get(), COMMS_SYM_BITS, bits_, nullptr), who);
     }
-    SymbolSyncCore(SymbolSyncCore&& o) noexcept : h_(o.h_), sps_(o.sps_), dphase_(o.dphase_), bits_(o.bits_) { o.h_ = nullptr; }
-    ~SymbolSyncCore() { comms_symsync_destroy(h_); }
-    comms_status_t drain(NodeReceiver<SymbolSyncUpdate>& update) {
+    std::string kernel(size_t n) const { return kernel_name(comms_symsync_get_kernel, h_.get(), n); }  // "symsync_kernel<..> ..."
+
+protected:
+    // applies the queued updates; m = the elements of the message's output: symbols, or bytes of packed bits
+    comms_status_t prepare(size_t n, size_t& m) {
         while (update) {
             const std::optional<SymbolSyncUpdate> u = update->try_recv();
             if (!u) break;
             comms_status_t st = COMMS_OK;
-            if (!std::isnan(u->tau)) st = comms_symsync_set_timing(h_, u->tau);
-            if (st == COMMS_OK && !std::isnan(u->phase)) st = comms_symsync_set_rotation(h_, dphase_, u->phase);
+            if (!std::isnan(u->tau)) st = comms_symsync_set_timing(h_.get(), u->tau);
+            if (st == COMMS_OK && !std::isnan(u->phase)) st = comms_symsync_set_rotation(h_.get(), dphase_, u->phase);
             if (st != COMMS_OK) return st;
         }
+        const size_t n_sym = n / sps_;
+        m = bits_ ? (n_sym * static_cast<size_t>(bits_) + 7) / 8 : n_sym;
         return COMMS_OK;
     }
-    // elements of a message's output: symbols, or bytes of packed bits
-    size_t out_len(size_t n) const {
-        const size_t n_sym = n / sps_;
-        return bits_ ? (n_sym * static_cast<size_t>(bits_) + 7) / 8 : n_sym;
-    }
-    comms_symsync_t* h() const { return h_; }
-
-private:
-    comms_symsync_t* h_ = nullptr;
+    comms_status_t launch(const Complex32* in, size_t n, Out* out) { return comms_symsync_run(h_.get(), c32(in), n, out); }
+    comms_status_t launch_dev(const Complex32* in, size_t n, Out* out, void* s) { return comms_symsync_run_dev(h_.get(), c32(in), n, out, s); }
+    Owned<comms_symsync_t, comms_symsync_destroy> h_;
     size_t sps_;
     double dphase_;
     int bits_;
 };
-}  // namespace detail
-
 template <class Out = Complex32>
-class SymbolSyncNode : public DeriveNode<SymbolSyncNode<Out>> {
-    static_assert(std::is_same_v<Out, Complex32> || std::is_same_v<Out, uint8_t>, "symbols (Complex32) or packed bits (uint8_t)");
-
+class SymbolSyncNode : public HostNode<SymbolSyncNode<Out>, SymbolSyncOp<Out>> {
 public:
-    NodeReceiver<std::vector<Complex32>> input;
-    NodeReceiver<SymbolSyncUpdate> update;  // optional; drained before each block
-    NodeSender<std::vector<Out>> output;
     SymbolSyncNode(const std::vector<float>& taps, size_t phases, size_t sps, double dphase = 0.0, int bits_per_sym = 2, int device = 0)
-        : core_(taps, phases, sps, dphase, std::is_same_v<Out, uint8_t> ? bits_per_sym : 0, device, "SymbolSyncNode::new") {}
-    SymbolSyncNode(SymbolSyncNode&&) noexcept = default;
-    Result<std::vector<Out>> run(const std::vector<Complex32>& in) {
-        comms_status_t st = core_.drain(update);
-        if (st != COMMS_OK) return to_node_error(st);
-        std::vector<Out> out(core_.out_len(in.size()));
-        st = comms_symsync_run(core_.h(), reinterpret_cast<const comms_c32*>(in.data()), in.size(), out.data());
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    std::string kernel(size_t n) const {  // "symsync_kernel<..> ..."
-        char name[240] = {0};
-        comms_symsync_get_kernel(core_.h(), n, name, sizeof name);
-        return name;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    detail::SymbolSyncCore core_;
+        : SymbolSyncNode::HostNode("SymbolSyncNode::new", taps, phases, sps, dphase, bits_per_sym, device) {}
+};
+template <class Out = Complex32>
+class SymbolSyncNodeDev : public DevNode<SymbolSyncNodeDev<Out>, SymbolSyncOp<Out>> {
+public:
+    SymbolSyncNodeDev(const std::vector<float>& taps, size_t phases, size_t sps, double dphase = 0.0, int bits_per_sym = 2, int device = 0)
+        : SymbolSyncNodeDev::DevNode(device, "SymbolSyncNodeDev::new", taps, phases, sps, dphase, bits_per_sym, device) {}
 };
 
 // ---------------------------------------------------------------- mixer
-template <class D, class T>
-class MixerNodeOf : public DeriveNode<D> {
-public:
-    NodeReceiver<T> input;
-    NodeSender<T> output;
+template <class T>
+struct MixerOp : protected SameLength {
+    using In = T;
+    using Out = T;
+    MixerOp(const char* who, double dphase, std::optional<double> phase, int device)
+        : h_(create<decltype(h_)>(who, comms_mixer_create, dphase, phase.value_or(0.0), device)) {}
 
+protected:
+    comms_status_t launch(const T* in, size_t n, T* out) { return Sample<T>::mixer_run(h_.get(), abi(in), n, abi(out)); }
+    comms_status_t launch_dev(const T* in, size_t n, T* out, void* s) { return Sample<T>::mixer_run_dev(h_.get(), abi(in), n, abi(out), s); }
+    Owned<comms_mixer_t, comms_mixer_destroy> h_;
+};
+
+template <class D, class T>
+class MixerNodeOf : public DeriveNode<D>, public Ports<T, T>, public MixerOp<T> {
+public:
     // NB (dphase, phase): the node's order, not Mixer::new's (mixer.rs:128 vs :43)
-    explicit MixerNodeOf(double dphase, std::optional<double> phase = std::nullopt, int device = 0) {
-        throw_on(comms_mixer_create(dphase, phase.value_or(0.0), device, &h_), D::kNew);
-    }
-    MixerNodeOf(MixerNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~MixerNodeOf() { comms_mixer_destroy(h_); }
+    explicit MixerNodeOf(double dphase, std::optional<double> phase = std::nullopt, int device = 0) : MixerOp<T>(D::kNew, dphase, phase, device) {}
 
     Result<T> run(const T& in) {
         T out;
-        comms_status_t st = Sample<T>::mixer_run(h_, abi(&in), 1, abi(&out));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
+        return ok_or(this->launch(&in, 1, &out), out);
     }
     Result<std::vector<T>> run_block(const std::vector<T>& ins) {  // see FirNodeOf::run_block
         std::vector<T> out(ins.size());
-        comms_status_t st = Sample<T>::mixer_run(h_, abi(ins.data()), ins.size(), abi(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
+        return ok_or(this->launch(ins.data(), ins.size(), out.data()), out);
     }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_mixer_t* h_ = nullptr;
 };
 
 struct MixerNode : MixerNodeOf<MixerNode, Complex32> {
@@ -856,139 +966,101 @@ struct MixerNode64 : MixerNodeOf<MixerNode64, Complex64> {
 };
 
 // The reference has no batch mixer node; this one mixes a whole Vec per message.
-class BatchMixerNode : public DeriveNode<BatchMixerNode> {
+class BatchMixerNode : public HostNode<BatchMixerNode, MixerOp<Complex32>> {
 public:
-    NodeReceiver<std::vector<Complex32>> input;
-    NodeSender<std::vector<Complex32>> output;
-
-    explicit BatchMixerNode(double dphase, std::optional<double> phase = std::nullopt, int device = 0) {
-        throw_on(comms_mixer_create(dphase, phase.value_or(0.0), device, &h_), "BatchMixerNode::new");
-    }
-    BatchMixerNode(BatchMixerNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~BatchMixerNode() { comms_mixer_destroy(h_); }
-
-    Result<std::vector<Complex32>> run(const std::vector<Complex32>& in) {
-        std::vector<Complex32> out(in.size());
-        comms_status_t st = comms_mixer_run(h_, c32(in.data()), in.size(), c32(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_mixer_t* h_ = nullptr;
+    explicit BatchMixerNode(double dphase, std::optional<double> phase = std::nullopt, int device = 0)
+        : HostNode("BatchMixerNode::new", dphase, phase, device) {}
+};
+class BatchMixerNodeDev : public DevNode<BatchMixerNodeDev, MixerOp<Complex32>> {
+public:
+    explicit BatchMixerNodeDev(double dphase, std::optional<double> phase = std::nullopt, int device = 0)
+        : DevNode(device, "BatchMixerNodeDev::new", dphase, phase, device) {}
 };
 
 // ---------------------------------------------------------------- decimate / upsample (T: Copy)
-template <class T>
-class DecimateNode : public DeriveNode<DecimateNode<T>> {
-public:
-    NodeReceiver<std::vector<T>> input;
-    NodeSender<std::vector<T>> output;
-    explicit DecimateNode(size_t dec_rate, int device = 0) : rate_(dec_rate), device_(device) {}
+// No handle: the rate and the device are all there is.  OutLen / Run / RunDev are the comms_decimate_* or comms_upsample_* entries.
+template <class T, auto OutLen, auto Run, auto RunDev>
+struct RateOp {
+    using In = T;
+    using Out = T;
+    RateOp(const char*, size_t rate, int device) : rate_(rate), device_(device) {}
 
-    Result<std::vector<T>> run(const std::vector<T>& signal) {
-        std::vector<T> out;
-        comms_status_t st = decimate(signal, out);
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const { return OutLen(n, rate_, &m); }
+    comms_status_t launch(const T* in, size_t n, T* out) const { return Run(in, n, sizeof(T), rate_, out, nullptr, device_); }
+    comms_status_t launch_dev(const T* in, size_t n, T* out, void* s) const { return RunDev(in, n, sizeof(T), rate_, out, nullptr, device_, s); }
+    comms_status_t apply(const std::vector<T>& data, std::vector<T>& out) const {
+        size_t m = 0;
+        comms_status_t st = prepare(data.size(), m);
+        if (st != COMMS_OK) return st;
+        out.resize(m);
+        return launch(data.data(), data.size(), out.data());
     }
-    comms_status_t decimate(const std::vector<T>& data, std::vector<T>& out) const {
-        size_t n_out = 0;
-        comms_decimate_out_len(data.size(), rate_, &n_out);
-        out.resize(n_out);
-        return comms_decimate_run(data.data(), data.size(), sizeof(T), rate_, out.data(), nullptr, device_);
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
     size_t rate_;
     int device_;
 };
+template <class T>
+using DecimateOp = RateOp<T, comms_decimate_out_len, comms_decimate_run, comms_decimate_run_dev>;
+template <class T>
+using UpsampleOp = RateOp<T, comms_upsample_out_len, comms_upsample_run, comms_upsample_run_dev>;
 
 template <class T>
-class UpsampleNode : public DeriveNode<UpsampleNode<T>> {
+class DecimateNode : public HostNode<DecimateNode<T>, DecimateOp<T>> {
 public:
-    NodeReceiver<std::vector<T>> input;
-    NodeSender<std::vector<T>> output;
-    explicit UpsampleNode(size_t ups_rate, int device = 0) : rate_(ups_rate), device_(device) {}
-
-    Result<std::vector<T>> run(const std::vector<T>& signal) {
-        std::vector<T> out;
-        comms_status_t st = upsample(signal, out);
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    comms_status_t upsample(const std::vector<T>& data, std::vector<T>& out) const {
-        size_t n_out = 0;
-        comms_status_t st = comms_upsample_out_len(data.size(), rate_, &n_out);
-        if (st != COMMS_OK) return st;
-        out.resize(n_out);
-        return comms_upsample_run(data.data(), data.size(), sizeof(T), rate_, out.data(), nullptr, device_);
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    size_t rate_;
-    int device_;
+    explicit DecimateNode(size_t dec_rate, int device = 0) : DecimateNode::HostNode(nullptr, dec_rate, device) {}
+    comms_status_t decimate(const std::vector<T>& data, std::vector<T>& out) const { return this->apply(data, out); }
+};
+template <class T>
+class UpsampleNode : public HostNode<UpsampleNode<T>, UpsampleOp<T>> {
+public:
+    explicit UpsampleNode(size_t ups_rate, int device = 0) : UpsampleNode::HostNode(nullptr, ups_rate, device) {}
+    comms_status_t upsample(const std::vector<T>& data, std::vector<T>& out) const { return this->apply(data, out); }
+};
+class DecimateNodeDev : public DevNode<DecimateNodeDev, DecimateOp<Complex32>> {
+public:
+    explicit DecimateNodeDev(size_t dec_rate, int device = 0) : DevNode(device, nullptr, dec_rate, device) {}
+};
+class UpsampleNodeDev : public DevNode<UpsampleNodeDev, UpsampleOp<Complex32>> {
+public:
+    explicit UpsampleNodeDev(size_t ups_rate, int device = 0) : DevNode(device, nullptr, ups_rate, device) {}
 };
 
 // ---------------------------------------------------------------- FM demod
+template <class T>
+struct FmOp : protected SameLength {
+    using In = T;
+    using Out = typename Sample<T>::Real;
+    FmOp(const char* who, int device) : h_(create<decltype(h_)>(who, Sample<T>::fm_create, device)) {}
+
+protected:
+    comms_status_t launch(const T* in, size_t n, Out* out) { return Sample<T>::fm_run(h_.get(), abi(in), n, out); }
+    comms_status_t launch_dev(const T* in, size_t n, Out* out, void* s) { return Sample<T>::fm_run_dev(h_.get(), abi(in), n, out, s); }
+    Owned<typename Sample<T>::Fm, Sample<T>::fm_destroy> h_;
+};
 template <class D, class T>
-class FMDemodNodeOf : public DeriveNode<D> {
-    using S = Sample<T>;
-
+class FMDemodNodeOf : public HostNode<D, FmOp<T>> {
 public:
-    NodeReceiver<std::vector<T>> input;
-    NodeSender<std::vector<typename S::Real>> output;
-
-    explicit FMDemodNodeOf(int device = 0) { throw_on(S::fm_create(device, &h_), D::kNew); }
-    FMDemodNodeOf(FMDemodNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FMDemodNodeOf() { S::fm_destroy(h_); }
-
-    Result<std::vector<typename S::Real>> run(const std::vector<T>& samples) {
-        std::vector<typename S::Real> out(samples.size());
-        comms_status_t st = S::fm_run(h_, abi(samples.data()), samples.size(), out.data());
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    typename S::Fm* h_ = nullptr;
+    explicit FMDemodNodeOf(int device = 0) : FMDemodNodeOf::HostNode(D::kNew, device) {}
 };
 
 // ---------------------------------------------------------------- FFT
+// the message may hold any whole number of transforms (the reference: exactly one); a wrong length panics inside rustfft in
+// the reference, here it is DataError
+template <class T>
+struct FftOp : protected SameLength {
+    using In = T;
+    using Out = T;
+    FftOp(const char* who, size_t fft_size, bool ifft, int device) : h_(create<decltype(h_)>(who, Sample<T>::fft_create, fft_size, ifft ? 1 : 0, device)) {}
+
+protected:
+    comms_status_t launch(const T* in, size_t n, T* out) { return Sample<T>::fft_run(h_.get(), abi(in), n, abi(out)); }
+    comms_status_t launch_dev(const T* in, size_t n, T* out, void* s) { return Sample<T>::fft_run_dev(h_.get(), abi(in), n, abi(out), s); }
+    Owned<typename Sample<T>::Fft, Sample<T>::fft_destroy> h_;
+};
 template <class D, class T>
-class FFTBatchNodeOf : public DeriveNode<D> {
-    using S = Sample<T>;
-
+class FFTBatchNodeOf : public HostNode<D, FftOp<T>> {
 public:
-    NodeReceiver<std::vector<T>> input;
-    NodeSender<std::vector<T>> output;
-
-    FFTBatchNodeOf(size_t fft_size, bool ifft, int device = 0) {
-        throw_on(S::fft_create(fft_size, ifft ? 1 : 0, device, &h_), D::kNew);
-    }
-    FFTBatchNodeOf(FFTBatchNodeOf&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~FFTBatchNodeOf() { S::fft_destroy(h_); }
-
-    Result<std::vector<T>> run(const std::vector<T>& data) {
-        std::vector<T> out(data.size());
-        // a wrong length panics inside rustfft in the reference; here it is DataError
-        comms_status_t st = S::fft_run(h_, abi(data.data()), data.size(), abi(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    typename S::Fft* h_ = nullptr;
+    FFTBatchNodeOf(size_t fft_size, bool ifft, int device = 0) : FFTBatchNodeOf::HostNode(D::kNew, fft_size, ifft, device) {}
 };
 
 struct FMDemodNode : FMDemodNodeOf<FMDemodNode, Complex32> {
@@ -1009,27 +1081,25 @@ struct FMDemodNodeF64 : FMDemodNodeOf<FMDemodNodeF64, Complex64> {
     using FMDemodNodeOf::FMDemodNodeOf;
     static constexpr const char* kNew = "FMDemodNode<f64>::new";
 };
+class FFTBatchNodeDev : public DevNode<FFTBatchNodeDev, FftOp<Complex32>> {
+public:
+    FFTBatchNodeDev(size_t fft_size, bool ifft, int device = 0) : DevNode(device, "FFTBatchNodeDev::new", fft_size, ifft, device) {}
+};
+class FMDemodNodeDev : public DevNode<FMDemodNodeDev, FmOp<Complex32>> {
+public:
+    explicit FMDemodNodeDev(int device = 0) : DevNode(device, "FMDemodNodeDev::new", device) {}
+};
 
 // #[aggregate]: run returns Some(vec) every fft_size pushes, None otherwise
-class FFTSampleNode : public DeriveNode<FFTSampleNode> {
+class FFTSampleNode : public DeriveNode<FFTSampleNode>, public Ports<Complex32, std::vector<Complex32>>, public FftOp<Complex32> {
 public:
-    NodeReceiver<Complex32> input;
-    NodeSender<std::vector<Complex32>> output;
-
-    FFTSampleNode(size_t fft_size, bool ifft, int device = 0) : n_(fft_size) {
-        throw_on(comms_fft_create(fft_size, ifft ? 1 : 0, device, &h_), "FFTSampleNode::new");
-    }
-    FFTSampleNode(FFTSampleNode&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), n_(o.n_), samples_(std::move(o.samples_)) {
-        o.h_ = nullptr;
-    }
-    ~FFTSampleNode() { comms_fft_destroy(h_); }
+    FFTSampleNode(size_t fft_size, bool ifft, int device = 0) : FftOp("FFTSampleNode::new", fft_size, ifft, device), n_(fft_size) {}
 
     Result<std::optional<std::vector<Complex32>>> run(const Complex32& sample) {
         samples_.push_back(sample);
         if (samples_.size() != n_) return std::optional<std::vector<Complex32>>(std::nullopt);
         std::vector<Complex32> out(n_);
-        comms_status_t st = comms_fft_run(h_, c32(samples_.data()), n_, c32(out.data()));
+        comms_status_t st = launch(samples_.data(), n_, out.data());
         samples_.clear();
         if (st != COMMS_OK) return to_node_error(st);
         return std::optional<std::vector<Complex32>>(std::move(out));
@@ -1042,18 +1112,15 @@ public:
         std::vector<std::vector<Complex32>> outs;
         if (!k) return outs;
         std::vector<Complex32> flat(k * n_);
-        comms_status_t st = comms_fft_run(h_, c32(samples_.data()), k * n_, c32(flat.data()));
+        comms_status_t st = launch(samples_.data(), k * n_, flat.data());
         samples_.erase(samples_.begin(), samples_.begin() + k * n_);
         if (st != COMMS_OK) return to_node_error(st);
         outs.resize(k);
         for (size_t i = 0; i < k; ++i) outs[i].assign(flat.begin() + i * n_, flat.begin() + (i + 1) * n_);
         return outs;
     }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
 
 private:
-    comms_fft_t* h_ = nullptr;
     size_t n_;
     std::vector<Complex32> samples_;
 };
@@ -1081,8 +1148,6 @@ inline std::vector<Complex32> rect_taps(size_t n_taps) {
 }
 
 // ---------------------------------------------------------------- demodulation
-using Complex64 = std::complex<double>;
-
 // TimingEstimatorNode::new(n, d, alpha) -> Result<Self, MathError>; run(&[Complex<f64>]) -> f64
 // (src/demodulation/timing_estimator.rs:116-136).  A bad alpha throws (the reference returns Err).
 class TimingEstimatorNode : public DeriveNode<TimingEstimatorNode> {
@@ -1090,24 +1155,18 @@ public:
     NodeReceiver<std::vector<Complex64>> input;
     NodeSender<double> output;
 
-    TimingEstimatorNode(uint32_t n, uint32_t d, double alpha, int device = 0) {
-        throw_on(comms_timing_create(n, d, alpha, device, &h_), "TimingEstimatorNode::new");
-    }
-    TimingEstimatorNode(TimingEstimatorNode&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~TimingEstimatorNode() { comms_timing_destroy(h_); }
+    TimingEstimatorNode(uint32_t n, uint32_t d, double alpha, int device = 0)
+        : h_(create<decltype(h_)>("TimingEstimatorNode::new", comms_timing_create, n, d, alpha, device)) {}
 
     Result<double> run(const std::vector<Complex64>& samples) {
         double est = 0.0;
-        comms_status_t st = comms_timing_push(h_, reinterpret_cast<const double*>(samples.data()), samples.size(), &est);
-        if (st != COMMS_OK) return to_node_error(st);
-        return est;
+        return ok_or(comms_timing_push(h_.get(), reinterpret_cast<const double*>(samples.data()), samples.size(), &est), est);
     }
     auto receivers() { return std::tie(input); }
     auto senders() { return std::tie(output); }
 
 private:
-    comms_timing_t* h_ = nullptr;
+    Owned<comms_timing_t, comms_timing_destroy> h_;
 };
 
 // Timing and frequency estimates of a Complex<f32> block from one read of it (comms_syncest_*; an additional node):
@@ -1115,147 +1174,141 @@ private:
 // `output` carries the whole comms_sync_estimate_t, `update` the SymbolSyncUpdate{tau, NaN} that puts a SymbolSyncNode of
 // (n_taps, phases) -- its sps = n -- on the symbol centres: tau = timing + (n_taps - 1) / (2 phases) (mod n); the NaN leaves
 // the synchroniser's phase alone.  `update` plugs straight into SymbolSyncNode::update.
+// The output is a host value on either message kind (the call synchronises its stream), so the two nodes have run() bodies
+// of their own over the description.
 struct SyncEstimate {
     comms_sync_estimate_t estimate;
     SymbolSyncUpdate update;
     operator comms_sync_estimate_t() const { return estimate; }
     operator SymbolSyncUpdate() const { return update; }
 };
-namespace detail {
-class SyncEstimatorCore {
-public:
-    SyncEstimatorCore(uint32_t n, uint32_t d, double alpha, size_t n_taps, size_t phases, int device, const char* who)
-        : n_(n), delay_(n_taps ? static_cast<double>(n_taps - 1) / (2.0 * static_cast<double>(phases < 1 ? 1 : phases)) : 0.0) {
-        throw_on(comms_syncest_create(n, d, alpha, device, &h_), who);
+struct SyncEstimatorOp {
+    SyncEstimatorOp(const char* who, uint32_t n, uint32_t d, double alpha, size_t n_taps, size_t phases, int device)
+        : h_(create<decltype(h_)>(who, comms_syncest_create, n, d, alpha, device)),
+          n_(n),
+          delay_(n_taps ? static_cast<double>(n_taps - 1) / (2.0 * static_cast<double>(phases < 1 ? 1 : phases)) : 0.0) {}
+    std::string kernel(size_t n) const { return kernel_name(comms_syncest_get_kernel, h_.get(), n); }  // "syncest_kernel ..."
+
+protected:
+    Result<SyncEstimate> estimate(const Complex32* in, size_t n) {
+        comms_sync_estimate_t e{};
+        return message(comms_syncest_run(h_.get(), c32(in), n, &e), e);
     }
-    SyncEstimatorCore(SyncEstimatorCore&& o) noexcept : h_(o.h_), n_(o.n_), delay_(o.delay_) { o.h_ = nullptr; }
-    ~SyncEstimatorCore() { comms_syncest_destroy(h_); }
-    SyncEstimate message(const comms_sync_estimate_t& e) const {
+    Result<SyncEstimate> estimate_dev(const Complex32* in, size_t n, void* s) {
+        comms_sync_estimate_t e{};
+        return message(comms_syncest_run_dev(h_.get(), c32(in), n, &e, s), e);
+    }
+
+private:
+    Result<SyncEstimate> message(comms_status_t st, const comms_sync_estimate_t& e) const {
+        if (st != COMMS_OK) return to_node_error(st);
         double tau = std::fmod(e.timing + delay_, static_cast<double>(n_));
         if (tau < 0) tau += static_cast<double>(n_);
         return SyncEstimate{e, SymbolSyncUpdate{tau, std::numeric_limits<double>::quiet_NaN()}};
     }
-    comms_syncest_t* h() const { return h_; }
-
-private:
-    comms_syncest_t* h_ = nullptr;
+    Owned<comms_syncest_t, comms_syncest_destroy> h_;
     uint32_t n_;
     double delay_;
 };
-}  // namespace detail
 
-class SyncEstimatorNode : public DeriveNode<SyncEstimatorNode> {
-public:
-    NodeReceiver<std::vector<Complex32>> input;
+template <class In>
+struct SyncEstimatorPorts {  // as Ports, with the second sender
+    NodeReceiver<In> input;
     NodeSender<comms_sync_estimate_t> output;
     NodeSender<SymbolSyncUpdate> update;
-    SyncEstimatorNode(uint32_t n, uint32_t d, double alpha, size_t n_taps, size_t phases, int device = 0)
-        : core_(n, d, alpha, n_taps, phases, device, "SyncEstimatorNode::new") {}
-    SyncEstimatorNode(SyncEstimatorNode&&) noexcept = default;
-    Result<SyncEstimate> run(const std::vector<Complex32>& samples) {
-        comms_sync_estimate_t e{};
-        comms_status_t st = comms_syncest_run(core_.h(), reinterpret_cast<const comms_c32*>(samples.data()), samples.size(), &e);
-        if (st != COMMS_OK) return to_node_error(st);
-        return core_.message(e);
-    }
-    std::string kernel(size_t n) const {  // "syncest_kernel ..."
-        char name[240] = {0};
-        comms_syncest_get_kernel(core_.h(), n, name, sizeof name);
-        return name;
-    }
     auto receivers() { return std::tie(input); }
     auto senders() { return std::tie(output, update); }
-
-private:
-    detail::SyncEstimatorCore core_;
+};
+class SyncEstimatorNode : public DeriveNode<SyncEstimatorNode>, public SyncEstimatorPorts<std::vector<Complex32>>, public SyncEstimatorOp {
+public:
+    SyncEstimatorNode(uint32_t n, uint32_t d, double alpha, size_t n_taps, size_t phases, int device = 0)
+        : SyncEstimatorOp("SyncEstimatorNode::new", n, d, alpha, n_taps, phases, device) {}
+    Result<SyncEstimate> run(const std::vector<Complex32>& samples) { return estimate(samples.data(), samples.size()); }
+};
+class SyncEstimatorNodeDev : public DeriveNode<SyncEstimatorNodeDev>, public SyncEstimatorPorts<DeviceBuf<Complex32>>, public OnStream<SyncEstimatorOp> {
+public:
+    SyncEstimatorNodeDev(uint32_t n, uint32_t d, double alpha, size_t n_taps, size_t phases, int device = 0)
+        : OnStream(device, "SyncEstimatorNodeDev::new", n, d, alpha, n_taps, phases, device) {}
+    Result<SyncEstimate> run(const DeviceBuf<Complex32>& in) {
+        comms_status_t st = wait(in);
+        if (st != COMMS_OK) return to_node_error(st);
+        return estimate_dev(in.ptr(), in.size(), get());
+    }
 };
 
 // Frame synchroniser (comms_framesync_*; an additional node): takes SymbolSyncNode<Complex32>'s symbol output and sends, per
 // block, the detections of a known word that the block decides -- possibly none -- as a vector ordered by stream index.
 // index + word.size() is the first payload symbol, atan2(corr_im, corr_re) the rotation to take out.  A block of n symbols
 // decides n positions, so a word is reported by the block that brings the last symbol of its guard window; flush() ends a
-// stream.  The detections do not depend on how the stream is cut into blocks.
-namespace detail {
-class FrameSyncCore {
-public:
-    FrameSyncCore(const std::vector<Complex32>& word, double threshold, size_t guard, int device, const char* who)
-        : n_word_(word.size()), guard_(guard) {
-        throw_on(comms_framesync_create(reinterpret_cast<const comms_c32*>(word.data()), word.size(), threshold, guard, device, &h_), who);
+// stream.  The detections do not depend on how the stream is cut into blocks.  They are host values on either message kind
+// (the call synchronises its stream): run() bodies of their own, as the estimator's.
+struct FrameSyncOp {
+    using Detections = std::vector<comms_frame_detection_t>;
+    FrameSyncOp(const char* who, const std::vector<Complex32>& word, double threshold, size_t guard, int device)
+        : h_(create<decltype(h_)>(who, comms_framesync_create, c32(word.data()), word.size(), threshold, guard, device)),
+          n_word_(word.size()),
+          guard_(guard) {}
+    Result<Detections> flush() {  // a flush decides word + guard positions
+        return collect(n_word_ + guard_, [&](auto* out, size_t cap, size_t* found) { return comms_framesync_flush(h_.get(), out, cap, found); });
     }
-    FrameSyncCore(FrameSyncCore&& o) noexcept : h_(o.h_), n_word_(o.n_word_), guard_(o.guard_) { o.h_ = nullptr; }
-    ~FrameSyncCore() { comms_framesync_destroy(h_); }
-    // no call on n symbols has more detections: they are more than `guard` apart
-    size_t bound(size_t n) const { return (n + guard_) / (guard_ + 1); }
-    Result<std::vector<comms_frame_detection_t>> flush() {
+    std::string kernel(size_t n) const { return kernel_name(comms_framesync_get_kernel, h_.get(), n); }  // "framesync_kernel ..."
+
+protected:
+    Result<Detections> detect(const Complex32* in, size_t n) {
+        return collect(n, [&](auto* out, size_t cap, size_t* found) { return comms_framesync_run(h_.get(), c32(in), n, out, cap, found); });
+    }
+    Result<Detections> detect_dev(const Complex32* in, size_t n, void* s) {
+        return collect(n, [&](auto* out, size_t cap, size_t* found) { return comms_framesync_run_dev(h_.get(), c32(in), n, out, cap, found, s); });
+    }
+
+private:
+    // no call that decides n positions has more than (n + guard) / (guard + 1) detections: they are more than `guard` apart
+    template <class F>
+    Result<Detections> collect(size_t n, F&& call) {
+        Detections out((n + guard_) / (guard_ + 1));
         size_t found = 0;
-        std::vector<comms_frame_detection_t> out(bound(n_word_ + guard_));  // a flush decides word + guard positions
-        comms_status_t st = comms_framesync_flush(h_, out.data(), out.size(), &found);
+        comms_status_t st = call(out.data(), out.size(), &found);
         if (st != COMMS_OK) return to_node_error(st);
         out.resize(found);
         return out;
     }
-    comms_framesync_t* h() const { return h_; }
-
-private:
-    comms_framesync_t* h_ = nullptr;
+    Owned<comms_framesync_t, comms_framesync_destroy> h_;
     size_t n_word_, guard_;
 };
-}  // namespace detail
 
-class FrameSyncNode : public DeriveNode<FrameSyncNode> {
+class FrameSyncNode : public DeriveNode<FrameSyncNode>, public Ports<std::vector<Complex32>, FrameSyncOp::Detections>, public FrameSyncOp {
 public:
-    NodeReceiver<std::vector<Complex32>> input;
-    NodeSender<std::vector<comms_frame_detection_t>> output;
     FrameSyncNode(const std::vector<Complex32>& word, double threshold, size_t guard, int device = 0)
-        : core_(word, threshold, guard, device, "FrameSyncNode::new") {}
-    FrameSyncNode(FrameSyncNode&&) noexcept = default;
-    Result<std::vector<comms_frame_detection_t>> run(const std::vector<Complex32>& symbols) {
-        std::vector<comms_frame_detection_t> out(core_.bound(symbols.size()));
-        size_t found = 0;
-        comms_status_t st = comms_framesync_run(core_.h(), reinterpret_cast<const comms_c32*>(symbols.data()), symbols.size(), out.data(),
-                                                out.size(), &found);
+        : FrameSyncOp("FrameSyncNode::new", word, threshold, guard, device) {}
+    Result<Detections> run(const std::vector<Complex32>& symbols) { return detect(symbols.data(), symbols.size()); }
+};
+// on device-resident messages: SymbolSyncNodeDev<Complex32>'s output
+class FrameSyncNodeDev : public DeriveNode<FrameSyncNodeDev>, public Ports<DeviceBuf<Complex32>, FrameSyncOp::Detections>, public OnStream<FrameSyncOp> {
+public:
+    FrameSyncNodeDev(const std::vector<Complex32>& word, double threshold, size_t guard, int device = 0)
+        : OnStream(device, "FrameSyncNodeDev::new", word, threshold, guard, device) {}
+    Result<Detections> run(const DeviceBuf<Complex32>& in) {
+        comms_status_t st = wait(in);
         if (st != COMMS_OK) return to_node_error(st);
-        out.resize(found);
-        return out;
+        return detect_dev(in.ptr(), in.size(), get());
     }
-    Result<std::vector<comms_frame_detection_t>> flush() { return core_.flush(); }
-    std::string kernel(size_t n) const {  // "framesync_kernel ..."
-        char name[240] = {0};
-        comms_framesync_get_kernel(core_.h(), n, name, sizeof name);
-        return name;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    detail::FrameSyncCore core_;
 };
 
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)
-class BatchNcoNode : public DeriveNode<BatchNcoNode> {
+struct NcoOp : protected SameLength {
+    using In = double;
+    using Out = Complex64;
+    NcoOp(const char* who, double dphase, double phase, int device) : h_(create<decltype(h_)>(who, comms_nco_create, dphase, phase, device)) {}
+
+protected:
+    comms_status_t launch(const double* perr, size_t n, Complex64* out) { return comms_nco_run(h_.get(), perr, n, reinterpret_cast<double*>(out)); }
+    Owned<comms_nco_t, comms_nco_destroy> h_;
+};
+class BatchNcoNode : public HostNode<BatchNcoNode, NcoOp> {
 public:
-    NodeReceiver<std::vector<double>> input;
-    NodeSender<std::vector<Complex64>> output;
-
-    explicit BatchNcoNode(double dphase, double phase = 0.0, int device = 0) {
-        throw_on(comms_nco_create(dphase, phase, device, &h_), "NcoNode::new");
-    }
-    BatchNcoNode(BatchNcoNode&& o) noexcept : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_) { o.h_ = nullptr; }
-    ~BatchNcoNode() { comms_nco_destroy(h_); }
-
-    Result<std::vector<Complex64>> run(const std::vector<double>& perr) {
-        std::vector<Complex64> out(perr.size());
-        comms_status_t st = comms_nco_run(h_, perr.data(), perr.size(), reinterpret_cast<double*>(out.data()));
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_nco_t* h_ = nullptr;
+    explicit BatchNcoNode(double dphase, double phase = 0.0, int device = 0) : HostNode("NcoNode::new", dphase, phase, device) {}
 };
 
 inline std::vector<double> qfilt_taps(uint32_t n_taps, double alpha, uint32_t sam_per_sym) {
@@ -1263,231 +1316,6 @@ inline std::vector<double> qfilt_taps(uint32_t n_taps, double alpha, uint32_t sa
     throw_on(comms_qfilt_taps(n_taps, alpha, sam_per_sym, t.data()), "qfilt_taps");
     return t;
 }
-
-// ---------------------------------------------------------------- device-resident nodes
-// Messages are DeviceBuf<T>: nothing crosses PCIe between nodes and nothing ever synchronises
-// the device.  Every node owns a stream (DevStream); run() is
-//     wait_ready(in)  ->  one asynchronous launch on the node's stream  ->  record_use(in),
-//     record_ready(out)  ->  send(out)
-// so the consumer's stream starts its own launch only after the producer's has finished, while the
-// node threads themselves run ahead of the device.  An edge stays on ONE GPU: the buffer's events
-// belong to its device and the kernels read it directly, so a message whose device is not the node's is a
-// DataError (COMMS_ERR_ARG) -- between GPUs the host copies or sends the samples itself (sharding, above).  Output
-// buffers come from the library's cache (no hipMalloc / hipFree in steady state); a buffer's
-// memory is recycled only after the launches that read it.  to_host() waits for the producer.
-class DevStream {
-public:
-    explicit DevStream(int device) : device_(device) { throw_on(comms_stream_create(device, &s_), "comms_stream_create"); }
-    DevStream(DevStream&& o) noexcept : s_(o.s_), device_(o.device_) { o.s_ = nullptr; }
-    DevStream(const DevStream&) = delete;
-    ~DevStream() {
-        if (!s_) return;
-        comms_stream_synchronize(device_, s_);
-        comms_stream_destroy(device_, s_);
-    }
-    // `launch(stream)` is the node's *_run_dev call
-    template <class TI, class TO, class F>
-    comms_status_t run(const DeviceBuf<TI>& in, DeviceBuf<TO>& out, F&& launch) {
-        if (in.device() != device_ || out.device() != device_) return COMMS_ERR_ARG;  // no cross-device edges (see above)
-        comms_status_t st = comms_buf_wait_ready(in.raw(), s_);
-        if (st == COMMS_OK) st = launch(s_);
-        if (st == COMMS_OK) st = comms_buf_record_use(in.raw(), s_);
-        if (st == COMMS_OK) st = comms_buf_record_ready(out.raw(), s_);
-        return st;
-    }
-    int device() const { return device_; }
-
-private:
-    void* s_ = nullptr;
-    int device_;
-};
-
-class BatchFirNodeDev : public DeriveNode<BatchFirNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<Complex32>> output;
-    BatchFirNodeDev(const std::vector<Complex32>& taps, const std::optional<std::vector<Complex32>>& state = std::nullopt,
-                    int device = 0)
-        : device_(device), st_(device) {
-        throw_on(comms_fir_create(c32(taps.data()), taps.size(), state ? c32(state->data()) : nullptr,
-                                  state ? state->size() : 0, device, &h_),
-                 "BatchFirNodeDev::new");
-    }
-    BatchFirNodeDev(BatchFirNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
-    ~BatchFirNodeDev() { comms_fir_destroy(h_); }
-    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& in) {
-        DeviceBuf<Complex32> out(in.size(), device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_fir_run_dev(h_, c32(in.ptr()), in.size(), c32(out.ptr()), s); });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_fir_t* h_ = nullptr;
-    int device_;
-    DevStream st_;
-};
-
-class BatchMixerNodeDev : public DeriveNode<BatchMixerNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<Complex32>> output;
-    explicit BatchMixerNodeDev(double dphase, std::optional<double> phase = std::nullopt, int device = 0) : device_(device), st_(device) {
-        throw_on(comms_mixer_create(dphase, phase.value_or(0.0), device, &h_), "BatchMixerNodeDev::new");
-    }
-    BatchMixerNodeDev(BatchMixerNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
-    ~BatchMixerNodeDev() { comms_mixer_destroy(h_); }
-    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& in) {
-        DeviceBuf<Complex32> out(in.size(), device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_mixer_run_dev(h_, c32(in.ptr()), in.size(), c32(out.ptr()), s); });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_mixer_t* h_ = nullptr;
-    int device_;
-    DevStream st_;
-};
-
-class DecimateNodeDev : public DeriveNode<DecimateNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<Complex32>> output;
-    explicit DecimateNodeDev(size_t dec_rate, int device = 0) : rate_(dec_rate), device_(device), st_(device) {}
-    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& in) {
-        size_t n_out = 0;
-        comms_decimate_out_len(in.size(), rate_, &n_out);
-        DeviceBuf<Complex32> out(n_out, device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) {
-            return comms_decimate_run_dev(in.ptr(), in.size(), sizeof(Complex32), rate_, out.ptr(), nullptr, device_, s);
-        });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    size_t rate_;
-    int device_;
-    DevStream st_;
-};
-
-// One macro-free pattern for the remaining device-resident nodes: own the C handle, move-only,
-// run() takes the output DeviceBuf from the cache and launches on the node's stream.
-class FFTBatchNodeDev : public DeriveNode<FFTBatchNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<Complex32>> output;
-    FFTBatchNodeDev(size_t fft_size, bool ifft, int device = 0) : device_(device), st_(device) {
-        throw_on(comms_fft_create(fft_size, ifft ? 1 : 0, device, &h_), "FFTBatchNodeDev::new");
-    }
-    FFTBatchNodeDev(FFTBatchNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
-    ~FFTBatchNodeDev() { comms_fft_destroy(h_); }
-    // the message may hold any whole number of transforms (the reference: exactly one)
-    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& in) {
-        DeviceBuf<Complex32> out(in.size(), device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_fft_run_dev(h_, c32(in.ptr()), in.size(), c32(out.ptr()), s); });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_fft_t* h_ = nullptr;
-    int device_;
-    DevStream st_;
-};
-
-class FMDemodNodeDev : public DeriveNode<FMDemodNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<float>> output;
-    explicit FMDemodNodeDev(int device = 0) : device_(device), st_(device) {
-        throw_on(comms_fmdemod_create(device, &h_), "FMDemodNodeDev::new");
-    }
-    FMDemodNodeDev(FMDemodNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
-    ~FMDemodNodeDev() { comms_fmdemod_destroy(h_); }
-    Result<DeviceBuf<float>> run(const DeviceBuf<Complex32>& in) {
-        DeviceBuf<float> out(in.size(), device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_fmdemod_run_dev(h_, c32(in.ptr()), in.size(), out.ptr(), s); });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_fmdemod_t* h_ = nullptr;
-    int device_;
-    DevStream st_;
-};
-
-// PulseNode over whole symbol blocks: n symbols in, n * sam_per_sym samples out
-class BatchPulseNodeDev : public DeriveNode<BatchPulseNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<Complex32>> output;
-    BatchPulseNodeDev(const std::vector<Complex32>& taps, size_t sam_per_sym, int device = 0)
-        : sps_(sam_per_sym), device_(device), st_(device) {
-        throw_on(comms_pulse_create(c32(taps.data()), taps.size(), sam_per_sym, device, &h_), "BatchPulseNodeDev::new");
-    }
-    BatchPulseNodeDev(BatchPulseNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sps_(o.sps_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
-    ~BatchPulseNodeDev() { comms_pulse_destroy(h_); }
-    BatchPulseNodeDev& with_mixer(double dphase, std::optional<double> phase = std::nullopt) {
-        throw_on(comms_pulse_set_mixer(h_, dphase, phase.value_or(0.0)), "BatchPulseNodeDev::with_mixer");
-        return *this;
-    }
-    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& sym) {
-        DeviceBuf<Complex32> out(sym.size() * sps_, device_);
-        comms_status_t st = st_.run(sym, out, [&](void* s) { return comms_pulse_run_dev(h_, c32(sym.ptr()), sym.size(), c32(out.ptr()), s); });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_pulse_t* h_ = nullptr;
-    size_t sps_;
-    int device_;
-    DevStream st_;
-};
-
-class UpsampleNodeDev : public DeriveNode<UpsampleNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<Complex32>> output;
-    explicit UpsampleNodeDev(size_t ups_rate, int device = 0) : rate_(ups_rate), device_(device), st_(device) {}
-    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& in) {
-        size_t n_out = 0;
-        comms_upsample_out_len(in.size(), rate_, &n_out);
-        DeviceBuf<Complex32> out(n_out, device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) {
-            return comms_upsample_run_dev(in.ptr(), in.size(), sizeof(Complex32), rate_, out.ptr(), nullptr, device_, s);
-        });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    size_t rate_;
-    int device_;
-    DevStream st_;
-};
 
 // ---------------------------------------------------------------- stream shards
 // One long stream over several GPUs, one node set per GPU: contiguous shards and one hand-over of the raw samples
@@ -1517,277 +1345,14 @@ inline size_t chain_prefix_len(size_t n_taps, size_t rate, bool fm_demod) {
     return n;
 }
 
-// mixer / FIR / decimate [/ FM demod] as ONE node (comms_chain_*; an additional node, the results of
-// the reference nodes in series).  Out = Complex32 without FM demod, float with it.
+// mixer / FIR / decimate [/ FM demod] as ONE node on device-resident messages.  Out = Complex32 without FM demod, float with it.
 template <class Out>
-class ChainNodeDev : public DeriveNode<ChainNodeDev<Out>> {
+class ChainNodeDev : public DevNode<ChainNodeDev<Out>, ChainOp<Complex32, Out>> {
 public:
     static constexpr bool kFm = std::is_same<Out, float>::value;
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<Out>> output;
-    ChainNodeDev(double dphase, double phase, const std::vector<Complex32>& taps, size_t rate, bool mixer_after_fir = false,
-                 int device = 0)
-        : rate_(rate), device_(device), st_(device) {
-        const int32_t flags = (kFm ? COMMS_CHAIN_FM_DEMOD : 0) | (mixer_after_fir ? COMMS_CHAIN_MIXER_AFTER_FIR : 0);
-        throw_on(comms_chain_create_ex(dphase, phase, c32(taps.data()), taps.size(), rate, flags, device, &h_),
-                 "ChainNodeDev::new");
-    }
-    ChainNodeDev(ChainNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), rate_(o.rate_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
-    ~ChainNodeDev() { comms_chain_destroy(h_); }
-    Result<DeviceBuf<Out>> run(const DeviceBuf<Complex32>& in) {
-        if (rate_ == 0 || in.size() % rate_) return NodeError::DataError;
-        DeviceBuf<Out> out(in.size() / rate_, device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_chain_run_dev(h_, c32(in.ptr()), in.size(), out.ptr(), s); });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    int fused_kind() const {  // 0 four kernels, 1 overlap-save fusion, 2 time-domain decimating kernel, 3 its any-rate form, 4 the polyphase
-                              // frequency-domain kernel (what the last call ran on: rates 4, 8, 12 ... 64)
-        int32_t f = 0;
-        comms_chain_is_fused(h_, &f);
-        return f;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_chain_t* h_ = nullptr;
-    size_t rate_;
-    int device_;
-    DevStream st_;
-};
-
-// The real FIR + decimator on device-resident messages (the angles a ChainNodeDev<float> sends never leave the device)
-class RealFirDecimNodeDev : public DeriveNode<RealFirDecimNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<float>> input;
-    NodeSender<DeviceBuf<float>> output;
-    RealFirDecimNodeDev(const std::vector<float>& taps, size_t rate, const std::optional<std::vector<float>>& state = std::nullopt,
-                        int device = 0)
-        : rate_(rate), device_(device), st_(device) {
-        throw_on(comms_rfir_create(taps.data(), taps.size(), state ? state->data() : nullptr, state ? state->size() : 0, rate,
-                                   device, &h_),
-                 "RealFirDecimNodeDev::new");
-    }
-    RealFirDecimNodeDev(RealFirDecimNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), rate_(o.rate_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
-    ~RealFirDecimNodeDev() { comms_rfir_destroy(h_); }
-    Result<DeviceBuf<float>> run(const DeviceBuf<float>& in) {
-        size_t m = 0;
-        comms_rfir_out_len(in.size(), rate_, &m);
-        DeviceBuf<float> out(m, device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_rfir_run_dev(h_, in.ptr(), in.size(), out.ptr(), s); });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_rfir_t* h_ = nullptr;
-    size_t rate_;
-    int device_;
-    DevStream st_;
-};
-
-// The rational resampler on device-resident messages
-template <class T>
-class ResampleNodeDev : public DeriveNode<ResampleNodeDev<T>> {
-public:
-    NodeReceiver<DeviceBuf<T>> input;
-    NodeSender<DeviceBuf<T>> output;
-    ResampleNodeDev(const std::vector<float>& taps, size_t up, size_t down, int device = 0)
-        : up_(up), down_(down), device_(device), st_(device) {
-        throw_on(comms_resample_create(taps.data(), taps.size(), up, down, ResampleElem<T>::value, device, &h_), "ResampleNodeDev::new");
-    }
-    ResampleNodeDev(ResampleNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), up_(o.up_), down_(o.down_), device_(o.device_), st_(std::move(o.st_)) {
-        o.h_ = nullptr;
-    }
-    ~ResampleNodeDev() { comms_resample_destroy(h_); }
-    Result<DeviceBuf<T>> run(const DeviceBuf<T>& in) {
-        size_t m = 0;
-        if (comms_resample_out_len(in.size(), up_, down_, &m) != COMMS_OK) return NodeError::DataError;
-        DeviceBuf<T> out(m, device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_resample_run_dev(h_, in.ptr(), in.size(), out.ptr(), s); });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_resample_t* h_ = nullptr;
-    size_t up_, down_;
-    int device_;
-    DevStream st_;
-};
-
-// The channelizer on device-resident messages: channel k of a channel-major message is a contiguous device stream
-class ChannelizerNodeDev : public DeriveNode<ChannelizerNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<Complex32>> output;
-    ChannelizerNodeDev(const std::vector<float>& taps, size_t channels, size_t down, int32_t layout = COMMS_CHANNELIZER_CHANNEL_MAJOR, int device = 0)
-        : channels_(channels), down_(down), device_(device), st_(device) {
-        throw_on(comms_channelizer_create(taps.data(), taps.size(), channels, down, layout, device, &h_), "ChannelizerNodeDev::new");
-    }
-    ChannelizerNodeDev(ChannelizerNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), channels_(o.channels_), down_(o.down_), device_(o.device_),
-          st_(std::move(o.st_)) {
-        o.h_ = nullptr;
-    }
-    ~ChannelizerNodeDev() { comms_channelizer_destroy(h_); }
-    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& in) {
-        size_t frames = 0;
-        if (comms_channelizer_out_len(in.size(), down_, &frames) != COMMS_OK) return NodeError::DataError;
-        DeviceBuf<Complex32> out(frames * channels_, device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) {
-            return comms_channelizer_run_dev(h_, reinterpret_cast<const comms_c32*>(in.ptr()), in.size(), reinterpret_cast<comms_c32*>(out.ptr()), s);
-        });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_channelizer_t* h_ = nullptr;
-    size_t channels_, down_;
-    int device_;
-    DevStream st_;
-};
-
-// The symbol synchroniser on device-resident messages (`update` as SymbolSyncNode's: host values, drained before each block)
-template <class Out = Complex32>
-class SymbolSyncNodeDev : public DeriveNode<SymbolSyncNodeDev<Out>> {
-    static_assert(std::is_same_v<Out, Complex32> || std::is_same_v<Out, uint8_t>, "symbols (Complex32) or packed bits (uint8_t)");
-
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeReceiver<SymbolSyncUpdate> update;
-    NodeSender<DeviceBuf<Out>> output;
-    SymbolSyncNodeDev(const std::vector<float>& taps, size_t phases, size_t sps, double dphase = 0.0, int bits_per_sym = 2, int device = 0)
-        : core_(taps, phases, sps, dphase, std::is_same_v<Out, uint8_t> ? bits_per_sym : 0, device, "SymbolSyncNodeDev::new"),
-          device_(device), st_(device) {}
-    SymbolSyncNodeDev(SymbolSyncNodeDev&&) noexcept = default;
-    Result<DeviceBuf<Out>> run(const DeviceBuf<Complex32>& in) {
-        comms_status_t st = core_.drain(update);
-        if (st != COMMS_OK) return to_node_error(st);
-        DeviceBuf<Out> out(core_.out_len(in.size()), device_);
-        st = st_.run(in, out, [&](void* s) {
-            return comms_symsync_run_dev(core_.h(), reinterpret_cast<const comms_c32*>(in.ptr()), in.size(), out.ptr(), s);
-        });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    detail::SymbolSyncCore core_;
-    int device_;
-    DevStream st_;
-};
-
-// The synchronisation estimator on device-resident messages: the estimates themselves are host values (the call
-// synchronises its stream), so the outputs are SyncEstimatorNode's
-class SyncEstimatorNodeDev : public DeriveNode<SyncEstimatorNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<comms_sync_estimate_t> output;
-    NodeSender<SymbolSyncUpdate> update;
-    SyncEstimatorNodeDev(uint32_t n, uint32_t d, double alpha, size_t n_taps, size_t phases, int device = 0)
-        : core_(n, d, alpha, n_taps, phases, device, "SyncEstimatorNodeDev::new"), device_(device) {
-        throw_on(comms_stream_create(device, &s_), "comms_stream_create");
-    }
-    SyncEstimatorNodeDev(SyncEstimatorNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), update(std::move(o.update)), core_(std::move(o.core_)),
-          device_(o.device_), s_(o.s_) { o.s_ = nullptr; }
-    ~SyncEstimatorNodeDev() {
-        if (s_) comms_stream_destroy(device_, s_);   // every run ends synchronised
-    }
-    Result<SyncEstimate> run(const DeviceBuf<Complex32>& in) {
-        if (in.device() != device_) return to_node_error(COMMS_ERR_ARG);
-        comms_sync_estimate_t e{};
-        comms_status_t st = comms_buf_wait_ready(in.raw(), s_);
-        if (st == COMMS_OK) st = comms_syncest_run_dev(core_.h(), reinterpret_cast<const comms_c32*>(in.ptr()), in.size(), &e, s_);
-        if (st != COMMS_OK) return to_node_error(st);
-        return core_.message(e);
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output, update); }
-
-private:
-    detail::SyncEstimatorCore core_;
-    int device_;
-    void* s_ = nullptr;
-};
-
-// The frame synchroniser on device-resident messages (SymbolSyncNodeDev<Complex32>'s output): the detections are host
-// values (the call synchronises its stream), so the output is FrameSyncNode's
-class FrameSyncNodeDev : public DeriveNode<FrameSyncNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<std::vector<comms_frame_detection_t>> output;
-    FrameSyncNodeDev(const std::vector<Complex32>& word, double threshold, size_t guard, int device = 0)
-        : core_(word, threshold, guard, device, "FrameSyncNodeDev::new"), device_(device) {
-        throw_on(comms_stream_create(device, &s_), "comms_stream_create");
-    }
-    FrameSyncNodeDev(FrameSyncNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), core_(std::move(o.core_)), device_(o.device_), s_(o.s_) { o.s_ = nullptr; }
-    ~FrameSyncNodeDev() {
-        if (s_) comms_stream_destroy(device_, s_);   // every run ends synchronised
-    }
-    Result<std::vector<comms_frame_detection_t>> run(const DeviceBuf<Complex32>& in) {
-        if (in.device() != device_) return to_node_error(COMMS_ERR_ARG);
-        std::vector<comms_frame_detection_t> out(core_.bound(in.size()));
-        size_t found = 0;
-        comms_status_t st = comms_buf_wait_ready(in.raw(), s_);
-        if (st == COMMS_OK)
-            st = comms_framesync_run_dev(core_.h(), reinterpret_cast<const comms_c32*>(in.ptr()), in.size(), out.data(), out.size(), &found, s_);
-        if (st != COMMS_OK) return to_node_error(st);
-        out.resize(found);
-        return out;
-    }
-    Result<std::vector<comms_frame_detection_t>> flush() { return core_.flush(); }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    detail::FrameSyncCore core_;
-    int device_;
-    void* s_ = nullptr;
-};
-
-// AWGN channel on device-resident messages: wait_ready(in) -> comms_awgn_run_dev on the node's stream -> record_use(in),
-// record_ready(out) -> send(out), the ordering of every *Dev node
-class AwgnNodeDev : public DeriveNode<AwgnNodeDev> {
-public:
-    NodeReceiver<DeviceBuf<Complex32>> input;
-    NodeSender<DeviceBuf<Complex32>> output;
-    AwgnNodeDev(float sigma, std::optional<uint64_t> seed = std::nullopt, uint64_t stream = 0, int device = 0)
-        : sigma_(sigma), device_(device), st_(device) {
-        throw_on(comms_noise_create(seed ? *seed : entropy_seed(), stream, device, &h_), "AwgnNodeDev::new");
-    }
-    AwgnNodeDev(AwgnNodeDev&& o) noexcept
-        : input(std::move(o.input)), output(std::move(o.output)), h_(o.h_), sigma_(o.sigma_), device_(o.device_), st_(std::move(o.st_)) { o.h_ = nullptr; }
-    ~AwgnNodeDev() { comms_noise_destroy(h_); }
-    Result<DeviceBuf<Complex32>> run(const DeviceBuf<Complex32>& in) {
-        DeviceBuf<Complex32> out(in.size(), device_);
-        comms_status_t st = st_.run(in, out, [&](void* s) { return comms_awgn_run_dev(h_, in.ptr(), in.size(), sigma_, c32(out.ptr()), s); });
-        if (st != COMMS_OK) return to_node_error(st);
-        return out;
-    }
-    auto receivers() { return std::tie(input); }
-    auto senders() { return std::tie(output); }
-
-private:
-    comms_noise_t* h_ = nullptr;
-    float sigma_;
-    int device_;
-    DevStream st_;
+    ChainNodeDev(double dphase, double phase, const std::vector<Complex32>& taps, size_t rate, bool mixer_after_fir = false, int device = 0)
+        : ChainNodeDev::DevNode(device, "ChainNodeDev::new", dphase, phase, taps, rate,
+                                (kFm ? COMMS_CHAIN_FM_DEMOD : 0) | (mixer_after_fir ? COMMS_CHAIN_MIXER_AFTER_FIR : 0), device) {}
 };
 
 }  // namespace comms

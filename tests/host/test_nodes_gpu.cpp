@@ -13,6 +13,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <optional>
 #include <string>
 #include <thread>
 
@@ -40,6 +42,63 @@ static_assert(kIo<FMDemodNodeF64, std::vector<Complex64>, std::vector<double>>);
 static_assert(kIo<FFTBatchNode, std::vector<Complex32>, std::vector<Complex32>>);
 static_assert(kIo<FFTBatchNodeF64, std::vector<Complex64>, std::vector<Complex64>>);
 static_assert(std::is_same_v<decltype(std::declval<const BatchFirNode&>().handle()), comms_fir_t*>);
+
+// every public node type of the header: moved into its thread without throwing, never copied (a copy would own the same C
+// handle), and the documented message types on `input` / `output` (and `update` where there is one)
+template <class N>
+constexpr bool kMoveOnly = std::is_nothrow_move_constructible_v<N> && !std::is_copy_constructible_v<N>;
+template <class N, class In, class Out>
+constexpr bool kNode = kMoveOnly<N> && kIo<N, In, Out>;
+template <class N, class Out>
+constexpr bool kSource = kMoveOnly<N> && std::is_same_v<decltype(N::output), NodeSender<Out>>;
+template <class N, class Msg>
+constexpr bool kUpdate = std::is_same_v<decltype(N::update), Msg>;
+template <class T>
+using Vec = std::vector<T>;
+template <class T>
+using Dev = DeviceBuf<T>;
+using Detections = std::vector<comms_frame_detection_t>;
+static_assert(kMoveOnly<BatchFirNode> && kMoveOnly<FirNode> && kMoveOnly<PulseNode> && kMoveOnly<BatchFirNodeI16> && kMoveOnly<FirNodeI16> &&
+              kMoveOnly<PulseNodeI16> && kMoveOnly<BatchFirNodeF64> && kMoveOnly<FirNodeF64> && kMoveOnly<PulseNodeF64> &&
+              kMoveOnly<MixerNode> && kMoveOnly<MixerNode64> && kMoveOnly<FMDemodNode> && kMoveOnly<FMDemodNodeF64> &&
+              kMoveOnly<FFTBatchNode> && kMoveOnly<FFTBatchNodeF64>);
+static_assert(kSource<PrnsNode, uint8_t>);
+static_assert(kSource<NormalNode, double>);
+static_assert(kSource<UniformNode<float>, float>);
+static_assert(kSource<UniformNode<uint8_t>, uint8_t>);
+static_assert(kNode<AwgnNode, Vec<Complex32>, Vec<Complex32>>);
+static_assert(kNode<PulseBitsNode, Vec<uint8_t>, Vec<Complex16>>);
+static_assert(kNode<ChainBitsNode, Vec<Complex16>, Vec<uint8_t>>);
+static_assert(kNode<RealFirDecimNode, Vec<float>, Vec<float>>);
+static_assert(kNode<ResampleNode<float>, Vec<float>, Vec<float>>);
+static_assert(kNode<ResampleNode<Complex32>, Vec<Complex32>, Vec<Complex32>>);
+static_assert(kNode<ChannelizerNode, Vec<Complex32>, Vec<Complex32>>);
+static_assert(kNode<SymbolSyncNode<Complex32>, Vec<Complex32>, Vec<Complex32>> && kUpdate<SymbolSyncNode<Complex32>, NodeReceiver<SymbolSyncUpdate>>);
+static_assert(kNode<SymbolSyncNode<uint8_t>, Vec<Complex32>, Vec<uint8_t>> && kUpdate<SymbolSyncNode<uint8_t>, NodeReceiver<SymbolSyncUpdate>>);
+static_assert(kNode<BatchMixerNode, Vec<Complex32>, Vec<Complex32>>);
+static_assert(kNode<DecimateNode<Complex32>, Vec<Complex32>, Vec<Complex32>> && kNode<DecimateNode<int>, Vec<int>, Vec<int>>);
+static_assert(kNode<UpsampleNode<Complex32>, Vec<Complex32>, Vec<Complex32>> && kNode<UpsampleNode<int>, Vec<int>, Vec<int>>);
+static_assert(kNode<FFTSampleNode, Complex32, Vec<Complex32>>);
+static_assert(kNode<TimingEstimatorNode, Vec<Complex64>, double>);
+static_assert(kNode<SyncEstimatorNode, Vec<Complex32>, comms_sync_estimate_t> && kUpdate<SyncEstimatorNode, NodeSender<SymbolSyncUpdate>>);
+static_assert(kNode<FrameSyncNode, Vec<Complex32>, Detections>);
+static_assert(kNode<BatchNcoNode, Vec<double>, Vec<Complex64>>);
+static_assert(kNode<BatchFirNodeDev, Dev<Complex32>, Dev<Complex32>>);
+static_assert(kNode<BatchMixerNodeDev, Dev<Complex32>, Dev<Complex32>>);
+static_assert(kNode<DecimateNodeDev, Dev<Complex32>, Dev<Complex32>>);
+static_assert(kNode<UpsampleNodeDev, Dev<Complex32>, Dev<Complex32>>);
+static_assert(kNode<FFTBatchNodeDev, Dev<Complex32>, Dev<Complex32>>);
+static_assert(kNode<FMDemodNodeDev, Dev<Complex32>, Dev<float>>);
+static_assert(kNode<BatchPulseNodeDev, Dev<Complex32>, Dev<Complex32>>);
+static_assert(kNode<ChainNodeDev<Complex32>, Dev<Complex32>, Dev<Complex32>> && kNode<ChainNodeDev<float>, Dev<Complex32>, Dev<float>>);
+static_assert(kNode<RealFirDecimNodeDev, Dev<float>, Dev<float>>);
+static_assert(kNode<ResampleNodeDev<float>, Dev<float>, Dev<float>> && kNode<ResampleNodeDev<Complex32>, Dev<Complex32>, Dev<Complex32>>);
+static_assert(kNode<ChannelizerNodeDev, Dev<Complex32>, Dev<Complex32>>);
+static_assert(kNode<SymbolSyncNodeDev<Complex32>, Dev<Complex32>, Dev<Complex32>> && kUpdate<SymbolSyncNodeDev<Complex32>, NodeReceiver<SymbolSyncUpdate>>);
+static_assert(kNode<SymbolSyncNodeDev<uint8_t>, Dev<Complex32>, Dev<uint8_t>> && kUpdate<SymbolSyncNodeDev<uint8_t>, NodeReceiver<SymbolSyncUpdate>>);
+static_assert(kNode<SyncEstimatorNodeDev, Dev<Complex32>, comms_sync_estimate_t> && kUpdate<SyncEstimatorNodeDev, NodeSender<SymbolSyncUpdate>>);
+static_assert(kNode<FrameSyncNodeDev, Dev<Complex32>, Detections>);
+static_assert(kNode<AwgnNodeDev, Dev<Complex32>, Dev<Complex32>>);
 
 static int g_fail = 0;
 #define CHECK(cond)                                                                       \
@@ -799,6 +858,88 @@ static void test_per_sample_nodes_keep_up() {
     }
 }
 
+// A node moved between two messages: the state travels with the handle, and the moved-from object, going out of scope,
+// destroys nothing.  `make(first)` builds a node, `one(node, msg)` runs one message and returns the output on the host (empty
+// on an error); both outputs equal `want` -- one C handle fed the same two messages -- bit for bit.
+template <class T>
+static bool same_bits(const std::vector<T>& a, const std::vector<T>& b) {
+    return a.size() == b.size() && !a.empty() && std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0;
+}
+template <class N, class Make, class One, class In, class Out>
+static void two_messages_across_a_move(Make make, One one, const std::vector<In> (&msg)[2], const std::vector<Out> (&want)[2]) {
+    std::optional<N> second;
+    std::vector<Out> got0;
+    {
+        N first = make();
+        got0 = one(first, msg[0]);
+        second.emplace(std::move(first));
+    }  // the moved-from `first` is gone
+    const std::vector<Out> got1 = one(*second, msg[1]);
+    CHECK(same_bits(got0, want[0]));
+    CHECK(same_bits(got1, want[1]));
+}
+static const auto run_host = [](auto& node, const auto& msg) {
+    auto r = node.run(msg);
+    CHECK(r.is_ok());
+    return r.is_ok() ? std::move(r.value()) : std::decay_t<decltype(r.value())>{};
+};
+static const auto run_dev = [](auto& node, const auto& msg) {
+    using In = typename std::decay_t<decltype(msg)>::value_type;
+    auto r = node.run(DeviceBuf<In>::from_host(msg));
+    CHECK(r.is_ok());
+    return r.is_ok() ? r.value().to_host() : decltype(r.value().to_host()){};
+};
+
+static void test_moved_nodes_keep_their_state() {
+    std::vector<float> real[2] = {std::vector<float>(64), std::vector<float>(64)};
+    std::vector<C> iq[2] = {std::vector<C>(64), std::vector<C>(64)};
+    for (size_t m = 0; m < 2; ++m)
+        for (size_t i = 0; i < 64; ++i) {
+            const float t = static_cast<float>(64 * m + i);
+            real[m][i] = std::sin(0.37f * t) + 0.01f * t;
+            iq[m][i] = C(std::cos(0.21f * t), std::sin(0.45f * t) - 0.5f);
+        }
+    // one shell each, on an operation that keeps state across messages: the real FIR + decimator, 5 taps, rate 2
+    const std::vector<float> taps5 = {0.5f, -0.25f, 0.125f, 1.0f, 0.75f};
+    std::vector<float> want[2] = {std::vector<float>(32), std::vector<float>(32)};
+    comms_rfir_t* h = nullptr;
+    CHECK(comms_rfir_create(taps5.data(), taps5.size(), nullptr, 0, 2, 0, &h) == COMMS_OK);
+    if (!h) return;
+    for (size_t m = 0; m < 2; ++m) CHECK(comms_rfir_run(h, real[m].data(), 64, want[m].data()) == COMMS_OK);
+    comms_rfir_destroy(h);
+    CHECK(!same_bits(want[0], want[1]));
+    two_messages_across_a_move<RealFirDecimNode>([&] { return RealFirDecimNode(taps5, 2); }, run_host, real, want);
+    two_messages_across_a_move<RealFirDecimNodeDev>([&] { return RealFirDecimNodeDev(taps5, 2); }, run_dev, real, want);
+
+    // the symbol synchroniser (a description with settings applied after its create): 9 taps, 2 phases, sps 2
+    std::vector<float> taps9(9);
+    for (size_t k = 0; k < 9; ++k) taps9[k] = 0.3f - 0.05f * static_cast<float>(k) * (k % 2 ? -1.f : 1.f);
+    std::vector<C> wsym[2] = {std::vector<C>(32), std::vector<C>(32)};
+    comms_symsync_t* hs = nullptr;
+    CHECK(comms_symsync_create(taps9.data(), taps9.size(), 2, 2, 0, &hs) == COMMS_OK);
+    if (!hs) return;
+    CHECK(comms_symsync_set_rotation(hs, 0.0, 0.0) == COMMS_OK);  // what the node's constructor sets
+    for (size_t m = 0; m < 2; ++m) CHECK(comms_symsync_run(hs, c32(iq[m].data()), 64, wsym[m].data()) == COMMS_OK);
+    comms_symsync_destroy(hs);
+    CHECK(!same_bits(wsym[0], wsym[1]));
+    using Sync = SymbolSyncNodeDev<Complex32>;
+    two_messages_across_a_move<Sync>([&] { return Sync(taps9, 2, 2); }, run_dev, iq, wsym);
+}
+
+// A device node releases its handle before its stream: comms_stream_pool_trim refuses while a handle still follows a pooled
+// stream, and the node's own stream is back in the pool once the node is gone.
+static void test_device_node_teardown_order() {
+    std::vector<C> x(64);
+    for (size_t i = 0; i < x.size(); ++i) x[i] = C(static_cast<float>(i), -0.5f * static_cast<float>(i));
+    {
+        ChannelizerNodeDev chz({0.25f, 0.5f, 0.5f, 0.25f}, 2, 2);
+        auto r = chz.run(DeviceBuf<C>::from_host(x));
+        CHECK(r.is_ok());
+        if (r.is_ok()) CHECK(r.value().to_host().size() == 2 * 32);
+    }
+    CHECK(comms_stream_pool_trim(0) == COMMS_OK);
+}
+
 int main() {
     int32_t ndev = 0;
     if (comms_device_count(&ndev) != COMMS_OK || ndev < 1) {
@@ -821,6 +962,8 @@ int main() {
     test_device_resident_chain_and_fft();
     test_stream_cut_over_two_chain_nodes();
     test_per_sample_nodes_keep_up();
+    test_moved_nodes_keep_their_state();
+    test_device_node_teardown_order();
     if (g_fail) {
         std::fprintf(stderr, "%d check(s) failed\n", g_fail);
         return 1;
