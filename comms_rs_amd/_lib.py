@@ -17,6 +17,8 @@ COMMS_OK, COMMS_ERR_ARG, COMMS_ERR_DEVICE = 0, 1, 2
 FIR_AUTO, FIR_DIRECT, FIR_OVERLAP_SAVE, FIR_OS1024, FIR_OS4096, FIR_OS16K, FIR_OS1024_FIXED = 0, 1, 2, 3, 4, 5, 6
 IQ_C32, IQ_I16, IQ_U8 = 0, 1, 2
 SYM_C32, SYM_BITS = 0, 1        # comms_pulse_set_input_format, comms_chain_set_output_format
+SYM_LLR = 3                     # comms_deframe_set_output_format only
+DEFRAME_NORMALISE = 1           # comms_deframe_create: flags
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 RESAMPLE_F32, RESAMPLE_C32 = 4, 8  # comms_resample_create: bytes per sample
 CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR = 0, 1  # comms_channelizer_create: layout
@@ -292,6 +294,24 @@ _PROTOS = {
     "comms_framesync_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_framesync_set_timer": [_vp, _vp],
     "comms_framesync_destroy": [_vp],
+    "comms_deframe_create": [_sz, _sz, _sz, _i32, _vp, _i32, _i32, _pp],
+    "comms_deframe_set_word_energy": [_vp, _f64],
+    "comms_deframe_set_output_format": [_vp, _i32],
+    "comms_deframe_set_llr_scale": [_vp, C.c_float],
+    "comms_deframe_frames_ready": [_vp, _sz, _vp, _sz, _psz],
+    "comms_deframe_run_dev": [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _psz, _vp],
+    "comms_deframe_run": [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _psz],
+    "comms_deframe_flush": [_vp, _psz],
+    "comms_deframe_state_len": [_sz, _sz, _psz],
+    "comms_deframe_get_state": [_vp, _vp, _sz],
+    "comms_deframe_set_state": [_vp, _vp, _sz],
+    "comms_deframe_get_position": [_vp, C.POINTER(C.c_uint64)],
+    "comms_deframe_set_position": [_vp, C.c_uint64],
+    "comms_deframe_get_pending": [_vp, _vp, _sz, _psz],
+    "comms_deframe_set_pending": [_vp, _vp, _sz],
+    "comms_deframe_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_deframe_set_timer": [_vp, _vp],
+    "comms_deframe_destroy": [_vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],
@@ -309,6 +329,7 @@ _OTHER = {
     "comms_buf_ptr": (_vp, [_vp]),
     "comms_buf_size": (_sz, [_vp]),
     "comms_qfilt_len": (_sz, [_u32]),
+    "comms_deframe_frame_bytes": (_sz, [_vp]),
     "comms_buf_device": (_i32, [_vp]),
     "comms_synth_iq_host": (None, [_vp, _sz, _u64, _u64]),
 }

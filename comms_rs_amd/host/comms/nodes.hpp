@@ -1294,6 +1294,105 @@ public:
     }
 };
 
+// Deframer (comms_deframe_*; an additional node): takes the symbol blocks FrameSyncNode takes and, on a second receiver, the
+// detections FrameSyncNode sent for the same block, and sends per block the frames that became complete in it -- possibly
+// none -- as one message: the records back to back (frame f at data[f * frame_bytes]; packed bits, LLRs or symbols, see
+// `format`) and one header per frame.  A payload that ends in a later block comes out of that block; the frames do not
+// depend on how the stream is cut into blocks.  Connect SymbolSyncNode's output to both nodes.  One description, two shells
+// with run() bodies of their own (two receivers; the call synchronises its stream), as the frame synchroniser's.
+template <class Store>
+struct FramesOf {
+    Store data;                                    // headers.size() * frame_bytes bytes hold the records (a buffer may be longer)
+    std::vector<comms_deframe_header_t> headers;   // one per frame, ascending index
+    size_t frame_bytes = 0;
+    size_t size() const { return headers.size(); }
+};
+struct DeframeOp {
+    using Detections = FrameSyncOp::Detections;
+    using Frames = FramesOf<std::vector<uint8_t>>;
+    using FramesDev = FramesOf<DeviceBuf<uint8_t>>;
+    // format: COMMS_SYM_C32, COMMS_SYM_BITS or COMMS_SYM_LLR; word_energy > 0 turns COMMS_DEFRAME_NORMALISE on
+    DeframeOp(const char* who, size_t n_payload, size_t offset, size_t lookback, int bits_per_sym, int32_t format, double word_energy,
+              float llr_scale, int device)
+        : h_(create<decltype(h_)>(who, comms_deframe_create, n_payload, offset, lookback, bits_per_sym, static_cast<const comms_c32*>(nullptr),
+                                  word_energy > 0.0 ? COMMS_DEFRAME_NORMALISE : 0, device)) {
+        if (word_energy > 0.0) throw_on(comms_deframe_set_word_energy(h_.get(), word_energy), who);
+        throw_on(comms_deframe_set_output_format(h_.get(), format), who);
+        throw_on(comms_deframe_set_llr_scale(h_.get(), llr_scale), who);
+    }
+    size_t frame_bytes() const { return comms_deframe_frame_bytes(h_.get()); }
+    size_t flush() {  // drops the incomplete frames; how many
+        size_t dropped = 0;
+        throw_on(comms_deframe_flush(h_.get(), &dropped), "DeframeNode::flush");
+        return dropped;
+    }
+    std::string kernel(size_t n_frames) const { return kernel_name(comms_deframe_get_kernel, h_.get(), n_frames); }  // "deframe_kernel ..."
+
+protected:
+    Result<Frames> extract(const Complex32* in, size_t n, const Detections& dets) {
+        Frames out;
+        size_t cap = 0;
+        comms_status_t st = ready(n, dets, out, cap);
+        if (st != COMMS_OK) return to_node_error(st);
+        out.data.resize(cap * out.frame_bytes);
+        size_t found = 0;
+        st = comms_deframe_run(h_.get(), c32(in), n, dets.data(), dets.size(), out.data.data(), cap, out.headers.data(), &found);
+        return ok_or(st, out);
+    }
+    Result<FramesDev> extract_dev(const Complex32* in, size_t n, const Detections& dets, void* s, int device) {
+        FramesDev out;
+        size_t cap = 0;
+        comms_status_t st = ready(n, dets, out, cap);
+        if (st != COMMS_OK) return to_node_error(st);
+        out.data = DeviceBuf<uint8_t>(cap ? cap * out.frame_bytes : 8, device);
+        size_t found = 0;
+        st = comms_deframe_run_dev(h_.get(), c32(in), n, dets.data(), dets.size(), out.data.ptr(), cap, out.headers.data(), &found, s);
+        if (st == COMMS_OK) st = comms_buf_record_ready(out.data.raw(), s);
+        return ok_or(st, out);
+    }
+
+private:
+    template <class F>
+    comms_status_t ready(size_t n, const Detections& dets, F& out, size_t& cap) const {
+        const comms_status_t st = comms_deframe_frames_ready(h_.get(), n, dets.data(), dets.size(), &cap);
+        out.headers.resize(cap);
+        out.frame_bytes = frame_bytes();
+        return st;
+    }
+    Owned<comms_deframe_t, comms_deframe_destroy> h_;
+};
+
+template <class Sym, class Out>
+struct DeframePorts {  // as Ports, with the second receiver
+    NodeReceiver<Sym> input;                               // the symbol blocks
+    NodeReceiver<DeframeOp::Detections> detections;        // FrameSyncNode's message for the same block
+    NodeSender<Out> output;
+    auto receivers() { return std::tie(input, detections); }
+    auto senders() { return std::tie(output); }
+};
+class DeframeNode : public DeriveNode<DeframeNode>, public DeframePorts<std::vector<Complex32>, DeframeOp::Frames>, public DeframeOp {
+public:
+    DeframeNode(size_t n_payload, size_t offset, size_t lookback, int bits_per_sym = 2, int32_t format = COMMS_SYM_BITS, double word_energy = 0.0,
+                float llr_scale = 1.0f, int device = 0)
+        : DeframeOp("DeframeNode::new", n_payload, offset, lookback, bits_per_sym, format, word_energy, llr_scale, device) {}
+    Result<Frames> run(const std::vector<Complex32>& symbols, const Detections& dets) { return extract(symbols.data(), symbols.size(), dets); }
+};
+// on device-resident messages: SymbolSyncNodeDev<Complex32>'s output in, the records in a DeviceBuf out (headers on the host)
+class DeframeNodeDev : public DeriveNode<DeframeNodeDev>, public DeframePorts<DeviceBuf<Complex32>, DeframeOp::FramesDev>, public OnStream<DeframeOp> {
+public:
+    DeframeNodeDev(size_t n_payload, size_t offset, size_t lookback, int bits_per_sym = 2, int32_t format = COMMS_SYM_BITS, double word_energy = 0.0,
+                   float llr_scale = 1.0f, int device = 0)
+        : OnStream(device, "DeframeNodeDev::new", n_payload, offset, lookback, bits_per_sym, format, word_energy, llr_scale, device) {}
+    Result<FramesDev> run(const DeviceBuf<Complex32>& in, const Detections& dets) {
+        comms_status_t st = wait(in);
+        if (st != COMMS_OK) return to_node_error(st);
+        auto out = extract_dev(in.ptr(), in.size(), dets, get(), device());
+        if (out.is_ok()) st = comms_buf_record_use(in.raw(), get());
+        if (st != COMMS_OK) return to_node_error(st);
+        return out;
+    }
+};
+
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)

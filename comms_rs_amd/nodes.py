@@ -1496,6 +1496,164 @@ class FrameSyncNode(_Handle):
         return self
 
 
+class _FrameHeaderStruct(C.Structure):
+    _fields_ = [("index", C.c_uint64), ("start", C.c_uint64), ("rot_re", C.c_float), ("rot_im", C.c_float), ("gain", C.c_float),
+                ("metric", C.c_float)]
+
+
+FRAME_HEADER_DTYPE = np.dtype([("index", np.uint64), ("start", np.uint64), ("rot_re", np.float32), ("rot_im", np.float32),
+                               ("gain", np.float32), ("metric", np.float32)])
+_SYM_FORMATS = {"c32": _lib.SYM_C32, "bits": _lib.SYM_BITS, "llr": _lib.SYM_LLR}
+
+
+def _as_detections(detections):
+    """FrameSyncNode's raw=True array, or its FrameDetection list, as a contiguous FRAME_DETECTION_DTYPE array."""
+    if isinstance(detections, np.ndarray) and detections.dtype == FRAME_DETECTION_DTYPE:
+        return np.ascontiguousarray(detections)
+    detections = [] if detections is None else list(detections)
+    out = np.zeros(len(detections), FRAME_DETECTION_DTYPE)
+    for i, d in enumerate(detections):
+        out[i] = (d.index, d.corr.real, d.corr.imag, d.metric, d.energy)
+    return out
+
+
+class DeframeNode(_Handle):
+    """Deframer (comms_deframe_*): takes the symbol stream FrameSyncNode takes, in the same calls, and the detections those
+    calls return, and writes every frame that becomes complete in a call -- `n_payload` symbols from index + `offset`,
+    derotated by the detection's correlation and, with normalise=True, scaled by word_energy / |corr| -- in one launch:
+    packed bits ("bits"), max-log LLRs ("llr", positive = bit 0, scaled by llr_scale) or Complex<f32> symbols ("c32", the
+    default), one record per frame.  A frame that ends in a later call stays pending and comes out of that call; the frames do
+    not depend on how the stream is cut into calls.  `lookback` >= the frame synchroniser's guard - 1.  run() returns an array
+    of shape (n_frames, n_payload) complex64, (n_frames, frame_bytes) uint8 or (n_frames, n_payload * bits_per_sym) float32;
+    `headers` holds the FRAME_HEADER_DTYPE records of the last call."""
+    _destroy = "comms_deframe_destroy"
+
+    def __init__(self, n_payload, offset, lookback, bits_per_sym=2, constellation=None, normalise=False, word_energy=None, device=0):
+        super().__init__()
+        self.n_payload, self.offset, self.lookback, self.bits_per_sym = int(n_payload), int(offset), int(lookback), int(bits_per_sym)
+        self.format = "c32"
+        self.headers = np.zeros(0, FRAME_HEADER_DTYPE)
+        table = None if constellation is None else np.ascontiguousarray(constellation, dtype=np.complex64)
+        if table is not None and table.size != 1 << self.bits_per_sym:
+            raise ValueError("constellation must hold 2**bits_per_sym points")
+        check(lib().comms_deframe_create(self.n_payload, self.offset, self.lookback, self.bits_per_sym,
+                                         None if table is None else _ptr(table), _lib.DEFRAME_NORMALISE if normalise else 0, device,
+                                         C.byref(self._h)))
+        if word_energy is not None:
+            self.set_word_energy(word_energy)
+
+    def set_word_energy(self, word_energy):
+        """sum |p|^2 of the word: what normalise=True divides |corr| into."""
+        check(lib().comms_deframe_set_word_energy(self._h, float(word_energy)))
+        return self
+
+    def set_output_format(self, fmt):
+        """ "c32" (default), "bits" or "llr"; may change between calls."""
+        if fmt not in _SYM_FORMATS:
+            raise ValueError("the deframer writes 'c32', 'bits' or 'llr'")
+        check(lib().comms_deframe_set_output_format(self._h, _SYM_FORMATS[fmt]))
+        self.format = fmt
+        return self
+
+    def set_llr_scale(self, scale):
+        """s of L = s (D1 - D0): 1 / (2 sigma^2) for noise of sigma per component."""
+        check(lib().comms_deframe_set_llr_scale(self._h, float(scale)))
+        return self
+
+    def frame_bytes(self):
+        return lib().comms_deframe_frame_bytes(self._h)
+
+    def frames_ready(self, n, detections=None):
+        """How many frames a call on n symbols with these detections would emit (host arithmetic)."""
+        det, count = _as_detections(detections), C.c_size_t()
+        check(lib().comms_deframe_frames_ready(self._h, int(n), _ptr(det) if det.size else None, det.size, C.byref(count)))
+        return count.value
+
+    def _shape(self, raw, n_frames):
+        dtype = {"c32": np.complex64, "bits": np.uint8, "llr": np.float32}[self.format]
+        fb = self.frame_bytes()
+        return raw[: n_frames * fb].view(dtype).reshape(n_frames, fb // np.dtype(dtype).itemsize)
+
+    def run(self, symbols, detections=None, cap=None):
+        x = np.ascontiguousarray(symbols, dtype=np.complex64)
+        det = _as_detections(detections)
+        cap = self.frames_ready(x.size, det) if cap is None else int(cap)
+        raw = np.zeros(cap * self.frame_bytes(), np.uint8)
+        hdr, found = np.zeros(cap, FRAME_HEADER_DTYPE), C.c_size_t()
+        check(lib().comms_deframe_run(self._h, _ptr(x), x.size, _ptr(det) if det.size else None, det.size, _ptr(raw) if cap else None,
+                                      cap, _ptr(hdr) if cap else None, C.byref(found)))
+        self.headers = hdr[: found.value]
+        return self._shape(raw, found.value)
+
+    def run_dev(self, in_ptr, n, detections, out_ptr, cap_frames, stream=0):
+        """Device pointers; returns the number of frames written at out_ptr (frame f at f * frame_bytes())."""
+        det = _as_detections(detections)
+        cap = int(cap_frames)
+        hdr, found = np.zeros(cap, FRAME_HEADER_DTYPE), C.c_size_t()
+        check(lib().comms_deframe_run_dev(self._h, in_ptr, int(n), _ptr(det) if det.size else None, det.size, out_ptr, cap,
+                                          _ptr(hdr) if cap else None, C.byref(found), stream))
+        self.headers = hdr[: found.value]
+        return found.value
+
+    def flush(self):
+        """Drops the pending (incomplete) frames and returns how many; history zero afterwards, position kept."""
+        dropped = C.c_size_t()
+        check(lib().comms_deframe_flush(self._h, C.byref(dropped)))
+        return dropped.value
+
+    def state_len(self):
+        m = C.c_size_t()
+        check(lib().comms_deframe_state_len(self.n_payload, self.lookback, C.byref(m)))
+        return m.value
+
+    def state(self, n_state=None):
+        """The last n_state symbols (default: all max(lookback, n_payload - 1)), newest first."""
+        n_state = self.state_len() if n_state is None else int(n_state)
+        st = np.empty(n_state, np.complex64)
+        check(lib().comms_deframe_get_state(self._h, _ptr(st) if n_state else None, n_state))
+        return st
+
+    def set_state(self, state):
+        state = np.ascontiguousarray(state, dtype=np.complex64)
+        check(lib().comms_deframe_set_state(self._h, _ptr(state) if state.size else None, state.size))
+        return self
+
+    def position(self):
+        """Stream index of the next symbol."""
+        t = C.c_uint64()
+        check(lib().comms_deframe_get_position(self._h, C.byref(t)))
+        return t.value
+
+    def set_position(self, position):
+        """Also forgets the pending frames: restore a checkpoint as set_state, set_position, set_pending."""
+        check(lib().comms_deframe_set_position(self._h, int(position)))
+        return self
+
+    def pending(self):
+        """The frames admitted and not yet complete (FRAME_HEADER_DTYPE), ascending."""
+        n = C.c_size_t()
+        check(lib().comms_deframe_get_pending(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, FRAME_HEADER_DTYPE)
+        check(lib().comms_deframe_get_pending(self._h, _ptr(out) if n.value else None, n.value, C.byref(n)))
+        return out
+
+    def set_pending(self, pending):
+        pending = np.ascontiguousarray(pending, dtype=FRAME_HEADER_DTYPE)
+        check(lib().comms_deframe_set_pending(self._h, _ptr(pending) if pending.size else None, pending.size))
+        return self
+
+    def kernel(self, n_frames):
+        """What a call that emits n_frames frames is run by: "deframe_kernel wg=.. items=.. lanes=.. grid=.. max_grid=.. lds=.."."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_deframe_get_kernel(self._h, int(n_frames), buf, 240))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch."""
+        check(lib().comms_deframe_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
 def qfilt_taps(n_taps, alpha, sam_per_sym):
     """util/math.rs:307-342 (f64, real); even n_taps is incremented."""
     out = np.empty(lib().comms_qfilt_len(int(n_taps)), np.float64)
@@ -1569,7 +1727,8 @@ class KernelTimer:
                 "comms_channelizer_destroy": "comms_channelizer_set_timer",
                 "comms_symsync_destroy": "comms_symsync_set_timer",
                 "comms_syncest_destroy": "comms_syncest_set_timer",
-                "comms_framesync_destroy": "comms_framesync_set_timer"}[node._destroy]
+                "comms_framesync_destroy": "comms_framesync_set_timer",
+                "comms_deframe_destroy": "comms_deframe_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

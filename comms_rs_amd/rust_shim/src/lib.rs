@@ -1230,6 +1230,76 @@ impl FrameSyncNode {
     }
 }
 
+/// What `DeframeNode` sends per block: the records of the frames that became complete in it, back to back (frame f at
+/// `data[f * frame_bytes..]`), and one header per frame.
+#[derive(Clone, Debug, Default, PartialEq)]
+pub struct Frames {
+    pub data: Vec<u8>,
+    pub headers: Vec<comms_deframe_header_t>,
+    pub frame_bytes: usize,
+}
+
+/// Deframer (an additional node, comms_deframe_*): takes the symbol blocks `FrameSyncNode` takes and, on `detections`, what
+/// `FrameSyncNode` sent for the same block; sends the payloads of the frames that became complete in the block -- `n_payload`
+/// symbols from `index + offset`, derotated by the detection's correlation -- as packed bits (`COMMS_SYM_BITS`), max-log LLRs
+/// (`COMMS_SYM_LLR`, f32, positive = bit 0) or symbols (`COMMS_SYM_C32`), all by one launch.  A payload that ends in a later
+/// block comes out of that block.  `lookback` >= the frame synchroniser's guard - 1.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct DeframeNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    pub detections: NodeReceiver<Vec<comms_frame_detection_t>>,
+    h: *mut comms_deframe_t,
+    pub output: NodeSender<Frames>,
+}
+handle_node!(DeframeNode, comms_deframe_destroy);
+impl DeframeNode {
+    /// `word_energy`: `Some(sum |p|^2)` scales every payload by it over |corr| (COMMS_DEFRAME_NORMALISE).
+    /// `Err(())`: n_payload outside 1 ..= 2^20, offset or lookback beyond 2^20, bits_per_sym not 1 or 2, an unknown format.
+    pub fn new(n_payload: usize, offset: usize, lookback: usize, bits_per_sym: i32, format: i32, word_energy: Option<f64>) -> Result<Self, ()> {
+        let mut h = ptr::null_mut();
+        let flags = if word_energy.is_some() { COMMS_DEFRAME_NORMALISE } else { 0 };
+        let st = unsafe { comms_deframe_create(n_payload, offset, lookback, bits_per_sym, ptr::null(), flags, 0, &mut h) };
+        if st != COMMS_OK { return Err(()); }
+        let node = DeframeNode { input: Default::default(), detections: Default::default(), h, output: Default::default() };
+        if let Some(ep) = word_energy {
+            if unsafe { comms_deframe_set_word_energy(node.h, ep) } != COMMS_OK { return Err(()); }
+        }
+        if unsafe { comms_deframe_set_output_format(node.h, format) } != COMMS_OK { return Err(()); }
+        Ok(node)
+    }
+    /// s of L = s (D1 - D0): 1 / (2 sigma^2).
+    pub fn set_llr_scale(&mut self, scale: f32) -> Result<(), NodeError> {
+        let st = unsafe { comms_deframe_set_llr_scale(self.h, scale) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    pub fn run(&mut self, input: &[Complex<f32>], detections: &[comms_frame_detection_t]) -> Result<Frames, NodeError> {
+        let mut cap = 0usize;
+        let st = unsafe { comms_deframe_frames_ready(self.h, input.len(), detections.as_ptr(), detections.len(), &mut cap) };
+        if st != COMMS_OK { return Err(to_err(st)); }
+        let frame_bytes = unsafe { comms_deframe_frame_bytes(self.h) };
+        let mut out = Frames { data: vec![0u8; cap * frame_bytes], headers: vec![comms_deframe_header_t::default(); cap], frame_bytes };
+        let mut found = 0usize;
+        let st = unsafe {
+            comms_deframe_run(self.h, input.as_ptr(), input.len(), detections.as_ptr(), detections.len(),
+                              out.data.as_mut_ptr() as *mut c_void, cap, out.headers.as_mut_ptr(), &mut found)
+        };
+        if st != COMMS_OK { return Err(to_err(st)); }
+        Ok(out)
+    }
+    /// Drops the incomplete frames and returns how many; the history is zero afterwards, the position kept.
+    pub fn flush(&mut self) -> Result<usize, NodeError> {
+        let mut dropped = 0usize;
+        let st = unsafe { comms_deframe_flush(self.h, &mut dropped) };
+        if st == COMMS_OK { Ok(dropped) } else { Err(to_err(st)) }
+    }
+    pub fn position(&self) -> u64 {
+        let mut t = 0u64;
+        unsafe { comms_deframe_get_position(self.h, &mut t) };
+        t
+    }
+}
+
 /// demodulation/nco.rs:118-133 in block form: a vector of phase errors per message.
 #[derive(Node)]
 #[pass_by_ref]
