@@ -60,13 +60,13 @@ struct comms_chain : Handle {
     bool ran_poly8 = false;    // Decim / DecimAny: the last call ran fir_poly8_kernel (comms_chain_is_fused)
     size_t rate = 1;
     bool fm_demod = false;
-    comms_fir_t* fir = nullptr;
+    InnerHandle<comms_fir_t, comms_fir_destroy> fir;
     // fused kinds: oscillator phase and FM demod state
     uint64_t turns = 0, frac = 0;
     History fm_prev;  // has_fm_prev: FM.prev, one sample
     // series kinds
-    comms_mixer_t* mixer = nullptr;
-    comms_fmdemod_t* fm = nullptr;  // (and fm_separate)
+    InnerHandle<comms_mixer_t, comms_mixer_destroy> mixer;
+    InnerHandle<comms_fmdemod_t, comms_fmdemod_destroy> fm;  // (and fm_separate)
     double dphase = 0.0;  // wrapped, as the mixer steps it
     Scratch t1, t2, t3;
     History raw_hist;                          // has_raw_history: last n_eff raw inputs
@@ -77,6 +77,7 @@ struct comms_chain : Handle {
     int out_bits = 0;                          // COMMS_SYM_BITS output: bits per symbol (0: Complex<f32> / FM angles)
     SymTable out_sym{};                        // ... and the decision table (comms_chain_set_output_format)
 };
+static_assert(!std::is_copy_constructible_v<comms_chain>, "a handle is never copied");
 
 // bytes of a call's output of n_dec decimated samples
 static size_t chain_out_bytes(const comms_chain* h, size_t n_dec) {
@@ -91,7 +92,7 @@ static size_t chain_out_bytes(const comms_chain* h, size_t n_dec) {
 static comms_status_t chain_flush_raw_state(comms_chain* h) {
     if (h->pending_raw.empty()) return COMMS_OK;
     double ph = 0.0;
-    COMMS_TRY(comms_mixer_get_phase(h->mixer, &ph));
+    COMMS_TRY(comms_mixer_get_phase(h->mixer.get(), &ph));
     const size_t n_state = h->pending_raw.size();
     std::vector<comms_c32> mixed(n_state);
     for (size_t k = 0; k < n_state; ++k) {
@@ -102,22 +103,7 @@ static comms_status_t chain_flush_raw_state(comms_chain* h) {
         mixed[k].im = static_cast<float>(re * s + im * c);
     }
     h->pending_raw.clear();
-    return comms_fir_set_state(h->fir, mixed.data(), n_state);
-}
-
-static void free_chain(comms_chain* h) {
-    if (h->mixer) comms_mixer_destroy(h->mixer);
-    if (h->fir) comms_fir_destroy(h->fir);
-    if (h->fm) comms_fmdemod_destroy(h->fm);
-    (void)use_device(h->device);
-    h->fm_prev.release();
-    h->raw_hist.release();
-    h->t1.release();
-    h->t2.release();
-    h->t3.release();
-    h->t0.release();
-    h->fini();
-    delete h;
+    return comms_fir_set_state(h->fir.get(), mixed.data(), n_state);
 }
 
 // Which kind runs this chain, decided once from the filter (the user's taps), the rate and the COMMS_CHAIN_* flags.
@@ -239,41 +225,41 @@ comms_status_t comms_chain_create_ex(double dphase, double phase, const comms_c3
     *out = nullptr;
     COMMS_ARG(rate >= 1, "rate must be >= 1");
     COMMS_ARG(std::isfinite(dphase) && std::isfinite(phase), "dphase/phase must be finite");
-    comms_chain* h = nullptr;
+    HandlePtr<comms_chain> h;
     COMMS_TRY(make_handle(device, &h));
     h->rate = rate;
     h->dphase = mix_wrap_dphase(dphase);
     h->fm_demod = (flags & COMMS_CHAIN_FM_DEMOD) != 0;
     h->time_domain = (flags & COMMS_CHAIN_TIME_DOMAIN) != 0;
-    const comms_status_t st = [&]() -> comms_status_t {
-        COMMS_TRY(comms_fir_create(taps, n_taps, nullptr, 0, device, &h->fir));
-        const ChainPlan p = plan_chain(h->fir, rate, flags);
-        h->kind = p.kind;
-        h->fm_separate = p.fm_separate;
-        h->mode = p.mode;
-        if (p.taps_modulated) {
-            const std::vector<comms_c32> mod = modulated_taps(taps, n_taps, h->dphase);
-            comms_fir_destroy(h->fir);
-            h->fir = nullptr;
-            COMMS_TRY(comms_fir_create(mod.data(), n_taps, nullptr, 0, device, &h->fir));
-        }
-        if (is_fused(p.kind)) {
-            h->frac = mix_to_turns(h->dphase);
-            h->turns = mix_to_turns(phase);
-        } else {
-            COMMS_TRY(comms_mixer_create(dphase, phase, device, &h->mixer));
-        }
-        if (p.fm_separate) COMMS_TRY(comms_fmdemod_create(device, &h->fm));
-        hipError_t e = has_fm_prev(p.kind) ? h->fm_prev.alloc(1, sizeof(float2)) : hipSuccess;
-        if (e == hipSuccess && has_raw_history(p.kind)) e = h->raw_hist.alloc(static_cast<size_t>(h->fir->n_eff), sizeof(float2));
-        if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "chain state alloc: %s", hipGetErrorString(e));
-        return COMMS_OK;
-    }();
-    if (st != COMMS_OK) {
-        free_chain(h);
-        return st;
+    comms_fir_t* fir = nullptr;
+    COMMS_TRY(comms_fir_create(taps, n_taps, nullptr, 0, device, &fir));
+    h->fir.reset(fir);
+    const ChainPlan p = plan_chain(fir, rate, flags);
+    h->kind = p.kind;
+    h->fm_separate = p.fm_separate;
+    h->mode = p.mode;
+    if (p.taps_modulated) {
+        const std::vector<comms_c32> mod = modulated_taps(taps, n_taps, h->dphase);
+        h->fir.reset();
+        COMMS_TRY(comms_fir_create(mod.data(), n_taps, nullptr, 0, device, &fir));
+        h->fir.reset(fir);
     }
-    *out = h;
+    if (is_fused(p.kind)) {
+        h->frac = mix_to_turns(h->dphase);
+        h->turns = mix_to_turns(phase);
+    } else {
+        comms_mixer_t* mixer = nullptr;
+        COMMS_TRY(comms_mixer_create(dphase, phase, device, &mixer));
+        h->mixer.reset(mixer);
+    }
+    if (p.fm_separate) {
+        comms_fmdemod_t* fm = nullptr;
+        COMMS_TRY(comms_fmdemod_create(device, &fm));
+        h->fm.reset(fm);
+    }
+    if (has_fm_prev(p.kind)) COMMS_HIP_TRY(h->fm_prev.alloc(1, sizeof(float2)));
+    if (has_raw_history(p.kind)) COMMS_HIP_TRY(h->raw_hist.alloc(static_cast<size_t>(h->fir->n_eff), sizeof(float2)));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -337,39 +323,39 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
         float2* prev_new = h->fm_prev.next<float2>();
         switch (h->kind) {
             case ChainKind::Os4096Dec:
-                COMMS_TRY(comms_fir_run_os4096_decim_dev(h->fir, d_in, n, stage_out, h->turns, h->frac, rate, s));
+                COMMS_TRY(comms_fir_run_os4096_decim_dev(h->fir.get(), d_in, n, stage_out, h->turns, h->frac, rate, s));
                 break;
             case ChainKind::Os16kDec:
-                COMMS_TRY(comms_fir_run_os16k_decim_dev(h->fir, d_in, n, stage_out, h->turns, h->frac, rate, s));
+                COMMS_TRY(comms_fir_run_os16k_decim_dev(h->fir.get(), d_in, n, stage_out, h->turns, h->frac, rate, s));
                 break;
             case ChainKind::Decim:
             case ChainKind::DecimAny:
                 // long filters on long batches: the polyphase frequency-domain kernel, where it is the faster form (fir_poly8.hip)
-                if (h->time_domain || comms_fir_poly8_supported(h->fir, rate, h->mode, n) != 2) {
+                if (h->time_domain || comms_fir_poly8_supported(h->fir.get(), rate, h->mode, n) != 2) {
                     h->ran_poly8 = false;
                     if (h->kind == ChainKind::Decim && h->out_bits) {  // the decision in fir_decim_kernel's store stage
-                        COMMS_TRY(comms_fir_run_decim_bits_dev(h->fir, d_in, n, d_out, h->mode, h->turns, h->frac, rate, &h->out_sym, stage_out, s));
+                        COMMS_TRY(comms_fir_run_decim_bits_dev(h->fir.get(), d_in, n, d_out, h->mode, h->turns, h->frac, rate, &h->out_sym, stage_out, s));
                         decided = true;
                     } else if (h->kind == ChainKind::Decim)
-                        COMMS_TRY(comms_fir_run_decim_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
+                        COMMS_TRY(comms_fir_run_decim_dev(h->fir.get(), d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
                     else
-                        COMMS_TRY(comms_fir_run_decim_any_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
+                        COMMS_TRY(comms_fir_run_decim_any_dev(h->fir.get(), d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
                     break;
                 }
                 [[fallthrough]];
             case ChainKind::Poly8:
-                COMMS_TRY(comms_fir_run_poly8_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
+                COMMS_TRY(comms_fir_run_poly8_dev(h->fir.get(), d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
                 h->ran_poly8 = true;
                 break;
             default:
-                COMMS_TRY(comms_fir_run_fused_dev(h->fir, d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
+                COMMS_TRY(comms_fir_run_fused_dev(h->fir.get(), d_in, n, stage_out, h->mode, h->turns, h->frac, rate, prev, prev_new, s));
                 break;
         }
         h->turns += static_cast<uint64_t>(n) * h->frac;
         if (h->out_bits && !decided)
             return sym_to_bits_launch(static_cast<const comms_c32*>(stage_out), n_dec, h->out_sym, static_cast<uint8_t*>(d_out), hs);
         if (h->fm_separate)
-            return comms_fmdemod_run_dev(h->fm, static_cast<const comms_c32*>(stage_out), n_dec, static_cast<float*>(d_out), s);
+            return comms_fmdemod_run_dev(h->fm.get(), static_cast<const comms_c32*>(stage_out), n_dec, static_cast<float*>(d_out), s);
         if (h->fm_demod) h->fm_prev.flip();
         return COMMS_OK;
     }
@@ -381,14 +367,14 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
         dec = static_cast<comms_c32*>(h->t3.p);
     }
     if (h->kind == ChainKind::SeriesPost) {  // FIR, then mixer + decimate in one pass over the kept samples only
-        COMMS_TRY(comms_fir_run_dev(h->fir, d_in, n, a, s));
-        COMMS_TRY(comms_mixer_run_decim_dev(h->mixer, a, n, h->rate, dec, s));
+        COMMS_TRY(comms_fir_run_dev(h->fir.get(), d_in, n, a, s));
+        COMMS_TRY(comms_mixer_run_decim_dev(h->mixer.get(), a, n, h->rate, dec, s));
     } else {
         COMMS_TRY(h->t2.reserve(n * sizeof(comms_c32)));
         comms_c32* b = static_cast<comms_c32*>(h->t2.p);
         COMMS_TRY(chain_flush_raw_state(h));
-        COMMS_TRY(comms_mixer_run_dev(h->mixer, d_in, n, a, s));
-        COMMS_TRY(comms_fir_run_dev(h->fir, a, n, b, s));
+        COMMS_TRY(comms_mixer_run_dev(h->mixer.get(), d_in, n, a, s));
+        COMMS_TRY(comms_fir_run_dev(h->fir.get(), a, n, b, s));
         chain_raw_hist_kernel<<<dim3(1), dim3(256), 0, hs>>>(h->raw_hist.cur<float2>(), reinterpret_cast<const float2*>(d_in), n,
                                                              h->raw_hist.next<float2>(), h->fir->n_eff);
         COMMS_TRY(launch_ok("chain_raw_hist_kernel"));
@@ -397,7 +383,7 @@ comms_status_t comms_chain_run_dev(comms_chain_t* h, const comms_c32* d_in_any, 
     }
     if (h->out_bits) return sym_to_bits_launch(dec, n_dec, h->out_sym, static_cast<uint8_t*>(d_out), hs);
     if (!h->fm_demod) return COMMS_OK;
-    return comms_fmdemod_run_dev(h->fm, dec, n_dec, static_cast<float*>(d_out), s);
+    return comms_fmdemod_run_dev(h->fm.get(), dec, n_dec, static_cast<float*>(d_out), s);
 }
 
 comms_status_t comms_chain_run(comms_chain_t* h, const comms_c32* in, size_t n, void* out) {
@@ -417,7 +403,7 @@ comms_status_t comms_chain_run(comms_chain_t* h, const comms_c32* in, size_t n, 
         return comms_chain_run_dev(h, static_cast<const comms_c32*>(d_in), ib / in_elem, d_out, COMMS_STREAM_HANDLE);
     }));
     // (a long filter runs the 16384-point FIR kernel inside the series of launches: its failure is this call's)
-    return h->fir ? fir_check_sticky(h->fir) : COMMS_OK;
+    return h->fir ? fir_check_sticky(h->fir.get()) : COMMS_OK;
 }
 
 // d_in of the run entries then points to raw IQ samples of that format; the conversion (iqformat.hip's
@@ -429,7 +415,7 @@ comms_status_t comms_chain_set_input_format(comms_chain_t* h, int32_t format, fl
     COMMS_ARG(format != COMMS_IQ_I16 || std::isfinite(scale), "scale must be finite");
     h->in_fmt = format;
     h->in_scale = format == COMMS_IQ_I16 ? scale : 1.0f;
-    if (reads_wire_format(h->kind)) COMMS_TRY(comms_fir_set_input_format(h->fir, format, scale));
+    if (reads_wire_format(h->kind)) COMMS_TRY(comms_fir_set_input_format(h->fir.get(), format, scale));
     return COMMS_OK;
 }
 
@@ -452,7 +438,7 @@ comms_status_t comms_chain_set_output_format(comms_chain_t* h, int32_t format, i
 
 comms_status_t comms_chain_set_timer(comms_chain_t* h, comms_timer_t* t) {
     COMMS_ARG(h != nullptr, "handle is NULL");
-    return comms_fir_set_timer(h->fir, t);
+    return comms_fir_set_timer(h->fir.get(), t);
 }
 
 comms_status_t comms_chain_set_fir_state(comms_chain_t* h, const comms_c32* state, size_t n_state) {
@@ -460,7 +446,7 @@ comms_status_t comms_chain_set_fir_state(comms_chain_t* h, const comms_c32* stat
     COMMS_ARG(state || !n_state, "state is NULL");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    if (!has_raw_history(h->kind)) return comms_fir_set_state(h->fir, state, n_state);
+    if (!has_raw_history(h->kind)) return comms_fir_set_state(h->fir.get(), state, n_state);
     COMMS_ARG(n_state == static_cast<size_t>(h->fir->n_eff), "state must hold exactly the %d effective taps", h->fir->n_eff);
     COMMS_HIP_TRY(h->raw_hist.upload(state, n_state));
     h->pending_raw.assign(state, state + n_state);  // mixed into the FIR node's history at the next run
@@ -471,7 +457,7 @@ comms_status_t comms_chain_get_fir_state(comms_chain_t* h, comms_c32* state, siz
     COMMS_ARG(h && state, "NULL argument");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    if (!has_raw_history(h->kind)) return comms_fir_get_state(h->fir, state, n_state);
+    if (!has_raw_history(h->kind)) return comms_fir_get_state(h->fir.get(), state, n_state);
     const size_t N = static_cast<size_t>(h->fir->n_eff);
     COMMS_ARG(n_state <= N, "n_state %zu exceeds the %zu effective taps", n_state, N);
     COMMS_HIP_TRY(h->raw_hist.download(state, n_state));
@@ -481,7 +467,7 @@ comms_status_t comms_chain_get_fir_state(comms_chain_t* h, comms_c32* state, siz
 // Oscillator phase of the next input sample (radians, as comms_mixer_get_phase).
 comms_status_t comms_chain_get_phase(comms_chain_t* h, double* out_phase) {
     COMMS_ARG(h && out_phase, "NULL argument");
-    if (!is_fused(h->kind)) return comms_mixer_get_phase(h->mixer, out_phase);
+    if (!is_fused(h->kind)) return comms_mixer_get_phase(h->mixer.get(), out_phase);
     *out_phase = static_cast<double>(h->turns >> 11) * (kMixT * 0x1.0p-53);
     return COMMS_OK;
 }
@@ -489,7 +475,7 @@ comms_status_t comms_chain_get_phase(comms_chain_t* h, double* out_phase) {
 comms_status_t comms_chain_set_phase(comms_chain_t* h, double phase) {
     COMMS_ARG(h != nullptr, "handle is NULL");
     COMMS_ARG(std::isfinite(phase), "phase must be finite");
-    if (!is_fused(h->kind)) return comms_mixer_set_phase(h->mixer, phase);
+    if (!is_fused(h->kind)) return comms_mixer_set_phase(h->mixer.get(), phase);
     h->turns = mix_to_turns(phase);
     return COMMS_OK;
 }
@@ -499,7 +485,7 @@ comms_status_t comms_chain_set_phase(comms_chain_t* h, double phase) {
 comms_status_t comms_chain_get_fm_prev(comms_chain_t* h, comms_c32* out_prev) {
     COMMS_ARG(h && out_prev, "NULL argument");
     COMMS_ARG(h->fm_demod, "this chain has no FM demodulator");
-    if (h->fm_separate) return comms_fmdemod_get_prev(h->fm, out_prev);
+    if (h->fm_separate) return comms_fmdemod_get_prev(h->fm.get(), out_prev);
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
     COMMS_HIP_TRY(h->fm_prev.download(out_prev, 1));
@@ -509,17 +495,13 @@ comms_status_t comms_chain_get_fm_prev(comms_chain_t* h, comms_c32* out_prev) {
 comms_status_t comms_chain_set_fm_prev(comms_chain_t* h, const comms_c32* prev) {
     COMMS_ARG(h && prev, "NULL argument");
     COMMS_ARG(h->fm_demod, "this chain has no FM demodulator");
-    if (h->fm_separate) return comms_fmdemod_set_prev(h->fm, prev);
+    if (h->fm_separate) return comms_fmdemod_set_prev(h->fm.get(), prev);
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
     COMMS_HIP_TRY(h->fm_prev.upload(prev, 1));
     return COMMS_OK;
 }
 
-comms_status_t comms_chain_destroy(comms_chain_t* h) {
-    if (!h) return COMMS_OK;
-    free_chain(h);
-    return COMMS_OK;
-}
+comms_status_t comms_chain_destroy(comms_chain_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

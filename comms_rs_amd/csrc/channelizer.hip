@@ -261,14 +261,15 @@ struct comms_channelizer : Handle {
     bool staged = true, tab_lds = true;
     size_t lds = 0;
     unsigned max_grid = 1;
-    float* d_tab = nullptr;
-    float2* d_tw = nullptr;
+    DevBuf<float> d_tab;
+    DevBuf<float2> d_tw;
     History hist;            // last H samples
     // the series: one chain per channel (made on first use), the padded stream and the chains' outputs
     std::vector<float> taps;
-    std::vector<comms_chain_t*> chains;
+    std::vector<InnerHandle<comms_chain_t, comms_chain_destroy>> chains;
     Scratch ext, tmp;
 };
+static_assert(!std::is_copy_constructible_v<comms_channelizer>, "a handle is never copied");
 
 namespace {
 
@@ -311,19 +312,6 @@ void plan_tile(comms_channelizer* h) {
     h->lds = tab + 2 * F0 * MS * 8;
 }
 
-void free_channelizer(comms_channelizer* h) {
-    (void)use_device(h->device);
-    for (comms_chain_t* c : h->chains)
-        if (c) (void)comms_chain_destroy(c);
-    if (h->d_tab) (void)hipFree(h->d_tab);
-    if (h->d_tw) (void)hipFree(h->d_tw);
-    h->hist.release();
-    h->ext.release();
-    h->tmp.release();
-    h->fini();
-    delete h;
-}
-
 template <bool STAGED, bool TAB_LDS>
 comms_status_t launch_channelizer(const ChzArgs& a, unsigned blocks, size_t lds, hipStream_t s) {
     static DeviceOnce once;
@@ -342,18 +330,15 @@ comms_status_t ensure_chains(comms_channelizer* h) {
     if (!h->chains.empty()) return COMMS_OK;
     std::vector<comms_c32> ct(h->n_taps);
     for (size_t i = 0; i < h->n_taps; ++i) ct[i] = comms_c32{h->taps[i], 0.0f};
-    std::vector<comms_chain_t*> made(h->M, nullptr);
+    std::vector<InnerHandle<comms_chain_t, comms_chain_destroy>> made(h->M);  // all M of them, or none
     for (size_t k = 0; k < h->M; ++k) {
         const double dphase = -kMixT * (static_cast<double>(k) / static_cast<double>(h->M));
-        comms_status_t st = comms_chain_create_ex(dphase, 0.0, ct.data(), h->n_taps, h->D, 0, h->device, &made[k]);
-        if (st != COMMS_OK) {
-            for (comms_chain_t* c : made)
-                if (c) (void)comms_chain_destroy(c);
-            return st;
-        }
+        comms_chain_t* c = nullptr;
+        COMMS_TRY(comms_chain_create_ex(dphase, 0.0, ct.data(), h->n_taps, h->D, 0, h->device, &c));
+        made[k].reset(c);
     }
     h->chains.swap(made);
-    if (h->timer) COMMS_TRY(comms_chain_set_timer(h->chains[0], h->timer));
+    if (h->timer) COMMS_TRY(comms_chain_set_timer(h->chains[0].get(), h->timer));
     return COMMS_OK;
 }
 
@@ -375,8 +360,8 @@ comms_status_t run_series(comms_channelizer* h, const float2* d_in, size_t n, fl
     const uint64_t t0 = (h->r + M - P % M) % M;  // (t - P) mod M: the stream index of ext[0]
     for (size_t k = 0; k < M; ++k) {
         const uint64_t turn = ((M - k) % M) * t0 % M;  // -(k t0) mod M
-        COMMS_TRY(comms_chain_set_phase(h->chains[k], kMixT * (static_cast<double>(turn) / static_cast<double>(M))));
-        COMMS_TRY(comms_chain_run_dev(h->chains[k], reinterpret_cast<const comms_c32*>(ext), total, tmp + k * row, s));
+        COMMS_TRY(comms_chain_set_phase(h->chains[k].get(), kMixT * (static_cast<double>(turn) / static_cast<double>(M))));
+        COMMS_TRY(comms_chain_run_dev(h->chains[k].get(), reinterpret_cast<const comms_c32*>(ext), total, tmp + k * row, s));
     }
     const size_t outs = frames * M;
     const unsigned sblocks = static_cast<unsigned>(std::min<size_t>((outs + 255) / 256, static_cast<size_t>(kNumCU) * 8));
@@ -424,7 +409,7 @@ comms_status_t comms_channelizer_create(const float* taps, size_t n_taps, size_t
     const bool series = !in_kernel_range(channels, n_taps, D);
     COMMS_ARG(!series || channels <= CHZ_MAX_SERIES_M, "%zu channels: outside the kernel's range the node runs one chain per channel, at most %zu",
               channels, CHZ_MAX_SERIES_M);
-    comms_channelizer* h = nullptr;
+    HandlePtr<comms_channelizer> h;
     COMMS_TRY(make_handle(device, &h));
     h->n_taps = n_taps;
     h->M = channels;
@@ -433,12 +418,12 @@ comms_status_t comms_channelizer_create(const float* taps, size_t n_taps, size_t
     h->layout = layout;
     h->series = series;
     h->taps.assign(taps, taps + n_taps);
-    hipError_t e = h->hist.alloc(h->H, sizeof(float2));
-    if (e == hipSuccess && !series) {
+    COMMS_HIP_TRY(h->hist.alloc(h->H, sizeof(float2)));
+    if (!series) {
         const size_t M = channels;
         while ((static_cast<size_t>(1) << h->lgM) < M) ++h->lgM;
         h->Q = static_cast<int>((n_taps + M - 1) / M);
-        plan_tile(h);
+        plan_tile(h.get());
         h->max_grid = resident_workgroups(h->lds);
         const int cap = diag_knob("COMMS_CHANNELIZER_GRID", 0);  // sweeps: fewer workgroups
         if (cap > 0 && static_cast<unsigned>(cap) < h->max_grid) h->max_grid = static_cast<unsigned>(cap);
@@ -449,23 +434,11 @@ comms_status_t comms_channelizer_create(const float* taps, size_t n_taps, size_t
             const double ang = 2.0 * 3.14159265358979323846264338327950288 * static_cast<double>(m) / static_cast<double>(M);
             tw[m] = make_float2(static_cast<float>(cos(ang)), static_cast<float>(sin(ang)));
         }
-        e = hipMalloc(reinterpret_cast<void**>(&h->d_tab), tab.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(h->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_tw), tw.size() * sizeof(float2));
-        if (e == hipSuccess) e = hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice);
+        COMMS_HIP_TRY(h->d_tab.upload(tab));
+        COMMS_HIP_TRY(h->d_tw.upload(tw));
     }
-    if (e != hipSuccess) {
-        free_channelizer(h);
-        return fail(COMMS_ERR_DEVICE, "channelizer alloc: %s", hipGetErrorString(e));
-    }
-    if (series) {
-        const comms_status_t st = ensure_chains(h);
-        if (st != COMMS_OK) {
-            free_channelizer(h);
-            return st;
-        }
-    }
-    *out = h;
+    if (series) COMMS_TRY(ensure_chains(h.get()));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -491,8 +464,8 @@ comms_status_t comms_channelizer_run_dev(comms_channelizer_t* h, const comms_c32
         a.hist = h->hist.cur<float2>();
         a.new_hist = h->hist.next<float2>();
         a.out = out;
-        a.taps = h->d_tab;
-        a.tw = h->d_tw;
+        a.taps = h->d_tab.get();
+        a.tw = h->d_tw.get();
         a.n = n;
         a.frames = frames;
         const unsigned grid = chz_grid(h, frames, &a.tiles, &a.tiles_per_wg);
@@ -568,7 +541,7 @@ comms_status_t comms_channelizer_get_kernel(const comms_channelizer_t* h, size_t
     COMMS_ARG(h && name && name_len, "NULL argument");
     if (h->series || forced_series()) {
         int32_t kind = -1;  // comms_chain_is_fused of the channels' chains (made on first use where the series is forced)
-        if (!h->chains.empty()) COMMS_TRY(comms_chain_is_fused(h->chains[0], &kind));
+        if (!h->chains.empty()) COMMS_TRY(comms_chain_is_fused(h->chains[0].get(), &kind));
         std::snprintf(name, name_len, "series: chz_prep_kernel + %zu x comms_chain (kind %d) + chz_scatter_kernel", h->M, kind);
     } else {
         size_t tiles = 0, per = 0;
@@ -583,16 +556,10 @@ comms_status_t comms_channelizer_get_kernel(const comms_channelizer_t* h, size_t
 comms_status_t comms_channelizer_set_timer(comms_channelizer_t* h, comms_timer_t* t) {
     COMMS_ARG(h != nullptr, "handle is NULL");
     h->timer = t;
-    if (!h->chains.empty()) return comms_chain_set_timer(h->chains[0], t);  // the series: the pair brackets channel 0's FIR launch
+    if (!h->chains.empty()) return comms_chain_set_timer(h->chains[0].get(), t);  // the series: the pair brackets channel 0's FIR launch
     return COMMS_OK;
 }
 
-comms_status_t comms_channelizer_destroy(comms_channelizer_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    (void)h->quiesce();
-    free_channelizer(h);
-    return COMMS_OK;
-}
+comms_status_t comms_channelizer_destroy(comms_channelizer_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

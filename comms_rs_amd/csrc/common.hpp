@@ -10,9 +10,12 @@
 #include <cstdio>
 #include <cstring>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/comms_hip.h"
@@ -140,10 +143,18 @@ struct DeviceOnce {
     }
 };
 
+// ---- owners of device and pinned memory -----------------------------------------------------------------------------
+// Every allocation of a handle is a member of one of these types (Scratch, Pinned, DevBuf, History): freed by its
+// destructor, never copied.  They are the only places of the library (runtime.hip's pools aside) that free memory.
+
 // Grow-only device scratch used by the host-pointer (`*_run`) entry points.
 struct Scratch {
     void* p = nullptr;
     size_t cap = 0;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { release(); }
     comms_status_t reserve(size_t bytes) {
         if (bytes <= cap) return COMMS_OK;
         if (p) {
@@ -171,6 +182,10 @@ struct Pinned {
     void* h = nullptr;  // host address
     void* d = nullptr;  // the same memory as the device sees it
     size_t cap = 0;
+    Pinned() = default;
+    Pinned(const Pinned&) = delete;
+    Pinned& operator=(const Pinned&) = delete;
+    ~Pinned() { release(); }
     comms_status_t reserve(size_t bytes) {
         if (bytes <= cap) return COMMS_OK;
         release();
@@ -202,6 +217,48 @@ inline hipError_t zero_device(void* p, size_t bytes) {
     return e;
 }
 
+// A device array of n elements of T, fixed once allocated (alloc again replaces it).  The three ways a create fills
+// one: left as allocated, zero-filled and waited for (zero_device), or uploaded from a host array (synchronous).
+template <class T>
+struct DevBuf {
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = std::exchange(o.p_, nullptr);
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    T* get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    hipError_t alloc(size_t n) {
+        reset();
+        return hipMalloc(reinterpret_cast<void**>(&p_), n * sizeof(T));
+    }
+    hipError_t alloc_zero(size_t n) {
+        hipError_t e = alloc(n);
+        if (e == hipSuccess) e = zero_device(p_, n * sizeof(T));
+        return e;
+    }
+    hipError_t upload(const T* host, size_t n) {
+        hipError_t e = alloc(n);
+        if (e == hipSuccess) e = hipMemcpy(p_, host, n * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
+    hipError_t upload(const std::vector<T>& v) { return upload(v.data(), v.size()); }
+
+private:
+    T* p_ = nullptr;
+};
+
 // The sample history every stateful node carries from one launch to the next: the last `len` samples in time order
 // (the "ring" of history_order.hpp), twice.  A launch reads cur() and writes the advanced history to next() -- all
 // `len` entries of it, so next() never needs a defined content -- and the host calls flip() once the launch is queued.
@@ -211,6 +268,10 @@ struct History {
     void* buf[2] = {nullptr, nullptr};
     size_t len = 0, elem = 0;  // samples kept, bytes per sample
     int idx = 0;
+    History() = default;
+    History(const History&) = delete;
+    History& operator=(const History&) = delete;
+    ~History() { release(); }
     // both buffers zero-filled (at least one sample each: an empty history still hands the kernels a valid address)
     hipError_t alloc(size_t n_elems, size_t elem_bytes) {
         len = n_elems;
@@ -248,6 +309,9 @@ struct History {
         return e;
     }
 };
+static_assert(!std::is_copy_constructible_v<Scratch> && !std::is_copy_constructible_v<Pinned> &&
+                  !std::is_copy_constructible_v<DevBuf<float>> && !std::is_copy_constructible_v<History>,
+              "the owners of device memory are never copied");
 
 // calls moving at most this many bytes each way take the zero-copy route (COMMS_ZERO_COPY_BYTES)
 size_t zero_copy_limit();
@@ -591,69 +655,79 @@ struct Handle {
         return COMMS_OK;
     }
 
-    void fini() {
+    // Runs after the members of the derived handle have gone (their device memory is freed first), on the handle's
+    // device (HandleDelete): staging freed, the streams back to the device's pool.
+    Handle() = default;
+    Handle(const Handle&) = delete;
+    Handle& operator=(const Handle&) = delete;
+    ~Handle() {
         set_following(nullptr);
         for (hipEvent_t e : pipe_events) (void)hipEventDestroy(e);
-        pipe_events.clear();
         if (out_stream) stream_release(device, out_stream);
-        out_stream = nullptr;
         in_scratch.release();
         out_scratch.release();
         pin_in.release();
         pin_out.release();
         if (stream) stream_release(device, stream);
-        stream = nullptr;
         if (counted) handle_count(device, -1);
-        counted = false;
     }
 };
 
+// The one owner of a handle: its deleter selects the handle's device (the current device is thread-local, and the
+// members' destructors free device memory), then deletes.  Creates hold their handle in one until `*out = h.release()`,
+// so every failure exit is a plain return; inner handles of a handle (the chain's FIR, a channelizer's chains) are
+// members of this type.
+struct HandleDelete {
+    template <class H>
+    void operator()(H* h) const {
+        if (h->stream) (void)use_device(h->device);  // (no stream: init failed, nothing on any device yet)
+        delete h;
+    }
+};
+template <class H>
+using HandlePtr = std::unique_ptr<H, HandleDelete>;
+
 // What every *_create starts with: a handle of its own stream on `device`, or the error and no handle
 template <class H>
-comms_status_t make_handle(int32_t device, H** out) {
-    H* h = new (std::nothrow) H;
+comms_status_t make_handle(int32_t device, HandlePtr<H>* out, bool count_me = true) {
+    HandlePtr<H> h(new (std::nothrow) H);
     COMMS_ARG(h != nullptr, "out of host memory");
-    const comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
-    *out = h;
+    COMMS_TRY(h->init(device, count_me));
+    *out = std::move(h);
     return COMMS_OK;
 }
+// ... and the body of every *_destroy: the handle drained (the launches pending on the stream it followed last may
+// still touch its memory; a failure to wait changes nothing about what follows), then deleted.  NULL is fine.
+template <class H>
+comms_status_t destroy_handle(H* h) {
+    if (!h) return COMMS_OK;
+    (void)use_device(h->device);
+    (void)h->quiesce();
+    HandleDelete{}(h);
+    return COMMS_OK;
+}
+// An inner handle whose type is opaque where it is held (the chain's mixer): made by its public create, ended by its
+// public destroy -- which is destroy_handle again
+template <auto Destroy>
+struct DestroyWith {
+    template <class H>
+    void operator()(H* h) const {
+        (void)Destroy(h);
+    }
+};
+template <class H, auto Destroy>
+using InnerHandle = std::unique_ptr<H, DestroyWith<Destroy>>;
 
 // Handle-less host-pointer entry points (resampling, IQ formats, estimators) borrow a per-thread,
 // per-device handle (stream + staging), created on first use and kept for the thread's life:
 // no hipMalloc / hipFree -- which also synchronise the device -- per call.  The handles END with their thread
 // (comms-rs starts one thread per node, src/node/mod.rs:276-284: a graph that is torn down and rebuilt must not leave
 // a pooled stream, device scratch and pinned staging behind per retired node thread).
-struct ThreadHandles {
-    Handle* h[64] = {};
-    ~ThreadHandles() {
-        for (Handle*& p : h) {
-            if (!p) continue;
-            (void)use_device(p->device);
-            p->fini();  // scratch and staging freed, the stream back to the device's pool
-            delete p;
-            p = nullptr;
-        }
-    }
-};
 inline comms_status_t thread_handle(int32_t device, Handle** out) {
-    static thread_local ThreadHandles th;
-    Handle** tl = th.h;
+    static thread_local HandlePtr<Handle> th[64];
     COMMS_ARG(device >= 0 && device < 64, "device index out of range");
-    if (!tl[device]) {
-        Handle* nh = new (std::nothrow) Handle;
-        COMMS_ARG(nh != nullptr, "out of host memory");
-        comms_status_t st = nh->init(device, false);
-        if (st != COMMS_OK) {
-            delete nh;
-            return st;
-        }
-        tl[device] = nh;
-    }
-    *out = tl[device];
+    if (!th[device]) COMMS_TRY(make_handle(device, &th[device], false));
+    *out = th[device].get();
     return COMMS_OK;
 }
 

@@ -127,17 +127,9 @@ struct comms_deframe : Handle {
     Scratch desc_dev;          // ... and where the launch reads it
     History hist;              // last H symbols
 };
+static_assert(!std::is_copy_constructible_v<comms_deframe>, "a handle is never copied");
 
 namespace {
-
-void free_deframe(comms_deframe* h) {
-    (void)use_device(h->device);
-    h->desc_host.release();
-    h->desc_dev.release();
-    h->hist.release();
-    h->fini();
-    delete h;
-}
 
 comms_status_t check_shape(size_t n_payload, size_t lookback) {
     COMMS_ARG(n_payload >= 1 && n_payload <= DF_MAX_PAYLOAD, "n_payload must be 1 ... %zu symbols (got %zu)", DF_MAX_PAYLOAD, n_payload);
@@ -297,7 +289,7 @@ comms_status_t comms_deframe_create(size_t n_payload, size_t offset, size_t look
     COMMS_ARG((flags & ~COMMS_DEFRAME_NORMALISE) == 0, "unknown flags 0x%x", flags);
     SymTable t{};
     COMMS_TRY(sym_table(bits_per_sym, constellation, &t));
-    comms_deframe* h = nullptr;
+    HandlePtr<comms_deframe> h;
     COMMS_TRY(make_handle(device, &h));
     h->F = n_payload;
     h->offset = offset;
@@ -306,12 +298,8 @@ comms_status_t comms_deframe_create(size_t n_payload, size_t offset, size_t look
     h->normalise = (flags & COMMS_DEFRAME_NORMALISE) != 0;
     h->table = t;
     h->max_grid = resident_workgroups(0);
-    const hipError_t e = h->hist.alloc(static_cast<size_t>(h->H), sizeof(comms_c32));
-    if (e != hipSuccess) {
-        free_deframe(h);
-        return fail(COMMS_ERR_DEVICE, "deframer alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->hist.alloc(static_cast<size_t>(h->H), sizeof(comms_c32)));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -479,12 +467,6 @@ comms_status_t comms_deframe_set_timer(comms_deframe_t* h, comms_timer_t* t) {
     return COMMS_OK;
 }
 
-comms_status_t comms_deframe_destroy(comms_deframe_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    (void)h->quiesce();
-    free_deframe(h);
-    return COMMS_OK;
-}
+comms_status_t comms_deframe_destroy(comms_deframe_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

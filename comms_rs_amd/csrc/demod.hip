@@ -384,18 +384,20 @@ using namespace comms;
 
 struct comms_timing : Handle {
     uint32_t n = 0, d = 0, n_q = 0;
-    double* d_taps = nullptr;
-    double2* d_part = nullptr;
+    DevBuf<double> d_taps;
+    DevBuf<double2> d_part;
     unsigned max_blocks = 4 * kNumCU;
     Scratch qacc;  // running filter sums between the passes of a filter longer than TE_QMAX taps
 };
+static_assert(!std::is_copy_constructible_v<comms_timing>, "a handle is never copied");
 
 struct comms_nco : Handle {
     double dphase = 0.0;
-    uint64_t* d_phase = nullptr;  // fixed-point turns, device resident
-    double2* d_tab = nullptr;     // (cos, sin)(2 pi k / 1024), f64
+    DevBuf<uint64_t> d_phase;  // fixed-point turns, device resident
+    DevBuf<double2> d_tab;     // (cos, sin)(2 pi k / 1024), f64
     Scratch tiles;
 };
+static_assert(!std::is_copy_constructible_v<comms_nco>, "a handle is never copied");
 
 static comms_status_t qfilt_host(uint32_t n_taps, double alpha, uint32_t sam_per_sym, std::vector<double>& out) {
     COMMS_ARG(alpha >= 0.0 && alpha <= 1.0, "InvalidRolloffError: alpha=%g outside [0,1]", alpha);
@@ -437,27 +439,15 @@ comms_status_t comms_timing_create(uint32_t n, uint32_t d, double alpha, int32_t
     COMMS_ARG(static_cast<uint64_t>(n) * d < (1u << 24), "filter delay n*d too large");
     std::vector<double> taps;
     COMMS_TRY(qfilt_host(2 * n * d + 1, alpha, n, taps));
-    comms_timing* h = new (std::nothrow) comms_timing;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    HandlePtr<comms_timing> h;
+    COMMS_TRY(make_handle(device, &h));
     h->n = n;
     h->d = d;
     h->n_q = static_cast<uint32_t>(taps.size());
     taps.resize((taps.size() + 11) / 12 * 12, 0.0);  // the kernel walks the taps in blocks of 12; zero taps add nothing
-    hipError_t e = hipMalloc(&h->d_taps, taps.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(h->d_taps, taps.data(), taps.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&h->d_part, h->max_blocks * sizeof(double2));
-    if (e != hipSuccess) {
-        if (h->d_taps) (void)hipFree(h->d_taps);
-        h->fini();
-        delete h;
-        return fail(COMMS_ERR_DEVICE, "timing estimator alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->d_taps.upload(taps));
+    COMMS_HIP_TRY(h->d_part.alloc(h->max_blocks));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -491,13 +481,13 @@ comms_status_t comms_timing_push_dev(comms_timing_t* h, const double* d_samples,
             const int win = TE_TILE + static_cast<int>(nk) - 1;
             const size_t lds = (static_cast<size_t>(win + 1 + ((win + 1) >> 3)) + 1) * sizeof(double2);  // te_slot(win + 1) + 1 slots
             timing_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(TE_WG), lds, s>>>(
-                reinterpret_cast<const double2*>(d_samples), len, h->d_taps + k_lo, nk, k_lo, h->n * h->d,
-                static_cast<double>(h->n), w_wg, w_1, p + 1 == n_pass ? 1 : 0, qacc, h->d_part);
+                reinterpret_cast<const double2*>(d_samples), len, h->d_taps.get() + k_lo, nk, k_lo, h->n * h->d,
+                static_cast<double>(h->n), w_wg, w_1, p + 1 == n_pass ? 1 : 0, qacc, h->d_part.get());
         }
         h->toc(s);
         COMMS_TRY(launch_ok("timing_kernel"));
         std::vector<double2> part(blocks);
-        COMMS_HIP_TRY(hipMemcpyAsync(part.data(), h->d_part, blocks * sizeof(double2), hipMemcpyDeviceToHost, s));
+        COMMS_HIP_TRY(hipMemcpyAsync(part.data(), h->d_part.get(), blocks * sizeof(double2), hipMemcpyDeviceToHost, s));
         COMMS_HIP_TRY(hipStreamSynchronize(s));
         for (size_t b = 0; b < blocks; ++b) {
             re += part[b].x;
@@ -520,29 +510,15 @@ comms_status_t comms_timing_push(comms_timing_t* h, const double* samples, size_
     return comms_timing_push_dev(h, static_cast<const double*>(h->in_scratch.p), len, estimate, COMMS_STREAM_HANDLE);
 }
 
-comms_status_t comms_timing_destroy(comms_timing_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    if (h->d_taps) (void)hipFree(h->d_taps);
-    if (h->d_part) (void)hipFree(h->d_part);
-    h->qacc.release();
-    h->fini();
-    delete h;
-    return COMMS_OK;
-}
+comms_status_t comms_timing_destroy(comms_timing_t* h) { return destroy_handle(h); }
 
 // ---- NCO -------------------------------------------------------------------------
 comms_status_t comms_nco_create(double dphase, double phase, int32_t device, comms_nco_t** out) {
     COMMS_ARG(out != nullptr, "out is NULL");
     *out = nullptr;
     COMMS_ARG(std::isfinite(dphase) && std::isfinite(phase), "dphase and phase must be finite");
-    comms_nco* h = new (std::nothrow) comms_nco;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    HandlePtr<comms_nco> h;
+    COMMS_TRY(make_handle(device, &h));
     h->dphase = mix_wrap_dphase(dphase);  // Nco::new, nco.rs:41-49 (same wrap as Mixer::new)
     const uint64_t turns = mix_to_turns(phase);
     std::vector<double2> tab(1024);
@@ -550,15 +526,9 @@ comms_status_t comms_nco_create(double dphase, double phase, int32_t device, com
         const long double a = 2.0L * 3.14159265358979323846264338327950288L * static_cast<long double>(k) / 1024.0L;
         tab[k] = make_double2(static_cast<double>(cosl(a)), static_cast<double>(sinl(a)));
     }
-    hipError_t e = hipMalloc(&h->d_phase, sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMemcpy(h->d_phase, &turns, sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&h->d_tab, tab.size() * sizeof(double2));
-    if (e == hipSuccess) e = hipMemcpy(h->d_tab, tab.data(), tab.size() * sizeof(double2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        comms_nco_destroy(h);
-        return fail(COMMS_ERR_DEVICE, "nco state alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->d_phase.upload(&turns, 1));
+    COMMS_HIP_TRY(h->d_tab.upload(tab));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -581,8 +551,8 @@ comms_status_t comms_nco_run_dev(comms_nco_t* h, const double* d_perr, size_t n,
     const unsigned blocks = static_cast<unsigned>(ntiles < slots ? ntiles : slots);
     h->tic(s);
     nco_sum_kernel<<<dim3(blocks), dim3(NCO_WG), 0, s>>>(d_perr, n, h->dphase, tiles, ntiles);
-    nco_scan_kernel<<<dim3(1), dim3(1024), 0, s>>>(tiles, ntiles, h->d_phase);
-    nco_apply_kernel<<<dim3(blocks), dim3(NCO_WG), 0, s>>>(d_perr, n, h->dphase, tiles, ntiles, h->d_tab,
+    nco_scan_kernel<<<dim3(1), dim3(1024), 0, s>>>(tiles, ntiles, h->d_phase.get());
+    nco_apply_kernel<<<dim3(blocks), dim3(NCO_WG), 0, s>>>(d_perr, n, h->dphase, tiles, ntiles, h->d_tab.get(),
                                                           reinterpret_cast<double2*>(d_out));
     h->toc(s);
     COMMS_TRY(launch_ok("nco kernels"));
@@ -609,20 +579,11 @@ comms_status_t comms_nco_get_phase(comms_nco_t* h, double* phase) {
     COMMS_TRY(use_device(h->device));
     uint64_t turns = 0;
     COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(hipMemcpy(&turns, h->d_phase, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    COMMS_HIP_TRY(hipMemcpy(&turns, h->d_phase.get(), sizeof(uint64_t), hipMemcpyDeviceToHost));
     *phase = static_cast<double>(turns >> 11) * (kMixT * 0x1.0p-53);
     return COMMS_OK;
 }
 
-comms_status_t comms_nco_destroy(comms_nco_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    if (h->d_phase) (void)hipFree(h->d_phase);
-    if (h->d_tab) (void)hipFree(h->d_tab);
-    h->tiles.release();
-    h->fini();
-    delete h;
-    return COMMS_OK;
-}
+comms_status_t comms_nco_destroy(comms_nco_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

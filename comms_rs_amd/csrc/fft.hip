@@ -1211,44 +1211,25 @@ struct Pow2Plan {
     size_t N = 0;
     int n_pass = 0;
     FftTileParams pass[2];
-    float2* d_tw[4] = {nullptr, nullptr, nullptr, nullptr};  // twL(pass0), twL(pass1), tw_lo, tw_hi
-    float2* d_fw1 = nullptr;  // fast 16x1024 kernel: W1024^{lane*k0} [16][64]
-    float2* d_fw2 = nullptr;  //                       W64^{c*k1}     [16][4]
+    DevBuf<float2> d_tw[4];  // twL(pass0), twL(pass1), tw_lo, tw_hi
+    DevBuf<float2> d_fw1;  // fast 16x1024 kernel: W1024^{lane*k0} [16][64]
+    DevBuf<float2> d_fw2;  //                       W64^{c*k1}     [16][4]
     int rx_rad = 0;           // N = rx_rad * 1024 (2, 4, 8, 16): single-pass fft_rx1024_kernel
-    float2* d_rxa = nullptr;  //   W_N^{64*wave*k1} [rad][16]
-    float2* d_rxb = nullptr;  //   W_N^{lane*k1}    [rad][64]
-    float2* d_rx32 = nullptr;  // N = 32768 in one pass (fft_rx32k_kernel): W_N^{t}, W_N^{4 t}, W_N^{16 t}, t < 1024
+    DevBuf<float2> d_rxa;  //   W_N^{64*wave*k1} [rad][16]
+    DevBuf<float2> d_rxb;  //   W_N^{lane*k1}    [rad][64]
+    DevBuf<float2> d_rx32;  // N = 32768 in one pass (fft_rx32k_kernel): W_N^{t}, W_N^{4 t}, W_N^{16 t}, t < 1024
     int col_kind = -1;         // four-step pass 1 on fft_cols_kernel: 0 (N1 = 64), 128, 256, 512; -1: tile kernel
-    float2* d_colw1 = nullptr; //   the core's stage table (W256^{b*ka} for the 256-point form, else unused)
-    float2* d_colr = nullptr;  //   W_N1^{r}, r < N1/2 (radix-2 front stage of 128 / 512)
+    DevBuf<float2> d_colw1; //   the core's stage table (W256^{b*ka} for the 256-point form, else unused)
+    DevBuf<float2> d_colr;  //   W_N1^{r}, r < N1/2 (radix-2 front stage of 128 / 512)
     int threads[2] = {0, 0};
     size_t lds[2] = {0, 0};
-    Pow2Plan* rows = nullptr;  // N = 2^21 ... 2^24: the plan of the N2-point row transforms (columns: pass[0]; then the transpose)
+    std::unique_ptr<Pow2Plan> rows;  // N = 2^21 ... 2^24: the plan of the N2-point row transforms (columns: pass[0]; then the transpose)
 
-    void release() {
-        if (rows) {
-            rows->release();
-            delete rows;
-            rows = nullptr;
-        }
-        for (auto& p : d_tw)
-            if (p) {
-                (void)hipFree(p);
-                p = nullptr;
-            }
-        if (d_fw1) (void)hipFree(d_fw1);
-        if (d_fw2) (void)hipFree(d_fw2);
-        if (d_rxa) (void)hipFree(d_rxa);
-        if (d_rxb) (void)hipFree(d_rxb);
-        if (d_colw1) (void)hipFree(d_colw1);
-        if (d_colr) (void)hipFree(d_colr);
-        if (d_rx32) (void)hipFree(d_rx32);
-        d_fw1 = d_fw2 = d_rxa = d_rxb = d_colw1 = d_colr = d_rx32 = nullptr;
-    }
-    bool fast(int i) const { return pass[i].L == 1024 && (pass[i].C == 16 || pass[i].C == 8) && d_fw1 != nullptr; }
+    bool fast(int i) const { return pass[i].L == 1024 && (pass[i].C == 16 || pass[i].C == 8) && d_fw1; }
 };
+static_assert(!std::is_copy_constructible_v<Pow2Plan>, "a plan owns its tables: never copied");
 
-static comms_status_t upload_tw(size_t count, size_t denom, size_t mult, float2** d_out) {
+static comms_status_t upload_tw(size_t count, size_t denom, size_t mult, DevBuf<float2>& d_out) {
     // table[m] = exp(-2 pi i * (m * mult) / denom), m < count   (forward sign)
     std::vector<float2> t(count);
     for (size_t m = 0; m < count; ++m) {
@@ -1256,8 +1237,7 @@ static comms_status_t upload_tw(size_t count, size_t denom, size_t mult, float2*
         double a = -2.0 * kPiF * static_cast<double>(e) / static_cast<double>(denom);
         t[m] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
     }
-    COMMS_HIP_TRY(hipMalloc(d_out, count * sizeof(float2)));
-    COMMS_HIP_TRY(hipMemcpy(*d_out, t.data(), count * sizeof(float2), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(d_out.upload(t));
     return COMMS_OK;
 }
 
@@ -1296,8 +1276,8 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
         p.tiles_per_xform = 1;
         p.tile_step_in = p.tile_step_out = 0;
         p.N = static_cast<size_t>(p.C) * N;
-        COMMS_TRY(upload_tw(N, N, 1, &pl.d_tw[0]));
-        p.twL = reinterpret_cast<const cf*>(pl.d_tw[0]);
+        COMMS_TRY(upload_tw(N, N, 1, pl.d_tw[0]));
+        p.twL = reinterpret_cast<const cf*>(pl.d_tw[0].get());
     } else if (logN > 20) {
         // 2^21 .. 2^24: columns of 1024 points (stride N2) -> rows of N2 = N / 1024 points -> transpose
         pl.n_pass = 2;  // (pass[1] is unused; the row transforms have a plan of their own)
@@ -1316,12 +1296,12 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
         a.tile_step_in = a.tile_step_out = a.C;
         a.N = N;
         a.apply_tw = 1;
-        COMMS_TRY(upload_tw(1024, 1024, 1, &pl.d_tw[0]));
-        COMMS_TRY(upload_tw(4096, N, 1, &pl.d_tw[2]));
-        COMMS_TRY(upload_tw(N / 4096, N, 4096, &pl.d_tw[3]));
-        a.twL = reinterpret_cast<const cf*>(pl.d_tw[0]);
-        a.tw_lo = reinterpret_cast<const cf*>(pl.d_tw[2]);
-        a.tw_hi = reinterpret_cast<const cf*>(pl.d_tw[3]);
+        COMMS_TRY(upload_tw(1024, 1024, 1, pl.d_tw[0]));
+        COMMS_TRY(upload_tw(4096, N, 1, pl.d_tw[2]));
+        COMMS_TRY(upload_tw(N / 4096, N, 4096, pl.d_tw[3]));
+        a.twL = reinterpret_cast<const cf*>(pl.d_tw[0].get());
+        a.tw_lo = reinterpret_cast<const cf*>(pl.d_tw[2].get());
+        a.tw_hi = reinterpret_cast<const cf*>(pl.d_tw[3].get());
         // row pass of the two-pass form: tile t = the 16 adjacent outputs k of every column, as the column pass left them
         // ([k / 16][column][k % 16]); 1024-point transforms over the columns; X[k + N2 k2] in 128-byte pieces
         FftTileParams& b = pl.pass[1];
@@ -1337,7 +1317,7 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
         b.tile_step_out = 16;
         b.N = N;
         b.twL = a.twL;
-        pl.rows = new (std::nothrow) Pow2Plan;
+        pl.rows.reset(new (std::nothrow) Pow2Plan);
         COMMS_ARG(pl.rows != nullptr, "out of host memory");
         COMMS_TRY(pow2_plan_build(*pl.rows, N2));
     } else {
@@ -1360,12 +1340,12 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
         a.tile_step_in = a.tile_step_out = a.C;
         a.N = N;
         a.apply_tw = 1;
-        COMMS_TRY(upload_tw(N1, N1, 1, &pl.d_tw[0]));
-        COMMS_TRY(upload_tw(4096, N, 1, &pl.d_tw[2]));
-        COMMS_TRY(upload_tw(N / 4096, N, 4096, &pl.d_tw[3]));
-        a.twL = reinterpret_cast<const cf*>(pl.d_tw[0]);
-        a.tw_lo = reinterpret_cast<const cf*>(pl.d_tw[2]);
-        a.tw_hi = reinterpret_cast<const cf*>(pl.d_tw[3]);
+        COMMS_TRY(upload_tw(N1, N1, 1, pl.d_tw[0]));
+        COMMS_TRY(upload_tw(4096, N, 1, pl.d_tw[2]));
+        COMMS_TRY(upload_tw(N / 4096, N, 4096, pl.d_tw[3]));
+        a.twL = reinterpret_cast<const cf*>(pl.d_tw[0].get());
+        a.tw_lo = reinterpret_cast<const cf*>(pl.d_tw[2].get());
+        a.tw_hi = reinterpret_cast<const cf*>(pl.d_tw[3].get());
         // pass 2: rows k1, FFT over n2, transposed store -> X[k1 + N1*k2]
         FftTileParams& b = pl.pass[1];
         memset(&b, 0, sizeof(b));
@@ -1380,8 +1360,8 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
         b.tile_step_in = static_cast<size_t>(b.C) * N2;
         b.tile_step_out = b.C;
         b.N = N;
-        COMMS_TRY(upload_tw(N2, N2, 1, &pl.d_tw[1]));
-        b.twL = reinterpret_cast<const cf*>(pl.d_tw[1]);
+        COMMS_TRY(upload_tw(N2, N2, 1, pl.d_tw[1]));
+        b.twL = reinterpret_cast<const cf*>(pl.d_tw[1].get());
     }
     for (int i = 0; i < pl.n_pass; ++i) {
         const int npts = pl.pass[i].L * pl.pass[i].C;
@@ -1404,10 +1384,10 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
                 const double a = -2.0 * kPiF * static_cast<double>((c * k1) % 64) / 64.0;
                 t2[k1 * 4 + c] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
             }
-        COMMS_HIP_TRY(hipMalloc(&pl.d_fw1, t1.size() * sizeof(float2)));
-        COMMS_HIP_TRY(hipMalloc(&pl.d_fw2, t2.size() * sizeof(float2)));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_fw1, t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_fw2, t2.data(), t2.size() * sizeof(float2), hipMemcpyHostToDevice));
+        COMMS_HIP_TRY(pl.d_fw1.alloc(t1.size()));
+        COMMS_HIP_TRY(pl.d_fw2.alloc(t2.size()));
+        COMMS_HIP_TRY(hipMemcpy(pl.d_fw1.get(), t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
+        COMMS_HIP_TRY(hipMemcpy(pl.d_fw2.get(), t2.data(), t2.size() * sizeof(float2), hipMemcpyHostToDevice));
         const int fw_lds = (1024 + 64 + 16 * FW_BUF + 256) * static_cast<int>(sizeof(float2));
         COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft1024x16_kernel<1, 16>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, fw_lds));
@@ -1435,10 +1415,10 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
                 tb[k * 64 + l] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
             }
         }
-        COMMS_HIP_TRY(hipMalloc(&pl.d_rxa, ta.size() * sizeof(float2)));
-        COMMS_HIP_TRY(hipMalloc(&pl.d_rxb, tb.size() * sizeof(float2)));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_rxa, ta.data(), ta.size() * sizeof(float2), hipMemcpyHostToDevice));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_rxb, tb.data(), tb.size() * sizeof(float2), hipMemcpyHostToDevice));
+        COMMS_HIP_TRY(pl.d_rxa.alloc(ta.size()));
+        COMMS_HIP_TRY(pl.d_rxb.alloc(tb.size()));
+        COMMS_HIP_TRY(hipMemcpy(pl.d_rxa.get(), ta.data(), ta.size() * sizeof(float2), hipMemcpyHostToDevice));
+        COMMS_HIP_TRY(hipMemcpy(pl.d_rxb.get(), tb.data(), tb.size() * sizeof(float2), hipMemcpyHostToDevice));
         pl.rx_rad = N == 64 ? -1 : N == 256 ? -2 : N == 128 ? -3 : N == 512 ? -4 : N <= 32 ? -static_cast<int>(N) - 100 : rad;  // < 0: the short forms (-100 - N: the tiny ones)
         if (N == 128 || N == 512 || N == 32) {  // W_N^{n2}, n2 < N/2, for the radix-2 front stage
             std::vector<float2> t(N / 2 < 64 ? 64 : N / 2, make_float2(1.f, 0.f));
@@ -1446,10 +1426,8 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
                 const double a = -2.0 * kPiF * static_cast<double>(j) / static_cast<double>(N);
                 t[j] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
             }
-            (void)hipFree(pl.d_rxb);
-            pl.d_rxb = nullptr;
-            COMMS_HIP_TRY(hipMalloc(&pl.d_rxb, t.size() * sizeof(float2)));
-            COMMS_HIP_TRY(hipMemcpy(pl.d_rxb, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
+            COMMS_HIP_TRY(pl.d_rxb.alloc(t.size()));
+            COMMS_HIP_TRY(hipMemcpy(pl.d_rxb.get(), t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
         }
         if (N == 256 || N == 512) {  // its stage twiddle W256^{b*ka} at [ka*16 + b] takes the place of the W1024 table
             std::vector<float2> t1(1024, make_float2(1.f, 0.f));
@@ -1458,7 +1436,7 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
                     const double a = -2.0 * kPiF * static_cast<double>((bq * k) % 256) / 256.0;
                     t1[k * 16 + bq] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
                 }
-            COMMS_HIP_TRY(hipMemcpy(pl.d_fw1, t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
+            COMMS_HIP_TRY(hipMemcpy(pl.d_fw1.get(), t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
         }
     }
     if (pl.n_pass == 2 && pl.pass[1].L == 1024 && pl.d_fw1 &&
@@ -1476,10 +1454,10 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
             const double a = -2.0 * kPiF * static_cast<double>(r) / static_cast<double>(n1);
             tr[r] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
         }
-        COMMS_HIP_TRY(hipMalloc(&pl.d_colw1, t1.size() * sizeof(float2)));
-        COMMS_HIP_TRY(hipMalloc(&pl.d_colr, tr.size() * sizeof(float2)));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_colw1, t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_colr, tr.data(), tr.size() * sizeof(float2), hipMemcpyHostToDevice));
+        COMMS_HIP_TRY(pl.d_colw1.alloc(t1.size()));
+        COMMS_HIP_TRY(pl.d_colr.alloc(tr.size()));
+        COMMS_HIP_TRY(hipMemcpy(pl.d_colw1.get(), t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
+        COMMS_HIP_TRY(hipMemcpy(pl.d_colr.get(), tr.data(), tr.size() * sizeof(float2), hipMemcpyHostToDevice));
         pl.col_kind = n1 == 64 ? 0 : n1;
     }
     if (N == 32768 && pl.d_fw1) {  // the single-pass form: three twiddle values per thread
@@ -1490,8 +1468,8 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
                 const double a = -2.0 * kPiF * static_cast<double>((n2 * mult[i]) % N) / static_cast<double>(N);
                 t[i * 1024 + n2] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
             }
-        COMMS_HIP_TRY(hipMalloc(&pl.d_rx32, t.size() * sizeof(float2)));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_rx32, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
+        COMMS_HIP_TRY(pl.d_rx32.alloc(t.size()));
+        COMMS_HIP_TRY(hipMemcpy(pl.d_rx32.get(), t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
         COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rx32k_kernel<1>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(R32_LDS)));
         COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rx32k_kernel<-1>),
@@ -1512,8 +1490,8 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
 // reads what pass 1 wrote to `out`.
 static comms_status_t launch_fast(Pow2Plan& pl, const float2* src, float2* dst, const FftTileParams& p,
                                   bool inverse, hipStream_t s) {
-    const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1);
-    const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2);
+    const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1.get());
+    const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
     const cf* a = reinterpret_cast<const cf*>(src);
     cf* d = reinterpret_cast<cf*>(dst);
     if (p.C == 16) {  // one 16-wave workgroup per CU
@@ -1546,10 +1524,10 @@ static comms_status_t launch_rx(Pow2Plan& pl, const float2* src, float2* dst, si
     const size_t n_full = n_points / 16384, rem = n_points % 16384;
     const cf* a = reinterpret_cast<const cf*>(src);
     cf* d = reinterpret_cast<cf*>(dst);
-    const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1);
-    const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2);
-    const cf* ta = reinterpret_cast<const cf*>(pl.d_rxa);
-    const cf* tb = reinterpret_cast<const cf*>(pl.d_rxb);
+    const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1.get());
+    const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
+    const cf* ta = reinterpret_cast<const cf*>(pl.d_rxa.get());
+    const cf* tb = reinterpret_cast<const cf*>(pl.d_rxb.get());
     constexpr size_t lds = RxGeom<RAD>::LDS;
     static DeviceOnce attr_once;
     if (attr_once.need()) {
@@ -1604,10 +1582,10 @@ static comms_status_t launch_rx_cols(Pow2Plan& rows, const float2* src, float2* 
     const unsigned blocks = static_cast<unsigned>(n_tiles < static_cast<size_t>(kNumCU) ? n_tiles : kNumCU);
     const cf* a = reinterpret_cast<const cf*>(src);
     cf* d = reinterpret_cast<cf*>(dst);
-    const cf* t1 = reinterpret_cast<const cf*>(rows.d_fw1);
-    const cf* t2 = reinterpret_cast<const cf*>(rows.d_fw2);
-    const cf* ta = reinterpret_cast<const cf*>(rows.d_rxa);
-    const cf* tb = reinterpret_cast<const cf*>(rows.d_rxb);
+    const cf* t1 = reinterpret_cast<const cf*>(rows.d_fw1.get());
+    const cf* t2 = reinterpret_cast<const cf*>(rows.d_fw2.get());
+    const cf* ta = reinterpret_cast<const cf*>(rows.d_rxa.get());
+    const cf* tb = reinterpret_cast<const cf*>(rows.d_rxb.get());
     if (inverse)
         fft_rx1024_kernel<1, RAD, 3><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, n_tiles, 0, n_points, t1, t2, ta, tb, blu);
     else
@@ -1630,9 +1608,9 @@ static comms_status_t launch_cols(Pow2Plan& pl, const float2* src, float2* dst, 
     const unsigned blocks = static_cast<unsigned>(n_tiles < static_cast<size_t>(kNumCU) ? n_tiles : kNumCU);
     const cf* a = reinterpret_cast<const cf*>(src);
     cf* d = reinterpret_cast<cf*>(dst);
-    const cf* t1 = reinterpret_cast<const cf*>(pl.d_colw1);
-    const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2);
-    const cf* tr = reinterpret_cast<const cf*>(pl.d_colr);
+    const cf* t1 = reinterpret_cast<const cf*>(pl.d_colw1.get());
+    const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
+    const cf* tr = reinterpret_cast<const cf*>(pl.d_colr.get());
     const FftTileParams& p = pl.pass[0];
     if (inverse)
         fft_cols_kernel<1, KIND><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, n_tiles, static_cast<unsigned>(pl.N), t1, t2, tr, p.tw_lo, p.tw_hi, p.ks);
@@ -1673,9 +1651,9 @@ static comms_status_t pow2_run(Pow2Plan& pl, const float2* in, float2* out, size
     static const bool no_rx32k = diag_knob("COMMS_FFT_NO_RX32K", 0) != 0;
     if (pl.d_rx32 && !no_rx32k) {  // N = 32768: one pass, a transform per workgroup and step
         const unsigned blocks = static_cast<unsigned>(batch < static_cast<size_t>(kNumCU) ? batch : kNumCU);
-        const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1);
-        const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2);
-        const cf* tt = reinterpret_cast<const cf*>(pl.d_rx32);
+        const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1.get());
+        const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
+        const cf* tt = reinterpret_cast<const cf*>(pl.d_rx32.get());
         if (inverse)
             fft_rx32k_kernel<1><<<dim3(blocks), dim3(1024), R32_LDS, s>>>(reinterpret_cast<const cf*>(in), reinterpret_cast<cf*>(out), batch, t1, t2, tt, ks);
         else
@@ -1789,25 +1767,15 @@ struct comms_fft : Handle {
     bool inverse = false;
     int kind = 0;  // 0 pow2, 1 direct O(N^2), 2 Bluestein
     Pow2Plan plan;           // pow2: length N;  Bluestein: length M
-    float2* d_twN = nullptr;     // direct: W_N^m
+    DevBuf<float2> d_twN;     // direct: W_N^m
     size_t M = 0;                // Bluestein padded length
-    float2* d_chirp = nullptr;   // exp(-/+ i pi n^2 / N)
-    float2* d_bspec = nullptr;   // FFT_M(conj chirp, wrapped) / M
+    DevBuf<float2> d_chirp;   // exp(-/+ i pi n^2 / N)
+    DevBuf<float2> d_bspec;   // FFT_M(conj chirp, wrapped) / M
     Scratch work;                // four-step transpose buffer / Bluestein work
     Scratch work2;
 };
 
-static void free_fft(comms_fft* h) {
-    (void)use_device(h->device);
-    h->plan.release();
-    if (h->d_twN) (void)hipFree(h->d_twN);
-    if (h->d_chirp) (void)hipFree(h->d_chirp);
-    if (h->d_bspec) (void)hipFree(h->d_bspec);
-    h->work.release();
-    h->work2.release();
-    h->fini();
-    delete h;
-}
+static_assert(!std::is_copy_constructible_v<comms_fft>, "a handle is never copied");
 
 static comms_status_t fft_setup(comms_fft* h) {
     const size_t N = h->N;
@@ -1821,7 +1789,7 @@ static comms_status_t fft_setup(comms_fft* h) {
     static const size_t direct_max = static_cast<size_t>(diag_knob("COMMS_FFT_DIRECT_MAX", 64));
     if (N <= direct_max && N <= 4096) {
         h->kind = 1;
-        return upload_tw(N, N, 1, &h->d_twN);
+        return upload_tw(N, N, 1, h->d_twN);
     }
     // Bluestein: with chirp[n] = W^{n^2/2} (W = e^{-/+ 2 pi i/N} by direction),
     //   X[k] = chirp[k] * sum_n (x[n] chirp[n]) * conj(chirp)[k-n]
@@ -1849,22 +1817,22 @@ static comms_status_t fft_setup(comms_fft* h) {
         bvec[n] = v;
         if (n) bvec[M - n] = v;
     }
-    COMMS_HIP_TRY(hipMalloc(&h->d_chirp, N * sizeof(float2)));
-    COMMS_HIP_TRY(hipMemcpy(h->d_chirp, chirp.data(), N * sizeof(float2), hipMemcpyHostToDevice));
-    COMMS_HIP_TRY(hipMalloc(&h->d_bspec, M * sizeof(float2)));
-    COMMS_HIP_TRY(hipMemcpy(h->d_bspec, bvec.data(), M * sizeof(float2), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(h->d_chirp.alloc(N));
+    COMMS_HIP_TRY(hipMemcpy(h->d_chirp.get(), chirp.data(), N * sizeof(float2), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(h->d_bspec.alloc(M));
+    COMMS_HIP_TRY(hipMemcpy(h->d_bspec.get(), bvec.data(), M * sizeof(float2), hipMemcpyHostToDevice));
     COMMS_TRY(h->work.reserve(M * sizeof(float2)));
-    COMMS_TRY(pow2_run(h->plan, h->d_bspec, h->d_bspec, 1, false, h->stream, static_cast<float2*>(h->work.p)));
+    COMMS_TRY(pow2_run(h->plan, h->d_bspec.get(), h->d_bspec.get(), 1, false, h->stream, static_cast<float2*>(h->work.p)));
     COMMS_HIP_TRY(hipStreamSynchronize(h->stream));
     // fold the 1/M of the inverse transform into the spectrum
     std::vector<float2> spec(M);
-    COMMS_HIP_TRY(hipMemcpy(spec.data(), h->d_bspec, M * sizeof(float2), hipMemcpyDeviceToHost));
+    COMMS_HIP_TRY(hipMemcpy(spec.data(), h->d_bspec.get(), M * sizeof(float2), hipMemcpyDeviceToHost));
     const float inv = 1.0f / static_cast<float>(M);
     for (auto& v : spec) {
         v.x *= inv;
         v.y *= inv;
     }
-    COMMS_HIP_TRY(hipMemcpy(h->d_bspec, spec.data(), M * sizeof(float2), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(hipMemcpy(h->d_bspec.get(), spec.data(), M * sizeof(float2), hipMemcpyHostToDevice));
     return COMMS_OK;
 }
 
@@ -1875,21 +1843,12 @@ comms_status_t comms_fft_create(size_t fft_size, int32_t inverse, int32_t device
     COMMS_ARG(out != nullptr, "out is NULL");
     *out = nullptr;
     COMMS_ARG(fft_size >= 1, "fft_size must be >= 1");
-    comms_fft* h = new (std::nothrow) comms_fft;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    HandlePtr<comms_fft> h;
+    COMMS_TRY(make_handle(device, &h));
     h->N = fft_size;
     h->inverse = inverse != 0;
-    st = fft_setup(h);
-    if (st != COMMS_OK) {
-        free_fft(h);
-        return st;
-    }
-    *out = h;
+    COMMS_TRY(fft_setup(h.get()));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -1943,7 +1902,7 @@ comms_status_t comms_fft_run_dev(comms_fft_t* h, const comms_c32* d_in, size_t n
             h->tic(s);
             dft_small_kernel<<<dim3(gb), dim3(256), 0, s>>>(reinterpret_cast<const cf*>(in), reinterpret_cast<cf*>(o),
                                                             static_cast<int>(h->N), batch,
-                                                            reinterpret_cast<const cf*>(h->d_twN), h->inverse ? 1 : 0);
+                                                            reinterpret_cast<const cf*>(h->d_twN.get()), h->inverse ? 1 : 0);
             h->toc(s);
             return launch_ok("dft_small_kernel");
         }
@@ -1951,7 +1910,7 @@ comms_status_t comms_fft_run_dev(comms_fft_t* h, const comms_c32* d_in, size_t n
         h->tic(s);
         dft_direct_kernel<<<dim3(blocks), dim3(256), 2 * h->N * sizeof(float2), s>>>(
             reinterpret_cast<const cf*>(in), reinterpret_cast<cf*>(o), static_cast<int>(h->N), batch,
-            reinterpret_cast<const cf*>(h->d_twN), h->inverse ? 1 : 0);
+            reinterpret_cast<const cf*>(h->d_twN.get()), h->inverse ? 1 : 0);
         h->toc(s);
         return launch_ok("dft_direct_kernel");
     }
@@ -1979,20 +1938,20 @@ comms_status_t comms_fft_run_dev(comms_fft_t* h, const comms_c32* d_in, size_t n
         const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
         if (fuse) {
             // two launches: [x * chirp, pad, forward, * bspec] -> work;  [inverse, * chirp, first N] -> out
-            const cf* chirp = reinterpret_cast<const cf*>(h->d_chirp);
+            const cf* chirp = reinterpret_cast<const cf*>(h->d_chirp.get());
             COMMS_TRY(run_rx(h->plan, in + b0 * h->N, a, nb * M, false, s,
-                             BluArgs{1, static_cast<unsigned>(h->N), logM, chirp, reinterpret_cast<const cf*>(h->d_bspec)}));
+                             BluArgs{1, static_cast<unsigned>(h->N), logM, chirp, reinterpret_cast<const cf*>(h->d_bspec.get())}));
             COMMS_TRY(run_rx(h->plan, a, o + b0 * h->N, nb * M, true, s,
                              BluArgs{2, static_cast<unsigned>(h->N), logM, chirp, nullptr}));
             continue;
         }
-        blu_pre_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(reinterpret_cast<const cf*>(in + b0 * h->N), reinterpret_cast<const cf*>(h->d_chirp), reinterpret_cast<cf*>(a), h->N, M, nb);
+        blu_pre_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(reinterpret_cast<const cf*>(in + b0 * h->N), reinterpret_cast<const cf*>(h->d_chirp.get()), reinterpret_cast<cf*>(a), h->N, M, nb);
         COMMS_TRY(launch_ok("blu_pre_kernel"));
         COMMS_TRY(pow2_run(h->plan, a, a, nb, false, s, sc));
-        blu_mul_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(reinterpret_cast<cf*>(a), reinterpret_cast<const cf*>(h->d_bspec), M, nb);
+        blu_mul_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(reinterpret_cast<cf*>(a), reinterpret_cast<const cf*>(h->d_bspec.get()), M, nb);
         COMMS_TRY(launch_ok("blu_mul_kernel"));
         COMMS_TRY(pow2_run(h->plan, a, a, nb, true, s, sc));
-        blu_post_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(reinterpret_cast<const cf*>(a), reinterpret_cast<const cf*>(h->d_chirp), reinterpret_cast<cf*>(o + b0 * h->N), h->N, M, nb);
+        blu_post_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(reinterpret_cast<const cf*>(a), reinterpret_cast<const cf*>(h->d_chirp.get()), reinterpret_cast<cf*>(o + b0 * h->N), h->N, M, nb);
         COMMS_TRY(launch_ok("blu_post_kernel"));
     }
     return COMMS_OK;
@@ -2016,10 +1975,6 @@ comms_status_t comms_fft_set_timer(comms_fft_t* h, comms_timer_t* t) {
     return COMMS_OK;
 }
 
-comms_status_t comms_fft_destroy(comms_fft_t* h) {
-    if (!h) return COMMS_OK;
-    free_fft(h);
-    return COMMS_OK;
-}
+comms_status_t comms_fft_destroy(comms_fft_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

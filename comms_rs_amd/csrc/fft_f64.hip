@@ -147,13 +147,14 @@ struct comms_fft_f64 : Handle {
     int kind = 0;               // 0: one pass, 1: four-step, 2: DFT sum, 3: Bluestein
     size_t P = 0;               // the power-of-two length the passes run at (N, or Bluestein's M)
     unsigned logP = 0, logN1 = 0, logN2 = 0, h = 0;
-    double2* d_t4096 = nullptr;
-    double2* d_twa = nullptr;   // W_P^{e 2^h}
-    double2* d_twb = nullptr;   // W_P^{e}, e < 2^h
-    double2* d_roots = nullptr; // kind 2: W_N^e;  kind 3: the chirp c[n] = e^{-i pi n^2 / N}
-    double2* d_spec = nullptr;  // kind 3: FFT_M of the wrapped conjugate chirp, / M
+    DevBuf<double2> d_t4096;
+    DevBuf<double2> d_twa;    // W_P^{e 2^h}
+    DevBuf<double2> d_twb;    // W_P^{e}, e < 2^h
+    DevBuf<double2> d_roots;  // kind 2: W_N^e;  kind 3: the chirp c[n] = e^{-i pi n^2 / N}
+    DevBuf<double2> d_spec;   // kind 3: FFT_M of the wrapped conjugate chirp, / M
     Scratch s1, s2;
 };
+static_assert(!std::is_copy_constructible_v<comms_fft_f64>, "a handle is never copied");
 
 namespace {
 
@@ -162,11 +163,6 @@ double2 rootl(unsigned long long e, unsigned long long denom) {  // e^{-2 pi i e
     e %= denom;
     const long double a = 2.0L * kPiL * static_cast<long double>(e) / static_cast<long double>(denom);
     return make_double2(static_cast<double>(cosl(a)), static_cast<double>(-sinl(a)));
-}
-comms_status_t upload(const std::vector<double2>& v, double2** d) {
-    COMMS_HIP_TRY(hipMalloc(d, v.size() * sizeof(double2)));
-    COMMS_HIP_TRY(hipMemcpy(*d, v.data(), v.size() * sizeof(double2), hipMemcpyHostToDevice));
-    return COMMS_OK;
 }
 
 comms_status_t lds_pass(const F64Pass& p, unsigned ny, hipStream_t s) {
@@ -182,7 +178,7 @@ comms_status_t lds_pass(const F64Pass& p, unsigned ny, hipStream_t s) {
 // direction (Bluestein runs one transform each way)
 comms_status_t pow2_run(comms_fft_f64* h, const double2* in, double2* out, size_t batch, bool inverse, hipStream_t s) {
     F64Pass p{};
-    p.t4096 = h->d_t4096;
+    p.t4096 = h->d_t4096.get();
     p.inverse = inverse ? 1 : 0;
     if (h->logP <= 12) {
         p.in = in, p.out = out;
@@ -209,7 +205,7 @@ comms_status_t pow2_run(comms_fft_f64* h, const double2* in, double2* out, size_
         a.T = static_cast<unsigned>(N2), a.N = static_cast<unsigned>(N1), a.logN = h->logN1;
         a.B = F64_LDS_POINTS / a.N < 16 ? F64_LDS_POINTS / a.N : 16;
         a.in_st = 1, a.in_sj = N2, a.out_st = 1, a.out_sk = N2;
-        a.twa = h->d_twa, a.twb = h->d_twb, a.h = h->h;
+        a.twa = h->d_twa.get(), a.twb = h->d_twb.get(), a.h = h->h;
         COMMS_TRY(lds_pass(a, ny, s));
         // rows: N1 transforms of N2 points, tmp[k1 N2 + n2] -> out[k1 + N1 k2]
         F64Pass r = p;
@@ -223,16 +219,6 @@ comms_status_t pow2_run(comms_fft_f64* h, const double2* in, double2* out, size_
     return COMMS_OK;
 }
 
-void free_fft_f64(comms_fft_f64* h) {
-    (void)use_device(h->device);
-    for (double2* q : {h->d_t4096, h->d_twa, h->d_twb, h->d_roots, h->d_spec})
-        if (q) (void)hipFree(q);
-    h->s1.release();
-    h->s2.release();
-    h->fini();
-    delete h;
-}
-
 comms_status_t fft_f64_prepare(comms_fft_f64* h) {
     const size_t N = h->N;
     const bool pow2 = (N & (N - 1)) == 0;
@@ -240,7 +226,8 @@ comms_status_t fft_f64_prepare(comms_fft_f64* h) {
     if (h->kind == 2) {
         std::vector<double2> r(N);
         for (size_t e = 0; e < N; ++e) r[e] = rootl(e, N);
-        return upload(r, &h->d_roots);
+        COMMS_HIP_TRY(h->d_roots.upload(r));
+        return COMMS_OK;
     }
     size_t P = N;
     if (h->kind == 3) {
@@ -253,7 +240,7 @@ comms_status_t fft_f64_prepare(comms_fft_f64* h) {
     {
         std::vector<double2> t(4096);
         for (unsigned e = 0; e < 4096; ++e) t[e] = rootl(e, 4096);
-        COMMS_TRY(upload(t, &h->d_t4096));
+        COMMS_HIP_TRY(h->d_t4096.upload(t));
     }
     if (h->logP > 12) {
         h->logN1 = (h->logP + 1) / 2, h->logN2 = h->logP - h->logN1;
@@ -261,8 +248,8 @@ comms_status_t fft_f64_prepare(comms_fft_f64* h) {
         std::vector<double2> a((P >> h->h) + 1), b(static_cast<size_t>(1) << h->h);
         for (size_t e = 0; e < a.size(); ++e) a[e] = rootl(static_cast<unsigned long long>(e) << h->h, P);
         for (size_t e = 0; e < b.size(); ++e) b[e] = rootl(e, P);
-        COMMS_TRY(upload(a, &h->d_twa));
-        COMMS_TRY(upload(b, &h->d_twb));
+        COMMS_HIP_TRY(h->d_twa.upload(a));
+        COMMS_HIP_TRY(h->d_twb.upload(b));
     }
     if (h->kind == 3) {
         // chirp c[n] = e^{-i pi n^2 / N} = root(n^2 mod 2N, 2N); S = FFT_P(conj chirp, wrapped) / P
@@ -274,9 +261,9 @@ comms_status_t fft_f64_prepare(comms_fft_f64* h) {
             w[n] = cc;
             if (n) w[P - n] = cc;
         }
-        COMMS_TRY(upload(c, &h->d_roots));
-        COMMS_TRY(upload(w, &h->d_spec));
-        COMMS_TRY(pow2_run(h, h->d_spec, h->d_spec, 1, false, h->stream));
+        COMMS_HIP_TRY(h->d_roots.upload(c));
+        COMMS_HIP_TRY(h->d_spec.upload(w));
+        COMMS_TRY(pow2_run(h, h->d_spec.get(), h->d_spec.get(), 1, false, h->stream));
         COMMS_HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return COMMS_OK;
@@ -290,21 +277,12 @@ comms_status_t comms_fft_f64_create(size_t fft_size, int32_t inverse, int32_t de
     COMMS_ARG(out != nullptr, "out is NULL");
     *out = nullptr;
     COMMS_ARG(fft_size >= 1, "fft_size must be >= 1");
-    comms_fft_f64* h = new (std::nothrow) comms_fft_f64;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    HandlePtr<comms_fft_f64> h;
+    COMMS_TRY(make_handle(device, &h));
     h->N = fft_size;
     h->inverse = inverse != 0;
-    st = fft_f64_prepare(h);
-    if (st != COMMS_OK) {
-        free_fft_f64(h);
-        return st;
-    }
-    *out = h;
+    COMMS_TRY(fft_f64_prepare(h.get()));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -334,7 +312,7 @@ comms_status_t comms_fft_f64_run_dev(comms_fft_f64_t* h, const comms_c64* d_in, 
         for (size_t b0 = 0; b0 < batch; b0 += 32768) {
             const unsigned nb = static_cast<unsigned>(batch - b0 < 32768 ? batch - b0 : 32768);
             dft_f64_direct_kernel<<<dim3((N + 255) / 256, nb), dim3(256), static_cast<size_t>(N) * sizeof(double2), s>>>(
-                in + b0 * N, o + b0 * N, N, h->d_roots, h->inverse ? 1 : 0);
+                in + b0 * N, o + b0 * N, N, h->d_roots.get(), h->inverse ? 1 : 0);
             COMMS_TRY(launch_ok("dft_f64_direct_kernel"));
         }
     } else {
@@ -343,11 +321,11 @@ comms_status_t comms_fft_f64_run_dev(comms_fft_f64_t* h, const comms_c64* d_in, 
         const unsigned gm = static_cast<unsigned>((h->P + 255) / 256), gn = static_cast<unsigned>((h->N + 255) / 256);
         const int inv = h->inverse ? 1 : 0;
         for (size_t b = 0; b < batch; ++b) {
-            blue_in_kernel<<<dim3(gm), dim3(256), 0, s>>>(in + b * h->N, h->d_roots, a, h->N, h->P, inv);
+            blue_in_kernel<<<dim3(gm), dim3(256), 0, s>>>(in + b * h->N, h->d_roots.get(), a, h->N, h->P, inv);
             COMMS_TRY(pow2_run(h, a, a, 1, false, s));
-            blue_mul_kernel<<<dim3(gm), dim3(256), 0, s>>>(a, h->d_spec, h->P, inv);
+            blue_mul_kernel<<<dim3(gm), dim3(256), 0, s>>>(a, h->d_spec.get(), h->P, inv);
             COMMS_TRY(pow2_run(h, a, a, 1, true, s));
-            blue_out_kernel<<<dim3(gn), dim3(256), 0, s>>>(a, h->d_roots, o + b * h->N, h->N, inv);
+            blue_out_kernel<<<dim3(gn), dim3(256), 0, s>>>(a, h->d_roots.get(), o + b * h->N, h->N, inv);
             COMMS_TRY(launch_ok("blue_out_kernel"));
         }
     }
@@ -367,40 +345,26 @@ comms_status_t comms_fft_f64_run(comms_fft_f64_t* h, const comms_c64* in, size_t
                              });
 }
 
-comms_status_t comms_fft_f64_destroy(comms_fft_f64_t* h) {
-    if (!h) return COMMS_OK;
-    free_fft_f64(h);
-    return COMMS_OK;
-}
+comms_status_t comms_fft_f64_destroy(comms_fft_f64_t* h) { return destroy_handle(h); }
 
 }  // extern "C"
 
 // ------------------------------------------------------------------ FMDemodNode<f64>
 struct comms_fmdemod_f64 : Handle {
-    double2* d_prev = nullptr;  // FM.prev (analog.rs:9), starts 0+0i: two words, d_prev[cur] is the current one
+    DevBuf<double2> d_prev;  // FM.prev (analog.rs:9), starts 0+0i: two words, d_prev[cur] is the current one
     int cur = 0;
 };
+static_assert(!std::is_copy_constructible_v<comms_fmdemod_f64>, "a handle is never copied");
 
 extern "C" {
 
 comms_status_t comms_fmdemod_f64_create(int32_t device, comms_fmdemod_f64_t** out) {
     COMMS_ARG(out != nullptr, "out is NULL");
     *out = nullptr;
-    comms_fmdemod_f64* h = new (std::nothrow) comms_fmdemod_f64;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
-    hipError_t e = hipMalloc(&h->d_prev, 2 * sizeof(double2));
-    if (e == hipSuccess) e = zero_device(h->d_prev, 2 * sizeof(double2));
-    if (e != hipSuccess) {
-        h->fini();
-        delete h;
-        return fail(COMMS_ERR_DEVICE, "fmdemod state alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    HandlePtr<comms_fmdemod_f64> h;
+    COMMS_TRY(make_handle(device, &h));
+    COMMS_HIP_TRY(h->d_prev.alloc_zero(2));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -415,8 +379,8 @@ comms_status_t comms_fmdemod_f64_run_dev(comms_fmdemod_f64_t* h, const comms_c64
     const size_t want = (n + 255) / 256;
     const unsigned blocks = static_cast<unsigned>(want < 8u * kNumCU ? want : 8u * kNumCU);
     h->tic(s);
-    fmdemod_f64_kernel<<<dim3(blocks), dim3(256), 0, s>>>(reinterpret_cast<const double2*>(d_in), h->d_prev + h->cur,
-                                                          h->d_prev + (h->cur ^ 1), d_out, n);
+    fmdemod_f64_kernel<<<dim3(blocks), dim3(256), 0, s>>>(reinterpret_cast<const double2*>(d_in), h->d_prev.get() + h->cur,
+                                                          h->d_prev.get() + (h->cur ^ 1), d_out, n);
     h->toc(s);
     COMMS_TRY(launch_ok("fmdemod_f64_kernel"));
     h->cur ^= 1;
@@ -439,7 +403,7 @@ comms_status_t comms_fmdemod_f64_get_prev(comms_fmdemod_f64_t* h, comms_c64* out
     COMMS_ARG(h && out_prev, "NULL argument");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(hipMemcpy(out_prev, h->d_prev + h->cur, sizeof(double2), hipMemcpyDeviceToHost));
+    COMMS_HIP_TRY(hipMemcpy(out_prev, h->d_prev.get() + h->cur, sizeof(double2), hipMemcpyDeviceToHost));
     return COMMS_OK;
 }
 
@@ -447,17 +411,10 @@ comms_status_t comms_fmdemod_f64_set_prev(comms_fmdemod_f64_t* h, const comms_c6
     COMMS_ARG(h && prev, "NULL argument");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(hipMemcpy(h->d_prev + h->cur, prev, sizeof(double2), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(hipMemcpy(h->d_prev.get() + h->cur, prev, sizeof(double2), hipMemcpyHostToDevice));
     return COMMS_OK;
 }
 
-comms_status_t comms_fmdemod_f64_destroy(comms_fmdemod_f64_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    if (h->d_prev) (void)hipFree(h->d_prev);
-    h->fini();
-    delete h;
-    return COMMS_OK;
-}
+comms_status_t comms_fmdemod_f64_destroy(comms_fmdemod_f64_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

@@ -1329,28 +1329,6 @@ __global__ __launch_bounds__(256) void pulse_poly_in_kernel(const PulseArgs a, c
 using namespace comms;
 
 // ================================================================= FIR handle (struct comms_fir: fir_handle.hpp)
-static void free_fir(comms_fir* h) {
-    if (h->d_any_taps) (void)hipFree(h->d_any_taps);
-    if (h->d_p8) (void)hipFree(h->d_p8);
-    (void)use_device(h->device);
-    if (h->d_taps_pad) (void)hipFree(h->d_taps_pad);
-    if (h->d_wtw1) (void)hipFree(h->d_wtw1);
-    if (h->d_wtw2) (void)hipFree(h->d_wtw2);
-    if (h->d_whdev) (void)hipFree(h->d_whdev);
-    if (h->d_tw1) (void)hipFree(h->d_tw1);
-    if (h->d_tw2) (void)hipFree(h->d_tw2);
-    for (float2* q : h->d_hparts)
-        if (q) (void)hipFree(q);
-    for (float2* q : h->d_xh)
-        if (q) (void)hipFree(q);
-    for (float2* q : h->d_xt)
-        if (q) (void)hipFree(q);
-    h->hist.release();
-    if (h->err_host) (void)hipHostFree(h->err_host);
-    h->fini();
-    delete h;
-}
-
 // One launch of fir_os1024_kernel<.., MODE>: 16-wave workgroups (one per CU, 156 KiB of
 // LDS: shared tables + 16 private exchange buffers) by default, 4-wave workgroups
 // (three per CU) with COMMS_OS1024_WPB=4.
@@ -1487,10 +1465,8 @@ static comms_status_t fir_prepare_os(comms_fir* h) {
         for (int t = 0; t < 256; ++t) tw1[k0 * 256 + t] = unit_root_os(static_cast<long long>(t) * k0, OSF);
     for (int j = 0; j < 16; ++j)
         for (int lo = 0; lo < 16; ++lo) tw2[j * 16 + lo] = unit_root_os(lo * j, 256);
-    COMMS_HIP_TRY(hipMalloc(&h->d_tw1, tw1.size() * sizeof(float2)));
-    COMMS_HIP_TRY(hipMalloc(&h->d_tw2, tw2.size() * sizeof(float2)));
-    COMMS_HIP_TRY(hipMemcpy(h->d_tw1, tw1.data(), tw1.size() * sizeof(float2), hipMemcpyHostToDevice));
-    COMMS_HIP_TRY(hipMemcpy(h->d_tw2, tw2.data(), tw2.size() * sizeof(float2), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(h->d_tw1.upload(tw1));
+    COMMS_HIP_TRY(h->d_tw2.upload(tw2));
     std::vector<double> re, im;
     for (int pt = 0; pt < h->n_part; ++pt) {
         const int first = pt * per;
@@ -1501,12 +1477,9 @@ static comms_status_t fir_prepare_os(comms_fir* h) {
             hdev[k2 * 256 + 16 * k0 + k1] =
                 make_float2(static_cast<float>(re[k] / OSF), static_cast<float>(im[k] / OSF));
         }
-        float2* d = nullptr;
-        COMMS_HIP_TRY(hipMalloc(&d, hdev.size() * sizeof(float2)));
-        h->d_hparts.push_back(d);
-        COMMS_HIP_TRY(hipMemcpy(d, hdev.data(), hdev.size() * sizeof(float2), hipMemcpyHostToDevice));
+        h->d_hparts.emplace_back();
+        COMMS_HIP_TRY(h->d_hparts.back().upload(hdev));
     }
-    h->d_hdev = h->d_hparts[0];
     h->os_ready = true;
     return COMMS_OK;
 }
@@ -1555,12 +1528,6 @@ static void tap_spectrum(const comms_fir* h, int F, std::vector<double>& re, std
     tap_spectrum_range(h, 0, h->n_eff, F, re, im);
 }
 
-static comms_status_t upload_f2(const std::vector<float2>& v, float2** d) {
-    COMMS_HIP_TRY(hipMalloc(d, v.size() * sizeof(float2)));
-    COMMS_HIP_TRY(hipMemcpy(*d, v.data(), v.size() * sizeof(float2), hipMemcpyHostToDevice));
-    return COMMS_OK;
-}
-
 static float2 unit_root(long long e, int denom) {
     e %= denom;
     double a = -2.0 * kPi * static_cast<double>(e) / denom;
@@ -1586,9 +1553,9 @@ static comms_status_t fir_prepare_os1024(comms_fir* h) {
                 hdev[(4 * t + m) * 64 + l] =
                     make_float2(static_cast<float>(re[k] / WF), static_cast<float>(im[k] / WF));
             }
-    COMMS_TRY(upload_f2(tw1, &h->d_wtw1));
-    COMMS_TRY(upload_f2(tw2, &h->d_wtw2));
-    COMMS_TRY(upload_f2(hdev, &h->d_whdev));
+    COMMS_HIP_TRY(h->d_wtw1.upload(tw1));
+    COMMS_HIP_TRY(h->d_wtw2.upload(tw2));
+    COMMS_HIP_TRY(h->d_whdev.upload(hdev));
     h->w_ready = true;
     return COMMS_OK;
 }
@@ -1597,12 +1564,9 @@ constexpr int X_PART = 4097;  // taps per pass of the 16384-point kernel (halo 4
 
 static comms_status_t fir_prepare_os16k(comms_fir* h) {
     if (h->x_ready) return COMMS_OK;
-    if (!h->err_host) {  // sticky error word: pinned, coherent, mapped -- the kernel raises it, the host reads it without a sync
-        COMMS_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->err_host), 64, hipHostMallocMapped | hipHostMallocCoherent));
-        *h->err_host = 0;
-        void* d = nullptr;
-        COMMS_HIP_TRY(hipHostGetDevicePointer(&d, h->err_host, 0));
-        h->d_err = static_cast<unsigned*>(d);
+    if (!h->err_host()) {  // sticky error word: the kernel raises it, the host reads it without a sync
+        COMMS_TRY(h->err.reserve(64));
+        *h->err_host() = 0;
     }
     const int N = h->n_eff;
     h->x_part = (N + X_PART - 1) / X_PART;
@@ -1616,10 +1580,10 @@ static comms_status_t fir_prepare_os16k(comms_fir* h) {
         for (int c = 0; c < 4; ++c) tw2[k1 * 4 + c] = unit_root(c * k1, 64);
     for (int w = 0; w < 16; ++w)
         for (int k = 0; k < 16; ++k) ta[w * 16 + k] = unit_root(w * k, 256);
-    COMMS_TRY(upload_f2(tw1, &h->d_xt[0]));
-    COMMS_TRY(upload_f2(tw2, &h->d_xt[1]));
-    COMMS_TRY(upload_f2(ta, &h->d_xt[2]));
-    COMMS_TRY(upload_f2(tb, &h->d_xt[3]));
+    COMMS_HIP_TRY(h->d_xt[0].upload(tw1));
+    COMMS_HIP_TRY(h->d_xt[1].upload(tw2));
+    COMMS_HIP_TRY(h->d_xt[2].upload(ta));
+    COMMS_HIP_TRY(h->d_xt[3].upload(tb));
     std::vector<double> re, im;
     for (int pt = 0; pt < h->x_part; ++pt) {
         const int first = pt * X_PART;
@@ -1636,9 +1600,8 @@ static comms_status_t fir_prepare_os16k(comms_fir* h) {
                         make_float2(static_cast<float>(re[k] / XF), static_cast<float>(im[k] / XF));
                 }
         }
-        float2* d = nullptr;
-        COMMS_TRY(upload_f2(hdev, &d));
-        h->d_xh.push_back(d);
+        h->d_xh.emplace_back();
+        COMMS_HIP_TRY(h->d_xh.back().upload(hdev));
     }
     const int lds = static_cast<int>(X_LDS_BYTES);
 #define COMMS_X_ATTR(HRV, INV) \
@@ -1660,8 +1623,7 @@ static comms_status_t fir_prepare_direct(comms_fir* h) {
     h->NP = (h->n_eff + 7) / 8 * 8;
     std::vector<float2> tp(h->NP, make_float2(0.f, 0.f));
     for (int k = 0; k < h->n_eff; ++k) tp[k] = make_float2(h->taps[k].re, h->taps[k].im);
-    COMMS_HIP_TRY(hipMalloc(&h->d_taps_pad, tp.size() * sizeof(float2)));
-    COMMS_HIP_TRY(hipMemcpy(h->d_taps_pad, tp.data(), tp.size() * sizeof(float2), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(h->d_taps_pad.upload(tp));
     return COMMS_OK;
 }
 
@@ -1712,20 +1674,16 @@ comms_status_t comms_fir_create(const comms_c32* taps, size_t n_taps, const comm
     size_t n_eff = n_taps;
     if (state && n_state < n_eff) n_eff = n_state;  // zip(taps, state), fir.rs:53
     COMMS_ARG(n_eff <= (1u << 20), "too many taps (%zu)", n_eff);
-    comms_fir* h = nullptr;
+    HandlePtr<comms_fir> h;
     COMMS_TRY(make_handle(device, &h));
     h->n_eff = static_cast<int>(n_eff);
     h->taps.assign(taps, taps + n_eff);
     h->real_taps = true;
     for (size_t k = 0; k < n_eff; ++k)
         if (taps[k].im != 0.0f) h->real_taps = false;
-    hipError_t e = h->hist.alloc(n_eff, sizeof(float2));
-    if (e == hipSuccess && state) e = h->hist.upload(state, n_state);
-    if (e != hipSuccess) {
-        free_fir(h);
-        return fail(COMMS_ERR_DEVICE, "FIR history alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->hist.alloc(n_eff, sizeof(float2)));
+    if (state) COMMS_HIP_TRY(h->hist.upload(state, n_state));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -1845,9 +1803,9 @@ template <class In>
 static void launch_direct_in(comms_fir* h, In in, const float2* hist, float2* o, size_t n, float2* nh, unsigned blocks,
                              size_t lds, hipStream_t s) {
     if (h->real_taps)
-        fir_direct_kernel<true, In><<<dim3(blocks), dim3(256), lds, s>>>(in, hist, h->n_eff, h->d_taps_pad, h->NP, o, n, nh);
+        fir_direct_kernel<true, In><<<dim3(blocks), dim3(256), lds, s>>>(in, hist, h->n_eff, h->d_taps_pad.get(), h->NP, o, n, nh);
     else
-        fir_direct_kernel<false, In><<<dim3(blocks), dim3(256), lds, s>>>(in, hist, h->n_eff, h->d_taps_pad, h->NP, o, n, nh);
+        fir_direct_kernel<false, In><<<dim3(blocks), dim3(256), lds, s>>>(in, hist, h->n_eff, h->d_taps_pad.get(), h->NP, o, n, nh);
 }
 
 extern "C" {
@@ -1886,7 +1844,7 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
         const Os1024Plan pl = os1024_plan(h, n);
         const size_t nseg = pl.nseg;
         const size_t runs = os1024_runs(pl.wpb, nseg, pl.min_run);
-        WTables tb{reinterpret_cast<const cf*>(h->d_wtw1), reinterpret_cast<const cf*>(h->d_wtw2), reinterpret_cast<const cf*>(h->d_whdev)};
+        WTables tb{reinterpret_cast<const cf*>(h->d_wtw1.get()), reinterpret_cast<const cf*>(h->d_wtw2.get()), reinterpret_cast<const cf*>(h->d_whdev.get())};
         hipEvent_t ea = nullptr, eb = nullptr;
         const bool own_stamps = pl.wpb == 16;  // (16-wave launches report the kernel's own begin / end through the pair)
         if (own_stamps)
@@ -1911,11 +1869,11 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
         h->tic(s);
         const KStamp ks = h->next_stamp();  // (the passes of a partitioned filter stamp the same slots: the whole call)
         for (int pt = 0; pt < h->x_part; ++pt) {
-            XTables tb{reinterpret_cast<const cf*>(h->d_xt[0]), reinterpret_cast<const cf*>(h->d_xt[1]),
-                       reinterpret_cast<const cf*>(h->d_xt[2]), reinterpret_cast<const cf*>(h->d_xt[3]),
-                       reinterpret_cast<const cf*>(h->d_xh[pt])};
+            XTables tb{reinterpret_cast<const cf*>(h->d_xt[0].get()), reinterpret_cast<const cf*>(h->d_xt[1].get()),
+                       reinterpret_cast<const cf*>(h->d_xt[2].get()), reinterpret_cast<const cf*>(h->d_xt[3].get()),
+                       reinterpret_cast<const cf*>(h->d_xh[pt].get())};
             const int dl = pt * X_PART, acc = pt ? 1 : 0;
-            with_input_view(h, d_in, in, [&](auto v) { launch_os16k_hr(hr, blocks, lds, s, v, hist, h->n_eff, o, n, nseg, tb, nh, dl, acc, ks, h->d_err); });
+            with_input_view(h, d_in, in, [&](auto v) { launch_os16k_hr(hr, blocks, lds, s, v, hist, h->n_eff, o, n, nseg, tb, nh, dl, acc, ks, h->d_err()); });
         }
         h->toc(s);
         COMMS_TRY(launch_ok("fir_os16k_kernel"));
@@ -1936,8 +1894,8 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
         const unsigned blocks = static_cast<unsigned>(nseg < slots ? nseg : slots);
         h->tic(s);
         for (int pt = 0; pt < h->n_part; ++pt) {
-            OsTables tb{reinterpret_cast<const cf*>(h->d_tw1), reinterpret_cast<const cf*>(h->d_tw2),
-                        reinterpret_cast<const cf*>(h->d_hparts[pt])};
+            OsTables tb{reinterpret_cast<const cf*>(h->d_tw1.get()), reinterpret_cast<const cf*>(h->d_tw2.get()),
+                        reinterpret_cast<const cf*>(h->d_hparts[pt].get())};
             const int dl = pt * OS_PART, acc = pt ? 1 : 0;
             with_input_view(h, d_in, InC32Split{reinterpret_cast<const float*>(in)}, [&](auto v) {
                 fir_os4096_kernel<decltype(v)><<<dim3(blocks), dim3(256), 0, s>>>(v, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, dl, acc, il, OsDec{});
@@ -2038,7 +1996,7 @@ comms_status_t comms_fir_run_fused_dev(comms_fir_t* h, const comms_c32* d_in, si
     const size_t nseg = (n + WV - 1) / WV;
     static const int wpb = tune_int("COMMS_OS1024_WPB", 16);
     const size_t runs = os1024_runs(wpb, nseg, 1);
-    WTables tb{reinterpret_cast<const cf*>(h->d_wtw1), reinterpret_cast<const cf*>(h->d_wtw2), reinterpret_cast<const cf*>(h->d_whdev)};
+    WTables tb{reinterpret_cast<const cf*>(h->d_wtw1.get()), reinterpret_cast<const cf*>(h->d_wtw2.get()), reinterpret_cast<const cf*>(h->d_whdev.get())};
     h->tic(s);
     switch (mode) {
         case CH_PRE | CH_DEC:
@@ -2112,8 +2070,8 @@ comms_status_t comms_fir_run_os16k_decim_dev(comms_fir_t* h, const comms_c32* d_
         mix_host_rotor(static_cast<uint64_t>(1024 * j) * frac, c, sn);
         dc.step[j] = make_float2(static_cast<float>(c), static_cast<float>(sn));
     }
-    XTables tb{reinterpret_cast<const cf*>(h->d_xt[0]), reinterpret_cast<const cf*>(h->d_xt[1]), reinterpret_cast<const cf*>(h->d_xt[2]),
-               reinterpret_cast<const cf*>(h->d_xt[3]), reinterpret_cast<const cf*>(h->d_xh[0])};
+    XTables tb{reinterpret_cast<const cf*>(h->d_xt[0].get()), reinterpret_cast<const cf*>(h->d_xt[1].get()), reinterpret_cast<const cf*>(h->d_xt[2].get()),
+               reinterpret_cast<const cf*>(h->d_xt[3].get()), reinterpret_cast<const cf*>(h->d_xh[0].get())};
     const size_t lds = X_LDS_BYTES;
     static DeviceOnce attr_once;
     if (attr_once.need()) {
@@ -2125,9 +2083,9 @@ comms_status_t comms_fir_run_os16k_decim_dev(comms_fir_t* h, const comms_c32* d_
     const KStamp ks = h->next_stamp();
     const int fault = os16k_fault();
     switch (hr) {
-        case 2: fir_os16k_kernel<2, const float2*, true><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err, fault, dc); break;
-        case 3: fir_os16k_kernel<3, const float2*, true><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err, fault, dc); break;
-        default: fir_os16k_kernel<4, const float2*, true><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err, fault, dc); break;
+        case 2: fir_os16k_kernel<2, const float2*, true><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err(), fault, dc); break;
+        case 3: fir_os16k_kernel<3, const float2*, true><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err(), fault, dc); break;
+        default: fir_os16k_kernel<4, const float2*, true><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err(), fault, dc); break;
     }
     h->toc(s);
     COMMS_TRY(launch_ok("fir_os16k_kernel (decimating)"));
@@ -2172,7 +2130,7 @@ comms_status_t comms_fir_run_os4096_decim_dev(comms_fir_t* h, const void* d_in, 
         mix_host_rotor(static_cast<uint64_t>(256 * j) * frac, c, sn);
         dc.step[j] = make_float2(static_cast<float>(c), static_cast<float>(sn));
     }
-    OsTables tb{reinterpret_cast<const cf*>(h->d_tw1), reinterpret_cast<const cf*>(h->d_tw2), reinterpret_cast<const cf*>(h->d_hparts[0])};
+    OsTables tb{reinterpret_cast<const cf*>(h->d_tw1.get()), reinterpret_cast<const cf*>(h->d_tw2.get()), reinterpret_cast<const cf*>(h->d_hparts[0].get())};
     h->tic(s);
     with_input_view(h, d_in, InC32Split{static_cast<const float*>(d_in)}, [&](auto v) {
         fir_os4096_kernel<decltype(v), true><<<dim3(blocks), dim3(256), 0, s>>>(v, hist, h->n_eff, o, n, h->hblk, nseg, tb, nh, 0, 0, 1, dc);
@@ -2183,11 +2141,7 @@ comms_status_t comms_fir_run_os4096_decim_dev(comms_fir_t* h, const void* d_in, 
     return COMMS_OK;
 }
 
-comms_status_t comms_fir_destroy(comms_fir_t* h) {
-    if (!h) return COMMS_OK;
-    free_fir(h);
-    return COMMS_OK;
-}
+comms_status_t comms_fir_destroy(comms_fir_t* h) { return destroy_handle(h); }
 
 }  // extern "C"
 
@@ -2196,7 +2150,7 @@ struct comms_pulse : Handle {
     int n_taps = 0;
     int sps = 1;
     int hist_len = 0;  // symbols of history kept: ceil(n_taps / sps)
-    float2* d_taps = nullptr;
+    DevBuf<float2> d_taps;
     History hist;
     std::vector<comms_c32> taps;  // host copy (kernel-argument taps of the polyphase kernel)
     bool real_taps = false;
@@ -2208,6 +2162,7 @@ struct comms_pulse : Handle {
     int in_bits = 0;       // comms_pulse_set_input_format: 0 = Complex<f32> symbols, else bits per symbol (1, 2)
     float2 cons[4] = {};   //   ... and the constellation
 };
+static_assert(!std::is_copy_constructible_v<comms_pulse>, "a handle is never copied");
 
 // f(view) with the device view of d_sym that the handle's input format needs: the Complex<f32> pointer, or the
 // packed bits with the constellation (InBits)
@@ -2304,14 +2259,6 @@ static bool pulse_poly_launch(comms_pulse* h, In sym, size_t n_sym, float2* out,
     }
 }
 
-static void free_pulse(comms_pulse* h) {
-    (void)use_device(h->device);
-    if (h->d_taps) (void)hipFree(h->d_taps);
-    h->hist.release();
-    h->fini();
-    delete h;
-}
-
 extern "C" {
 
 comms_status_t comms_pulse_create(const comms_c32* taps, size_t n_taps, size_t sam_per_sym,
@@ -2322,7 +2269,7 @@ comms_status_t comms_pulse_create(const comms_c32* taps, size_t n_taps, size_t s
     COMMS_ARG(sam_per_sym >= 1, "sam_per_sym must be >= 1 (0 underflows in the reference, pulse.rs:88)");
     COMMS_ARG(n_taps <= 8192, "pulse shaping supports at most 8192 taps (got %zu)", n_taps);
     COMMS_ARG(sam_per_sym <= (1u << 20), "sam_per_sym too large");
-    comms_pulse* h = nullptr;
+    HandlePtr<comms_pulse> h;
     COMMS_TRY(make_handle(device, &h));
     h->n_taps = static_cast<int>(n_taps);
     h->sps = static_cast<int>(sam_per_sym);
@@ -2331,14 +2278,9 @@ comms_status_t comms_pulse_create(const comms_c32* taps, size_t n_taps, size_t s
     h->real_taps = true;
     for (size_t k = 0; k < n_taps; ++k)
         if (taps[k].im != 0.0f) h->real_taps = false;
-    hipError_t e = hipMalloc(&h->d_taps, n_taps * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpy(h->d_taps, taps, n_taps * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = h->hist.alloc(h->hist_len, sizeof(float2));
-    if (e != hipSuccess) {
-        free_pulse(h);
-        return fail(COMMS_ERR_DEVICE, "pulse alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->d_taps.upload(reinterpret_cast<const float2*>(taps), n_taps));
+    COMMS_HIP_TRY(h->hist.alloc(h->hist_len, sizeof(float2)));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -2371,11 +2313,11 @@ comms_status_t comms_pulse_run_dev(comms_pulse_t* h, const comms_c32* d_sym, siz
         with_pulse_input(h, d_sym, [&](auto sym) {
             if constexpr (std::is_same<decltype(sym), const float2*>::value)
                 pulse_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(256), h->n_taps * sizeof(float2), s>>>(
-                    sym, h->hist.cur<float2>(), h->hist_len, h->d_taps, h->n_taps, h->sps,
+                    sym, h->hist.cur<float2>(), h->hist_len, h->d_taps.get(), h->n_taps, h->sps,
                     reinterpret_cast<float2*>(d_out), n_sym, h->hist.next<float2>(), mx);
             else
                 pulse_in_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(256), h->n_taps * sizeof(float2), s>>>(
-                    sym, h->hist.cur<float2>(), h->hist_len, h->d_taps, h->n_taps, h->sps,
+                    sym, h->hist.cur<float2>(), h->hist_len, h->d_taps.get(), h->n_taps, h->sps,
                     reinterpret_cast<float2*>(d_out), n_sym, h->hist.next<float2>(), mx);
         });
         h->toc(s);
@@ -2461,10 +2403,6 @@ comms_status_t comms_pulse_set_timer(comms_pulse_t* h, comms_timer_t* t) {
     return COMMS_OK;
 }
 
-comms_status_t comms_pulse_destroy(comms_pulse_t* h) {
-    if (!h) return COMMS_OK;
-    free_pulse(h);
-    return COMMS_OK;
-}
+comms_status_t comms_pulse_destroy(comms_pulse_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

@@ -325,10 +325,7 @@ comms_status_t comms_fir_run_decim_any_dev(comms_fir_t* h, const void* d_in, siz
         COMMS_TRY(h->quiesce());
         h->last_stream = s;  // (quiesce forgot the stream `enter` just recorded: the launch below must stay tracked)
         h->launched = true;
-        if (h->d_any_taps) (void)hipFree(h->d_any_taps);
-        h->d_any_taps = nullptr;
-        COMMS_HIP_TRY(hipMalloc(&h->d_any_taps, tp.size() * sizeof(float2)));
-        COMMS_HIP_TRY(hipMemcpy(h->d_any_taps, tp.data(), tp.size() * sizeof(float2), hipMemcpyHostToDevice));
+        COMMS_HIP_TRY(h->d_any_taps.upload(tp));
         h->any_nt = NT;
     }
     const bool fm = (mode & COMMS_CHAIN_FM) != 0;
@@ -347,7 +344,7 @@ comms_status_t comms_fir_run_decim_any_dev(comms_fir_t* h, const void* d_in, siz
     a.out = d_out;
     a.fm_prev = static_cast<const float2*>(fm_prev);
     a.fm_prev_new = static_cast<float2*>(fm_prev_new);
-    a.taps = h->d_any_taps;
+    a.taps = h->d_any_taps.get();
     a.n = n;
     a.n_out = n / rate;
     a.hist_len = h->n_eff;

@@ -112,9 +112,10 @@ struct ExactFir : Handle {
     int n_eff = 0;      // taps that take part
     int sps = 1;
     int hist_len = 0;   // samples (FIR: n_eff) or symbols (pulse: ceil(n_taps / sps)) of history
-    V* d_taps = nullptr;
+    DevBuf<V> taps;
     History hist;
 };
+static_assert(!std::is_copy_constructible_v<ExactFir<short2>>, "a handle is never copied");
 
 }  // namespace comms
 
@@ -124,38 +125,27 @@ struct comms_fir_i16 : ExactFir<short2> {};
 struct comms_pulse_i16 : ExactFir<short2> {};
 struct comms_fir_f64 : ExactFir<double2> {};
 struct comms_pulse_f64 : ExactFir<double2> {};
+static_assert(!std::is_copy_constructible_v<comms_fir_i16> && !std::is_copy_constructible_v<comms_pulse_i16> &&
+                  !std::is_copy_constructible_v<comms_fir_f64> && !std::is_copy_constructible_v<comms_pulse_f64>,
+              "a handle is never copied");
 
 namespace {
 
 template <class V>
 using CxOf = typename Exact<V>::C;
 
-template <class V>
-void free_exact(ExactFir<V>* h) {
-    (void)use_device(h->device);
-    if (h->d_taps) (void)hipFree(h->d_taps);
-    h->hist.release();
-    h->fini();
-}
-
 template <class V, class H>
 comms_status_t create(const CxOf<V>* taps, size_t n_eff, int sps, size_t hist_len, const CxOf<V>* state, size_t n_state,
                       int32_t device, H** out) {
-    H* h = nullptr;
+    HandlePtr<H> h;
     COMMS_TRY(make_handle(device, &h));
     h->n_eff = static_cast<int>(n_eff);
     h->sps = sps;
     h->hist_len = static_cast<int>(hist_len);
-    hipError_t e = hipMalloc(&h->d_taps, n_eff * sizeof(V));
-    if (e == hipSuccess) e = hipMemcpy(h->d_taps, taps, n_eff * sizeof(V), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = h->hist.alloc(hist_len, sizeof(V));
-    if (e == hipSuccess && n_state) e = h->hist.upload(state, n_state);
-    if (e != hipSuccess) {
-        free_exact<V>(h);
-        delete h;
-        return fail(COMMS_ERR_DEVICE, "%s FIR alloc: %s", Exact<V>::kNoun, hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->taps.upload(reinterpret_cast<const V*>(taps), n_eff));
+    COMMS_HIP_TRY(h->hist.alloc(hist_len, sizeof(V)));
+    if (n_state) COMMS_HIP_TRY(h->hist.upload(state, n_state));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -199,7 +189,7 @@ comms_status_t run_dev(ExactFir<V>* h, const CxOf<V>* d_in, size_t n, CxOf<V>* d
     if (blocks > 8u * kNumCU) blocks = 8u * kNumCU;
     h->tic(s);
     fir_exact_kernel<V><<<dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s>>>(
-        reinterpret_cast<const V*>(d_in), h->hist.template cur<V>(), h->hist_len, h->d_taps, h->n_eff, h->sps,
+        reinterpret_cast<const V*>(d_in), h->hist.template cur<V>(), h->hist_len, h->taps.get(), h->n_eff, h->sps,
         reinterpret_cast<V*>(d_out), n, h->hist.template next<V>());
     h->toc(s);
     COMMS_TRY(launch_ok(Exact<V>::kKernel));
@@ -239,14 +229,6 @@ comms_status_t set_state(ExactFir<V>* h, const CxOf<V>* state, size_t n_state) {
     return COMMS_OK;
 }
 
-template <class H>
-comms_status_t destroy(H* h) {
-    if (!h) return COMMS_OK;
-    free_exact(h);
-    delete h;
-    return COMMS_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -260,7 +242,7 @@ comms_status_t comms_fir_i16_run_dev(comms_fir_i16_t* h, const comms_c16* d_in, 
     return run_dev(h, d_in, n, d_out, stream);
 }
 comms_status_t comms_fir_i16_get_state(comms_fir_i16_t* h, comms_c16* state, size_t n_state) { return get_state(h, state, n_state); }
-comms_status_t comms_fir_i16_destroy(comms_fir_i16_t* h) { return destroy(h); }
+comms_status_t comms_fir_i16_destroy(comms_fir_i16_t* h) { return destroy_handle(h); }
 
 comms_status_t comms_pulse_i16_create(const comms_c16* taps, size_t n_taps, size_t sam_per_sym, int32_t device,
                                       comms_pulse_i16_t** out) {
@@ -272,7 +254,7 @@ comms_status_t comms_pulse_i16_run(comms_pulse_i16_t* h, const comms_c16* sym, s
 comms_status_t comms_pulse_i16_run_dev(comms_pulse_i16_t* h, const comms_c16* d_sym, size_t n_sym, comms_c16* d_out, void* stream) {
     return run_dev(h, d_sym, n_sym, d_out, stream);
 }
-comms_status_t comms_pulse_i16_destroy(comms_pulse_i16_t* h) { return destroy(h); }
+comms_status_t comms_pulse_i16_destroy(comms_pulse_i16_t* h) { return destroy_handle(h); }
 
 comms_status_t comms_fir_f64_create(const comms_c64* taps, size_t n_taps, const comms_c64* state, size_t n_state,
                                     int32_t device, comms_fir_f64_t** out) {
@@ -284,7 +266,7 @@ comms_status_t comms_fir_f64_run_dev(comms_fir_f64_t* h, const comms_c64* d_in, 
 }
 comms_status_t comms_fir_f64_get_state(comms_fir_f64_t* h, comms_c64* state, size_t n_state) { return get_state(h, state, n_state); }
 comms_status_t comms_fir_f64_set_state(comms_fir_f64_t* h, const comms_c64* state, size_t n_state) { return set_state(h, state, n_state); }
-comms_status_t comms_fir_f64_destroy(comms_fir_f64_t* h) { return destroy(h); }
+comms_status_t comms_fir_f64_destroy(comms_fir_f64_t* h) { return destroy_handle(h); }
 
 comms_status_t comms_pulse_f64_create(const comms_c64* taps, size_t n_taps, size_t sam_per_sym, int32_t device,
                                       comms_pulse_f64_t** out) {
@@ -296,6 +278,6 @@ comms_status_t comms_pulse_f64_run(comms_pulse_f64_t* h, const comms_c64* sym, s
 comms_status_t comms_pulse_f64_run_dev(comms_pulse_f64_t* h, const comms_c64* d_sym, size_t n_sym, comms_c64* d_out, void* stream) {
     return run_dev(h, d_sym, n_sym, d_out, stream);
 }
-comms_status_t comms_pulse_f64_destroy(comms_pulse_f64_t* h) { return destroy(h); }
+comms_status_t comms_pulse_f64_destroy(comms_pulse_f64_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

@@ -193,37 +193,35 @@ struct comms_fir : comms::Handle {
     bool os1024_fixed = false;  // COMMS_FIR_OS1024_FIXED: never the ticketed kernel
     int in_fmt = 0;             // COMMS_IQ_C32 / _I16 / _U8: what d_in of the run entries points to
     float in_scale = 1.0f;      // i16 only
-    float2* d_any_taps = nullptr;  // any-rate chain kernel: taps zero-padded to 32 * any_nt
+    comms::DevBuf<float2> d_any_taps;  // any-rate chain kernel: taps zero-padded to 32 * any_nt
     int any_nt = 0;
-    float2* d_p8 = nullptr;     // polyphase frequency-domain chain kernel (fir_poly8.hip): branch spectra + twiddle tables ...
+    comms::DevBuf<float2> d_p8;  // polyphase frequency-domain chain kernel (fir_poly8.hip): branch spectra + twiddle tables ...
     bool p8_pre = false;        //   ... built for this mixer order and (mixer first: folded into the taps) increment
     uint64_t p8_frac = 0;
     // direct form
     int NP = 0;          // taps padded to a multiple of 8
-    float2* d_taps_pad = nullptr;
+    comms::DevBuf<float2> d_taps_pad;
     // overlap-save, F = 1024 (wave per segment)
     bool w_ready = false;
-    float2* d_wtw1 = nullptr;
-    float2* d_wtw2 = nullptr;
-    float2* d_whdev = nullptr;
+    comms::DevBuf<float2> d_wtw1, d_wtw2, d_whdev;
     // overlap-save, F = 4096 (workgroup per segment)
     bool os_ready = false;
     int hblk = 0;        // halo = 256*hblk >= (taps per partition) - 1
     // overlap-save, F = 16384 (workgroup per segment), > 2049 taps; partitions of 4097 taps
     bool x_ready = false;
     int x_part = 1;
-    unsigned* err_host = nullptr;  // sticky error word of the 16384-point kernel (pinned host memory) ...
-    unsigned* d_err = nullptr;     //   ... as the device addresses it
-    float2* d_xt[4] = {nullptr, nullptr, nullptr, nullptr};  // tw1, tw2, ta, tb
-    std::vector<float2*> d_xh;                                // spectrum per partition
+    comms::Pinned err;  // sticky error word of the 16384-point kernel: pinned, coherent, mapped (empty until that kernel is prepared)
+    unsigned* err_host() const { return static_cast<unsigned*>(err.h); }
+    unsigned* d_err() const { return static_cast<unsigned*>(err.d); }  // ... as the device addresses it
+    comms::DevBuf<float2> d_xt[4];             // tw1, tw2, ta, tb
+    std::vector<comms::DevBuf<float2>> d_xh;   // spectrum per partition
     int n_part = 1;      // (4096-pt kernel, forced) > 3841 taps: partitions of OS_PART taps
-    std::vector<float2*> d_hparts;  // filter spectrum per partition (d_hdev = partition 0)
-    float2* d_tw1 = nullptr;
-    float2* d_tw2 = nullptr;
-    float2* d_hdev = nullptr;
+    std::vector<comms::DevBuf<float2>> d_hparts;  // filter spectrum per partition
+    comms::DevBuf<float2> d_tw1, d_tw2;
     comms::History hist;  // last n_eff input samples
     std::vector<comms_c32> taps;  // effective taps (host copy)
 };
+static_assert(!std::is_copy_constructible_v<comms_fir>, "a handle is never copied");
 
 namespace comms {
 // Bytes of one IQ sample in a COMMS_IQ_* format
@@ -244,9 +242,9 @@ auto with_input_view(const comms_fir* h, const void* d_in, C32 c32, F&& f) {
 // call's own launches have been waited for: the synchronous caller of the failing call gets COMMS_ERR_DEVICE, not the
 // invalid samples with COMMS_OK.
 inline comms_status_t fir_check_sticky(const comms_fir* h) {
-    if (h->err_host && __atomic_load_n(h->err_host, __ATOMIC_RELAXED) != 0)
+    if (h->err_host() && __atomic_load_n(h->err_host(), __ATOMIC_RELAXED) != 0)
         return fail(COMMS_ERR_DEVICE, "fir_os16k_kernel: a workgroup's LDS wait ran out (code %u): the outputs of that call "
-                                      "are invalid and the handle is unusable", *h->err_host);
+                                      "are invalid and the handle is unusable", *h->err_host());
     return COMMS_OK;
 }
 }  // namespace comms

@@ -500,10 +500,10 @@ static comms_status_t poly8_prepare(comms_fir* h, bool pre, uint64_t frac, hipSt
         ln[3 * 64 + lane] = root(static_cast<long long>(q1 + 4) * k1, 128, +1);
         for (int tq = 1; tq < 4; ++tq) ln[(3 + tq) * 64 + lane] = root(static_cast<long long>(tq) * ka, 16, +1);
     }
-    if (!h->d_p8) COMMS_HIP_TRY(hipMalloc(&h->d_p8, t.size() * sizeof(float2)));
+    if (!h->d_p8) COMMS_HIP_TRY(h->d_p8.alloc(t.size()));
     // (in stream order behind the launches that still read the old tables; the source is pageable memory, so the call returns
     // once the copy has been staged)
-    COMMS_HIP_TRY(hipMemcpyAsync(h->d_p8, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice, s));
+    COMMS_HIP_TRY(hipMemcpyAsync(h->d_p8.get(), t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice, s));
     COMMS_HIP_TRY(hipStreamSynchronize(s));
     h->p8_pre = pre;
     h->p8_frac = frac;
@@ -651,7 +651,7 @@ comms_status_t comms_fir_run_poly8_dev(comms_fir_t* h, const void* d_in, size_t 
     COMMS_TRY(h->enter(stream, &s));
     COMMS_TRY(poly8_prepare(h, (mode & COMMS_CHAIN_PRE) != 0, frac, s));
     P8Tables tb;
-    tb.g = reinterpret_cast<const cf*>(h->d_p8);
+    tb.g = reinterpret_cast<const cf*>(h->d_p8.get());
     tb.tw = tb.g + 2048;
     tb.sc = tb.tw + 128;
     tb.lane = tb.sc + 64;

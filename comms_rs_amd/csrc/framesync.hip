@@ -194,24 +194,15 @@ struct comms_framesync : Handle {
     long long origin = 0;      // positions below it are no detections (0; the position of the last flush)
     size_t lds = 0;
     unsigned max_grid = 1;
-    float* d_taps = nullptr;   // [2][P padded to a multiple of eight]: re p, -im p
+    DevBuf<float> d_taps;      // [2][P padded to a multiple of eight]: re p, -im p
     int NP8 = 0;
-    float2* d_zero = nullptr;  // P + G zero symbols (flush)
+    DevBuf<float2> d_zero;     // P + G zero symbols (flush)
     Scratch list;              // count (8 bytes), then the detections of a call
     History hist;              // last H symbols
 };
+static_assert(!std::is_copy_constructible_v<comms_framesync>, "a handle is never copied");
 
 namespace {
-
-void free_framesync(comms_framesync* h) {
-    (void)use_device(h->device);
-    if (h->d_taps) (void)hipFree(h->d_taps);
-    if (h->d_zero) (void)hipFree(h->d_zero);
-    h->list.release();
-    h->hist.release();
-    h->fini();
-    delete h;
-}
 
 comms_status_t check_word_guard(size_t n_word, size_t guard) {
     COMMS_ARG(n_word >= FS_MIN_WORD && n_word <= FS_MAX_WORD, "n_word must be %zu ... %zu symbols (got %zu)", FS_MIN_WORD, FS_MAX_WORD, n_word);
@@ -244,8 +235,8 @@ comms_status_t framesync_step(comms_framesync* h, const comms_c32* d_in, size_t 
     a.in = reinterpret_cast<const float2*>(d_in);
     a.hist = h->hist.cur<float2>();
     a.new_hist = h->hist.next<float2>();
-    a.tre = h->d_taps;
-    a.tim = h->d_taps + h->NP8;
+    a.tre = h->d_taps.get();
+    a.tim = h->d_taps.get() + h->NP8;
     a.n = n;
     a.tiles = (n + FS_TILE - 1) / FS_TILE;
     a.k_first = static_cast<long long>(h->T) - (h->P + h->G) + 1;
@@ -314,7 +305,7 @@ comms_status_t comms_framesync_create(const comms_c32* word, size_t n_word, doub
         ep += static_cast<double>(word[j].re) * word[j].re + static_cast<double>(word[j].im) * word[j].im;
     }
     COMMS_ARG(static_cast<float>(ep) > 0.0f && std::isfinite(static_cast<float>(ep)), "the word has no energy (or too much for f32)");
-    comms_framesync* h = nullptr;
+    HandlePtr<comms_framesync> h;
     COMMS_TRY(make_handle(device, &h));
     h->P = static_cast<int>(n_word);
     h->G = static_cast<int>(guard);
@@ -331,17 +322,10 @@ comms_status_t comms_framesync_create(const comms_c32* word, size_t n_word, doub
         taps[j] = word[j].re;
         taps[h->NP8 + j] = -word[j].im;
     }
-    const size_t nz = static_cast<size_t>(h->P + h->G);
-    hipError_t e = hipMalloc(&h->d_taps, taps.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&h->d_zero, nz * sizeof(float2));
-    if (e == hipSuccess) e = zero_device(h->d_zero, nz * sizeof(float2));
-    if (e == hipSuccess) e = h->hist.alloc(static_cast<size_t>(h->H), sizeof(comms_c32));
-    if (e != hipSuccess) {
-        free_framesync(h);
-        return fail(COMMS_ERR_DEVICE, "frame synchroniser alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->d_taps.upload(taps));
+    COMMS_HIP_TRY(h->d_zero.alloc_zero(static_cast<size_t>(h->P + h->G)));
+    COMMS_HIP_TRY(h->hist.alloc(static_cast<size_t>(h->H), sizeof(comms_c32)));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -390,7 +374,7 @@ comms_status_t comms_framesync_flush(comms_framesync_t* h, comms_frame_detection
     *n_found = 0;
     COMMS_TRY(use_device(h->device));
     const uint64_t T = h->T;
-    COMMS_TRY(framesync_step(h, reinterpret_cast<const comms_c32*>(h->d_zero), static_cast<size_t>(h->P + h->G), out, cap, n_found,
+    COMMS_TRY(framesync_step(h, reinterpret_cast<const comms_c32*>(h->d_zero.get()), static_cast<size_t>(h->P + h->G), out, cap, n_found,
                              COMMS_STREAM_HANDLE));
     h->T = T;
     h->origin = static_cast<long long>(T);
@@ -453,12 +437,6 @@ comms_status_t comms_framesync_set_timer(comms_framesync_t* h, comms_timer_t* t)
     return COMMS_OK;
 }
 
-comms_status_t comms_framesync_destroy(comms_framesync_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    (void)h->quiesce();
-    free_framesync(h);
-    return COMMS_OK;
-}
+comms_status_t comms_framesync_destroy(comms_framesync_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

@@ -255,6 +255,7 @@ struct comms_noise : Handle {
         return s;
     }
 };
+static_assert(!std::is_copy_constructible_v<comms_noise>, "a handle is never copied");
 
 // lanes own blocks; at most 8 workgroups of 256 per CU, the grid-stride loop takes the rest
 static unsigned noise_grid(size_t n_values, unsigned off) {
@@ -308,26 +309,15 @@ extern "C" {
 comms_status_t comms_noise_create(uint64_t seed, uint64_t stream, int32_t device, comms_noise_t** out) {
     COMMS_ARG(out != nullptr, "out is NULL");
     *out = nullptr;
-    comms_noise* h = new (std::nothrow) comms_noise;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    HandlePtr<comms_noise> h;
+    COMMS_TRY(make_handle(device, &h));
     h->seed = seed;
     h->strm = stream;
-    *out = h;
+    *out = h.release();
     return COMMS_OK;
 }
 
-comms_status_t comms_noise_destroy(comms_noise_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    h->fini();
-    delete h;
-    return COMMS_OK;
-}
+comms_status_t comms_noise_destroy(comms_noise_t* h) { return destroy_handle(h); }
 
 comms_status_t comms_noise_set_timer(comms_noise_t* h, comms_timer_t* t) {
     COMMS_ARG(h != nullptr, "handle is NULL");

@@ -299,6 +299,7 @@ struct comms_mixer : Handle {
     uint64_t turns;      // current phase as a fraction of T, 2^-64 units
     uint64_t frac;       // dphase as a fraction of T
 };
+static_assert(!std::is_copy_constructible_v<comms_mixer>, "a handle is never copied");
 
 static uint64_t to_turns(double angle) { return mix_to_turns(angle); }
 static void host_rotor(uint64_t turns, double& c, double& s) { mix_host_rotor(turns, c, s); }
@@ -310,18 +311,13 @@ comms_status_t comms_mixer_create(double dphase, double phase, int32_t device,
     COMMS_ARG(out != nullptr, "out is NULL");
     *out = nullptr;
     COMMS_ARG(std::isfinite(dphase) && std::isfinite(phase), "dphase/phase must be finite");
-    comms_mixer* h = new (std::nothrow) comms_mixer;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    HandlePtr<comms_mixer> h;
+    COMMS_TRY(make_handle(device, &h));
     dphase = mix_wrap_dphase(dphase);  // Mixer::new (src/mixer.rs:43-51)
     h->dphase = dphase;
     h->frac = to_turns(dphase);
     h->turns = to_turns(phase);
-    *out = h;
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -434,13 +430,7 @@ comms_status_t comms_mixer_set_timer(comms_mixer_t* h, comms_timer_t* t) {
     return COMMS_OK;
 }
 
-comms_status_t comms_mixer_destroy(comms_mixer_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    h->fini();
-    delete h;
-    return COMMS_OK;
-}
+comms_status_t comms_mixer_destroy(comms_mixer_t* h) { return destroy_handle(h); }
 
 // ------------------------------------------------------------------ decimate / upsample
 comms_status_t comms_decimate_out_len(size_t n, size_t rate, size_t* out_n) {
@@ -558,30 +548,20 @@ comms_status_t comms_upsample_run(const void* in, size_t n, size_t elem, size_t 
 
 // ------------------------------------------------------------------ FM demod handle
 struct comms_fmdemod : Handle {
-    float2* d_prev = nullptr;  // FM.prev (analog.rs:9), starts 0+0i: two words, d_prev[cur] is the current one
+    DevBuf<float2> d_prev;  // FM.prev (analog.rs:9), starts 0+0i: two words, d_prev[cur] is the current one
     int cur = 0;
 };
+static_assert(!std::is_copy_constructible_v<comms_fmdemod>, "a handle is never copied");
 
 extern "C" {
 
 comms_status_t comms_fmdemod_create(int32_t device, comms_fmdemod_t** out) {
     COMMS_ARG(out != nullptr, "out is NULL");
     *out = nullptr;
-    comms_fmdemod* h = new (std::nothrow) comms_fmdemod;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
-    hipError_t e = hipMalloc(&h->d_prev, 2 * sizeof(float2));
-    if (e == hipSuccess) e = zero_device(h->d_prev, 2 * sizeof(float2));
-    if (e != hipSuccess) {
-        h->fini();
-        delete h;
-        return fail(COMMS_ERR_DEVICE, "fmdemod state alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    HandlePtr<comms_fmdemod> h;
+    COMMS_TRY(make_handle(device, &h));
+    COMMS_HIP_TRY(h->d_prev.alloc_zero(2));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -599,9 +579,9 @@ comms_status_t comms_fmdemod_run_dev(comms_fmdemod_t* h, const comms_c32* d_in, 
     bool aligned = ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0;
     h->tic(s);
     if (aligned)
-        fmdemod_kernel<true><<<dim3(blocks), dim3(256), 0, s>>>(in, h->d_prev + h->cur, h->d_prev + (h->cur ^ 1), d_out, n);
+        fmdemod_kernel<true><<<dim3(blocks), dim3(256), 0, s>>>(in, h->d_prev.get() + h->cur, h->d_prev.get() + (h->cur ^ 1), d_out, n);
     else
-        fmdemod_kernel<false><<<dim3(blocks), dim3(256), 0, s>>>(in, h->d_prev + h->cur, h->d_prev + (h->cur ^ 1), d_out, n);
+        fmdemod_kernel<false><<<dim3(blocks), dim3(256), 0, s>>>(in, h->d_prev.get() + h->cur, h->d_prev.get() + (h->cur ^ 1), d_out, n);
     h->toc(s);
     COMMS_TRY(launch_ok("fmdemod_kernel"));
     h->cur ^= 1;  // the kernel stored the batch's last sample in the other word (no separate copy command)
@@ -624,7 +604,7 @@ comms_status_t comms_fmdemod_get_prev(comms_fmdemod_t* h, comms_c32* out_prev) {
     COMMS_ARG(h && out_prev, "NULL argument");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(hipMemcpy(out_prev, h->d_prev + h->cur, sizeof(float2), hipMemcpyDeviceToHost));
+    COMMS_HIP_TRY(hipMemcpy(out_prev, h->d_prev.get() + h->cur, sizeof(float2), hipMemcpyDeviceToHost));
     return COMMS_OK;
 }
 
@@ -632,7 +612,7 @@ comms_status_t comms_fmdemod_set_prev(comms_fmdemod_t* h, const comms_c32* prev)
     COMMS_ARG(h && prev, "NULL argument");
     COMMS_TRY(use_device(h->device));
     COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(hipMemcpy(h->d_prev + h->cur, prev, sizeof(float2), hipMemcpyHostToDevice));
+    COMMS_HIP_TRY(hipMemcpy(h->d_prev.get() + h->cur, prev, sizeof(float2), hipMemcpyHostToDevice));
     return COMMS_OK;
 }
 
@@ -642,13 +622,6 @@ comms_status_t comms_fmdemod_set_timer(comms_fmdemod_t* h, comms_timer_t* t) {
     return COMMS_OK;
 }
 
-comms_status_t comms_fmdemod_destroy(comms_fmdemod_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    if (h->d_prev) (void)hipFree(h->d_prev);
-    h->fini();
-    delete h;
-    return COMMS_OK;
-}
+comms_status_t comms_fmdemod_destroy(comms_fmdemod_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

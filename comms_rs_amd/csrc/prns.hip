@@ -114,19 +114,14 @@ struct comms_prns : Handle {
     int W = 8;
     uint64_t mask = 0, state = 0;
     uint64_t pw[kPrnsPowers][64] = {};  // A^(2^i), rows (host copy)
-    uint64_t* d_pw = nullptr;           // the same table on the device
+    DevBuf<uint64_t> d_pw;              // the same table on the device
     void advance(uint64_t n) {
         for (int i = 0; i < kPrnsPowers; ++i)
             if ((n >> i) & 1) state = host_matvec(pw[i], W, state);
     }
 };
 
-static void free_prns(comms_prns* h) {
-    (void)use_device(h->device);
-    if (h->d_pw) (void)hipFree(h->d_pw);
-    h->fini();
-    delete h;
-}
+static_assert(!std::is_copy_constructible_v<comms_prns>, "a handle is never copied");
 
 static uint64_t width_mask(int W) { return W == 64 ? ~0ull : (1ull << W) - 1; }
 
@@ -139,13 +134,8 @@ comms_status_t comms_prns_create(uint64_t poly_mask, uint64_t state, int32_t wid
               "the register is 8, 16, 32 or 64 bits wide (got %d; signed types panic in the reference)", width_bits);
     COMMS_ARG((poly_mask & ~width_mask(width_bits)) == 0, "poly_mask does not fit %d bits", width_bits);
     COMMS_ARG((state & ~width_mask(width_bits)) == 0, "state does not fit %d bits", width_bits);
-    comms_prns* h = new (std::nothrow) comms_prns;
-    COMMS_ARG(h != nullptr, "out of host memory");
-    comms_status_t st = h->init(device);
-    if (st != COMMS_OK) {
-        delete h;
-        return st;
-    }
+    HandlePtr<comms_prns> h;
+    COMMS_TRY(make_handle(device, &h));
     const int W = width_bits;
     h->W = W;
     h->mask = poly_mask;
@@ -153,13 +143,8 @@ comms_status_t comms_prns_create(uint64_t poly_mask, uint64_t state, int32_t wid
     h->pw[0][0] = poly_mask;
     for (int i = 1; i < W; ++i) h->pw[0][i] = 1ull << (i - 1);
     for (int k = 1; k < kPrnsPowers; ++k) host_matmul(h->pw[k - 1], h->pw[k - 1], W, h->pw[k]);
-    hipError_t e = hipMalloc(&h->d_pw, sizeof(h->pw));
-    if (e == hipSuccess) e = hipMemcpy(h->d_pw, h->pw, sizeof(h->pw), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        free_prns(h);
-        return fail(COMMS_ERR_DEVICE, "prns alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->d_pw.upload(&h->pw[0][0], kPrnsPowers * 64));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -179,7 +164,7 @@ comms_status_t comms_prns_run_dev(comms_prns_t* h, size_t n, int32_t format, uin
     const int lg = lb + 8;
     const int packed = format == COMMS_BITS_PACKED;
     h->tic(s);
-#define COMMS_PRNS_GO(W) prns_kernel<W><<<dim3(1u << lb), dim3(256), 0, s>>>(h->d_pw, h->state, n, d_out, packed, lg)
+#define COMMS_PRNS_GO(W) prns_kernel<W><<<dim3(1u << lb), dim3(256), 0, s>>>(h->d_pw.get(), h->state, n, d_out, packed, lg)
     switch (h->W) {
         case 8: COMMS_PRNS_GO(8); break;
         case 16: COMMS_PRNS_GO(16); break;
@@ -232,10 +217,6 @@ comms_status_t comms_prns_set_timer(comms_prns_t* h, comms_timer_t* t) {
     return COMMS_OK;
 }
 
-comms_status_t comms_prns_destroy(comms_prns_t* h) {
-    if (!h) return COMMS_OK;
-    free_prns(h);
-    return COMMS_OK;
-}
+comms_status_t comms_prns_destroy(comms_prns_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

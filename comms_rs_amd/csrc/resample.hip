@@ -199,12 +199,13 @@ struct comms_resample : Handle {
     bool tab_lds = true;
     size_t lds = 0;
     unsigned max_grid = 1;
-    float* d_tab = nullptr;
+    DevBuf<float> d_tab;
     History hist;                   // last Q samples
     // the series: the complex FIR node carries the state (of the UPSAMPLED stream); two scratch streams of n up samples
-    comms_fir_t* fir = nullptr;
+    InnerHandle<comms_fir_t, comms_fir_destroy> fir;
     Scratch sa, sb;
 };
+static_assert(!std::is_copy_constructible_v<comms_resample>, "a handle is never copied");
 
 namespace {
 
@@ -228,17 +229,6 @@ bool plan_tile(comms_resample* h, size_t tab_bytes) {
             return true;
         }
     return false;
-}
-
-void free_resample(comms_resample* h) {
-    (void)use_device(h->device);
-    if (h->fir) (void)comms_fir_destroy(h->fir);
-    if (h->d_tab) (void)hipFree(h->d_tab);
-    h->hist.release();
-    h->sa.release();
-    h->sb.release();
-    h->fini();
-    delete h;
 }
 
 template <class T, bool TAB_LDS>
@@ -266,14 +256,14 @@ comms_status_t run_series(comms_resample* h, const void* d_in, size_t n, void* d
     comms_c32* xb = static_cast<comms_c32*>(h->sb.p);
     if (h->elem == COMMS_RESAMPLE_C32) {
         COMMS_TRY(comms_upsample_run_dev(d_in, n, 8, h->up, xa, nullptr, h->device, s));
-        COMMS_TRY(comms_fir_run_dev(h->fir, xa, nu, xb, s));
+        COMMS_TRY(comms_fir_run_dev(h->fir.get(), xa, nu, xb, s));
         return comms_decimate_run_dev(xb, nu, 8, h->down, d_out, nullptr, h->device, s);
     }
     float* fa = reinterpret_cast<float*>(xa);
     float* fb = reinterpret_cast<float*>(xb);
     COMMS_TRY(comms_upsample_run_dev(d_in, n, 4, h->up, fb, nullptr, h->device, s));
     COMMS_TRY(comms_iq_real_to_c32_dev(fb, nu, xa, h->device, s));
-    COMMS_TRY(comms_fir_run_dev(h->fir, xa, nu, xb, s));
+    COMMS_TRY(comms_fir_run_dev(h->fir.get(), xa, nu, xb, s));
     COMMS_TRY(comms_iq_c32_re_dev(xb, nu, fa, h->device, s));
     return comms_decimate_run_dev(fa, nu, 4, h->down, d_out, nullptr, h->device, s);
 }
@@ -306,7 +296,7 @@ comms_status_t comms_resample_create(const float* taps, size_t n_taps, size_t up
     COMMS_ARG(elem == COMMS_RESAMPLE_F32 || elem == COMMS_RESAMPLE_C32, "elem must be COMMS_RESAMPLE_F32 (4) or COMMS_RESAMPLE_C32 (8), got %d", elem);
     COMMS_ARG(up <= 0x7fffffffu && down <= 0x7fffffffu, "rates %zu / %zu are out of range", up, down);
     COMMS_ARG(n_taps <= (1u << 20), "too many taps (%zu)", n_taps);
-    comms_resample* h = nullptr;
+    HandlePtr<comms_resample> h;
     COMMS_TRY(make_handle(device, &h));
     h->elem = elem;
     h->n_taps = n_taps;
@@ -319,35 +309,26 @@ comms_status_t comms_resample_create(const float* taps, size_t n_taps, size_t up
     if (h->series) {
         std::vector<comms_c32> ct(n_taps);
         for (size_t k = 0; k < n_taps; ++k) ct[k] = comms_c32{taps[k], 0.0f};
-        const comms_status_t st = comms_fir_create(ct.data(), n_taps, nullptr, 0, device, &h->fir);
-        if (st != COMMS_OK) {
-            free_resample(h);
-            return st;
-        }
-        *out = h;
+        comms_fir_t* fir = nullptr;
+        COMMS_TRY(comms_fir_create(ct.data(), n_taps, nullptr, 0, device, &fir));
+        h->fir.reset(fir);
+        *out = h.release();
         return COMMS_OK;
     }
     h->NB = static_cast<int>((QP + 3) / 4);
     h->RS = 4 * (h->NB | 1);  // RS / 4 odd
     const size_t tab_floats = L * h->RS;
-    h->tab_lds = plan_tile(h, tab_floats * 4);
-    if (!h->tab_lds && !plan_tile(h, 0)) {
-        free_resample(h);
+    h->tab_lds = plan_tile(h.get(), tab_floats * 4);
+    if (!h->tab_lds && !plan_tile(h.get(), 0))
         return fail(COMMS_ERR_DEVICE, "resample: no tile fits (up %zu, down %zu, %zu taps)", L, M, n_taps);
-    }
     h->WG = h->TO >= 256 ? 256 : h->TO < 64 ? 64 : h->TO;
     h->max_grid = resident_workgroups(h->lds);
     std::vector<float> tab(tab_floats, 0.0f);
     for (size_t p = 0; p < L; ++p)
         for (size_t q = 0; p + L * q < n_taps; ++q) tab[p * h->RS + q] = taps[p + L * q];
-    hipError_t e = hipMalloc(&h->d_tab, tab.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = h->hist.alloc(h->Q, static_cast<size_t>(elem));
-    if (e != hipSuccess) {
-        free_resample(h);
-        return fail(COMMS_ERR_DEVICE, "resample alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->d_tab.upload(tab));
+    COMMS_HIP_TRY(h->hist.alloc(h->Q, static_cast<size_t>(elem)));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -372,7 +353,7 @@ comms_status_t comms_resample_run_dev(comms_resample_t* h, const void* d_in, siz
     a.hist = h->hist.cur();
     a.new_hist = h->hist.next();
     a.out = d_out;
-    a.taps = h->d_tab;
+    a.taps = h->d_tab.get();
     a.n = n;
     a.n_out = n_out;
     a.tiles = tiles;
@@ -429,7 +410,7 @@ comms_status_t comms_resample_get_state(comms_resample_t* h, void* state, size_t
         // the inner state is that of the upsampled stream, newest first: entry up - 1 + up q holds input sample n - 1 - q
         const size_t m = h->up * n_state;
         std::vector<comms_c32> cs(m);
-        COMMS_TRY(comms_fir_get_state(h->fir, cs.data(), m));
+        COMMS_TRY(comms_fir_get_state(h->fir.get(), cs.data(), m));
         for (size_t q = 0; q < n_state; ++q) {
             const comms_c32 v = cs[h->up - 1 + h->up * q];
             if (E == 8) static_cast<comms_c32*>(state)[q] = v;
@@ -452,7 +433,7 @@ comms_status_t comms_resample_set_state(comms_resample_t* h, const void* state, 
         std::vector<comms_c32> cs(h->n_taps, comms_c32{0.0f, 0.0f});  // the stuffed zeros between the input samples
         for (size_t q = 0; q < n_state; ++q)
             cs[h->up - 1 + h->up * q] = E == 8 ? static_cast<const comms_c32*>(state)[q] : comms_c32{static_cast<const float*>(state)[q], 0.0f};
-        return comms_fir_set_state(h->fir, cs.data(), cs.size());
+        return comms_fir_set_state(h->fir.get(), cs.data(), cs.size());
     }
     COMMS_HIP_TRY(h->hist.upload(state, n_state));
     return COMMS_OK;
@@ -462,7 +443,7 @@ comms_status_t comms_resample_get_kernel(const comms_resample_t* h, size_t n, ch
     COMMS_ARG(h && name && name_len, "NULL argument");
     if (h->series) {
         char fir[64] = {0};
-        COMMS_TRY(comms_fir_get_kernel(h->fir, n * h->up, fir, sizeof fir));
+        COMMS_TRY(comms_fir_get_kernel(h->fir.get(), n * h->up, fir, sizeof fir));
         if (h->elem == COMMS_RESAMPLE_C32)
             std::snprintf(name, name_len, "series: upsample_kernel + %s + decimate_kernel", fir);
         else
@@ -477,16 +458,10 @@ comms_status_t comms_resample_get_kernel(const comms_resample_t* h, size_t n, ch
 comms_status_t comms_resample_set_timer(comms_resample_t* h, comms_timer_t* t) {
     COMMS_ARG(h != nullptr, "handle is NULL");
     h->timer = t;
-    if (h->fir) return comms_fir_set_timer(h->fir, t);  // the series: the pair brackets its FIR launch
+    if (h->fir.get()) return comms_fir_set_timer(h->fir.get(), t);  // the series: the pair brackets its FIR launch
     return COMMS_OK;
 }
 
-comms_status_t comms_resample_destroy(comms_resample_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    (void)h->quiesce();
-    free_resample(h);
-    return COMMS_OK;
-}
+comms_status_t comms_resample_destroy(comms_resample_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

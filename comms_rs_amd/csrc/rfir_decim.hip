@@ -157,29 +157,19 @@ struct comms_rfir : Handle {
     // rfir_decim_kernel
     int OUT = 1, WG = 256, MP = 8, stride = 0;
     size_t lds = 0;
-    float* d_tab = nullptr;
+    DevBuf<float> d_tab;
     History hist;      // last n_eff samples
     // the series: the complex FIR node carries the state; two Complex<f32> scratch streams
-    comms_fir_t* fir = nullptr;
+    InnerHandle<comms_fir_t, comms_fir_destroy> fir;
     Scratch sa, sb;
 };
+static_assert(!std::is_copy_constructible_v<comms_rfir>, "a handle is never copied");
 
 namespace {
 
 constexpr int RF_MAX_TAPS = 257, RF_MAX_RATE = 64;
 
 // (the stride of the phase arrays: plan_stride, common.hpp)
-void free_rfir(comms_rfir* h) {
-    (void)use_device(h->device);
-    if (h->fir) (void)comms_fir_destroy(h->fir);
-    if (h->d_tab) (void)hipFree(h->d_tab);
-    h->hist.release();
-    h->sa.release();
-    h->sb.release();
-    h->fini();
-    delete h;
-}
-
 template <int OUT>
 comms_status_t launch_rfir(const RfArgs& a, unsigned blocks, int wg, size_t lds, hipStream_t s) {
     static DeviceOnce once;
@@ -204,7 +194,7 @@ comms_status_t run_series(comms_rfir* h, const float* d_in, size_t n, float* d_o
         d_in = reinterpret_cast<const float*>(y);
     }
     COMMS_TRY(comms_iq_real_to_c32_dev(d_in, n, x, h->device, s));
-    COMMS_TRY(comms_fir_run_dev(h->fir, x, n, y, s));
+    COMMS_TRY(comms_fir_run_dev(h->fir.get(), x, n, y, s));
     float* re = reinterpret_cast<float*>(x);
     COMMS_TRY(comms_iq_c32_re_dev(y, n, re, h->device, s));
     return comms_decimate_run_dev(re, n, 4, static_cast<size_t>(h->rate), d_out, nullptr, h->device, s);
@@ -226,7 +216,7 @@ comms_status_t comms_rfir_create(const float* taps, size_t n_taps, const float* 
     size_t n_eff = n_taps;
     if (state && n_state < n_eff) n_eff = n_state;  // zip(taps, state), fir.rs:53
     COMMS_ARG(n_eff <= (1u << 20), "too many taps (%zu)", n_eff);
-    comms_rfir* h = nullptr;
+    HandlePtr<comms_rfir> h;
     COMMS_TRY(make_handle(device, &h));
     h->n_eff = static_cast<int>(n_eff);
     h->rate = rate < 1 ? 1 : static_cast<int>(rate);
@@ -235,12 +225,10 @@ comms_status_t comms_rfir_create(const float* taps, size_t n_taps, const float* 
         std::vector<comms_c32> ct(n_eff), cs(state ? n_eff : 0);
         for (size_t k = 0; k < n_eff; ++k) ct[k] = comms_c32{taps[k], 0.0f};
         for (size_t k = 0; k < cs.size(); ++k) cs[k] = comms_c32{state[k], 0.0f};
-        const comms_status_t st = comms_fir_create(ct.data(), n_eff, state ? cs.data() : nullptr, cs.size(), device, &h->fir);
-        if (st != COMMS_OK) {
-            free_rfir(h);
-            return st;
-        }
-        *out = h;
+        comms_fir_t* fir = nullptr;
+        COMMS_TRY(comms_fir_create(ct.data(), n_eff, state ? cs.data() : nullptr, cs.size(), device, &fir));
+        h->fir.reset(fir);
+        *out = h.release();
         return COMMS_OK;
     }
     const int R = h->rate, N = h->n_eff;
@@ -258,16 +246,11 @@ comms_status_t comms_rfir_create(const float* taps, size_t n_taps, const float* 
             const long long k = static_cast<long long>(R) * m - r;
             if (k >= 0 && k < N) tab[static_cast<size_t>(r) * h->MP + m] = taps[k];
         }
-    hipError_t e = h->lds <= 64 * 1024 ? hipSuccess : hipErrorInvalidValue;
-    if (e == hipSuccess) e = hipMalloc(&h->d_tab, tab.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = h->hist.alloc(n_eff, sizeof(float));
-    if (e == hipSuccess && state) e = h->hist.upload(state, n_state);
-    if (e != hipSuccess) {
-        free_rfir(h);
-        return fail(COMMS_ERR_DEVICE, "real FIR alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    if (h->lds > 64 * 1024) return fail(COMMS_ERR_DEVICE, "real FIR alloc: %s", hipGetErrorString(hipErrorInvalidValue));
+    COMMS_HIP_TRY(h->d_tab.upload(tab));
+    COMMS_HIP_TRY(h->hist.alloc(n_eff, sizeof(float)));
+    if (state) COMMS_HIP_TRY(h->hist.upload(state, n_state));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -288,7 +271,7 @@ comms_status_t comms_rfir_run_dev(comms_rfir_t* h, const float* d_in, size_t n, 
     a.hist = h->hist.cur<float>();
     a.new_hist = h->hist.next<float>();
     a.out = d_out;
-    a.taps = h->d_tab;
+    a.taps = h->d_tab.get();
     a.n = n;
     a.n_out = n_out;
     a.hist_len = h->n_eff;
@@ -334,7 +317,7 @@ comms_status_t comms_rfir_get_state(comms_rfir_t* h, float* state, size_t n_stat
     if (!n_state) return COMMS_OK;  // (an empty read: the series' inner getter takes no empty buffer)
     if (h->series) {
         std::vector<comms_c32> cs(n_state);
-        COMMS_TRY(comms_fir_get_state(h->fir, cs.data(), n_state));
+        COMMS_TRY(comms_fir_get_state(h->fir.get(), cs.data(), n_state));
         for (size_t k = 0; k < n_state; ++k) state[k] = cs[k].re;
         return COMMS_OK;
     }
@@ -350,7 +333,7 @@ comms_status_t comms_rfir_set_state(comms_rfir_t* h, const float* state, size_t 
     if (h->series) {
         std::vector<comms_c32> cs(n_state);
         for (size_t k = 0; k < n_state; ++k) cs[k] = comms_c32{state[k], 0.0f};
-        return comms_fir_set_state(h->fir, cs.data(), n_state);
+        return comms_fir_set_state(h->fir.get(), cs.data(), n_state);
     }
     COMMS_HIP_TRY(h->hist.upload(state, n_state));
     return COMMS_OK;
@@ -360,7 +343,7 @@ comms_status_t comms_rfir_get_kernel(const comms_rfir_t* h, size_t n, char* name
     COMMS_ARG(h && name && name_len, "NULL argument");
     if (h->series) {
         char fir[64] = {0};
-        COMMS_TRY(comms_fir_get_kernel(h->fir, n, fir, sizeof fir));
+        COMMS_TRY(comms_fir_get_kernel(h->fir.get(), n, fir, sizeof fir));
         std::snprintf(name, name_len, "series: real_to_c32_kernel + %s + c32_re_kernel + decimate_kernel", fir);
     } else {
         std::snprintf(name, name_len, "rfir_decim_kernel<%d>", h->OUT);
@@ -371,16 +354,10 @@ comms_status_t comms_rfir_get_kernel(const comms_rfir_t* h, size_t n, char* name
 comms_status_t comms_rfir_set_timer(comms_rfir_t* h, comms_timer_t* t) {
     COMMS_ARG(h != nullptr, "handle is NULL");
     h->timer = t;
-    if (h->fir) return comms_fir_set_timer(h->fir, t);  // the series: the pair brackets its FIR launch
+    if (h->fir.get()) return comms_fir_set_timer(h->fir.get(), t);  // the series: the pair brackets its FIR launch
     return COMMS_OK;
 }
 
-comms_status_t comms_rfir_destroy(comms_rfir_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    (void)h->quiesce();
-    free_rfir(h);
-    return COMMS_OK;
-}
+comms_status_t comms_rfir_destroy(comms_rfir_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

@@ -196,9 +196,10 @@ struct comms_symsync : Handle {
     int RS = 4, NB = 1, HB = 0, TO = 0, WG = 256, U = 1, stride = 0;
     size_t lds = 0;
     unsigned max_grid = 1;
-    float* d_tab = nullptr;         // [L][RS]
+    DevBuf<float> d_tab;            // [L][RS]
     History hist;                   // last Q samples
 };
+static_assert(!std::is_copy_constructible_v<comms_symsync>, "a handle is never copied");
 
 namespace {
 
@@ -225,14 +226,6 @@ bool plan_tile(comms_symsync* h) {
             return true;
         }
     return false;
-}
-
-void free_symsync(comms_symsync* h) {
-    (void)use_device(h->device);
-    if (h->d_tab) (void)hipFree(h->d_tab);
-    h->hist.release();
-    h->fini();
-    delete h;
 }
 
 template <int U, int FMT>
@@ -284,7 +277,7 @@ comms_status_t comms_symsync_create(const float* taps, size_t n_taps, size_t pha
     COMMS_ARG(L <= SS_MAX_PHASES, "at most %zu phases (got %zu)", SS_MAX_PHASES, L);
     COMMS_ARG(S <= SS_MAX_SPS, "at most %zu samples per symbol (got %zu)", SS_MAX_SPS, S);
     COMMS_ARG(n_taps <= SS_MAX_ROW * L, "at most %zu taps per phase (%zu taps over %zu phases)", SS_MAX_ROW, n_taps, L);
-    comms_symsync* h = nullptr;
+    HandlePtr<comms_symsync> h;
     COMMS_TRY(make_handle(device, &h));
     h->n_taps = n_taps;
     h->L = L;
@@ -293,24 +286,17 @@ comms_status_t comms_symsync_create(const float* taps, size_t n_taps, size_t pha
     h->NB = static_cast<int>((h->Q + 1 + 3) / 4);
     h->RS = 4 * h->NB;
     h->HB = static_cast<int>((4 * h->NB - 1 + S - 1) / S);
-    if (!plan_tile(h)) {
-        free_symsync(h);
+    if (!plan_tile(h.get()))
         return fail(COMMS_ERR_DEVICE, "symsync: no tile fits (%zu phases, %zu samples per symbol, %zu taps)", L, S, n_taps);
-    }
     h->WG = h->TO >= 256 ? 256 : h->TO < 64 ? 64 : h->TO;
     h->U = h->TO >= 4 * h->WG ? 4 : h->TO >= 2 * h->WG ? 2 : 1;
     h->max_grid = resident_workgroups(h->lds);
     std::vector<float> tab(L * h->RS, 0.0f);
     for (size_t p = 0; p < L; ++p)
         for (size_t j = 0; p + L * j < n_taps; ++j) tab[p * h->RS + j] = taps[p + L * j];
-    hipError_t e = hipMalloc(&h->d_tab, tab.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = h->hist.alloc(h->Q, sizeof(comms_c32));
-    if (e != hipSuccess) {
-        free_symsync(h);
-        return fail(COMMS_ERR_DEVICE, "symsync alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->d_tab.upload(tab));
+    COMMS_HIP_TRY(h->hist.alloc(h->Q, sizeof(comms_c32)));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -384,7 +370,7 @@ comms_status_t comms_symsync_run_dev(comms_symsync_t* h, const comms_c32* d_in, 
     a.hist = h->hist.cur<float2>();
     a.new_hist = h->hist.next<float2>();
     a.out = d_out;
-    a.row = h->d_tab + static_cast<size_t>(h->mu % h->L) * h->RS;
+    a.row = h->d_tab.get() + static_cast<size_t>(h->mu % h->L) * h->RS;
     a.n = n;
     a.n_out = n_out;
     a.n_bytes = out_bytes;
@@ -468,12 +454,6 @@ comms_status_t comms_symsync_set_timer(comms_symsync_t* h, comms_timer_t* t) {
     return COMMS_OK;
 }
 
-comms_status_t comms_symsync_destroy(comms_symsync_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    (void)h->quiesce();
-    free_symsync(h);
-    return COMMS_OK;
-}
+comms_status_t comms_symsync_destroy(comms_symsync_t* h) { return destroy_handle(h); }
 
 }  // extern "C"

@@ -316,21 +316,13 @@ struct comms_syncest : Handle {
     int nk = 0;                   // taps staged (2 n d + 1 padded to a multiple of 12)
     size_t lds = 0;
     unsigned max_grid = 1;
-    float* d_taps = nullptr;      // nk
-    float2* d_rot = nullptr;      // 2 n
-    double* d_part = nullptr;     // [max_grid][4]
+    DevBuf<float> d_taps;   // nk
+    DevBuf<float2> d_rot;   // 2 n
+    DevBuf<double> d_part;  // [max_grid][4]
 };
+static_assert(!std::is_copy_constructible_v<comms_syncest>, "a handle is never copied");
 
 namespace {
-
-void free_syncest(comms_syncest* h) {
-    (void)use_device(h->device);
-    if (h->d_taps) (void)hipFree(h->d_taps);
-    if (h->d_rot) (void)hipFree(h->d_rot);
-    if (h->d_part) (void)hipFree(h->d_part);
-    h->fini();
-    delete h;
-}
 
 size_t syncest_grid(const comms_syncest* h, size_t len) {
     const size_t tiles = (len + SE_TILE - 1) / SE_TILE;
@@ -350,7 +342,7 @@ comms_status_t comms_syncest_create(uint32_t n, uint32_t d, double alpha, int32_
     const uint32_t n_q = 2 * n * d + 1;  // odd: qfilt_taps returns exactly n_q
     std::vector<double> t64(n_q);
     COMMS_TRY(comms_qfilt_taps(n_q, alpha, n, t64.data()));  // alpha outside [0, 1]: COMMS_ERR_ARG
-    comms_syncest* h = nullptr;
+    HandlePtr<comms_syncest> h;
     COMMS_TRY(make_handle(device, &h));
     h->n = n;
     h->d = d;
@@ -366,16 +358,10 @@ comms_status_t comms_syncest_create(uint32_t n, uint32_t d, double alpha, int32_
         const double th = (-kSePi * static_cast<double>(m)) / static_cast<double>(n);
         rot[m] = make_float2(static_cast<float>(std::cos(th)), static_cast<float>(std::sin(th)));
     }
-    hipError_t e = hipMalloc(&h->d_taps, taps.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&h->d_rot, rot.size() * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpy(h->d_rot, rot.data(), rot.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&h->d_part, static_cast<size_t>(h->max_grid) * 4 * sizeof(double));
-    if (e != hipSuccess) {
-        free_syncest(h);
-        return fail(COMMS_ERR_DEVICE, "sync estimator alloc: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    COMMS_HIP_TRY(h->d_taps.upload(taps));
+    COMMS_HIP_TRY(h->d_rot.upload(rot));
+    COMMS_HIP_TRY(h->d_part.alloc(static_cast<size_t>(h->max_grid) * 4));
+    *out = h.release();
     return COMMS_OK;
 }
 
@@ -393,18 +379,18 @@ comms_status_t comms_syncest_run_dev(comms_syncest_t* h, const comms_c32* d_in, 
         SeArgs a{};
         a.x = reinterpret_cast<const float2*>(d_in);
         a.len = len;
-        a.taps = h->d_taps;
-        a.rot = h->d_rot;
+        a.taps = h->d_taps.get();
+        a.rot = h->d_rot.get();
         a.nk = h->nk;
         a.nd = static_cast<int>(h->n * h->d);
         a.n2 = static_cast<int>(2 * h->n);
-        a.partials = h->d_part;
+        a.partials = h->d_part.get();
         h->tic(s);
         syncest_kernel<<<dim3(static_cast<unsigned>(grid)), dim3(SE_WG), h->lds, s>>>(a);
         h->toc(s);
         COMMS_TRY(launch_ok("syncest_kernel"));
         std::vector<double> part(grid * 4);
-        hipError_t e = hipMemcpyAsync(part.data(), h->d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+        hipError_t e = hipMemcpyAsync(part.data(), h->d_part.get(), part.size() * sizeof(double), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "sync estimator copy-back: %s", hipGetErrorString(e));
         for (size_t b = 0; b < grid; ++b)
@@ -443,13 +429,7 @@ comms_status_t comms_syncest_set_timer(comms_syncest_t* h, comms_timer_t* t) {
     return COMMS_OK;
 }
 
-comms_status_t comms_syncest_destroy(comms_syncest_t* h) {
-    if (!h) return COMMS_OK;
-    (void)use_device(h->device);
-    (void)h->quiesce();
-    free_syncest(h);
-    return COMMS_OK;
-}
+comms_status_t comms_syncest_destroy(comms_syncest_t* h) { return destroy_handle(h); }
 
 comms_status_t comms_psk_phase_estimate_c32_dev(const comms_c32* d_symbols, size_t n, uint32_t m, double* out, int32_t device,
                                                 void* stream) {
