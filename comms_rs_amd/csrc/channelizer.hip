@@ -314,12 +314,7 @@ void plan_tile(comms_channelizer* h) {
 
 template <bool STAGED, bool TAB_LDS>
 comms_status_t launch_channelizer(const ChzArgs& a, unsigned blocks, size_t lds, hipStream_t s) {
-    static DeviceOnce once;
-    if (once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&channelizer_kernel<STAGED, TAB_LDS>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(CHZ_LDS_MAX)));
-    channelizer_kernel<STAGED, TAB_LDS><<<dim3(blocks), dim3(256), lds, s>>>(a);
-    return launch_ok("channelizer_kernel");
+    return launch_kernel<channelizer_kernel<STAGED, TAB_LDS>>("channelizer_kernel", dim3(blocks), dim3(256), lds, s, {}, a);
 }
 
 size_t chz_frames(size_t n, size_t D) { return n / D + (n % D ? 1 : 0); }

@@ -1,6 +1,7 @@
 // common.hpp -- shared plumbing of libcomms_hip.so (gfx950 only; no CPU fallback).
 #pragma once
 
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -130,18 +131,54 @@ inline comms_status_t launch_ok(const char* what) {
     return COMMS_OK;
 }
 
-// hipFuncSetAttribute applies to the current device only: a `static DeviceOnce` per call site
-// remembers which devices have had it (a process may drive several GPUs through the C ABI).
-// Node threads of one process reach the same call site concurrently, hence atomics; two threads
-// racing on the first use both set the (idempotent) attribute, which is harmless.
-struct DeviceOnce {
-    std::atomic<bool> done[64] = {};
-    bool need() {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-        return !done[dev].exchange(true, std::memory_order_acq_rel);
-    }
+// The event pair of a timed launch (Handle::take_events): both events or neither.
+struct EventPair {
+    hipEvent_t start = nullptr, stop = nullptr;
 };
+
+// Dynamic LDS that `Kernel` may ask for, per device, in bytes: what launch_kernel has set
+// hipFuncAttributeMaxDynamicSharedMemorySize to there (0: never set).  The attribute applies to the current device only,
+// and a process may drive several GPUs through the C ABI.
+template <auto Kernel>
+struct LdsGranted {
+    static inline std::atomic<unsigned> bytes[64] = {};
+    static inline std::mutex grow;  // held while the limit is raised, never by a launch that fits
+};
+
+// The one way to launch a kernel: LDS opt-in, launch, check.
+//   launch_kernel<fir_decim_kernel<R, REAL, PRE, A>>("fir_decim_kernel", grid, block, lds, s, h->take_events(), args);
+// 1. A launch that asks for more dynamic LDS than the kernel has been granted on the current device raises the limit to
+//    what it asks for and remembers that; a failed hipFuncSetAttribute is not remembered.  Every other launch pays one
+//    hipGetDevice and one atomic load (nothing without dynamic LDS).  Node threads of one process reach the same kernel
+//    concurrently, hence the atomics; the limit is raised under the kernel's mutex, so that of two threads that first ask
+//    for different sizes the smaller one cannot be the last to set the attribute.
+// 2. With an event pair the launch is hipExtLaunchKernelGGL's: the pair takes the kernel's own begin / end timestamps (no
+//    dispatch gap), which is what rocprofv3 reports as its duration.  Without one it is a plain launch.
+// 3. launch_ok under `name`.
+// The arguments reach the launch expression by reference: no copy of a large argument block (PulseArgs, DecimArgs) is made
+// in front of the runtime's own.
+template <auto Kernel, class... Args>
+comms_status_t launch_kernel(const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t s, EventPair ev, const Args&... args) {
+    if (lds) {
+        using G = LdsGranted<Kernel>;
+        int dev = 0;
+        COMMS_HIP_TRY(hipGetDevice(&dev));
+        COMMS_ARG(dev >= 0 && dev < 64, "device index out of range");
+        if (lds > G::bytes[dev].load(std::memory_order_acquire)) {
+            std::lock_guard<std::mutex> lk(G::grow);
+            if (lds > G::bytes[dev].load(std::memory_order_relaxed)) {
+                COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  static_cast<int>(lds)));
+                G::bytes[dev].store(static_cast<unsigned>(lds), std::memory_order_release);
+            }
+        }
+    }
+    if (ev.start)
+        hipExtLaunchKernelGGL(Kernel, grid, block, static_cast<uint32_t>(lds), s, ev.start, ev.stop, 0u, args...);
+    else
+        Kernel<<<grid, block, lds, s>>>(args...);
+    return launch_ok(name);
+}
 
 // ---- owners of device and pinned memory -----------------------------------------------------------------------------
 // Every allocation of a handle is a member of one of these types (Scratch, Pinned, DevBuf, History): freed by its
@@ -451,18 +488,17 @@ struct Handle {
         }
         ++timer->seq;
     }
-    // For launches made with hipExtLaunchKernelGGL: the pair is updated with the kernel's own begin / end
-    // timestamps (no dispatch gap), which is what rocprofv3 reports as its duration.  False: launch plainly.
-    bool take_events(hipEvent_t& a, hipEvent_t& b) {
-        if (!has_events()) return false;
-        const bool on = timed();
-        ++timer->seq;
-        if (on) {
-            a = timer->start[timer->next % timer->n];
-            b = timer->stop[timer->next % timer->n];
+    // For launch_kernel's timed form: the pair that takes the kernel's own begin / end timestamps, or an empty one
+    // (launch plainly).
+    EventPair take_events() {
+        EventPair ev;
+        if (!has_events()) return ev;
+        if (timed()) {
+            ev = EventPair{timer->start[timer->next % timer->n], timer->stop[timer->next % timer->n]};
             ++timer->next;
         }
-        return on;
+        ++timer->seq;
+        return ev;
     }
     // In-kernel stamps: the slots of the launch about to be made, or a null KStamp when the attached timer has none
     // (left).  Only kernels that take a KStamp are timed this way.

@@ -1388,19 +1388,6 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
         COMMS_HIP_TRY(pl.d_fw2.alloc(t2.size()));
         COMMS_HIP_TRY(hipMemcpy(pl.d_fw1.get(), t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
         COMMS_HIP_TRY(hipMemcpy(pl.d_fw2.get(), t2.data(), t2.size() * sizeof(float2), hipMemcpyHostToDevice));
-        const int fw_lds = (1024 + 64 + 16 * FW_BUF + 256) * static_cast<int>(sizeof(float2));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft1024x16_kernel<1, 16>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, fw_lds));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft1024x16_kernel<-1, 16>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, fw_lds));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft1024x16_kernel<1, 16, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, fw_lds));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft1024x16_kernel<-1, 16, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, fw_lds));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft1024x16_kernel<1, 8>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, fw_lds));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft1024x16_kernel<-1, 8>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, fw_lds));
     }
     if (rx) {
         const int rad = N < 1024 ? 1 : static_cast<int>(N / 1024);  // (N = 64, 256: tables unused, kept for the common signature)
@@ -1470,18 +1457,7 @@ static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
             }
         COMMS_HIP_TRY(pl.d_rx32.alloc(t.size()));
         COMMS_HIP_TRY(hipMemcpy(pl.d_rx32.get(), t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rx32k_kernel<1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(R32_LDS)));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rx32k_kernel<-1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(R32_LDS)));
     }
-    // tiles above 64 KiB need the dynamic-LDS limit raised (160 KiB per CU on gfx950)
-    COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_tile_kernel<1>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      FT_MAX_POINTS * sizeof(float2)));
-    COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_tile_kernel<-1>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      FT_MAX_POINTS * sizeof(float2)));
     return COMMS_OK;
 }
 
@@ -1496,26 +1472,19 @@ static comms_status_t launch_fast(Pow2Plan& pl, const float2* src, float2* dst, 
     cf* d = reinterpret_cast<cf*>(dst);
     if (p.C == 16) {  // one 16-wave workgroup per CU
         const size_t lds = (1024 + 64 + 16 * FW_BUF + 256) * sizeof(float2);
-        const unsigned blocks = static_cast<unsigned>(p.n_tiles < static_cast<size_t>(kNumCU) ? p.n_tiles : kNumCU);
-        if (p.apply_tw && p.out_c_fast) {
-            if (inverse)
-                fft1024x16_kernel<1, 16, true><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, p, t1, t2);
-            else
-                fft1024x16_kernel<-1, 16, true><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, p, t1, t2);
-        } else if (inverse)
-            fft1024x16_kernel<1, 16><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, p, t1, t2);
-        else
-            fft1024x16_kernel<-1, 16><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, p, t1, t2);
-    } else {  // two 8-wave workgroups per CU: one loads/stores while the other computes
-        const size_t lds = (1024 + 64 + 8 * FW_BUF + 256) * sizeof(float2);
-        const size_t slots = 2 * static_cast<size_t>(kNumCU);
-        const unsigned blocks = static_cast<unsigned>(p.n_tiles < slots ? p.n_tiles : slots);
-        if (inverse)
-            fft1024x16_kernel<1, 8><<<dim3(blocks), dim3(512), lds, s>>>(a, d, p, t1, t2);
-        else
-            fft1024x16_kernel<-1, 8><<<dim3(blocks), dim3(512), lds, s>>>(a, d, p, t1, t2);
+        const dim3 grid(static_cast<unsigned>(p.n_tiles < static_cast<size_t>(kNumCU) ? p.n_tiles : kNumCU));
+        if (p.apply_tw && p.out_c_fast)
+            return inverse ? launch_kernel<fft1024x16_kernel<1, 16, true>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2)
+                           : launch_kernel<fft1024x16_kernel<-1, 16, true>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2);
+        return inverse ? launch_kernel<fft1024x16_kernel<1, 16>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2)
+                       : launch_kernel<fft1024x16_kernel<-1, 16>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2);
     }
-    return launch_ok("fft1024x16_kernel");
+    // two 8-wave workgroups per CU: one loads/stores while the other computes
+    const size_t lds = (1024 + 64 + 8 * FW_BUF + 256) * sizeof(float2);
+    const size_t slots = 2 * static_cast<size_t>(kNumCU);
+    const dim3 grid(static_cast<unsigned>(p.n_tiles < slots ? p.n_tiles : slots));
+    return inverse ? launch_kernel<fft1024x16_kernel<1, 8>>("fft1024x16_kernel", grid, dim3(512), lds, s, {}, a, d, p, t1, t2)
+                   : launch_kernel<fft1024x16_kernel<-1, 8>>("fft1024x16_kernel", grid, dim3(512), lds, s, {}, a, d, p, t1, t2);
 }
 
 template <int RAD>
@@ -1529,40 +1498,26 @@ static comms_status_t launch_rx(Pow2Plan& pl, const float2* src, float2* dst, si
     const cf* ta = reinterpret_cast<const cf*>(pl.d_rxa.get());
     const cf* tb = reinterpret_cast<const cf*>(pl.d_rxb.get());
     constexpr size_t lds = RxGeom<RAD>::LDS;
-    static DeviceOnce attr_once;
-    if (attr_once.need()) {
-#define COMMS_RX_ATTR(...)                                                                             \
-    COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rx1024_kernel<__VA_ARGS__>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)))
-        COMMS_RX_ATTR(1, RAD);
-        COMMS_RX_ATTR(-1, RAD);
-        COMMS_RX_ATTR(-1, RAD, 1);
-        COMMS_RX_ATTR(1, RAD, 2);
-        COMMS_RX_ATTR(1, RAD, 0, true);
-        COMMS_RX_ATTR(-1, RAD, 0, true);
-        COMMS_RX_ATTR(-1, RAD, 1, true);
-        COMMS_RX_ATTR(1, RAD, 2, true);
-#undef COMMS_RX_ATTR
-    }
     // full tiles on the persistent grid; a partly filled last tile as one more workgroup.  In the
     // Bluestein modes the two launches address in / out by the global element index, so the second
     // one simply starts at tile n_full.
-    auto go = [&](auto kern_full, auto kern_part) {
+    auto go = [&](auto dir, auto mode) -> comms_status_t {
+        constexpr int DIR = decltype(dir)::value, MODE = decltype(mode)::value;
         if (n_full) {
             const unsigned blocks = static_cast<unsigned>(n_full < static_cast<size_t>(kNumCU) ? n_full : kNumCU);
-            kern_full<<<dim3(blocks), dim3(1024), lds, s>>>(a, d, n_full, 0, n_full * 16384, t1, t2, ta, tb, blu);
+            COMMS_TRY((launch_kernel<fft_rx1024_kernel<DIR, RAD, MODE>>("fft_rx1024_kernel", dim3(blocks), dim3(1024), lds, s, {}, a, d, n_full, 0,
+                                                                        n_full * 16384, t1, t2, ta, tb, blu)));
         }
-        if (rem) kern_part<<<dim3(1), dim3(1024), lds, s>>>(a, d, n_full + 1, n_full, n_points, t1, t2, ta, tb, blu);
+        if (rem)
+            COMMS_TRY((launch_kernel<fft_rx1024_kernel<DIR, RAD, MODE, true>>("fft_rx1024_kernel", dim3(1), dim3(1024), lds, s, {}, a, d, n_full + 1,
+                                                                              n_full, n_points, t1, t2, ta, tb, blu)));
+        return COMMS_OK;
     };
-    if (blu.mode == 1)  // Bluestein, first half: always the forward transform
-        go(fft_rx1024_kernel<-1, RAD, 1>, fft_rx1024_kernel<-1, RAD, 1, true>);
-    else if (blu.mode == 2)  // second half: always the inverse
-        go(fft_rx1024_kernel<1, RAD, 2>, fft_rx1024_kernel<1, RAD, 2, true>);
-    else if (inverse)
-        go(fft_rx1024_kernel<1, RAD>, fft_rx1024_kernel<1, RAD, 0, true>);
-    else
-        go(fft_rx1024_kernel<-1, RAD>, fft_rx1024_kernel<-1, RAD, 0, true>);
-    return launch_ok("fft_rx1024_kernel");
+    using std::integral_constant;
+    if (blu.mode == 1) return go(integral_constant<int, -1>{}, integral_constant<int, 1>{});  // Bluestein, first half: always forward
+    if (blu.mode == 2) return go(integral_constant<int, 1>{}, integral_constant<int, 2>{});   // second half: always the inverse
+    if (inverse) return go(integral_constant<int, 1>{}, integral_constant<int, 0>{});
+    return go(integral_constant<int, -1>{}, integral_constant<int, 0>{});
 }
 
 // Column pass of N = 2^21 ... 2^24 (BluArgs mode 3) on the row plan's tables: `rows` is the plan of the N / 1024-point transforms.
@@ -1570,53 +1525,44 @@ template <int RAD>
 static comms_status_t launch_rx_cols(Pow2Plan& rows, const float2* src, float2* dst, size_t n_points, bool inverse, hipStream_t s,
                                      const cf* tw_lo, const cf* tw_hi) {
     constexpr size_t lds = rx_cols_lds(RAD);
-    static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rx1024_kernel<1, RAD, 3>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rx1024_kernel<-1, RAD, 3>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    }
     BluArgs blu{3, 0, 0, nullptr, nullptr, tw_lo, tw_hi};
     const size_t n_tiles = n_points / 16384;  // whole transforms of at least 2^21 points: no partial tile
-    const unsigned blocks = static_cast<unsigned>(n_tiles < static_cast<size_t>(kNumCU) ? n_tiles : kNumCU);
+    const dim3 grid(static_cast<unsigned>(n_tiles < static_cast<size_t>(kNumCU) ? n_tiles : kNumCU));
     const cf* a = reinterpret_cast<const cf*>(src);
     cf* d = reinterpret_cast<cf*>(dst);
     const cf* t1 = reinterpret_cast<const cf*>(rows.d_fw1.get());
     const cf* t2 = reinterpret_cast<const cf*>(rows.d_fw2.get());
     const cf* ta = reinterpret_cast<const cf*>(rows.d_rxa.get());
     const cf* tb = reinterpret_cast<const cf*>(rows.d_rxb.get());
-    if (inverse)
-        fft_rx1024_kernel<1, RAD, 3><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, n_tiles, 0, n_points, t1, t2, ta, tb, blu);
-    else
-        fft_rx1024_kernel<-1, RAD, 3><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, n_tiles, 0, n_points, t1, t2, ta, tb, blu);
-    return launch_ok("fft_rx1024_kernel (columns)");
+    const char* name = "fft_rx1024_kernel (columns)";
+    return inverse ? launch_kernel<fft_rx1024_kernel<1, RAD, 3>>(name, grid, dim3(1024), lds, s, {}, a, d, n_tiles, 0, n_points, t1, t2, ta, tb, blu)
+                   : launch_kernel<fft_rx1024_kernel<-1, RAD, 3>>(name, grid, dim3(1024), lds, s, {}, a, d, n_tiles, 0, n_points, t1, t2, ta, tb, blu);
 }
 
 template <int KIND>
 static comms_status_t launch_cols(Pow2Plan& pl, const float2* src, float2* dst, size_t batch, bool inverse,
                                   hipStream_t s) {
     constexpr size_t lds = ColGeom<KIND>::LDS;
-    static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_cols_kernel<1, KIND>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_cols_kernel<-1, KIND>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    }
     const size_t n_tiles = batch * (1024 / ColGeom<KIND>::C);
-    const unsigned blocks = static_cast<unsigned>(n_tiles < static_cast<size_t>(kNumCU) ? n_tiles : kNumCU);
+    const dim3 grid(static_cast<unsigned>(n_tiles < static_cast<size_t>(kNumCU) ? n_tiles : kNumCU));
     const cf* a = reinterpret_cast<const cf*>(src);
     cf* d = reinterpret_cast<cf*>(dst);
     const cf* t1 = reinterpret_cast<const cf*>(pl.d_colw1.get());
     const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
     const cf* tr = reinterpret_cast<const cf*>(pl.d_colr.get());
     const FftTileParams& p = pl.pass[0];
-    if (inverse)
-        fft_cols_kernel<1, KIND><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, n_tiles, static_cast<unsigned>(pl.N), t1, t2, tr, p.tw_lo, p.tw_hi, p.ks);
-    else
-        fft_cols_kernel<-1, KIND><<<dim3(blocks), dim3(1024), lds, s>>>(a, d, n_tiles, static_cast<unsigned>(pl.N), t1, t2, tr, p.tw_lo, p.tw_hi, p.ks);
-    return launch_ok("fft_cols_kernel");
+    const unsigned N = static_cast<unsigned>(pl.N);
+    return inverse ? launch_kernel<fft_cols_kernel<1, KIND>>("fft_cols_kernel", grid, dim3(1024), lds, s, {}, a, d, n_tiles, N, t1, t2, tr, p.tw_lo, p.tw_hi, p.ks)
+                   : launch_kernel<fft_cols_kernel<-1, KIND>>("fft_cols_kernel", grid, dim3(1024), lds, s, {}, a, d, n_tiles, N, t1, t2, tr, p.tw_lo, p.tw_hi, p.ks);
+}
+
+// The generic tile kernel (tiles above 64 KiB need the dynamic-LDS limit raised: 160 KiB per CU on gfx950)
+static comms_status_t launch_tile(bool inverse, unsigned blocks, int threads, size_t lds, hipStream_t s, const float2* src, float2* dst,
+                                  const FftTileParams& p) {
+    const cf* a = reinterpret_cast<const cf*>(src);
+    cf* d = reinterpret_cast<cf*>(dst);
+    return inverse ? launch_kernel<fft_tile_kernel<1>>("fft_tile_kernel", dim3(blocks), dim3(threads), lds, s, {}, a, d, p)
+                   : launch_kernel<fft_tile_kernel<-1>>("fft_tile_kernel", dim3(blocks), dim3(threads), lds, s, {}, a, d, p);
 }
 
 // All of a batch on the single-pass kernel (plain, or as one half of a Bluestein pair).
@@ -1650,15 +1596,14 @@ static comms_status_t pow2_run(Pow2Plan& pl, const float2* in, float2* out, size
     if (pl.rx_rad && !no_rx) return run_rx(pl, in, out, batch * pl.N, inverse, s);
     static const bool no_rx32k = diag_knob("COMMS_FFT_NO_RX32K", 0) != 0;
     if (pl.d_rx32 && !no_rx32k) {  // N = 32768: one pass, a transform per workgroup and step
-        const unsigned blocks = static_cast<unsigned>(batch < static_cast<size_t>(kNumCU) ? batch : kNumCU);
+        const dim3 grid(static_cast<unsigned>(batch < static_cast<size_t>(kNumCU) ? batch : kNumCU));
+        const cf* a = reinterpret_cast<const cf*>(in);
+        cf* d = reinterpret_cast<cf*>(out);
         const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1.get());
         const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
         const cf* tt = reinterpret_cast<const cf*>(pl.d_rx32.get());
-        if (inverse)
-            fft_rx32k_kernel<1><<<dim3(blocks), dim3(1024), R32_LDS, s>>>(reinterpret_cast<const cf*>(in), reinterpret_cast<cf*>(out), batch, t1, t2, tt, ks);
-        else
-            fft_rx32k_kernel<-1><<<dim3(blocks), dim3(1024), R32_LDS, s>>>(reinterpret_cast<const cf*>(in), reinterpret_cast<cf*>(out), batch, t1, t2, tt, ks);
-        return launch_ok("fft_rx32k_kernel");
+        return inverse ? launch_kernel<fft_rx32k_kernel<1>>("fft_rx32k_kernel", grid, dim3(1024), R32_LDS, s, {}, a, d, batch, t1, t2, tt, ks)
+                       : launch_kernel<fft_rx32k_kernel<-1>>("fft_rx32k_kernel", grid, dim3(1024), R32_LDS, s, {}, a, d, batch, t1, t2, tt, ks);
     }
     if (pl.rows) {
         // N = 2^21 ... 2^24 in two passes: N / 1024-point columns gathered in pieces of 64 ... 8 B (small pieces cost far less
@@ -1705,11 +1650,7 @@ static comms_status_t pow2_run(Pow2Plan& pl, const float2* in, float2* out, size
             } else if (full) {
                 static const unsigned wgs = static_cast<unsigned>(diag_knob("COMMS_FFT_TILE_WGS", 4));
                 unsigned blocks = static_cast<unsigned>(full < wgs * kNumCU ? full : wgs * kNumCU);
-                if (inverse)
-                    fft_tile_kernel<1><<<dim3(blocks), dim3(pl.threads[i]), pl.lds[i], s>>>(reinterpret_cast<const cf*>(src), reinterpret_cast<cf*>(dst), p);
-                else
-                    fft_tile_kernel<-1><<<dim3(blocks), dim3(pl.threads[i]), pl.lds[i], s>>>(reinterpret_cast<const cf*>(src), reinterpret_cast<cf*>(dst), p);
-                COMMS_TRY(launch_ok("fft_tile_kernel"));
+                COMMS_TRY(launch_tile(inverse, blocks, pl.threads[i], pl.lds[i], s, src, dst, p));
             }
             const size_t rem = batch - full * p.C;
             if (rem) {
@@ -1722,11 +1663,7 @@ static comms_status_t pow2_run(Pow2Plan& pl, const float2* in, float2* out, size
                 int T = static_cast<int>(pl.N) / FT_PTS;
                 if (T < 64) T = 64;
                 unsigned blocks = static_cast<unsigned>(rem < 4u * kNumCU ? rem : 4u * kNumCU);
-                if (inverse)
-                    fft_tile_kernel<1><<<dim3(blocks), dim3(T), pl.N * sizeof(float2), s>>>(reinterpret_cast<const cf*>(src + off), reinterpret_cast<cf*>(dst + off), q);
-                else
-                    fft_tile_kernel<-1><<<dim3(blocks), dim3(T), pl.N * sizeof(float2), s>>>(reinterpret_cast<const cf*>(src + off), reinterpret_cast<cf*>(dst + off), q);
-                COMMS_TRY(launch_ok("fft_tile_kernel"));
+                COMMS_TRY(launch_tile(inverse, blocks, T, pl.N * sizeof(float2), s, src + off, dst + off, q));
             }
         } else {
             // pass 1: in -> scratch (same positions, twiddled); pass 2: scratch -> out
@@ -1752,11 +1689,7 @@ static comms_status_t pow2_run(Pow2Plan& pl, const float2* in, float2* out, size
                 continue;
             }
             unsigned blocks = static_cast<unsigned>(p.n_tiles < 4u * kNumCU ? p.n_tiles : 4u * kNumCU);
-            if (inverse)
-                fft_tile_kernel<1><<<dim3(blocks), dim3(pl.threads[i]), pl.lds[i], s>>>(reinterpret_cast<const cf*>(src), reinterpret_cast<cf*>(dst), p);
-            else
-                fft_tile_kernel<-1><<<dim3(blocks), dim3(pl.threads[i]), pl.lds[i], s>>>(reinterpret_cast<const cf*>(src), reinterpret_cast<cf*>(dst), p);
-            COMMS_TRY(launch_ok("fft_tile_kernel"));
+            COMMS_TRY(launch_tile(inverse, blocks, pl.threads[i], pl.lds[i], s, src, dst, p));
         }
     }
     return COMMS_OK;

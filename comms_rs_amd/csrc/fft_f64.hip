@@ -166,12 +166,8 @@ double2 rootl(unsigned long long e, unsigned long long denom) {  // e^{-2 pi i e
 }
 
 comms_status_t lds_pass(const F64Pass& p, unsigned ny, hipStream_t s) {
-    static DeviceOnce attr_once;
-    if (attr_once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_f64_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          static_cast<int>(F64_LDS_POINTS * sizeof(double2))));
-    fft_f64_lds_kernel<<<dim3((p.T + p.B - 1) / p.B, ny), dim3(256), static_cast<size_t>(p.B) * p.N * sizeof(double2), s>>>(p);
-    return launch_ok("fft_f64_lds_kernel");
+    return launch_kernel<fft_f64_lds_kernel>("fft_f64_lds_kernel", dim3((p.T + p.B - 1) / p.B, ny), dim3(256),
+                                             static_cast<size_t>(p.B) * p.N * sizeof(double2), s, {}, p);
 }
 
 // `batch` transforms of P = 2^logP points, back to back in `in`, to `out` (may be `in`); `inverse` overrides the handle's
@@ -305,15 +301,11 @@ comms_status_t comms_fft_f64_run_dev(comms_fft_f64_t* h, const comms_c64* d_in, 
         COMMS_TRY(pow2_run(h, in, o, batch, h->inverse, s));
     } else if (h->kind == 2) {
         const unsigned N = static_cast<unsigned>(h->N);
-        static DeviceOnce attr_once;
-        if (attr_once.need())
-            COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&dft_f64_direct_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              static_cast<int>(F64_LDS_POINTS * sizeof(double2))));
         for (size_t b0 = 0; b0 < batch; b0 += 32768) {
             const unsigned nb = static_cast<unsigned>(batch - b0 < 32768 ? batch - b0 : 32768);
-            dft_f64_direct_kernel<<<dim3((N + 255) / 256, nb), dim3(256), static_cast<size_t>(N) * sizeof(double2), s>>>(
-                in + b0 * N, o + b0 * N, N, h->d_roots.get(), h->inverse ? 1 : 0);
-            COMMS_TRY(launch_ok("dft_f64_direct_kernel"));
+            COMMS_TRY(launch_kernel<dft_f64_direct_kernel>("dft_f64_direct_kernel", dim3((N + 255) / 256, nb), dim3(256),
+                                                           static_cast<size_t>(N) * sizeof(double2), s, {}, in + b0 * N, o + b0 * N, N,
+                                                           h->d_roots.get(), h->inverse ? 1 : 0));
         }
     } else {
         COMMS_TRY(h->s2.reserve(h->P * sizeof(double2)));

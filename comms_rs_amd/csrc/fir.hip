@@ -26,7 +26,6 @@
 #include <utility>
 #include <vector>
 
-#include <hip/hip_ext.h>
 
 #include <atomic>
 #include <cstdio>
@@ -1335,30 +1334,15 @@ using namespace comms;
 template <int MODE, int HR = 4, class In = const float2*>
 static comms_status_t launch_os1024(int wpb, size_t runs, hipStream_t s, In in, const float2* hist,
                                     int n_eff, float2* o, size_t n, size_t nseg, const comms::WTables& tb,
-                                    float2* nh, const comms::ChainArgs& ch, hipEvent_t ev_start = nullptr,
-                                    hipEvent_t ev_stop = nullptr) {
+                                    float2* nh, const comms::ChainArgs& ch, EventPair ev = {}) {
     using namespace comms;
-    if (wpb == 16) {
-        const size_t lds = (2112 + 16 * W_LDS) * sizeof(float2);
-        static DeviceOnce attr_once;
-        if (attr_once.need()) {
-            COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_os1024_kernel<16, 4, MODE, HR, In>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        }
-        if (ev_start) {  // timed launch: the events take the kernel's own begin / end timestamps
-            hipExtLaunchKernelGGL((fir_os1024_kernel<16, 4, MODE, HR, In>), dim3(static_cast<unsigned>((runs + 15) / 16)),
-                                  dim3(1024), static_cast<uint32_t>(lds), s, ev_start, ev_stop, 0u, in, hist, n_eff, o, n,
-                                  nseg, runs, tb, nh, ch);
-            return COMMS_OK;
-        }
-        fir_os1024_kernel<16, 4, MODE, HR, In><<<dim3(static_cast<unsigned>((runs + 15) / 16)), dim3(1024), lds, s>>>(
+    if (wpb == 16)
+        return launch_kernel<fir_os1024_kernel<16, 4, MODE, HR, In>>(
+            "fir_os1024_kernel", dim3(static_cast<unsigned>((runs + 15) / 16)), dim3(1024), (2112 + 16 * W_LDS) * sizeof(float2), s, ev,
             in, hist, n_eff, o, n, nseg, runs, tb, nh, ch);
-    } else {
-        const size_t lds = (2112 + 4 * W_LDS) * sizeof(float2);
-        fir_os1024_kernel<4, 3, MODE, HR, In><<<dim3(static_cast<unsigned>((runs + 3) / 4)), dim3(256), lds, s>>>(
-            in, hist, n_eff, o, n, nseg, runs, tb, nh, ch);
-    }
-    return COMMS_OK;
+    return launch_kernel<fir_os1024_kernel<4, 3, MODE, HR, In>>(
+        "fir_os1024_kernel", dim3(static_cast<unsigned>((runs + 3) / 4)), dim3(256), (2112 + 4 * W_LDS) * sizeof(float2), s, {},
+        in, hist, n_eff, o, n, nseg, runs, tb, nh, ch);
 }
 static size_t os1024_runs(int wpb, size_t nseg, size_t min_run) {
     // persistent: every wave slot of the chip gets one run (fewer for short inputs, where a
@@ -1410,25 +1394,15 @@ extern "C" void comms_debug_os1024_chunk_log2(int k) { g_os1024_chunk.store(k, s
 template <int HR, bool TRACE = false, class In = const float2*>
 static comms_status_t launch_os1024_dyn(hipStream_t s, In in, const float2* hist, int n_eff, float2* o,
                                         size_t n, const comms::WTables& tb, float2* nh, void* trace_buf = nullptr,
-                                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                                        KStamp ks = KStamp{nullptr, nullptr}) {
+                                        EventPair ev = {}, KStamp ks = KStamp{nullptr, nullptr}) {
     using namespace comms;
     const size_t lds = (2112 + 16 * W_LDS + 1) * sizeof(float2);  // tables, exchange buffers, ticket counter
-    static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_os1024_dyn_kernel<HR, TRACE, In>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    }
     const size_t nseg = (n + (1024 - 64 * HR) - 1) / (1024 - 64 * HR);
     const size_t want = (nseg + 15) / 16;
     const dim3 grid(static_cast<unsigned>(want < static_cast<size_t>(kNumCU) ? want : kNumCU));
     const unsigned chunk_log2 = os1024_chunk_log2(nseg, grid.x);
-    if (ev_start)  // timed launch: the events take the kernel's own begin / end timestamps
-        hipExtLaunchKernelGGL((fir_os1024_dyn_kernel<HR, TRACE, In>), grid, dim3(1024), static_cast<uint32_t>(lds), s, ev_start,
-                              ev_stop, 0u, in, hist, n_eff, o, n, tb, nh, trace_buf, chunk_log2, ks);
-    else
-        fir_os1024_dyn_kernel<HR, TRACE, In><<<grid, dim3(1024), lds, s>>>(in, hist, n_eff, o, n, tb, nh, trace_buf, chunk_log2, ks);
-    return COMMS_OK;
+    return launch_kernel<fir_os1024_dyn_kernel<HR, TRACE, In>>("fir_os1024_dyn_kernel", grid, dim3(1024), lds, s, ev, in, hist, n_eff, o, n,
+                                                               tb, nh, trace_buf, chunk_log2, ks);
 }
 
 static const double kPi = 3.14159265358979323846264338327950288;
@@ -1603,15 +1577,6 @@ static comms_status_t fir_prepare_os16k(comms_fir* h) {
         h->d_xh.emplace_back();
         COMMS_HIP_TRY(h->d_xh.back().upload(hdev));
     }
-    const int lds = static_cast<int>(X_LDS_BYTES);
-#define COMMS_X_ATTR(HRV, INV) \
-    COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_os16k_kernel<HRV, INV>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-#define COMMS_X_ATTR4(INV) COMMS_X_ATTR(1, INV); COMMS_X_ATTR(2, INV); COMMS_X_ATTR(3, INV); COMMS_X_ATTR(4, INV)
-    COMMS_X_ATTR4(const float2*);
-    COMMS_X_ATTR4(InI16);
-    COMMS_X_ATTR4(InU8);
-#undef COMMS_X_ATTR4
-#undef COMMS_X_ATTR
     h->x_ready = true;
     return COMMS_OK;
 }
@@ -1750,30 +1715,16 @@ comms_status_t comms_fir_get_algo(const comms_fir_t* h, size_t n, int32_t* out_a
 
 }  // extern "C"
 
-template <int HR, class In>
-static comms_status_t launch_dyn_in(hipStream_t s, In in, comms_fir* h, float2* o, size_t n, const WTables& tb, float2* nh,
-                                    hipEvent_t ea, hipEvent_t eb, KStamp ks) {
-    return launch_os1024_dyn<HR, false, In>(s, in, h->hist.cur<float2>(), h->n_eff, o, n, tb, nh, nullptr, ea, eb, ks);
-}
-template <class In>
-static comms_status_t launch_dyn_hr(int hr, hipStream_t s, In in, comms_fir* h, float2* o, size_t n, const WTables& tb,
-                                    float2* nh, hipEvent_t ea, hipEvent_t eb, KStamp ks) {
-    switch (hr) {
-        case 1: return launch_dyn_in<1>(s, in, h, o, n, tb, nh, ea, eb, ks);
-        case 2: return launch_dyn_in<2>(s, in, h, o, n, tb, nh, ea, eb, ks);
-        case 3: return launch_dyn_in<3>(s, in, h, o, n, tb, nh, ea, eb, ks);
-        default: return launch_dyn_in<4>(s, in, h, o, n, tb, nh, ea, eb, ks);
+// f(std::integral_constant<int, hr>) for the halo rows LO ... 4 of a call (the one ladder from the run-time count to the
+// kernels' template parameter; anything above 3 is 4)
+template <int LO = 1, class F>
+static auto with_halo_rows(int hr, F&& f) {
+    if constexpr (LO <= 1) {
+        if (hr == 1) return f(std::integral_constant<int, 1>{});
     }
-}
-template <class In>
-static comms_status_t launch_fixed_hr(int hr, int wpb, size_t runs, hipStream_t s, In in, const float2* hist, int n_eff, float2* o,
-                                      size_t n, size_t nseg, const WTables& tb, float2* nh, hipEvent_t ea, hipEvent_t eb) {
-    switch (hr) {
-        case 1: return launch_os1024<0, 1, In>(wpb, runs, s, in, hist, n_eff, o, n, nseg, tb, nh, ChainArgs{}, ea, eb);
-        case 2: return launch_os1024<0, 2, In>(wpb, runs, s, in, hist, n_eff, o, n, nseg, tb, nh, ChainArgs{}, ea, eb);
-        case 3: return launch_os1024<0, 3, In>(wpb, runs, s, in, hist, n_eff, o, n, nseg, tb, nh, ChainArgs{}, ea, eb);
-        default: return launch_os1024<0, 4, In>(wpb, runs, s, in, hist, n_eff, o, n, nseg, tb, nh, ChainArgs{}, ea, eb);
-    }
+    if (hr == 2) return f(std::integral_constant<int, 2>{});
+    if (hr == 3) return f(std::integral_constant<int, 3>{});
+    return f(std::integral_constant<int, 4>{});
 }
 // diagnostic build: comms_debug_os16k_fault(1) makes the next 16384-point launches withhold one LDS signal
 static std::atomic<int> g_os16k_fault{0};
@@ -1788,17 +1739,6 @@ extern "C" unsigned comms_debug_os16k_trace(void* buf) {
     return X_TRACE_SEGS;
 }
 #endif
-template <class In>
-static void launch_os16k_hr(int hr, unsigned blocks, size_t lds, hipStream_t s, In in, const float2* hist, int n_eff, float2* o, size_t n,
-                            size_t nseg, const XTables& tb, float2* nh, int dl, int acc, KStamp ks, unsigned* err) {
-    const int fault = os16k_fault();
-    switch (hr) {
-        case 1: fir_os16k_kernel<1, In><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, n_eff, o, n, nseg, tb, nh, dl, acc, ks, err, fault); break;
-        case 2: fir_os16k_kernel<2, In><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, n_eff, o, n, nseg, tb, nh, dl, acc, ks, err, fault); break;
-        case 3: fir_os16k_kernel<3, In><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, n_eff, o, n, nseg, tb, nh, dl, acc, ks, err, fault); break;
-        default: fir_os16k_kernel<4, In><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, n_eff, o, n, nseg, tb, nh, dl, acc, ks, err, fault); break;
-    }
-}
 template <class In>
 static void launch_direct_in(comms_fir* h, In in, const float2* hist, float2* o, size_t n, float2* nh, unsigned blocks,
                              size_t lds, hipStream_t s) {
@@ -1845,19 +1785,21 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
         const size_t nseg = pl.nseg;
         const size_t runs = os1024_runs(pl.wpb, nseg, pl.min_run);
         WTables tb{reinterpret_cast<const cf*>(h->d_wtw1.get()), reinterpret_cast<const cf*>(h->d_wtw2.get()), reinterpret_cast<const cf*>(h->d_whdev.get())};
-        hipEvent_t ea = nullptr, eb = nullptr;
+        EventPair ev;
         const bool own_stamps = pl.wpb == 16;  // (16-wave launches report the kernel's own begin / end through the pair)
         if (own_stamps)
-            (void)h->take_events(ea, eb);
+            ev = h->take_events();
         else
             h->tic(s);
         const KStamp ks = pl.dyn ? h->next_stamp() : KStamp{nullptr, nullptr};
         COMMS_TRY(with_input_view(h, d_in, in, [&](auto v) {
-            return pl.dyn ? launch_dyn_hr(pl.hr, s, v, h, o, n, tb, nh, ea, eb, ks)
-                          : launch_fixed_hr(pl.hr, pl.wpb, runs, s, v, hist, h->n_eff, o, n, nseg, tb, nh, ea, eb);
+            return with_halo_rows(pl.hr, [&](auto hr) {
+                using In = decltype(v);
+                return pl.dyn ? launch_os1024_dyn<hr(), false, In>(s, v, hist, h->n_eff, o, n, tb, nh, nullptr, ev, ks)
+                              : launch_os1024<0, hr(), In>(pl.wpb, runs, s, v, hist, h->n_eff, o, n, nseg, tb, nh, ChainArgs{}, ev);
+            });
         }));
         if (!own_stamps) h->toc(s);
-        COMMS_TRY(launch_ok("fir_os1024_kernel"));
     } else if (algo == COMMS_FIR_OS16K) {
         COMMS_TRY(fir_prepare_os16k(h));
         // halo rows: what the taps need (one pass), the full four for the 4097-tap partitions of longer filters
@@ -1868,15 +1810,20 @@ comms_status_t comms_fir_run_dev(comms_fir_t* h, const comms_c32* d_in_any, size
         const size_t lds = X_LDS_BYTES;
         h->tic(s);
         const KStamp ks = h->next_stamp();  // (the passes of a partitioned filter stamp the same slots: the whole call)
+        const int fault = os16k_fault();
         for (int pt = 0; pt < h->x_part; ++pt) {
             XTables tb{reinterpret_cast<const cf*>(h->d_xt[0].get()), reinterpret_cast<const cf*>(h->d_xt[1].get()),
                        reinterpret_cast<const cf*>(h->d_xt[2].get()), reinterpret_cast<const cf*>(h->d_xt[3].get()),
                        reinterpret_cast<const cf*>(h->d_xh[pt].get())};
             const int dl = pt * X_PART, acc = pt ? 1 : 0;
-            with_input_view(h, d_in, in, [&](auto v) { launch_os16k_hr(hr, blocks, lds, s, v, hist, h->n_eff, o, n, nseg, tb, nh, dl, acc, ks, h->d_err()); });
+            COMMS_TRY(with_input_view(h, d_in, in, [&](auto v) {
+                return with_halo_rows(hr, [&](auto hrc) {
+                    return launch_kernel<fir_os16k_kernel<hrc(), decltype(v)>>("fir_os16k_kernel", dim3(blocks), dim3(1024), lds, s, {}, v, hist,
+                                                                               h->n_eff, o, n, nseg, tb, nh, dl, acc, ks, h->d_err(), fault, OsNoDec{});
+                });
+            }));
         }
         h->toc(s);
-        COMMS_TRY(launch_ok("fir_os16k_kernel"));
     } else {
         COMMS_TRY(fir_prepare_os(h));
         const size_t V = OSF - 256 * static_cast<size_t>(h->hblk);
@@ -2018,7 +1965,6 @@ comms_status_t comms_fir_run_fused_dev(comms_fir_t* h, const comms_c32* d_in, si
             return fail(COMMS_ERR_ARG, "unsupported fused mode %d", mode);
     }
     h->toc(s);
-    COMMS_TRY(launch_ok("fir_os1024_kernel (fused)"));
     h->hist.flip();
     return COMMS_OK;
 }
@@ -2073,22 +2019,14 @@ comms_status_t comms_fir_run_os16k_decim_dev(comms_fir_t* h, const comms_c32* d_
     XTables tb{reinterpret_cast<const cf*>(h->d_xt[0].get()), reinterpret_cast<const cf*>(h->d_xt[1].get()), reinterpret_cast<const cf*>(h->d_xt[2].get()),
                reinterpret_cast<const cf*>(h->d_xt[3].get()), reinterpret_cast<const cf*>(h->d_xh[0].get())};
     const size_t lds = X_LDS_BYTES;
-    static DeviceOnce attr_once;
-    if (attr_once.need()) {
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_os16k_kernel<2, const float2*, true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_os16k_kernel<3, const float2*, true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_os16k_kernel<4, const float2*, true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    }
     h->tic(s);
     const KStamp ks = h->next_stamp();
     const int fault = os16k_fault();
-    switch (hr) {
-        case 2: fir_os16k_kernel<2, const float2*, true><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err(), fault, dc); break;
-        case 3: fir_os16k_kernel<3, const float2*, true><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err(), fault, dc); break;
-        default: fir_os16k_kernel<4, const float2*, true><<<dim3(blocks), dim3(1024), lds, s>>>(in, hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err(), fault, dc); break;
-    }
+    COMMS_TRY(with_halo_rows<2>(hr, [&](auto hrc) {
+        return launch_kernel<fir_os16k_kernel<hrc(), const float2*, true>>("fir_os16k_kernel (decimating)", dim3(blocks), dim3(1024), lds, s, {}, in,
+                                                                         hist, h->n_eff, o, n, nseg, tb, nh, 0, 0, ks, h->d_err(), fault, dc);
+    }));
     h->toc(s);
-    COMMS_TRY(launch_ok("fir_os16k_kernel (decimating)"));
     h->hist.flip();
     return COMMS_OK;
 }
@@ -2174,9 +2112,9 @@ static auto with_pulse_input(const comms_pulse* h, const void* d_sym, F&& f) {
     return f(static_cast<const float2*>(d_sym));
 }
 
-// Launches pulse_poly_kernel if (sps, taps) fit it; false -> the caller runs the generic kernel.
+// Launches pulse_poly_kernel if (sps, taps) fit it (*st: how the launch went); false -> the caller runs the generic kernel.
 template <int SPS, class In>
-static bool pulse_poly_try(comms_pulse* h, In sym, size_t n_sym, float2* out, hipStream_t s) {
+static bool pulse_poly_try(comms_pulse* h, In sym, size_t n_sym, float2* out, hipStream_t s, comms_status_t* st) {
     constexpr int SPSP = SPS + (SPS & 1);
     int J = (h->n_taps + SPS - 1) / SPS;
     J = (J + comms::PP_JB - 1) / comms::PP_JB * comms::PP_JB;
@@ -2214,22 +2152,14 @@ static bool pulse_poly_try(comms_pulse* h, In sym, size_t n_sym, float2* out, hi
     }
     // with a kernel timer attached: the kernel's own begin / end timestamps (events recorded around a launch of config 1's
     // size -- 5 us -- would mostly time the dispatch gap)
-    hipEvent_t ea = nullptr, eb = nullptr;
-    (void)h->take_events(ea, eb);
+    const EventPair ev = h->take_events();
     a.ks = h->next_stamp();
-#define COMMS_PULSE_GO(REAL, MIX)                                                                                            \
-    do {                                                                                                                     \
-        if constexpr (std::is_same<In, const float2*>::value) {                                                              \
-            if (ea)                                                                                                          \
-                hipExtLaunchKernelGGL((comms::pulse_poly_kernel<SPS, REAL, MIX>), dim3(blocks), dim3(256), 0u, s, ea, eb, 0u, a); \
-            else                                                                                                             \
-                comms::pulse_poly_kernel<SPS, REAL, MIX><<<dim3(blocks), dim3(256), 0, s>>>(a);                              \
-        } else {                                                                                                             \
-            if (ea)                                                                                                          \
-                hipExtLaunchKernelGGL((comms::pulse_poly_in_kernel<SPS, REAL, MIX, In>), dim3(blocks), dim3(256), 0u, s, ea, eb, 0u, a, sym); \
-            else                                                                                                             \
-                comms::pulse_poly_in_kernel<SPS, REAL, MIX, In><<<dim3(blocks), dim3(256), 0, s>>>(a, sym);                  \
-        }                                                                                                                    \
+#define COMMS_PULSE_GO(REAL, MIX)                                                                                              \
+    do {                                                                                                                       \
+        if constexpr (std::is_same<In, const float2*>::value)                                                                  \
+            *st = launch_kernel<comms::pulse_poly_kernel<SPS, REAL, MIX>>("pulse_poly_kernel", dim3(blocks), dim3(256), 0, s, ev, a); \
+        else                                                                                                                   \
+            *st = launch_kernel<comms::pulse_poly_in_kernel<SPS, REAL, MIX, In>>("pulse_poly_in_kernel", dim3(blocks), dim3(256), 0, s, ev, a, sym); \
     } while (0)
     if (h->mix) {
         if (h->real_taps) COMMS_PULSE_GO(true, true); else COMMS_PULSE_GO(false, true);
@@ -2240,21 +2170,21 @@ static bool pulse_poly_try(comms_pulse* h, In sym, size_t n_sym, float2* out, hi
     return true;
 }
 template <class In>
-static bool pulse_poly_launch(comms_pulse* h, In sym, size_t n_sym, float2* out, hipStream_t s) {
+static bool pulse_poly_launch(comms_pulse* h, In sym, size_t n_sym, float2* out, hipStream_t s, comms_status_t* st) {
     static const bool off = diag_knob("COMMS_PULSE_GENERIC", 0) != 0;
     if (off) return false;
     switch (h->sps) {
-        case 2: return pulse_poly_try<2>(h, sym, n_sym, out, s);
-        case 3: return pulse_poly_try<3>(h, sym, n_sym, out, s);
-        case 4: return pulse_poly_try<4>(h, sym, n_sym, out, s);
-        case 5: return pulse_poly_try<5>(h, sym, n_sym, out, s);
-        case 6: return pulse_poly_try<6>(h, sym, n_sym, out, s);
-        case 8: return pulse_poly_try<8>(h, sym, n_sym, out, s);
-        case 10: return pulse_poly_try<10>(h, sym, n_sym, out, s);
-        case 12: return pulse_poly_try<12>(h, sym, n_sym, out, s);
-        case 16: return pulse_poly_try<16>(h, sym, n_sym, out, s);
-        case 20: return pulse_poly_try<20>(h, sym, n_sym, out, s);
-        case 32: return pulse_poly_try<32>(h, sym, n_sym, out, s);
+        case 2: return pulse_poly_try<2>(h, sym, n_sym, out, s, st);
+        case 3: return pulse_poly_try<3>(h, sym, n_sym, out, s, st);
+        case 4: return pulse_poly_try<4>(h, sym, n_sym, out, s, st);
+        case 5: return pulse_poly_try<5>(h, sym, n_sym, out, s, st);
+        case 6: return pulse_poly_try<6>(h, sym, n_sym, out, s, st);
+        case 8: return pulse_poly_try<8>(h, sym, n_sym, out, s, st);
+        case 10: return pulse_poly_try<10>(h, sym, n_sym, out, s, st);
+        case 12: return pulse_poly_try<12>(h, sym, n_sym, out, s, st);
+        case 16: return pulse_poly_try<16>(h, sym, n_sym, out, s, st);
+        case 20: return pulse_poly_try<20>(h, sym, n_sym, out, s, st);
+        case 32: return pulse_poly_try<32>(h, sym, n_sym, out, s, st);
         default: return false;
     }
 }
@@ -2296,7 +2226,9 @@ comms_status_t comms_pulse_run_dev(comms_pulse_t* h, const comms_c32* d_sym, siz
     COMMS_ARG(!ranges_overlap(d_sym, in_bytes, d_out, n_out * (h->out_i16 ? 4 : 8)), "pulse shaping cannot run in place");
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
-    const bool poly = with_pulse_input(h, d_sym, [&](auto sym) { return pulse_poly_launch(h, sym, n_sym, reinterpret_cast<float2*>(d_out), s); });
+    comms_status_t st = COMMS_OK;
+    const bool poly = with_pulse_input(h, d_sym, [&](auto sym) { return pulse_poly_launch(h, sym, n_sym, reinterpret_cast<float2*>(d_out), s, &st); });
+    COMMS_TRY(st);
     if (!poly) {
         h->tic(s);
         size_t blocks = (n_out + 255) / 256;
@@ -2321,9 +2253,9 @@ comms_status_t comms_pulse_run_dev(comms_pulse_t* h, const comms_c32* d_sym, siz
                     reinterpret_cast<float2*>(d_out), n_sym, h->hist.next<float2>(), mx);
         });
         h->toc(s);
+        COMMS_TRY(launch_ok("pulse_kernel"));
     }
-    COMMS_TRY(launch_ok("pulse kernel"));  // (workgroup 0 of the same launch advanced the history)
-    h->hist.flip();
+    h->hist.flip();  // (workgroup 0 of the same launch advanced the history)
     if (h->mix) h->turns += static_cast<uint64_t>(n_out) * h->frac;
     return COMMS_OK;
 }

@@ -18,7 +18,6 @@
 // i.e. scalar loads into SGPR pairs that the packed FMA reads directly (op_sel picks the
 // half): no tap ever occupies a VGPR or an LDS slot.  Four workgroups per CU (37 KiB of LDS
 // each at R = 8) cover each other's load / compute / store phases.
-#include <hip/hip_ext.h>
 
 #include <cmath>
 #include <type_traits>
@@ -669,13 +668,11 @@ __global__ __launch_bounds__(64, 4) void fir_decim_wave_kernel(const DecimArgs a
 }
 
 
-// Event pair of an attached kernel timer for the launch about to be made (set by comms_fir_run_decim_dev, taken by
-// launch_decim_v): the kernel's own begin / end timestamps, as the FIR kernels' timed launches -- events recorded
+// `ev` below: the event pair of an attached kernel timer for this launch (Handle::take_events in run_decim), or an empty
+// one.  The pair takes the kernel's own begin / end timestamps, as the FIR kernels' timed launches -- events recorded
 // around the launch would include the dispatch gap in front of it whenever the launch before it carried no events.
-static thread_local hipEvent_t g_decim_ev_start = nullptr, g_decim_ev_stop = nullptr;
-
 template <int R, bool REAL, bool PRE, int HR, int AUX>
-static comms_status_t launch_decim_wave_v(const DecimArgs& a, hipStream_t s) {
+static comms_status_t launch_decim_wave_v(const DecimArgs& a, hipStream_t s, EventPair ev) {
     using G = DwGeom<R, HR>;
     // (single-wave workgroups ask for a sixteenth of the CU's LDS: seventeen would fit at HR = 2, and the dispatcher
     // would then fill some CUs with 17 waves and leave others 15)
@@ -683,71 +680,51 @@ static comms_status_t launch_decim_wave_v(const DecimArgs& a, hipStream_t s) {
     const size_t want = static_cast<size_t>(a.n_chunks);
     const size_t slots = (160u * 1024u / lds) * kNumCU;
     const unsigned blocks = static_cast<unsigned>(want < slots ? want : slots);
-    static DeviceOnce attr_once;
-    if (attr_once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_decim_wave_kernel<R, REAL, PRE, HR, AUX>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipEvent_t ea = g_decim_ev_start, eb = g_decim_ev_stop;
-    g_decim_ev_start = g_decim_ev_stop = nullptr;
-    if (ea)
-        hipExtLaunchKernelGGL((fir_decim_wave_kernel<R, REAL, PRE, HR, AUX>), dim3(blocks), dim3(64), static_cast<uint32_t>(lds), s, ea, eb, 0u, a);
-    else
-        fir_decim_wave_kernel<R, REAL, PRE, HR, AUX><<<dim3(blocks), dim3(64), lds, s>>>(a);
-    return launch_ok("fir_decim_wave_kernel");
+    return launch_kernel<fir_decim_wave_kernel<R, REAL, PRE, HR, AUX>>("fir_decim_wave_kernel", dim3(blocks), dim3(64), lds, s, ev, a);
 }
 
 // rates 2, 4 and 8 (Complex<f32> input, up to 129 taps: two halo rows); nt: nontemporal loads and stores
 template <int R>
-static comms_status_t launch_decim_wave(const DecimArgs& a, bool real, bool pre, bool nt, hipStream_t s) {
+static comms_status_t launch_decim_wave(const DecimArgs& a, bool real, bool pre, bool nt, hipStream_t s, EventPair ev) {
     if (real) {
-        if (pre) return nt ? launch_decim_wave_v<R, true, true, 2, 6>(a, s) : launch_decim_wave_v<R, true, true, 2, 0>(a, s);
-        return nt ? launch_decim_wave_v<R, true, false, 2, 6>(a, s) : launch_decim_wave_v<R, true, false, 2, 0>(a, s);
+        if (pre) return nt ? launch_decim_wave_v<R, true, true, 2, 6>(a, s, ev) : launch_decim_wave_v<R, true, true, 2, 0>(a, s, ev);
+        return nt ? launch_decim_wave_v<R, true, false, 2, 6>(a, s, ev) : launch_decim_wave_v<R, true, false, 2, 0>(a, s, ev);
     }
-    if (pre) return nt ? launch_decim_wave_v<R, false, true, 2, 6>(a, s) : launch_decim_wave_v<R, false, true, 2, 0>(a, s);
-    return nt ? launch_decim_wave_v<R, false, false, 2, 6>(a, s) : launch_decim_wave_v<R, false, false, 2, 0>(a, s);
+    if (pre) return nt ? launch_decim_wave_v<R, false, true, 2, 6>(a, s, ev) : launch_decim_wave_v<R, false, true, 2, 0>(a, s, ev);
+    return nt ? launch_decim_wave_v<R, false, false, 2, 6>(a, s, ev) : launch_decim_wave_v<R, false, false, 2, 0>(a, s, ev);
 }
 
 template <int R, bool REAL, bool PRE, class A>
-static comms_status_t launch_decim_v(const A& a, hipStream_t s) {
+static comms_status_t launch_decim_v(const A& a, hipStream_t s, EventPair ev) {
     using G = DcGeom<R>;
     constexpr size_t lds = G::LDS;
     // persistent grid: one workgroup per slot of the chip; tile b, b + slots, ... (or a contiguous run) each
     const size_t slots = static_cast<size_t>(G::template wgpc<PRE>()) * kNumCU;
     const unsigned blocks = static_cast<unsigned>(a.n_tiles < slots ? a.n_tiles : slots);
-    static DeviceOnce attr_once;
-    if (attr_once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_decim_kernel<R, REAL, PRE, A>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     A b = a;
     if (a.interleave) {
         // a workgroup's next tile is `blocks` tiles on: the per-step rotor of its tile-wide phase follows the grid
         const uint64_t ts = static_cast<uint64_t>(DC_TILE) - ((a.mode & COMMS_CHAIN_FM) ? 1 : 0);
         mix_host_rotor(static_cast<uint64_t>(R) * ts * blocks * a.frac, b.tile_c, b.tile_s);
     }
-    hipEvent_t ea = g_decim_ev_start, eb = g_decim_ev_stop;
-    g_decim_ev_start = g_decim_ev_stop = nullptr;
-    if (ea)
-        hipExtLaunchKernelGGL((fir_decim_kernel<R, REAL, PRE, A>), dim3(blocks), dim3(G::WG), static_cast<uint32_t>(lds), s, ea, eb, 0u, b);
-    else
-        fir_decim_kernel<R, REAL, PRE, A><<<dim3(blocks), dim3(G::WG), lds, s>>>(b);
-    return launch_ok("fir_decim_kernel");
+    return launch_kernel<fir_decim_kernel<R, REAL, PRE, A>>("fir_decim_kernel", dim3(blocks), dim3(G::WG), lds, s, ev, b);
 }
 
 // A = DecimArgs (Complex<f32> / FM outputs) or DecimBitsArgs (hard decisions); 11 / 13 / 15 (chunks of R taps): real taps only
 template <int R, class A>
-static comms_status_t launch_decim(const A& a, bool real, hipStream_t s) {
+static comms_status_t launch_decim(const A& a, bool real, hipStream_t s, EventPair ev) {
     const bool pre = (a.mode & COMMS_CHAIN_PRE) != 0;
     if constexpr (R != 11 && R != 13 && R != 15) {
-        if (!real) return pre ? launch_decim_v<R, false, true>(a, s) : launch_decim_v<R, false, false>(a, s);
+        if (!real) return pre ? launch_decim_v<R, false, true>(a, s, ev) : launch_decim_v<R, false, false>(a, s, ev);
     }
-    return pre ? launch_decim_v<R, true, true>(a, s) : launch_decim_v<R, true, false>(a, s);
+    return pre ? launch_decim_v<R, true, true>(a, s, ev) : launch_decim_v<R, true, false>(a, s, ev);
 }
 
 template <class A>
-static comms_status_t launch_decim_rate(const A& a, int R, bool real, hipStream_t s) {
+static comms_status_t launch_decim_rate(const A& a, int R, bool real, hipStream_t s, EventPair ev) {
     switch (R) {
 #define COMMS_DR(RV) \
-    case RV: return launch_decim<RV>(a, real, s);
+    case RV: return launch_decim<RV>(a, real, s, ev);
         COMMS_DR(2) COMMS_DR(3) COMMS_DR(4) COMMS_DR(5) COMMS_DR(6) COMMS_DR(7) COMMS_DR(8) COMMS_DR(9) COMMS_DR(10)
         COMMS_DR(11) COMMS_DR(12) COMMS_DR(13) COMMS_DR(14) COMMS_DR(15) COMMS_DR(16)
 #undef COMMS_DR
@@ -874,12 +851,7 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
         a.are[m] = in_range ? h->taps[k].re : 0.f;
         a.aim[m] = in_range ? h->taps[k].im : 0.f;
     }
-    // (the pair travels to launch_decim_v through thread-local slots: whatever the exit, none stays behind for the next
-    // launch on this thread, possibly another handle's)
-    struct EvGuard {
-        ~EvGuard() { g_decim_ev_start = g_decim_ev_stop = nullptr; }
-    } ev_guard;
-    (void)h->take_events(g_decim_ev_start, g_decim_ev_stop);
+    const EventPair ev = h->take_events();
     a.ks = h->next_stamp();
     comms_status_t st;
     // The wave-private form (fir_decim_wave_kernel): rate 8, Complex<f32> input, and a batch whose tiles of 128 outputs
@@ -920,9 +892,9 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
             // (config 3 at 2^26 samples: 128.3 -> 120.3 us; at 2^24 the re-read input of a benchmark loop would lose its
             // cache hits)
             const bool nt_big = n * sizeof(float2) > (192u << 20);
-            st = R == 2 ? launch_decim_wave<2>(a, real, pre, nt_big, s)
-                 : R == 4 ? launch_decim_wave<4>(a, real, pre, nt_big, s)
-                          : launch_decim_wave<8>(a, real, pre, nt_big, s);
+            st = R == 2 ? launch_decim_wave<2>(a, real, pre, nt_big, s, ev)
+                 : R == 4 ? launch_decim_wave<4>(a, real, pre, nt_big, s, ev)
+                          : launch_decim_wave<8>(a, real, pre, nt_big, s, ev);
             COMMS_TRY(st);
             h->hist.flip();
             if (bits) return sym_to_bits_launch(static_cast<const comms_c32*>(wave_out), a.n_out, *bits, static_cast<uint8_t*>(d_out), s);
@@ -933,9 +905,9 @@ static comms_status_t run_decim(comms_fir_t* h, const void* d_in, size_t n, void
         DecimBitsArgs b;
         static_cast<DecimArgs&>(b) = a;
         b.sym = *bits;
-        st = launch_decim_rate(b, R, real, s);
+        st = launch_decim_rate(b, R, real, s, ev);
     } else {
-        st = launch_decim_rate(a, R, real, s);
+        st = launch_decim_rate(a, R, real, s, ev);
     }
     COMMS_TRY(st);
     h->hist.flip();

@@ -272,21 +272,14 @@ namespace {
 
 template <int NT>
 comms_status_t launch_any(const AnyArgs& a, bool real, bool staged, unsigned blocks, size_t lds, hipStream_t s) {
-#define COMMS_ANY_GO(REALV, STG)                                                                                           \
-    do {                                                                                                                   \
-        static DeviceOnce once;                                                                                            \
-        if (once.need())                                                                                                   \
-            COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_decim_any_kernel<NT, REALV, STG>),         \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));                     \
-        fir_decim_any_kernel<NT, REALV, STG><<<dim3(blocks), dim3(ANY_WG), lds, s>>>(a);                                    \
-    } while (0)
+#define COMMS_ANY_GO(REALV, STG) \
+    return launch_kernel<fir_decim_any_kernel<NT, REALV, STG>>("fir_decim_any_kernel", dim3(blocks), dim3(ANY_WG), lds, s, {}, a)
     if (real) {
         if (staged) COMMS_ANY_GO(true, true); else COMMS_ANY_GO(true, false);
     } else {
         if (staged) COMMS_ANY_GO(false, true); else COMMS_ANY_GO(false, false);
     }
 #undef COMMS_ANY_GO
-    return launch_ok("fir_decim_any_kernel");
 }
 
 }  // namespace

@@ -38,7 +38,6 @@
 // 832 / 768 new samples per segment), and 5 / 6 / 8 for filters of up to 321 / 385 / 513 taps (704 / 640 / 512 new samples: more
 // transforms per sample, still one launch where the alternative is the overlap-save FIR and a mixer-decimator behind it).  Raw
 // i16 / u8 IQ converted in the load stage, four-wave workgroups for short batches.  Lane-accurate numpy model: scripts/proto_poly8.py.
-#include <hip/hip_ext.h>
 
 #include <cmath>
 #include <vector>
@@ -531,20 +530,10 @@ comms_status_t poly8_launch_w(comms_fir* h, hipStream_t s, In in, void* out, siz
     const dim3 grid(static_cast<unsigned>(want < slots ? want : slots));
     static const int chunk_knob = diag_knob("COMMS_POLY8_CHUNK_LOG2", -1);
     const unsigned chunk_log2 = chunk_knob >= 0 ? static_cast<unsigned>(chunk_knob) : nseg < 160u * static_cast<size_t>(kNumCU) ? 1u : 3u;
-    static DeviceOnce attr_once;
-    if (attr_once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_poly8_kernel<HR, FM, In, WPB, NPH>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipEvent_t ea = nullptr, eb = nullptr;
-    (void)h->take_events(ea, eb);
+    const EventPair ev = h->take_events();
     const KStamp ks = h->next_stamp();
-    if (ea)
-        hipExtLaunchKernelGGL((fir_poly8_kernel<HR, FM, In, WPB, NPH>), grid, dim3(64 * WPB), static_cast<uint32_t>(lds), s, ea, eb, 0u, in,
-                              h->hist.cur<float2>(), h->n_eff, out, n, tb, h->hist.next<float2>(), chunk_log2, mx, fmx, ks);
-    else
-        fir_poly8_kernel<HR, FM, In, WPB, NPH><<<grid, dim3(64 * WPB), lds, s>>>(in, h->hist.cur<float2>(), h->n_eff, out, n, tb,
-                                                                                h->hist.next<float2>(), chunk_log2, mx, fmx, ks);
-    return launch_ok("fir_poly8_kernel");
+    return launch_kernel<fir_poly8_kernel<HR, FM, In, WPB, NPH>>("fir_poly8_kernel", grid, dim3(64 * WPB), lds, s, ev, in, h->hist.cur<float2>(),
+                                                                 h->n_eff, out, n, tb, h->hist.next<float2>(), chunk_log2, mx, fmx, ks);
 }
 
 template <int HR, bool FM, class In, int NPH>

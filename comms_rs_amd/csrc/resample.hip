@@ -233,12 +233,7 @@ bool plan_tile(comms_resample* h, size_t tab_bytes) {
 
 template <class T, bool TAB_LDS>
 comms_status_t launch_resample(const RsArgs& a, unsigned blocks, int wg, size_t lds, hipStream_t s) {
-    static DeviceOnce once;
-    if (once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&resample_kernel<T, TAB_LDS>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    resample_kernel<T, TAB_LDS><<<dim3(blocks), dim3(wg), lds, s>>>(a);
-    return launch_ok("resample_kernel");
+    return launch_kernel<resample_kernel<T, TAB_LDS>>("resample_kernel", dim3(blocks), dim3(wg), lds, s, {}, a);
 }
 
 size_t resample_out_len(size_t n, size_t up, size_t down) {  // n * up does not overflow (checked by the callers)

@@ -172,12 +172,7 @@ constexpr int RF_MAX_TAPS = 257, RF_MAX_RATE = 64;
 // (the stride of the phase arrays: plan_stride, common.hpp)
 template <int OUT>
 comms_status_t launch_rfir(const RfArgs& a, unsigned blocks, int wg, size_t lds, hipStream_t s) {
-    static DeviceOnce once;
-    if (once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&rfir_decim_kernel<OUT>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    rfir_decim_kernel<OUT><<<dim3(blocks), dim3(wg), lds, s>>>(a);
-    return launch_ok("rfir_decim_kernel");
+    return launch_kernel<rfir_decim_kernel<OUT>>("rfir_decim_kernel", dim3(blocks), dim3(wg), lds, s, {}, a);
 }
 
 size_t rfir_out_len(size_t n, int rate) { return (n + rate - 1) / rate; }

@@ -230,12 +230,7 @@ bool plan_tile(comms_symsync* h) {
 
 template <int U, int FMT>
 comms_status_t launch_symsync(const SsArgs& a, unsigned blocks, int wg, size_t lds, hipStream_t s) {
-    static DeviceOnce once;
-    if (once.need())
-        COMMS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&symsync_kernel<U, FMT>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(SS_LDS_WIDE)));
-    symsync_kernel<U, FMT><<<dim3(blocks), dim3(wg), lds, s>>>(a);
-    return launch_ok("symsync_kernel");
+    return launch_kernel<symsync_kernel<U, FMT>>("symsync_kernel", dim3(blocks), dim3(wg), lds, s, {}, a);
 }
 
 template <int U>
