@@ -19,6 +19,7 @@ IQ_C32, IQ_I16, IQ_U8 = 0, 1, 2
 SYM_C32, SYM_BITS = 0, 1        # comms_pulse_set_input_format, comms_chain_set_output_format
 SYM_LLR = 3                     # comms_deframe_set_output_format only
 DEFRAME_NORMALISE = 1           # comms_deframe_create: flags
+CONV_TERMINATED, CONV_TRUNCATED = 0, 1  # comms_convenc_create, comms_viterbi_create: flags
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 RESAMPLE_F32, RESAMPLE_C32 = 4, 8  # comms_resample_create: bytes per sample
 CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR = 0, 1  # comms_channelizer_create: layout
@@ -312,6 +313,19 @@ _PROTOS = {
     "comms_deframe_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_deframe_set_timer": [_vp, _vp],
     "comms_deframe_destroy": [_vp],
+    "comms_convenc_create": [_i32, _i32, _vp, _i32, _sz, _i32, _pp],
+    "comms_convenc_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_convenc_run": [_vp, _vp, _sz, _vp],
+    "comms_convenc_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_convenc_set_timer": [_vp, _vp],
+    "comms_convenc_destroy": [_vp],
+    "comms_viterbi_create": [_i32, _i32, _vp, _i32, _sz, _sz, _i32, _pp],
+    "comms_viterbi_set_quant_scale": [_vp, C.c_float],
+    "comms_viterbi_run_dev": [_vp, _vp, _sz, _vp, _vp, _vp],
+    "comms_viterbi_run": [_vp, _vp, _sz, _vp, _vp],
+    "comms_viterbi_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_viterbi_set_timer": [_vp, _vp],
+    "comms_viterbi_destroy": [_vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],
@@ -330,6 +344,10 @@ _OTHER = {
     "comms_buf_size": (_sz, [_vp]),
     "comms_qfilt_len": (_sz, [_u32]),
     "comms_deframe_frame_bytes": (_sz, [_vp]),
+    "comms_convenc_in_frame_bytes": (_sz, [_vp]),
+    "comms_convenc_out_frame_bytes": (_sz, [_vp]),
+    "comms_viterbi_in_frame_bytes": (_sz, [_vp]),
+    "comms_viterbi_out_frame_bytes": (_sz, [_vp]),
     "comms_buf_device": (_i32, [_vp]),
     "comms_synth_iq_host": (None, [_vp, _sz, _u64, _u64]),
 }

@@ -1393,6 +1393,94 @@ public:
     }
 };
 
+// Convolutional FEC (comms_convenc_*, comms_viterbi_*; additional nodes).  A code is (K, generators, terminated); no
+// generators = the defaults of K = 7, (0171, 0133).  One description per operation, two shells each.
+struct ConvCodeSpec {
+    size_t n_info_bits;
+    int K = 7;
+    std::vector<uint32_t> gens = {};
+    bool terminated = true;
+    int n() const { return gens.empty() ? 2 : static_cast<int>(gens.size()); }
+    const uint32_t* g() const { return gens.empty() ? nullptr : gens.data(); }
+    int32_t flags() const { return terminated ? COMMS_CONV_TERMINATED : COMMS_CONV_TRUNCATED; }
+};
+
+// Encoder: a message is whole records of packed information bits (in_frame_bytes() each, LSB first), the output the records
+// of coded bits (out_frame_bytes() each) -- the bytes PulseBitsNode and the byte modulators take as they stand.
+struct ConvEncOp {
+    using In = uint8_t;
+    using Out = uint8_t;
+    ConvEncOp(const char* who, const ConvCodeSpec& code, int device)
+        : h_(create<decltype(h_)>(who, comms_convenc_create, code.K, code.n(), code.g(), code.flags(), code.n_info_bits, device)) {}
+    size_t in_frame_bytes() const { return comms_convenc_in_frame_bytes(h_.get()); }
+    size_t out_frame_bytes() const { return comms_convenc_out_frame_bytes(h_.get()); }
+    std::string kernel(size_t n_frames) const { return kernel_name(comms_convenc_get_kernel, h_.get(), n_frames); }  // "conv_encode_kernel ..."
+
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const {
+        if (n % in_frame_bytes()) return COMMS_ERR_ARG;
+        m = n / in_frame_bytes() * out_frame_bytes();
+        return COMMS_OK;
+    }
+    comms_status_t launch(const uint8_t* in, size_t n, uint8_t* out) { return comms_convenc_run(h_.get(), in, n / in_frame_bytes(), out); }
+    comms_status_t launch_dev(const uint8_t* in, size_t n, uint8_t* out, void* s) {
+        return comms_convenc_run_dev(h_.get(), in, n / in_frame_bytes(), out, s);
+    }
+    Owned<comms_convenc_t, comms_convenc_destroy> h_;
+};
+class ConvEncoderNode : public HostNode<ConvEncoderNode, ConvEncOp> {
+public:
+    explicit ConvEncoderNode(const ConvCodeSpec& code, int device = 0) : HostNode("ConvEncoderNode::new", code, device) {}
+};
+class ConvEncoderNodeDev : public DevNode<ConvEncoderNodeDev, ConvEncOp> {
+public:
+    explicit ConvEncoderNodeDev(const ConvCodeSpec& code, int device = 0) : DevNode(device, "ConvEncoderNodeDev::new", code, device) {}
+};
+
+// Decoder: takes DeframeNode's message in the COMMS_SYM_LLR format (records of frame_bytes / 4 >= n * steps values) and
+// sends the decoded records under the same headers: frame f at data[f * frame_bytes], frame_bytes = out_frame_bytes().
+// A message without frames passes through empty.
+struct ViterbiOp {
+    using Frames = DeframeOp::Frames;
+    using FramesDev = DeframeOp::FramesDev;
+    // record_llrs: values per input record (0: exactly n * steps); qscale: comms_viterbi_set_quant_scale
+    ViterbiOp(const char* who, const ConvCodeSpec& code, size_t record_llrs, float qscale, int device)
+        : h_(create<decltype(h_)>(who, comms_viterbi_create, code.K, code.n(), code.g(), code.flags(), code.n_info_bits, record_llrs, device)) {
+        throw_on(comms_viterbi_set_quant_scale(h_.get(), qscale), who);
+    }
+    size_t in_frame_bytes() const { return comms_viterbi_in_frame_bytes(h_.get()); }
+    size_t out_frame_bytes() const { return comms_viterbi_out_frame_bytes(h_.get()); }
+    std::string kernel(size_t n_frames) const { return kernel_name(comms_viterbi_get_kernel, h_.get(), n_frames); }  // "viterbi_kernel<..> ..."
+
+protected:
+    Result<Frames> decode(const Frames& in) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        Frames out{std::vector<uint8_t>(in.size() * out_frame_bytes()), in.headers, out_frame_bytes()};
+        return ok_or(comms_viterbi_run(h_.get(), reinterpret_cast<const float*>(in.data.data()), in.size(), out.data.data(), nullptr), out);
+    }
+    Result<FramesDev> decode_dev(const FramesDev& in, const DevStream& on) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        FramesDev out{DeviceBuf<uint8_t>(in.size() ? in.size() * out_frame_bytes() : 8, on.device()), in.headers, out_frame_bytes()};
+        return ok_or(on.submit(in.data, out.data, [&](void* s) {
+            return comms_viterbi_run_dev(h_.get(), reinterpret_cast<const float*>(in.data.ptr()), in.size(), out.data.ptr(), nullptr, s);
+        }), out);
+    }
+    Owned<comms_viterbi_t, comms_viterbi_destroy> h_;
+};
+class ViterbiNode : public DeriveNode<ViterbiNode>, public Ports<ViterbiOp::Frames, ViterbiOp::Frames>, public ViterbiOp {
+public:
+    explicit ViterbiNode(const ConvCodeSpec& code, size_t record_llrs = 0, float qscale = 1.0f, int device = 0)
+        : ViterbiOp("ViterbiNode::new", code, record_llrs, qscale, device) {}
+    Result<Frames> run(const Frames& in) { return decode(in); }
+};
+// on device-resident messages: DeframeNodeDev's records in, the decoded records in a DeviceBuf out (headers on the host)
+class ViterbiNodeDev : public DeriveNode<ViterbiNodeDev>, public Ports<ViterbiOp::FramesDev, ViterbiOp::FramesDev>, public OnStream<ViterbiOp> {
+public:
+    explicit ViterbiNodeDev(const ConvCodeSpec& code, size_t record_llrs = 0, float qscale = 1.0f, int device = 0)
+        : OnStream(device, "ViterbiNodeDev::new", code, record_llrs, qscale, device) {}
+    Result<FramesDev> run(const FramesDev& in) { return decode_dev(in, *this); }
+};
+
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)

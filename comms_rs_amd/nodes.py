@@ -1654,6 +1654,118 @@ class DeframeNode(_Handle):
         return self
 
 
+# ------------------------------------------------------------------ convolutional FEC
+def _conv_args(K, n, gens, terminated):
+    """(K, n, gens array or None, flags) of a code: gens=None is K = 7, g = (0o171, 0o133)."""
+    g = None if gens is None else np.ascontiguousarray(gens, dtype=np.uint32)
+    n = (2 if g is None else g.size) if n is None else int(n)
+    if g is not None and g.size != n:
+        raise ValueError("gens must hold n generators")
+    return int(K), n, g, _lib.CONV_TERMINATED if terminated else _lib.CONV_TRUNCATED
+
+
+class ConvEncoderNode(_Handle):
+    """Rate-1/n convolutional encoder (comms_convenc_*): frame-major records of `n_info_bits` packed bits (LSB first, each
+    record ceil(bits / 8) bytes rounded up to 4) -> records of n * steps coded bits, coded bit j of step t at t * n + j, all
+    frames of a call in one launch.  terminated=True appends K - 1 zero bits (steps = n_info_bits + K - 1).  Stateless:
+    every frame starts in state 0.  run() takes and returns uint8 arrays of shape (n_frames, frame bytes)."""
+    _destroy = "comms_convenc_destroy"
+
+    def __init__(self, n_info_bits, K=7, gens=None, n=None, terminated=True, device=0):
+        super().__init__()
+        K, n, g, flags = _conv_args(K, n, gens, terminated)
+        self.n_info_bits, self.K, self.n = int(n_info_bits), K, n
+        check(lib().comms_convenc_create(K, n, None if g is None else _ptr(g), flags, self.n_info_bits, device, C.byref(self._h)))
+
+    @property
+    def in_frame_bytes(self):
+        return lib().comms_convenc_in_frame_bytes(self._h)
+
+    @property
+    def out_frame_bytes(self):
+        return lib().comms_convenc_out_frame_bytes(self._h)
+
+    def run(self, frames):
+        x = np.ascontiguousarray(frames, dtype=np.uint8)
+        if x.size % self.in_frame_bytes:
+            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
+        n_frames = x.size // self.in_frame_bytes
+        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
+        check(lib().comms_convenc_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
+        return out
+
+    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
+        check(lib().comms_convenc_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+
+    def kernel(self, n_frames):
+        """ "conv_encode_kernel wg=.. K=.. n=.. steps=.. words=.. grid=.. max_grid=.. lds=0" for a call on n_frames frames."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_convenc_get_kernel(self._h, int(n_frames), buf, 240))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        check(lib().comms_convenc_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
+class ViterbiNode(_Handle):
+    """Viterbi decoder of ConvEncoderNode's code (comms_viterbi_*): frame-major records of `record_llrs` f32 LLRs (positive =
+    bit 0; the first n * steps are used; None = exactly that many) -> records of `n_info_bits` decoded bits, all frames of a
+    call in one launch, one wave per frame.  The decisions are integer arithmetic on q = clamp(rint(L * qscale), -127, 127)
+    (NaN: 0), so they are the bits of the definition exactly.  A DeframeNode "llr" record of at least n * steps values is a
+    valid input as it stands.  run() returns uint8 (n_frames, out_frame_bytes); with metrics=True also the final int32
+    path metric of every frame."""
+    _destroy = "comms_viterbi_destroy"
+
+    def __init__(self, n_info_bits, K=7, gens=None, n=None, terminated=True, record_llrs=None, qscale=None, device=0):
+        super().__init__()
+        K, n, g, flags = _conv_args(K, n, gens, terminated)
+        self.n_info_bits, self.K, self.n = int(n_info_bits), K, n
+        check(lib().comms_viterbi_create(K, n, None if g is None else _ptr(g), flags, self.n_info_bits,
+                                         0 if record_llrs is None else int(record_llrs), device, C.byref(self._h)))
+        if qscale is not None:
+            self.set_quant_scale(qscale)
+
+    def set_quant_scale(self, qscale):
+        """q = clamp(rint(L * qscale), -127, 127): for LLRs 2 y / sigma^2 of unit symbols, about 127 / (6 + 4 / sigma^2)
+        keeps all but the rarest values off the clamp."""
+        check(lib().comms_viterbi_set_quant_scale(self._h, float(qscale)))
+        return self
+
+    @property
+    def in_frame_bytes(self):
+        return lib().comms_viterbi_in_frame_bytes(self._h)
+
+    @property
+    def out_frame_bytes(self):
+        return lib().comms_viterbi_out_frame_bytes(self._h)
+
+    def run(self, llr, metrics=False):
+        x = np.ascontiguousarray(llr, dtype=np.float32)
+        per = self.in_frame_bytes // 4
+        if x.size % per:
+            raise ValueError("the input must hold whole records of in_frame_bytes / 4 values")
+        n_frames = x.size // per
+        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
+        m = np.zeros(n_frames, np.int32)
+        check(lib().comms_viterbi_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None,
+                                      _ptr(m) if metrics and n_frames else None))
+        return (out, m) if metrics else out
+
+    def run_dev(self, llr_ptr, n_frames, bits_ptr, metrics_ptr=None, stream=0):
+        check(lib().comms_viterbi_run_dev(self._h, llr_ptr, int(n_frames), bits_ptr, metrics_ptr, stream))
+
+    def kernel(self, n_frames):
+        """ "viterbi_kernel<n,lds|workspace> wg=.. waves=.. K=.. steps=.. seam=.. grid=.. max_grid=.. lds=.. workspace=.."."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_viterbi_get_kernel(self._h, int(n_frames), buf, 240))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        check(lib().comms_viterbi_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
 def qfilt_taps(n_taps, alpha, sam_per_sym):
     """util/math.rs:307-342 (f64, real); even n_taps is incremented."""
     out = np.empty(lib().comms_qfilt_len(int(n_taps)), np.float64)
@@ -1728,7 +1840,9 @@ class KernelTimer:
                 "comms_symsync_destroy": "comms_symsync_set_timer",
                 "comms_syncest_destroy": "comms_syncest_set_timer",
                 "comms_framesync_destroy": "comms_framesync_set_timer",
-                "comms_deframe_destroy": "comms_deframe_set_timer"}[node._destroy]
+                "comms_deframe_destroy": "comms_deframe_set_timer",
+                "comms_convenc_destroy": "comms_convenc_set_timer",
+                "comms_viterbi_destroy": "comms_viterbi_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

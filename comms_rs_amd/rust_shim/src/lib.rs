@@ -1300,6 +1300,78 @@ impl DeframeNode {
     }
 }
 
+/// Convolutional encoder (an additional node, comms_convenc_*): a message is whole records of packed information bits (LSB
+/// first, `in_frame_bytes()` each), the output the records of n * steps coded bits (`out_frame_bytes()` each), coded bit j of
+/// step t at t * n + j.  `gens`: `None` = K = 7, (0o171, 0o133).  Stateless: every frame starts in state 0.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct ConvEncoderNode {
+    pub input: NodeReceiver<Vec<u8>>,
+    h: *mut comms_convenc_t,
+    pub output: NodeSender<Vec<u8>>,
+}
+handle_node!(ConvEncoderNode, comms_convenc_destroy);
+impl ConvEncoderNode {
+    /// `Err(())`: K outside 3 ..= 7, other than 2 or 3 generators, a generator outside 1 .. 2^K, more than 2^16 steps.
+    pub fn new(n_info_bits: usize, k: i32, gens: Option<&[u32]>, terminated: bool) -> Result<Self, ()> {
+        let mut h = ptr::null_mut();
+        let flags = if terminated { COMMS_CONV_TERMINATED } else { COMMS_CONV_TRUNCATED };
+        let (n, g) = match gens { Some(g) => (g.len() as i32, g.as_ptr()), None => (2, ptr::null()) };
+        let st = unsafe { comms_convenc_create(k, n, g, flags, n_info_bits, 0, &mut h) };
+        if st != COMMS_OK { return Err(()); }
+        Ok(ConvEncoderNode { input: Default::default(), h, output: Default::default() })
+    }
+    pub fn in_frame_bytes(&self) -> usize { unsafe { comms_convenc_in_frame_bytes(self.h) } }
+    pub fn out_frame_bytes(&self) -> usize { unsafe { comms_convenc_out_frame_bytes(self.h) } }
+    pub fn run(&mut self, records: &[u8]) -> Result<Vec<u8>, NodeError> {
+        let fin = self.in_frame_bytes();
+        if fin == 0 || records.len() % fin != 0 { return Err(NodeError::DataError); }
+        let n_frames = records.len() / fin;
+        let mut out = vec![0u8; n_frames * self.out_frame_bytes()];
+        let st = unsafe { comms_convenc_run(self.h, records.as_ptr() as *const c_void, n_frames, out.as_mut_ptr() as *mut c_void) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
+/// Viterbi decoder of `ConvEncoderNode`'s code (an additional node, comms_viterbi_*): takes `DeframeNode`'s `COMMS_SYM_LLR`
+/// message (records of at least n * steps f32 values, positive = bit 0) and sends the decoded records under the same headers,
+/// all frames by one launch.  Integer decisions on q = clamp(rint(L * qscale), -127, 127).
+#[derive(Node)]
+#[pass_by_ref]
+pub struct ViterbiNode {
+    pub input: NodeReceiver<Frames>,
+    h: *mut comms_viterbi_t,
+    pub output: NodeSender<Frames>,
+}
+handle_node!(ViterbiNode, comms_viterbi_destroy);
+impl ViterbiNode {
+    /// `record_llrs`: values per input record, 0 = exactly n * steps.  `Err(())` as `ConvEncoderNode::new`, or fewer values.
+    pub fn new(n_info_bits: usize, k: i32, gens: Option<&[u32]>, terminated: bool, record_llrs: usize) -> Result<Self, ()> {
+        let mut h = ptr::null_mut();
+        let flags = if terminated { COMMS_CONV_TERMINATED } else { COMMS_CONV_TRUNCATED };
+        let (n, g) = match gens { Some(g) => (g.len() as i32, g.as_ptr()), None => (2, ptr::null()) };
+        let st = unsafe { comms_viterbi_create(k, n, g, flags, n_info_bits, record_llrs, 0, &mut h) };
+        if st != COMMS_OK { return Err(()); }
+        Ok(ViterbiNode { input: Default::default(), h, output: Default::default() })
+    }
+    pub fn set_quant_scale(&mut self, qscale: f32) -> Result<(), NodeError> {
+        let st = unsafe { comms_viterbi_set_quant_scale(self.h, qscale) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    pub fn in_frame_bytes(&self) -> usize { unsafe { comms_viterbi_in_frame_bytes(self.h) } }
+    pub fn out_frame_bytes(&self) -> usize { unsafe { comms_viterbi_out_frame_bytes(self.h) } }
+    pub fn run(&mut self, frames: &Frames) -> Result<Frames, NodeError> {
+        let n_frames = frames.headers.len();
+        if frames.frame_bytes != self.in_frame_bytes() || frames.data.len() < n_frames * frames.frame_bytes { return Err(NodeError::DataError); }
+        let frame_bytes = self.out_frame_bytes();
+        let mut out = Frames { data: vec![0u8; n_frames * frame_bytes], headers: frames.headers.clone(), frame_bytes };
+        let st = unsafe {
+            comms_viterbi_run(self.h, frames.data.as_ptr() as *const f32, n_frames, out.data.as_mut_ptr() as *mut c_void, ptr::null_mut())
+        };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
 /// demodulation/nco.rs:118-133 in block form: a vector of phase errors per message.
 #[derive(Node)]
 #[pass_by_ref]
