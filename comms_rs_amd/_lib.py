@@ -20,6 +20,7 @@ SYM_C32, SYM_BITS = 0, 1        # comms_pulse_set_input_format, comms_chain_set_
 SYM_LLR = 3                     # comms_deframe_set_output_format only
 DEFRAME_NORMALISE = 1           # comms_deframe_create: flags
 CONV_TERMINATED, CONV_TRUNCATED = 0, 1  # comms_convenc_create, comms_viterbi_create: flags
+RATEMATCH_TX, RATEMATCH_RX = 0, 1  # comms_ratematch_get_kernel: direction
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 RESAMPLE_F32, RESAMPLE_C32 = 4, 8  # comms_resample_create: bytes per sample
 CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR = 0, 1  # comms_channelizer_create: layout
@@ -326,6 +327,15 @@ _PROTOS = {
     "comms_viterbi_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_viterbi_set_timer": [_vp, _vp],
     "comms_viterbi_destroy": [_vp],
+    "comms_ratematch_create": [_sz, _vp, _sz, _sz, _vp, _vp, _sz, _i32, _pp],
+    "comms_ratematch_get_map": [_vp, _vp, _sz],
+    "comms_ratematch_tx_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_ratematch_rx_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_ratematch_tx_run": [_vp, _vp, _sz, _vp],
+    "comms_ratematch_rx_run": [_vp, _vp, _sz, _vp],
+    "comms_ratematch_get_kernel": [_vp, _i32, _sz, C.c_char_p, _sz],
+    "comms_ratematch_set_timer": [_vp, _vp],
+    "comms_ratematch_destroy": [_vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],
@@ -348,6 +358,11 @@ _OTHER = {
     "comms_convenc_out_frame_bytes": (_sz, [_vp]),
     "comms_viterbi_in_frame_bytes": (_sz, [_vp]),
     "comms_viterbi_out_frame_bytes": (_sz, [_vp]),
+    "comms_ratematch_n_tx_bits": (_sz, [_vp]),
+    "comms_ratematch_tx_in_frame_bytes": (_sz, [_vp]),
+    "comms_ratematch_tx_out_frame_bytes": (_sz, [_vp]),
+    "comms_ratematch_rx_in_frame_bytes": (_sz, [_vp]),
+    "comms_ratematch_rx_out_frame_bytes": (_sz, [_vp]),
     "comms_buf_device": (_i32, [_vp]),
     "comms_synth_iq_host": (None, [_vp, _sz, _u64, _u64]),
 }

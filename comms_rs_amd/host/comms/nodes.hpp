@@ -1481,6 +1481,113 @@ public:
     Result<FramesDev> run(const FramesDev& in) { return decode_dev(in, *this); }
 };
 
+// Rate matching (comms_ratematch_*; additional nodes): puncturer, interleaver and scrambler of one frame format, the same
+// description on both sides of the link.  One description per direction, two shells each.
+struct RateMatchSpec {
+    size_t n_coded;                       // the encoder's n * steps
+    std::vector<uint8_t> pattern = {};    // 0 / 1 per coded position, repeated; empty keeps everything
+    size_t cols = 0;                      // columns of the pruned block interleaver (0, 1: none) ...
+    std::vector<uint32_t> perm = {};      // ... or an explicit permutation of the kept bits (cols = 0 then)
+    std::vector<uint8_t> scramble = {};   // one bit per transmitted bit, packed LSB first; empty: none
+    const uint8_t* p() const { return pattern.empty() ? nullptr : pattern.data(); }
+    const uint32_t* pi() const { return perm.empty() ? nullptr : perm.data(); }
+    const uint8_t* s() const { return scramble.empty() ? nullptr : scramble.data(); }
+};
+struct RateMatchHandle {
+    // perm and scramble are read for as many entries as the pattern keeps positions: checked here, where their lengths are known
+    RateMatchHandle(const char* who, const RateMatchSpec& f, size_t record_llrs, int device) {
+        size_t kept = 0;
+        for (size_t i = 0; i < f.n_coded; ++i) kept += f.pattern.empty() || f.pattern[i % f.pattern.size()] != 0;
+        if ((!f.perm.empty() && f.perm.size() != kept) || (!f.scramble.empty() && f.scramble.size() < (kept + 7) / 8))
+            throw std::runtime_error(std::string(who) + ": perm and scramble must hold one entry per transmitted bit");
+        h_ = create<decltype(h_)>(who, comms_ratematch_create, f.n_coded, f.p(), f.pattern.size(), f.cols, f.pi(), static_cast<const void*>(f.s()),
+                                  record_llrs, device);
+    }
+    size_t n_tx_bits() const { return comms_ratematch_n_tx_bits(h_.get()); }
+    std::vector<uint32_t> map() const {   // src: the coded position that feeds transmitted bit k
+        std::vector<uint32_t> src(n_tx_bits());
+        throw_on(comms_ratematch_get_map(h_.get(), src.data(), src.size()), "RateMatch::map");
+        return src;
+    }
+
+protected:
+    std::string kernel_of(int32_t direction, size_t n_frames) const {
+        return kernel_name([direction](const comms_ratematch_t* h, size_t n, char* name, size_t len) { return comms_ratematch_get_kernel(h, direction, n, name, len); },
+                           h_.get(), n_frames);
+    }
+    Owned<comms_ratematch_t, comms_ratematch_destroy> h_;
+};
+
+// Transmit: a message is whole records of coded bits (in_frame_bytes() each: ConvEncoderNode's output as it stands), the output
+// the records of transmitted bits (out_frame_bytes() each) -- the bytes PulseBitsNode and the byte modulators take.
+struct RateMatchOp : RateMatchHandle {
+    using In = uint8_t;
+    using Out = uint8_t;
+    RateMatchOp(const char* who, const RateMatchSpec& format, int device) : RateMatchHandle(who, format, 0, device) {}
+    size_t in_frame_bytes() const { return comms_ratematch_tx_in_frame_bytes(h_.get()); }
+    size_t out_frame_bytes() const { return comms_ratematch_tx_out_frame_bytes(h_.get()); }
+    std::string kernel(size_t n_frames) const { return kernel_of(COMMS_RATEMATCH_TX, n_frames); }  // "ratematch_tx_kernel ..."
+
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const {
+        if (n % in_frame_bytes()) return COMMS_ERR_ARG;
+        m = n / in_frame_bytes() * out_frame_bytes();
+        return COMMS_OK;
+    }
+    comms_status_t launch(const uint8_t* in, size_t n, uint8_t* out) { return comms_ratematch_tx_run(h_.get(), in, n / in_frame_bytes(), out); }
+    comms_status_t launch_dev(const uint8_t* in, size_t n, uint8_t* out, void* s) {
+        return comms_ratematch_tx_run_dev(h_.get(), in, n / in_frame_bytes(), out, s);
+    }
+};
+class RateMatchNode : public HostNode<RateMatchNode, RateMatchOp> {
+public:
+    explicit RateMatchNode(const RateMatchSpec& format, int device = 0) : HostNode("RateMatchNode::new", format, device) {}
+};
+class RateMatchNodeDev : public DevNode<RateMatchNodeDev, RateMatchOp> {
+public:
+    explicit RateMatchNodeDev(const RateMatchSpec& format, int device = 0) : DevNode(device, "RateMatchNodeDev::new", format, device) {}
+};
+
+// Receive: takes DeframeNode's message in the COMMS_SYM_LLR format (records of frame_bytes / 4 >= n_tx_bits() values) and sends
+// records of n_coded values under the same headers, zeros at the punctured positions: ViterbiNode's input (record_llrs = 0).
+// A message without frames passes through empty.
+struct RateDematchOp : RateMatchHandle {
+    using Frames = DeframeOp::Frames;
+    using FramesDev = DeframeOp::FramesDev;
+    // record_llrs: values per input record (0: exactly n_tx_bits())
+    RateDematchOp(const char* who, const RateMatchSpec& format, size_t record_llrs, int device) : RateMatchHandle(who, format, record_llrs, device) {}
+    size_t in_frame_bytes() const { return comms_ratematch_rx_in_frame_bytes(h_.get()); }
+    size_t out_frame_bytes() const { return comms_ratematch_rx_out_frame_bytes(h_.get()); }
+    std::string kernel(size_t n_frames) const { return kernel_of(COMMS_RATEMATCH_RX, n_frames); }  // "ratematch_rx_kernel ..."
+
+protected:
+    Result<Frames> dematch(const Frames& in) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        Frames out{std::vector<uint8_t>(in.size() * out_frame_bytes()), in.headers, out_frame_bytes()};
+        return ok_or(comms_ratematch_rx_run(h_.get(), reinterpret_cast<const float*>(in.data.data()), in.size(), reinterpret_cast<float*>(out.data.data())), out);
+    }
+    Result<FramesDev> dematch_dev(const FramesDev& in, const DevStream& on) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        FramesDev out{DeviceBuf<uint8_t>(in.size() ? in.size() * out_frame_bytes() : 8, on.device()), in.headers, out_frame_bytes()};
+        return ok_or(on.submit(in.data, out.data, [&](void* s) {
+            return comms_ratematch_rx_run_dev(h_.get(), reinterpret_cast<const float*>(in.data.ptr()), in.size(), reinterpret_cast<float*>(out.data.ptr()), s);
+        }), out);
+    }
+};
+class RateDematchNode : public DeriveNode<RateDematchNode>, public Ports<RateDematchOp::Frames, RateDematchOp::Frames>, public RateDematchOp {
+public:
+    explicit RateDematchNode(const RateMatchSpec& format, size_t record_llrs = 0, int device = 0)
+        : RateDematchOp("RateDematchNode::new", format, record_llrs, device) {}
+    Result<Frames> run(const Frames& in) { return dematch(in); }
+};
+// on device-resident messages: DeframeNodeDev's records in, the dematched records in a DeviceBuf out (headers on the host)
+class RateDematchNodeDev : public DeriveNode<RateDematchNodeDev>, public Ports<RateDematchOp::FramesDev, RateDematchOp::FramesDev>, public OnStream<RateDematchOp> {
+public:
+    explicit RateDematchNodeDev(const RateMatchSpec& format, size_t record_llrs = 0, int device = 0)
+        : OnStream(device, "RateDematchNodeDev::new", format, record_llrs, device) {}
+    Result<FramesDev> run(const FramesDev& in) { return dematch_dev(in, *this); }
+};
+
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)

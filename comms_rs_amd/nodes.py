@@ -1766,6 +1766,111 @@ class ViterbiNode(_Handle):
         return self
 
 
+# ------------------------------------------------------------------ rate matching
+class _RateMatch(_Handle):
+    """One frame format of comms_ratematch_*: n_coded coded bits, a puncturing `pattern` (0 / 1 per coded position, repeated;
+    None keeps everything), an interleaver over the n_tx_bits kept bits (`cols` columns of the pruned block interleaver, or an
+    explicit `perm` with perm[k] the kept-bit index transmitted k-th) and `scramble`, n_tx_bits bits packed LSB first (uint8)
+    that are XORed onto the transmitted bits, or None."""
+    _destroy = "comms_ratematch_destroy"
+    _direction = None
+
+    def __init__(self, n_coded, pattern=None, cols=0, perm=None, scramble=None, record_llrs=0, device=0):
+        super().__init__()
+        self.n_coded = int(n_coded)
+        pat = None if pattern is None else np.ascontiguousarray(pattern, dtype=np.uint8)
+        pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.uint32)
+        sc = None if scramble is None else np.ascontiguousarray(scramble, dtype=np.uint8)
+        kept = self.n_coded if pat is None or pat.size == 0 else int(np.count_nonzero(np.resize(pat, max(self.n_coded, 0))))
+        if pm is not None and pm.size != kept:
+            raise ValueError("perm must hold one entry per transmitted bit (%d)" % kept)
+        if sc is not None and sc.size < (kept + 7) // 8:
+            raise ValueError("scramble must hold %d packed bits" % kept)
+        check(lib().comms_ratematch_create(self.n_coded, None if pat is None else _ptr(pat), 0 if pat is None else pat.size, int(cols),
+                                           None if pm is None else _ptr(pm), None if sc is None else _ptr(sc), int(record_llrs), device,
+                                           C.byref(self._h)))
+
+    @property
+    def n_tx_bits(self):
+        return lib().comms_ratematch_n_tx_bits(self._h)
+
+    def map(self):
+        """src: the coded position that feeds transmitted bit k (uint32, n_tx_bits entries)."""
+        src = np.zeros(self.n_tx_bits, np.uint32)
+        check(lib().comms_ratematch_get_map(self._h, _ptr(src), src.size))
+        return src
+
+    def kernel(self, n_frames):
+        """ "ratematch_tx_kernel | ratematch_rx_kernel wg=.. table=lds|global seam=.. n_coded=.. n_tx=.. words= | values=..
+        grid=.. max_grid=.. lds=.." for a call on n_frames frames."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_ratematch_get_kernel(self._h, self._direction, int(n_frames), buf, 240))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        check(lib().comms_ratematch_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
+class RateMatchNode(_RateMatch):
+    """Transmit rate matching between ConvEncoderNode and the bit-input modulators: frame-major records of n_coded packed
+    bits (the encoder's records) -> records of n_tx_bits bits, tx_bit[k] = in_bit[map()[k]] ^ scramble_bit[k], all frames of a
+    call in one launch.  Stateless.  run() takes and returns uint8 arrays of shape (n_frames, frame bytes)."""
+    _direction = _lib.RATEMATCH_TX
+
+    def __init__(self, n_coded, pattern=None, cols=0, perm=None, scramble=None, device=0):
+        super().__init__(n_coded, pattern, cols, perm, scramble, 0, device)
+
+    @property
+    def in_frame_bytes(self):
+        return lib().comms_ratematch_tx_in_frame_bytes(self._h)
+
+    @property
+    def out_frame_bytes(self):
+        return lib().comms_ratematch_tx_out_frame_bytes(self._h)
+
+    def run(self, frames):
+        x = np.ascontiguousarray(frames, dtype=np.uint8)
+        if x.size % self.in_frame_bytes:
+            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
+        n_frames = x.size // self.in_frame_bytes
+        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
+        check(lib().comms_ratematch_tx_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
+        return out
+
+    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
+        check(lib().comms_ratematch_tx_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+
+
+class RateDematchNode(_RateMatch):
+    """Receive rate matching between DeframeNode ("llr") and ViterbiNode, of the same frame format as RateMatchNode: records
+    of `record_llrs` f32 (0 = exactly n_tx_bits; the first n_tx_bits are used) -> records of n_coded f32, +0.0 at the punctured
+    positions and elsewhere the input value with its sign bit toggled where the scramble bit is 1: a ViterbiNode input as it
+    stands.  Stateless.  run() takes float32 and returns float32 (n_frames, n_coded)."""
+    _direction = _lib.RATEMATCH_RX
+
+    @property
+    def in_frame_bytes(self):
+        return lib().comms_ratematch_rx_in_frame_bytes(self._h)
+
+    @property
+    def out_frame_bytes(self):
+        return lib().comms_ratematch_rx_out_frame_bytes(self._h)
+
+    def run(self, llr):
+        x = np.ascontiguousarray(llr, dtype=np.float32)
+        per = self.in_frame_bytes // 4
+        if x.size % per:
+            raise ValueError("the input must hold whole records of in_frame_bytes / 4 values")
+        n_frames = x.size // per
+        out = np.zeros((n_frames, self.n_coded), np.float32)
+        check(lib().comms_ratematch_rx_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
+        return out
+
+    def run_dev(self, llr_ptr, n_frames, out_ptr, stream=0):
+        check(lib().comms_ratematch_rx_run_dev(self._h, llr_ptr, int(n_frames), out_ptr, stream))
+
+
 def qfilt_taps(n_taps, alpha, sam_per_sym):
     """util/math.rs:307-342 (f64, real); even n_taps is incremented."""
     out = np.empty(lib().comms_qfilt_len(int(n_taps)), np.float64)
@@ -1842,7 +1947,8 @@ class KernelTimer:
                 "comms_framesync_destroy": "comms_framesync_set_timer",
                 "comms_deframe_destroy": "comms_deframe_set_timer",
                 "comms_convenc_destroy": "comms_convenc_set_timer",
-                "comms_viterbi_destroy": "comms_viterbi_set_timer"}[node._destroy]
+                "comms_viterbi_destroy": "comms_viterbi_set_timer",
+                "comms_ratematch_destroy": "comms_ratematch_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

@@ -1372,6 +1372,90 @@ impl ViterbiNode {
     }
 }
 
+/// One frame format of the rate matching (comms_ratematch_*), the same on both sides of the link: `pattern` holds 0 / 1 per
+/// coded position and repeats (empty keeps everything), `cols` is the width of the pruned block interleaver over the kept bits
+/// (0, 1: none) or `perm` an explicit permutation of them (`cols` = 0 then), `scramble` one bit per transmitted bit packed LSB
+/// first (empty: none).
+#[derive(Clone, Default)]
+pub struct RateMatchFormat {
+    pub n_coded: usize,
+    pub pattern: Vec<u8>,
+    pub cols: usize,
+    pub perm: Vec<u32>,
+    pub scramble: Vec<u8>,
+}
+impl RateMatchFormat {
+    /// `Err(())`: what comms_ratematch_create refuses, or a `perm` / `scramble` that does not cover the transmitted bits.
+    fn create(&self, record_llrs: usize) -> Result<*mut comms_ratematch_t, ()> {
+        let kept = (0..self.n_coded).filter(|i| self.pattern.is_empty() || self.pattern[i % self.pattern.len()] != 0).count();
+        if (!self.perm.is_empty() && self.perm.len() != kept) || (!self.scramble.is_empty() && self.scramble.len() < (kept + 7) / 8) { return Err(()); }
+        let opt = |p: *const u8, empty: bool| if empty { ptr::null() } else { p };
+        let perm = if self.perm.is_empty() { ptr::null() } else { self.perm.as_ptr() };
+        let mut h = ptr::null_mut();
+        let st = unsafe {
+            comms_ratematch_create(self.n_coded, opt(self.pattern.as_ptr(), self.pattern.is_empty()), self.pattern.len(), self.cols, perm,
+                                   opt(self.scramble.as_ptr(), self.scramble.is_empty()) as *const c_void, record_llrs, 0, &mut h)
+        };
+        if st == COMMS_OK { Ok(h) } else { Err(()) }
+    }
+}
+
+/// Transmit rate matching (an additional node): takes `ConvEncoderNode`'s records of `n_coded` packed bits and sends records of
+/// `n_tx_bits()` bits -- selected, permuted and whitened -- that the bit-input modulators take as they stand.  Stateless.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct RateMatchNode {
+    pub input: NodeReceiver<Vec<u8>>,
+    h: *mut comms_ratematch_t,
+    pub output: NodeSender<Vec<u8>>,
+}
+handle_node!(RateMatchNode, comms_ratematch_destroy);
+impl RateMatchNode {
+    pub fn new(format: &RateMatchFormat) -> Result<Self, ()> {
+        Ok(RateMatchNode { input: Default::default(), h: format.create(0)?, output: Default::default() })
+    }
+    pub fn n_tx_bits(&self) -> usize { unsafe { comms_ratematch_n_tx_bits(self.h) } }
+    pub fn in_frame_bytes(&self) -> usize { unsafe { comms_ratematch_tx_in_frame_bytes(self.h) } }
+    pub fn out_frame_bytes(&self) -> usize { unsafe { comms_ratematch_tx_out_frame_bytes(self.h) } }
+    pub fn run(&mut self, records: &[u8]) -> Result<Vec<u8>, NodeError> {
+        let fin = self.in_frame_bytes();
+        if fin == 0 || records.len() % fin != 0 { return Err(NodeError::DataError); }
+        let n_frames = records.len() / fin;
+        let mut out = vec![0u8; n_frames * self.out_frame_bytes()];
+        let st = unsafe { comms_ratematch_tx_run(self.h, records.as_ptr() as *const c_void, n_frames, out.as_mut_ptr() as *mut c_void) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
+/// Receive rate matching (an additional node): takes `DeframeNode`'s `COMMS_SYM_LLR` message (records of at least
+/// `n_tx_bits()` f32 values) and sends records of `n_coded` values under the same headers, +0.0 at the punctured positions:
+/// `ViterbiNode`'s input with `record_llrs` = 0.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct RateDematchNode {
+    pub input: NodeReceiver<Frames>,
+    h: *mut comms_ratematch_t,
+    pub output: NodeSender<Frames>,
+}
+handle_node!(RateDematchNode, comms_ratematch_destroy);
+impl RateDematchNode {
+    /// `record_llrs`: values per input record, 0 = exactly the transmitted bits.
+    pub fn new(format: &RateMatchFormat, record_llrs: usize) -> Result<Self, ()> {
+        Ok(RateDematchNode { input: Default::default(), h: format.create(record_llrs)?, output: Default::default() })
+    }
+    pub fn n_tx_bits(&self) -> usize { unsafe { comms_ratematch_n_tx_bits(self.h) } }
+    pub fn in_frame_bytes(&self) -> usize { unsafe { comms_ratematch_rx_in_frame_bytes(self.h) } }
+    pub fn out_frame_bytes(&self) -> usize { unsafe { comms_ratematch_rx_out_frame_bytes(self.h) } }
+    pub fn run(&mut self, frames: &Frames) -> Result<Frames, NodeError> {
+        let n_frames = frames.headers.len();
+        if frames.frame_bytes != self.in_frame_bytes() || frames.data.len() < n_frames * frames.frame_bytes { return Err(NodeError::DataError); }
+        let frame_bytes = self.out_frame_bytes();
+        let mut out = Frames { data: vec![0u8; n_frames * frame_bytes], headers: frames.headers.clone(), frame_bytes };
+        let st = unsafe { comms_ratematch_rx_run(self.h, frames.data.as_ptr() as *const f32, n_frames, out.data.as_mut_ptr() as *mut f32) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
 /// demodulation/nco.rs:118-133 in block form: a vector of phase errors per message.
 #[derive(Node)]
 #[pass_by_ref]
