@@ -21,6 +21,7 @@ SYM_LLR = 3                     # comms_deframe_set_output_format only
 DEFRAME_NORMALISE = 1           # comms_deframe_create: flags
 CONV_TERMINATED, CONV_TRUNCATED = 0, 1  # comms_convenc_create, comms_viterbi_create: flags
 RATEMATCH_TX, RATEMATCH_RX = 0, 1  # comms_ratematch_get_kernel: direction
+CRC_ATTACH, CRC_CHECK = 0, 1    # comms_crc_get_kernel: direction
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 RESAMPLE_F32, RESAMPLE_C32 = 4, 8  # comms_resample_create: bytes per sample
 CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR = 0, 1  # comms_channelizer_create: layout
@@ -336,6 +337,14 @@ _PROTOS = {
     "comms_ratematch_get_kernel": [_vp, _i32, _sz, C.c_char_p, _sz],
     "comms_ratematch_set_timer": [_vp, _vp],
     "comms_ratematch_destroy": [_vp],
+    "comms_crc_create": [_i32, _u32, _u32, _u32, _sz, _i32, _pp],
+    "comms_crc_attach_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_crc_check_run_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
+    "comms_crc_attach_run": [_vp, _vp, _sz, _vp],
+    "comms_crc_check_run": [_vp, _vp, _sz, _vp, _vp, _vp, _psz],
+    "comms_crc_get_kernel": [_vp, _i32, _sz, C.c_char_p, _sz],
+    "comms_crc_set_timer": [_vp, _vp],
+    "comms_crc_destroy": [_vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],
@@ -363,6 +372,8 @@ _OTHER = {
     "comms_ratematch_tx_out_frame_bytes": (_sz, [_vp]),
     "comms_ratematch_rx_in_frame_bytes": (_sz, [_vp]),
     "comms_ratematch_rx_out_frame_bytes": (_sz, [_vp]),
+    "comms_crc_payload_frame_bytes": (_sz, [_vp]),
+    "comms_crc_coded_frame_bytes": (_sz, [_vp]),
     "comms_buf_device": (_i32, [_vp]),
     "comms_synth_iq_host": (None, [_vp, _sz, _u64, _u64]),
 }

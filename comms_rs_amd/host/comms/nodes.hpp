@@ -1588,6 +1588,108 @@ public:
     Result<FramesDev> run(const FramesDev& in) { return dematch_dev(in, *this); }
 };
 
+// Frame check (comms_crc_*; additional nodes): a CRC of 1 ... 32 bits over frames of fixed length, the same description on both
+// sides of the link.  One description per direction, two shells each.
+struct CrcSpec {
+    int width;              // W, 1 ... 32
+    uint32_t poly;          // normal form, without the x^W term
+    uint32_t init = 0;
+    uint32_t xorout = 0;
+    size_t n_payload_bits;  // T, with T + W <= 2^16
+};
+struct CrcHandle {
+    CrcHandle(const char* who, const CrcSpec& f, int device)
+        : h_(create<decltype(h_)>(who, comms_crc_create, static_cast<int32_t>(f.width), f.poly, f.init, f.xorout, f.n_payload_bits, device)) {}
+    size_t payload_frame_bytes() const { return comms_crc_payload_frame_bytes(h_.get()); }
+    size_t coded_frame_bytes() const { return comms_crc_coded_frame_bytes(h_.get()); }
+
+protected:
+    std::string kernel_of(int32_t direction, size_t n_frames) const {
+        return kernel_name([direction](const comms_crc_t* h, size_t n, char* name, size_t len) { return comms_crc_get_kernel(h, direction, n, name, len); },
+                           h_.get(), n_frames);
+    }
+    Owned<comms_crc_t, comms_crc_destroy> h_;
+};
+
+// Attach: a message is whole records of payload bits (in_frame_bytes() each), the output the records of payload + CRC bits
+// (out_frame_bytes() each) -- ConvEncoderNode's input with n_info_bits = T + W as they stand.
+struct CrcAttachOp : CrcHandle {
+    using In = uint8_t;
+    using Out = uint8_t;
+    CrcAttachOp(const char* who, const CrcSpec& format, int device) : CrcHandle(who, format, device) {}
+    size_t in_frame_bytes() const { return payload_frame_bytes(); }
+    size_t out_frame_bytes() const { return coded_frame_bytes(); }
+    std::string kernel(size_t n_frames) const { return kernel_of(COMMS_CRC_ATTACH, n_frames); }  // "crc_attach_kernel ..."
+
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const {
+        if (n % in_frame_bytes()) return COMMS_ERR_ARG;
+        m = n / in_frame_bytes() * out_frame_bytes();
+        return COMMS_OK;
+    }
+    comms_status_t launch(const uint8_t* in, size_t n, uint8_t* out) { return comms_crc_attach_run(h_.get(), in, n / in_frame_bytes(), out); }
+    comms_status_t launch_dev(const uint8_t* in, size_t n, uint8_t* out, void* s) {
+        return comms_crc_attach_run_dev(h_.get(), in, n / in_frame_bytes(), out, s);
+    }
+};
+class CrcAttachNode : public HostNode<CrcAttachNode, CrcAttachOp> {
+public:
+    explicit CrcAttachNode(const CrcSpec& format, int device = 0) : HostNode("CrcAttachNode::new", format, device) {}
+};
+class CrcAttachNodeDev : public DevNode<CrcAttachNodeDev, CrcAttachOp> {
+public:
+    explicit CrcAttachNodeDev(const CrcSpec& format, int device = 0) : DevNode(device, "CrcAttachNodeDev::new", format, device) {}
+};
+
+// Check: takes ViterbiNode's message (records of T + W decoded bits under the deframer's headers) and sends the payload records
+// under the same headers with one pass flag per frame: 1 where the recomputed CRC equals the received bits.  A message without
+// frames passes through empty.
+template <class Store, class Flags>
+struct CheckedOf {
+    FramesOf<Store> frames;   // the payload records, frame_bytes = out_frame_bytes()
+    Flags passed;             // int32 per frame
+    size_t size() const { return frames.size(); }
+};
+struct CrcCheckOp : CrcHandle {
+    using Frames = DeframeOp::Frames;
+    using FramesDev = DeframeOp::FramesDev;
+    using Checked = CheckedOf<std::vector<uint8_t>, std::vector<int32_t>>;
+    using CheckedDev = CheckedOf<DeviceBuf<uint8_t>, DeviceBuf<int32_t>>;
+    CrcCheckOp(const char* who, const CrcSpec& format, int device) : CrcHandle(who, format, device) {}
+    size_t in_frame_bytes() const { return coded_frame_bytes(); }
+    size_t out_frame_bytes() const { return payload_frame_bytes(); }
+    std::string kernel(size_t n_frames) const { return kernel_of(COMMS_CRC_CHECK, n_frames); }  // "crc_check_kernel ..."
+
+protected:
+    Result<Checked> check(const Frames& in) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        Checked out{{std::vector<uint8_t>(in.size() * out_frame_bytes()), in.headers, out_frame_bytes()}, std::vector<int32_t>(in.size())};
+        return ok_or(comms_crc_check_run(h_.get(), in.data.data(), in.size(), out.frames.data.data(), out.passed.data(), nullptr, nullptr), out);
+    }
+    Result<CheckedDev> check_dev(const FramesDev& in, const DevStream& on) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        const size_t n = in.size();
+        CheckedDev out{{DeviceBuf<uint8_t>(n ? n * out_frame_bytes() : 8, on.device()), in.headers, out_frame_bytes()},
+                       DeviceBuf<int32_t>(n ? n : 2, on.device())};
+        comms_status_t st = on.submit(in.data, out.frames.data, [&](void* s) {
+            return comms_crc_check_run_dev(h_.get(), in.data.ptr(), n, out.frames.data.ptr(), out.passed.ptr(), nullptr, nullptr, s);
+        });
+        if (st == COMMS_OK) st = comms_buf_record_ready(out.passed.raw(), on.get());   // the same launch wrote the flags
+        return ok_or(st, out);
+    }
+};
+class CrcCheckNode : public DeriveNode<CrcCheckNode>, public Ports<CrcCheckOp::Frames, CrcCheckOp::Checked>, public CrcCheckOp {
+public:
+    explicit CrcCheckNode(const CrcSpec& format, int device = 0) : CrcCheckOp("CrcCheckNode::new", format, device) {}
+    Result<Checked> run(const Frames& in) { return check(in); }
+};
+// on device-resident messages: ViterbiNodeDev's records in, the payload records and the flags in DeviceBufs out (headers on the host)
+class CrcCheckNodeDev : public DeriveNode<CrcCheckNodeDev>, public Ports<CrcCheckOp::FramesDev, CrcCheckOp::CheckedDev>, public OnStream<CrcCheckOp> {
+public:
+    explicit CrcCheckNodeDev(const CrcSpec& format, int device = 0) : OnStream(device, "CrcCheckNodeDev::new", format, device) {}
+    Result<CheckedDev> run(const FramesDev& in) { return check_dev(in, *this); }
+};
+
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)

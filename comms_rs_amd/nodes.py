@@ -1871,6 +1871,105 @@ class RateDematchNode(_RateMatch):
         check(lib().comms_ratematch_rx_run_dev(self._h, llr_ptr, int(n_frames), out_ptr, stream))
 
 
+# ------------------------------------------------------------------ frame check (CRC)
+class _Crc(_Handle):
+    """One frame check of comms_crc_*: a `width`-bit CRC (1 ... 32) with polynomial `poly` (normal form, no x^width term),
+    register `init` and final `xorout`, no reflection, over frames of `n_payload_bits` bits; the CRC follows the payload with
+    its x^(width-1) coefficient first.  Records are packed LSB first, so (32, 0x04C11DB7, 0xFFFFFFFF, 0xFFFFFFFF) is the
+    Ethernet FCS."""
+    _destroy = "comms_crc_destroy"
+    _direction = None
+
+    def __init__(self, width, poly, init, xorout, n_payload_bits, device=0):
+        super().__init__()
+        self.width, self.n_payload_bits = int(width), int(n_payload_bits)
+        for v in (poly, init, xorout):
+            if not 0 <= int(v) < (1 << 32):
+                raise ValueError("poly, init and xorout are unsigned 32-bit values")
+        check(lib().comms_crc_create(self.width, int(poly), int(init), int(xorout), self.n_payload_bits, device, C.byref(self._h)))
+
+    @property
+    def payload_frame_bytes(self):
+        return lib().comms_crc_payload_frame_bytes(self._h)
+
+    @property
+    def coded_frame_bytes(self):
+        return lib().comms_crc_coded_frame_bytes(self._h)
+
+    def kernel(self, n_frames):
+        """ "crc_attach_kernel | crc_check_kernel wg=.. group=.. rounds=.. width=.. words=.. frames=.. grid=.. max_grid=.. lds=0"
+        for a call on n_frames frames."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_crc_get_kernel(self._h, self._direction, int(n_frames), buf, 240))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        check(lib().comms_crc_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+    def _frames(self, frames):
+        x = np.ascontiguousarray(frames, dtype=np.uint8)
+        if x.size % self.in_frame_bytes:
+            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
+        return x, x.size // self.in_frame_bytes
+
+
+class CrcAttachNode(_Crc):
+    """Appends the CRC in front of ConvEncoderNode: frame-major records of n_payload_bits packed bits -> records of
+    n_payload_bits + width bits, all frames of a call in one launch.  Stateless.  run() takes and returns uint8 arrays of shape
+    (n_frames, frame bytes)."""
+    _direction = _lib.CRC_ATTACH
+
+    @property
+    def in_frame_bytes(self):
+        return self.payload_frame_bytes
+
+    @property
+    def out_frame_bytes(self):
+        return self.coded_frame_bytes
+
+    def run(self, frames):
+        x, n_frames = self._frames(frames)
+        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
+        check(lib().comms_crc_attach_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
+        return out
+
+    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
+        check(lib().comms_crc_attach_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+
+
+class CrcCheckNode(_Crc):
+    """Checks the CRC behind ViterbiNode, of the same format as CrcAttachNode: records of n_payload_bits + width bits (the
+    decoder's records with n_info_bits = n_payload_bits + width) -> the payload records, one pass flag per frame (int32, 1 =
+    the recomputed CRC equals the received bits) and the recomputed CRC (uint32), all frames of a call in one launch.
+    Stateless.  run() returns (payload, passed, crc); n_failed holds the failed frames of the last run().  run_dev takes a
+    pointer per output, each may be None; the launch ADDS the call's failed frames to the uint32 at n_failed_ptr."""
+    _direction = _lib.CRC_CHECK
+    n_failed = 0
+
+    @property
+    def in_frame_bytes(self):
+        return self.coded_frame_bytes
+
+    @property
+    def out_frame_bytes(self):
+        return self.payload_frame_bytes
+
+    def run(self, frames):
+        x, n_frames = self._frames(frames)
+        payload = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
+        passed = np.zeros(n_frames, np.int32)
+        crc = np.zeros(n_frames, np.uint32)
+        failed = C.c_size_t(0)
+        p = (lambda a: _ptr(a) if n_frames else None)
+        check(lib().comms_crc_check_run(self._h, p(x), n_frames, p(payload), p(passed), p(crc), C.byref(failed)))
+        self.n_failed = failed.value
+        return payload, passed, crc
+
+    def run_dev(self, in_ptr, n_frames, payload_ptr=None, pass_ptr=None, crc_ptr=None, n_failed_ptr=None, stream=0):
+        check(lib().comms_crc_check_run_dev(self._h, in_ptr, int(n_frames), payload_ptr, pass_ptr, crc_ptr, n_failed_ptr, stream))
+
+
 def qfilt_taps(n_taps, alpha, sam_per_sym):
     """util/math.rs:307-342 (f64, real); even n_taps is incremented."""
     out = np.empty(lib().comms_qfilt_len(int(n_taps)), np.float64)
@@ -1948,7 +2047,8 @@ class KernelTimer:
                 "comms_deframe_destroy": "comms_deframe_set_timer",
                 "comms_convenc_destroy": "comms_convenc_set_timer",
                 "comms_viterbi_destroy": "comms_viterbi_set_timer",
-                "comms_ratematch_destroy": "comms_ratematch_set_timer"}[node._destroy]
+                "comms_ratematch_destroy": "comms_ratematch_set_timer",
+                "comms_crc_destroy": "comms_crc_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

@@ -1456,6 +1456,89 @@ impl RateDematchNode {
     }
 }
 
+/// One frame check (comms_crc_*), the same on both sides of the link: a `width`-bit CRC (1 ..= 32) with polynomial `poly` in
+/// normal form without the x^width term, register `init` and final `xorout`, no reflection, over frames of `n_payload_bits`
+/// bits.  Records are packed LSB first: (32, 0x04C11DB7, 0xFFFFFFFF, 0xFFFFFFFF) is the Ethernet FCS.
+#[derive(Clone, Copy, Default)]
+pub struct CrcSpec {
+    pub width: i32,
+    pub poly: u32,
+    pub init: u32,
+    pub xorout: u32,
+    pub n_payload_bits: usize,
+}
+impl CrcSpec {
+    /// `Err(())`: what comms_crc_create refuses.
+    fn create(&self) -> Result<*mut comms_crc_t, ()> {
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_crc_create(self.width, self.poly, self.init, self.xorout, self.n_payload_bits, 0, &mut h) };
+        if st == COMMS_OK { Ok(h) } else { Err(()) }
+    }
+}
+
+/// Appends the CRC (an additional node), in front of `ConvEncoderNode`: takes records of `n_payload_bits` packed bits and sends
+/// records of `n_payload_bits + width` bits.  Stateless.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct CrcAttachNode {
+    pub input: NodeReceiver<Vec<u8>>,
+    h: *mut comms_crc_t,
+    pub output: NodeSender<Vec<u8>>,
+}
+handle_node!(CrcAttachNode, comms_crc_destroy);
+impl CrcAttachNode {
+    pub fn new(spec: &CrcSpec) -> Result<Self, ()> {
+        Ok(CrcAttachNode { input: Default::default(), h: spec.create()?, output: Default::default() })
+    }
+    pub fn in_frame_bytes(&self) -> usize { unsafe { comms_crc_payload_frame_bytes(self.h) } }
+    pub fn out_frame_bytes(&self) -> usize { unsafe { comms_crc_coded_frame_bytes(self.h) } }
+    pub fn run(&mut self, records: &[u8]) -> Result<Vec<u8>, NodeError> {
+        let fin = self.in_frame_bytes();
+        if fin == 0 || records.len() % fin != 0 { return Err(NodeError::DataError); }
+        let n_frames = records.len() / fin;
+        let mut out = vec![0u8; n_frames * self.out_frame_bytes()];
+        let st = unsafe { comms_crc_attach_run(self.h, records.as_ptr() as *const c_void, n_frames, out.as_mut_ptr() as *mut c_void) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
+/// What `CrcCheckNode` sends: the payload records and, per frame, whether the recomputed CRC equals the received bits.
+#[derive(Clone, Default)]
+pub struct CheckedFrames {
+    pub payload: Vec<u8>,
+    pub passed: Vec<i32>,
+    pub n_failed: usize,
+}
+
+/// Checks the CRC (an additional node), behind `ViterbiNode` with `n_info_bits = n_payload_bits + width`: takes the decoder's
+/// records and sends the payload records with one pass flag per frame.  Stateless.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct CrcCheckNode {
+    pub input: NodeReceiver<Vec<u8>>,
+    h: *mut comms_crc_t,
+    pub output: NodeSender<CheckedFrames>,
+}
+handle_node!(CrcCheckNode, comms_crc_destroy);
+impl CrcCheckNode {
+    pub fn new(spec: &CrcSpec) -> Result<Self, ()> {
+        Ok(CrcCheckNode { input: Default::default(), h: spec.create()?, output: Default::default() })
+    }
+    pub fn in_frame_bytes(&self) -> usize { unsafe { comms_crc_coded_frame_bytes(self.h) } }
+    pub fn out_frame_bytes(&self) -> usize { unsafe { comms_crc_payload_frame_bytes(self.h) } }
+    pub fn run(&mut self, records: &[u8]) -> Result<CheckedFrames, NodeError> {
+        let fin = self.in_frame_bytes();
+        if fin == 0 || records.len() % fin != 0 { return Err(NodeError::DataError); }
+        let n_frames = records.len() / fin;
+        let mut out = CheckedFrames { payload: vec![0u8; n_frames * self.out_frame_bytes()], passed: vec![0i32; n_frames], n_failed: 0 };
+        let st = unsafe {
+            comms_crc_check_run(self.h, records.as_ptr() as *const c_void, n_frames, out.payload.as_mut_ptr() as *mut c_void,
+                                out.passed.as_mut_ptr(), ptr::null_mut(), &mut out.n_failed)
+        };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
 /// demodulation/nco.rs:118-133 in block form: a vector of phase errors per message.
 #[derive(Node)]
 #[pass_by_ref]
