@@ -803,10 +803,15 @@ inline int plan_stride(int R, int len, int lanes = 32) {
 
 constexpr int kNumCU = 256;  // MI355X: 8 XCD x 32 CU
 // Grid cap of a persistent kernel that uses `lds` bytes per workgroup: the workgroups the chip holds at once, at most
-// eight per CU and as many as fit the CU's 160 KiB of LDS (a kernel below 1 KiB counts as 1 KiB)
+// eight per CU and as many as fit the CU's 160 KiB of LDS (a kernel below 1 KiB counts as 1 KiB).  The diagnostic build's
+// COMMS_GRID_CAP = c > 0 lowers it to at most c, so that every persistent loop makes many passes over a small call
+// (tests/test_gpu_small_grids.py); it is read at each call: a handle takes its cap at create, one process makes handles
+// under several.
 inline unsigned resident_workgroups(size_t lds) {
     const size_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : lds);
-    return static_cast<unsigned>(kNumCU * (per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu));
+    const unsigned chip = static_cast<unsigned>(kNumCU * (per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu));
+    const int cap = diag_knob("COMMS_GRID_CAP", 0);
+    return cap > 0 && static_cast<unsigned>(cap) < chip ? static_cast<unsigned>(cap) : chip;
 }
 
 // Mixer phase bookkeeping shared by the mixer node and the fused chain: phases are

@@ -444,8 +444,10 @@ comms_status_t comms_resample_get_kernel(const comms_resample_t* h, size_t n, ch
         else
             std::snprintf(name, name_len, "series: upsample_kernel + real_to_c32_kernel + %s + c32_re_kernel + decimate_kernel", fir);
     } else {
-        std::snprintf(name, name_len, "resample_kernel<%s, %s> tile=%d lds=%zu", h->elem == COMMS_RESAMPLE_C32 ? "c32" : "f32",
-                      h->tab_lds ? "taps in LDS" : "taps in global memory", h->TO, h->lds);
+        const size_t tiles = (resample_out_len(n, h->up, h->down) + h->TO - 1) / h->TO;
+        std::snprintf(name, name_len, "resample_kernel<%s, %s> tile=%d lds=%zu tiles=%zu grid=%zu max_grid=%u",
+                      h->elem == COMMS_RESAMPLE_C32 ? "c32" : "f32", h->tab_lds ? "taps in LDS" : "taps in global memory", h->TO, h->lds, tiles,
+                      tiles < h->max_grid ? tiles : static_cast<size_t>(h->max_grid), h->max_grid);
     }
     return COMMS_OK;
 }

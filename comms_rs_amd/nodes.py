@@ -789,7 +789,8 @@ class ResampleNode(_Handle):
         return m.value
 
     def kernel(self, n):
-        """What a batch of n samples is run by: "resample_kernel<..> tile=.. lds=..", or "series: ..." (the launches)."""
+        """What a batch of n samples is run by: "resample_kernel<..> tile=.. lds=.. tiles=.. grid=.. max_grid=..", or "series: ..."
+        (the launches)."""
         buf = C.create_string_buffer(200)
         check(lib().comms_resample_get_kernel(self._h, n, buf, 200))
         return buf.value.decode()

@@ -1,0 +1,474 @@
+"""Persistent kernels on capped grids: the case table of tests/test_gpu_small_grids.py and each node's pass count restated from
+its launch code (no GPU here; tests/test_grid_cases.py holds the table to the rules below).
+
+The diagnostic build reads COMMS_GRID_CAP in resident_workgroups() (csrc/common.hpp): a handle made under cap c has
+max_grid = c, so a call of a few tens of thousands of samples makes every workgroup, wave or lane walk many passes.  Every
+grid formula used here is listed in ANCHORS with the source text it restates.
+
+A case is Case(family, kernel, name, fmt, size): `fmt` the node's format (a dict), `size(cap)` the call's size in the unit of
+its family -- samples (syncest, framesync), tiles (symsync, resample, channelizer; their tile is planned per handle and read
+from kernel() on the device), frames (the rest).  walk(case, cap) restates the launch: Walk(total, unit, grid, passes), `total`
+the items of the call, `unit` the items one workgroup takes per pass; the busiest workgroup, wave or lane makes `passes`
+passes (four or more: five in most cases, up to 17).  The rules: passes >= MIN_PASSES, grid == cap (the channelizer: its own formula's grid), total no multiple of
+grid * unit (a ragged last pass), and no case moves more than MAX_BYTES."""
+import collections
+import functools
+
+import numpy as np
+
+import crc_ref
+import deframe_ref as dr
+import framesync_ref as fr
+import ratematch_ref as rr
+import rx_ref
+import syncest_ref
+import viterbi_ref as vr
+
+CAPS = (1, 3, 7)         # odd, no powers of two: the grid-dependent steps take residues they never take on the full chip
+MIN_PASSES = 4
+MAX_BYTES = 4 << 20      # input + output of one call
+
+CSRC = "comms_rs_amd/csrc/"
+ANCHORS = [
+    (CSRC + "common.hpp", 'const int cap = diag_knob("COMMS_GRID_CAP", 0);'),
+    (CSRC + "common.hpp", "return cap > 0 && static_cast<unsigned>(cap) < chip ? static_cast<unsigned>(cap) : chip;"),
+    (CSRC + "syncest.hip", "constexpr int SE_TILE = SE_WG * SE_OPL;     // outputs per tile"),
+    (CSRC + "syncest.hip", "return tiles < h->max_grid ? tiles : h->max_grid;"),
+    (CSRC + "syncest.hip", "const int mt_step = static_cast<int>((static_cast<unsigned long long>(gridDim.x) * SE_TILE) % static_cast<unsigned>(n2));"),
+    (CSRC + "framesync.hip", "return tiles < h->max_grid ? tiles : h->max_grid;"),
+    (CSRC + "framesync.hip", "for (size_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {"),
+    (CSRC + "symsync.hip", "for (int TO = 1024; TO >="),
+    (CSRC + "symsync.hip", "const unsigned grid = tiles < h->max_grid ? static_cast<unsigned>(tiles) : h->max_grid;"),
+    (CSRC + "resample.hip", "for (size_t TO = 1024; TO >="),
+    (CSRC + "resample.hip", "const unsigned grid = tiles < h->max_grid ? static_cast<unsigned>(tiles) : h->max_grid;"),
+    (CSRC + "resample.hip", "const unsigned long long step = static_cast<unsigned long long>(grid) * h->TO * h->down;"),
+    (CSRC + "channelizer.hip", "const size_t per = (tiles + h->max_grid - 1) / h->max_grid;"),
+    (CSRC + "channelizer.hip", "return static_cast<unsigned>((tiles + per1 - 1) / per1);"),
+    (CSRC + "channelizer.hip", "// F = 2048 / M frames per tile, halved while"),
+    (CSRC + "deframe.hip", "size_t deframe_lanes(const comms_deframe* h, size_t n_frames) { return (n_frames * lanes_per_frame(h) + 63) / 64 * 64; }"),
+    (CSRC + "deframe.hip", "const size_t b = (deframe_lanes(h, n_frames) + DF_WG - 1) / DF_WG;"),
+    (CSRC + "deframe.hip", "const unsigned dq = stride / a.lpf, dr = stride % a.lpf;"),
+    (CSRC + "convcode.hip", "const size_t b = (n_frames * (enc_out_bytes(h) / 4) + CC_WG - 1) / CC_WG;"),
+    (CSRC + "convcode.hip", "const size_t b = (n_frames + VT_WAVES - 1) / VT_WAVES;"),
+    (CSRC + "convcode.hip", "constexpr unsigned VT_LDS_STEPS = 2048;"),
+    (CSRC + "convcode.hip", "h->in_lds = c.steps <= VT_LDS_STEPS;"),
+    (CSRC + "ratematch.hip", "constexpr unsigned RM_LDS_SEAM = 2048;"),
+    (CSRC + "ratematch.hip", "return clamp_grid((n_frames * (tx_out_bytes(h) / 4) + RM_WG - 1) / RM_WG, h->tx_max_grid);"),
+    (CSRC + "ratematch.hip", "const size_t per = h->rx_lds && h->n_coded > RM_WG ? h->n_coded : RM_WG;"),
+    (CSRC + "ratematch.hip", "h->tx_lds = h->n_tx <= RM_LDS_SEAM ?"),
+    (CSRC + "ratematch.hip", "h->rx_lds = h->n_coded <= RM_LDS_SEAM ?"),
+    (CSRC + "ratematch.hip", "if (pos >= per) {"),
+    (CSRC + "crc.hip", "const size_t fpw = 64 / h->plan.group, items = (n_frames + fpw - 1) / fpw, b = (items + CRC_WAVES - 1) / CRC_WAVES;"),
+]
+
+WG = 256                 # lanes per workgroup of every kernel here
+SE_TILE = FS_TILE = 2048
+TILE_MAX = 1024          # symsync, resample: the largest tile their planners try
+CHZ_TILE_POINTS = 2048   # channelizer: F = 2048 / M frames per tile at most
+
+Case = collections.namedtuple("Case", "family kernel name fmt size")
+Walk = collections.namedtuple("Walk", "total unit grid passes")
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def _capped(blocks, cap):
+    return max(1, min(blocks, cap))
+
+
+def _walk(total, unit, grid):
+    return Walk(total, unit, grid, cdiv(total, grid * unit))
+
+
+def smallest(walk_of, cap):
+    """The smallest size whose launch walk_of(size, cap) fills the capped grid, makes more than MIN_PASSES passes' worth of
+    items and ends on a ragged pass.  The residue of the items modulo cap * unit repeats within cap * unit sizes, so where none of
+    that many fitting sizes is ragged none ever is (frames of 256 or 2048 items at cap 1), and the smallest fitting size is
+    returned: never_ragged() names those cases."""
+    fits, size = [], 0
+    while not fits or size < fits[0] + cap * WG:
+        size += 1
+        assert size < 1 << 20, "no size fills a grid of %d" % cap
+        w = walk_of(size, cap)
+        if w.grid == cap and w.total > MIN_PASSES * cap * w.unit:
+            if w.total % (cap * w.unit) != 0:
+                return size
+            fits.append(size)
+    return fits[0]
+
+
+# ---------------------------------------------------------------- the launch of each family, restated
+def tiles_walk(tiles, cap):
+    """syncest, framesync, symsync, resample: grid = min(tiles, max_grid), tile t, t + grid, ..."""
+    return _walk(tiles, 1, _capped(tiles, cap))
+
+
+def channelizer_walk(tiles, cap):
+    """chz_grid: per = ceil(tiles / max_grid) consecutive tiles per workgroup, grid = ceil(tiles / per)."""
+    per = max(cdiv(tiles, cap), 1)
+    return Walk(tiles, 1, cdiv(tiles, per), per)
+
+
+def deframe_lpf(F, K, fmt):
+    """lanes_per_frame: the record's words times the 32 / K lanes of a word for BITS, the symbols otherwise."""
+    if fmt == "bits":
+        return cdiv(cdiv(F * K, 8), 4) * (32 // K)
+    return F
+
+
+def deframe_walk(frames, cap, lpf):
+    """the flattened (frame, lane) space rounded up to whole waves"""
+    lanes = cdiv(frames * lpf, 64) * 64
+    return _walk(lanes, WG, _capped(cdiv(lanes, WG), cap))
+
+
+def enc_words(K, n, T, terminated=True):
+    return vr.record_bytes(n * vr.n_steps(T, K, terminated)) // 4
+
+
+def encoder_walk(frames, cap, words):
+    return _walk(frames * words, WG, _capped(cdiv(frames * words, WG), cap))
+
+
+def viterbi_walk(frames, cap):
+    """one wave per frame, VT_WAVES = 4 per workgroup"""
+    return _walk(frames, vr.WAVES, _capped(cdiv(frames, vr.WAVES), cap))
+
+
+def rm_tx_words(n_tx):
+    return rr.record_bytes(n_tx) // 4
+
+
+def rm_tx_walk(frames, cap, n_tx):
+    items = frames * rm_tx_words(n_tx)
+    return _walk(items, WG, _capped(cdiv(items, WG), cap))
+
+
+def rm_rx_walk(frames, cap, n_coded):
+    per = n_coded if n_coded <= rr.LDS_SEAM and n_coded > WG else WG
+    items = frames * n_coded
+    return _walk(items, WG, _capped(cdiv(items, per), cap))
+
+
+def crc_items_walk(items, cap):
+    """CRC_WAVES = 4 wave-items per workgroup and pass"""
+    return _walk(items, 4, _capped(cdiv(items, 4), cap))
+
+
+def crc_walk(frames, cap, T):
+    """a wave-item is 64 / group frames"""
+    return crc_items_walk(cdiv(frames, 64 // crc_ref.group_of(T)), cap)
+
+
+def rm_regime(stride, per):
+    """RmWalk and the deframer's (dq, dr): which of the walk's forms a stride takes over frames of `per` items."""
+    sf, sp = divmod(stride, per)
+    if sp == 0:
+        return "stride_pos=0"
+    return "stride_frames=0" if sf == 0 else "stride_frames>=1"
+
+
+def rm_walk_positions(first, stride, per, items, strict=False):
+    """RmWalk from item `first`: [(frame, pos)] of every item the lane takes, by the kernel's additions (strict: with `>` for
+    `>=`, the walk that leaves a frame's positions on equality)."""
+    sf, sp = divmod(stride, per)
+    frame, pos = divmod(first, per)
+    out, i = [], first
+    while i < items:
+        out.append((frame, pos))
+        frame += sf
+        pos += sp
+        if pos > per or (pos == per and not strict):
+            pos -= per
+            frame += 1
+        i += stride
+    return out
+
+
+def rm_carries(first, stride, per, items):
+    """The carries of a lane's steps (True where `pos >= per` fired), and whether one of them fired on equality."""
+    sp = stride % per
+    pos = first % per
+    carries, on_equal, i = [], False, first + stride
+    while i < items:
+        pos += sp
+        c = pos >= per
+        on_equal |= pos == per
+        if c:
+            pos -= per
+        carries.append(c)
+        i += stride
+    return carries, on_equal
+
+
+# ---------------------------------------------------------------- the table
+P34 = rr.PATTERNS["3/4"]
+RM_COLS = 17
+
+
+@functools.lru_cache(maxsize=None)
+def n_coded_for(n_tx):
+    """The smallest N whose rate-3/4 puncturing keeps n_tx bits."""
+    return next(N for N in range(n_tx, 2 * n_tx + 2) if rr.n_tx_bits(N, P34) == n_tx)
+
+
+def _syncest_len(cap):
+    return 4 * cap * SE_TILE + 1031
+
+
+def _framesync_len(cap):
+    return 4 * cap * FS_TILE + 777
+
+
+def _channelizer_tiles(cap):
+    return 5 * cap - 1
+
+
+def _syncest():
+    # tiles = 4 cap + 1, the last one 1031 samples; n2 = 2 n: 8 and 16 divide cap * 2048, 6 and 10 do not
+    return [Case("syncest", "syncest.hip", "n%d-d%d" % (n, d), dict(n=n, d=d, alpha=0.25), _syncest_len)
+            for n, d in ((4, 4), (8, 8), (3, 5), (5, 4))]
+
+
+FS_WORDS = {13: ("barker13", 0.8, 12), 64: ("qpsk64", 0.5, 63)}
+
+
+def _framesync():
+    return [Case("framesync", "framesync.hip", "P%d" % P, dict(P=P, word=w, thr=thr, G=G), _framesync_len)
+            for P, (w, thr, G) in FS_WORDS.items()]
+
+
+def framesync_positions(P, G, cap):
+    """Where the words are planted.  Position k of a single call is decided as the kernel's position k + P + G - 1, so the
+    first and last decided positions of tile t are k = t TILE - (P + G - 1) and that + TILE - 1; a word that starts P / 2
+    symbols before symbol t TILE lies across the staged tiles' boundary.  Tiles 2 cap and 3 cap are workgroup 0's third and
+    fourth pass, 2 cap + cap - 1 and 3 cap + cap - 1 the last workgroup's."""
+    out = []
+    for t, kind in ((2 * cap, 0), (3 * cap, 1), (3 * cap - 1, 2), (4 * cap - 1, 0), (2 * cap + 1, 3)):
+        first = t * FS_TILE - (P + G - 1)
+        out.append((first, first + FS_TILE - 1, t * FS_TILE - P // 2, t * FS_TILE + 1000)[kind])
+    return sorted(out)
+
+
+def framesync_word(name):
+    if name == "qpsk64":
+        w = rx_ref.QPSK_DEF[np.random.default_rng(64).integers(0, 4, 64)]
+        w.setflags(write=False)
+        return w
+    return fr.words()[name]
+
+
+@functools.lru_cache(maxsize=None)
+def framesync_stream(P, cap):
+    """framesync_ref's past-the-grid stream at this size: noise alone, the word (turned by 0.3 rad) at framesync_positions."""
+    cs = [c for c in cases_of("framesync") if c.fmt["P"] == P][0]
+    n = cs.size(cap)
+    rng = np.random.default_rng(1000 * P + cap)
+    y = (fr.SIGMA * (rng.standard_normal(n) + 1j * rng.standard_normal(n))).astype(np.complex64)
+    w = framesync_word(cs.fmt["word"])
+    for k in framesync_positions(P, cs.fmt["G"], cap):
+        y[k: k + P] = (w * np.exp(0.3j)).astype(np.complex64) + y[k: k + P]
+    y.setflags(write=False)
+    return y
+
+
+def syncest_signal(cs, cap):
+    return syncest_ref.signal(cs.fmt["n"], cs.size(cap))
+
+
+@functools.lru_cache(maxsize=None)
+def deframe_case(F, K, frames):
+    """deframe_ref's back-to-back frames (word, payload, three symbols): one call emits them all."""
+    per = dr.P + F + 3
+    return dr._case("grid-F%d-K%d-%d" % (F, K, frames), [7 + per * i for i in range(frames)], 7 + per * frames + 40, F, K, seed=900 + F + K,
+                    scale=0.5 * K)
+
+
+def _tiles(cap):
+    return 4 * cap + 1
+
+
+def _symsync():
+    return [Case("symsync", "symsync.hip", "L%d-S%d-N%d" % f, dict(L=f[0], S=f[1], N=f[2], mu=5), _tiles) for f in ((32, 4, 1025), (7, 3, 50))]
+
+
+RESAMPLE_FORMATS = ((3, 2, 64, "f32"), (3, 2, 64, "c32"), (147, 152, 1000, "c32"), (160, 147, 1601, "f32"))
+
+
+def _resample():
+    return [Case("resample", "resample.hip", "L%d-M%d-N%d-%s" % f, dict(L=f[0], M=f[1], N=f[2], dtype=f[3]), _tiles) for f in RESAMPLE_FORMATS]
+
+
+def _channelizer():
+    # 5 cap - 1 tiles: per = 5, the grid is cap and its last workgroup has four
+    return [Case("channelizer", "channelizer.hip", "M%d-%s" % (M, lay), dict(M=M, D=D, N=N, layout=lay), _channelizer_tiles)
+            for M, D, N in ((16, 8, 70), (1024, 3, 1025)) for lay in ("channel", "frame")]
+
+
+# 64 and 2048 are the issue's.  2048 lanes are a multiple of the workgroup: no frame count is ragged at cap 1 (never_ragged), and
+# at cap 1 the walk's remainder of 256 carries on `pos == lpf` every eighth step; 2053 is the ragged frame of that size.  100
+# (112 and 128 lanes in the BITS records) is the frame the stride passes whole with a remainder: dq >= 1, dr != 0.
+DEFRAME_F = (64, 100, 2048, 2053)
+
+
+@functools.lru_cache(maxsize=None)
+def _deframe_frames(lpf, cap):
+    """... and one frame more where the frame is a multiple of cap workgroups (2048 lanes at cap 1): a lane then walks from one
+    frame into the next, by a carry on `pos == lpf`."""
+    return smallest(functools.partial(deframe_walk, lpf=lpf), cap) + (lpf % (cap * WG) == 0)
+
+
+def _deframe():
+    return [Case("deframe", "deframe.hip", "F%d-K%d-%s" % (F, K, fmt), dict(F=F, K=K, fmt=fmt), functools.partial(_deframe_frames, deframe_lpf(F, K, fmt)))
+            for F in DEFRAME_F for K in (1, 2) for fmt in ("bits", "llr")]
+
+
+ENCODER_FORMATS = ((7, 3, 40), (3, 2, 6))
+
+
+def _encoder_frames(words, cap):
+    """the issue's words >= 4 cap 256 + 77"""
+    return cdiv(4 * cap * WG + 77, words)
+
+
+def _encoder():
+    return [Case("convcode", "convcode.hip", "enc-K%d-n%d-T%d" % (K, n, T), dict(node="encoder", K=K, n=n, T=T),
+                 functools.partial(_encoder_frames, enc_words(K, n, T))) for K, n, T in ENCODER_FORMATS]
+
+
+# (K, n, terminated, steps, kinds of the calls on one handle)
+VITERBI_FORMATS = ((3, 2, False, 6, ("noisy",)), (7, 3, True, 70, ("noisy",)), (7, 2, True, vr.LDS_STEPS, ("noisy",)),
+                   (3, 2, False, vr.LDS_STEPS + 1, ("special", "noisy")), (7, 3, True, vr.LDS_STEPS + 1, ("noisy",)))
+
+
+def _viterbi_frames(cap):
+    """four frames per wave and a ragged tail"""
+    return 4 * cap * vr.WAVES + 3
+
+
+def _viterbi():
+    return [Case("convcode", "convcode.hip", "vit-K%d-n%d-steps%d" % (K, n, steps),
+                 dict(node="viterbi", K=K, n=n, terminated=term, steps=steps, kinds=kinds), _viterbi_frames)
+            for K, n, term, steps, kinds in VITERBI_FORMATS]
+
+
+RM_RX_CODED = (140, 255, 256, 257, 767, 769, 2048, 2049, 4108)
+RM_TX_WORDS = (1, 5, 8, 9, 64, 65, 129, 300)   # 300: the only transmit record longer than a workgroup (stride_frames = 0 at cap 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _rm_rx_frames(n_coded, cap):
+    return smallest(functools.partial(rm_rx_walk, n_coded=n_coded), cap)
+
+
+@functools.lru_cache(maxsize=None)
+def _rm_tx_frames(n_tx, cap):
+    return smallest(functools.partial(rm_tx_walk, n_tx=n_tx), cap)
+
+
+def _ratematch():
+    rx = [Case("ratematch", "ratematch.hip", "rx-N%d" % N, dict(dir="rx", n_coded=N), functools.partial(_rm_rx_frames, N)) for N in RM_RX_CODED]
+    tx = [Case("ratematch", "ratematch.hip", "tx-W%d" % w, dict(dir="tx", n_tx=32 * w - 3, n_coded=n_coded_for(32 * w - 3)),
+               functools.partial(_rm_tx_frames, 32 * w - 3)) for w in RM_TX_WORDS]
+    return rx + tx
+
+
+# (W, T): groups 1, 2 and 64 (one round), and 66 words: two rounds
+CRC_FORMATS = ((8, 20), (16, 40), (24, 64 * 32 - 24), (32, 65 * 32 + 3))
+
+
+@functools.lru_cache(maxsize=None)
+def _crc_frames(fpw, cap):
+    """A ragged pass of wave-items, the last of them partly empty where a wave holds several frames."""
+    return (smallest(crc_items_walk, cap) - 1) * fpw + max(fpw // 2, 1)
+
+
+def _crc():
+    return [Case("crc", "crc.hip", "W%d-T%d" % (W, T), dict(W=W, T=T), functools.partial(_crc_frames, 64 // crc_ref.group_of(T))) for W, T in CRC_FORMATS]
+
+
+def crc_corrupted(frames):
+    """The frames of a check call that carry one flipped bit: two of every five and the last one, so that every pass of the
+    grid -- the ragged last one too -- and every wave meets some."""
+    f = np.arange(frames)
+    return f[(f % 5 == 0) | (f % 5 == 3) | (f == frames - 1)]
+
+
+CASES = _syncest() + _framesync() + _symsync() + _resample() + _channelizer() + _deframe() + _encoder() + _viterbi() + _ratematch() + _crc()
+FAMILIES = ("syncest", "framesync", "symsync", "resample", "channelizer", "deframe", "convcode", "ratematch", "crc")
+# not bitwise equal to the uncapped run: the [gridDim.x][4] partial sums of syncest_kernel are a reduction across workgroups
+REDUCED_ACROSS_WORKGROUPS = ("syncest",)
+
+
+def cases_of(family):
+    return [cs for cs in CASES if cs.family == family]
+
+
+def walk(cs, cap):
+    size, f = cs.size(cap), cs.fmt
+    if cs.family == "syncest":
+        return tiles_walk(cdiv(size, SE_TILE), cap)
+    if cs.family == "framesync":
+        return tiles_walk(cdiv(size, FS_TILE), cap)
+    if cs.family in ("symsync", "resample"):
+        return tiles_walk(size, cap)
+    if cs.family == "channelizer":
+        return channelizer_walk(size, cap)
+    if cs.family == "deframe":
+        return deframe_walk(size, cap, deframe_lpf(f["F"], f["K"], f["fmt"]))
+    if cs.family == "convcode":
+        return encoder_walk(size, cap, enc_words(f["K"], f["n"], f["T"])) if f["node"] == "encoder" else viterbi_walk(size, cap)
+    if cs.family == "ratematch":
+        return rm_rx_walk(size, cap, f["n_coded"]) if f["dir"] == "rx" else rm_tx_walk(size, cap, f["n_tx"])
+    if cs.family == "crc":
+        return crc_walk(size, cap, f["T"])
+    raise ValueError(cs.family)
+
+
+def ragged(cs, cap):
+    """The last pass is partial: the call's total is no multiple of grid * unit.  The tile kernels count in samples: syncest
+    and framesync against cap * 2048 here; symsync, resample and channelizer cut their last tile short on the device, where
+    the handle's tile is known (tests/grid_children.py asserts it), so they count as ragged here."""
+    if cs.family in ("syncest", "framesync"):
+        return cs.size(cap) % (cap * SE_TILE) != 0
+    if cs.family in ("symsync", "resample", "channelizer"):
+        return True
+    w = walk(cs, cap)
+    return w.total % (w.grid * w.unit) != 0
+
+
+def never_ragged(cs, cap):
+    """Receive records of 256 or 2048 values and deframer frames of 2048 lanes, at cap 1: every frame count gives a multiple of
+    the workgroup's 256 lanes."""
+    if cs.family == "ratematch" and cs.fmt["dir"] == "rx":
+        return cs.fmt["n_coded"] % (cap * WG) == 0
+    return cs.family == "deframe" and deframe_lpf(cs.fmt["F"], cs.fmt["K"], cs.fmt["fmt"]) % (cap * WG) == 0
+
+
+def bytes_moved(cs, cap):
+    """Input plus output bytes of one call, from above (tile-planned nodes at their largest tile)."""
+    size, f = cs.size(cap), cs.fmt
+    if cs.family in ("syncest", "framesync"):
+        return 8 * size
+    if cs.family == "symsync":
+        return 8 * size * TILE_MAX * (f["S"] + 1)
+    if cs.family == "resample":
+        e = 8 if f["dtype"] == "c32" else 4
+        return e * size * TILE_MAX * (cdiv(f["M"], f["L"]) + 1)
+    if cs.family == "channelizer":
+        frames = size * max(CHZ_TILE_POINTS // f["M"], 1)
+        return 8 * frames * (f["D"] + f["M"])
+    if cs.family == "deframe":
+        return 8 * size * (f["F"] + 40) * 2
+    if cs.family == "convcode":
+        if f["node"] == "encoder":
+            return size * (vr.record_bytes(f["T"]) + 4 * enc_words(f["K"], f["n"], f["T"]))
+        return size * (4 * f["n"] * f["steps"] + vr.record_bytes(f["steps"]) + 4)
+    if cs.family == "ratematch":
+        E = rr.n_tx_bits(f["n_coded"], P34)
+        return size * (4 * E + 4 * f["n_coded"]) if f["dir"] == "rx" else size * (rr.record_bytes(f["n_coded"]) + rr.record_bytes(E))
+    if cs.family == "crc":
+        return size * (2 * crc_ref.record_bytes(f["T"] + f["W"]) + 8)
+    raise ValueError(cs.family)
