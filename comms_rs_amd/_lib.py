@@ -22,6 +22,7 @@ DEFRAME_NORMALISE = 1           # comms_deframe_create: flags
 CONV_TERMINATED, CONV_TRUNCATED = 0, 1  # comms_convenc_create, comms_viterbi_create: flags
 RATEMATCH_TX, RATEMATCH_RX = 0, 1  # comms_ratematch_get_kernel: direction
 CRC_ATTACH, CRC_CHECK = 0, 1    # comms_crc_get_kernel: direction
+DEMAP_TABLE = 1                 # comms_demap_create: flags
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 RESAMPLE_F32, RESAMPLE_C32 = 4, 8  # comms_resample_create: bytes per sample
 CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR = 0, 1  # comms_channelizer_create: layout
@@ -345,6 +346,22 @@ _PROTOS = {
     "comms_crc_get_kernel": [_vp, _i32, _sz, C.c_char_p, _sz],
     "comms_crc_set_timer": [_vp, _vp],
     "comms_crc_destroy": [_vp],
+    "comms_constellation_qam": [_i32, _f64, _vp],
+    "comms_constellation_psk": [_i32, _f64, _vp],
+    "comms_symmap_create": [_i32, _vp, _sz, _vp, _sz, _sz, _i32, _pp],
+    "comms_symmap_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_symmap_run": [_vp, _vp, _sz, _vp],
+    "comms_symmap_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_symmap_set_timer": [_vp, _vp],
+    "comms_symmap_destroy": [_vp],
+    "comms_demap_create": [_i32, _vp, _sz, _i32, _i32, _pp],
+    "comms_demap_set_output_format": [_vp, _i32],
+    "comms_demap_set_llr_scale": [_vp, C.c_float],
+    "comms_demap_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_demap_run": [_vp, _vp, _sz, _vp],
+    "comms_demap_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_demap_set_timer": [_vp, _vp],
+    "comms_demap_destroy": [_vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],
@@ -374,6 +391,10 @@ _OTHER = {
     "comms_ratematch_rx_out_frame_bytes": (_sz, [_vp]),
     "comms_crc_payload_frame_bytes": (_sz, [_vp]),
     "comms_crc_coded_frame_bytes": (_sz, [_vp]),
+    "comms_symmap_in_frame_bytes": (_sz, [_vp]),
+    "comms_symmap_out_frame_syms": (_sz, [_vp]),
+    "comms_demap_in_frame_bytes": (_sz, [_vp]),
+    "comms_demap_out_frame_bytes": (_sz, [_vp]),
     "comms_buf_device": (_i32, [_vp]),
     "comms_synth_iq_host": (None, [_vp, _sz, _u64, _u64]),
 }

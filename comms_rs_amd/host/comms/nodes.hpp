@@ -1690,6 +1690,118 @@ public:
     Result<CheckedDev> run(const FramesDev& in) { return check_dev(in, *this); }
 };
 
+// Symbol mapper and soft demapper (comms_symmap_*, comms_demap_*; additional nodes): the constellation stages of a coded link with
+// 1 ... 8 bits per symbol.  One description per operation, two shells each.
+inline std::vector<Complex32> qam_table(int bits_per_sym, double scale = 1.0) {
+    std::vector<Complex32> t(size_t(1) << (bits_per_sym >= 0 && bits_per_sym <= 8 ? bits_per_sym : 0));
+    throw_on(comms_constellation_qam(bits_per_sym, scale, reinterpret_cast<comms_c32*>(t.data())), "qam_table");
+    return t;
+}
+inline std::vector<Complex32> psk_table(int bits_per_sym, double scale = 1.0) {
+    std::vector<Complex32> t(size_t(1) << (bits_per_sym >= 0 && bits_per_sym <= 8 ? bits_per_sym : 0));
+    throw_on(comms_constellation_psk(bits_per_sym, scale, reinterpret_cast<comms_c32*>(t.data())), "psk_table");
+    return t;
+}
+struct SymbolMapSpec {
+    int bits_per_sym;                      // m, 1 ... 8
+    std::vector<Complex32> constellation;  // 2^m points; empty = digital.rs's tables (m <= 2)
+    size_t n_bits;                         // E bits per input record (RateMatchNode's n_tx_bits())
+    std::vector<Complex32> word = {};      // sent in front of every frame's symbols
+    size_t gap = 0;                        // zero symbols behind them
+};
+// Map: a message is whole records of n_bits packed bits (in_frame_bytes() each: RateMatchNode's output as it stands), the output
+// out_frame_syms() symbols per record -- word, payload, gap -- which PulseNode takes.
+struct SymbolMapOp {
+    using In = uint8_t;
+    using Out = Complex32;
+    SymbolMapOp(const char* who, const SymbolMapSpec& f, int device) {
+        if (!f.constellation.empty() && f.bits_per_sym >= 1 && f.bits_per_sym <= 8 && f.constellation.size() != size_t(1) << f.bits_per_sym)
+            throw std::runtime_error(std::string(who) + ": the constellation holds 2^bits_per_sym points");
+        h_ = create<decltype(h_)>(who, comms_symmap_create, static_cast<int32_t>(f.bits_per_sym),
+                                  f.constellation.empty() ? nullptr : reinterpret_cast<const comms_c32*>(f.constellation.data()), f.n_bits,
+                                  f.word.empty() ? nullptr : reinterpret_cast<const comms_c32*>(f.word.data()), f.word.size(), f.gap, device);
+    }
+    size_t in_frame_bytes() const { return comms_symmap_in_frame_bytes(h_.get()); }
+    size_t out_frame_syms() const { return comms_symmap_out_frame_syms(h_.get()); }
+    std::string kernel(size_t n_frames) const { return kernel_name(comms_symmap_get_kernel, h_.get(), n_frames); }  // "symmap_kernel ..."
+
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const {
+        if (n % in_frame_bytes()) return COMMS_ERR_ARG;
+        m = n / in_frame_bytes() * out_frame_syms();
+        return COMMS_OK;
+    }
+    comms_status_t launch(const uint8_t* in, size_t n, Complex32* out) {
+        return comms_symmap_run(h_.get(), in, n / in_frame_bytes(), reinterpret_cast<comms_c32*>(out));
+    }
+    comms_status_t launch_dev(const uint8_t* in, size_t n, Complex32* out, void* s) {
+        return comms_symmap_run_dev(h_.get(), in, n / in_frame_bytes(), reinterpret_cast<comms_c32*>(out), s);
+    }
+    Owned<comms_symmap_t, comms_symmap_destroy> h_;
+};
+class SymbolMapNode : public HostNode<SymbolMapNode, SymbolMapOp> {
+public:
+    explicit SymbolMapNode(const SymbolMapSpec& format, int device = 0) : HostNode("SymbolMapNode::new", format, device) {}
+};
+class SymbolMapNodeDev : public DevNode<SymbolMapNodeDev, SymbolMapOp> {
+public:
+    explicit SymbolMapNodeDev(const SymbolMapSpec& format, int device = 0) : DevNode(device, "SymbolMapNodeDev::new", format, device) {}
+};
+
+// Demap: takes DeframeNode's message in the COMMS_SYM_C32 format (records of n_payload symbols, normalised to the table's scale)
+// and sends records of max-log LLRs (COMMS_SYM_LLR: n_payload * bits_per_sym f32, RateDematchNode's input with that record_llrs)
+// or packed hard bits (COMMS_SYM_BITS) under the same headers.  A message without frames passes through empty.
+struct DemapSpec {
+    int bits_per_sym;
+    std::vector<Complex32> constellation;  // 2^m points; empty = digital.rs's tables (m <= 2)
+    size_t n_payload;                      // F symbols per record
+    int32_t format = COMMS_SYM_LLR;
+    float llr_scale = 1.0f;                // 1 / (2 sigma^2) at the table's scale
+    bool force_table = false;              // COMMS_DEMAP_TABLE: the general kernel form for a separable table too
+};
+struct DemapOp {
+    using Frames = DeframeOp::Frames;
+    using FramesDev = DeframeOp::FramesDev;
+    DemapOp(const char* who, const DemapSpec& f, int device) {
+        if (!f.constellation.empty() && f.bits_per_sym >= 1 && f.bits_per_sym <= 8 && f.constellation.size() != size_t(1) << f.bits_per_sym)
+            throw std::runtime_error(std::string(who) + ": the constellation holds 2^bits_per_sym points");
+        h_ = create<decltype(h_)>(who, comms_demap_create, static_cast<int32_t>(f.bits_per_sym),
+                                  f.constellation.empty() ? nullptr : reinterpret_cast<const comms_c32*>(f.constellation.data()), f.n_payload,
+                                  static_cast<int32_t>(f.force_table ? COMMS_DEMAP_TABLE : 0), device);
+        throw_on(comms_demap_set_output_format(h_.get(), f.format), who);
+        throw_on(comms_demap_set_llr_scale(h_.get(), f.llr_scale), who);
+    }
+    size_t in_frame_bytes() const { return comms_demap_in_frame_bytes(h_.get()); }
+    size_t out_frame_bytes() const { return comms_demap_out_frame_bytes(h_.get()); }
+    std::string kernel(size_t n_frames) const { return kernel_name(comms_demap_get_kernel, h_.get(), n_frames); }  // "demap_table_kernel ..." | "demap_axis_kernel ..."
+
+protected:
+    Result<Frames> demap(const Frames& in) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        Frames out{std::vector<uint8_t>(in.size() * out_frame_bytes()), in.headers, out_frame_bytes()};
+        return ok_or(comms_demap_run(h_.get(), reinterpret_cast<const comms_c32*>(in.data.data()), in.size(), out.data.data()), out);
+    }
+    Result<FramesDev> demap_dev(const FramesDev& in, const DevStream& on) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        FramesDev out{DeviceBuf<uint8_t>(in.size() ? in.size() * out_frame_bytes() : 16, on.device()), in.headers, out_frame_bytes()};
+        return ok_or(on.submit(in.data, out.data, [&](void* s) {
+            return comms_demap_run_dev(h_.get(), reinterpret_cast<const comms_c32*>(in.data.ptr()), in.size(), out.data.ptr(), s);
+        }), out);
+    }
+    Owned<comms_demap_t, comms_demap_destroy> h_;
+};
+class DemapNode : public DeriveNode<DemapNode>, public Ports<DemapOp::Frames, DemapOp::Frames>, public DemapOp {
+public:
+    explicit DemapNode(const DemapSpec& format, int device = 0) : DemapOp("DemapNode::new", format, device) {}
+    Result<Frames> run(const Frames& in) { return demap(in); }
+};
+// on device-resident messages: DeframeNodeDev's records in, the demapped records in a DeviceBuf out (headers on the host)
+class DemapNodeDev : public DeriveNode<DemapNodeDev>, public Ports<DemapOp::FramesDev, DemapOp::FramesDev>, public OnStream<DemapOp> {
+public:
+    explicit DemapNodeDev(const DemapSpec& format, int device = 0) : OnStream(device, "DemapNodeDev::new", format, device) {}
+    Result<FramesDev> run(const FramesDev& in) { return demap_dev(in, *this); }
+};
+
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)

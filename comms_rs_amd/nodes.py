@@ -1971,6 +1971,148 @@ class CrcCheckNode(_Crc):
         check(lib().comms_crc_check_run_dev(self._h, in_ptr, int(n_frames), payload_ptr, pass_ptr, crc_ptr, n_failed_ptr, stream))
 
 
+# ------------------------------------------------------------------ symbol mapper and soft demapper
+def _table(fn, bits_per_sym, scale):
+    out = np.zeros(256, np.complex64)                     # the largest table; a refused bits_per_sym writes nothing
+    check(getattr(lib(), fn)(int(bits_per_sym), float(scale), _ptr(out)))
+    return out[: 1 << int(bits_per_sym)].copy()
+
+
+def qam_table(bits_per_sym, scale=1.0):
+    """The Gray-coded square QAM table of comms_constellation_qam (bits_per_sym 2, 4, 6, 8; 1 is BPSK on the real axis): the
+    low half of a value's bits chooses the real level, the high half the imaginary one, levels (2^k - 1 - 2 rank) * scale.
+    Host arithmetic, no device.  np.complex64, 2**bits_per_sym points."""
+    return _table("comms_constellation_qam", bits_per_sym, scale)
+
+
+def psk_table(bits_per_sym, scale=1.0):
+    """The Gray-coded PSK table of comms_constellation_psk (bits_per_sym 1 ... 4): point v at angle 2 pi rank(v) / 2^m, plus
+    pi/4 at bits_per_sym = 2 (scale sqrt(2) gives digital.rs's QPSK table).  Host arithmetic, no device."""
+    return _table("comms_constellation_psk", bits_per_sym, scale)
+
+
+class SymbolMapNode(_Handle):
+    """Packed bit records -> frames of Complex<f32> symbols (comms_symmap_*), behind RateMatchNode and in front of PulseNode in
+    "c32" input format: every record of n_bits bits (RateMatchNode's output record) becomes `word` (the known word a
+    FrameSyncNode looks for, or None), ceil(n_bits / bits_per_sym) payload symbols table[v] -- v the record's next
+    bits_per_sym bits, the first as the LSB, bits beyond n_bits reading as 0 -- and `gap` symbols (0, 0); all frames of a call
+    in one launch.  constellation: 2**bits_per_sym points (qam_table, psk_table, or any), None = digital.rs's tables at 1 or 2
+    bits.  Stateless.  run() takes uint8 (n_frames, in_frame_bytes) and returns complex64 (n_frames, out_frame_syms)."""
+    _destroy = "comms_symmap_destroy"
+
+    def __init__(self, bits_per_sym, constellation, n_bits, word=None, gap=0, device=0):
+        super().__init__()
+        self.bits_per_sym, self.n_bits = int(bits_per_sym), int(n_bits)
+        cons = None if constellation is None else _as_c64(constellation).ravel()
+        if cons is not None and 1 <= self.bits_per_sym <= 8 and cons.size != 1 << self.bits_per_sym:
+            raise ValueError("the constellation holds 2**bits_per_sym points")
+        w = None if word is None else _as_c64(word).ravel()
+        check(lib().comms_symmap_create(self.bits_per_sym, None if cons is None else _ptr(cons), self.n_bits,
+                                        None if w is None or not w.size else _ptr(w), 0 if w is None else w.size, int(gap), device,
+                                        C.byref(self._h)))
+
+    @property
+    def in_frame_bytes(self):
+        return lib().comms_symmap_in_frame_bytes(self._h)
+
+    @property
+    def out_frame_syms(self):
+        return lib().comms_symmap_out_frame_syms(self._h)
+
+    @property
+    def out_frame_bytes(self):
+        return 8 * self.out_frame_syms
+
+    def run(self, frames):
+        x = np.ascontiguousarray(frames, dtype=np.uint8)
+        if x.size % self.in_frame_bytes:
+            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
+        n_frames = x.size // self.in_frame_bytes
+        out = np.zeros((n_frames, self.out_frame_syms), np.complex64)
+        check(lib().comms_symmap_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
+        return out
+
+    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
+        check(lib().comms_symmap_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+
+    def kernel(self, n_frames):
+        """ "symmap_kernel wg=.. bits=.. n_bits=.. word=.. payload=.. gap=.. syms=.. frames=.. grid=.. max_grid=.. lds=.."."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_symmap_get_kernel(self._h, int(n_frames), buf, 240))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        check(lib().comms_symmap_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
+class DemapNode(_Handle):
+    """Records of n_payload Complex<f32> symbols -> max-log LLRs ("llr", the default: bits_per_sym float32 per symbol, positive
+    = bit 0, scaled by llr_scale = 1 / (2 sigma^2)) or packed hard bits ("bits") against a table of 2**bits_per_sym points
+    (comms_demap_*), all frames of a call in one launch: behind DeframeNode in "c32" format with normalise=True, in front of
+    RateDematchNode(record_llrs = n_payload * bits_per_sym).  The rule is sym_to_bits's and DeframeNode's over the whole table.
+    A separable table (any square or rectangular QAM) runs per axis, the same bits from far fewer distances; force_table=True
+    keeps the general form.  Stateless.  run() takes complex64 and returns float32 (n_frames, n_payload * bits_per_sym) or
+    uint8 (n_frames, out_frame_bytes)."""
+    _destroy = "comms_demap_destroy"
+
+    def __init__(self, bits_per_sym, constellation, n_payload, force_table=False, device=0):
+        super().__init__()
+        self.bits_per_sym, self.n_payload = int(bits_per_sym), int(n_payload)
+        self.format = "llr"
+        cons = None if constellation is None else _as_c64(constellation).ravel()
+        if cons is not None and 1 <= self.bits_per_sym <= 8 and cons.size != 1 << self.bits_per_sym:
+            raise ValueError("the constellation holds 2**bits_per_sym points")
+        check(lib().comms_demap_create(self.bits_per_sym, None if cons is None else _ptr(cons), self.n_payload,
+                                       _lib.DEMAP_TABLE if force_table else 0, device, C.byref(self._h)))
+
+    def set_output_format(self, fmt):
+        """ "llr" (default) or "bits"; may change between calls."""
+        if fmt not in ("llr", "bits"):
+            raise ValueError("the output format is 'llr' or 'bits'")
+        check(lib().comms_demap_set_output_format(self._h, _SYM_FORMATS[fmt]))
+        self.format = fmt
+        return self
+
+    def set_llr_scale(self, scale):
+        check(lib().comms_demap_set_llr_scale(self._h, float(scale)))
+        return self
+
+    @property
+    def in_frame_bytes(self):
+        return lib().comms_demap_in_frame_bytes(self._h)
+
+    @property
+    def out_frame_bytes(self):
+        return lib().comms_demap_out_frame_bytes(self._h)
+
+    def run(self, symbols):
+        x = _as_c64(symbols).ravel()
+        if x.size % self.n_payload:
+            raise ValueError("the input must hold whole records of n_payload symbols")
+        n_frames = x.size // self.n_payload
+        if self.format == "llr":
+            out = np.zeros((n_frames, self.n_payload * self.bits_per_sym), np.float32)
+        else:
+            out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
+        check(lib().comms_demap_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
+        return out
+
+    def run_dev(self, sym_ptr, n_frames, out_ptr, stream=0):
+        check(lib().comms_demap_run_dev(self._h, sym_ptr, int(n_frames), out_ptr, stream))
+
+    def kernel(self, n_frames):
+        """ "demap_table_kernel<m,fmt> form=table ..." or "demap_axis_kernel<mI,mQ,fmt> form=axis ...", then "wg=.. bits=..
+        payload=.. items=.. lanes=.. frames=.. grid=.. max_grid=.. lds=0"."""
+        buf = C.create_string_buffer(240)
+        check(lib().comms_demap_get_kernel(self._h, int(n_frames), buf, 240))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        check(lib().comms_demap_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+
 def qfilt_taps(n_taps, alpha, sam_per_sym):
     """util/math.rs:307-342 (f64, real); even n_taps is incremented."""
     out = np.empty(lib().comms_qfilt_len(int(n_taps)), np.float64)
@@ -2049,7 +2191,9 @@ class KernelTimer:
                 "comms_convenc_destroy": "comms_convenc_set_timer",
                 "comms_viterbi_destroy": "comms_viterbi_set_timer",
                 "comms_ratematch_destroy": "comms_ratematch_set_timer",
-                "comms_crc_destroy": "comms_crc_set_timer"}[node._destroy]
+                "comms_crc_destroy": "comms_crc_set_timer",
+                "comms_symmap_destroy": "comms_symmap_set_timer",
+                "comms_demap_destroy": "comms_demap_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

@@ -1539,6 +1539,97 @@ impl CrcCheckNode {
     }
 }
 
+/// The Gray-coded square QAM table of comms_constellation_qam (`bits_per_sym` 2, 4, 6, 8; 1 is BPSK): host arithmetic, no device.
+pub fn qam_table(bits_per_sym: i32, scale: f64) -> Result<Vec<Complex<f32>>, ()> {
+    if !(1..=8).contains(&bits_per_sym) { return Err(()); }
+    let mut t = vec![Complex::new(0.0f32, 0.0f32); 1usize << bits_per_sym];
+    let st = unsafe { comms_constellation_qam(bits_per_sym, scale, t.as_mut_ptr() as *mut comms_c32) };
+    if st == COMMS_OK { Ok(t) } else { Err(()) }
+}
+/// The Gray-coded PSK table of comms_constellation_psk (`bits_per_sym` 1 ..= 4; pi/4 offset at 2): host arithmetic, no device.
+pub fn psk_table(bits_per_sym: i32, scale: f64) -> Result<Vec<Complex<f32>>, ()> {
+    if !(1..=8).contains(&bits_per_sym) { return Err(()); }
+    let mut t = vec![Complex::new(0.0f32, 0.0f32); 1usize << bits_per_sym];
+    let st = unsafe { comms_constellation_psk(bits_per_sym, scale, t.as_mut_ptr() as *mut comms_c32) };
+    if st == COMMS_OK { Ok(t) } else { Err(()) }
+}
+
+fn c32_or_null(v: &[Complex<f32>]) -> *const comms_c32 {
+    if v.is_empty() { ptr::null() } else { v.as_ptr() as *const comms_c32 }
+}
+
+/// Symbol mapper (comms_symmap_*; an additional node), behind `RateMatchNode`: takes records of `n_bits` packed bits and sends,
+/// per record, `word`, ceil(n_bits / bits_per_sym) points of `constellation` (empty = digital.rs's tables at 1 or 2 bits) and
+/// `gap` zero symbols -- the stream `PulseNode` shapes and `FrameSyncNode` / `DeframeNode` take apart again.  Stateless.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct SymbolMapNode {
+    pub input: NodeReceiver<Vec<u8>>,
+    h: *mut comms_symmap_t,
+    pub output: NodeSender<Vec<Complex<f32>>>,
+}
+handle_node!(SymbolMapNode, comms_symmap_destroy);
+impl SymbolMapNode {
+    /// `Err(())`: what comms_symmap_create refuses.
+    pub fn new(bits_per_sym: i32, constellation: &[Complex<f32>], n_bits: usize, word: &[Complex<f32>], gap: usize) -> Result<Self, ()> {
+        if !constellation.is_empty() && (1..=8).contains(&bits_per_sym) && constellation.len() != 1usize << bits_per_sym { return Err(()); }
+        let mut h = ptr::null_mut();
+        let st = unsafe {
+            comms_symmap_create(bits_per_sym, c32_or_null(constellation), n_bits,
+                                c32_or_null(word), word.len(), gap, 0, &mut h)
+        };
+        if st == COMMS_OK { Ok(SymbolMapNode { input: Default::default(), h, output: Default::default() }) } else { Err(()) }
+    }
+    pub fn in_frame_bytes(&self) -> usize { unsafe { comms_symmap_in_frame_bytes(self.h) } }
+    pub fn out_frame_syms(&self) -> usize { unsafe { comms_symmap_out_frame_syms(self.h) } }
+    pub fn run(&mut self, records: &[u8]) -> Result<Vec<Complex<f32>>, NodeError> {
+        let fin = self.in_frame_bytes();
+        if fin == 0 || records.len() % fin != 0 { return Err(NodeError::DataError); }
+        let n_frames = records.len() / fin;
+        let mut out = vec![Complex::new(0.0f32, 0.0f32); n_frames * self.out_frame_syms()];
+        let st = unsafe { comms_symmap_run(self.h, records.as_ptr() as *const c_void, n_frames, out.as_mut_ptr() as *mut comms_c32) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
+/// Soft demapper (comms_demap_*; an additional node), behind `DeframeNode` in the `COMMS_SYM_C32` format (normalising): takes
+/// records of `n_payload` symbols and sends, under the same headers, max-log LLRs (`COMMS_SYM_LLR`: `n_payload * bits_per_sym`
+/// f32 per record, `RateDematchNode`'s input with that `record_llrs`) or packed hard bits (`COMMS_SYM_BITS`).  Stateless.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct DemapNode {
+    pub input: NodeReceiver<Frames>,
+    h: *mut comms_demap_t,
+    pub output: NodeSender<Frames>,
+}
+handle_node!(DemapNode, comms_demap_destroy);
+impl DemapNode {
+    /// `format`: COMMS_SYM_LLR or COMMS_SYM_BITS; `llr_scale`: 1 / (2 sigma^2) at the table's scale; `force_table`: the general
+    /// kernel form for a separable table too.  `Err(())`: what the library refuses.
+    pub fn new(bits_per_sym: i32, constellation: &[Complex<f32>], n_payload: usize, format: i32, llr_scale: f32, force_table: bool) -> Result<Self, ()> {
+        if !constellation.is_empty() && (1..=8).contains(&bits_per_sym) && constellation.len() != 1usize << bits_per_sym { return Err(()); }
+        let mut h = ptr::null_mut();
+        let st = unsafe {
+            comms_demap_create(bits_per_sym, c32_or_null(constellation), n_payload,
+                               if force_table { COMMS_DEMAP_TABLE } else { 0 }, 0, &mut h)
+        };
+        if st != COMMS_OK { return Err(()); }
+        let node = DemapNode { input: Default::default(), h, output: Default::default() };   // (dropped, and so destroyed, on an error below)
+        let ok = unsafe { comms_demap_set_output_format(node.h, format) == COMMS_OK && comms_demap_set_llr_scale(node.h, llr_scale) == COMMS_OK };
+        if ok { Ok(node) } else { Err(()) }
+    }
+    pub fn in_frame_bytes(&self) -> usize { unsafe { comms_demap_in_frame_bytes(self.h) } }
+    pub fn out_frame_bytes(&self) -> usize { unsafe { comms_demap_out_frame_bytes(self.h) } }
+    pub fn run(&mut self, frames: &Frames) -> Result<Frames, NodeError> {
+        let n_frames = frames.headers.len();
+        if frames.frame_bytes != self.in_frame_bytes() || frames.data.len() < n_frames * frames.frame_bytes { return Err(NodeError::DataError); }
+        let frame_bytes = self.out_frame_bytes();
+        let mut out = Frames { data: vec![0u8; n_frames * frame_bytes], headers: frames.headers.clone(), frame_bytes };
+        let st = unsafe { comms_demap_run(self.h, frames.data.as_ptr() as *const comms_c32, n_frames, out.data.as_mut_ptr() as *mut c_void) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
 /// demodulation/nco.rs:118-133 in block form: a vector of phase errors per message.
 #[derive(Node)]
 #[pass_by_ref]
