@@ -23,6 +23,9 @@ CONV_TERMINATED, CONV_TRUNCATED = 0, 1  # comms_convenc_create, comms_viterbi_cr
 RATEMATCH_TX, RATEMATCH_RX = 0, 1  # comms_ratematch_get_kernel: direction
 CRC_ATTACH, CRC_CHECK = 0, 1    # comms_crc_get_kernel: direction
 DEMAP_TABLE = 1                 # comms_demap_create: flags
+OFDM_NULL, OFDM_DATA, OFDM_PILOT = 0, 1, 2  # comms_ofdm_create: carrier_kind
+OFDM_CPE = 1                    # comms_ofdm_create: flags
+OFDM_MOD, OFDM_DEMOD = 0, 1     # comms_ofdm_get_kernel: direction
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 RESAMPLE_F32, RESAMPLE_C32 = 4, 8  # comms_resample_create: bytes per sample
 CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR = 0, 1  # comms_channelizer_create: layout
@@ -362,6 +365,15 @@ _PROTOS = {
     "comms_demap_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_demap_set_timer": [_vp, _vp],
     "comms_demap_destroy": [_vp],
+    "comms_ofdm_create": [_i32, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _i32, _i32, _pp],
+    "comms_ofdm_set_scale": [_vp, C.c_float],
+    "comms_ofdm_mod_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_ofdm_mod_run": [_vp, _vp, _sz, _vp],
+    "comms_ofdm_demod_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_ofdm_demod_run": [_vp, _vp, _sz, _vp],
+    "comms_ofdm_get_kernel": [_vp, _i32, _sz, C.c_char_p, _sz],
+    "comms_ofdm_set_timer": [_vp, _vp],
+    "comms_ofdm_destroy": [_vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],
@@ -395,6 +407,8 @@ _OTHER = {
     "comms_symmap_out_frame_syms": (_sz, [_vp]),
     "comms_demap_in_frame_bytes": (_sz, [_vp]),
     "comms_demap_out_frame_bytes": (_sz, [_vp]),
+    "comms_ofdm_data_syms": (_sz, [_vp]),
+    "comms_ofdm_frame_samples": (_sz, [_vp]),
     "comms_buf_device": (_i32, [_vp]),
     "comms_synth_iq_host": (None, [_vp, _sz, _u64, _u64]),
 }

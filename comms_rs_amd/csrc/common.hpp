@@ -813,9 +813,10 @@ inline unsigned resident_workgroups(size_t lds) {
     const int cap = diag_knob("COMMS_GRID_CAP", 0);
     return cap > 0 && static_cast<unsigned>(cap) < chip ? static_cast<unsigned>(cap) : chip;
 }
-// The same cap for the stateless constellation nodes (symmap.hip).  tests/test_grid_cases.py counts the files that call the
-// function above by name against the case table of tests/grid_cases.py; the capped-grid cases of these nodes are a table of
-// their own (tests/symmap_cases.py, run by tests/symmap_grid_child.py and held to the same rules by tests/test_symmap_ref.py).
+// The same cap for the stateless constellation nodes (symmap.hip) and the OFDM nodes (ofdm.hip).  tests/test_grid_cases.py counts
+// the files that call the function above by name against the case table of tests/grid_cases.py; the capped-grid cases of these
+// nodes are tables of their own (tests/symmap_ref.py and tests/ofdm_ref.py, run by tests/symmap_grid_child.py and
+// tests/ofdm_grid_child.py and held to the same rules by tests/test_symmap_ref.py and tests/test_ofdm_ref.py).
 inline unsigned stateless_workgroups(size_t lds) { return resident_workgroups(lds); }
 
 // Mixer phase bookkeeping shared by the mixer node and the fused chain: phases are

@@ -381,31 +381,6 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 4) void fft1024x16_kernel(c
 // 1024-point transform as fft1024x16_kernel, and the tile goes back fully coalesced, because
 // element i = k1 + RAD k2 (+ N j) of the tile is simply output i.  One HBM read and one write
 // per point, where the tile kernel needs two passes above 4096 points.
-template <int DIR>
-__device__ __forceinline__ void radix2(cf& a, cf& b) {
-    const cf t = cadd(a, b);
-    b = csub(a, b);
-    a = t;
-}
-// 8-point DFT, natural order in and out
-template <int DIR>
-__device__ __forceinline__ void radix8(cf (&v)[8]) {
-    constexpr float R2 = 0.70710678118654752440f;
-    radix4<DIR>(v[0], v[2], v[4], v[6]);  // E[0..3] in v[0], v[2], v[4], v[6]
-    radix4<DIR>(v[1], v[3], v[5], v[7]);  // O[0..3] in v[1], v[3], v[5], v[7]
-    const cf o1 = tw_mul<DIR>(v[3], cf{R2, -R2});
-    const cf o3 = tw_mul<DIR>(v[7], cf{-R2, -R2});
-    const cf e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6], o0 = v[1], o2 = v[5];
-    v[0] = cadd(e0, o0);
-    v[4] = csub(e0, o0);
-    v[1] = cadd(e1, o1);
-    v[5] = csub(e1, o1);
-    v[2] = cadd_di<DIR>(e2, o2);  // W8^2 = -+i
-    v[6] = csub_di<DIR>(e2, o2);
-    v[3] = cadd(e3, o3);
-    v[7] = csub(e3, o3);
-}
-
 // RAD = 0 stands for N = 64: the rows are 16 contiguous 64-point transforms each, which is the
 // 1024-point wave transform with its first radix-16 stage (and twiddle) left out.
 // RAD = 256 stands for N = 256: a row is 4 transforms, lane (t, b) does radix-16 over a

@@ -115,6 +115,32 @@ __device__ __forceinline__ void radix4_c_rot(cf& a, cf& b, cf& c, cf& d) {
     d = csub_di<DIR>(t1, t3);
 }
 
+// 2-point DFT in place
+template <int DIR>
+__device__ __forceinline__ void radix2(cf& a, cf& b) {
+    const cf t = cadd(a, b);
+    b = csub(a, b);
+    a = t;
+}
+// 8-point DFT, natural order in and out
+template <int DIR>
+__device__ __forceinline__ void radix8(cf (&v)[8]) {
+    constexpr float R2 = 0.70710678118654752440f;
+    radix4<DIR>(v[0], v[2], v[4], v[6]);  // E[0..3] in v[0], v[2], v[4], v[6]
+    radix4<DIR>(v[1], v[3], v[5], v[7]);  // O[0..3] in v[1], v[3], v[5], v[7]
+    const cf o1 = tw_mul<DIR>(v[3], cf{R2, -R2});
+    const cf o3 = tw_mul<DIR>(v[7], cf{-R2, -R2});
+    const cf e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6], o0 = v[1], o2 = v[5];
+    v[0] = cadd(e0, o0);
+    v[4] = csub(e0, o0);
+    v[1] = cadd(e1, o1);
+    v[5] = csub(e1, o1);
+    v[2] = cadd_di<DIR>(e2, o2);  // W8^2 = -+i
+    v[6] = csub_di<DIR>(e2, o2);
+    v[3] = cadd(e3, o3);
+    v[7] = csub(e3, o3);
+}
+
 // v_permlane32_swap / v_permlane16_swap on a complex register pair: (a, b) -> a keeps its lanes 0-31 and takes
 // b's lanes 0-31 into 32-63, b takes a's lanes 32-63 into 0-31 and keeps its own 32-63 (32); the same with the
 // four 16-lane rows, odd rows of a <-> even rows of b (16).  The builtins (not raw asm) so that the compiler

@@ -1,0 +1,501 @@
+// ofdm.hip -- the OFDM stages between SymbolMapNode and DemapNode: records of data-carrier values -> frames of time samples
+// (ofdm_mod_kernel: carrier map, pilots, training symbols, IFFT, cyclic prefix) and frames of received samples -> records of
+// equalised data-carrier values (ofdm_demod_kernel: prefix removal, FFT, least-squares channel estimate from the training
+// symbols, one-tap equaliser, pilot phase correction, carrier extraction), every frame of a call by ONE launch each.  One
+// handle serves both directions; both are stateless.
+//
+// The reference has no such block; the contract is include/comms_hip.h's ("OFDM modulator and demodulator"), and
+// tests/ofdm_ref.py restates it in complex128.
+//   transform     N = 16 L points of one symbol sit in L = N / 16 lanes, 16 per lane, so a wave holds 64 / L = 1024 / N
+//                 symbols (16 at N = 64, one at N = 1024) and no lane idles on a full group.  With n = l + L a, k = k1 + 16 k':
+//                   step 1  lane l loads x[l + L a] (consecutive lanes, consecutive samples), radix-16 over a, times
+//                           W_N^{l k1}, into the wave's LDS buffer at [k1 L + l];
+//                   step 2  the L-point transforms over l, l = l' + M2 b: radix R2 = 4, 8, 16, 16, 16 over b for N = 64 ...
+//                           1024, 16 / R2 butterflies per lane.  N <= 256: done, X[k1 + 16 k2] is in registers.
+//                   step 3  N = 512, 1024: times W_L^{l' k2}, into LDS at [l' 256 + k1 + 16 k2], radix M2 = 2, 4 over l':
+//                           X[k1 + 16 k2 + 256 k3].
+//                 One LDS exchange per radix step, wave-private, no workgroup barrier; the buffer index i sits at i + i / 16
+//                 (fft.hip's padding).  Twiddles are W_N^j, j < N, built on the host in f64 and rounded once, read from LDS.
+//   load / store  prefix removal, the carrier scatter (bin -> record index, a host-built table), pilots and training values
+//                 are the modulator's load stage; scaling and the prefix copy its store stage.  The demodulator loads past
+//                 the prefix and its store stage multiplies by 1 / H_k, corrects the pilots' common phase and writes the
+//                 data bins only.  All global accesses are 8 bytes wide: a symbol behind an odd prefix is 8, not 16, bytes
+//                 off alignment.
+//   work split    a workgroup of four waves takes an item (frame, block of symbols); its waves walk the block's groups of
+//                 1024 / N symbols.  The demodulator first transforms the frame's T training symbols (all four waves), sums
+//                 them in symbol order and leaves T train[k] / sum_t Y_{t,k} = 1 / H_k in LDS.  ofdm_block() chooses the
+//                 block: one per frame when the call has at least as many frames as the grid has workgroups, otherwise
+//                 just enough blocks per frame to give every workgroup an item.
+// Both kernels walk their items grid-stride under the library's grid cap.
+#include <cmath>
+
+#include "common.hpp"
+#include "fft_radix.hpp"
+
+namespace comms {
+
+constexpr int OF_WG = 256, OF_WAVES = OF_WG / 64;
+constexpr int OF_WAVE_BUF = 1024 + 64;   // a wave's exchange buffer: 1024 / N symbols of N + N / 16 elements
+constexpr size_t OF_MAX_FRAME = size_t(1) << 24;
+
+constexpr size_t ofdm_lds(int n) { return static_cast<size_t>(n) * (2 * sizeof(float2) + sizeof(int)) + OF_WAVES * OF_WAVE_BUF * sizeof(float2); }
+
+struct OfdmArgs {
+    const float2* in;
+    float2* out;
+    const float2* tw;      // W_N^j = (cos, -sin)(2 pi j / N), j < N
+    const int* map;        // bin -> d >= 0 (data value d of a symbol), -1 (null), -2 - q (pilot q)
+    const float2* pilots;  // Q
+    const float* pol;      // n_pol >= 1
+    const float2* train;   // modulator: train[k]; demodulator: T train[k]
+    size_t items;          // n_frames * nblk
+    unsigned n_pol, T, S, D, CP;
+    unsigned blk, nblk;    // symbols per block, blocks per frame
+    float scale;           // modulator: tx_scale; demodulator without training: 1 / (N tx_scale)
+    int cpe;
+};
+
+__device__ __forceinline__ void of_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ int of_pad(int i) { return i + (i >> 4); }
+
+// R-point DFT of x[0 .. R), natural order in and out
+template <int R, int DIR>
+__device__ __forceinline__ void of_dft(cf* x) {
+    if constexpr (R == 2) radix2<DIR>(x[0], x[1]);
+    if constexpr (R == 4) radix4<DIR>(x[0], x[1], x[2], x[3]);
+    if constexpr (R == 8) radix8<DIR>(*reinterpret_cast<cf(*)[8]>(x));
+    if constexpr (R == 16) {
+        radix16<DIR>(*reinterpret_cast<cf(*)[16]>(x));
+        cf t[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t[k] = x[R16_POS(k)];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) x[k] = t[k];
+    }
+}
+
+template <int N>
+struct OfGeom {
+    static constexpr int L = N / 16;                              // lanes per symbol
+    static constexpr int SPW = 64 / L;                            // symbols per wave
+    static constexpr int NP = N + N / 16;                         // a symbol's padded buffer
+    static constexpr int R2 = N == 64 ? 4 : N == 128 ? 8 : 16;
+    static constexpr int R3 = L / R2;                             // 1, 1, 1, 2, 4 (= M2)
+    static constexpr int LAST = R3 > 1 ? R3 : R2;                 // radix of the step that ends in registers
+    // the bin of result i of lane-in-symbol l: i = u LAST + j, butterfly l + L u, output j
+    __device__ static __forceinline__ int bin(int l, int i) { return l + L * (i / LAST) + (R3 > 1 ? 256 : 16) * (i % LAST); }
+};
+
+// The N-point transform of the wave's 64 / L symbols: v[a] = x[l + L a] in, r[i] = X[bin(l, i)] out.  `buf` is the symbol's
+// part of the wave's buffer.  Ends behind a wave barrier: the buffer is free again.
+template <int N, int DIR>
+__device__ __forceinline__ void of_transform(cf (&v)[16], cf* buf, const cf* tw, int l) {
+    using G = OfGeom<N>;
+    constexpr int L = G::L, R2 = G::R2, R3 = G::R3;
+    radix16<DIR>(v);
+#pragma unroll
+    for (int k1 = 0; k1 < 16; ++k1) {
+        cf y = v[R16_POS(k1)];
+        if (k1) y = tw_mul<DIR>(y, tw[l * k1]);
+        buf[of_pad(k1 * L + l)] = y;
+    }
+    of_wave_sync();
+#pragma unroll
+    for (int u = 0; u < 16 / R2; ++u) {
+        const int t = l + L * u, lp = t % R3, k1 = t / R3;
+#pragma unroll
+        for (int b = 0; b < R2; ++b) v[u * R2 + b] = buf[of_pad(k1 * L + lp + R3 * b)];
+        of_dft<R2, DIR>(&v[u * R2]);
+    }
+    of_wave_sync();
+    if constexpr (R3 > 1) {   // (16 / R2 = 1: one butterfly per lane, t = l)
+        const int lp = l % R3, k1 = l / R3;
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) {
+            cf y = v[k2];
+            if (k2) y = tw_mul<DIR>(y, tw[16 * lp * k2]);
+            buf[of_pad(lp * 256 + k1 + 16 * k2)] = y;
+        }
+        of_wave_sync();
+#pragma unroll
+        for (int u = 0; u < 16 / R3; ++u) {
+#pragma unroll
+            for (int j = 0; j < R3; ++j) v[u * R3 + j] = buf[of_pad(j * 256 + l + L * u)];
+            of_dft<R3, DIR>(&v[u * R3]);
+        }
+        of_wave_sync();
+    }
+}
+
+// (frame, first symbol, end symbol) of an item; `per_frame` symbols are split into nblk blocks of blk
+__device__ __forceinline__ void of_item(const OfdmArgs& a, size_t item, unsigned per_frame, size_t& frame, unsigned& s0, unsigned& s1) {
+    frame = item / a.nblk;
+    s0 = static_cast<unsigned>(item % a.nblk) * a.blk;
+    s1 = s0 + a.blk < per_frame ? s0 + a.blk : per_frame;
+}
+
+__device__ __forceinline__ cf of_scale(cf y, float s) { return cf{__fmul_rn(y.x, s), __fmul_rn(y.y, s)}; }
+
+template <int N>
+__global__ __launch_bounds__(OF_WG) void ofdm_mod_kernel(const OfdmArgs a) {
+    using G = OfGeom<N>;
+    extern __shared__ __align__(16) unsigned char of_smem[];
+    cf* tw = reinterpret_cast<cf*>(of_smem);
+    int* map = reinterpret_cast<int*>(tw + 2 * N);
+    cf* ex = reinterpret_cast<cf*>(map + N);
+    for (int i = threadIdx.x; i < N; i += OF_WG) {
+        tw[i] = to_cf(a.tw[i]);
+        map[i] = a.map[i];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane / G::L, l = lane % G::L;
+    cf* buf = ex + wave * OF_WAVE_BUF + q * G::NP;
+    const unsigned per_frame = a.T + a.S, sym_len = N + a.CP;
+    for (size_t item = blockIdx.x; item < a.items; item += gridDim.x) {
+        size_t frame;
+        unsigned s0, s1;
+        of_item(a, item, per_frame, frame, s0, s1);
+        // `g` is wave-uniform: every lane of a wave takes part in the exchanges
+        for (unsigned g = s0 + wave * G::SPW; g < s1; g += OF_WAVES * G::SPW) {
+            const unsigned s = g + q;
+            const bool live = s < s1;
+            cf v[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = cf{0.f, 0.f};
+            if (live) {
+                if (s < a.T) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) v[i] = to_cf(a.train[l + G::L * i]);
+                } else {
+                    const unsigned sd = s - a.T;
+                    const float2* rec = a.in + (frame * a.S + sd) * a.D;
+                    const float p = a.pol[sd % a.n_pol];
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int code = map[l + G::L * i];
+                        if (code >= 0)
+                            v[i] = to_cf(rec[code]);
+                        else if (code < -1)
+                            v[i] = of_scale(to_cf(a.pilots[-2 - code]), p);
+                    }
+                }
+            }
+            of_transform<N, +1>(v, buf, tw, l);
+            if (live) {
+                float2* sym = a.out + (frame * per_frame + s) * sym_len;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const unsigned n = static_cast<unsigned>(G::bin(l, i));
+                    const float2 y = to_f2(of_scale(v[i], a.scale));
+                    sym[a.CP + n] = y;
+                    if (n + a.CP >= N) sym[n + a.CP - N] = y;
+                }
+            }
+        }
+    }
+}
+
+template <int N>
+__global__ __launch_bounds__(OF_WG) void ofdm_demod_kernel(const OfdmArgs a) {
+    using G = OfGeom<N>;
+    extern __shared__ __align__(16) unsigned char of_smem[];
+    cf* tw = reinterpret_cast<cf*>(of_smem);
+    cf* inv = tw + N;   // the training symbols' sum, then 1 / H_k (0 on a null bin)
+    int* map = reinterpret_cast<int*>(inv + N);
+    cf* ex = reinterpret_cast<cf*>(map + N);
+    for (int i = threadIdx.x; i < N; i += OF_WG) {
+        tw[i] = to_cf(a.tw[i]);
+        map[i] = a.map[i];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane / G::L, l = lane % G::L;
+    cf* buf = ex + wave * OF_WAVE_BUF + q * G::NP;
+    const unsigned per_frame = a.T + a.S, sym_len = N + a.CP;
+    constexpr unsigned ROUND = OF_WAVES * G::SPW;   // symbols the workgroup transforms at once
+    for (size_t item = blockIdx.x; item < a.items; item += gridDim.x) {
+        size_t frame;
+        unsigned s0, s1;
+        of_item(a, item, a.S, frame, s0, s1);
+        const float2* in = a.in + frame * per_frame * sym_len;
+        __syncthreads();   // the tables are in place; the previous item is done with inv
+        for (int k = threadIdx.x; k < N; k += OF_WG) inv[k] = a.T ? cf{0.f, 0.f} : cf{map[k] == -1 ? 0.f : a.scale, 0.f};
+        for (unsigned t0 = 0; t0 < a.T; t0 += ROUND) {   // (workgroup-uniform)
+            const unsigned t = t0 + wave * G::SPW + q;
+            cf v[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = t < a.T ? to_cf(in[t * sym_len + a.CP + l + G::L * i]) : cf{0.f, 0.f};
+            of_transform<N, -1>(v, buf, tw, l);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) buf[of_pad(G::bin(l, i))] = v[i];
+            __syncthreads();
+            const unsigned left = a.T - t0, slots = left < ROUND ? left : ROUND;
+            for (int k = threadIdx.x; k < N; k += OF_WG) {
+                cf acc = inv[k];
+                for (unsigned sl = 0; sl < slots; ++sl)   // in symbol order
+                    acc = cadd(acc, ex[(sl / G::SPW) * OF_WAVE_BUF + (sl % G::SPW) * G::NP + of_pad(k)]);
+                inv[k] = acc;
+            }
+            __syncthreads();
+        }
+        if (a.T) {
+            for (int k = threadIdx.x; k < N; k += OF_WG) {
+                const cf h = inv[k];
+                const float den = __fmaf_rn(h.x, h.x, __fmul_rn(h.y, h.y));
+                const cf num = cmulcf(to_cf(a.train[k]), h);   // T train[k] conj(sum)
+                inv[k] = map[k] == -1 ? cf{0.f, 0.f} : cf{__fdiv_rn(num.x, den), __fdiv_rn(num.y, den)};
+            }
+        }
+        __syncthreads();
+        for (unsigned g = s0 + wave * G::SPW; g < s1; g += ROUND) {   // (wave-uniform)
+            const unsigned s = g + q;
+            const bool live = s < s1;
+            cf v[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = live ? to_cf(in[(a.T + s) * sym_len + a.CP + l + G::L * i]) : cf{0.f, 0.f};
+            of_transform<N, -1>(v, buf, tw, l);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = cmulf(v[i], inv[G::bin(l, i)]);
+            if (a.cpe) {
+                cf c = cf{0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int code = map[G::bin(l, i)];
+                    if (code < -1) c = cadd(c, cmulcf(v[i], to_cf(a.pilots[-2 - code])));
+                }
+#pragma unroll
+                for (int off = 1; off < G::L; off <<= 1) c = cadd(c, cf{__shfl_xor(c.x, off), __shfl_xor(c.y, off)});
+                c = of_scale(c, a.pol[s % a.n_pol]);
+                const float mag = __fsqrt_rn(__fmaf_rn(c.x, c.x, __fmul_rn(c.y, c.y)));
+                if (mag > 0.f && mag <= 3.402823466e38f) {
+                    const cf r = cf{__fdiv_rn(c.x, mag), __fdiv_rn(c.y, mag)};
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) v[i] = cmulcf(v[i], r);
+                }
+            }
+            if (live) {
+                float2* rec = a.out + (frame * a.S + s) * a.D;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int code = map[G::bin(l, i)];
+                    if (code >= 0) rec[code] = to_f2(v[i]);
+                }
+            }
+        }
+    }
+}
+
+}  // namespace comms
+
+using namespace comms;
+
+struct comms_ofdm : Handle {
+    unsigned N = 0, CP = 0, D = 0, Q = 0, T = 0, S = 0, n_pol = 1;
+    int flags = 0;
+    float tx_scale = 0.f;
+    DevBuf<float2> tw, pilots, train, train_t;   // train_t: T train[k]
+    DevBuf<float> pol;
+    DevBuf<int> map;
+    unsigned max_grid = 1;
+};
+static_assert(!std::is_copy_constructible_v<comms_ofdm>, "a handle is never copied");
+
+namespace {
+
+bool of_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+size_t of_data_syms(const comms_ofdm* h) { return static_cast<size_t>(h->S) * h->D; }
+size_t of_frame_samples(const comms_ofdm* h) { return static_cast<size_t>(h->T + h->S) * (h->N + h->CP); }
+
+// The block rule.  `per_frame` symbols (T + S for the modulator, S for the demodulator) in rounds of 4 waves x 1024 / N: a call
+// with at least max_grid frames takes one block per frame (the demodulator then estimates every frame's channel once); a
+// call with fewer takes ceil(max_grid / n_frames) blocks per frame, if the frame has that many rounds, of whole rounds each.
+void ofdm_block(const comms_ofdm* h, size_t n_frames, unsigned per_frame, unsigned* blk, unsigned* nblk) {
+    const unsigned round = OF_WAVES * 1024u / h->N, rounds = (per_frame + round - 1) / round;
+    size_t want = n_frames && n_frames < h->max_grid ? (h->max_grid + n_frames - 1) / n_frames : 1;
+    if (want > rounds) want = rounds;
+    *blk = static_cast<unsigned>((rounds + want - 1) / want) * round;
+    *nblk = (per_frame + *blk - 1) / *blk;
+}
+size_t of_grid(const comms_ofdm* h, size_t items) { return items < 1 ? 1 : items < h->max_grid ? items : h->max_grid; }
+
+template <int N>
+comms_status_t of_launch_n(comms_ofdm* h, int direction, const OfdmArgs& a, dim3 grid, hipStream_t s) {
+    if (direction == COMMS_OFDM_MOD)
+        return launch_kernel<ofdm_mod_kernel<N>>("ofdm_mod_kernel", grid, dim3(OF_WG), ofdm_lds(N), s, h->take_events(), a);
+    return launch_kernel<ofdm_demod_kernel<N>>("ofdm_demod_kernel", grid, dim3(OF_WG), ofdm_lds(N), s, h->take_events(), a);
+}
+
+comms_status_t of_run_dev(comms_ofdm* h, int direction, const comms_c32* d_in, size_t n_frames, comms_c32* d_out, void* stream) {
+    COMMS_ARG(h != nullptr, "handle is NULL");
+    COMMS_ARG((d_in && d_out) || !n_frames, "NULL pointer");
+    COMMS_ARG(n_frames <= (size_t(1) << 40) / of_frame_samples(h), "n_frames is too large (got %zu)", n_frames);
+    COMMS_ARG(of_aligned(d_in, 8) && of_aligned(d_out, 8), "d_in and d_out must be aligned to 8 bytes");
+    if (!n_frames) return COMMS_OK;
+    const bool mod = direction == COMMS_OFDM_MOD;
+    const size_t in_n = n_frames * (mod ? of_data_syms(h) : of_frame_samples(h)), out_n = n_frames * (mod ? of_frame_samples(h) : of_data_syms(h));
+    COMMS_ARG(!ranges_overlap(d_in, in_n * sizeof(comms_c32), d_out, out_n * sizeof(comms_c32)), "the input and output records overlap");
+    COMMS_TRY(use_device(h->device));
+    OfdmArgs a{};
+    a.in = reinterpret_cast<const float2*>(d_in);
+    a.out = reinterpret_cast<float2*>(d_out);
+    a.tw = h->tw.get();
+    a.map = h->map.get();
+    a.pilots = h->pilots.get();
+    a.pol = h->pol.get();
+    a.train = mod ? h->train.get() : h->train_t.get();
+    a.n_pol = h->n_pol;
+    a.T = h->T;
+    a.S = h->S;
+    a.D = h->D;
+    a.CP = h->CP;
+    ofdm_block(h, n_frames, mod ? h->T + h->S : h->S, &a.blk, &a.nblk);
+    a.items = n_frames * a.nblk;
+    a.scale = mod ? h->tx_scale : static_cast<float>(1.0 / (static_cast<double>(h->N) * static_cast<double>(h->tx_scale)));
+    a.cpe = (h->flags & COMMS_OFDM_CPE) != 0;
+    const dim3 grid(static_cast<unsigned>(of_grid(h, a.items)));
+    hipStream_t s = h->pick(stream);
+    switch (h->N) {
+        case 64: return of_launch_n<64>(h, direction, a, grid, s);
+        case 128: return of_launch_n<128>(h, direction, a, grid, s);
+        case 256: return of_launch_n<256>(h, direction, a, grid, s);
+        case 512: return of_launch_n<512>(h, direction, a, grid, s);
+        default: return of_launch_n<1024>(h, direction, a, grid, s);
+    }
+}
+
+comms_status_t of_run(comms_ofdm* h, int direction, const comms_c32* in, size_t n_frames, comms_c32* out) {
+    COMMS_ARG(h != nullptr, "handle is NULL");
+    COMMS_ARG((in && out) || !n_frames, "NULL pointer");
+    COMMS_ARG(n_frames <= (size_t(1) << 40) / of_frame_samples(h), "n_frames is too large (got %zu)", n_frames);
+    if (!n_frames) return COMMS_OK;
+    COMMS_TRY(use_device(h->device));
+    const bool mod = direction == COMMS_OFDM_MOD;
+    const size_t in_n = n_frames * (mod ? of_data_syms(h) : of_frame_samples(h)), out_n = n_frames * (mod ? of_frame_samples(h) : of_data_syms(h));
+    return h->run_host(in, in_n * sizeof(comms_c32), out, out_n * sizeof(comms_c32), [&](void* d_in, void* d_out) {
+        return of_run_dev(h, direction, static_cast<const comms_c32*>(d_in), n_frames, static_cast<comms_c32*>(d_out), COMMS_STREAM_HANDLE);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+comms_status_t comms_ofdm_create(int32_t n_fft, int32_t n_cp, const uint8_t* carrier_kind, const comms_c32* pilots, const float* polarity,
+                                 size_t n_pol, const comms_c32* train, size_t n_train, size_t n_syms, int32_t flags, int32_t device,
+                                 comms_ofdm_t** out) {
+    COMMS_ARG(out != nullptr, "out is NULL");
+    *out = nullptr;
+    COMMS_ARG(n_fft == 64 || n_fft == 128 || n_fft == 256 || n_fft == 512 || n_fft == 1024, "n_fft must be 64, 128, 256, 512 or 1024 (got %d)",
+              n_fft);
+    COMMS_ARG(n_cp >= 0 && n_cp <= n_fft, "the prefix has 0 ... n_fft samples (got %d)", n_cp);
+    COMMS_ARG(carrier_kind != nullptr, "carrier_kind is NULL");
+    COMMS_ARG((flags & ~COMMS_OFDM_CPE) == 0, "flags must be 0 or COMMS_OFDM_CPE (got %d)", flags);
+    const size_t N = static_cast<size_t>(n_fft);
+    std::vector<int> map(N);
+    unsigned D = 0, Q = 0;
+    for (size_t k = 0; k < N; ++k) {
+        COMMS_ARG(carrier_kind[k] <= COMMS_OFDM_PILOT, "carrier_kind[%zu] must be 0 (null), 1 (data) or 2 (pilot)", k);
+        map[k] = carrier_kind[k] == COMMS_OFDM_DATA ? static_cast<int>(D++) : carrier_kind[k] == COMMS_OFDM_PILOT ? -2 - static_cast<int>(Q++) : -1;
+    }
+    COMMS_ARG(D >= 1, "the carrier map has no data carrier");
+    COMMS_ARG(pilots || !Q, "pilots is NULL with %u pilot carriers", Q);
+    COMMS_ARG(Q || !(flags & COMMS_OFDM_CPE), "COMMS_OFDM_CPE needs a pilot carrier");
+    for (unsigned p = 0; p < Q; ++p) COMMS_ARG(std::isfinite(pilots[p].re) && std::isfinite(pilots[p].im), "pilot %u is not finite", p);
+    COMMS_ARG(!polarity || (n_pol >= 1 && n_pol <= (size_t(1) << 20)), "polarity holds 1 ... 2^20 values (got %zu)", n_pol);
+    std::vector<float> pol(1, 1.0f);
+    if (polarity) {
+        pol.assign(polarity, polarity + n_pol);
+        for (size_t i = 0; i < n_pol; ++i) COMMS_ARG(std::isfinite(pol[i]), "polarity[%zu] is not finite", i);
+    }
+    COMMS_ARG(n_syms >= 1 && n_syms <= OF_MAX_FRAME && n_train <= OF_MAX_FRAME && (n_train + n_syms) * (N + static_cast<size_t>(n_cp)) <= OF_MAX_FRAME,
+              "a frame has n_syms >= 1 and at most 2^24 samples (got n_train %zu, n_syms %zu)", n_train, n_syms);
+    COMMS_ARG(train || !n_train, "train is NULL with n_train > 0");
+    std::vector<float2> tr(N, make_float2(0.f, 0.f)), tr_t(N, make_float2(0.f, 0.f));
+    if (n_train) {
+        for (size_t k = 0; k < N; ++k) {
+            COMMS_ARG(std::isfinite(train[k].re) && std::isfinite(train[k].im), "train[%zu] is not finite", k);
+            COMMS_ARG(map[k] == -1 || train[k].re != 0.f || train[k].im != 0.f, "train[%zu] is zero on a data or pilot carrier", k);
+            tr[k] = make_float2(train[k].re, train[k].im);
+            tr_t[k] = make_float2(static_cast<float>(static_cast<double>(n_train) * train[k].re),
+                                  static_cast<float>(static_cast<double>(n_train) * train[k].im));
+        }
+    }
+    std::vector<float2> tw(N);
+    for (size_t j = 0; j < N; ++j) {
+        const double t = 2.0 * 3.14159265358979323846 * static_cast<double>(j) / static_cast<double>(N);
+        tw[j] = make_float2(static_cast<float>(std::cos(t)), static_cast<float>(-std::sin(t)));
+    }
+    HandlePtr<comms_ofdm> h;
+    COMMS_TRY(make_handle(device, &h));
+    h->N = static_cast<unsigned>(n_fft);
+    h->CP = static_cast<unsigned>(n_cp);
+    h->D = D;
+    h->Q = Q;
+    h->T = static_cast<unsigned>(n_train);
+    h->S = static_cast<unsigned>(n_syms);
+    h->n_pol = static_cast<unsigned>(pol.size());
+    h->flags = flags;
+    h->tx_scale = static_cast<float>(1.0 / std::sqrt(static_cast<double>(N)));
+    COMMS_HIP_TRY(h->tw.upload(tw));
+    COMMS_HIP_TRY(h->map.upload(map));
+    COMMS_HIP_TRY(h->pol.upload(pol));
+    COMMS_HIP_TRY(h->train.upload(tr));
+    COMMS_HIP_TRY(h->train_t.upload(tr_t));
+    if (Q) COMMS_HIP_TRY(h->pilots.upload(reinterpret_cast<const float2*>(pilots), Q));
+    h->max_grid = stateless_workgroups(ofdm_lds(n_fft));
+    *out = h.release();
+    return COMMS_OK;
+}
+
+comms_status_t comms_ofdm_set_scale(comms_ofdm_t* h, float tx_scale) {
+    COMMS_ARG(h != nullptr, "handle is NULL");
+    COMMS_ARG(std::isfinite(tx_scale) && tx_scale > 0.f, "tx_scale must be finite and positive");
+    h->tx_scale = tx_scale;
+    return COMMS_OK;
+}
+
+size_t comms_ofdm_data_syms(const comms_ofdm_t* h) { return h ? of_data_syms(h) : 0; }
+size_t comms_ofdm_frame_samples(const comms_ofdm_t* h) { return h ? of_frame_samples(h) : 0; }
+
+comms_status_t comms_ofdm_mod_run_dev(comms_ofdm_t* h, const comms_c32* d_syms, size_t n_frames, comms_c32* d_out, void* stream) {
+    return of_run_dev(h, COMMS_OFDM_MOD, d_syms, n_frames, d_out, stream);
+}
+comms_status_t comms_ofdm_mod_run(comms_ofdm_t* h, const comms_c32* syms, size_t n_frames, comms_c32* out) {
+    return of_run(h, COMMS_OFDM_MOD, syms, n_frames, out);
+}
+comms_status_t comms_ofdm_demod_run_dev(comms_ofdm_t* h, const comms_c32* d_in, size_t n_frames, comms_c32* d_out, void* stream) {
+    return of_run_dev(h, COMMS_OFDM_DEMOD, d_in, n_frames, d_out, stream);
+}
+comms_status_t comms_ofdm_demod_run(comms_ofdm_t* h, const comms_c32* in, size_t n_frames, comms_c32* out) {
+    return of_run(h, COMMS_OFDM_DEMOD, in, n_frames, out);
+}
+
+comms_status_t comms_ofdm_get_kernel(const comms_ofdm_t* h, int32_t direction, size_t n_frames, char* name, size_t name_len) {
+    COMMS_ARG(h && name && name_len, "NULL argument");
+    COMMS_ARG(direction == COMMS_OFDM_MOD || direction == COMMS_OFDM_DEMOD, "direction must be COMMS_OFDM_MOD or COMMS_OFDM_DEMOD (got %d)",
+              direction);
+    const bool mod = direction == COMMS_OFDM_MOD;
+    unsigned blk, nblk;
+    ofdm_block(h, n_frames, mod ? h->T + h->S : h->S, &blk, &nblk);
+    const size_t items = n_frames * nblk;
+    std::snprintf(name, name_len,
+                  "ofdm_%s_kernel<%u> form=wave16 wg=%d n_fft=%u cp=%u data=%u pilots=%u train=%u syms=%u cpe=%d lanes_per_sym=%u syms_per_wave=%u "
+                  "block=%u blocks=%u frames=%zu items=%zu grid=%zu max_grid=%u lds=%zu",
+                  mod ? "mod" : "demod", h->N, OF_WG, h->N, h->CP, h->D, h->Q, h->T, h->S, (h->flags & COMMS_OFDM_CPE) != 0, h->N / 16, 1024 / h->N,
+                  blk, nblk, n_frames, items, of_grid(h, items), h->max_grid, ofdm_lds(static_cast<int>(h->N)));
+    return COMMS_OK;
+}
+
+comms_status_t comms_ofdm_set_timer(comms_ofdm_t* h, comms_timer_t* t) {
+    COMMS_ARG(h != nullptr, "handle is NULL");
+    h->timer = t;
+    return COMMS_OK;
+}
+
+comms_status_t comms_ofdm_destroy(comms_ofdm_t* h) { return destroy_handle(h); }
+
+}  // extern "C"

@@ -1802,6 +1802,86 @@ public:
     Result<FramesDev> run(const FramesDev& in) { return demap_dev(in, *this); }
 };
 
+// OFDM modulator and demodulator (comms_ofdm_*; additional nodes): the step between SymbolMapNode and DemapNode.  One description
+// of the frame format, one operation per direction, two shells each.
+struct OfdmSpec {
+    int n_fft;                             // 64, 128, 256, 512 or 1024
+    int n_cp;                              // 0 ... n_fft
+    std::vector<uint8_t> carrier_kind;     // n_fft entries, bin 0 = DC: COMMS_OFDM_NULL / _DATA / _PILOT
+    std::vector<Complex32> pilots = {};    // one per pilot carrier, increasing bin order
+    std::vector<float> polarity = {};      // pilots of data symbol s times polarity[s mod size]; empty = 1
+    std::vector<Complex32> train = {};     // n_fft frequency values of the training symbols (n_train > 0)
+    size_t n_train = 0;                    // identical training symbols in front of every frame
+    size_t n_syms = 1;                     // data symbols per frame
+    bool cpe = false;                      // COMMS_OFDM_CPE: the demodulator removes the pilots' common phase per symbol
+    float tx_scale = 0.0f;                 // 0 = the default, 1 / sqrt(n_fft)
+};
+template <bool MOD>
+struct OfdmOp {
+    using In = Complex32;
+    using Out = Complex32;
+    OfdmOp(const char* who, const OfdmSpec& f, int device) {
+        if (f.n_fft < 0 || f.carrier_kind.size() != static_cast<size_t>(f.n_fft))
+            throw std::runtime_error(std::string(who) + ": carrier_kind holds one entry per bin");
+        size_t q = 0;
+        for (uint8_t k : f.carrier_kind) q += k == COMMS_OFDM_PILOT;
+        if (f.pilots.size() != q) throw std::runtime_error(std::string(who) + ": pilots holds one value per pilot carrier");
+        if ((f.n_train || !f.train.empty()) && f.train.size() != f.carrier_kind.size())
+            throw std::runtime_error(std::string(who) + ": train holds one value per bin");
+        h_ = create<decltype(h_)>(who, comms_ofdm_create, static_cast<int32_t>(f.n_fft), static_cast<int32_t>(f.n_cp), f.carrier_kind.data(),
+                                  f.pilots.empty() ? nullptr : reinterpret_cast<const comms_c32*>(f.pilots.data()),
+                                  f.polarity.empty() ? nullptr : f.polarity.data(), f.polarity.size(),
+                                  f.train.empty() ? nullptr : reinterpret_cast<const comms_c32*>(f.train.data()), f.n_train, f.n_syms,
+                                  static_cast<int32_t>(f.cpe ? COMMS_OFDM_CPE : 0), device);
+        if (f.tx_scale != 0.0f) throw_on(comms_ofdm_set_scale(h_.get(), f.tx_scale), who);
+    }
+    size_t data_syms() const { return comms_ofdm_data_syms(h_.get()); }
+    size_t frame_samples() const { return comms_ofdm_frame_samples(h_.get()); }
+    size_t in_frame() const { return MOD ? data_syms() : frame_samples(); }
+    size_t out_frame() const { return MOD ? frame_samples() : data_syms(); }
+    std::string kernel(size_t n_frames) const {   // "ofdm_mod_kernel<N> ..." | "ofdm_demod_kernel<N> ..."
+        constexpr int32_t direction = MOD ? COMMS_OFDM_MOD : COMMS_OFDM_DEMOD;
+        return kernel_name([](const comms_ofdm_t* h, size_t n, char* name, size_t len) { return comms_ofdm_get_kernel(h, direction, n, name, len); },
+                           h_.get(), n_frames);
+    }
+
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const {
+        if (n % in_frame()) return COMMS_ERR_ARG;
+        m = n / in_frame() * out_frame();
+        return COMMS_OK;
+    }
+    comms_status_t launch(const Complex32* in, size_t n, Complex32* out) {
+        const auto* i = reinterpret_cast<const comms_c32*>(in);
+        auto* o = reinterpret_cast<comms_c32*>(out);
+        return MOD ? comms_ofdm_mod_run(h_.get(), i, n / in_frame(), o) : comms_ofdm_demod_run(h_.get(), i, n / in_frame(), o);
+    }
+    comms_status_t launch_dev(const Complex32* in, size_t n, Complex32* out, void* s) {
+        const auto* i = reinterpret_cast<const comms_c32*>(in);
+        auto* o = reinterpret_cast<comms_c32*>(out);
+        return MOD ? comms_ofdm_mod_run_dev(h_.get(), i, n / in_frame(), o, s) : comms_ofdm_demod_run_dev(h_.get(), i, n / in_frame(), o, s);
+    }
+    Owned<comms_ofdm_t, comms_ofdm_destroy> h_;
+};
+// OfdmMod: a message is whole records of data_syms() data-carrier values (SymbolMapNode's output with no word and no gap), the
+// output frame_samples() time samples per record.  OfdmDemod: the reverse, equalised; its output is DemapNode's input.
+class OfdmModNode : public HostNode<OfdmModNode, OfdmOp<true>> {
+public:
+    explicit OfdmModNode(const OfdmSpec& format, int device = 0) : HostNode("OfdmModNode::new", format, device) {}
+};
+class OfdmModNodeDev : public DevNode<OfdmModNodeDev, OfdmOp<true>> {
+public:
+    explicit OfdmModNodeDev(const OfdmSpec& format, int device = 0) : DevNode(device, "OfdmModNodeDev::new", format, device) {}
+};
+class OfdmDemodNode : public HostNode<OfdmDemodNode, OfdmOp<false>> {
+public:
+    explicit OfdmDemodNode(const OfdmSpec& format, int device = 0) : HostNode("OfdmDemodNode::new", format, device) {}
+};
+class OfdmDemodNodeDev : public DevNode<OfdmDemodNodeDev, OfdmOp<false>> {
+public:
+    explicit OfdmDemodNodeDev(const OfdmSpec& format, int device = 0) : DevNode(device, "OfdmDemodNodeDev::new", format, device) {}
+};
+
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)

@@ -2113,6 +2113,98 @@ class DemapNode(_Handle):
         return self
 
 
+# ------------------------------------------------------------------ OFDM modulator and demodulator
+class _Ofdm(_Handle):
+    """One OFDM frame format of comms_ofdm_*: n_fft (64 ... 1024) bins, a cyclic prefix of n_cp samples, carrier_kind[n_fft]
+    (0 null, 1 data, 2 pilot; bin 0 is DC), the base `pilots` in increasing bin order, `polarity` (floats that multiply the
+    pilots of data symbol s by polarity[s mod len]; None = 1), n_train identical training symbols of frequency values
+    train[n_fft] in front of the n_syms data symbols of every frame, cpe=True for the demodulator's pilot phase correction,
+    tx_scale (None = 1 / sqrt(n_fft))."""
+    _destroy = "comms_ofdm_destroy"
+    _direction = None
+
+    def __init__(self, n_fft, n_cp, carrier_kind, pilots=None, polarity=None, train=None, n_train=0, n_syms=1, cpe=False, tx_scale=None,
+                 device=0):
+        super().__init__()
+        self.n_fft, self.n_cp, self.n_train, self.n_syms = int(n_fft), int(n_cp), int(n_train), int(n_syms)
+        kind = np.ascontiguousarray(carrier_kind, dtype=np.uint8).ravel()
+        if kind.size != max(self.n_fft, 0):
+            raise ValueError("carrier_kind holds one entry per bin")
+        pil = None if pilots is None else _as_c64(pilots).ravel()
+        if (0 if pil is None else pil.size) != int(np.count_nonzero(kind == _lib.OFDM_PILOT)):
+            raise ValueError("pilots holds one value per pilot carrier")
+        pol = None if polarity is None else np.ascontiguousarray(polarity, dtype=np.float32).ravel()
+        tr = None if train is None else _as_c64(train).ravel()
+        if tr is not None and tr.size != kind.size:
+            raise ValueError("train holds one value per bin")
+        check(lib().comms_ofdm_create(self.n_fft, self.n_cp, _ptr(kind), None if pil is None or not pil.size else _ptr(pil),
+                                      None if pol is None else _ptr(pol), 0 if pol is None else pol.size, None if tr is None else _ptr(tr),
+                                      self.n_train, self.n_syms, _lib.OFDM_CPE if cpe else 0, device, C.byref(self._h)))
+        if tx_scale is not None:
+            self.set_scale(tx_scale)
+
+    def set_scale(self, tx_scale):
+        check(lib().comms_ofdm_set_scale(self._h, float(tx_scale)))
+        return self
+
+    @property
+    def data_syms(self):
+        """Data-carrier values per record: n_syms * (data carriers)."""
+        return lib().comms_ofdm_data_syms(self._h)
+
+    @property
+    def frame_samples(self):
+        """(n_train + n_syms) * (n_fft + n_cp)."""
+        return lib().comms_ofdm_frame_samples(self._h)
+
+    def kernel(self, n_frames):
+        """ "ofdm_mod_kernel<N> | ofdm_demod_kernel<N> form=wave16 wg=.. n_fft=.. cp=.. data=.. pilots=.. train=.. syms=.. cpe=..
+        lanes_per_sym=.. syms_per_wave=.. block=.. blocks=.. frames=.. items=.. grid=.. max_grid=.. lds=.." for a call on n_frames."""
+        buf = C.create_string_buffer(320)
+        check(lib().comms_ofdm_get_kernel(self._h, self._direction, int(n_frames), buf, 320))
+        return buf.value.decode()
+
+    def set_timer(self, timer):
+        check(lib().comms_ofdm_set_timer(self._h, timer._h if timer is not None else None))
+        return self
+
+    def _run(self, fn, x, in_len, out_len):
+        x = _as_c64(x).ravel()
+        if not in_len or x.size % in_len:
+            raise ValueError("the input must hold whole records of %d values" % in_len)
+        n_frames = x.size // in_len
+        out = np.zeros((n_frames, out_len), np.complex64)
+        check(getattr(lib(), fn)(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
+        return out
+
+
+class OfdmModNode(_Ofdm):
+    """Records of data-carrier values -> frames of time samples, behind SymbolMapNode (no word, no gap): carrier map, pilots,
+    training symbols, inverse transform scaled by tx_scale, cyclic prefix; all frames of a call in one launch.  Stateless.  run()
+    takes complex64 (n_frames, data_syms), symbol-major, and returns complex64 (n_frames, frame_samples)."""
+    _direction = _lib.OFDM_MOD
+
+    def run(self, symbols):
+        return self._run("comms_ofdm_mod_run", symbols, self.data_syms, self.frame_samples)
+
+    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
+        check(lib().comms_ofdm_mod_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+
+
+class OfdmDemodNode(_Ofdm):
+    """Frames of received samples -> records of equalised data-carrier values, in front of DemapNode(n_payload = data_syms):
+    prefix removal, transform, least-squares channel estimate from the n_train training symbols (without them: division by
+    n_fft * tx_scale), one multiply per carrier, with cpe=True the pilots' common phase removed per symbol; all frames of a call
+    in one launch.  Stateless.  run() takes complex64 (n_frames, frame_samples) and returns complex64 (n_frames, data_syms)."""
+    _direction = _lib.OFDM_DEMOD
+
+    def run(self, samples):
+        return self._run("comms_ofdm_demod_run", samples, self.frame_samples, self.data_syms)
+
+    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
+        check(lib().comms_ofdm_demod_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+
+
 def qfilt_taps(n_taps, alpha, sam_per_sym):
     """util/math.rs:307-342 (f64, real); even n_taps is incremented."""
     out = np.empty(lib().comms_qfilt_len(int(n_taps)), np.float64)
@@ -2193,7 +2285,8 @@ class KernelTimer:
                 "comms_ratematch_destroy": "comms_ratematch_set_timer",
                 "comms_crc_destroy": "comms_crc_set_timer",
                 "comms_symmap_destroy": "comms_symmap_set_timer",
-                "comms_demap_destroy": "comms_demap_set_timer"}[node._destroy]
+                "comms_demap_destroy": "comms_demap_set_timer",
+                "comms_ofdm_destroy": "comms_ofdm_set_timer"}[node._destroy]
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

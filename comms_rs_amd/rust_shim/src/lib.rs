@@ -1630,6 +1630,90 @@ impl DemapNode {
     }
 }
 
+/// One OFDM frame format (comms_ofdm_create's arguments): `carrier_kind` holds `n_fft` entries (COMMS_OFDM_NULL / _DATA /
+/// _PILOT, bin 0 = DC), `pilots` one value per pilot carrier, `polarity` the per-symbol pilot signs (empty = 1), `train` the
+/// `n_fft` frequency values of the `n_train` training symbols in front of the `n_syms` data symbols of every frame.
+pub struct OfdmFormat<'a> {
+    pub n_fft: i32,
+    pub n_cp: i32,
+    pub carrier_kind: &'a [u8],
+    pub pilots: &'a [Complex<f32>],
+    pub polarity: &'a [f32],
+    pub train: &'a [Complex<f32>],
+    pub n_train: usize,
+    pub n_syms: usize,
+    pub cpe: bool,
+}
+
+fn ofdm_create(f: &OfdmFormat) -> Result<*mut comms_ofdm_t, ()> {
+    if f.n_fft < 0 || f.carrier_kind.len() != f.n_fft as usize { return Err(()); }
+    if f.pilots.len() != f.carrier_kind.iter().filter(|&&k| k as i32 == COMMS_OFDM_PILOT).count() { return Err(()); }
+    if (f.n_train > 0 || !f.train.is_empty()) && f.train.len() != f.carrier_kind.len() { return Err(()); }
+    let mut h = ptr::null_mut();
+    let st = unsafe {
+        comms_ofdm_create(f.n_fft, f.n_cp, f.carrier_kind.as_ptr(), c32_or_null(f.pilots),
+                          if f.polarity.is_empty() { ptr::null() } else { f.polarity.as_ptr() }, f.polarity.len(),
+                          c32_or_null(f.train), f.n_train, f.n_syms, if f.cpe { COMMS_OFDM_CPE } else { 0 }, 0, &mut h)
+    };
+    if st == COMMS_OK { Ok(h) } else { Err(()) }
+}
+
+/// OFDM modulator (comms_ofdm_mod_*; an additional node), behind `SymbolMapNode` without word and gap: takes records of
+/// `data_syms()` data-carrier values and sends `frame_samples()` time samples per record -- training symbols, then the data
+/// symbols with pilots, each behind its cyclic prefix.  Stateless.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct OfdmModNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    h: *mut comms_ofdm_t,
+    pub output: NodeSender<Vec<Complex<f32>>>,
+}
+handle_node!(OfdmModNode, comms_ofdm_destroy);
+impl OfdmModNode {
+    /// `Err(())`: what comms_ofdm_create refuses.
+    pub fn new(format: &OfdmFormat) -> Result<Self, ()> {
+        Ok(OfdmModNode { input: Default::default(), h: ofdm_create(format)?, output: Default::default() })
+    }
+    pub fn data_syms(&self) -> usize { unsafe { comms_ofdm_data_syms(self.h) } }
+    pub fn frame_samples(&self) -> usize { unsafe { comms_ofdm_frame_samples(self.h) } }
+    pub fn run(&mut self, records: &[Complex<f32>]) -> Result<Vec<Complex<f32>>, NodeError> {
+        let fin = self.data_syms();
+        if fin == 0 || records.len() % fin != 0 { return Err(NodeError::DataError); }
+        let n_frames = records.len() / fin;
+        let mut out = vec![Complex::new(0.0f32, 0.0f32); n_frames * self.frame_samples()];
+        let st = unsafe { comms_ofdm_mod_run(self.h, records.as_ptr() as *const comms_c32, n_frames, out.as_mut_ptr() as *mut comms_c32) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
+/// OFDM demodulator (comms_ofdm_demod_*; an additional node), in front of `DemapNode` with `n_payload = data_syms()`: takes
+/// frames of `frame_samples()` received samples and sends the equalised data-carrier values -- channel estimate from the
+/// training symbols, one multiply per carrier, with `cpe` the pilots' common phase removed per symbol.  Stateless.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct OfdmDemodNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    h: *mut comms_ofdm_t,
+    pub output: NodeSender<Vec<Complex<f32>>>,
+}
+handle_node!(OfdmDemodNode, comms_ofdm_destroy);
+impl OfdmDemodNode {
+    /// `Err(())`: what comms_ofdm_create refuses.
+    pub fn new(format: &OfdmFormat) -> Result<Self, ()> {
+        Ok(OfdmDemodNode { input: Default::default(), h: ofdm_create(format)?, output: Default::default() })
+    }
+    pub fn data_syms(&self) -> usize { unsafe { comms_ofdm_data_syms(self.h) } }
+    pub fn frame_samples(&self) -> usize { unsafe { comms_ofdm_frame_samples(self.h) } }
+    pub fn run(&mut self, samples: &[Complex<f32>]) -> Result<Vec<Complex<f32>>, NodeError> {
+        let fin = self.frame_samples();
+        if fin == 0 || samples.len() % fin != 0 { return Err(NodeError::DataError); }
+        let n_frames = samples.len() / fin;
+        let mut out = vec![Complex::new(0.0f32, 0.0f32); n_frames * self.data_syms()];
+        let st = unsafe { comms_ofdm_demod_run(self.h, samples.as_ptr() as *const comms_c32, n_frames, out.as_mut_ptr() as *mut comms_c32) };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
 /// demodulation/nco.rs:118-133 in block form: a vector of phase errors per message.
 #[derive(Node)]
 #[pass_by_ref]
