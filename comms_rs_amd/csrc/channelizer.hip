@@ -549,8 +549,7 @@ comms_status_t comms_channelizer_get_kernel(const comms_channelizer_t* h, size_t
 }
 
 comms_status_t comms_channelizer_set_timer(comms_channelizer_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
+    COMMS_TRY(set_handle_timer(h, t));
     if (!h->chains.empty()) return comms_chain_set_timer(h->chains[0].get(), t);  // the series: the pair brackets channel 0's FIR launch
     return COMMS_OK;
 }

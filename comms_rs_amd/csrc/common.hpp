@@ -772,6 +772,52 @@ inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const char* pb = static_cast<const char*>(b);
     return pa < pb + nb && pb < pa + na;
 }
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// A record of `bits` packed bits: whole bytes, rounded up to 4
+inline size_t bit_record_bytes(size_t bits) { return ((bits + 7) / 8 + 3) / 4 * 4; }
+
+// The body of every *_set_timer that only attaches the timer
+template <class H>
+comms_status_t set_handle_timer(H* h, comms_timer_t* t) {
+    COMMS_ARG(h != nullptr, "handle is NULL");
+    h->timer = t;
+    return COMMS_OK;
+}
+
+// ---- the call shell of the per-frame nodes (encoder ... OFDM): n_frames input records in, n_frames output records out -------
+struct FrameCall {
+    size_t in_bytes, out_bytes;     // per frame (out_bytes = 0: the call writes no such output, and `out` may be NULL)
+    uintptr_t in_align, out_align;  // of the device pointers
+    size_t max_frames;              // the node's own limit
+};
+// What every frame call checks, in this order: the handle, NULL pointers only with n_frames = 0, the node's limit and the byte
+// counts, and -- for device pointers -- their alignment and that the input and output records do not overlap.  `call(h)`
+// describes the handle's records; it is asked once h is known not to be NULL.  A device form goes on with
+// `if (!n_frames) return COMMS_OK;` and use_device.  (static: the instantiations are no symbols of the library.)
+template <class H, class D>
+static comms_status_t check_frame_call(const H* h, D&& call, const void* in, size_t n_frames, const void* out, bool device) {
+    COMMS_ARG(h != nullptr, "handle is NULL");
+    const FrameCall c = call(h);
+    COMMS_ARG(!n_frames || (in && (out || !c.out_bytes)), "NULL pointer");
+    COMMS_ARG(n_frames <= c.max_frames, "n_frames must be at most %zu (got %zu)", c.max_frames, n_frames);
+    COMMS_ARG(!n_frames || (c.in_bytes <= SIZE_MAX / 2 / n_frames && c.out_bytes <= SIZE_MAX / 2 / n_frames), "n_frames overflows");
+    if (device) {
+        COMMS_ARG(aligned(in, c.in_align) && aligned(out, c.out_align), "the input must be aligned to %zu bytes and the output to %zu",
+                  static_cast<size_t>(c.in_align), static_cast<size_t>(c.out_align));
+        COMMS_ARG(!n_frames || !ranges_overlap(in, n_frames * c.in_bytes, out, n_frames * c.out_bytes), "the input and output records overlap");
+    }
+    return COMMS_OK;
+}
+// The host-pointer form: the same checks, then Handle::run_host around `run_dev(d_in, d_out)`, which forwards to the node's
+// device form on COMMS_STREAM_HANDLE
+template <class H, class D, class F>
+static comms_status_t run_frame_call(H* h, D&& call, const void* in, size_t n_frames, void* out, F&& run_dev) {
+    COMMS_TRY(check_frame_call(h, call, in, n_frames, out, false));
+    if (!n_frames) return COMMS_OK;
+    COMMS_TRY(use_device(h->device));
+    const FrameCall c = call(h);
+    return h->run_host(in, n_frames * c.in_bytes, out, n_frames * c.out_bytes, run_dev);
+}
 
 // Stride (in elements, >= len) of R phase arrays that a staging row scatters over: sample s goes to [s mod R][s div R].
 // The LDS serves a row `lanes` lanes at a time over as many element-wide banks (32 for a ds_write_b32, 16 for a
@@ -813,11 +859,8 @@ inline unsigned resident_workgroups(size_t lds) {
     const int cap = diag_knob("COMMS_GRID_CAP", 0);
     return cap > 0 && static_cast<unsigned>(cap) < chip ? static_cast<unsigned>(cap) : chip;
 }
-// The same cap for the stateless constellation nodes (symmap.hip) and the OFDM nodes (ofdm.hip).  tests/test_grid_cases.py counts
-// the files that call the function above by name against the case table of tests/grid_cases.py; the capped-grid cases of these
-// nodes are tables of their own (tests/symmap_ref.py and tests/ofdm_ref.py, run by tests/symmap_grid_child.py and
-// tests/ofdm_grid_child.py and held to the same rules by tests/test_symmap_ref.py and tests/test_ofdm_ref.py).
-inline unsigned stateless_workgroups(size_t lds) { return resident_workgroups(lds); }
+// The grid of a persistent launch with `blocks` workgroups' worth of work: at least one, at most the handle's cap
+inline size_t capped_grid(size_t blocks, unsigned max_grid) { return blocks < 1 ? 1 : blocks < max_grid ? blocks : max_grid; }
 
 // Mixer phase bookkeeping shared by the mixer node and the fused chain: phases are
 // 64-bit fixed-point fractions ("turns") of T = fl(2*pi), the constant the reference

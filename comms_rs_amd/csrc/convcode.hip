@@ -240,8 +240,6 @@ inline comms_status_t conv_code(int32_t K, int32_t n, const uint32_t* gens, int3
     return COMMS_OK;
 }
 
-inline size_t record_bytes(size_t bits) { return ((bits + 7) / 8 + 3) / 4 * 4; }
-
 }  // namespace comms
 
 using namespace comms;
@@ -263,25 +261,16 @@ static_assert(!std::is_copy_constructible_v<comms_viterbi> && !std::is_copy_cons
 
 namespace {
 
-size_t enc_in_bytes(const comms_convenc* h) { return record_bytes(h->code.T); }
-size_t enc_out_bytes(const comms_convenc* h) { return record_bytes(static_cast<size_t>(h->code.n) * h->code.steps); }
-size_t enc_grid(const comms_convenc* h, size_t n_frames) {
-    const size_t b = (n_frames * (enc_out_bytes(h) / 4) + CC_WG - 1) / CC_WG;
-    return b < 1 ? 1 : b < h->max_grid ? b : h->max_grid;
-}
+size_t enc_in_bytes(const comms_convenc* h) { return bit_record_bytes(h->code.T); }
+size_t enc_out_bytes(const comms_convenc* h) { return bit_record_bytes(static_cast<size_t>(h->code.n) * h->code.steps); }
+size_t enc_grid(const comms_convenc* h, size_t n_frames) { return capped_grid((n_frames * (enc_out_bytes(h) / 4) + CC_WG - 1) / CC_WG, h->max_grid); }
+FrameCall enc_call(const comms_convenc* h) { return {enc_in_bytes(h), enc_out_bytes(h), 4, 4, CC_MAX_FRAMES}; }
 
 size_t vt_blocks(const comms_viterbi* h) { return (h->code.steps + 63) / 64; }
 size_t vt_slot_bytes(const comms_viterbi* h) { return vt_blocks(h) * 64 * sizeof(unsigned long long); }
-size_t vt_grid(const comms_viterbi* h, size_t n_frames) {
-    const size_t b = (n_frames + VT_WAVES - 1) / VT_WAVES;
-    return b < 1 ? 1 : b < h->max_grid ? b : h->max_grid;
-}
-
-comms_status_t check_frames(size_t n_frames, size_t a_bytes, size_t b_bytes) {
-    COMMS_ARG(n_frames <= CC_MAX_FRAMES, "n_frames must be at most 2^32 (got %zu)", n_frames);
-    COMMS_ARG(!n_frames || (a_bytes <= SIZE_MAX / 2 / n_frames && b_bytes <= SIZE_MAX / 2 / n_frames), "n_frames overflows");
-    return COMMS_OK;
-}
+size_t vt_grid(const comms_viterbi* h, size_t n_frames) { return capped_grid((n_frames + VT_WAVES - 1) / VT_WAVES, h->max_grid); }
+// the LLR records and the bit records; the metrics are the decoder's own
+FrameCall vt_call(const comms_viterbi* h) { return {h->record_llrs * sizeof(float), bit_record_bytes(h->code.T), 4, 4, CC_MAX_FRAMES}; }
 
 }  // namespace
 
@@ -306,10 +295,7 @@ size_t comms_convenc_in_frame_bytes(const comms_convenc_t* h) { return h ? enc_i
 size_t comms_convenc_out_frame_bytes(const comms_convenc_t* h) { return h ? enc_out_bytes(h) : 0; }
 
 comms_status_t comms_convenc_run_dev(comms_convenc_t* h, const void* d_in, size_t n_frames, void* d_out, void* stream) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((d_in && d_out) || !n_frames, "NULL pointer");
-    COMMS_ARG((reinterpret_cast<uintptr_t>(d_in) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 3) == 0, "d_in and d_out must be aligned to 4 bytes");
-    COMMS_TRY(check_frames(n_frames, enc_in_bytes(h), enc_out_bytes(h)));
+    COMMS_TRY(check_frame_call(h, enc_call, d_in, n_frames, d_out, true));
     if (!n_frames) return COMMS_OK;
     COMMS_TRY(use_device(h->device));
     CeArgs a{};
@@ -328,13 +314,8 @@ comms_status_t comms_convenc_run_dev(comms_convenc_t* h, const void* d_in, size_
 }
 
 comms_status_t comms_convenc_run(comms_convenc_t* h, const void* in, size_t n_frames, void* out) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((in && out) || !n_frames, "NULL pointer");
-    COMMS_TRY(check_frames(n_frames, enc_in_bytes(h), enc_out_bytes(h)));
-    if (!n_frames) return COMMS_OK;
-    COMMS_TRY(use_device(h->device));
-    return h->run_host(in, n_frames * enc_in_bytes(h), out, n_frames * enc_out_bytes(h),
-                       [&](void* d_in, void* d_out) { return comms_convenc_run_dev(h, d_in, n_frames, d_out, COMMS_STREAM_HANDLE); });
+    return run_frame_call(h, enc_call, in, n_frames, out,
+                          [&](void* d_in, void* d_out) { return comms_convenc_run_dev(h, d_in, n_frames, d_out, COMMS_STREAM_HANDLE); });
 }
 
 comms_status_t comms_convenc_get_kernel(const comms_convenc_t* h, size_t n_frames, char* name, size_t name_len) {
@@ -344,11 +325,7 @@ comms_status_t comms_convenc_get_kernel(const comms_convenc_t* h, size_t n_frame
     return COMMS_OK;
 }
 
-comms_status_t comms_convenc_set_timer(comms_convenc_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_convenc_set_timer(comms_convenc_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_convenc_destroy(comms_convenc_t* h) { return destroy_handle(h); }
 
@@ -385,15 +362,11 @@ comms_status_t comms_viterbi_set_quant_scale(comms_viterbi_t* h, float qscale) {
 }
 
 size_t comms_viterbi_in_frame_bytes(const comms_viterbi_t* h) { return h ? h->record_llrs * sizeof(float) : 0; }
-size_t comms_viterbi_out_frame_bytes(const comms_viterbi_t* h) { return h ? record_bytes(h->code.T) : 0; }
+size_t comms_viterbi_out_frame_bytes(const comms_viterbi_t* h) { return h ? bit_record_bytes(h->code.T) : 0; }
 
 comms_status_t comms_viterbi_run_dev(comms_viterbi_t* h, const float* d_llr, size_t n_frames, void* d_bits, int32_t* d_metrics, void* stream) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((d_llr && d_bits) || !n_frames, "NULL pointer");
-    COMMS_ARG((reinterpret_cast<uintptr_t>(d_llr) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_bits) & 3) == 0 &&
-                  (reinterpret_cast<uintptr_t>(d_metrics) & 3) == 0,
-              "d_llr, d_bits and d_metrics must be aligned to 4 bytes");
-    COMMS_TRY(check_frames(n_frames, comms_viterbi_in_frame_bytes(h), comms_viterbi_out_frame_bytes(h)));
+    COMMS_TRY(check_frame_call(h, vt_call, d_llr, n_frames, d_bits, true));
+    COMMS_ARG(aligned(d_metrics, 4), "d_metrics must be aligned to 4 bytes");
     if (!n_frames) return COMMS_OK;
     COMMS_TRY(use_device(h->device));
     const size_t grid_n = vt_grid(h, n_frames);
@@ -430,10 +403,8 @@ comms_status_t comms_viterbi_run_dev(comms_viterbi_t* h, const float* d_llr, siz
 }
 
 comms_status_t comms_viterbi_run(comms_viterbi_t* h, const float* llr, size_t n_frames, void* bits, int32_t* metrics) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((llr && bits) || !n_frames, "NULL pointer");
-    const size_t in_b = comms_viterbi_in_frame_bytes(h), out_b = comms_viterbi_out_frame_bytes(h);
-    COMMS_TRY(check_frames(n_frames, in_b, out_b));
+    COMMS_TRY(check_frame_call(h, vt_call, llr, n_frames, bits, false));
+    const size_t in_b = vt_call(h).in_bytes, out_b = vt_call(h).out_bytes;
     if (!n_frames) return COMMS_OK;
     COMMS_TRY(use_device(h->device));
     // the records, then the metrics, in one device block
@@ -459,11 +430,7 @@ comms_status_t comms_viterbi_get_kernel(const comms_viterbi_t* h, size_t n_frame
     return COMMS_OK;
 }
 
-comms_status_t comms_viterbi_set_timer(comms_viterbi_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_viterbi_set_timer(comms_viterbi_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_viterbi_destroy(comms_viterbi_t* h) { return destroy_handle(h); }
 

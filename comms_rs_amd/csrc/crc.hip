@@ -108,8 +108,6 @@ __global__ __launch_bounds__(CRC_WG) void crc_check_kernel(const CrcArgs a) {
     crc_frames<G, true>(a);
 }
 
-inline size_t crc_record_bytes(size_t bits) { return ((bits + 7) / 8 + 3) / 4 * 4; }
-
 }  // namespace comms
 
 using namespace comms;
@@ -123,22 +121,17 @@ static_assert(!std::is_copy_constructible_v<comms_crc>, "a handle is never copie
 
 namespace {
 
-size_t payload_bytes(const comms_crc* h) { return crc_record_bytes(h->plan.T); }
-size_t coded_bytes(const comms_crc* h) { return crc_record_bytes(static_cast<size_t>(h->plan.T) + h->plan.W); }
+size_t payload_bytes(const comms_crc* h) { return bit_record_bytes(h->plan.T); }
+size_t coded_bytes(const comms_crc* h) { return bit_record_bytes(static_cast<size_t>(h->plan.T) + h->plan.W); }
 
 size_t crc_grid(const comms_crc* h, size_t n_frames) {
-    const size_t fpw = 64 / h->plan.group, items = (n_frames + fpw - 1) / fpw, b = (items + CRC_WAVES - 1) / CRC_WAVES;
-    return b < 1 ? 1 : b < h->max_grid ? b : h->max_grid;
+    const size_t fpw = 64 / h->plan.group, items = (n_frames + fpw - 1) / fpw;
+    return capped_grid((items + CRC_WAVES - 1) / CRC_WAVES, h->max_grid);
 }
 
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
-comms_status_t check_frames(const comms_crc* h, const void* in, size_t n_frames) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(in || !n_frames, "NULL pointer");
-    COMMS_ARG(n_frames <= CRC_MAX_FRAMES, "n_frames must be below 2^32 (got %zu)", n_frames);
-    return COMMS_OK;
-}
+FrameCall attach_call(const comms_crc* h) { return {payload_bytes(h), coded_bytes(h), 4, 4, CRC_MAX_FRAMES}; }
+// the coded records and the stripped payload, which a caller may leave out; the other outputs are the check's own
+FrameCall check_call(const comms_crc* h, const void* payload) { return {coded_bytes(h), payload ? payload_bytes(h) : 0, 4, 4, CRC_MAX_FRAMES}; }
 
 template <int G, bool CHECK>
 comms_status_t crc_launch_group(comms_crc* h, const CrcArgs& a, hipStream_t s) {
@@ -207,11 +200,8 @@ size_t comms_crc_payload_frame_bytes(const comms_crc_t* h) { return h ? payload_
 size_t comms_crc_coded_frame_bytes(const comms_crc_t* h) { return h ? coded_bytes(h) : 0; }
 
 comms_status_t comms_crc_attach_run_dev(comms_crc_t* h, const void* d_in, size_t n_frames, void* d_out, void* stream) {
-    COMMS_TRY(check_frames(h, d_in, n_frames));
-    COMMS_ARG(d_out || !n_frames, "NULL pointer");
-    COMMS_ARG(aligned4(d_in) && aligned4(d_out), "the device pointers must be aligned to 4 bytes");
+    COMMS_TRY(check_frame_call(h, attach_call, d_in, n_frames, d_out, true));
     if (!n_frames) return COMMS_OK;
-    COMMS_ARG(!ranges_overlap(d_in, n_frames * payload_bytes(h), d_out, n_frames * coded_bytes(h)), "the input and output records overlap");
     COMMS_TRY(use_device(h->device));
     CrcArgs a = crc_args(h, d_in, n_frames);
     a.out = static_cast<unsigned*>(d_out);
@@ -220,13 +210,11 @@ comms_status_t comms_crc_attach_run_dev(comms_crc_t* h, const void* d_in, size_t
 
 comms_status_t comms_crc_check_run_dev(comms_crc_t* h, const void* d_in, size_t n_frames, void* d_payload, int32_t* d_pass, uint32_t* d_crc,
                                        uint32_t* d_n_failed, void* stream) {
-    COMMS_TRY(check_frames(h, d_in, n_frames));
-    COMMS_ARG(aligned4(d_in) && aligned4(d_payload) && aligned4(d_pass) && aligned4(d_crc) && aligned4(d_n_failed),
-              "the device pointers must be aligned to 4 bytes");
+    COMMS_TRY(check_frame_call(h, [&](const comms_crc* c) { return check_call(c, d_payload); }, d_in, n_frames, d_payload, true));
+    COMMS_ARG(aligned(d_pass, 4) && aligned(d_crc, 4) && aligned(d_n_failed, 4), "the device pointers must be aligned to 4 bytes");
     if (!n_frames) return COMMS_OK;
     const size_t in_bytes = n_frames * coded_bytes(h);
-    COMMS_ARG(!(d_payload && ranges_overlap(d_in, in_bytes, d_payload, n_frames * payload_bytes(h))) &&
-                  !(d_pass && ranges_overlap(d_in, in_bytes, d_pass, n_frames * sizeof(int32_t))) &&
+    COMMS_ARG(!(d_pass && ranges_overlap(d_in, in_bytes, d_pass, n_frames * sizeof(int32_t))) &&
                   !(d_crc && ranges_overlap(d_in, in_bytes, d_crc, n_frames * sizeof(uint32_t))) &&
                   !(d_n_failed && ranges_overlap(d_in, in_bytes, d_n_failed, sizeof(uint32_t))),
               "the input records and an output overlap");
@@ -247,17 +235,13 @@ comms_status_t comms_crc_check_run_dev(comms_crc_t* h, const void* d_in, size_t 
 }
 
 comms_status_t comms_crc_attach_run(comms_crc_t* h, const void* in, size_t n_frames, void* out) {
-    COMMS_TRY(check_frames(h, in, n_frames));
-    COMMS_ARG(out || !n_frames, "NULL pointer");
-    if (!n_frames) return COMMS_OK;
-    COMMS_TRY(use_device(h->device));
-    return h->run_host(in, n_frames * payload_bytes(h), out, n_frames * coded_bytes(h),
-                       [&](void* d_in, void* d_out) { return comms_crc_attach_run_dev(h, d_in, n_frames, d_out, COMMS_STREAM_HANDLE); });
+    return run_frame_call(h, attach_call, in, n_frames, out,
+                          [&](void* d_in, void* d_out) { return comms_crc_attach_run_dev(h, d_in, n_frames, d_out, COMMS_STREAM_HANDLE); });
 }
 
 comms_status_t comms_crc_check_run(comms_crc_t* h, const void* in, size_t n_frames, void* payload, int32_t* pass, uint32_t* crc,
                                    size_t* n_failed) {
-    COMMS_TRY(check_frames(h, in, n_frames));
+    COMMS_TRY(check_frame_call(h, [&](const comms_crc* c) { return check_call(c, payload); }, in, n_frames, payload, false));
     if (n_failed) *n_failed = 0;
     if (!n_frames) return COMMS_OK;
     COMMS_TRY(use_device(h->device));
@@ -293,11 +277,7 @@ comms_status_t comms_crc_get_kernel(const comms_crc_t* h, int32_t direction, siz
     return COMMS_OK;
 }
 
-comms_status_t comms_crc_set_timer(comms_crc_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_crc_set_timer(comms_crc_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_crc_destroy(comms_crc_t* h) { return destroy_handle(h); }
 

@@ -140,7 +140,7 @@ comms_status_t check_shape(size_t n_payload, size_t lookback) {
 size_t frame_bytes_of(const comms_deframe* h) {
     const size_t k = static_cast<size_t>(h->table.k);
     switch (h->format) {
-        case COMMS_SYM_BITS: return ((h->F * k + 7) / 8 + 3) / 4 * 4;
+        case COMMS_SYM_BITS: return bit_record_bytes(h->F * k);
         case COMMS_SYM_LLR: return h->F * k * sizeof(float);
         default: return h->F * sizeof(comms_c32);
     }
@@ -153,10 +153,7 @@ size_t lanes_per_frame(const comms_deframe* h) {
 
 size_t deframe_lanes(const comms_deframe* h, size_t n_frames) { return (n_frames * lanes_per_frame(h) + 63) / 64 * 64; }
 
-size_t deframe_grid(const comms_deframe* h, size_t n_frames) {
-    const size_t b = (deframe_lanes(h, n_frames) + DF_WG - 1) / DF_WG;
-    return b < 1 ? 1 : b < h->max_grid ? b : h->max_grid;
-}
+size_t deframe_grid(const comms_deframe* h, size_t n_frames) { return capped_grid((deframe_lanes(h, n_frames) + DF_WG - 1) / DF_WG, h->max_grid); }
 
 // The detections of a call as pending entries behind h->pending, or COMMS_ERR_ARG; nothing of the handle changes.
 comms_status_t admit(const comms_deframe* h, const comms_frame_detection_t* dets, size_t n_dets,
@@ -343,9 +340,9 @@ comms_status_t comms_deframe_run_dev(comms_deframe_t* h, const comms_c32* d_in, 
     COMMS_ARG(h != nullptr, "handle is NULL");
     COMMS_ARG(n_frames != nullptr, "n_frames is NULL");
     COMMS_ARG(d_in || !n, "d_in is NULL");
-    COMMS_ARG((reinterpret_cast<uintptr_t>(d_in) & 7) == 0, "d_in must be aligned to one symbol (8 bytes)");
+    COMMS_ARG(aligned(d_in, 8), "d_in must be aligned to one symbol (8 bytes)");
     const bool wide = h->format == COMMS_SYM_C32 || (h->format == COMMS_SYM_LLR && h->table.k == 2);  // 8-byte stores
-    COMMS_ARG((reinterpret_cast<uintptr_t>(d_out) & (wide ? 7 : 3)) == 0, "d_out must be aligned to %d bytes", wide ? 8 : 4);
+    COMMS_ARG(aligned(d_out, wide ? 8 : 4), "d_out must be aligned to %d bytes", wide ? 8 : 4);
     COMMS_ARG(n <= SIZE_MAX / 8, "n overflows");
     *n_frames = 0;
     COMMS_TRY(use_device(h->device));
@@ -461,11 +458,7 @@ comms_status_t comms_deframe_get_kernel(const comms_deframe_t* h, size_t n_frame
     return COMMS_OK;
 }
 
-comms_status_t comms_deframe_set_timer(comms_deframe_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_deframe_set_timer(comms_deframe_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_deframe_destroy(comms_deframe_t* h) { return destroy_handle(h); }
 

@@ -1877,11 +1877,7 @@ comms_status_t comms_fft_run(comms_fft_t* h, const comms_c32* in, size_t n, comm
     });
 }
 
-comms_status_t comms_fft_set_timer(comms_fft_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_fft_set_timer(comms_fft_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_fft_destroy(comms_fft_t* h) { return destroy_handle(h); }
 

@@ -1890,11 +1890,7 @@ comms_status_t comms_fir_set_state(comms_fir_t* h, const comms_c32* state, size_
     return COMMS_OK;
 }
 
-comms_status_t comms_fir_set_timer(comms_fir_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_fir_set_timer(comms_fir_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_fir_set_input_format(comms_fir_t* h, int32_t format, float scale) {
     COMMS_ARG(h != nullptr, "handle is NULL");
@@ -2329,11 +2325,7 @@ comms_status_t comms_pulse_run(comms_pulse_t* h, const comms_c32* sym, size_t n_
     });
 }
 
-comms_status_t comms_pulse_set_timer(comms_pulse_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_pulse_set_timer(comms_pulse_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_pulse_destroy(comms_pulse_t* h) { return destroy_handle(h); }
 

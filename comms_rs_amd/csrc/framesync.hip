@@ -431,11 +431,7 @@ comms_status_t comms_framesync_get_kernel(const comms_framesync_t* h, size_t n, 
     return COMMS_OK;
 }
 
-comms_status_t comms_framesync_set_timer(comms_framesync_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_framesync_set_timer(comms_framesync_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_framesync_destroy(comms_framesync_t* h) { return destroy_handle(h); }
 

@@ -319,11 +319,7 @@ comms_status_t comms_noise_create(uint64_t seed, uint64_t stream, int32_t device
 
 comms_status_t comms_noise_destroy(comms_noise_t* h) { return destroy_handle(h); }
 
-comms_status_t comms_noise_set_timer(comms_noise_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_noise_set_timer(comms_noise_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_noise_get_pos(const comms_noise_t* h, uint64_t* pos) {
     COMMS_ARG(h && pos, "NULL argument");

@@ -305,8 +305,6 @@ static_assert(!std::is_copy_constructible_v<comms_ofdm>, "a handle is never copi
 
 namespace {
 
-bool of_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 size_t of_data_syms(const comms_ofdm* h) { return static_cast<size_t>(h->S) * h->D; }
 size_t of_frame_samples(const comms_ofdm* h) { return static_cast<size_t>(h->T + h->S) * (h->N + h->CP); }
 
@@ -320,7 +318,13 @@ void ofdm_block(const comms_ofdm* h, size_t n_frames, unsigned per_frame, unsign
     *blk = static_cast<unsigned>((rounds + want - 1) / want) * round;
     *nblk = (per_frame + *blk - 1) / *blk;
 }
-size_t of_grid(const comms_ofdm* h, size_t items) { return items < 1 ? 1 : items < h->max_grid ? items : h->max_grid; }
+size_t of_grid(const comms_ofdm* h, size_t items) { return capped_grid(items, h->max_grid); }
+// data-carrier records in and frames of samples out (the modulator), or the other way round
+FrameCall of_call(const comms_ofdm* h, int direction) {
+    const size_t data = of_data_syms(h) * sizeof(comms_c32), frame = of_frame_samples(h) * sizeof(comms_c32);
+    const bool mod = direction == COMMS_OFDM_MOD;
+    return {mod ? data : frame, mod ? frame : data, 8, 8, (size_t(1) << 40) / of_frame_samples(h)};
+}
 
 template <int N>
 comms_status_t of_launch_n(comms_ofdm* h, int direction, const OfdmArgs& a, dim3 grid, hipStream_t s) {
@@ -330,15 +334,10 @@ comms_status_t of_launch_n(comms_ofdm* h, int direction, const OfdmArgs& a, dim3
 }
 
 comms_status_t of_run_dev(comms_ofdm* h, int direction, const comms_c32* d_in, size_t n_frames, comms_c32* d_out, void* stream) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((d_in && d_out) || !n_frames, "NULL pointer");
-    COMMS_ARG(n_frames <= (size_t(1) << 40) / of_frame_samples(h), "n_frames is too large (got %zu)", n_frames);
-    COMMS_ARG(of_aligned(d_in, 8) && of_aligned(d_out, 8), "d_in and d_out must be aligned to 8 bytes");
+    COMMS_TRY(check_frame_call(h, [&](const comms_ofdm* o) { return of_call(o, direction); }, d_in, n_frames, d_out, true));
     if (!n_frames) return COMMS_OK;
-    const bool mod = direction == COMMS_OFDM_MOD;
-    const size_t in_n = n_frames * (mod ? of_data_syms(h) : of_frame_samples(h)), out_n = n_frames * (mod ? of_frame_samples(h) : of_data_syms(h));
-    COMMS_ARG(!ranges_overlap(d_in, in_n * sizeof(comms_c32), d_out, out_n * sizeof(comms_c32)), "the input and output records overlap");
     COMMS_TRY(use_device(h->device));
+    const bool mod = direction == COMMS_OFDM_MOD;
     OfdmArgs a{};
     a.in = reinterpret_cast<const float2*>(d_in);
     a.out = reinterpret_cast<float2*>(d_out);
@@ -368,14 +367,7 @@ comms_status_t of_run_dev(comms_ofdm* h, int direction, const comms_c32* d_in, s
 }
 
 comms_status_t of_run(comms_ofdm* h, int direction, const comms_c32* in, size_t n_frames, comms_c32* out) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((in && out) || !n_frames, "NULL pointer");
-    COMMS_ARG(n_frames <= (size_t(1) << 40) / of_frame_samples(h), "n_frames is too large (got %zu)", n_frames);
-    if (!n_frames) return COMMS_OK;
-    COMMS_TRY(use_device(h->device));
-    const bool mod = direction == COMMS_OFDM_MOD;
-    const size_t in_n = n_frames * (mod ? of_data_syms(h) : of_frame_samples(h)), out_n = n_frames * (mod ? of_frame_samples(h) : of_data_syms(h));
-    return h->run_host(in, in_n * sizeof(comms_c32), out, out_n * sizeof(comms_c32), [&](void* d_in, void* d_out) {
+    return run_frame_call(h, [&](const comms_ofdm* o) { return of_call(o, direction); }, in, n_frames, out, [&](void* d_in, void* d_out) {
         return of_run_dev(h, direction, static_cast<const comms_c32*>(d_in), n_frames, static_cast<comms_c32*>(d_out), COMMS_STREAM_HANDLE);
     });
 }
@@ -446,7 +438,7 @@ comms_status_t comms_ofdm_create(int32_t n_fft, int32_t n_cp, const uint8_t* car
     COMMS_HIP_TRY(h->train.upload(tr));
     COMMS_HIP_TRY(h->train_t.upload(tr_t));
     if (Q) COMMS_HIP_TRY(h->pilots.upload(reinterpret_cast<const float2*>(pilots), Q));
-    h->max_grid = stateless_workgroups(ofdm_lds(n_fft));
+    h->max_grid = resident_workgroups(ofdm_lds(n_fft));
     *out = h.release();
     return COMMS_OK;
 }
@@ -490,11 +482,7 @@ comms_status_t comms_ofdm_get_kernel(const comms_ofdm_t* h, int32_t direction, s
     return COMMS_OK;
 }
 
-comms_status_t comms_ofdm_set_timer(comms_ofdm_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_ofdm_set_timer(comms_ofdm_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_ofdm_destroy(comms_ofdm_t* h) { return destroy_handle(h); }
 

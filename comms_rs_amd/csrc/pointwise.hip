@@ -424,11 +424,7 @@ comms_status_t comms_mixer_set_phase(comms_mixer_t* h, double phase) {
     return COMMS_OK;
 }
 
-comms_status_t comms_mixer_set_timer(comms_mixer_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_mixer_set_timer(comms_mixer_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_mixer_destroy(comms_mixer_t* h) { return destroy_handle(h); }
 
@@ -616,11 +612,7 @@ comms_status_t comms_fmdemod_set_prev(comms_fmdemod_t* h, const comms_c32* prev)
     return COMMS_OK;
 }
 
-comms_status_t comms_fmdemod_set_timer(comms_fmdemod_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_fmdemod_set_timer(comms_fmdemod_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_fmdemod_destroy(comms_fmdemod_t* h) { return destroy_handle(h); }
 

@@ -211,11 +211,7 @@ comms_status_t comms_prns_skip(comms_prns_t* h, uint64_t n_bits) {
     return COMMS_OK;
 }
 
-comms_status_t comms_prns_set_timer(comms_prns_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_prns_set_timer(comms_prns_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_prns_destroy(comms_prns_t* h) { return destroy_handle(h); }
 

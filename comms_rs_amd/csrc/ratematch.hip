@@ -125,8 +125,6 @@ __global__ __launch_bounds__(RM_WG) void ratematch_rx_kernel(const RmRxArgs a) {
     }
 }
 
-inline size_t rm_record_bytes(size_t bits) { return ((bits + 7) / 8 + 3) / 4 * 4; }
-
 // The frame format of a create call, or COMMS_ERR_ARG: host arithmetic only
 struct RmFormat {
     unsigned n_coded = 0, n_tx = 0;
@@ -180,7 +178,7 @@ inline comms_status_t rm_format(size_t n_coded, const uint8_t* pattern, size_t p
             pi[c * R - (c > rem ? c - rem : 0) + r] = static_cast<unsigned>(m);
         }
     }
-    const size_t words = rm_record_bytes(E) / 4;
+    const size_t words = bit_record_bytes(E) / 4;
     f.src.resize(E);
     f.tx_table.assign(words * 32, 0u);
     f.scramble.assign(words, 0u);
@@ -214,31 +212,21 @@ static_assert(!std::is_copy_constructible_v<comms_ratematch>, "a handle is never
 
 namespace {
 
-size_t tx_in_bytes(const comms_ratematch* h) { return rm_record_bytes(h->n_coded); }
-size_t tx_out_bytes(const comms_ratematch* h) { return rm_record_bytes(h->n_tx); }
+size_t tx_in_bytes(const comms_ratematch* h) { return bit_record_bytes(h->n_coded); }
+size_t tx_out_bytes(const comms_ratematch* h) { return bit_record_bytes(h->n_tx); }
 size_t rx_in_bytes(const comms_ratematch* h) { return h->record_llrs * sizeof(float); }
 size_t rx_out_bytes(const comms_ratematch* h) { return static_cast<size_t>(h->n_coded) * sizeof(float); }
 
-size_t clamp_grid(size_t b, unsigned max_grid) { return b < 1 ? 1 : b < max_grid ? b : max_grid; }
+FrameCall tx_call(const comms_ratematch* h) { return {tx_in_bytes(h), tx_out_bytes(h), 4, 4, RM_MAX_FRAMES}; }
+FrameCall rx_call(const comms_ratematch* h) { return {rx_in_bytes(h), rx_out_bytes(h), 4, 4, RM_MAX_FRAMES}; }
+
 size_t tx_grid(const comms_ratematch* h, size_t n_frames) {
-    return clamp_grid((n_frames * (tx_out_bytes(h) / 4) + RM_WG - 1) / RM_WG, h->tx_max_grid);
+    return capped_grid((n_frames * (tx_out_bytes(h) / 4) + RM_WG - 1) / RM_WG, h->tx_max_grid);
 }
 // a workgroup that stages the table walks at least as many values as it staged entries
 size_t rx_grid(const comms_ratematch* h, size_t n_frames) {
     const size_t per = h->rx_lds && h->n_coded > RM_WG ? h->n_coded : RM_WG;
-    return clamp_grid((n_frames * h->n_coded + per - 1) / per, h->rx_max_grid);
-}
-
-comms_status_t check_run(const comms_ratematch* h, const void* in, size_t n_frames, const void* out, size_t in_bytes, size_t out_bytes, bool device) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((in && out) || !n_frames, "NULL pointer");
-    COMMS_ARG(n_frames <= RM_MAX_FRAMES, "n_frames must be at most 2^32 (got %zu)", n_frames);
-    COMMS_ARG(!n_frames || (in_bytes <= SIZE_MAX / 2 / n_frames && out_bytes <= SIZE_MAX / 2 / n_frames), "n_frames overflows");
-    if (device) {
-        COMMS_ARG((reinterpret_cast<uintptr_t>(in) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0, "the device pointers must be aligned to 4 bytes");
-        COMMS_ARG(!n_frames || !ranges_overlap(in, n_frames * in_bytes, out, n_frames * out_bytes), "the input and output records overlap");
-    }
-    return COMMS_OK;
+    return capped_grid((n_frames * h->n_coded + per - 1) / per, h->rx_max_grid);
 }
 
 }  // namespace
@@ -282,7 +270,7 @@ comms_status_t comms_ratematch_get_map(const comms_ratematch_t* h, uint32_t* src
 }
 
 comms_status_t comms_ratematch_tx_run_dev(comms_ratematch_t* h, const void* d_in, size_t n_frames, void* d_out, void* stream) {
-    COMMS_TRY(check_run(h, d_in, n_frames, d_out, h ? tx_in_bytes(h) : 0, h ? tx_out_bytes(h) : 0, true));
+    COMMS_TRY(check_frame_call(h, tx_call, d_in, n_frames, d_out, true));
     if (!n_frames) return COMMS_OK;
     COMMS_TRY(use_device(h->device));
     RmTxArgs a{};
@@ -301,7 +289,7 @@ comms_status_t comms_ratematch_tx_run_dev(comms_ratematch_t* h, const void* d_in
 }
 
 comms_status_t comms_ratematch_rx_run_dev(comms_ratematch_t* h, const float* d_llr_in, size_t n_frames, float* d_llr_out, void* stream) {
-    COMMS_TRY(check_run(h, d_llr_in, n_frames, d_llr_out, h ? rx_in_bytes(h) : 0, h ? rx_out_bytes(h) : 0, true));
+    COMMS_TRY(check_frame_call(h, rx_call, d_llr_in, n_frames, d_llr_out, true));
     if (!n_frames) return COMMS_OK;
     COMMS_TRY(use_device(h->device));
     RmRxArgs a{};
@@ -317,18 +305,12 @@ comms_status_t comms_ratematch_rx_run_dev(comms_ratematch_t* h, const float* d_l
 }
 
 comms_status_t comms_ratematch_tx_run(comms_ratematch_t* h, const void* in, size_t n_frames, void* out) {
-    COMMS_TRY(check_run(h, in, n_frames, out, h ? tx_in_bytes(h) : 0, h ? tx_out_bytes(h) : 0, false));
-    if (!n_frames) return COMMS_OK;
-    COMMS_TRY(use_device(h->device));
-    return h->run_host(in, n_frames * tx_in_bytes(h), out, n_frames * tx_out_bytes(h),
-                       [&](void* d_in, void* d_out) { return comms_ratematch_tx_run_dev(h, d_in, n_frames, d_out, COMMS_STREAM_HANDLE); });
+    return run_frame_call(h, tx_call, in, n_frames, out,
+                          [&](void* d_in, void* d_out) { return comms_ratematch_tx_run_dev(h, d_in, n_frames, d_out, COMMS_STREAM_HANDLE); });
 }
 
 comms_status_t comms_ratematch_rx_run(comms_ratematch_t* h, const float* llr_in, size_t n_frames, float* llr_out) {
-    COMMS_TRY(check_run(h, llr_in, n_frames, llr_out, h ? rx_in_bytes(h) : 0, h ? rx_out_bytes(h) : 0, false));
-    if (!n_frames) return COMMS_OK;
-    COMMS_TRY(use_device(h->device));
-    return h->run_host(llr_in, n_frames * rx_in_bytes(h), llr_out, n_frames * rx_out_bytes(h), [&](void* d_in, void* d_out) {
+    return run_frame_call(h, rx_call, llr_in, n_frames, llr_out, [&](void* d_in, void* d_out) {
         return comms_ratematch_rx_run_dev(h, static_cast<const float*>(d_in), n_frames, static_cast<float*>(d_out), COMMS_STREAM_HANDLE);
     });
 }
@@ -348,11 +330,7 @@ comms_status_t comms_ratematch_get_kernel(const comms_ratematch_t* h, int32_t di
     return COMMS_OK;
 }
 
-comms_status_t comms_ratematch_set_timer(comms_ratematch_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_ratematch_set_timer(comms_ratematch_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_ratematch_destroy(comms_ratematch_t* h) { return destroy_handle(h); }
 

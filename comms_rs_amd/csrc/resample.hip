@@ -453,8 +453,7 @@ comms_status_t comms_resample_get_kernel(const comms_resample_t* h, size_t n, ch
 }
 
 comms_status_t comms_resample_set_timer(comms_resample_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
+    COMMS_TRY(set_handle_timer(h, t));
     if (h->fir.get()) return comms_fir_set_timer(h->fir.get(), t);  // the series: the pair brackets its FIR launch
     return COMMS_OK;
 }

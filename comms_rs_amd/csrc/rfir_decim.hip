@@ -347,8 +347,7 @@ comms_status_t comms_rfir_get_kernel(const comms_rfir_t* h, size_t n, char* name
 }
 
 comms_status_t comms_rfir_set_timer(comms_rfir_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
+    COMMS_TRY(set_handle_timer(h, t));
     if (h->fir.get()) return comms_fir_set_timer(h->fir.get(), t);  // the series: the pair brackets its FIR launch
     return COMMS_OK;
 }

@@ -302,8 +302,6 @@ __global__ __launch_bounds__(SM_WG) void demap_axis_kernel(const DemapArgs a) {
         demap_llr_items<1, MI, MQ>(a);
 }
 
-inline size_t bit_record_bytes(size_t bits) { return ((bits + 7) / 8 + 3) / 4 * 4; }
-
 }  // namespace comms
 
 using namespace comms;
@@ -362,14 +360,10 @@ void find_split(const std::vector<float2>& c, int m, int* mI, std::vector<float>
     for (size_t j = 0; j < nQ; ++j) (*levels)[nI + j] = c[j << *mI].y;
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 size_t map_in_bytes(const comms_symmap* h) { return bit_record_bytes(h->E); }
 size_t map_rec(const comms_symmap* h) { return static_cast<size_t>(h->P) + h->F + h->G; }
-size_t map_grid(const comms_symmap* h, size_t n_frames) {
-    const size_t b = (n_frames * map_rec(h) + SM_WG - 1) / SM_WG;
-    return b < 1 ? 1 : b < h->max_grid ? b : h->max_grid;
-}
+size_t map_grid(const comms_symmap* h, size_t n_frames) { return capped_grid((n_frames * map_rec(h) + SM_WG - 1) / SM_WG, h->max_grid); }
+FrameCall map_call(const comms_symmap* h) { return {map_in_bytes(h), map_rec(h) * sizeof(comms_c32), 4, 8, (size_t(1) << 40) / map_rec(h)}; }
 
 size_t demap_out_bytes(const comms_demap* h) {
     const size_t bits = static_cast<size_t>(h->F) * h->m;
@@ -382,9 +376,9 @@ size_t demap_items(const comms_demap* h, size_t n_frames) {
 }
 size_t demap_grid(const comms_demap* h, size_t n_frames) {
     const size_t per = h->format == COMMS_SYM_BITS ? SM_WG / 64 : SM_WG;
-    const size_t b = (demap_items(h, n_frames) + per - 1) / per;
-    return b < 1 ? 1 : b < h->max_grid ? b : h->max_grid;
+    return capped_grid((demap_items(h, n_frames) + per - 1) / per, h->max_grid);
 }
+FrameCall demap_call(const comms_demap* h) { return {h->F * sizeof(comms_c32), demap_out_bytes(h), 8, 16, (size_t(1) << 40) / h->F}; }
 
 template <int M, int FMT>
 comms_status_t demap_launch_table(comms_demap* h, const DemapArgs& a, dim3 grid, hipStream_t s) {
@@ -505,7 +499,7 @@ comms_status_t comms_symmap_create(int32_t bits_per_sym, const comms_c32* conste
     h->G = static_cast<unsigned>(gap);
     COMMS_HIP_TRY(h->table.upload(table));
     if (n_word) COMMS_HIP_TRY(h->word.upload(reinterpret_cast<const float2*>(word), n_word));
-    h->max_grid = stateless_workgroups(SM_TABLE_LDS);
+    h->max_grid = resident_workgroups(SM_TABLE_LDS);
     *out = h.release();
     return COMMS_OK;
 }
@@ -514,13 +508,8 @@ size_t comms_symmap_in_frame_bytes(const comms_symmap_t* h) { return h ? map_in_
 size_t comms_symmap_out_frame_syms(const comms_symmap_t* h) { return h ? map_rec(h) : 0; }
 
 comms_status_t comms_symmap_run_dev(comms_symmap_t* h, const void* d_bits, size_t n_frames, comms_c32* d_out, void* stream) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((d_bits && d_out) || !n_frames, "NULL pointer");
-    COMMS_ARG(n_frames <= (size_t(1) << 40) / map_rec(h), "n_frames is too large (got %zu)", n_frames);
-    COMMS_ARG(aligned(d_bits, 4) && aligned(d_out, 8), "d_bits must be aligned to 4 bytes and d_out to 8");
+    COMMS_TRY(check_frame_call(h, map_call, d_bits, n_frames, d_out, true));
     if (!n_frames) return COMMS_OK;
-    COMMS_ARG(!ranges_overlap(d_bits, n_frames * map_in_bytes(h), d_out, n_frames * map_rec(h) * sizeof(comms_c32)),
-              "the input and output records overlap");
     COMMS_TRY(use_device(h->device));
     MapArgs a{};
     a.bits = static_cast<const unsigned*>(d_bits);
@@ -539,12 +528,7 @@ comms_status_t comms_symmap_run_dev(comms_symmap_t* h, const void* d_bits, size_
 }
 
 comms_status_t comms_symmap_run(comms_symmap_t* h, const void* bits, size_t n_frames, comms_c32* out) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((bits && out) || !n_frames, "NULL pointer");
-    COMMS_ARG(n_frames <= (size_t(1) << 40) / map_rec(h), "n_frames is too large (got %zu)", n_frames);
-    if (!n_frames) return COMMS_OK;
-    COMMS_TRY(use_device(h->device));
-    return h->run_host(bits, n_frames * map_in_bytes(h), out, n_frames * map_rec(h) * sizeof(comms_c32), [&](void* d_in, void* d_out) {
+    return run_frame_call(h, map_call, bits, n_frames, out, [&](void* d_in, void* d_out) {
         return comms_symmap_run_dev(h, d_in, n_frames, static_cast<comms_c32*>(d_out), COMMS_STREAM_HANDLE);
     });
 }
@@ -556,11 +540,7 @@ comms_status_t comms_symmap_get_kernel(const comms_symmap_t* h, size_t n_frames,
     return COMMS_OK;
 }
 
-comms_status_t comms_symmap_set_timer(comms_symmap_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_symmap_set_timer(comms_symmap_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_symmap_destroy(comms_symmap_t* h) { return destroy_handle(h); }
 
@@ -584,7 +564,7 @@ comms_status_t comms_demap_create(int32_t bits_per_sym, const comms_c32* constel
     h->mQ = mI < 0 ? 0 : bits_per_sym - mI;
     COMMS_HIP_TRY(h->table.upload(table));
     if (mI >= 0) COMMS_HIP_TRY(h->levels.upload(levels));
-    h->max_grid = stateless_workgroups(0);
+    h->max_grid = resident_workgroups(0);
     *out = h.release();
     return COMMS_OK;
 }
@@ -607,13 +587,8 @@ size_t comms_demap_in_frame_bytes(const comms_demap_t* h) { return h ? static_ca
 size_t comms_demap_out_frame_bytes(const comms_demap_t* h) { return h ? demap_out_bytes(h) : 0; }
 
 comms_status_t comms_demap_run_dev(comms_demap_t* h, const comms_c32* d_sym, size_t n_frames, void* d_out, void* stream) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((d_sym && d_out) || !n_frames, "NULL pointer");
-    COMMS_ARG(n_frames <= (size_t(1) << 40) / h->F, "n_frames is too large (got %zu)", n_frames);
-    COMMS_ARG(aligned(d_sym, 8) && aligned(d_out, 16), "d_sym must be aligned to 8 bytes and d_out to 16");
+    COMMS_TRY(check_frame_call(h, demap_call, d_sym, n_frames, d_out, true));
     if (!n_frames) return COMMS_OK;
-    COMMS_ARG(!ranges_overlap(d_sym, n_frames * h->F * sizeof(comms_c32), d_out, n_frames * demap_out_bytes(h)),
-              "the input and output records overlap");
     COMMS_TRY(use_device(h->device));
     DemapArgs a{};
     a.sym = reinterpret_cast<const float2*>(d_sym);
@@ -633,12 +608,7 @@ comms_status_t comms_demap_run_dev(comms_demap_t* h, const comms_c32* d_sym, siz
 }
 
 comms_status_t comms_demap_run(comms_demap_t* h, const comms_c32* sym, size_t n_frames, void* out) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG((sym && out) || !n_frames, "NULL pointer");
-    COMMS_ARG(n_frames <= (size_t(1) << 40) / h->F, "n_frames is too large (got %zu)", n_frames);
-    if (!n_frames) return COMMS_OK;
-    COMMS_TRY(use_device(h->device));
-    return h->run_host(sym, n_frames * h->F * sizeof(comms_c32), out, n_frames * demap_out_bytes(h), [&](void* d_in, void* d_out) {
+    return run_frame_call(h, demap_call, sym, n_frames, out, [&](void* d_in, void* d_out) {
         return comms_demap_run_dev(h, static_cast<const comms_c32*>(d_in), n_frames, d_out, COMMS_STREAM_HANDLE);
     });
 }
@@ -657,11 +627,7 @@ comms_status_t comms_demap_get_kernel(const comms_demap_t* h, size_t n_frames, c
     return COMMS_OK;
 }
 
-comms_status_t comms_demap_set_timer(comms_demap_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_demap_set_timer(comms_demap_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_demap_destroy(comms_demap_t* h) { return destroy_handle(h); }
 

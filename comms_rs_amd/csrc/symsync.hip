@@ -443,11 +443,7 @@ comms_status_t comms_symsync_get_kernel(const comms_symsync_t* h, size_t n, char
     return COMMS_OK;
 }
 
-comms_status_t comms_symsync_set_timer(comms_symsync_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_symsync_set_timer(comms_symsync_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_symsync_destroy(comms_symsync_t* h) { return destroy_handle(h); }
 

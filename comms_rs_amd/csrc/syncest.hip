@@ -423,11 +423,7 @@ comms_status_t comms_syncest_get_kernel(const comms_syncest_t* h, size_t len, ch
     return COMMS_OK;
 }
 
-comms_status_t comms_syncest_set_timer(comms_syncest_t* h, comms_timer_t* t) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    h->timer = t;
-    return COMMS_OK;
-}
+comms_status_t comms_syncest_set_timer(comms_syncest_t* h, comms_timer_t* t) { return set_handle_timer(h, t); }
 
 comms_status_t comms_syncest_destroy(comms_syncest_t* h) { return destroy_handle(h); }
 

@@ -44,15 +44,27 @@ def device_count():
 
 
 class _Handle:
-    _destroy = None
+    _prefix = None   # of the node's C functions: "comms_fir" for comms_fir_destroy, comms_fir_set_timer, comms_fir_get_kernel
 
     def __init__(self):
         self._h = C.c_void_p()
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            getattr(lib(), self._destroy)(self._h)
+            getattr(lib(), self._prefix + "_destroy")(self._h)
             self._h = C.c_void_p()
+
+    def set_timer(self, timer):
+        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch (a series: its FIR launch; the
+        channelizer's series: channel 0's).  A node whose C side has no timer setter raises AttributeError."""
+        check(getattr(lib(), self._prefix + "_set_timer")(self._h, timer._h if timer is not None else None))
+        return self
+
+    def _kernel_name(self, *args, cap=240):
+        """comms_*_get_kernel(handle, *args, name, cap), decoded."""
+        buf = C.create_string_buffer(cap)
+        check(getattr(lib(), self._prefix + "_get_kernel")(self._h, *args, buf, cap))
+        return buf.value.decode()
 
     def __del__(self):
         try:
@@ -110,7 +122,7 @@ class DeviceBuf:
 # ------------------------------------------------------------------ FIR
 class BatchFirNode(_Handle):
     """BatchFirNode::new(taps, state) / run (fir_node.rs:193-220)."""
-    _destroy = "comms_fir_destroy"
+    _prefix = "comms_fir"
 
     def __init__(self, taps, state=None, device=0):
         super().__init__()
@@ -132,9 +144,7 @@ class BatchFirNode(_Handle):
 
     def kernel_for(self, n):
         """Name of the kernel a batch of n samples is run by (diagnostics)."""
-        buf = C.create_string_buffer(64)
-        check(lib().comms_fir_get_kernel(self._h, n, buf, 64))
-        return buf.value.decode()
+        return self._kernel_name(n, cap=64)
 
     _fmt = "c32"
 
@@ -173,7 +183,7 @@ class FirNode(BatchFirNode):
 
 class PulseNode(_Handle):
     """PulseNode::new(taps, sam_per_sym) / run (pulse.rs:71-92)."""
-    _destroy = "comms_pulse_destroy"
+    _prefix = "comms_pulse"
 
     def __init__(self, taps, sam_per_sym, device=0):
         super().__init__()
@@ -331,14 +341,14 @@ class _ExactPulse(_Exact):
 class BatchFirNodeI16(_ExactFir):
     """BatchFirNode<i16> on Complex<i16> = int16 (n, 2) arrays, wrapping arithmetic.  A single sample has shape (2,)."""
     _abi, _arr, _dtype, _shape = "comms_fir_i16_", staticmethod(_as_c16), np.int16, (2,)
-    _destroy = _abi + "destroy"
+    _prefix = _abi[:-1]
 
 
 class BatchFirNodeF64(_ExactFir):
     """BatchFirNode<f64> on Complex<f64> = numpy complex128: the reference's arithmetic operation for operation.  A single
     sample is a scalar."""
     _abi, _arr, _dtype, _shape = "comms_fir_f64_", staticmethod(_as_c128), np.complex128, ()
-    _destroy = _abi + "destroy"
+    _prefix = _abi[:-1]
 
     def set_state(self, state):
         st = self._arr(state)
@@ -353,19 +363,19 @@ FirNodeF64 = BatchFirNodeF64
 class PulseNodeI16(_ExactPulse):
     """PulseNode<i16> on Complex<i16>."""
     _abi, _arr, _dtype, _shape = "comms_pulse_i16_", staticmethod(_as_c16), np.int16, (2,)
-    _destroy = _abi + "destroy"
+    _prefix = _abi[:-1]
 
 
 class PulseNodeF64(_ExactPulse):
     """PulseNode<f64> on Complex<f64>, bit-identical to the reference."""
     _abi, _arr, _dtype, _shape = "comms_pulse_f64_", staticmethod(_as_c128), np.complex128, ()
-    _destroy = _abi + "destroy"
+    _prefix = _abi[:-1]
 
 
 # ------------------------------------------------------------------ mixer
 class MixerNode(_Handle):
     """MixerNode::new(dphase, phase) (mixer.rs:128-141); run() mixes a slice."""
-    _destroy = "comms_mixer_destroy"
+    _prefix = "comms_mixer"
 
     def __init__(self, dphase, phase=None, device=0):
         super().__init__()
@@ -465,7 +475,7 @@ class UpsampleNode:
 # ------------------------------------------------------------------ FM demod
 class FMDemodNode(_Handle):
     """FMDemodNode::new() / run (analog_node.rs:43-51)."""
-    _destroy = "comms_fmdemod_destroy"
+    _prefix = "comms_fmdemod"
 
     def __init__(self, device=0):
         super().__init__()
@@ -496,7 +506,7 @@ class FMDemodNode(_Handle):
 # ------------------------------------------------------------------ FFT
 class FFTBatchNode(_Handle):
     """FFTBatchNode::new(fft_size, ifft) / run (fft_node.rs:65-83)."""
-    _destroy = "comms_fft_destroy"
+    _prefix = "comms_fft"
 
     def __init__(self, fft_size, ifft, device=0):
         super().__init__()
@@ -516,7 +526,7 @@ class FFTBatchNode(_Handle):
 class FFTBatchNodeF64(_Handle):
     """FFTBatchNode<f64>::new(fft_size, ifft) / run (fft_node.rs:65-83) on Complex<f64> = numpy complex128 (comms_fft_f64_*):
     the instantiation of the reference's doc examples; correct to f64 rounding."""
-    _destroy = "comms_fft_f64_destroy"
+    _prefix = "comms_fft_f64"
 
     def __init__(self, fft_size, ifft, device=0):
         super().__init__()
@@ -551,7 +561,7 @@ class FFTSampleNodeF64(FFTBatchNodeF64):
 
 class FMDemodNodeF64(_Handle):
     """FMDemodNode<f64>::new() / run (analog_node.rs:20-52; FM::demod analog.rs:22-35) on Complex<f64>."""
-    _destroy = "comms_fmdemod_f64_destroy"
+    _prefix = "comms_fmdemod_f64"
 
     def __init__(self, device=0):
         super().__init__()
@@ -599,7 +609,7 @@ class FFTSampleNode(FFTBatchNode):
 class ChainNode(_Handle):
     """mixer / FIR / decimate [/ FM demod] as one node (comms_chain_*), an additional node.
     mixer_after_fir=False: mixer -> FIR -> decimate [-> FM]; True: FIR -> mixer -> decimate."""
-    _destroy = "comms_chain_destroy"
+    _prefix = "comms_chain"
 
     def __init__(self, dphase, phase, taps, rate, fm_demod, device=0, mixer_after_fir=False, unfused=False,
                  kernel="auto"):
@@ -715,7 +725,7 @@ class RealFirDecimNode(_Handle):
     """Real FIR with decimation (comms_rfir_*): the audio stage of examples/fm_radio.rs:98-164 -- Convert2Node ->
     BatchFirNode<f32> -> Convert3Node -> DecimateNode<f32>(rate) -- as one node over an f32 stream.  Any batch length:
     the decimator restarts at sample 0 of every call, the FIR history advances by all samples."""
-    _destroy = "comms_rfir_destroy"
+    _prefix = "comms_rfir"
 
     def __init__(self, taps, rate, state=None, device=0):
         super().__init__()
@@ -734,9 +744,7 @@ class RealFirDecimNode(_Handle):
 
     def kernel(self, n):
         """What a batch of n samples is run by: "rfir_decim_kernel<..>", or "series: ..." (the four launches)."""
-        buf = C.create_string_buffer(160)
-        check(lib().comms_rfir_get_kernel(self._h, n, buf, 160))
-        return buf.value.decode()
+        return self._kernel_name(n, cap=160)
 
     def run(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -756,18 +764,13 @@ class RealFirDecimNode(_Handle):
         state = np.ascontiguousarray(state, dtype=np.float32)
         check(lib().comms_rfir_set_state(self._h, _ptr(state), state.size))
 
-    def set_timer(self, timer):
-        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch (the series: its FIR launch)."""
-        check(lib().comms_rfir_set_timer(self._h, timer._h if timer is not None else None))
-        return self
-
 
 class ResampleNode(_Handle):
     """Rational resampler by up / down (comms_resample_*): UpsampleNode(up) -> BatchFirNode(Complex(taps, 0)) ->
     DecimateNode(down) as one node over an f32 or Complex<f32> stream, which forms only the products with input samples.
     Any batch length: ceil(n up / down) outputs per call, the decimator restarts at sample 0 of every call and the
     history -- (len(taps) - 1) // up INPUT samples -- advances by all samples."""
-    _destroy = "comms_resample_destroy"
+    _prefix = "comms_resample"
 
     def __init__(self, taps, up, down, dtype=np.float32, device=0):
         super().__init__()
@@ -791,9 +794,7 @@ class ResampleNode(_Handle):
     def kernel(self, n):
         """What a batch of n samples is run by: "resample_kernel<..> tile=.. lds=.. tiles=.. grid=.. max_grid=..", or "series: ..."
         (the launches)."""
-        buf = C.create_string_buffer(200)
-        check(lib().comms_resample_get_kernel(self._h, n, buf, 200))
-        return buf.value.decode()
+        return self._kernel_name(n, cap=200)
 
     def run(self, x):
         x = np.ascontiguousarray(x, dtype=self.dtype)
@@ -815,11 +816,6 @@ class ResampleNode(_Handle):
         state = np.ascontiguousarray(state, dtype=self.dtype)
         check(lib().comms_resample_set_state(self._h, _ptr(state), state.size))
 
-    def set_timer(self, timer):
-        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch (the series: its FIR launch)."""
-        check(lib().comms_resample_set_timer(self._h, timer._h if timer is not None else None))
-        return self
-
 
 class ChannelizerNode(_Handle):
     """Polyphase channelizer (comms_channelizer_*): M chains MixerNode(0, -2 pi k / M) -> BatchFirNode(Complex(taps, 0)) ->
@@ -827,7 +823,7 @@ class ChannelizerNode(_Handle):
     sample once and spends len(taps) multiply-adds per frame (one output of each channel).  Any batch length: ceil(n / down)
     frames per call, returned as an array [channels][frames] (layout "channel", each row a contiguous stream) or
     [frames][channels] (layout "frame").  State: the last len(taps) - 1 input samples and the stream index mod M."""
-    _destroy = "comms_channelizer_destroy"
+    _prefix = "comms_channelizer"
     LAYOUTS = {"channel": 0, "frame": 1, 0: 0, 1: 1}
 
     def __init__(self, taps, channels, down, layout="channel", device=0):
@@ -852,9 +848,7 @@ class ChannelizerNode(_Handle):
 
     def kernel(self, n):
         """What a batch of n samples is run by: "channelizer_kernel<..> ...", or "series: ..." (the launches)."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_channelizer_get_kernel(self._h, n, buf, 240))
-        return buf.value.decode()
+        return self._kernel_name(n)
 
     def shape(self, n):
         frames = self.out_len(n)
@@ -894,11 +888,6 @@ class ChannelizerNode(_Handle):
 
     phase = property(get_phase, set_phase)
 
-    def set_timer(self, timer):
-        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch (the series: channel 0's FIR launch)."""
-        check(lib().comms_channelizer_set_timer(self._h, timer._h if timer is not None else None))
-        return self
-
 
 class SymbolSyncNode(_Handle):
     """Symbol synchroniser (comms_symsync_*): matched filter with a fractional delay, symbol-rate sampler, rotation and
@@ -906,7 +895,7 @@ class SymbolSyncNode(_Handle):
     0)) -> skip mu -> DecimateNode(phases * sps) -> MixerNode -> decision, computing only the kept outputs.  taps are real,
     designed at `phases` times the input rate (rrc_taps(N, phases * sps, beta)); batches are multiples of sps samples and
     give n / sps outputs; the history -- (len(taps) - 1) // phases RAW input samples -- does not depend on the timing."""
-    _destroy = "comms_symsync_destroy"
+    _prefix = "comms_symsync"
     _out_bits = 0
 
     def __init__(self, taps, phases, sps, device=0):
@@ -972,9 +961,7 @@ class SymbolSyncNode(_Handle):
 
     def kernel(self, n):
         """What a batch of n samples is run by: "symsync_kernel<..> tile=.. wg=.. lds=.. tiles=.. grid=.. max_grid=.."."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_symsync_get_kernel(self._h, n, buf, 240))
-        return buf.value.decode()
+        return self._kernel_name(n)
 
     def run(self, x):
         x = np.ascontiguousarray(x, dtype=np.complex64)
@@ -997,11 +984,6 @@ class SymbolSyncNode(_Handle):
         check(lib().comms_symsync_set_state(self._h, _ptr(state), state.size))
 
     state = property(get_state, set_state)
-
-    def set_timer(self, timer):
-        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch."""
-        check(lib().comms_symsync_set_timer(self._h, timer._h if timer is not None else None))
-        return self
 
 
 def _taps(fn, n_taps, *args):
@@ -1139,7 +1121,7 @@ class PrnsNode(_Handle):
     """PrnsNode::new(poly_mask, state) (prns.rs:93-137) on an unsigned register of `width` = 8, 16, 32 or 64 bits:
     run() returns the next bit, as the reference; run_batch(n) the next n bits (uint8 0/1 per bit, or packed LSB
     first with packed=True), generated on the device.  `state` and skip(n) never wait for the device."""
-    _destroy = "comms_prns_destroy"
+    _prefix = "comms_prns"
 
     def __init__(self, poly_mask, state, width=8, device=0):
         super().__init__()
@@ -1179,7 +1161,7 @@ class NoiseSource(_Handle):
     """comms_noise_*: the counter-based source (Philox4x32-10 of (seed, stream); include/comms_hip.h has the contract)
     behind NormalNode / UniformNode / random_bit (util/rand_node.rs:26-152) and the AWGN channel node.  `pos` is the
     position in 32-bit stream words, kept on the host: reading, setting and skip(n) never wait for the device."""
-    _destroy = "comms_noise_destroy"
+    _prefix = "comms_noise"
 
     def __init__(self, seed, stream=0, device=0):
         super().__init__()
@@ -1198,10 +1180,6 @@ class NoiseSource(_Handle):
 
     def skip(self, n_words):
         check(lib().comms_noise_skip(self._h, int(n_words)))
-        return self
-
-    def set_timer(self, timer):
-        check(lib().comms_noise_set_timer(self._h, timer._h if timer is not None else None))
         return self
 
     def bits(self, n, packed=False):
@@ -1281,7 +1259,7 @@ def qam_phase_estimate(symbols, device=0):
 class TimingEstimatorNode(_Handle):
     """TimingEstimatorNode::new(n, d, alpha) / run (timing_estimator.rs:116-136): Complex<f64>
     block in, timing offset in samples out."""
-    _destroy = "comms_timing_destroy"
+    _prefix = "comms_timing"
 
     def __init__(self, n, d, alpha, device=0):
         super().__init__()
@@ -1322,7 +1300,7 @@ class SyncEstimatorNode(_Handle):
     at (n, d, alpha) and frequency_offset_estimate of the widened samples, the timing filter in f32.  What to feed
     SymbolSyncNode (estimator at n = sps): timing = est.timing + (N - 1) / (2 phases), set_rotation(-est.freq * sps,
     -phase estimate)."""
-    _destroy = "comms_syncest_destroy"
+    _prefix = "comms_syncest"
 
     def __init__(self, n, d, alpha, device=0):
         super().__init__()
@@ -1341,14 +1319,7 @@ class SyncEstimatorNode(_Handle):
 
     def kernel(self, n):
         """What a block of n samples is run by: "syncest_kernel tile=.. wg=.. taps=.. lds=.. tiles=.. grid=.. max_grid=.."."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_syncest_get_kernel(self._h, n, buf, 240))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch."""
-        check(lib().comms_syncest_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(n)
 
 
 def psk_phase_estimate_c32(symbols, m, device=0):
@@ -1417,7 +1388,7 @@ class FrameSyncNode(_Handle):
     stream.  Detections are bit-identical however the stream is cut into calls.  `cap` limits the detections returned (the
     lowest indices); `found` is the true count of the last call.  With raw=True a call returns the structured array
     (FRAME_DETECTION_DTYPE) instead of FrameDetection values."""
-    _destroy = "comms_framesync_destroy"
+    _prefix = "comms_framesync"
     found = 0
 
     def __init__(self, word, threshold, guard, device=0):
@@ -1487,14 +1458,7 @@ class FrameSyncNode(_Handle):
 
     def kernel(self, n):
         """What a call on n symbols is run by: "framesync_kernel tile=.. wg=.. word=.. guard=.. lds=.. tiles=.. grid=.. max_grid=.."."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_framesync_get_kernel(self._h, n, buf, 240))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch."""
-        check(lib().comms_framesync_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(n)
 
 
 class _FrameHeaderStruct(C.Structure):
@@ -1527,7 +1491,7 @@ class DeframeNode(_Handle):
     not depend on how the stream is cut into calls.  `lookback` >= the frame synchroniser's guard - 1.  run() returns an array
     of shape (n_frames, n_payload) complex64, (n_frames, frame_bytes) uint8 or (n_frames, n_payload * bits_per_sym) float32;
     `headers` holds the FRAME_HEADER_DTYPE records of the last call."""
-    _destroy = "comms_deframe_destroy"
+    _prefix = "comms_deframe"
 
     def __init__(self, n_payload, offset, lookback, bits_per_sym=2, constellation=None, normalise=False, word_energy=None, device=0):
         super().__init__()
@@ -1645,14 +1609,7 @@ class DeframeNode(_Handle):
 
     def kernel(self, n_frames):
         """What a call that emits n_frames frames is run by: "deframe_kernel wg=.. items=.. lanes=.. grid=.. max_grid=.. lds=.."."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_deframe_get_kernel(self._h, int(n_frames), buf, 240))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        """Attach a KernelTimer (None detaches): its pairs bracket the node's launch."""
-        check(lib().comms_deframe_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(int(n_frames))
 
 
 # ------------------------------------------------------------------ convolutional FEC
@@ -1670,7 +1627,7 @@ class ConvEncoderNode(_Handle):
     record ceil(bits / 8) bytes rounded up to 4) -> records of n * steps coded bits, coded bit j of step t at t * n + j, all
     frames of a call in one launch.  terminated=True appends K - 1 zero bits (steps = n_info_bits + K - 1).  Stateless:
     every frame starts in state 0.  run() takes and returns uint8 arrays of shape (n_frames, frame bytes)."""
-    _destroy = "comms_convenc_destroy"
+    _prefix = "comms_convenc"
 
     def __init__(self, n_info_bits, K=7, gens=None, n=None, terminated=True, device=0):
         super().__init__()
@@ -1700,13 +1657,7 @@ class ConvEncoderNode(_Handle):
 
     def kernel(self, n_frames):
         """ "conv_encode_kernel wg=.. K=.. n=.. steps=.. words=.. grid=.. max_grid=.. lds=0" for a call on n_frames frames."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_convenc_get_kernel(self._h, int(n_frames), buf, 240))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        check(lib().comms_convenc_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(int(n_frames))
 
 
 class ViterbiNode(_Handle):
@@ -1716,7 +1667,7 @@ class ViterbiNode(_Handle):
     (NaN: 0), so they are the bits of the definition exactly.  A DeframeNode "llr" record of at least n * steps values is a
     valid input as it stands.  run() returns uint8 (n_frames, out_frame_bytes); with metrics=True also the final int32
     path metric of every frame."""
-    _destroy = "comms_viterbi_destroy"
+    _prefix = "comms_viterbi"
 
     def __init__(self, n_info_bits, K=7, gens=None, n=None, terminated=True, record_llrs=None, qscale=None, device=0):
         super().__init__()
@@ -1758,13 +1709,7 @@ class ViterbiNode(_Handle):
 
     def kernel(self, n_frames):
         """ "viterbi_kernel<n,lds|workspace> wg=.. waves=.. K=.. steps=.. seam=.. grid=.. max_grid=.. lds=.. workspace=.."."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_viterbi_get_kernel(self._h, int(n_frames), buf, 240))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        check(lib().comms_viterbi_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(int(n_frames))
 
 
 # ------------------------------------------------------------------ rate matching
@@ -1773,7 +1718,7 @@ class _RateMatch(_Handle):
     None keeps everything), an interleaver over the n_tx_bits kept bits (`cols` columns of the pruned block interleaver, or an
     explicit `perm` with perm[k] the kept-bit index transmitted k-th) and `scramble`, n_tx_bits bits packed LSB first (uint8)
     that are XORed onto the transmitted bits, or None."""
-    _destroy = "comms_ratematch_destroy"
+    _prefix = "comms_ratematch"
     _direction = None
 
     def __init__(self, n_coded, pattern=None, cols=0, perm=None, scramble=None, record_llrs=0, device=0):
@@ -1804,13 +1749,7 @@ class _RateMatch(_Handle):
     def kernel(self, n_frames):
         """ "ratematch_tx_kernel | ratematch_rx_kernel wg=.. table=lds|global seam=.. n_coded=.. n_tx=.. words= | values=..
         grid=.. max_grid=.. lds=.." for a call on n_frames frames."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_ratematch_get_kernel(self._h, self._direction, int(n_frames), buf, 240))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        check(lib().comms_ratematch_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(self._direction, int(n_frames))
 
 
 class RateMatchNode(_RateMatch):
@@ -1878,7 +1817,7 @@ class _Crc(_Handle):
     register `init` and final `xorout`, no reflection, over frames of `n_payload_bits` bits; the CRC follows the payload with
     its x^(width-1) coefficient first.  Records are packed LSB first, so (32, 0x04C11DB7, 0xFFFFFFFF, 0xFFFFFFFF) is the
     Ethernet FCS."""
-    _destroy = "comms_crc_destroy"
+    _prefix = "comms_crc"
     _direction = None
 
     def __init__(self, width, poly, init, xorout, n_payload_bits, device=0):
@@ -1900,13 +1839,7 @@ class _Crc(_Handle):
     def kernel(self, n_frames):
         """ "crc_attach_kernel | crc_check_kernel wg=.. group=.. rounds=.. width=.. words=.. frames=.. grid=.. max_grid=.. lds=0"
         for a call on n_frames frames."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_crc_get_kernel(self._h, self._direction, int(n_frames), buf, 240))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        check(lib().comms_crc_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(self._direction, int(n_frames))
 
     def _frames(self, frames):
         x = np.ascontiguousarray(frames, dtype=np.uint8)
@@ -1998,7 +1931,7 @@ class SymbolMapNode(_Handle):
     bits_per_sym bits, the first as the LSB, bits beyond n_bits reading as 0 -- and `gap` symbols (0, 0); all frames of a call
     in one launch.  constellation: 2**bits_per_sym points (qam_table, psk_table, or any), None = digital.rs's tables at 1 or 2
     bits.  Stateless.  run() takes uint8 (n_frames, in_frame_bytes) and returns complex64 (n_frames, out_frame_syms)."""
-    _destroy = "comms_symmap_destroy"
+    _prefix = "comms_symmap"
 
     def __init__(self, bits_per_sym, constellation, n_bits, word=None, gap=0, device=0):
         super().__init__()
@@ -2037,13 +1970,7 @@ class SymbolMapNode(_Handle):
 
     def kernel(self, n_frames):
         """ "symmap_kernel wg=.. bits=.. n_bits=.. word=.. payload=.. gap=.. syms=.. frames=.. grid=.. max_grid=.. lds=.."."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_symmap_get_kernel(self._h, int(n_frames), buf, 240))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        check(lib().comms_symmap_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(int(n_frames))
 
 
 class DemapNode(_Handle):
@@ -2054,7 +1981,7 @@ class DemapNode(_Handle):
     A separable table (any square or rectangular QAM) runs per axis, the same bits from far fewer distances; force_table=True
     keeps the general form.  Stateless.  run() takes complex64 and returns float32 (n_frames, n_payload * bits_per_sym) or
     uint8 (n_frames, out_frame_bytes)."""
-    _destroy = "comms_demap_destroy"
+    _prefix = "comms_demap"
 
     def __init__(self, bits_per_sym, constellation, n_payload, force_table=False, device=0):
         super().__init__()
@@ -2104,13 +2031,7 @@ class DemapNode(_Handle):
     def kernel(self, n_frames):
         """ "demap_table_kernel<m,fmt> form=table ..." or "demap_axis_kernel<mI,mQ,fmt> form=axis ...", then "wg=.. bits=..
         payload=.. items=.. lanes=.. frames=.. grid=.. max_grid=.. lds=0"."""
-        buf = C.create_string_buffer(240)
-        check(lib().comms_demap_get_kernel(self._h, int(n_frames), buf, 240))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        check(lib().comms_demap_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(int(n_frames))
 
 
 # ------------------------------------------------------------------ OFDM modulator and demodulator
@@ -2120,7 +2041,7 @@ class _Ofdm(_Handle):
     pilots of data symbol s by polarity[s mod len]; None = 1), n_train identical training symbols of frequency values
     train[n_fft] in front of the n_syms data symbols of every frame, cpe=True for the demodulator's pilot phase correction,
     tx_scale (None = 1 / sqrt(n_fft))."""
-    _destroy = "comms_ofdm_destroy"
+    _prefix = "comms_ofdm"
     _direction = None
 
     def __init__(self, n_fft, n_cp, carrier_kind, pilots=None, polarity=None, train=None, n_train=0, n_syms=1, cpe=False, tx_scale=None,
@@ -2160,13 +2081,7 @@ class _Ofdm(_Handle):
     def kernel(self, n_frames):
         """ "ofdm_mod_kernel<N> | ofdm_demod_kernel<N> form=wave16 wg=.. n_fft=.. cp=.. data=.. pilots=.. train=.. syms=.. cpe=..
         lanes_per_sym=.. syms_per_wave=.. block=.. blocks=.. frames=.. items=.. grid=.. max_grid=.. lds=.." for a call on n_frames."""
-        buf = C.create_string_buffer(320)
-        check(lib().comms_ofdm_get_kernel(self._h, self._direction, int(n_frames), buf, 320))
-        return buf.value.decode()
-
-    def set_timer(self, timer):
-        check(lib().comms_ofdm_set_timer(self._h, timer._h if timer is not None else None))
-        return self
+        return self._kernel_name(self._direction, int(n_frames), cap=320)
 
     def _run(self, fn, x, in_len, out_len):
         x = _as_c64(x).ravel()
@@ -2215,7 +2130,7 @@ def qfilt_taps(n_taps, alpha, sam_per_sym):
 class NcoNode(_Handle):
     """NcoNode::new(dphase, phase) (nco.rs:118-133) in block form: run() takes a vector of
     phase errors and returns exp(i*phase) per sample (Complex<f64>)."""
-    _destroy = "comms_nco_destroy"
+    _prefix = "comms_nco"
 
     def __init__(self, dphase, phase=None, device=0):
         super().__init__()
@@ -2270,23 +2185,7 @@ class KernelTimer:
                 check(lib().comms_timer_set_stride(self._h, int(stride)))
 
     def attach(self, node):
-        name = {"comms_fir_destroy": "comms_fir_set_timer", "comms_mixer_destroy": "comms_mixer_set_timer",
-                "comms_fmdemod_destroy": "comms_fmdemod_set_timer", "comms_fft_destroy": "comms_fft_set_timer",
-                "comms_chain_destroy": "comms_chain_set_timer", "comms_pulse_destroy": "comms_pulse_set_timer",
-                "comms_rfir_destroy": "comms_rfir_set_timer", "comms_noise_destroy": "comms_noise_set_timer",
-                "comms_resample_destroy": "comms_resample_set_timer",
-                "comms_channelizer_destroy": "comms_channelizer_set_timer",
-                "comms_symsync_destroy": "comms_symsync_set_timer",
-                "comms_syncest_destroy": "comms_syncest_set_timer",
-                "comms_framesync_destroy": "comms_framesync_set_timer",
-                "comms_deframe_destroy": "comms_deframe_set_timer",
-                "comms_convenc_destroy": "comms_convenc_set_timer",
-                "comms_viterbi_destroy": "comms_viterbi_set_timer",
-                "comms_ratematch_destroy": "comms_ratematch_set_timer",
-                "comms_crc_destroy": "comms_crc_set_timer",
-                "comms_symmap_destroy": "comms_symmap_set_timer",
-                "comms_demap_destroy": "comms_demap_set_timer",
-                "comms_ofdm_destroy": "comms_ofdm_set_timer"}[node._destroy]
+        name = node._prefix + "_set_timer"   # (a node without one: AttributeError)
         check(getattr(lib(), name)(node._h, self._h))
         self._node, self._setter = node, name
         return self

@@ -19,8 +19,10 @@ import numpy as np
 import crc_ref
 import deframe_ref as dr
 import framesync_ref as fr
+import ofdm_ref
 import ratematch_ref as rr
 import rx_ref
+import symmap_ref as sm
 import syncest_ref
 import viterbi_ref as vr
 
@@ -46,19 +48,30 @@ ANCHORS = [
     (CSRC + "channelizer.hip", "return static_cast<unsigned>((tiles + per1 - 1) / per1);"),
     (CSRC + "channelizer.hip", "// F = 2048 / M frames per tile, halved while"),
     (CSRC + "deframe.hip", "size_t deframe_lanes(const comms_deframe* h, size_t n_frames) { return (n_frames * lanes_per_frame(h) + 63) / 64 * 64; }"),
-    (CSRC + "deframe.hip", "const size_t b = (deframe_lanes(h, n_frames) + DF_WG - 1) / DF_WG;"),
+    (CSRC + "deframe.hip", "return capped_grid((deframe_lanes(h, n_frames) + DF_WG - 1) / DF_WG, h->max_grid);"),
     (CSRC + "deframe.hip", "const unsigned dq = stride / a.lpf, dr = stride % a.lpf;"),
-    (CSRC + "convcode.hip", "const size_t b = (n_frames * (enc_out_bytes(h) / 4) + CC_WG - 1) / CC_WG;"),
-    (CSRC + "convcode.hip", "const size_t b = (n_frames + VT_WAVES - 1) / VT_WAVES;"),
+    (CSRC + "common.hpp", "inline size_t capped_grid(size_t blocks, unsigned max_grid) { return blocks < 1 ? 1 : blocks < max_grid ? blocks : max_grid; }"),
+    (CSRC + "convcode.hip", "return capped_grid((n_frames * (enc_out_bytes(h) / 4) + CC_WG - 1) / CC_WG, h->max_grid);"),
+    (CSRC + "convcode.hip", "return capped_grid((n_frames + VT_WAVES - 1) / VT_WAVES, h->max_grid);"),
     (CSRC + "convcode.hip", "constexpr unsigned VT_LDS_STEPS = 2048;"),
     (CSRC + "convcode.hip", "h->in_lds = c.steps <= VT_LDS_STEPS;"),
     (CSRC + "ratematch.hip", "constexpr unsigned RM_LDS_SEAM = 2048;"),
-    (CSRC + "ratematch.hip", "return clamp_grid((n_frames * (tx_out_bytes(h) / 4) + RM_WG - 1) / RM_WG, h->tx_max_grid);"),
+    (CSRC + "ratematch.hip", "return capped_grid((n_frames * (tx_out_bytes(h) / 4) + RM_WG - 1) / RM_WG, h->tx_max_grid);"),
     (CSRC + "ratematch.hip", "const size_t per = h->rx_lds && h->n_coded > RM_WG ? h->n_coded : RM_WG;"),
+    (CSRC + "ratematch.hip", "return capped_grid((n_frames * h->n_coded + per - 1) / per, h->rx_max_grid);"),
     (CSRC + "ratematch.hip", "h->tx_lds = h->n_tx <= RM_LDS_SEAM ?"),
     (CSRC + "ratematch.hip", "h->rx_lds = h->n_coded <= RM_LDS_SEAM ?"),
     (CSRC + "ratematch.hip", "if (pos >= per) {"),
-    (CSRC + "crc.hip", "const size_t fpw = 64 / h->plan.group, items = (n_frames + fpw - 1) / fpw, b = (items + CRC_WAVES - 1) / CRC_WAVES;"),
+    (CSRC + "crc.hip", "const size_t fpw = 64 / h->plan.group, items = (n_frames + fpw - 1) / fpw;"),
+    (CSRC + "crc.hip", "return capped_grid((items + CRC_WAVES - 1) / CRC_WAVES, h->max_grid);"),
+    (CSRC + "symmap.hip", "return capped_grid((n_frames * map_rec(h) + SM_WG - 1) / SM_WG, h->max_grid);"),
+    (CSRC + "symmap.hip", "return h->format == COMMS_SYM_BITS ? n_frames * demap_chunks(h) : n_frames * h->F;"),
+    (CSRC + "symmap.hip", "const size_t per = h->format == COMMS_SYM_BITS ? SM_WG / 64 : SM_WG;"),
+    (CSRC + "symmap.hip", "return capped_grid((demap_items(h, n_frames) + per - 1) / per, h->max_grid);"),
+    (CSRC + "ofdm.hip", "size_t want = n_frames && n_frames < h->max_grid ? (h->max_grid + n_frames - 1) / n_frames : 1;"),
+    (CSRC + "ofdm.hip", "*blk = static_cast<unsigned>((rounds + want - 1) / want) * round;"),
+    (CSRC + "ofdm.hip", "*nblk = (per_frame + *blk - 1) / *blk;"),
+    (CSRC + "ofdm.hip", "size_t of_grid(const comms_ofdm* h, size_t items) { return capped_grid(items, h->max_grid); }"),
 ]
 
 WG = 256                 # lanes per workgroup of every kernel here
@@ -160,6 +173,30 @@ def crc_items_walk(items, cap):
 def crc_walk(frames, cap, T):
     """a wave-item is 64 / group frames"""
     return crc_items_walk(cdiv(frames, 64 // crc_ref.group_of(T)), cap)
+
+
+def map_rec(E, m, P, G):
+    """symbols of a mapper record: the word, the payload, the gap"""
+    return P + cdiv(E, m) + G
+
+
+def map_walk(frames, cap, rec):
+    """one lane per output symbol of the flattened (frame, position) space"""
+    return _walk(frames * rec, WG, _capped(cdiv(frames * rec, WG), cap))
+
+
+def demap_walk(frames, cap, F, fmt):
+    """LLR: one lane per symbol; BITS: one wave per 64 symbols of ONE frame, SM_WG / 64 = 4 waves per workgroup and pass"""
+    items, per = (frames * cdiv(F, 64), WG // 64) if fmt == "bits" else (frames * F, WG)
+    return _walk(items, per, _capped(cdiv(items, per), cap))
+
+
+def ofdm_walk(frames, cap, f, direction):
+    """an item is (frame, block of symbols), ofdm_block's blocks per frame (T + S symbols for the modulator, S for the
+    demodulator); a workgroup takes one item per pass"""
+    per_frame = f.n_syms + (f.n_train if direction == "mod" else 0)
+    items = frames * ofdm_ref.block_rule(f.n_fft, per_frame, frames, cap)[1]
+    return _walk(items, 1, _capped(items, cap))
 
 
 def rm_regime(stride, per):
@@ -396,8 +433,51 @@ def crc_corrupted(frames):
     return f[(f % 5 == 0) | (f % 5 == 3) | (f == frames - 1)]
 
 
-CASES = _syncest() + _framesync() + _symsync() + _resample() + _channelizer() + _deframe() + _encoder() + _viterbi() + _ratematch() + _crc()
-FAMILIES = ("syncest", "framesync", "symsync", "resample", "channelizer", "deframe", "convcode", "ratematch", "crc")
+# (m, table, E, P, G): 8 divides 32, 3 and 6 do not (fields that straddle two input words); a word and a gap, and neither
+SYMMAP_MAP_FORMATS = ((3, "8psk", 100, 13, 5), (6, "64qam", 333, 0, 0), (8, "256qam", 64, 1, 0))
+# (table, F): the table form (8psk, rand8) and the per-axis form (64qam, sep32); F below, above and far above one 64-symbol chunk
+SYMMAP_DEMAP_FORMATS = (("8psk", 67), ("64qam", 130), ("sep32", 33), ("rand8", 3000))
+
+
+@functools.lru_cache(maxsize=None)
+def _map_frames(rec, cap):
+    return smallest(functools.partial(map_walk, rec=rec), cap)
+
+
+@functools.lru_cache(maxsize=None)
+def _demap_frames(F, fmt, cap):
+    return smallest(functools.partial(demap_walk, F=F, fmt=fmt), cap)
+
+
+def _symmap():
+    maps = [Case("symmap", "symmap.hip", "map-%s-E%d" % (t, E), dict(node="map", m=m, table=t, E=E, P=P, G=G),
+                 functools.partial(_map_frames, map_rec(E, m, P, G))) for m, t, E, P, G in SYMMAP_MAP_FORMATS]
+    demaps = [Case("symmap", "symmap.hip", "demap-%s-F%d-%s" % (t, F, fmt), dict(node="demap", table=t, F=F, fmt=fmt),
+                   functools.partial(_demap_frames, F, fmt)) for t, F in SYMMAP_DEMAP_FORMATS for fmt in ("llr", "bits")]
+    return maps + demaps
+
+
+# the pilot phase correction on and two training symbols everywhere; n64_long: two rounds of 64 symbols, the second ragged
+OFDM_FORMATS = {
+    "n64_long": ofdm_ref.Format(64, 16, ofdm_ref.map_80211a(), 70, 2, ofdm_ref.POLARITY, cpe=True, seed=11),
+    "n512_cp36": ofdm_ref.FORMATS["n512_cp36"].but(cpe=True),
+    "n1024_cp72": ofdm_ref.FORMATS["n1024_cp72"].but(cpe=True),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _ofdm_frames(name, direction, cap):
+    return smallest(functools.partial(ofdm_walk, f=OFDM_FORMATS[name], direction=direction), cap)
+
+
+def _ofdm():
+    # ofdm.hip takes its cap once for both directions: one label, the direction in `direction`
+    return [Case("ofdm", "ofdm.hip", "%s-%s" % (d, name), dict(format=name, direction=d), functools.partial(_ofdm_frames, name, d))
+            for name in OFDM_FORMATS for d in ("mod", "demod")]
+
+
+CASES = _syncest() + _framesync() + _symsync() + _resample() + _channelizer() + _deframe() + _encoder() + _viterbi() + _ratematch() + _crc() + _symmap() + _ofdm()
+FAMILIES = ("syncest", "framesync", "symsync", "resample", "channelizer", "deframe", "convcode", "ratematch", "crc", "symmap", "ofdm")
 # not bitwise equal to the uncapped run: the [gridDim.x][4] partial sums of syncest_kernel are a reduction across workgroups
 REDUCED_ACROSS_WORKGROUPS = ("syncest",)
 
@@ -424,6 +504,10 @@ def walk(cs, cap):
         return rm_rx_walk(size, cap, f["n_coded"]) if f["dir"] == "rx" else rm_tx_walk(size, cap, f["n_tx"])
     if cs.family == "crc":
         return crc_walk(size, cap, f["T"])
+    if cs.family == "symmap":
+        return map_walk(size, cap, map_rec(f["E"], f["m"], f["P"], f["G"])) if f["node"] == "map" else demap_walk(size, cap, f["F"], f["fmt"])
+    if cs.family == "ofdm":
+        return ofdm_walk(size, cap, OFDM_FORMATS[f["format"]], f["direction"])
     raise ValueError(cs.family)
 
 
@@ -441,7 +525,10 @@ def ragged(cs, cap):
 
 def never_ragged(cs, cap):
     """Receive records of 256 or 2048 values and deframer frames of 2048 lanes, at cap 1: every frame count gives a multiple of
-    the workgroup's 256 lanes."""
+    the workgroup's 256 lanes.  The OFDM kernels at cap 1: a workgroup takes ONE item per pass, so a grid of one has no partial
+    pass (the ragged end of an item is within it: the last group of a block, tests/test_grid_cases.py)."""
+    if cs.family == "ofdm":
+        return cap == 1
     if cs.family == "ratematch" and cs.fmt["dir"] == "rx":
         return cs.fmt["n_coded"] % (cap * WG) == 0
     return cs.family == "deframe" and deframe_lpf(cs.fmt["F"], cs.fmt["K"], cs.fmt["fmt"]) % (cap * WG) == 0
@@ -471,4 +558,11 @@ def bytes_moved(cs, cap):
         return size * (4 * E + 4 * f["n_coded"]) if f["dir"] == "rx" else size * (rr.record_bytes(f["n_coded"]) + rr.record_bytes(E))
     if cs.family == "crc":
         return size * (2 * crc_ref.record_bytes(f["T"] + f["W"]) + 8)
+    if cs.family == "symmap":
+        if f["node"] == "map":
+            return size * (sm.record_bytes(f["E"]) + 8 * map_rec(f["E"], f["m"], f["P"], f["G"]))
+        bits = f["F"] * sm.table_of(f["table"])[0]
+        return size * (8 * f["F"] + (4 * bits if f["fmt"] == "llr" else sm.record_bytes(bits)))
+    if cs.family == "ofdm":
+        return 8 * size * (OFDM_FORMATS[f["format"]].data_syms + OFDM_FORMATS[f["format"]].frame_samples)
     raise ValueError(cs.family)

@@ -361,8 +361,80 @@ def crc(c):
             print("crc %s cap %d: %d frames, %d failed, exact" % (cs.name, cap, frames, n_bad))
 
 
+# ---------------------------------------------------------------- symbol mapper and demapper
+def symmap(c):
+    import symmap_ref as sm
+
+    for cs in gc.cases_of("symmap"):
+        f = cs.fmt
+        if f["node"] == "map":
+            m, E, P, G = f["m"], f["E"], f["P"], f["G"]
+            table = sm.table_of(f["table"])[1]
+            word = sm.noisy_points(sm.QPSK, P, 3) if P else None
+            new = lambda: c.SymbolMapNode(m, table, E, word, G)  # noqa: E731
+            plain = make(new)
+            for cap in gc.CAPS:
+                frames = cs.size(cap)
+                node = make(new, cap)
+                k = fields(node.kernel(frames))
+                held(cs, cap, k, k["syms"], k["wg"])
+                bits = np.random.default_rng(E + cap).integers(0, 2, (frames, E), dtype=np.uint8)
+                records = sm.dirty_records(bits, 1)
+                got = node.run(records)
+                assert got.tobytes() == sm.ref_map(bits, m, table, word, G).tobytes(), (cs.name, cap)
+                assert plain.run(records).tobytes() == got.tobytes(), (cs.name, cap)
+                print("symmap %s cap %d: %d frames, exact" % (cs.name, cap, frames))
+            continue
+        F, fmt = f["F"], f["fmt"]
+        m, table, given, split = sm.table_of(f["table"])
+        new = lambda: c.DemapNode(m, given, F).set_llr_scale(0.6).set_output_format(fmt)  # noqa: E731
+        plain = make(new)
+        for cap in gc.CAPS:
+            frames = cs.size(cap)
+            node = make(new, cap)
+            name = node.kernel(frames)
+            k = fields(name)
+            held(cs, cap, k, k["items"], k["wg"] // 64 if fmt == "bits" else k["wg"])
+            assert ("form=table" in name) == (split is None), name
+            z = sm.demap_input(table, frames * F, F + cap)
+            got = node.run(z)
+            if fmt == "llr":
+                assert sm.same_floats(got, sm.ref_llr_records(z, table, F, 0.6)), (cs.name, cap)
+            else:
+                assert got.tobytes() == sm.ref_bits_records(z, table, F).tobytes(), (cs.name, cap)
+            assert plain.run(z).tobytes() == got.tobytes(), (cs.name, cap)
+            print("symmap %s cap %d: %d frames, exact" % (cs.name, cap, frames))
+
+
+# ---------------------------------------------------------------- OFDM
+def ofdm(c):
+    import ofdm_ref as r
+
+    for cs in gc.cases_of("ofdm"):
+        f, mod = gc.OFDM_FORMATS[cs.fmt["format"]], cs.fmt["direction"] == "mod"
+        args, kw = f.node_args()
+        new = lambda: (c.OfdmModNode if mod else c.OfdmDemodNode)(*args, **kw)  # noqa: E731
+        plain = make(new)
+        for cap in gc.CAPS:
+            frames = cs.size(cap)
+            node = make(new, cap)
+            k = fields(node.kernel(frames))
+            held(cs, cap, k, k["items"], 1)
+            z = r.data_values(f, frames)
+            if mod:
+                x, want, per, bound = z, r.ref_mod(f, z), f.sym_len, r.FFT_BOUND
+            else:
+                x = r.through_channel(f, r.ref_mod(f, z), r.symbol_thetas(f))
+                want, per, bound = r.ref_demod(f, x), f.D, r.CHANNEL_BOUND
+            got = node.run(x)
+            err = float(r.symbol_errors(got, want, per).max())
+            print("ofdm %s cap %d: %d frames, %d items, worst symbol off by %.3e (bound %.3e)" % (cs.name, cap, frames, k["items"], err, bound))
+            assert err <= bound, (cs.name, cap, err)
+            assert plain.run(x).tobytes() == got.tobytes(), (cs.name, cap)
+
+
 CHILDREN = dict(syncest=syncest, framesync=framesync, symsync=symsync, resample=resample, channelizer=channelizer, deframe=deframe,
-                convcode=convcode, ratematch=ratematch, crc=crc)
+                convcode=convcode, ratematch=ratematch, crc=crc, symmap=symmap, ofdm=ofdm)
 
 if __name__ == "__main__":
     import comms_rs_amd

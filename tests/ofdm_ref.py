@@ -274,17 +274,7 @@ CHANNEL_BOUND = 4 * CHANNEL_MODEL_WORST
 LINK_FORMAT = "n64_11a"
 LINK_FRAMES = 5
 
-# ---------------------------------------------------------------- capped grids (check 6)
-CAPS = (1, 3)
-MIN_PASSES = 4
-GRID_FORMATS = {
-    "n64_long": Format(64, 16, map_80211a(), 70, 2, POLARITY, cpe=True, seed=11),      # two rounds of 64 symbols, the second ragged
-    "n512_cp36": FORMATS["n512_cp36"].but(cpe=True),
-    "n1024_cp72": FORMATS["n1024_cp72"].but(cpe=True),
-}
-GRID_CASES = (("n64_long", 13), ("n512_cp36", 13), ("n1024_cp72", 13))   # (format, frames)
-
-
+# ---------------------------------------------------------------- the block rule (the capped-grid cases are tests/grid_cases.py's)
 def block_rule(n_fft, per_frame, n_frames, max_grid):
     """ofdm.hip's ofdm_block: (symbols per block, blocks per frame)."""
     rnd = 4096 // n_fft
@@ -293,12 +283,3 @@ def block_rule(n_fft, per_frame, n_frames, max_grid):
     want = min(want, rounds)
     blk = -(-rounds // want) * rnd
     return blk, -(-per_frame // blk)
-
-
-def grid_items(f, direction, n_frames, max_grid):
-    per_frame = f.n_syms + (f.n_train if direction == "mod" else 0)
-    return n_frames * block_rule(f.n_fft, per_frame, n_frames, max_grid)[1]
-
-
-def grid_passes(f, direction, n_frames, cap):
-    return -(-grid_items(f, direction, n_frames, cap) // cap)

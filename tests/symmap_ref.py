@@ -340,25 +340,6 @@ def demap_lengths(m):
     return sorted(want)
 
 
-# ------------------------------------------------------------------ capped grids (tests/symmap_grid_child.py)
-CAPS = (1, 3)
-MIN_PASSES = 4
-# (m, table name, E, P, G, frames): the mapper walks frames * (P + F + G) lanes
-GRID_MAP_CASES = ((3, "8psk", 100, 13, 5, 70), (6, "64qam", 333, 0, 0, 60), (8, "256qam", 64, 1, 0, 350))
-# (table name, F, frames): the demapper walks frames * F lanes (LLR) or frames * ceil(F / 64) waves (BITS)
-GRID_DEMAP_CASES = (("8psk", 67, 50), ("64qam", 130, 26), ("sep32", 33, 100), ("rand8", 3000, 2))
-
-
-def map_passes(E, m, P, G, frames, cap):
-    return -(-(frames * (P + -(-E // m) + G)) // (cap * WG))
-
-
-def demap_passes(F, frames, cap, fmt):
-    if fmt == "bits":
-        return -(-(frames * -(-F // 64)) // (cap * (WG // 64)))
-    return -(-(frames * F) // (cap * WG))
-
-
 # ------------------------------------------------------------------ the coded link of tests/test_gpu_symmap.py
 # CRC-24 -> K = 7 encoder -> rate 3/4 matcher -> 16-QAM mapper behind a 13-symbol word; noise and a constant rotation on the
 # host; frame synchroniser -> deframer (C32, normalising) -> demapper -> dematcher -> Viterbi -> CRC check

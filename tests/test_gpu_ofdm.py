@@ -3,7 +3,6 @@ include/comms_hip.h's "OFDM modulator and demodulator".  Formats, inputs and bou
 holds them to their rules); no bound here comes from a kernel's output.  Every figure is printed before it is asserted."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -111,16 +110,6 @@ def test_link_16qam_bits_are_exact(c):
     demap = c.DemapNode(4, table, f.data_syms).set_output_format("bits")
     got = demap.run(dem.run(rx))
     assert got[:, : records.shape[1]].tobytes() == records.tobytes()
-
-
-def test_capped_grids(c):
-    diag = os.path.join(os.path.dirname(c.LIB_PATH), "libcomms_hip_diag.so")
-    assert os.path.exists(diag), "the diagnostic build is part of build()"
-    env = dict(os.environ, COMMS_HIP_LIB=diag)
-    env.pop("COMMS_GRID_CAP", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ofdm_grid_child.py")], env=env, capture_output=True, text=True, timeout=300)
-    print(p.stdout[-3000:], p.stderr[-3000:])
-    assert p.returncode == 0 and p.stdout.strip().endswith("ok")
 
 
 def test_host_graph_nodes(c):

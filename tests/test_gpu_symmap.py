@@ -6,7 +6,6 @@ import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,7 +13,6 @@ import pytest
 import symmap_ref as sr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIAG_LIB = os.path.join(ROOT, "comms_rs_amd", "lib", "libcomms_hip_diag.so")
 pytestmark = pytest.mark.gpu
 GUARD = 256
 
@@ -296,19 +294,6 @@ def test_coded_link_over_16qam(c):
     assert np.array_equal(d_pass.download(np.int32, frames), want_pass) and np.array_equal(d_crc.download(np.uint32, frames), want_crc)
     assert same_bytes(d_out.download(np.uint8, frames * chk.out_frame_bytes).reshape(frames, -1), sr.pack_records(want_payload))
     assert want_pass.all() and int(d_failed.download(np.uint32, 1)[0]) == 0 and np.array_equal(want_payload, payload)
-
-
-# ------------------------------------------------------------------ 6. capped grids
-def test_both_nodes_on_capped_grids():
-    """One child process on the diagnostic build, COMMS_GRID_CAP = 1, then 3: four or more passes per lane, outputs equal an
-    uncapped handle's and the reference."""
-    assert os.path.exists(DIAG_LIB), "the diagnostic build is part of build(): %s" % DIAG_LIB
-    env = dict(os.environ, COMMS_HIP_LIB=DIAG_LIB)
-    env.pop("COMMS_GRID_CAP", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "symmap_grid_child.py")], env=env, capture_output=True, text=True,
-                         timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-3000:] + out.stderr[-3000:]
 
 
 # ------------------------------------------------------------------ 7. host graph

@@ -10,6 +10,7 @@ import deframe_ref as dr
 import framesync_ref as fr
 import grid_cases as gc
 import ratematch_ref as rr
+import symmap_ref as sm
 import syncest_ref as sr
 import viterbi_ref as vr
 
@@ -36,12 +37,13 @@ def test_every_persistent_kernel_has_a_case():
             if n:
                 calls[name] = n
     assert calls == {"syncest.hip": 1, "symsync.hip": 1, "framesync.hip": 1, "resample.hip": 1, "channelizer.hip": 1, "deframe.hip": 1,
-                     "convcode.hip": 2, "ratematch.hip": 2, "crc.hip": 1}, calls
+                     "convcode.hip": 2, "ratematch.hip": 2, "crc.hip": 1, "symmap.hip": 2, "ofdm.hip": 1}, calls
     have = {}
     for cs in gc.CASES:
         have.setdefault(cs.kernel, set()).add(cs.fmt.get("node") or cs.fmt.get("dir") or "")
     assert {k: len(v) for k, v in have.items()} == calls
-    assert have["convcode.hip"] == {"encoder", "viterbi"} and have["ratematch.hip"] == {"tx", "rx"}
+    assert have["convcode.hip"] == {"encoder", "viterbi"} and have["ratematch.hip"] == {"tx", "rx"} and have["symmap.hip"] == {"map", "demap"}
+    assert {cs.fmt["direction"] for cs in gc.cases_of("ofdm")} == {"mod", "demod"}     # ofdm.hip takes its cap once for both
     assert {cs.family for cs in gc.CASES} == set(gc.FAMILIES)
 
 
@@ -52,9 +54,10 @@ def test_every_case_makes_four_passes_and_a_ragged_last_one():
             assert w.passes >= gc.MIN_PASSES, (cs.name, cap, w)
             assert w.grid == cap, (cs.name, cap, w)
             assert gc.ragged(cs, cap) or gc.never_ragged(cs, cap), (cs.name, cap, w)
-    # the exceptions are the frames and receive lengths the workgroup divides, at cap 1 only
+    # the exceptions are the frames and receive lengths the workgroup divides and the OFDM kernels' one item per pass, at cap 1 only
     assert [(cs.name, cap) for cs in gc.CASES for cap in gc.CAPS if not gc.ragged(cs, cap)] == \
-        [("F2048-K%d-%s" % (K, fmt), 1) for K in (1, 2) for fmt in ("bits", "llr")] + [("rx-N256", 1), ("rx-N2048", 1)]
+        [("F2048-K%d-%s" % (K, fmt), 1) for K in (1, 2) for fmt in ("bits", "llr")] + [("rx-N256", 1), ("rx-N2048", 1)] + \
+        [(cs.name, 1) for cs in gc.cases_of("ofdm")]
     assert {cs.fmt["F"] for cs in gc.cases_of("deframe")} >= {64, 2048}                 # the issue's two frame lengths
 
 
@@ -89,6 +92,35 @@ def test_seam_cases_sit_on_both_sides():
     assert vr.LDS_STEPS in steps and steps.count(vr.LDS_STEPS + 1) == 2 and {6, 70} <= set(steps)
     assert {cs.fmt["n"] for cs in gc.cases_of("convcode") if cs.fmt.get("steps") == vr.LDS_STEPS + 1} == {2, 3}
     assert any(cs.fmt.get("kinds") == ("special", "noisy") for cs in gc.cases_of("convcode"))
+
+
+def test_constellation_cases_reach_the_seams():
+    """symmap.hip takes its grid cap twice (the mapper, the demapper): ragged map calls, fields that straddle two words and
+    fields that do not, both demapper forms in both formats, a record that is no whole number of 64-symbol chunks and one of
+    several chunks."""
+    maps = [cs.fmt for cs in gc.cases_of("symmap") if cs.fmt["node"] == "map"]
+    demaps = [cs.fmt for cs in gc.cases_of("symmap") if cs.fmt["node"] == "demap"]
+    assert all(gc.ragged(cs, cap) for cs in gc.cases_of("symmap") for cap in gc.CAPS)
+    assert {32 % f["m"] != 0 for f in maps} == {True, False}
+    assert any(f["P"] and f["G"] for f in maps) and any(not f["P"] and not f["G"] for f in maps)
+    for fmt in ("llr", "bits"):
+        assert {sm.table_of(f["table"])[3] is None for f in demaps if f["fmt"] == fmt} == {True, False}      # table form, per-axis form
+        assert {(f["table"], f["F"]) for f in demaps if f["fmt"] == fmt} == set(gc.SYMMAP_DEMAP_FORMATS)
+    assert any(f["F"] % 64 for f in demaps) and any(f["F"] > 64 for f in demaps)
+
+
+def test_ofdm_cases_reach_every_transform_and_a_ragged_group():
+    """The three shapes of the transform (N = 64: no third step; 512 and 1024: radix 2 and 4 in it), the pilot phase correction
+    and the channel estimate in every case, and a last group of a block that a wave does not fill."""
+    assert {f.n_fft for f in gc.OFDM_FORMATS.values()} >= {64, 512, 1024}
+    for cs in gc.cases_of("ofdm"):
+        f, direction = gc.OFDM_FORMATS[cs.fmt["format"]], cs.fmt["direction"]
+        assert f.cpe and f.n_train
+        for cap in gc.CAPS:
+            items = gc.walk(cs, cap).total
+            assert cap == 1 or items % cap, (cs.name, cap)                   # the last pass is ragged across workgroups ...
+        per_frame = f.n_syms + (f.n_train if direction == "mod" else 0)
+        assert per_frame % (1024 // f.n_fft) or f.n_fft == 1024              # ... and the last group of a block within a wave
 
 
 def test_rate_matching_walks_take_every_regime():

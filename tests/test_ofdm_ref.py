@@ -4,6 +4,7 @@ fixes the bound the GPU tests use) and the rules of the case tables."""
 import numpy as np
 import pytest
 
+import grid_cases as gc
 import ofdm_ref as r
 
 
@@ -113,23 +114,8 @@ def test_format_table_covers_the_issue():
     assert {f.n_fft for f in fs.values()} == {64, 128, 256, 512, 1024}
     assert r.FRAME_COUNTS == (1, 5)
     assert "n64_11a" in r.CHANNEL_FORMATS and "n128_cp9" in r.CPE_FORMATS and "n1024_cp72" in r.CPE_FORMATS
-    for f in list(fs.values()) + list(r.GRID_FORMATS.values()):
+    for f in list(fs.values()) + list(gc.OFDM_FORMATS.values()):
         assert f.frame_samples <= 1 << 24 and f.D >= 1
-
-
-@pytest.mark.parametrize("direction", ("mod", "demod"))
-def test_grid_cases_make_four_ragged_passes(direction):
-    assert r.CAPS == (1, 3) and r.MIN_PASSES == 4
-    assert {r.GRID_FORMATS[name].n_fft for name, _ in r.GRID_CASES} >= {64, 512, 1024}
-    for name, n_frames in r.GRID_CASES:
-        f = r.GRID_FORMATS[name]
-        assert f.cpe and f.n_train
-        for cap in r.CAPS:
-            items = r.grid_items(f, direction, n_frames, cap)
-            assert r.grid_passes(f, direction, n_frames, cap) >= r.MIN_PASSES
-            assert cap == 1 or items % cap, (name, cap)                      # the last pass is ragged across workgroups ...
-        per_frame = f.n_syms + (f.n_train if direction == "mod" else 0)
-        assert per_frame % (1024 // f.n_fft) or f.n_fft == 1024              # ... and the last group of a block within a wave
 
 
 def test_block_rule():

@@ -1,17 +1,13 @@
 """The symbol mapper's and soft demapper's reference (tests/symmap_ref.py) held to its own claims, the host-side tables of the
 library against it, the per-axis identities the demapper's second kernel form rests on against the brute-force definition on
-the adversarial input set, the argument refusals of both creates (which never reach a device), and the capped-grid case table
-of tests/symmap_grid_child.py.  No GPU."""
+the adversarial input set, and the argument refusals of both creates (which never reach a device).  No GPU."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import symmap_ref as sr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_ADVERSARIAL = 200_000
 
 
@@ -193,27 +189,6 @@ def test_creates_refuse_bad_arguments_before_the_device(c):
     assert e.value.code == c.COMMS_ERR_ARG
     with pytest.raises(ValueError):
         c.DemapNode(3, pts[:4], 8)
-
-
-# ------------------------------------------------------------------ the capped-grid cases of tests/symmap_grid_child.py
-def test_capped_grid_cases_make_four_passes_and_reach_the_seams():
-    """symmap.hip takes its grid cap twice (the mapper, the demapper); each has cases that make four or more passes per lane at
-    both caps, a ragged last pass somewhere, straddling fields, and both kernel forms."""
-    text = open(os.path.join(ROOT, "comms_rs_amd", "csrc", "symmap.hip")).read()
-    assert len(re.findall(r"max_grid = stateless_workgroups\(", text)) == 2
-    for m, _, E, P, G, frames in sr.GRID_MAP_CASES:
-        for cap in sr.CAPS:
-            assert sr.map_passes(E, m, P, G, frames, cap) >= sr.MIN_PASSES, (m, E, cap)
-    assert any(frames * (P + -(-E // m) + G) % (cap * sr.WG) for m, _, E, P, G, frames in sr.GRID_MAP_CASES for cap in sr.CAPS)
-    assert {32 % m != 0 for m, *_ in sr.GRID_MAP_CASES} == {True, False}
-    forms = set()
-    for name, F, frames in sr.GRID_DEMAP_CASES:
-        forms.add(sr.table_of(name)[3] is None)
-        for cap in sr.CAPS:
-            for fmt in ("llr", "bits"):
-                assert sr.demap_passes(F, frames, cap, fmt) >= sr.MIN_PASSES, (name, F, cap, fmt)
-    assert forms == {True, False}
-    assert any(F % 64 for _, F, _ in sr.GRID_DEMAP_CASES) and any(F > 64 for _, F, _ in sr.GRID_DEMAP_CASES)
 
 
 def test_demap_lengths_reach_the_word_seams():
