@@ -374,6 +374,21 @@ _PROTOS = {
     "comms_ofdm_get_kernel": [_vp, _i32, _sz, C.c_char_p, _sz],
     "comms_ofdm_set_timer": [_vp, _vp],
     "comms_ofdm_destroy": [_vp],
+    "comms_ofdmsync_create": [_sz, _sz, _f64, _sz, _sz, _sz, _i32, _pp],
+    "comms_ofdmsync_run_dev": [_vp, _vp, _sz, _vp, _vp, _sz, _psz, _vp],
+    "comms_ofdmsync_run": [_vp, _vp, _sz, _vp, _vp, _sz, _psz],
+    "comms_ofdmsync_flush": [_vp, _vp, _vp, _sz, _psz],
+    "comms_ofdmsync_correct_run_dev": [_vp, _vp, _sz, _vp, _vp, _vp],
+    "comms_ofdmsync_correct_run": [_vp, _vp, _sz, _vp, _vp],
+    "comms_ofdmsync_state_len": [_sz, _sz, _sz, _psz],
+    "comms_ofdmsync_get_state": [_vp, _vp, _sz],
+    "comms_ofdmsync_set_state": [_vp, _vp, _sz],
+    "comms_ofdmsync_get_position": [_vp, C.POINTER(C.c_uint64)],
+    "comms_ofdmsync_set_position": [_vp, C.c_uint64],
+    "comms_ofdmsync_set_threshold": [_vp, _f64],
+    "comms_ofdmsync_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_ofdmsync_set_timer": [_vp, _vp],
+    "comms_ofdmsync_destroy": [_vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],

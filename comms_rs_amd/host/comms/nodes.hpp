@@ -1882,6 +1882,172 @@ public:
     explicit OfdmDemodNodeDev(const OfdmSpec& format, int device = 0) : DevNode(device, "OfdmDemodNodeDev::new", format, device) {}
 };
 
+// OFDM stream synchroniser (comms_ofdmsync_*; additional nodes): what stands between a received sample stream and OfdmDemodNode.
+//   stream -> OfdmSyncNode -+- detections -> DeframeNode (COMMS_SYM_C32, n_payload = frame_samples, offset 0, lookback())
+//                            +- output ----------------------+-> OfdmCfoCorrectNode -> OfdmDemodNode
+// OfdmSyncNode takes the sample blocks and sends, per block, the frame starts that the block decides -- possibly none -- with
+// the carrier-frequency offset of each (rad / sample): the whole message on `output`, the detections alone on `detections`,
+// which is what DeframeNode's second receiver takes.  A block of n samples decides n positions; flush() ends a stream; the
+// message does not depend on how the stream is cut into blocks.  It is a host value on either message kind (the call
+// synchronises its stream): run() bodies of their own, as the frame synchroniser's.
+struct OfdmSyncSpec {
+    size_t lag;            // 1 ... 2048: distance of the two correlated windows
+    size_t window;         // 2 ... 2048: their length
+    double threshold;      // 0 < threshold <= 1
+    size_t guard;          // <= 512: half-width of the peak search
+    size_t advance = 0;    // <= 2048: samples by which `index` lies ahead of the peak, into the prefix
+    // the frames of an OfdmModNode / OfdmDemodNode format with n_train >= 2: lag = window = n_fft + n_cp
+    static OfdmSyncSpec for_format(const OfdmSpec& f, double threshold, size_t guard, size_t advance = 0) {
+        const size_t sym = static_cast<size_t>(f.n_fft) + static_cast<size_t>(f.n_cp);
+        return OfdmSyncSpec{sym, sym, threshold, guard, advance};
+    }
+    size_t lookback() const { return window + lag + guard + advance - 1; }  // the least `lookback` of the DeframeNode behind
+};
+struct OfdmSyncFound {
+    FrameSyncOp::Detections detections;  // ascending index
+    std::vector<double> cfo;             // one per detection: atan2(corr_im, corr_re) / lag
+    size_t size() const { return detections.size(); }
+    operator FrameSyncOp::Detections() const { return detections; }
+};
+struct OfdmSyncOp {
+    OfdmSyncOp(const char* who, const OfdmSyncSpec& f, int device)
+        : h_(create<decltype(h_)>(who, comms_ofdmsync_create, f.lag, f.window, f.threshold, f.guard, f.advance, size_t(0), static_cast<int32_t>(device))),
+          spec_(f) {}
+    Result<OfdmSyncFound> flush() {  // a flush decides window + lag + guard positions
+        return collect(spec_.window + spec_.lag + spec_.guard,
+                       [&](auto* out, double* cfo, size_t cap, size_t* found) { return comms_ofdmsync_flush(h_.get(), out, cfo, cap, found); });
+    }
+    size_t lookback() const { return spec_.lookback(); }
+    uint64_t position() const {  // stream index of the next sample
+        uint64_t t = 0;
+        throw_on(comms_ofdmsync_get_position(h_.get(), &t), "OfdmSyncNode::position");
+        return t;
+    }
+    std::string kernel(size_t n) const { return kernel_name(comms_ofdmsync_get_kernel, h_.get(), n); }  // "ofdmsync_detect_kernel ..."
+
+protected:
+    Result<OfdmSyncFound> detect(const Complex32* in, size_t n) {
+        return collect(n, [&](auto* out, double* cfo, size_t cap, size_t* found) { return comms_ofdmsync_run(h_.get(), c32(in), n, out, cfo, cap, found); });
+    }
+    Result<OfdmSyncFound> detect_dev(const Complex32* in, size_t n, void* s) {
+        return collect(n, [&](auto* out, double* cfo, size_t cap, size_t* found) {
+            return comms_ofdmsync_run_dev(h_.get(), c32(in), n, out, cfo, cap, found, s);
+        });
+    }
+
+private:
+    // no call that decides n positions has more than (n + guard) / (guard + 1) detections: they are more than `guard` apart
+    template <class F>
+    Result<OfdmSyncFound> collect(size_t n, F&& call) {
+        const size_t cap = (n + spec_.guard) / (spec_.guard + 1);
+        OfdmSyncFound out{FrameSyncOp::Detections(cap), std::vector<double>(cap)};
+        size_t found = 0;
+        comms_status_t st = call(out.detections.data(), out.cfo.data(), cap, &found);
+        if (st != COMMS_OK) return to_node_error(st);
+        out.detections.resize(found);
+        out.cfo.resize(found);
+        return out;
+    }
+    Owned<comms_ofdmsync_t, comms_ofdmsync_destroy> h_;
+    OfdmSyncSpec spec_;
+};
+template <class In>
+struct OfdmSyncPorts {  // as Ports, with the second sender
+    NodeReceiver<In> input;
+    NodeSender<OfdmSyncFound> output;
+    NodeSender<FrameSyncOp::Detections> detections;
+    auto receivers() { return std::tie(input); }
+    auto senders() { return std::tie(output, detections); }
+};
+class OfdmSyncNode : public DeriveNode<OfdmSyncNode>, public OfdmSyncPorts<std::vector<Complex32>>, public OfdmSyncOp {
+public:
+    explicit OfdmSyncNode(const OfdmSyncSpec& spec, int device = 0) : OfdmSyncOp("OfdmSyncNode::new", spec, device) {}
+    Result<OfdmSyncFound> run(const std::vector<Complex32>& samples) { return detect(samples.data(), samples.size()); }
+};
+class OfdmSyncNodeDev : public DeriveNode<OfdmSyncNodeDev>, public OfdmSyncPorts<DeviceBuf<Complex32>>, public OnStream<OfdmSyncOp> {
+public:
+    explicit OfdmSyncNodeDev(const OfdmSyncSpec& spec, int device = 0) : OnStream(device, "OfdmSyncNodeDev::new", spec, device) {}
+    Result<OfdmSyncFound> run(const DeviceBuf<Complex32>& in) {
+        comms_status_t st = wait(in);
+        if (st != COMMS_OK) return to_node_error(st);
+        return detect_dev(in.ptr(), in.size(), get());
+    }
+};
+
+// The correct stage (comms_ofdmsync_correct_*): takes DeframeNode's message in the COMMS_SYM_C32 format (records of n_frame
+// samples) and, on a second receiver, what OfdmSyncNode sent on `output` for the same block; sends record f times
+// exp(-i cfo n) under the same headers, all records of a message by one launch -- OfdmDemodNode's input once `data` is read as
+// samples.  A frame's offset arrives with its detection and is kept until its record does (a record ends in a later block than
+// its detection); a record whose detection was never seen is a DataError.  A message without frames passes through empty.
+struct OfdmCfoCorrectOp {
+    using Frames = DeframeOp::Frames;
+    using FramesDev = DeframeOp::FramesDev;
+    OfdmCfoCorrectOp(const char* who, size_t n_frame, int device) : n_frame_(n_frame) {
+        if (n_frame == 0) throw std::runtime_error(std::string(who) + ": n_frame is 1 ... 2^20");
+        // the handle's detect stage is not used: the least lag and window
+        h_ = create<decltype(h_)>(who, comms_ofdmsync_create, size_t(1), size_t(2), 1.0, size_t(0), size_t(0), n_frame, static_cast<int32_t>(device));
+    }
+    size_t frame_bytes() const { return n_frame_ * sizeof(Complex32); }
+
+protected:
+    Result<Frames> correct(const Frames& in, const OfdmSyncFound& found) {
+        std::vector<double> cfo;
+        if (!match(in.headers, in.frame_bytes, in.data.size(), found, cfo)) return NodeError::DataError;
+        Frames out{std::vector<uint8_t>(in.size() * frame_bytes()), in.headers, frame_bytes()};
+        return ok_or(comms_ofdmsync_correct_run(h_.get(), reinterpret_cast<const comms_c32*>(in.data.data()), in.size(), cfo.data(),
+                                                reinterpret_cast<comms_c32*>(out.data.data())), out);
+    }
+    Result<FramesDev> correct_dev(const FramesDev& in, const OfdmSyncFound& found, const DevStream& on) {
+        std::vector<double> cfo;
+        if (!match(in.headers, in.frame_bytes, in.data.size(), found, cfo)) return NodeError::DataError;
+        FramesDev out{DeviceBuf<uint8_t>(in.size() ? in.size() * frame_bytes() : 16, on.device()), in.headers, frame_bytes()};
+        return ok_or(on.submit(in.data, out.data, [&](void* s) {
+            return comms_ofdmsync_correct_run_dev(h_.get(), reinterpret_cast<const comms_c32*>(in.data.ptr()), in.size(), cfo.data(),
+                                                  reinterpret_cast<comms_c32*>(out.data.ptr()), s);
+        }), out);
+    }
+
+private:
+    // the offsets of the message's records, by index; records come in ascending index, so what lies before a matched
+    // detection belongs to frames that the deframer dropped
+    bool match(const std::vector<comms_deframe_header_t>& headers, size_t in_frame_bytes, size_t bytes, const OfdmSyncFound& found,
+               std::vector<double>& cfo) {
+        if (found.cfo.size() != found.detections.size() || in_frame_bytes != frame_bytes() || bytes < headers.size() * in_frame_bytes) return false;
+        for (size_t i = 0; i < found.size(); ++i) pending_.emplace_back(found.detections[i].index, found.cfo[i]);
+        cfo.reserve(headers.size());
+        for (const comms_deframe_header_t& hd : headers) {
+            size_t at = 0;
+            while (at < pending_.size() && pending_[at].first != hd.index) ++at;
+            if (at == pending_.size()) return false;
+            cfo.push_back(pending_[at].second);
+            pending_.erase(pending_.begin(), pending_.begin() + static_cast<std::ptrdiff_t>(at) + 1);
+        }
+        return true;
+    }
+    Owned<comms_ofdmsync_t, comms_ofdmsync_destroy> h_;
+    size_t n_frame_;
+    std::vector<std::pair<uint64_t, double>> pending_;  // (index, cfo) of the detections whose records are still to come
+};
+template <class FramesT>
+struct OfdmCfoCorrectPorts {  // as Ports, with the second receiver
+    NodeReceiver<FramesT> input;          // DeframeNode's message
+    NodeReceiver<OfdmSyncFound> found;    // OfdmSyncNode's message for the same block
+    NodeSender<FramesT> output;
+    auto receivers() { return std::tie(input, found); }
+    auto senders() { return std::tie(output); }
+};
+class OfdmCfoCorrectNode : public DeriveNode<OfdmCfoCorrectNode>, public OfdmCfoCorrectPorts<OfdmCfoCorrectOp::Frames>, public OfdmCfoCorrectOp {
+public:
+    explicit OfdmCfoCorrectNode(size_t n_frame, int device = 0) : OfdmCfoCorrectOp("OfdmCfoCorrectNode::new", n_frame, device) {}
+    Result<Frames> run(const Frames& in, const OfdmSyncFound& found) { return correct(in, found); }
+};
+// on device-resident messages: DeframeNodeDev's records in, the corrected records in a DeviceBuf out (headers on the host)
+class OfdmCfoCorrectNodeDev : public DeriveNode<OfdmCfoCorrectNodeDev>, public OfdmCfoCorrectPorts<OfdmCfoCorrectOp::FramesDev>, public OnStream<OfdmCfoCorrectOp> {
+public:
+    explicit OfdmCfoCorrectNodeDev(size_t n_frame, int device = 0) : OnStream(device, "OfdmCfoCorrectNodeDev::new", n_frame, device) {}
+    Result<FramesDev> run(const FramesDev& in, const OfdmSyncFound& found) { return correct_dev(in, found, *this); }
+};
+
 // NcoNode::new(dphase, Option<phase>) (src/demodulation/nco.rs:118-133) in block form: one
 // message is a vector of phase errors, the output is exp(i*phase) per sample.  (The reference
 // node is per sample, f64 -> Complex<f64>; a closed loop runs it at block rate here.)

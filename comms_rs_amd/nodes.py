@@ -2120,6 +2120,122 @@ class OfdmDemodNode(_Ofdm):
         check(lib().comms_ofdm_demod_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
 
 
+class OfdmSyncNode(_Handle):
+    """OFDM stream synchroniser (comms_ofdmsync_*).  run() correlates the received sample stream with itself at `lag` over
+    `window` samples, searches peaks of the normalised metric over +-`guard` positions above `threshold`, in one launch, and
+    returns (detections, cfo): FrameDetection values whose `index` lies `advance` samples ahead of the peak, and the
+    carrier-frequency offsets arg(corr) / lag in rad / sample (float64).  A call on n samples decides n positions; flush() ends a
+    stream; the detections do not depend on how the stream is cut into calls.  The detections feed
+    DeframeNode(n_frame, 0, lookback >= window + lag + guard + advance - 1) in "c32"; correct() then multiplies record f by
+    exp(-i cfo[f] n), all records in one launch, in front of OfdmDemodNode.  `found` is the true count of the last call."""
+    _prefix = "comms_ofdmsync"
+    found = 0
+
+    def __init__(self, lag, window, threshold, guard, advance=0, n_frame=0, device=0):
+        super().__init__()
+        self.lag, self.window, self.guard, self.advance, self.n_frame = int(lag), int(window), int(guard), int(advance), int(n_frame)
+        check(lib().comms_ofdmsync_create(self.lag, self.window, float(threshold), self.guard, self.advance, self.n_frame, device,
+                                          C.byref(self._h)))
+
+    @classmethod
+    def for_format(cls, ofdm_node, threshold, guard, advance=0, device=0):
+        """The node for OfdmModNode / OfdmDemodNode `ofdm_node`'s frames (n_train >= 2): lag = window = n_fft + n_cp and
+        n_frame = frame_samples."""
+        sym = ofdm_node.n_fft + ofdm_node.n_cp
+        return cls(sym, sym, threshold, guard, advance=advance, n_frame=ofdm_node.frame_samples, device=device)
+
+    @property
+    def lookback(self):
+        """The least `lookback` of the DeframeNode behind this node."""
+        return self.window + self.lag + self.guard + self.advance - 1
+
+    def _cap(self, n, cap):
+        return (n + self.guard) // (self.guard + 1) if cap is None else int(cap)
+
+    def _result(self, out, cfo, cap, found, raw):
+        self.found = found.value
+        k = min(self.found, cap)
+        return (out[:k] if raw else [FrameDetection(d) for d in out[:k]]), cfo[:k]
+
+    def run(self, samples, cap=None, raw=False):
+        x = np.ascontiguousarray(samples, dtype=np.complex64)
+        cap = self._cap(x.size, cap)
+        out, cfo, found = np.zeros(cap, FRAME_DETECTION_DTYPE), np.zeros(cap, np.float64), C.c_size_t()
+        check(lib().comms_ofdmsync_run(self._h, _ptr(x), x.size, _ptr(out) if cap else None, _ptr(cfo) if cap else None, cap,
+                                       C.byref(found)))
+        return self._result(out, cfo, cap, found, raw)
+
+    def run_dev(self, in_ptr, n, cap=None, stream=0, raw=False):
+        cap = self._cap(n, cap)
+        out, cfo, found = np.zeros(cap, FRAME_DETECTION_DTYPE), np.zeros(cap, np.float64), C.c_size_t()
+        check(lib().comms_ofdmsync_run_dev(self._h, in_ptr, n, _ptr(out) if cap else None, _ptr(cfo) if cap else None, cap,
+                                           C.byref(found), stream))
+        return self._result(out, cfo, cap, found, raw)
+
+    def flush(self, cap=None, raw=False):
+        """The positions still undecided, as if window + lag + guard zero samples followed; history zero afterwards, position kept."""
+        cap = self._cap(self.window + self.lag + self.guard, cap)
+        out, cfo, found = np.zeros(cap, FRAME_DETECTION_DTYPE), np.zeros(cap, np.float64), C.c_size_t()
+        check(lib().comms_ofdmsync_flush(self._h, _ptr(out) if cap else None, _ptr(cfo) if cap else None, cap, C.byref(found)))
+        return self._result(out, cfo, cap, found, raw)
+
+    def correct(self, records, cfo):
+        """complex64 (n_frames, n_frame) records and one cfo per record -> the records times exp(-i cfo n)."""
+        x = _as_c64(records)
+        if not self.n_frame or x.size % self.n_frame:
+            raise ValueError("the input must hold whole records of n_frame = %d samples" % self.n_frame)
+        n_frames = x.size // self.n_frame
+        w = np.ascontiguousarray(cfo, dtype=np.float64).ravel()
+        if w.size != n_frames:
+            raise ValueError("cfo holds one value per record")
+        out = np.zeros((n_frames, self.n_frame), np.complex64)
+        check(lib().comms_ofdmsync_correct_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(w) if n_frames else None,
+                                               _ptr(out) if n_frames else None))
+        return out
+
+    def correct_dev(self, in_ptr, n_frames, cfo, out_ptr, stream=0):
+        w = np.ascontiguousarray(cfo, dtype=np.float64).ravel()
+        if w.size != int(n_frames):
+            raise ValueError("cfo holds one value per record")
+        check(lib().comms_ofdmsync_correct_run_dev(self._h, in_ptr, int(n_frames), _ptr(w) if w.size else None, out_ptr, stream))
+
+    def state_len(self):
+        m = C.c_size_t()
+        check(lib().comms_ofdmsync_state_len(self.lag, self.window, self.guard, C.byref(m)))
+        return m.value
+
+    def state(self, n_state=None):
+        """The last n_state samples (default: all window + lag + 2 guard - 1), newest first."""
+        n_state = self.state_len() if n_state is None else int(n_state)
+        st = np.empty(n_state, np.complex64)
+        check(lib().comms_ofdmsync_get_state(self._h, _ptr(st), n_state))
+        return st
+
+    def set_state(self, state):
+        state = np.ascontiguousarray(state, dtype=np.complex64)
+        check(lib().comms_ofdmsync_set_state(self._h, _ptr(state), state.size))
+        return self
+
+    def position(self):
+        """Stream index of the next sample."""
+        t = C.c_uint64()
+        check(lib().comms_ofdmsync_get_position(self._h, C.byref(t)))
+        return t.value
+
+    def set_position(self, position):
+        check(lib().comms_ofdmsync_set_position(self._h, int(position)))
+        return self
+
+    def set_threshold(self, threshold):
+        check(lib().comms_ofdmsync_set_threshold(self._h, float(threshold)))
+        return self
+
+    def kernel(self, n):
+        """What a call on n samples is run by: "ofdmsync_detect_kernel tile=.. wg=.. lag=.. window=.. guard=.. lds=.. tiles=.. grid=..".
+        """
+        return self._kernel_name(n)
+
+
 def qfilt_taps(n_taps, alpha, sam_per_sym):
     """util/math.rs:307-342 (f64, real); even n_taps is incremented."""
     out = np.empty(lib().comms_qfilt_len(int(n_taps)), np.float64)

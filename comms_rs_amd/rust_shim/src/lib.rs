@@ -1714,6 +1714,160 @@ impl OfdmDemodNode {
     }
 }
 
+/// What `OfdmSyncNode` sends per block: the detections the block decides (possibly none), ordered by stream index, and next to
+/// each its carrier-frequency offset `corr_im.atan2(corr_re) / lag` in rad / sample.
+#[derive(Clone, Debug, Default, PartialEq)]
+pub struct OfdmDetections {
+    pub detections: Vec<comms_frame_detection_t>,
+    pub cfo: Vec<f64>,
+}
+
+/// OFDM stream synchroniser (comms_ofdmsync_*; an additional node), in front of `DeframeNode`: correlates the received
+/// `Complex<f32>` sample stream with itself at `lag` over `window` samples (the repeated training symbol: `lag = window =
+/// n_fft + n_cp`), searches peaks of the normalised metric over +-`guard` positions above `threshold` and sends, per block, the
+/// frame starts (`index` lies `advance` samples ahead of the peak) with their offsets.  A block of n samples decides n
+/// positions; `flush` ends a stream; the detections do not depend on how the stream is cut into blocks.  The deframer behind it:
+/// `DeframeNode::new(n_frame, 0, lookback(), .., COMMS_SYM_C32, None)`, then `OfdmCfoCorrectNode`.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct OfdmSyncNode {
+    pub input: NodeReceiver<Vec<Complex<f32>>>,
+    h: *mut comms_ofdmsync_t,
+    lag: usize,
+    window: usize,
+    guard: usize,
+    advance: usize,
+    pub output: NodeSender<OfdmDetections>,
+}
+handle_node!(OfdmSyncNode, comms_ofdmsync_destroy);
+impl OfdmSyncNode {
+    /// `Err(())`: lag outside 1 ..= 2048, window outside 2 ..= 2048, a threshold outside (0, 1], a guard beyond 512 or an advance
+    /// beyond 2048.
+    pub fn new(lag: usize, window: usize, threshold: f64, guard: usize, advance: usize) -> Result<Self, ()> {
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_ofdmsync_create(lag, window, threshold, guard, advance, 0, 0, &mut h) };
+        if st != COMMS_OK { return Err(()); }
+        Ok(OfdmSyncNode { input: Default::default(), h, lag, window, guard, advance, output: Default::default() })
+    }
+    /// The node for the frames of `format` (n_train >= 2): `lag = window = n_fft + n_cp`.
+    pub fn for_format(format: &OfdmFormat, threshold: f64, guard: usize, advance: usize) -> Result<Self, ()> {
+        if format.n_fft < 0 || format.n_cp < 0 { return Err(()); }
+        let sym = (format.n_fft + format.n_cp) as usize;
+        Self::new(sym, sym, threshold, guard, advance)
+    }
+    /// The least `lookback` of the `DeframeNode` behind this node.
+    pub fn lookback(&self) -> usize { self.window + self.lag + self.guard + self.advance - 1 }
+    fn collect<F>(&mut self, n: usize, call: F) -> Result<OfdmDetections, NodeError>
+    where
+        F: FnOnce(*mut comms_ofdmsync_t, *mut comms_frame_detection_t, *mut f64, usize, *mut usize) -> comms_status_t,
+    {
+        // detections are more than `guard` apart: no call that decides n positions has more than ceil(n / (guard + 1))
+        let cap = (n + self.guard) / (self.guard + 1);
+        let mut out = OfdmDetections { detections: vec![comms_frame_detection_t::default(); cap], cfo: vec![0.0f64; cap] };
+        let mut found = 0usize;
+        let st = call(self.h, out.detections.as_mut_ptr(), out.cfo.as_mut_ptr(), cap, &mut found);
+        if st != COMMS_OK { return Err(to_err(st)); }
+        out.detections.truncate(found);
+        out.cfo.truncate(found);
+        Ok(out)
+    }
+    pub fn run(&mut self, input: &[Complex<f32>]) -> Result<OfdmDetections, NodeError> {
+        self.collect(input.len(), |h, out, cfo, cap, found| unsafe {
+            comms_ofdmsync_run(h, input.as_ptr() as *const comms_c32, input.len(), out, cfo, cap, found)
+        })
+    }
+    /// The positions still undecided, as if `window + lag + guard` zero samples followed; the history is zero afterwards.
+    pub fn flush(&mut self) -> Result<OfdmDetections, NodeError> {
+        self.collect(self.window + self.lag + self.guard, |h, out, cfo, cap, found| unsafe { comms_ofdmsync_flush(h, out, cfo, cap, found) })
+    }
+    /// The last `window + lag + 2 guard - 1` raw samples, newest first (checkpoints; the halo in front of a stream shard).
+    pub fn state(&self) -> Result<Vec<Complex<f32>>, NodeError> {
+        let mut n = 0usize;
+        let st = unsafe { comms_ofdmsync_state_len(self.lag, self.window, self.guard, &mut n) };
+        if st != COMMS_OK { return Err(to_err(st)); }
+        let mut state = vec![Complex::new(0.0f32, 0.0f32); n];
+        let st = unsafe { comms_ofdmsync_get_state(self.h, state.as_mut_ptr() as *mut comms_c32, n) };
+        if st == COMMS_OK { Ok(state) } else { Err(to_err(st)) }
+    }
+    pub fn set_state(&mut self, state: &[Complex<f32>]) -> Result<(), NodeError> {
+        let st = unsafe { comms_ofdmsync_set_state(self.h, state.as_ptr() as *const comms_c32, state.len()) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    /// Stream index of the next sample (checkpoints; the first index of a stream shard).
+    pub fn position(&self) -> u64 {
+        let mut t = 0u64;
+        unsafe { comms_ofdmsync_get_position(self.h, &mut t) };
+        t
+    }
+    pub fn set_position(&mut self, position: u64) -> Result<(), NodeError> {
+        let st = unsafe { comms_ofdmsync_set_position(self.h, position) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+    pub fn set_threshold(&mut self, threshold: f64) -> Result<(), NodeError> {
+        let st = unsafe { comms_ofdmsync_set_threshold(self.h, threshold) };
+        if st == COMMS_OK { Ok(()) } else { Err(to_err(st)) }
+    }
+}
+
+/// The correct stage of the OFDM synchroniser (comms_ofdmsync_correct_*; an additional node), between `DeframeNode`
+/// (`COMMS_SYM_C32`, records of `n_frame` samples) and `OfdmDemodNode`: takes the deframer's message and, on `found`, what
+/// `OfdmSyncNode` sent for the same block; sends record f times exp(-i cfo n), all records by one launch, under the same
+/// headers.  A frame's offset arrives with its detection and is kept until its record does; a record whose detection was never
+/// seen is `NodeError::DataError`.
+#[derive(Node)]
+#[pass_by_ref]
+pub struct OfdmCfoCorrectNode {
+    pub input: NodeReceiver<Frames>,
+    pub found: NodeReceiver<OfdmDetections>,
+    h: *mut comms_ofdmsync_t,
+    n_frame: usize,
+    pending: Vec<(u64, f64)>,   // (index, cfo) of the detections whose records are still to come, ascending
+    pub output: NodeSender<Frames>,
+}
+handle_node!(OfdmCfoCorrectNode, comms_ofdmsync_destroy);
+impl OfdmCfoCorrectNode {
+    /// `Err(())`: n_frame outside 1 ..= 2^20.
+    pub fn new(n_frame: usize) -> Result<Self, ()> {
+        if n_frame == 0 { return Err(()); }
+        let mut h = ptr::null_mut();
+        let st = unsafe { comms_ofdmsync_create(1, 2, 1.0, 0, 0, n_frame, 0, &mut h) };   // the detect stage of this handle is not used
+        if st != COMMS_OK { return Err(()); }
+        Ok(OfdmCfoCorrectNode { input: Default::default(), found: Default::default(), h, n_frame, pending: Vec::new(), output: Default::default() })
+    }
+    /// `records` holds `cfo.len()` records of `n_frame` samples.
+    pub fn correct(&mut self, records: &[Complex<f32>], cfo: &[f64]) -> Result<Vec<Complex<f32>>, NodeError> {
+        if records.len() != cfo.len() * self.n_frame { return Err(NodeError::DataError); }
+        let mut out = vec![Complex::new(0.0f32, 0.0f32); records.len()];
+        let st = unsafe {
+            comms_ofdmsync_correct_run(self.h, records.as_ptr() as *const comms_c32, cfo.len(), cfo.as_ptr(), out.as_mut_ptr() as *mut comms_c32)
+        };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+    pub fn run(&mut self, frames: &Frames, found: &OfdmDetections) -> Result<Frames, NodeError> {
+        let n_frames = frames.headers.len();
+        let frame_bytes = self.n_frame * size_of::<Complex<f32>>();
+        if found.cfo.len() != found.detections.len() || frames.frame_bytes != frame_bytes || frames.data.len() < n_frames * frame_bytes {
+            return Err(NodeError::DataError);
+        }
+        self.pending.extend(found.detections.iter().zip(&found.cfo).map(|(d, &w)| (d.index, w)));
+        let mut cfo = Vec::with_capacity(n_frames);
+        for hd in &frames.headers {
+            match self.pending.iter().position(|&(index, _)| index == hd.index) {
+                Some(at) => {
+                    cfo.push(self.pending[at].1);
+                    self.pending.drain(..=at);   // records come in ascending index: what lies before was dropped by the deframer
+                }
+                None => return Err(NodeError::DataError),
+            }
+        }
+        let mut out = Frames { data: vec![0u8; n_frames * frame_bytes], headers: frames.headers.clone(), frame_bytes };
+        let st = unsafe {
+            comms_ofdmsync_correct_run(self.h, frames.data.as_ptr() as *const comms_c32, n_frames, cfo.as_ptr(), out.data.as_mut_ptr() as *mut comms_c32)
+        };
+        if st == COMMS_OK { Ok(out) } else { Err(to_err(st)) }
+    }
+}
+
 /// demodulation/nco.rs:118-133 in block form: a vector of phase errors per message.
 #[derive(Node)]
 #[pass_by_ref]
