@@ -5,6 +5,8 @@ tests/test_gpu_framesync.py:
   model_detect  the ARITHMETIC of framesync_kernel: f32, j ascending from +0, one FMA per real product (an FMA is emulated as
                 the f64 sum of the exact product, rounded to f32), the metric with every operation rounded on its own.
   WORDS, cases  every word and every block the GPU test runs, so that the CPU test measures the model on exactly those.
+  dense_*       streams on which every position is a detection, and the positions whose model metric serves as the threshold
+                (tests/test_gpu_dense_metrics.py compares the kernel with model_detect bit for bit).
 """
 import functools
 
@@ -12,6 +14,7 @@ import numpy as np
 
 import oracle
 import rx_ref
+from ofdmsync_ref import fma32
 import symsync_ref
 import syncest_ref
 
@@ -23,6 +26,10 @@ N_BIG = (GRID_CAP + 1) * TILE + 5   # every workgroup walks at least two tiles, 
 # that they still hold): the metric (absolute; it lies in [0, 1]) and the correlation relative to sqrt(Ep e) -- the energy, relative to itself, shares that figure.
 MODEL_METRIC_DISTANCE = 1.4e-6   # measured 1.382e-6: "w512-B" (512 taps: about sqrt(P) ulps of a metric near 1); 13 ... 63 taps: below 4.2e-7
 MODEL_CORR_DISTANCE = 7.6e-7     # measured 7.571e-7: "w512-A", its energy (a chain of 1024 f32 additions)
+# The same over EVERY position of the dense streams (dense_stream: thousands of positions each, where cases() has a few
+# detections).  The metric stays inside MODEL_METRIC_DISTANCE (9.70e-7, qpsk512); the sums do not: no GPU tolerance rests on
+# this one (the dense GPU tests compare bits), it records how far the chosen order lies from the definition.
+DENSE_CORR_DISTANCE = 1.29e-6    # measured 1.282e-6: qpsk512, the energy; its correlation 4.58e-7; 2 ... 63 taps: below 4.6e-7
 # The GPU tolerances: four times those (the kernel may fuse where the model does not).
 METRIC_TOL = 4 * MODEL_METRIC_DISTANCE
 CORR_TOL = 4 * MODEL_CORR_DISTANCE
@@ -71,11 +78,11 @@ def ref_detect(y, p, thr, G):
 
 
 def _fma(a, b, acc):
-    return (acc.astype(np.float64) + a.astype(np.float64) * b.astype(np.float64)).astype(np.float32)
+    return fma32(a, b, acc)      # one rounding, as the hardware's: the f64 sum of the exact product, rounded to f32, tie-corrected
 
 
-def model_detect(y, p, thr, G):
-    """framesync_kernel's arithmetic: (index, c as complex64 parts in complex128, m, e, all metrics) as ref_detect."""
+def model_sums(y, p, G):
+    """framesync_kernel's arithmetic at the positions -G ... len(y) + G - 1: (cr, ci, e, m) as float32."""
     f32 = np.float32
     p = np.asarray(p).astype(np.complex64)
     P, T = p.size, len(y)
@@ -97,7 +104,14 @@ def model_detect(y, p, thr, G):
         num = (cr * cr) + (ci * ci)
         den = Ep * e
         m = np.where(e == 0, f32(0), num / np.where(e == 0, f32(1), den)).astype(f32)
-    idx = _decide(m, -G, f32(thr), G, T)
+    return cr, ci, e, m
+
+
+def model_detect(y, p, thr, G, sums=None):
+    """framesync_kernel's arithmetic: (index, c as complex64 parts in complex128, m, e, all metrics) as ref_detect; `sums` are
+    model_sums(y, p, G) where the caller holds them."""
+    cr, ci, e, m = model_sums(y, p, G) if sums is None else sums
+    idx = _decide(m, -G, np.float32(thr), G, len(y))
     c = cr.astype(np.float64) + 1j * ci.astype(np.float64)
     return idx, c[idx + G], m[idx + G].astype(np.float64), e[idx + G].astype(np.float64), m
 
@@ -238,6 +252,66 @@ def reference(idx):
 
 def case(name):
     return [i for i, cs in enumerate(cases()) if cs[0] == name][0]
+
+
+# ------------------------------------------------------------------ dense streams (tests/test_gpu_dense_metrics.py)
+# With G = 0 the peak rule is "m >= thr": under a tiny threshold every position is a detection, and the metric of the kernel's
+# register-window path decides at every position what the scalar loop then reports.
+DENSE_N = 2 * TILE + 77        # positions whose whole word lies in the stream: two tiles and a ragged third
+DENSE_THR = 1e-30
+DENSE_WORDS = ("p2", "barker13", "qpsk32", "mseq63", "qpsk512")
+DENSE_FAR_WORDS = ("p2", "barker13", "qpsk512")                      # run again at positions past 2^32
+PASS = 2048                    # metrics per pass of a workgroup (256 lanes of eight): FS_PASS
+LATE_GUARD = 8                 # the least guard whose second, partial pass holds all eight lane columns as decided positions
+
+
+@functools.lru_cache(maxsize=None)
+def dense_stream(wn):
+    """DENSE_N + P - 1 symbols of stream(): a QPSK payload with noise everywhere, the word planted twice."""
+    P = words()[wn].size
+    return stream(words()[wn], [300, TILE + 900], DENSE_N + P - 1, 1.0, 0.7, 900 + P)
+
+
+@functools.lru_cache(maxsize=None)
+def dense_sums(wn, G=0):
+    out = model_sums(dense_stream(wn), words()[wn], G)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def dense_detect(wn, thr, G=0):
+    """model_detect of the dense stream: (index, c, m, e, all metrics)."""
+    return model_detect(dense_stream(wn), words()[wn], thr, G, sums=dense_sums(wn, G))
+
+
+def first_pass_picks(wn):
+    """{column: k} at G = 0: metric index r of a single call's tile is position k = r - (P - 1) (mod TILE), its lane column r mod
+    8.  Per column a position with the whole word in the stream and a model metric between the 20th and the 80th percentile:
+    the first such at or behind column * DENSE_N / 8, so that the eight lie in different lanes and tiles."""
+    P = words()[wn].size
+    m = dense_sums(wn)[3][:DENSE_N]
+    lo, hi = np.percentile(m, [20, 80])
+    k = np.flatnonzero((m >= lo) & (m <= hi))
+    return {col: int(k[((k + P - 1) % 8 == col) & (k >= col * DENSE_N // 8)][0]) for col in range(8)}
+
+
+def late_pass_picks(wn):
+    """{column: (k, n1)} at G = LATE_GUARD: metric PASS + column of a tile is computed by the second, partial pass, and is decided
+    position r = PASS + column - G.  A peak k of the model lands there in the second of two calls when the first one takes
+    n1 = k - r + P + G - 1 symbols (the second call's first decided position is n1 - (P + G) + 1).  The peaks are the model's
+    under DENSE_THR with metrics between the 20th and 80th percentile of all peaks, eight of them spread over that range."""
+    P, G = words()[wn].size, LATE_GUARD
+    T = dense_stream(wn).size
+    idx, _, m, _, _ = dense_detect(wn, DENSE_THR, G)
+    lo, hi = np.percentile(m, [20, 80])
+    ok = (m >= lo) & (m <= hi) & (idx >= PASS + 7 - G - P - G + 1) & (idx <= T - P - G)
+    idx = idx[ok][np.argsort(m[ok], kind="stable")]
+    out = {}
+    for col in range(8):
+        k = int(idx[col * idx.size // 8])
+        out[col] = (k, k - (PASS + col - G) + P + G - 1)
+    return out
 
 
 # ------------------------------------------------------------------ the loop the node exists for

@@ -1,6 +1,7 @@
 """The definition of the OFDM synchroniser (include/comms_hip.h, "OFDM synchroniser") in numpy complex128 / float64, an f32
 model of the kernels' order of summation and of the correct stage's rotor, and the streams, cases and bounds that
-tests/test_ofdmsync_ref.py (no GPU) and tests/test_gpu_ofdmsync.py share.  Nothing here touches the library."""
+tests/test_ofdmsync_ref.py (no GPU), tests/test_gpu_ofdmsync.py and tests/test_gpu_dense_metrics.py (the model at every
+position, bit for bit) share.  Nothing here touches the library."""
 import functools
 
 import numpy as np
@@ -50,6 +51,8 @@ def peaks(m, G, thr, lo):
     out = []
     with np.errstate(invalid="ignore"):
         cand = np.flatnonzero(m >= thr)
+    if G == 0:                      # no neighbours to beat: every candidate wins (the dense streams have thousands)
+        return cand.astype(np.int64)
     for k in cand:
         if k - G < 0 or k + G >= m.size:
             continue
@@ -84,8 +87,22 @@ def ref_correct(records, cfo):
 # ---------------------------------------------------------------- the f32 model of the chosen order
 
 
-def _fma(a, b, c):
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+def fma32(a, b, c):
+    """fma(a, b, c) of f32 arrays, rounded once.  The product of two f32 values is exact in f64; its f64 sum with c is rounded to
+    53 bits, and rounding that to f32 is a second rounding that differs from the single one exactly where the f64 sum lands on
+    the midpoint of two f32 values without being it: there the sum is moved one f64 step towards what it lost."""
+    p, c = a.astype(np.float64) * b.astype(np.float64), c.astype(np.float64)
+    t = p + c
+    tie = (t.view(np.int64) & 0x1FFFFFFF) == 0x10000000
+    if np.any(tie):
+        p, c, s = np.broadcast_to(p, t.shape)[tie], np.broadcast_to(c, t.shape)[tie], t[tie]
+        v = s - p
+        lost = (p - (s - v)) + (c - v)                       # the exact sum minus its rounded value (Knuth's two-sum)
+        t[tie] = np.where(lost == 0, s, np.nextafter(s, np.where(lost > 0, np.inf, -np.inf)))
+    return t.astype(np.float32)
+
+
+_fma = fma32
 
 
 def model_metric(x, L, W, d_lo, d_hi):
@@ -265,10 +282,100 @@ def correct_distance(got, want, x):
 # Four times the worst distance of model_metric from ref_metric over cases() and seam_stream() -- of P and R relative to R, of
 # m absolutely (the OFDM tests' rule for CHANNEL_BOUND).  tests/test_ofdmsync_ref.py measures it and holds the constant to it.
 METRIC_MODEL_WORST = 6.68e-7           # sym1280; half32 5.41e-7, sym80 4.45e-7, link 4.94e-7, prefix64 4.46e-7, seams 3.06e-7, odd7 2.12e-7
+#                                        (the dense streams below stay inside it at every position: at most 5.69e-7, (2048, 2048))
 METRIC_BOUND = 4 * METRIC_MODEL_WORST
 # Four times the worst correct_distance of model_correct from ref_correct over CORRECT_SHAPES.
 CORRECT_MODEL_WORST = 4.09e-7          # 257 records of 1280; a record of 2^20 samples 3.52e-7
 CORRECT_BOUND = 4 * CORRECT_MODEL_WORST
+
+# ---------------------------------------------------------------- dense streams (tests/test_gpu_dense_metrics.py)
+# With G = 0 the peak rule is "m >= thr": under a tiny threshold every position with a metric above 0 is a detection, and the
+# kernel's sums show at every position.  The streams hold noise everywhere, so no window has R == 0 before the stream's end.
+DENSE_N = 2 * TILE + 77                # positions whose whole reach W + L lies in the stream: two tiles and a ragged third
+DENSE_THR = 1e-30
+DENSE_SIGMA = 0.15                     # per component, against planted repetitions of power 1: their metric is near 0.9
+DENSE_SHAPES = ((1, 2), (7, 13), (33, 31), (32, 32), (31, 33), (64, 65), (80, 80), (2048, 2048))     # (L, W)
+DENSE_GUARD = 512                      # the large-guard layout of the residue runs
+DENSE_RESIDUE_SHAPES = ((31, 33), (80, 80))
+DENSE_LEAD = 4096                      # the residue runs start at position DENSE_LEAD + r, r = 0 .. 31
+DENSE_FAR_SHAPES = ((7, 13), (31, 33), (2048, 2048))                 # run again at positions past 2^32
+FAR_BASE, FAR_RESIDUES = 8192, (0, 1, 31)
+FAR_SHIFTS = ((1 << 32) - 12288, 1 << 40, (1 << 62) - (1 << 20))     # multiples of 32; base + the first lies below 2^32
+BRANCHES = ("direct", "ke0", "ke0+1")
+
+
+@functools.lru_cache(maxsize=None)
+def dense_stream(L, W):
+    """DENSE_N + W + L - 1 samples of noise with a repetition of period L (W + L samples of power 1, turned by 0.3 pi / L per
+    sample) added at 300 and 200 before the last full reach: positions 0 .. DENSE_N - 1 have their whole reach in the stream."""
+    n = DENSE_N + W + L - 1
+    rng = np.random.default_rng(7000 + 31 * L + W)
+    x = DENSE_SIGMA * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    u = (rng.standard_normal(L) + 1j * rng.standard_normal(L)) / np.sqrt(2)
+    i = np.arange(W + L)
+    seg = u[i % L] * np.exp(1j * (0.3 * np.pi / L) * i)
+    for at in (300, n - (W + L) - 200):
+        x[at: at + W + L] += seg
+    x = x.astype(np.complex64)
+    x.setflags(write=False)
+    return x
+
+
+def behind_zeros(x, lead):
+    """The stream a node sees that starts at position `lead` with zero state."""
+    return np.concatenate([np.zeros(lead, np.complex64), x])
+
+
+def dense_expected(x, L, W, G=0, lead=0, metric=model_metric):
+    """The records of x behind `lead` zeros under DENSE_THR, in the kernel's order of operations (or the definition's)."""
+    return ref_detect(behind_zeros(x, lead), L, W, G, 0, DENSE_THR, metric=metric)
+
+
+@functools.lru_cache(maxsize=None)
+def dense_model(L, W):
+    """(P, R, m) of model_metric at the positions 0 .. len of dense_stream(L, W): position d at element d."""
+    out = model_metric(dense_stream(L, W), L, W, 0, dense_stream(L, W).size + 1)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def branch_of(d, W):
+    """(lane column, branch) of the absolute positions d in ofdmsync_detect_kernel: a lane holds the eight positions from
+    idx0 = d - d % 8, all in block kd; ke0 is the block of the first one's end.  0 direct (the window lies in one block),
+    1 joined with the mid of [kd + 1, ke0), 2 joined with that mid extended by block ke0."""
+    d = np.asarray(d, np.int64)
+    kd, ke, ke0 = d // BLK, (d + W - 1) // BLK, (d - d % RUN + W - 1) // BLK
+    return d % RUN, np.where(ke == kd, 0, np.where(ke == ke0, 1, 2))
+
+
+def branch_classes(W):
+    """Every (column, branch) that window W can produce: the pattern repeats with the block."""
+    c, b = branch_of(np.arange(BLK), W)
+    return sorted(set(zip(c.tolist(), b.tolist())))
+
+
+def class_picks(L, W):
+    """{(column, branch): d}: per class a position of dense_stream(L, W) whose whole reach lies in the stream and whose model
+    metric lies between the 20th and the 80th percentile, so that a threshold of exactly m[d] splits thousands of positions on
+    either side.  Class i of n takes the first such position at or behind i DENSE_N / (n + 1): they spread over the tiles."""
+    m = dense_model(L, W)[2][:DENSE_N]
+    lo, hi = np.percentile(m, [20, 80])
+    d = np.flatnonzero((m >= lo) & (m <= hi))
+    c, b = branch_of(d, W)
+    classes = branch_classes(W)
+    out = {}
+    for i, (ci, bi) in enumerate(classes):
+        hit = d[(c == ci) & (b == bi) & (d >= i * DENSE_N // (len(classes) + 1))]
+        if hit.size:
+            out[(ci, bi)] = int(hit[0])
+    return out
+
+
+def nan_reach(at, L, W):
+    """The positions whose P or R holds sample `at`."""
+    return np.unique(np.concatenate([np.arange(at - W + 1, at + 1), np.arange(at - L - W + 1, at - L + 1)]))
+
 
 # ---------------------------------------------------------------- the link of check 8
 LINK_FRAMES = 12

@@ -102,6 +102,47 @@ def test_expected_detections_of_the_special_streams():
     assert {7, (fr.GRID_CAP // 2) * fr.TILE + fr.TILE - 5, fr.N_BIG - 20} <= set(big) and len(big) == 23
 
 
+# ------------------------------------------------------------------ the dense streams (tests/test_gpu_dense_metrics.py)
+def test_dense_streams_model_distance_and_every_position_a_detection():
+    """At every position of the dense streams the model's metric stays within MODEL_METRIC_DISTANCE and its correlation within
+    MODEL_CORR_DISTANCE of the definition; the energy of 512 taps does not (DENSE_CORR_DISTANCE records it).  And what the dense
+    GPU test rests on: no e is 0, every metric of the model and of the definition exceeds 1e-12, both report every position."""
+    worst = 0.0
+    for wn in fr.DENSE_WORDS:
+        y, p = fr.dense_stream(wn), fr.words()[wn]
+        assert y.size == fr.DENSE_N + p.size - 1
+        k, c, m, e, _ = fr.ref_detect(y, p, fr.DENSE_THR, 0)
+        km, cm, mm, em, _ = fr.dense_detect(wn, fr.DENSE_THR)
+        assert np.array_equal(k, np.arange(y.size)) and np.array_equal(km, k), wn
+        Ep = float(np.sum(np.abs(p.astype(np.complex128)) ** 2))
+        dm, dc, de = np.max(np.abs(mm - m)), np.max(np.abs(cm - c) / np.sqrt(Ep * e)), np.max(np.abs(em - e) / e)
+        print("dense %-8s %d positions: metric off by %.3e, corr by %.3e, energy by %.3e; metrics %.3e ... %.3f" % (wn, y.size, dm, dc, de, mm.min(), mm.max()))
+        assert dm <= fr.MODEL_METRIC_DISTANCE and dc <= fr.MODEL_CORR_DISTANCE and de <= fr.DENSE_CORR_DISTANCE, wn
+        assert min(e.min(), em.min()) > 0 and min(m.min(), mm.min()) > 1e-12 and mm.max() > 0.9, wn
+        worst = max(worst, dc, de)
+    assert worst <= fr.DENSE_CORR_DISTANCE <= 1.05 * worst
+
+
+def test_dense_picks_cover_every_lane_column_of_both_passes():
+    for wn in fr.DENSE_WORDS:
+        P, T = fr.words()[wn].size, fr.dense_stream(wn).size
+        m = fr.dense_sums(wn)[3][: fr.DENSE_N]
+        lo, hi = np.percentile(m, [20, 80])
+        first = fr.first_pass_picks(wn)
+        assert sorted(first) == list(range(8)) and len({k // fr.TILE for k in first.values()}) >= 2, wn
+        for col, k in first.items():
+            r = (k - (1 - P)) % fr.TILE                   # a single call's first decided position is -(P + 0) + 1
+            assert r % 8 == col and lo <= m[k] <= hi and min(np.sum(m >= m[k]), np.sum(m < m[k])) >= 800, (wn, col)
+        G = fr.LATE_GUARD
+        late = fr.late_pass_picks(wn)
+        peaks = set(fr.dense_detect(wn, fr.DENSE_THR, G)[0].tolist())
+        assert sorted(late) == list(range(8)) and len({k for k, _ in late.values()}) == 8, wn
+        for col, (k, n1) in late.items():
+            r = k - (n1 - (P + G) + 1)                    # counted from the second call's first decided position
+            assert k in peaks and 0 <= n1 and r < min(fr.TILE, T - n1), (wn, col)
+            assert fr.PASS <= r + G < fr.TILE + 2 * G and (r + G) % 8 == col, (wn, col)     # metric r + G: second pass, that column
+
+
 # ------------------------------------------------------------------ part 3
 def test_cut_and_flushed_equals_uncut():
     rng = np.random.default_rng(5)

@@ -149,6 +149,76 @@ def test_model_detections_equal_the_references():
         assert np.array_equal(a["index"], b["index"]), name
 
 
+# ---------------------------------------------------------------- the dense streams (tests/test_gpu_dense_metrics.py)
+@pytest.mark.parametrize("L,W", o.DENSE_SHAPES)
+def test_dense_stream_model_distance_and_every_position_a_detection(L, W):
+    """At every position of a dense stream the model stays within METRIC_MODEL_WORST of the definition; and what the dense GPU
+    test rests on: no R is 0 inside the stream, every metric that has a product inside the stream exceeds 1e-12 in the model and
+    in the definition, and both report exactly those positions under DENSE_THR."""
+    x = o.dense_stream(L, W)
+    n = x.size
+    assert n == o.DENSE_N + W + L - 1
+    P, R, m = o.ref_metric(x, L, W, 0, n + 1)
+    Pm, Rm, mm = o.dense_model(L, W)
+    assert not np.any(R[:n] == 0) and not np.any(Rm[:n] == 0) and R[n] == 0 and Rm[n] == 0
+    dist = max(float(np.max(np.abs(Pm[:n] - P[:n]) / R[:n])), float(np.max(np.abs(Rm[:n] - R[:n]) / R[:n])), float(np.max(np.abs(mm - m))))
+    low = min(float(m[: n - L].min()), float(mm[: n - L].min()))
+    print("dense (%d, %d): model_metric is %.3e from ref_metric over %d positions; metrics %.3e ... %.3f" % (L, W, dist, n, low, mm.max()))
+    assert dist <= o.METRIC_MODEL_WORST
+    assert low > 1e-12 and mm.max() > 0.75 and not np.any(m[n - L:]) and not np.any(mm[n - L:])
+    a, b = o.dense_expected(x, L, W), o.dense_expected(x, L, W, metric=o.ref_metric)
+    assert np.array_equal(a["index"], np.arange(n - L)) and np.array_equal(b["index"], a["index"])
+    assert np.array_equal(a["m"].astype(np.float32), mm[: n - L])                                     # the records ARE the model's values
+
+
+def test_dense_picks_hit_every_class_the_kernel_distinguishes():
+    assert o.branch_classes(33) == [(c, 1) for c in range(8)]                # a window of 33 always ends in the next block
+    assert {(c, 0) for c in range(8)} <= set(o.branch_classes(13))           # one of 13 may lie inside a block, at every column
+    seen = set()
+    for L, W in o.DENSE_SHAPES[1:-1]:
+        picks, m = o.class_picks(L, W), o.dense_model(L, W)[2][: o.DENSE_N]
+        assert sorted(picks) == o.branch_classes(W), (L, W)
+        lo, hi = np.percentile(m, [20, 80])
+        for (col, branch), d in picks.items():
+            # the kernel's own arithmetic on the lane's first element idx0 (the image starts on a multiple of 32)
+            idx0 = d - d % 8
+            kd, ke0, ke = idx0 >> 5, (idx0 + W - 1) >> 5, (d + W - 1) >> 5
+            assert d % 8 == col and branch == (0 if ke == kd else 1 if ke == ke0 else 2) and ke in (kd, ke0, ke0 + 1)
+            assert 0 <= d < o.DENSE_N and lo <= m[d] <= hi
+            assert min(np.sum(m >= m[d]), np.sum(m < m[d])) >= 800          # thousands of positions around the threshold
+        seen |= {b for _, b in picks}
+        assert len({d // o.TILE for d in picks.values()}) >= 2               # spread over the tiles
+    assert seen == {0, 1, 2}
+
+
+@pytest.mark.parametrize("L,W", o.DENSE_RESIDUE_SHAPES)
+def test_dense_largest_guard_model_and_definition_agree(L, W):
+    x = o.dense_stream(L, W)
+    for r in (0, 1, 31):
+        a = o.dense_expected(x, L, W, G=o.DENSE_GUARD, lead=o.DENSE_LEAD + r)
+        b = o.dense_expected(x, L, W, G=o.DENSE_GUARD, lead=o.DENSE_LEAD + r, metric=o.ref_metric)
+        assert a.size >= 3 and np.array_equal(a["index"], b["index"]), (L, W, r)
+
+def test_dense_far_positions_keep_the_block_alignment():
+    assert all(K % o.BLK == 0 and o.FAR_BASE + 31 + K + o.dense_stream(2048, 2048).size <= 1 << 62 for K in o.FAR_SHIFTS)
+    assert all(s in o.DENSE_SHAPES for s in o.DENSE_RESIDUE_SHAPES + o.DENSE_FAR_SHAPES)
+
+
+def test_fma32_rounds_once():
+    """(1 + 2^-23)(1 - 2^-23) + (255 + 3 2^-16) = M - 2^-46 with M = 256 + 3 2^-16, the midpoint of the f32 neighbours
+    256 + 2^-15 and 256 + 2^-14.  In f64 (steps of 2^-44 there) the sum rounds to M, and M rounds to the even neighbour
+    256 + 2^-14; the single rounding of an FMA gives 256 + 2^-15."""
+    f32 = np.float32
+    a, b, c = np.full(3, 1 + 2.0 ** -23, f32), np.full(3, 1 - 2.0 ** -23, f32), np.full(3, 255 + 3 * 2.0 ** -16, f32)
+    assert float(a[0]) * float(b[0]) + float(c[0]) == 256 + 3 * 2.0 ** -16                  # what f64 makes of it
+    assert np.all(o.fma32(a, b, c) == f32(256 + 2.0 ** -15)) and np.all(o.fma32(-a, b, -c) == -f32(256 + 2.0 ** -15))
+    one = np.ones(3, f32)
+    assert np.all(o.fma32(one, one, c) ==f32(256 + 2.0 ** -14))                        # the tie itself goes to even
+    assert np.all(o.fma32(a, a, c) == f32(256 + 2.0 ** -14))                                  # M + 2^-22 + 2^-46: up
+    import framesync_ref as fr
+    assert np.all(fr._fma(a, b, c) == f32(256 + 2.0 ** -15))                                  # (a, b, acc): the same function
+
+
 # ---------------------------------------------------------------- the link
 def test_link_decodes_in_the_reference_chain_and_not_without_the_correction():
     f = o.link_format()
