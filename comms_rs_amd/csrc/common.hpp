@@ -862,6 +862,36 @@ inline unsigned resident_workgroups(size_t lds) {
 // The grid of a persistent launch with `blocks` workgroups' worth of work: at least one, at most the handle's cap
 inline size_t capped_grid(size_t blocks, unsigned max_grid) { return blocks < 1 ? 1 : blocks < max_grid ? blocks : max_grid; }
 
+// ---- 16-byte output stores of the streaming kernels: plain, or written through the L2 ----------------------------------
+// A plain store leaves its line dirty in the XCD's L2; what is still dirty when the kernel ends is written back behind its
+// last wave, in front of the next kernel of the stream.  An `sc1` store writes through and drops the line, so the bytes
+// leave while the kernel is still streaming -- at 16 bytes per lane at the price of a plain store (narrower ones pay per
+// byte: the 8-byte kernels keep plain stores).  WT = false is the plain twin: both forms of a kernel come from one body.
+// `p` is 16-byte aligned.  (A vector store; the string ends in `s_nop 1`: the compiler's next instruction must not
+// overwrite the data registers before the store has read them.)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+template <bool WT>
+__device__ __forceinline__ void store16(void* p, uint4 v) {
+    if constexpr (WT) {
+        const u32x4 d = {v.x, v.y, v.z, v.w};
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(d) : "memory");
+    } else {
+        *static_cast<uint4*>(p) = v;
+    }
+}
+template <bool WT>
+__device__ __forceinline__ void store16(void* p, float4 v) {
+    store16<WT>(p, make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)));
+}
+// Which form a call takes is decided here, for the mixer and the decimator alike: write-through only when the call's output
+// exceeds the chip's L2 (8 XCDs x 4 MiB) -- a smaller output is better left there for the next kernel's first reads.
+// COMMS_WT_MIN_BYTES (the diagnostic build, read once) moves the threshold: 0 = every call that can (tests/test_gpu_store_forms.py).
+constexpr size_t kWriteThroughMinBytes = 32u << 20;
+inline bool write_through(size_t out_bytes) {
+    static const size_t min_bytes = static_cast<size_t>(diag_knob("COMMS_WT_MIN_BYTES", static_cast<int>(kWriteThroughMinBytes)));
+    return out_bytes > min_bytes;
+}
+
 // Mixer phase bookkeeping shared by the mixer node and the fused chain: phases are
 // 64-bit fixed-point fractions ("turns") of T = fl(2*pi), the constant the reference
 // wraps with (src/mixer.rs:79-82).

@@ -593,6 +593,8 @@ __global__ void probe_swap_semantics_kernel(unsigned* out) {
     out[192 + threadIdx.x] = q[1];
 }
 }  // namespace comms
+// the store form a mixer or decimator call with `out_bytes` of output takes under this process's COMMS_WT_MIN_BYTES: 1 = write-through
+extern "C" int32_t comms_debug_store_form(size_t out_bytes) { return comms::write_through(out_bytes) ? 1 : 0; }
 extern "C" comms_status_t comms_debug_swap_semantics(unsigned* d_out, void* stream) {
     comms::probe_swap_semantics_kernel<<<dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream)>>>(d_out);
     return comms::launch_ok("probe_swap_semantics");

@@ -29,11 +29,16 @@ __device__ inline void rot_step(double& c, double& s, double sc, double ss) {
 }
 
 // VEC = samples per thread per sweep (2 -> float4 accesses, needs 16-B alignment)
-template <int VEC>
+// WT (VEC == 2 only): the float4 stores write through the L2 (common.hpp: store16); no lane re-reads an output line, in
+// place or not, so dropping the line costs nothing.  The odd tail is one sample: a plain store.
+// ks: in-kernel begin / end stamps of the launch (common.hpp; a null KStamp costs a scalar compare at either end).
+template <int VEC, bool WT>
 __global__ __launch_bounds__(256) void mixer_kernel(const float2* __restrict__ in,
                                                     float2* __restrict__ out, size_t n,
                                                     uint64_t turns0, uint64_t frac, double sweep_c,
-                                                    double sweep_s, double d_c, double d_s) {
+                                                    double sweep_s, double d_c, double d_s, KStamp ks) {
+    static_assert(VEC == 2 || !WT, "write-through stores are 16 bytes wide");
+    kstamp_begin(ks);
     const size_t nthreads = static_cast<size_t>(gridDim.x) * blockDim.x;
     const size_t gid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const size_t ngroups = n / VEC;
@@ -47,7 +52,7 @@ __global__ __launch_bounds__(256) void mixer_kernel(const float2* __restrict__ i
                 float4 x = reinterpret_cast<const float4*>(in)[g];
                 float2 a = mix_one(make_float2(x.x, x.y), c0, s0);
                 float2 b = mix_one(make_float2(x.z, x.w), c1, s1);
-                reinterpret_cast<float4*>(out)[g] = make_float4(a.x, a.y, b.x, b.y);
+                store16<WT>(reinterpret_cast<float4*>(out) + g, make_float4(a.x, a.y, b.x, b.y));
                 rot_step(c1, s1, sweep_c, sweep_s);
             } else {
                 out[g] = mix_one(in[g], c0, s0);
@@ -61,6 +66,7 @@ __global__ __launch_bounds__(256) void mixer_kernel(const float2* __restrict__ i
         mix_rotor_at(turns0 + static_cast<uint64_t>(n - 1) * frac, c, s);
         out[n - 1] = mix_one(in[n - 1], c, s);
     }
+    kstamp_end(ks);
 }
 
 // Mixer::mix::<f64> -- the instantiation the reference's own mixer tests use (src/mixer.rs:160-246, :250-336):
@@ -107,6 +113,22 @@ __global__ __launch_bounds__(256) void decimate_kernel(const V* __restrict__ in,
     for (size_t j = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < n_out;
          j += stride)
         out[j] = in[j * rate];
+}
+
+// The same for 8-byte elements, 16 output bytes per lane: a lane copies outputs 2j and 2j + 1 (two 8-byte loads in flight,
+// one 16-byte store; WT: written through the L2, common.hpp: store16).  `out` is 16-byte aligned.  The last input read is
+// in[(n_out - 1) * rate], as in the kernel above; an odd n_out leaves its last output to one lane's plain 8-byte store.
+template <bool WT>
+__global__ __launch_bounds__(256) void decimate_kernel16(const uint2* __restrict__ in, uint2* __restrict__ out, size_t n_out,
+                                                            size_t rate) {
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    const size_t gid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const size_t n_pairs = n_out / 2;
+    for (size_t j = gid; j < n_pairs; j += stride) {
+        const uint2 a = in[2 * j * rate], b = in[(2 * j + 1) * rate];
+        store16<WT>(out + 2 * j, make_uint4(a.x, a.y, b.x, b.y));
+    }
+    if (gid == 0 && (n_out & 1)) out[n_out - 1] = in[(n_out - 1) * rate];
 }
 
 template <typename V>
@@ -337,11 +359,18 @@ comms_status_t comms_mixer_run_dev(comms_mixer_t* h, const comms_c32* d_in, size
     host_rotor(h->frac, dc, ds);
     const float2* in = reinterpret_cast<const float2*>(d_in);
     float2* o = reinterpret_cast<float2*>(d_out);
+#ifdef COMMS_DIAG  // the gap measurement of profiles/store_forms_gaps.txt; in the product the mixer is a node without stamps
+    const KStamp ks = h->next_stamp();
+#else
+    const KStamp ks{nullptr, nullptr};
+#endif
     h->tic(s);
-    if (vec2)
-        mixer_kernel<2><<<dim3(blocks), dim3(256), 0, s>>>(in, o, n, h->turns, h->frac, sc, ss, dc, ds);
+    if (vec2 && write_through(n * sizeof(comms_c32)))
+        mixer_kernel<2, true><<<dim3(blocks), dim3(256), 0, s>>>(in, o, n, h->turns, h->frac, sc, ss, dc, ds, ks);
+    else if (vec2)
+        mixer_kernel<2, false><<<dim3(blocks), dim3(256), 0, s>>>(in, o, n, h->turns, h->frac, sc, ss, dc, ds, ks);
     else
-        mixer_kernel<1><<<dim3(blocks), dim3(256), 0, s>>>(in, o, n, h->turns, h->frac, sc, ss, dc, ds);
+        mixer_kernel<1, false><<<dim3(blocks), dim3(256), 0, s>>>(in, o, n, h->turns, h->frac, sc, ss, dc, ds, ks);
     h->toc(s);
     COMMS_TRY(launch_ok("mixer_kernel"));
     h->turns += static_cast<uint64_t>(n) * h->frac;
@@ -474,6 +503,16 @@ comms_status_t comms_decimate_run_dev(const void* d_in, size_t n, size_t elem, s
         return COMMS_OK;
     }
     COMMS_ARG(!ranges_overlap(d_in, n * elem, d_out, n_out * elem), "decimate cannot run in place");
+    if (elem == 8 && aligned(d_out, 16)) {  // 16 output bytes per lane (rate >= 2 here)
+        unsigned blocks = grid_for(n_out / 2, 256, 8 * kNumCU);
+        const uint2* in = static_cast<const uint2*>(d_in);
+        uint2* o = static_cast<uint2*>(d_out);
+        if (write_through(n_out * elem))
+            decimate_kernel16<true><<<dim3(blocks), dim3(256), 0, s>>>(in, o, n_out, rate);
+        else
+            decimate_kernel16<false><<<dim3(blocks), dim3(256), 0, s>>>(in, o, n_out, rate);
+        return launch_ok("decimate_kernel16");
+    }
     unsigned blocks = grid_for(n_out, 256, 8 * kNumCU);
     COMMS_RESAMPLE_DISPATCH(decimate_kernel, elem, n_out, rate)
     return launch_ok("decimate_kernel");
