@@ -40,6 +40,7 @@
 
 #include "common.hpp"
 #include "fft_radix.hpp"
+#include "stream_call.hpp"
 
 namespace comms {
 
@@ -501,23 +502,11 @@ comms_status_t comms_channelizer_run(comms_channelizer_t* h, const comms_c32* in
 }
 
 comms_status_t comms_channelizer_get_state(comms_channelizer_t* h, comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state <= h->H, "n_state %zu exceeds the %zu samples of the state", n_state, h->H);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());  // the history is advanced by the launches, on whatever stream they ran
-    COMMS_HIP_TRY(h->hist.download(state, n_state));
-    return COMMS_OK;
+    return get_history_state(h, state, n_state, "samples");
 }
 
 comms_status_t comms_channelizer_set_state(comms_channelizer_t* h, const comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state == h->H, "state must hold exactly the %zu samples of the state", h->H);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());  // no pending launch may still read the buffer that is overwritten
-    COMMS_HIP_TRY(h->hist.upload(state, n_state));
-    return COMMS_OK;
+    return set_history_state(h, state, n_state, "samples");
 }
 
 comms_status_t comms_channelizer_get_phase(comms_channelizer_t* h, uint64_t* out_phase) {

@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "fir_handle.hpp"
+#include "stream_call.hpp"
 
 namespace comms {
 
@@ -361,17 +362,8 @@ comms_status_t comms_deframe_run(comms_deframe_t* h, const comms_c32* in, size_t
     COMMS_ARG(ready <= cap_frames, "%zu frames become complete in this call, more than cap_frames = %zu", ready, cap_frames);
     COMMS_ARG(out != nullptr || !ready, "out is NULL");
     COMMS_TRY(use_device(h->device));
-    // input: short blocks are read straight from pinned host memory, long ones uploaded (as comms_framesync_run)
     const void* d = nullptr;
-    if (n && n * 8 <= zero_copy_limit()) {
-        COMMS_TRY(h->pin_in.reserve(n * 8));
-        std::memcpy(h->pin_in.h, in, n * 8);
-        d = h->pin_in.d;
-    } else if (n) {
-        COMMS_TRY(h->in_scratch.reserve(n * 8));
-        COMMS_HIP_TRY(hipMemcpyAsync(h->in_scratch.p, in, n * 8, hipMemcpyHostToDevice, h->stream));
-        d = h->in_scratch.p;
-    }
+    if (n) COMMS_TRY(stage_input(h, in, n * 8, &d));
     const size_t bytes = ready * frame_bytes_of(h);
     COMMS_TRY(h->out_scratch.reserve(bytes ? bytes : 8));
     COMMS_TRY(deframe_step(h, static_cast<const comms_c32*>(d), n, dets, n_dets, h->out_scratch.p, cap_frames, headers, n_frames,
@@ -391,38 +383,17 @@ comms_status_t comms_deframe_flush(comms_deframe_t* h, size_t* n_dropped) {
 }
 
 comms_status_t comms_deframe_get_state(comms_deframe_t* h, comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state <= static_cast<size_t>(h->H), "n_state %zu exceeds the %d symbols of the state", n_state, h->H);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());
-    if (!n_state) return COMMS_OK;
-    COMMS_HIP_TRY(h->hist.download(state, n_state));
-    return COMMS_OK;
+    return get_history_state(h, state, n_state, "symbols");
 }
 
 comms_status_t comms_deframe_set_state(comms_deframe_t* h, const comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state == static_cast<size_t>(h->H), "n_state must be exactly the %d symbols of the state (got %zu)", h->H, n_state);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(h->hist.upload(state, n_state));
-    return COMMS_OK;
+    return set_history_state(h, state, n_state, "symbols");
 }
 
-comms_status_t comms_deframe_get_position(const comms_deframe_t* h, uint64_t* out_position) {
-    COMMS_ARG(h && out_position, "NULL argument");
-    *out_position = h->T;
-    return COMMS_OK;
-}
+comms_status_t comms_deframe_get_position(const comms_deframe_t* h, uint64_t* out_position) { return get_position(h, out_position); }
 
 comms_status_t comms_deframe_set_position(comms_deframe_t* h, uint64_t position) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(position <= (1ull << 62), "position is out of range");
-    h->T = position;
-    h->pending.clear();
-    return COMMS_OK;
+    return set_position(h, position, [&] { h->pending.clear(); });
 }
 
 comms_status_t comms_deframe_get_pending(const comms_deframe_t* h, comms_deframe_header_t* out, size_t cap, size_t* n_pending) {

@@ -15,6 +15,7 @@
 
 #include "common.hpp"
 #include "zpow.hpp"
+#include "stream_call.hpp"
 
 namespace comms {
 
@@ -122,17 +123,8 @@ static comms_status_t estimate_host(int kind, const double* x, size_t n, unsigne
     Handle* h = nullptr;
     COMMS_TRY(thread_handle(device, &h));
     if (!n) return estimate(kind, nullptr, 0, m, out, device, h->stream);
-    // input only: short blocks are read straight from pinned host memory, long ones uploaded
     const void* d = nullptr;
-    if (n * 16 <= zero_copy_limit()) {
-        COMMS_TRY(h->pin_in.reserve(n * 16));
-        std::memcpy(h->pin_in.h, x, n * 16);
-        d = h->pin_in.d;
-    } else {
-        COMMS_TRY(h->in_scratch.reserve(n * 16));
-        COMMS_HIP_TRY(hipMemcpyAsync(h->in_scratch.p, x, n * 16, hipMemcpyHostToDevice, h->stream));
-        d = h->in_scratch.p;
-    }
+    COMMS_TRY(stage_input(h, x, n * 16, &d));
     return estimate(kind, static_cast<const double*>(d), n, m, out, device, h->stream);
 }
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "stream_call.hpp"
 
 namespace comms {
 
@@ -209,24 +210,17 @@ comms_status_t run_host(ExactFir<V>* h, const CxOf<V>* in, size_t n, CxOf<V>* ou
     });
 }
 
+// (both refuse a NULL state outright: the shared rule would take one with an empty read)
 template <class V>
 comms_status_t get_state(ExactFir<V>* h, CxOf<V>* state, size_t n_state) {
     COMMS_ARG(h && state, "NULL argument");
-    COMMS_ARG(n_state <= static_cast<size_t>(h->hist_len), "n_state %zu exceeds the %d effective taps", n_state, h->hist_len);
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(h->hist.download(state, n_state));
-    return COMMS_OK;
+    return get_history_state(h, state, n_state, "samples");
 }
 
 template <class V>
 comms_status_t set_state(ExactFir<V>* h, const CxOf<V>* state, size_t n_state) {
     COMMS_ARG(h && state, "NULL argument");
-    COMMS_ARG(n_state == static_cast<size_t>(h->hist_len), "state must hold exactly the %d effective taps", h->hist_len);
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());  // no pending launch may still read the buffer that is overwritten
-    COMMS_HIP_TRY(h->hist.upload(state, n_state));
-    return COMMS_OK;
+    return set_history_state(h, state, n_state, "samples");
 }
 
 }  // namespace

@@ -27,13 +27,13 @@
 //     list is sized to that bound before the launch and cannot overflow.  The host copies the count and the entries back and
 //     sorts them by index: the order of arrival does not show.
 //   * workgroup 0 writes the new history to the other half of the ping-pong pair (History, common.hpp).
-#include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "common.hpp"
 #include "fir_handle.hpp"
 #include "sgpr_mac.hpp"
+#include "stream_call.hpp"
 
 namespace comms {
 
@@ -43,7 +43,6 @@ constexpr int FS_PASS = FS_WG * FS_OPL;     // metrics per pass of the workgroup
 constexpr int FS_TILE = 2048;               // decided positions per tile
 constexpr int FS_SLACK = 16;                // image elements past the staged ones that the register window may load (unused values)
 constexpr size_t FS_MIN_WORD = 2, FS_MAX_WORD = 512, FS_MAX_GUARD = 512;
-constexpr size_t FS_FIRST = 16;             // detections copied back together with the count
 
 // LDS image: element e at e + (e >> 3), so that lanes eight elements (72 bytes) apart spread over all the banks
 __host__ __device__ __forceinline__ int fs_slot(int e) { return e + (e >> 3); }
@@ -210,75 +209,45 @@ comms_status_t check_word_guard(size_t n_word, size_t guard) {
     return COMMS_OK;
 }
 
-comms_status_t check_threshold(double thr) {
-    COMMS_ARG(thr > 0.0 && thr <= 1.0, "threshold must lie in (0, 1] (got %g)", thr);  // a NaN fails both
-    return COMMS_OK;
-}
+size_t framesync_tiles(size_t n) { return (n + FS_TILE - 1) / FS_TILE; }
+size_t framesync_grid(const comms_framesync* h, size_t n) { return tile_grid(framesync_tiles(n), h->max_grid); }
 
-size_t framesync_grid(const comms_framesync* h, size_t n) {
-    const size_t tiles = (n + FS_TILE - 1) / FS_TILE;
-    return tiles < h->max_grid ? tiles : h->max_grid;
-}
-
-// One launch on n symbols at d_in, the copy-back and the sort; history and position advance.  Ends synchronised.
+// One launch on n symbols at d_in and its detections (detection_step); history and position advance.  Ends synchronised.
 comms_status_t framesync_step(comms_framesync* h, const comms_c32* d_in, size_t n, comms_frame_detection_t* out, size_t cap,
                               size_t* n_found, void* stream) {
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
-    const size_t step = static_cast<size_t>(h->G) + 1;
-    const size_t bound = n / step + (n % step ? 1 : 0);
-    COMMS_ARG(bound <= 0xFFFFFFFFull / sizeof(comms_frame_detection_t), "n is too long for one call");
-    COMMS_TRY(h->list.reserve(8 + bound * sizeof(comms_frame_detection_t)));
-    char* d_list = static_cast<char*>(h->list.p);
-    COMMS_HIP_TRY(hipMemsetAsync(d_list, 0, 8, s));
-    FsArgs a{};
-    a.in = reinterpret_cast<const float2*>(d_in);
-    a.hist = h->hist.cur<float2>();
-    a.new_hist = h->hist.next<float2>();
-    a.tre = h->d_taps.get();
-    a.tim = h->d_taps.get() + h->NP8;
-    a.n = n;
-    a.tiles = (n + FS_TILE - 1) / FS_TILE;
-    a.k_first = static_cast<long long>(h->T) - (h->P + h->G) + 1;
-    a.origin = h->origin;
-    a.P = h->P;
-    a.G = h->G;
-    a.H = h->H;
-    a.NM = h->NM;
-    a.NS = h->NS;
-    a.thr = h->thr;
-    a.Ep = h->Ep;
-    a.count = reinterpret_cast<unsigned*>(d_list);
-    a.list = reinterpret_cast<comms_frame_detection_t*>(d_list + 8);
-    a.list_cap = static_cast<unsigned>(bound);
-    h->tic(s);
-    framesync_kernel<<<dim3(static_cast<unsigned>(framesync_grid(h, n))), dim3(FS_WG), h->lds, s>>>(a);
-    h->toc(s);
-    COMMS_TRY(launch_ok("framesync_kernel"));
-    h->hist.flip();
-    h->T += n;
-    // the count and the first few entries in one copy; the rest, rarely, in a second
-    const size_t first = bound < FS_FIRST ? bound : FS_FIRST;
-    constexpr size_t kDet = sizeof(comms_frame_detection_t);
-    char head[8 + FS_FIRST * kDet];
-    hipError_t e = hipMemcpyAsync(head, d_list, 8 + first * kDet, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "frame synchroniser copy-back: %s", hipGetErrorString(e));
-    unsigned count = 0;
-    std::memcpy(&count, head, sizeof count);
-    if (count > bound) return fail(COMMS_ERR_DEVICE, "framesync_kernel reported %u detections, more than the bound %zu", count, bound);
-    std::vector<comms_frame_detection_t> det(count);
-    if (count) std::memcpy(det.data(), head + 8, (count < first ? count : first) * kDet);
-    if (count > first) {
-        e = hipMemcpyAsync(det.data() + first, d_list + 8 + first * kDet, (count - first) * kDet, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "frame synchroniser copy-back: %s", hipGetErrorString(e));
-    }
-    std::sort(det.begin(), det.end(), [](const comms_frame_detection_t& x, const comms_frame_detection_t& y) { return x.index < y.index; });
-    const size_t take = count < cap ? count : cap;
-    if (take) std::memcpy(out, det.data(), take * sizeof(comms_frame_detection_t));
-    *n_found = count;
-    return COMMS_OK;
+    auto launch = [&](unsigned* count, comms_frame_detection_t* list, unsigned list_cap) -> comms_status_t {
+        FsArgs a{};
+        a.in = reinterpret_cast<const float2*>(d_in);
+        a.hist = h->hist.cur<float2>();
+        a.new_hist = h->hist.next<float2>();
+        a.tre = h->d_taps.get();
+        a.tim = h->d_taps.get() + h->NP8;
+        a.n = n;
+        a.tiles = framesync_tiles(n);
+        a.k_first = static_cast<long long>(h->T) - (h->P + h->G) + 1;
+        a.origin = h->origin;
+        a.P = h->P;
+        a.G = h->G;
+        a.H = h->H;
+        a.NM = h->NM;
+        a.NS = h->NS;
+        a.thr = h->thr;
+        a.Ep = h->Ep;
+        a.count = count;
+        a.list = list;
+        a.list_cap = list_cap;
+        h->tic(s);
+        const comms_status_t st = launch_kernel<framesync_kernel>("framesync_kernel", dim3(static_cast<unsigned>(framesync_grid(h, n))),
+                                                                  dim3(FS_WG), h->lds, s, {}, a);
+        h->toc(s);
+        COMMS_TRY(st);
+        h->hist.flip();
+        h->T += n;
+        return COMMS_OK;
+    };
+    return detection_step(h->list, detection_bound(n, static_cast<size_t>(h->G)), s, "framesync_kernel", launch, out, cap, n_found);
 }
 
 }  // namespace
@@ -331,51 +300,27 @@ comms_status_t comms_framesync_create(const comms_c32* word, size_t n_word, doub
 
 comms_status_t comms_framesync_run_dev(comms_framesync_t* h, const comms_c32* d_in, size_t n, comms_frame_detection_t* out, size_t cap,
                                        size_t* n_found, void* stream) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_found != nullptr, "n_found is NULL");
-    COMMS_ARG(out != nullptr || !cap, "out is NULL with cap > 0");
-    COMMS_ARG(d_in || !n, "d_in is NULL");
-    COMMS_ARG((reinterpret_cast<uintptr_t>(d_in) & 7) == 0, "d_in must be aligned to one symbol (8 bytes)");
-    COMMS_ARG(n <= SIZE_MAX / 8, "n overflows");
-    *n_found = 0;
-    COMMS_TRY(use_device(h->device));
+    COMMS_TRY(detect_prologue(h, d_in, n, true, out, cap, n_found));
     if (!n) return COMMS_OK;
     return framesync_step(h, d_in, n, out, cap, n_found, stream);
 }
 
 comms_status_t comms_framesync_run(comms_framesync_t* h, const comms_c32* in, size_t n, comms_frame_detection_t* out, size_t cap,
                                    size_t* n_found) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_found != nullptr, "n_found is NULL");
-    COMMS_ARG(out != nullptr || !cap, "out is NULL with cap > 0");
-    COMMS_ARG(in || !n, "in is NULL");
-    COMMS_ARG(n <= SIZE_MAX / 8, "n overflows");
-    *n_found = 0;
-    COMMS_TRY(use_device(h->device));
+    COMMS_TRY(detect_prologue(h, in, n, false, out, cap, n_found));
     if (!n) return COMMS_OK;
-    // input only: short blocks are read straight from pinned host memory, long ones uploaded
     const void* d = nullptr;
-    if (n * 8 <= zero_copy_limit()) {
-        COMMS_TRY(h->pin_in.reserve(n * 8));
-        std::memcpy(h->pin_in.h, in, n * 8);
-        d = h->pin_in.d;
-    } else {
-        COMMS_TRY(h->in_scratch.reserve(n * 8));
-        COMMS_HIP_TRY(hipMemcpyAsync(h->in_scratch.p, in, n * 8, hipMemcpyHostToDevice, h->stream));
-        d = h->in_scratch.p;
-    }
+    COMMS_TRY(stage_input(h, in, n * 8, &d));
     return framesync_step(h, static_cast<const comms_c32*>(d), n, out, cap, n_found, COMMS_STREAM_HANDLE);
 }
 
 comms_status_t comms_framesync_flush(comms_framesync_t* h, comms_frame_detection_t* out, size_t cap, size_t* n_found) {
     COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_found != nullptr, "n_found is NULL");
-    COMMS_ARG(out != nullptr || !cap, "out is NULL with cap > 0");
-    *n_found = 0;
-    COMMS_TRY(use_device(h->device));
+    const comms_c32* zeros = reinterpret_cast<const comms_c32*>(h->d_zero.get());
+    const size_t n = static_cast<size_t>(h->P + h->G);
+    COMMS_TRY(detect_prologue(h, zeros, n, true, out, cap, n_found));
     const uint64_t T = h->T;
-    COMMS_TRY(framesync_step(h, reinterpret_cast<const comms_c32*>(h->d_zero.get()), static_cast<size_t>(h->P + h->G), out, cap, n_found,
-                             COMMS_STREAM_HANDLE));
+    COMMS_TRY(framesync_step(h, zeros, n, out, cap, n_found, COMMS_STREAM_HANDLE));
     h->T = T;
     h->origin = static_cast<long long>(T);
     COMMS_HIP_TRY(h->hist.upload(nullptr, 0));  // zeros (the step ended synchronised)
@@ -383,51 +328,26 @@ comms_status_t comms_framesync_flush(comms_framesync_t* h, comms_frame_detection
 }
 
 comms_status_t comms_framesync_get_state(comms_framesync_t* h, comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state <= static_cast<size_t>(h->H), "n_state %zu exceeds the %d symbols of the state", n_state, h->H);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());
-    if (!n_state) return COMMS_OK;
-    COMMS_HIP_TRY(h->hist.download(state, n_state));
-    return COMMS_OK;
+    return get_history_state(h, state, n_state, "symbols");
 }
 
+// (n_state must be H = P + 2 G - 1 >= 1: a NULL state never comes with a length the setter accepts)
 comms_status_t comms_framesync_set_state(comms_framesync_t* h, const comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state == static_cast<size_t>(h->H), "n_state must be exactly the %d symbols of the state (got %zu)", h->H, n_state);
-    COMMS_ARG(state != nullptr, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(h->hist.upload(state, n_state));
-    return COMMS_OK;
+    return set_history_state(h, state, n_state, "symbols");
 }
 
-comms_status_t comms_framesync_get_position(const comms_framesync_t* h, uint64_t* out_position) {
-    COMMS_ARG(h && out_position, "NULL argument");
-    *out_position = h->T;
-    return COMMS_OK;
-}
+comms_status_t comms_framesync_get_position(const comms_framesync_t* h, uint64_t* out_position) { return get_position(h, out_position); }
 
 comms_status_t comms_framesync_set_position(comms_framesync_t* h, uint64_t position) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(position <= (1ull << 62), "position is out of range");
-    h->T = position;
-    h->origin = 0;
-    return COMMS_OK;
+    return set_position(h, position, [&] { h->origin = 0; });
 }
 
-comms_status_t comms_framesync_set_threshold(comms_framesync_t* h, double threshold) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_TRY(check_threshold(threshold));
-    h->thr = static_cast<float>(threshold);
-    return COMMS_OK;
-}
+comms_status_t comms_framesync_set_threshold(comms_framesync_t* h, double threshold) { return set_threshold(h, threshold); }
 
 comms_status_t comms_framesync_get_kernel(const comms_framesync_t* h, size_t n, char* name, size_t name_len) {
     COMMS_ARG(h && name && name_len, "NULL argument");
     std::snprintf(name, name_len, "framesync_kernel tile=%d wg=%d word=%d guard=%d lds=%zu tiles=%zu grid=%zu max_grid=%u", FS_TILE, FS_WG,
-                  h->P, h->G, h->lds, (n + FS_TILE - 1) / FS_TILE, framesync_grid(h, n), h->max_grid);
+                  h->P, h->G, h->lds, framesync_tiles(n), framesync_grid(h, n), h->max_grid);
     return COMMS_OK;
 }
 

@@ -32,12 +32,12 @@
 // ofdmsync_correct_kernel: out[f][n] = in[f][n] exp(-i cfo[f] n) over the flattened (frame, eight samples) space.  A lane
 // takes the f64 anchor sincos(-(cfo n0)) at n0 = 8 j, rounds it to f32 and steps it by the frame's f32 rotor exp(-i cfo)
 // (formed in f64 on the host): 16-byte loads and stores where the record length is even.
-#include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "common.hpp"
 #include "fir_handle.hpp"
+#include "stream_call.hpp"
 
 namespace comms {
 
@@ -48,7 +48,6 @@ constexpr int OS_TILE = 2048;               // decided positions per tile
 constexpr int OS_BLK = 32;                  // absolute indices per block of prefix / suffix sums
 constexpr size_t OS_MAX_LAG = 2048, OS_MIN_WINDOW = 2, OS_MAX_WINDOW = 2048, OS_MAX_GUARD = 512, OS_MAX_ADVANCE = 2048;
 constexpr size_t OS_MAX_FRAME = size_t(1) << 20;
-constexpr size_t OS_FIRST = 16;             // detections copied back together with the count
 constexpr int OC_WG = 256;                  // lanes per workgroup of the correct kernel
 constexpr int OC_RUN = 8;                   // samples per lane and anchor
 
@@ -383,69 +382,43 @@ comms_status_t check_shape(size_t lag, size_t window, size_t guard) {
     return COMMS_OK;
 }
 
-comms_status_t check_threshold(double thr) {
-    COMMS_ARG(thr > 0.0 && thr <= 1.0, "threshold must lie in (0, 1] (got %g)", thr);  // a NaN fails both
-    return COMMS_OK;
-}
-
 size_t tiles_of(size_t n) { return (n + OS_TILE - 1) / OS_TILE; }
 
-// One launch on n samples at d_in, the copy-back and the sort; history and position advance.  Ends synchronised.
+// One launch on n samples at d_in and its detections (detection_step), then their CFO column; history and position advance.
+// Ends synchronised.
 comms_status_t detect_step(comms_ofdmsync* h, const comms_c32* d_in, size_t n, comms_frame_detection_t* out, double* cfo_out, size_t cap,
                            size_t* n_found, void* stream) {
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
-    const size_t step = static_cast<size_t>(h->G) + 1;
-    const size_t bound = n / step + (n % step ? 1 : 0);
-    COMMS_ARG(bound <= 0xFFFFFFFFull / sizeof(comms_frame_detection_t) && tiles_of(n) <= 0x7FFFFFFFull, "n is too long for one call");
-    COMMS_TRY(h->list.reserve(8 + bound * sizeof(comms_frame_detection_t)));
-    char* d_list = static_cast<char*>(h->list.p);
-    COMMS_HIP_TRY(hipMemsetAsync(d_list, 0, 8, s));
-    OsArgs a{};
-    a.in = reinterpret_cast<const float2*>(d_in);
-    a.hist = h->hist.cur<float2>();
-    a.new_hist = h->hist.next<float2>();
-    a.n = n;
-    a.d_first = static_cast<long long>(h->T) - (h->W + h->L + h->G) + 1;
-    a.d_min = h->origin + h->A;
-    a.L = h->L;
-    a.W = h->W;
-    a.G = h->G;
-    a.A = h->A;
-    a.H = h->H;
-    a.y = h->y;
-    a.thr = h->thr;
-    a.count = reinterpret_cast<unsigned*>(d_list);
-    a.list = reinterpret_cast<comms_frame_detection_t*>(d_list + 8);
-    a.list_cap = static_cast<unsigned>(bound);
-    COMMS_TRY(launch_kernel<ofdmsync_detect_kernel>("ofdmsync_detect_kernel", dim3(static_cast<unsigned>(tiles_of(n))), dim3(OS_WG), h->y.lds, s,
-                                                    h->take_events(), a));
-    h->hist.flip();
-    h->T += n;
-    // the count and the first few entries in one copy; the rest, rarely, in a second
-    const size_t first = bound < OS_FIRST ? bound : OS_FIRST;
-    constexpr size_t kDet = sizeof(comms_frame_detection_t);
-    char head[8 + OS_FIRST * kDet];
-    hipError_t e = hipMemcpyAsync(head, d_list, 8 + first * kDet, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "OFDM synchroniser copy-back: %s", hipGetErrorString(e));
-    unsigned count = 0;
-    std::memcpy(&count, head, sizeof count);
-    if (count > bound) return fail(COMMS_ERR_DEVICE, "ofdmsync_detect_kernel reported %u detections, more than the bound %zu", count, bound);
-    std::vector<comms_frame_detection_t> det(count);
-    if (count) std::memcpy(det.data(), head + 8, (count < first ? count : first) * kDet);
-    if (count > first) {
-        e = hipMemcpyAsync(det.data() + first, d_list + 8 + first * kDet, (count - first) * kDet, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(COMMS_ERR_DEVICE, "OFDM synchroniser copy-back: %s", hipGetErrorString(e));
-    }
-    std::sort(det.begin(), det.end(), [](const comms_frame_detection_t& x, const comms_frame_detection_t& y) { return x.index < y.index; });
-    const size_t take = count < cap ? count : cap;
-    if (take) std::memcpy(out, det.data(), take * sizeof(comms_frame_detection_t));
+    COMMS_ARG(tiles_of(n) <= 0x7FFFFFFFull, "n is too long for one call");
+    auto launch = [&](unsigned* count, comms_frame_detection_t* list, unsigned list_cap) -> comms_status_t {
+        OsArgs a{};
+        a.in = reinterpret_cast<const float2*>(d_in);
+        a.hist = h->hist.cur<float2>();
+        a.new_hist = h->hist.next<float2>();
+        a.n = n;
+        a.d_first = static_cast<long long>(h->T) - (h->W + h->L + h->G) + 1;
+        a.d_min = h->origin + h->A;
+        a.L = h->L;
+        a.W = h->W;
+        a.G = h->G;
+        a.A = h->A;
+        a.H = h->H;
+        a.y = h->y;
+        a.thr = h->thr;
+        a.count = count;
+        a.list = list;
+        a.list_cap = list_cap;
+        COMMS_TRY(launch_kernel<ofdmsync_detect_kernel>("ofdmsync_detect_kernel", dim3(static_cast<unsigned>(tiles_of(n))), dim3(OS_WG), h->y.lds,
+                                                        s, h->take_events(), a));
+        h->hist.flip();
+        h->T += n;
+        return COMMS_OK;
+    };
+    COMMS_TRY(detection_step(h->list, detection_bound(n, static_cast<size_t>(h->G)), s, "ofdmsync_detect_kernel", launch, out, cap, n_found));
     if (cfo_out)
-        for (size_t i = 0; i < take; ++i)
-            cfo_out[i] = std::atan2(static_cast<double>(det[i].corr_im), static_cast<double>(det[i].corr_re)) / static_cast<double>(h->L);
-    *n_found = count;
+        for (size_t i = 0; i < *n_found && i < cap; ++i)
+            cfo_out[i] = std::atan2(static_cast<double>(out[i].corr_im), static_cast<double>(out[i].corr_re)) / static_cast<double>(h->L);
     return COMMS_OK;
 }
 
@@ -492,51 +465,27 @@ comms_status_t comms_ofdmsync_create(size_t lag, size_t window, double threshold
 
 comms_status_t comms_ofdmsync_run_dev(comms_ofdmsync_t* h, const comms_c32* d_in, size_t n, comms_frame_detection_t* out, double* cfo_out,
                                       size_t cap, size_t* n_found, void* stream) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_found != nullptr, "n_found is NULL");
-    COMMS_ARG(out != nullptr || !cap, "out is NULL with cap > 0");
-    COMMS_ARG(d_in || !n, "d_in is NULL");
-    COMMS_ARG(aligned(d_in, 8), "d_in must be aligned to one sample (8 bytes)");
-    COMMS_ARG(n <= SIZE_MAX / 8, "n overflows");
-    *n_found = 0;
-    COMMS_TRY(use_device(h->device));
+    COMMS_TRY(detect_prologue(h, d_in, n, true, out, cap, n_found));
     if (!n) return COMMS_OK;
     return detect_step(h, d_in, n, out, cfo_out, cap, n_found, stream);
 }
 
 comms_status_t comms_ofdmsync_run(comms_ofdmsync_t* h, const comms_c32* in, size_t n, comms_frame_detection_t* out, double* cfo_out, size_t cap,
                                   size_t* n_found) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_found != nullptr, "n_found is NULL");
-    COMMS_ARG(out != nullptr || !cap, "out is NULL with cap > 0");
-    COMMS_ARG(in || !n, "in is NULL");
-    COMMS_ARG(n <= SIZE_MAX / 8, "n overflows");
-    *n_found = 0;
-    COMMS_TRY(use_device(h->device));
+    COMMS_TRY(detect_prologue(h, in, n, false, out, cap, n_found));
     if (!n) return COMMS_OK;
-    // input only: short blocks are read straight from pinned host memory, long ones uploaded (as comms_framesync_run)
     const void* d = nullptr;
-    if (n * 8 <= zero_copy_limit()) {
-        COMMS_TRY(h->pin_in.reserve(n * 8));
-        std::memcpy(h->pin_in.h, in, n * 8);
-        d = h->pin_in.d;
-    } else {
-        COMMS_TRY(h->in_scratch.reserve(n * 8));
-        COMMS_HIP_TRY(hipMemcpyAsync(h->in_scratch.p, in, n * 8, hipMemcpyHostToDevice, h->stream));
-        d = h->in_scratch.p;
-    }
+    COMMS_TRY(stage_input(h, in, n * 8, &d));
     return detect_step(h, static_cast<const comms_c32*>(d), n, out, cfo_out, cap, n_found, COMMS_STREAM_HANDLE);
 }
 
 comms_status_t comms_ofdmsync_flush(comms_ofdmsync_t* h, comms_frame_detection_t* out, double* cfo_out, size_t cap, size_t* n_found) {
     COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_found != nullptr, "n_found is NULL");
-    COMMS_ARG(out != nullptr || !cap, "out is NULL with cap > 0");
-    *n_found = 0;
-    COMMS_TRY(use_device(h->device));
+    const comms_c32* zeros = reinterpret_cast<const comms_c32*>(h->d_zero.get());
+    const size_t n = static_cast<size_t>(h->W + h->L + h->G);
+    COMMS_TRY(detect_prologue(h, zeros, n, true, out, cap, n_found));
     const uint64_t T = h->T;
-    COMMS_TRY(detect_step(h, reinterpret_cast<const comms_c32*>(h->d_zero.get()), static_cast<size_t>(h->W + h->L + h->G), out, cfo_out, cap,
-                          n_found, COMMS_STREAM_HANDLE));
+    COMMS_TRY(detect_step(h, zeros, n, out, cfo_out, cap, n_found, COMMS_STREAM_HANDLE));
     h->T = T;
     h->origin = static_cast<long long>(T);
     COMMS_HIP_TRY(h->hist.upload(nullptr, 0));  // zeros (the step ended synchronised)
@@ -589,46 +538,21 @@ comms_status_t comms_ofdmsync_correct_run(comms_ofdmsync_t* h, const comms_c32* 
 }
 
 comms_status_t comms_ofdmsync_get_state(comms_ofdmsync_t* h, comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state <= static_cast<size_t>(h->H), "n_state %zu exceeds the %d samples of the state", n_state, h->H);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());
-    if (!n_state) return COMMS_OK;
-    COMMS_HIP_TRY(h->hist.download(state, n_state));
-    return COMMS_OK;
+    return get_history_state(h, state, n_state, "samples");
 }
 
+// (n_state must be H = W + L + 2 G - 1 >= 2: a NULL state never comes with a length the setter accepts)
 comms_status_t comms_ofdmsync_set_state(comms_ofdmsync_t* h, const comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state == static_cast<size_t>(h->H), "n_state must be exactly the %d samples of the state (got %zu)", h->H, n_state);
-    COMMS_ARG(state != nullptr, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());
-    COMMS_HIP_TRY(h->hist.upload(state, n_state));
-    return COMMS_OK;
+    return set_history_state(h, state, n_state, "samples");
 }
 
-comms_status_t comms_ofdmsync_get_position(const comms_ofdmsync_t* h, uint64_t* out_position) {
-    COMMS_ARG(h && out_position, "NULL argument");
-    *out_position = h->T;
-    return COMMS_OK;
-}
+comms_status_t comms_ofdmsync_get_position(const comms_ofdmsync_t* h, uint64_t* out_position) { return get_position(h, out_position); }
 
 comms_status_t comms_ofdmsync_set_position(comms_ofdmsync_t* h, uint64_t position) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(position <= (1ull << 62), "position is out of range");
-    h->T = position;
-    h->origin = 0;
-    return COMMS_OK;
+    return set_position(h, position, [&] { h->origin = 0; });
 }
 
-comms_status_t comms_ofdmsync_set_threshold(comms_ofdmsync_t* h, double threshold) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_TRY(check_threshold(threshold));
-    h->thr = static_cast<float>(threshold);
-    return COMMS_OK;
-}
+comms_status_t comms_ofdmsync_set_threshold(comms_ofdmsync_t* h, double threshold) { return set_threshold(h, threshold); }
 
 comms_status_t comms_ofdmsync_get_kernel(const comms_ofdmsync_t* h, size_t n, char* name, size_t name_len) {
     COMMS_ARG(h && name && name_len, "NULL argument");

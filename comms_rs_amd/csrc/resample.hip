@@ -39,6 +39,7 @@
 
 #include "common.hpp"
 #include "fir_handle.hpp"
+#include "stream_call.hpp"
 
 namespace comms {
 
@@ -241,6 +242,10 @@ size_t resample_out_len(size_t n, size_t up, size_t down) {  // n * up does not 
     return nu / down + (nu % down ? 1 : 0);
 }
 
+// tiles of a call that writes n_out samples, and the grid that walks them
+size_t resample_tiles(const comms_resample* h, size_t n_out) { return (n_out + h->TO - 1) / h->TO; }
+size_t resample_grid(const comms_resample* h, size_t n_out) { return tile_grid(resample_tiles(h, n_out), h->max_grid); }
+
 // The reference's nodes one by one: upsampler, [cast,] complex FIR (its handle keeps the history), [cast,] decimator
 comms_status_t run_series(comms_resample* h, const void* d_in, size_t n, void* d_out, hipStream_t s) {
     const size_t nu = n * h->up;
@@ -316,12 +321,9 @@ comms_status_t comms_resample_create(const float* taps, size_t n_taps, size_t up
     h->tab_lds = plan_tile(h.get(), tab_floats * 4);
     if (!h->tab_lds && !plan_tile(h.get(), 0))
         return fail(COMMS_ERR_DEVICE, "resample: no tile fits (up %zu, down %zu, %zu taps)", L, M, n_taps);
-    h->WG = h->TO >= 256 ? 256 : h->TO < 64 ? 64 : h->TO;
+    h->WG = tile_workgroup(h->TO);
     h->max_grid = resident_workgroups(h->lds);
-    std::vector<float> tab(tab_floats, 0.0f);
-    for (size_t p = 0; p < L; ++p)
-        for (size_t q = 0; p + L * q < n_taps; ++q) tab[p * h->RS + q] = taps[p + L * q];
-    COMMS_HIP_TRY(h->d_tab.upload(tab));
+    COMMS_HIP_TRY(h->d_tab.upload(polyphase_rows(taps, n_taps, L, static_cast<size_t>(h->RS))));
     COMMS_HIP_TRY(h->hist.alloc(h->Q, static_cast<size_t>(elem)));
     *out = h.release();
     return COMMS_OK;
@@ -341,8 +343,7 @@ comms_status_t comms_resample_run_dev(comms_resample_t* h, const void* d_in, siz
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
     if (h->series) return run_series(h, d_in, n, d_out, s);
-    const size_t tiles = (n_out + h->TO - 1) / h->TO;
-    const unsigned grid = tiles < h->max_grid ? static_cast<unsigned>(tiles) : h->max_grid;
+    const unsigned grid = static_cast<unsigned>(resample_grid(h, n_out));
     RsArgs a{};
     a.in = d_in;
     a.hist = h->hist.cur();
@@ -351,7 +352,7 @@ comms_status_t comms_resample_run_dev(comms_resample_t* h, const void* d_in, siz
     a.taps = h->d_tab.get();
     a.n = n;
     a.n_out = n_out;
-    a.tiles = tiles;
+    a.tiles = resample_tiles(h, n_out);
     a.Q = static_cast<int>(h->Q);
     a.L = static_cast<int>(h->up);
     a.M = static_cast<int>(h->down);
@@ -394,14 +395,11 @@ comms_status_t comms_resample_run(comms_resample_t* h, const void* in, size_t n,
 }
 
 comms_status_t comms_resample_get_state(comms_resample_t* h, void* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state <= h->Q, "n_state %zu exceeds the %zu samples of the state", n_state, h->Q);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());  // the history is advanced by the launches, on whatever stream they ran
+    if (!h || !h->series) return get_history_state(h, state, n_state, "samples");
+    COMMS_TRY(state_access(h, h->Q, state, n_state, false, "samples"));
     if (!n_state) return COMMS_OK;
     const size_t E = static_cast<size_t>(h->elem);
-    if (h->series) {
+    {
         // the inner state is that of the upsampled stream, newest first: entry up - 1 + up q holds input sample n - 1 - q
         const size_t m = h->up * n_state;
         std::vector<comms_c32> cs(m);
@@ -413,25 +411,16 @@ comms_status_t comms_resample_get_state(comms_resample_t* h, void* state, size_t
         }
         return COMMS_OK;
     }
-    COMMS_HIP_TRY(h->hist.download(state, n_state));
-    return COMMS_OK;
 }
 
 comms_status_t comms_resample_set_state(comms_resample_t* h, const void* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state == h->Q, "state must hold exactly the %zu samples of the state", h->Q);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());  // no pending launch may still read the buffer that is overwritten
+    if (!h || !h->series) return set_history_state(h, state, n_state, "samples");
+    COMMS_TRY(state_access(h, h->Q, state, n_state, true, "samples"));
     const size_t E = static_cast<size_t>(h->elem);
-    if (h->series) {
-        std::vector<comms_c32> cs(h->n_taps, comms_c32{0.0f, 0.0f});  // the stuffed zeros between the input samples
-        for (size_t q = 0; q < n_state; ++q)
-            cs[h->up - 1 + h->up * q] = E == 8 ? static_cast<const comms_c32*>(state)[q] : comms_c32{static_cast<const float*>(state)[q], 0.0f};
-        return comms_fir_set_state(h->fir.get(), cs.data(), cs.size());
-    }
-    COMMS_HIP_TRY(h->hist.upload(state, n_state));
-    return COMMS_OK;
+    std::vector<comms_c32> cs(h->n_taps, comms_c32{0.0f, 0.0f});  // the stuffed zeros between the input samples
+    for (size_t q = 0; q < n_state; ++q)
+        cs[h->up - 1 + h->up * q] = E == 8 ? static_cast<const comms_c32*>(state)[q] : comms_c32{static_cast<const float*>(state)[q], 0.0f};
+    return comms_fir_set_state(h->fir.get(), cs.data(), cs.size());
 }
 
 comms_status_t comms_resample_get_kernel(const comms_resample_t* h, size_t n, char* name, size_t name_len) {
@@ -444,10 +433,10 @@ comms_status_t comms_resample_get_kernel(const comms_resample_t* h, size_t n, ch
         else
             std::snprintf(name, name_len, "series: upsample_kernel + real_to_c32_kernel + %s + c32_re_kernel + decimate_kernel", fir);
     } else {
-        const size_t tiles = (resample_out_len(n, h->up, h->down) + h->TO - 1) / h->TO;
+        const size_t n_out = resample_out_len(n, h->up, h->down);
         std::snprintf(name, name_len, "resample_kernel<%s, %s> tile=%d lds=%zu tiles=%zu grid=%zu max_grid=%u",
-                      h->elem == COMMS_RESAMPLE_C32 ? "c32" : "f32", h->tab_lds ? "taps in LDS" : "taps in global memory", h->TO, h->lds, tiles,
-                      tiles < h->max_grid ? tiles : static_cast<size_t>(h->max_grid), h->max_grid);
+                      h->elem == COMMS_RESAMPLE_C32 ? "c32" : "f32", h->tab_lds ? "taps in LDS" : "taps in global memory", h->TO, h->lds,
+                      resample_tiles(h, n_out), resample_grid(h, n_out), h->max_grid);
     }
     return COMMS_OK;
 }

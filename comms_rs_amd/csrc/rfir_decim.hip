@@ -34,6 +34,7 @@
 
 #include "common.hpp"
 #include "fir_handle.hpp"
+#include "stream_call.hpp"
 
 namespace comms {
 
@@ -305,33 +306,23 @@ comms_status_t comms_rfir_run(comms_rfir_t* h, const float* in, size_t n, float*
 }
 
 comms_status_t comms_rfir_get_state(comms_rfir_t* h, float* state, size_t n_state) {
-    COMMS_ARG(h && state, "NULL argument");
-    COMMS_ARG(n_state <= static_cast<size_t>(h->n_eff), "n_state %zu exceeds the %d effective taps", n_state, h->n_eff);
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());  // the history is advanced by the launches, on whatever stream they ran
+    COMMS_ARG(h && state, "NULL argument");  // this node refuses a NULL state even for an empty read
+    if (!h->series) return get_history_state(h, state, n_state, "samples");
+    COMMS_TRY(state_access(h, static_cast<size_t>(h->n_eff), state, n_state, false, "samples"));
     if (!n_state) return COMMS_OK;  // (an empty read: the series' inner getter takes no empty buffer)
-    if (h->series) {
-        std::vector<comms_c32> cs(n_state);
-        COMMS_TRY(comms_fir_get_state(h->fir.get(), cs.data(), n_state));
-        for (size_t k = 0; k < n_state; ++k) state[k] = cs[k].re;
-        return COMMS_OK;
-    }
-    COMMS_HIP_TRY(h->hist.download(state, n_state));
+    std::vector<comms_c32> cs(n_state);
+    COMMS_TRY(comms_fir_get_state(h->fir.get(), cs.data(), n_state));
+    for (size_t k = 0; k < n_state; ++k) state[k] = cs[k].re;
     return COMMS_OK;
 }
 
+// (n_state must be n_eff >= 1: a NULL state never comes with a length the setter accepts)
 comms_status_t comms_rfir_set_state(comms_rfir_t* h, const float* state, size_t n_state) {
-    COMMS_ARG(h && state, "NULL argument");
-    COMMS_ARG(n_state == static_cast<size_t>(h->n_eff), "state must hold exactly the %d effective taps", h->n_eff);
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());  // no pending launch may still read the buffer that is overwritten
-    if (h->series) {
-        std::vector<comms_c32> cs(n_state);
-        for (size_t k = 0; k < n_state; ++k) cs[k] = comms_c32{state[k], 0.0f};
-        return comms_fir_set_state(h->fir.get(), cs.data(), n_state);
-    }
-    COMMS_HIP_TRY(h->hist.upload(state, n_state));
-    return COMMS_OK;
+    if (!h || !h->series) return set_history_state(h, state, n_state, "samples");
+    COMMS_TRY(state_access(h, static_cast<size_t>(h->n_eff), state, n_state, true, "samples"));
+    std::vector<comms_c32> cs(n_state);
+    for (size_t k = 0; k < n_state; ++k) cs[k] = comms_c32{state[k], 0.0f};
+    return comms_fir_set_state(h->fir.get(), cs.data(), n_state);
 }
 
 comms_status_t comms_rfir_get_kernel(const comms_rfir_t* h, size_t n, char* name, size_t name_len) {

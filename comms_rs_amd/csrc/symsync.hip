@@ -40,6 +40,7 @@
 #include "common.hpp"
 #include "fir_handle.hpp"
 #include "sgpr_mac.hpp"
+#include "stream_call.hpp"
 
 namespace comms {
 
@@ -242,6 +243,10 @@ comms_status_t launch_symsync_fmt(int fmt, const SsArgs& a, unsigned blocks, int
     }
 }
 
+// tiles of a call that writes n_out symbols, and the grid that walks them
+size_t symsync_tiles(const comms_symsync* h, size_t n_out) { return (n_out + h->TO - 1) / h->TO; }
+size_t symsync_grid(const comms_symsync* h, size_t n_out) { return tile_grid(symsync_tiles(h, n_out), h->max_grid); }
+
 size_t symsync_out_bytes(const comms_symsync* h, size_t n_out) {
     return h->out_bits ? (n_out * h->out_bits + 7) / 8 : n_out * sizeof(comms_c32);
 }
@@ -283,13 +288,10 @@ comms_status_t comms_symsync_create(const float* taps, size_t n_taps, size_t pha
     h->HB = static_cast<int>((4 * h->NB - 1 + S - 1) / S);
     if (!plan_tile(h.get()))
         return fail(COMMS_ERR_DEVICE, "symsync: no tile fits (%zu phases, %zu samples per symbol, %zu taps)", L, S, n_taps);
-    h->WG = h->TO >= 256 ? 256 : h->TO < 64 ? 64 : h->TO;
+    h->WG = tile_workgroup(h->TO);
     h->U = h->TO >= 4 * h->WG ? 4 : h->TO >= 2 * h->WG ? 2 : 1;
     h->max_grid = resident_workgroups(h->lds);
-    std::vector<float> tab(L * h->RS, 0.0f);
-    for (size_t p = 0; p < L; ++p)
-        for (size_t j = 0; p + L * j < n_taps; ++j) tab[p * h->RS + j] = taps[p + L * j];
-    COMMS_HIP_TRY(h->d_tab.upload(tab));
+    COMMS_HIP_TRY(h->d_tab.upload(polyphase_rows(taps, n_taps, L, static_cast<size_t>(h->RS))));
     COMMS_HIP_TRY(h->hist.alloc(h->Q, sizeof(comms_c32)));
     *out = h.release();
     return COMMS_OK;
@@ -358,8 +360,7 @@ comms_status_t comms_symsync_run_dev(comms_symsync_t* h, const comms_c32* d_in, 
     if (!n) return COMMS_OK;
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
-    const size_t tiles = (n_out + h->TO - 1) / h->TO;
-    const unsigned grid = tiles < h->max_grid ? static_cast<unsigned>(tiles) : h->max_grid;
+    const unsigned grid = static_cast<unsigned>(symsync_grid(h, n_out));
     SsArgs a{};
     a.in = reinterpret_cast<const float2*>(d_in);
     a.hist = h->hist.cur<float2>();
@@ -369,7 +370,7 @@ comms_status_t comms_symsync_run_dev(comms_symsync_t* h, const comms_c32* d_in, 
     a.n = n;
     a.n_out = n_out;
     a.n_bytes = out_bytes;
-    a.tiles = tiles;
+    a.tiles = symsync_tiles(h, n_out);
     a.Q = static_cast<int>(h->Q);
     a.S = static_cast<int>(h->S);
     a.NB = h->NB;
@@ -414,32 +415,18 @@ comms_status_t comms_symsync_run(comms_symsync_t* h, const comms_c32* in, size_t
 }
 
 comms_status_t comms_symsync_get_state(comms_symsync_t* h, comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state <= h->Q, "n_state %zu exceeds the %zu samples of the state", n_state, h->Q);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());  // the history is advanced by the launches, on whatever stream they ran
-    if (!n_state) return COMMS_OK;
-    COMMS_HIP_TRY(h->hist.download(state, n_state));
-    return COMMS_OK;
+    return get_history_state(h, state, n_state, "samples");
 }
 
 comms_status_t comms_symsync_set_state(comms_symsync_t* h, const comms_c32* state, size_t n_state) {
-    COMMS_ARG(h != nullptr, "handle is NULL");
-    COMMS_ARG(n_state == h->Q, "state must hold exactly the %zu samples of the state", h->Q);
-    COMMS_ARG(state != nullptr || !n_state, "state is NULL");
-    COMMS_TRY(use_device(h->device));
-    COMMS_TRY(h->quiesce());  // no pending launch may still read the buffer that is overwritten
-    COMMS_HIP_TRY(h->hist.upload(state, n_state));
-    return COMMS_OK;
+    return set_history_state(h, state, n_state, "samples");
 }
 
 comms_status_t comms_symsync_get_kernel(const comms_symsync_t* h, size_t n, char* name, size_t name_len) {
     COMMS_ARG(h && name && name_len, "NULL argument");
-    const size_t tiles = (n / h->S + h->TO - 1) / h->TO;
     std::snprintf(name, name_len, "symsync_kernel<%d, %s> tile=%d wg=%d lds=%zu tiles=%zu grid=%zu max_grid=%u", h->U,
-                  h->out_bits == 0 ? "c32" : h->out_bits == 1 ? "bits1" : "bits2", h->TO, h->WG, h->lds, tiles,
-                  tiles < h->max_grid ? tiles : static_cast<size_t>(h->max_grid), h->max_grid);
+                  h->out_bits == 0 ? "c32" : h->out_bits == 1 ? "bits1" : "bits2", h->TO, h->WG, h->lds, symsync_tiles(h, n / h->S),
+                  symsync_grid(h, n / h->S), h->max_grid);
     return COMMS_OK;
 }
 

@@ -35,6 +35,7 @@
 
 #include "common.hpp"
 #include "sgpr_mac.hpp"
+#include "stream_call.hpp"
 #include "zpow.hpp"
 
 namespace comms {
@@ -282,20 +283,6 @@ static comms_status_t phase_c32(int kind, const comms_c32* d_x, size_t n, unsign
     return COMMS_OK;
 }
 
-// input only: short blocks are read straight from pinned host memory, long ones uploaded
-static comms_status_t stage_c32(Handle* h, const comms_c32* x, size_t n, const void** d) {
-    if (n * 8 <= zero_copy_limit()) {
-        COMMS_TRY(h->pin_in.reserve(n * 8));
-        std::memcpy(h->pin_in.h, x, n * 8);
-        *d = h->pin_in.d;
-    } else {
-        COMMS_TRY(h->in_scratch.reserve(n * 8));
-        COMMS_HIP_TRY(hipMemcpyAsync(h->in_scratch.p, x, n * 8, hipMemcpyHostToDevice, h->stream));
-        *d = h->in_scratch.p;
-    }
-    return COMMS_OK;
-}
-
 static comms_status_t phase_c32_host(int kind, const comms_c32* x, size_t n, unsigned m, double* out, int32_t device) {
     COMMS_ARG(out != nullptr && (x || !n), "NULL argument");
     COMMS_ARG(n <= SIZE_MAX / 8, "n overflows");
@@ -303,7 +290,7 @@ static comms_status_t phase_c32_host(int kind, const comms_c32* x, size_t n, uns
     Handle* h = nullptr;
     COMMS_TRY(thread_handle(device, &h));
     const void* d = nullptr;
-    if (n) COMMS_TRY(stage_c32(h, x, n, &d));
+    if (n) COMMS_TRY(stage_input(h, x, n * 8, &d));
     return phase_c32(kind, static_cast<const comms_c32*>(d), n, m, out, device, h->stream);
 }
 
@@ -324,10 +311,8 @@ static_assert(!std::is_copy_constructible_v<comms_syncest>, "a handle is never c
 
 namespace {
 
-size_t syncest_grid(const comms_syncest* h, size_t len) {
-    const size_t tiles = (len + SE_TILE - 1) / SE_TILE;
-    return tiles < h->max_grid ? tiles : h->max_grid;
-}
+size_t syncest_tiles(size_t len) { return (len + SE_TILE - 1) / SE_TILE; }
+size_t syncest_grid(const comms_syncest* h, size_t len) { return tile_grid(syncest_tiles(len), h->max_grid); }
 
 }  // namespace
 
@@ -412,14 +397,14 @@ comms_status_t comms_syncest_run(comms_syncest_t* h, const comms_c32* in, size_t
     COMMS_ARG(len <= SIZE_MAX / 8, "len overflows");
     COMMS_TRY(use_device(h->device));
     const void* d = nullptr;
-    if (len) COMMS_TRY(stage_c32(h, in, len, &d));
+    if (len) COMMS_TRY(stage_input(h, in, len * 8, &d));
     return comms_syncest_run_dev(h, static_cast<const comms_c32*>(d), len, out, COMMS_STREAM_HANDLE);
 }
 
 comms_status_t comms_syncest_get_kernel(const comms_syncest_t* h, size_t len, char* name, size_t name_len) {
     COMMS_ARG(h && name && name_len, "NULL argument");
     std::snprintf(name, name_len, "syncest_kernel tile=%d wg=%d taps=%d lds=%zu tiles=%zu grid=%zu max_grid=%u", SE_TILE, SE_WG,
-                  h->nk, h->lds, (len + SE_TILE - 1) / SE_TILE, syncest_grid(h, len), h->max_grid);
+                  h->nk, h->lds, syncest_tiles(len), syncest_grid(h, len), h->max_grid);
     return COMMS_OK;
 }
 

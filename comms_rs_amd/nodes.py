@@ -73,6 +73,66 @@ class _Handle:
             pass
 
 
+class _History:
+    """The history accessors of a stream node (csrc/stream_call.hpp) over comms_<prefix>_{state_len, get_state, set_state}:
+    `_state_dtype` is the sample type, `_state_args` names the attributes comms_<prefix>_state_len takes.  The length is fixed
+    at create: the library is asked once per node."""
+    _state_dtype = np.complex64
+    _state_args = ()
+    _state_len = None
+
+    def state_len(self):
+        if self._state_len is None:
+            m = C.c_size_t()
+            check(getattr(lib(), self._prefix + "_state_len")(*[getattr(self, a) for a in self._state_args], C.byref(m)))
+            self._state_len = m.value
+        return self._state_len
+
+    def get_state(self, n_state=None):
+        """The last n_state input samples (default: all state_len() of them), newest first."""
+        n_state = self.state_len() if n_state is None else int(n_state)
+        st = np.empty(n_state, self._state_dtype)
+        check(getattr(lib(), self._prefix + "_get_state")(self._h, _ptr(st), n_state))
+        return st
+
+    def set_state(self, state):
+        state = np.ascontiguousarray(state, dtype=self._state_dtype)
+        check(getattr(lib(), self._prefix + "_set_state")(self._h, _ptr(state), state.size))
+        return self
+
+
+class _Position:
+    """The stream index of a node that reports positions: comms_<prefix>_{get_position, set_position}."""
+
+    def position(self):
+        """Stream index of the next sample (symbol)."""
+        t = C.c_uint64()
+        check(getattr(lib(), self._prefix + "_get_position")(self._h, C.byref(t)))
+        return t.value
+
+    def set_position(self, position):
+        check(getattr(lib(), self._prefix + "_set_position")(self._h, int(position)))
+        return self
+
+
+class _Detector(_Position):
+    """What the two synchronisers share beside their history: the threshold, the default capacity of a call (detections are more
+    than `guard` positions apart) and the packing of its detections."""
+    found = 0
+
+    def set_threshold(self, threshold):
+        check(getattr(lib(), self._prefix + "_set_threshold")(self._h, float(threshold)))
+        return self
+
+    def _cap(self, n, cap):
+        return (n + self.guard) // (self.guard + 1) if cap is None else int(cap)
+
+    def _result(self, out, cap, found, raw):
+        self.found = found.value
+        out = out[: min(self.found, cap)]
+        return out if raw else [FrameDetection(d) for d in out]
+
+
 # ------------------------------------------------------------------ device buffers
 class DeviceBuf:
     """Ref-counted device allocation (comms_buf_*): the device-resident message type."""
@@ -721,11 +781,12 @@ class ChainNode(_Handle):
 
 
 # ------------------------------------------------------------------ tap design
-class RealFirDecimNode(_Handle):
+class RealFirDecimNode(_History, _Handle):
     """Real FIR with decimation (comms_rfir_*): the audio stage of examples/fm_radio.rs:98-164 -- Convert2Node ->
     BatchFirNode<f32> -> Convert3Node -> DecimateNode<f32>(rate) -- as one node over an f32 stream.  Any batch length:
     the decimator restarts at sample 0 of every call, the FIR history advances by all samples."""
     _prefix = "comms_rfir"
+    _state_dtype = np.float32   # (no comms_rfir_state_len: get_state takes its n_state)
 
     def __init__(self, taps, rate, state=None, device=0):
         super().__init__()
@@ -755,27 +816,19 @@ class RealFirDecimNode(_Handle):
     def run_dev(self, in_ptr, n, out_ptr, stream=0):
         check(lib().comms_rfir_run_dev(self._h, in_ptr, n, out_ptr, stream))
 
-    def get_state(self, n_state):
-        st = np.empty(n_state, np.float32)
-        check(lib().comms_rfir_get_state(self._h, _ptr(st), n_state))
-        return st
 
-    def set_state(self, state):
-        state = np.ascontiguousarray(state, dtype=np.float32)
-        check(lib().comms_rfir_set_state(self._h, _ptr(state), state.size))
-
-
-class ResampleNode(_Handle):
+class ResampleNode(_History, _Handle):
     """Rational resampler by up / down (comms_resample_*): UpsampleNode(up) -> BatchFirNode(Complex(taps, 0)) ->
     DecimateNode(down) as one node over an f32 or Complex<f32> stream, which forms only the products with input samples.
     Any batch length: ceil(n up / down) outputs per call, the decimator restarts at sample 0 of every call and the
     history -- (len(taps) - 1) // up INPUT samples -- advances by all samples."""
     _prefix = "comms_resample"
+    _state_args = ("n_taps", "up")
 
     def __init__(self, taps, up, down, dtype=np.float32, device=0):
         super().__init__()
         taps = np.ascontiguousarray(taps, dtype=np.float32)
-        self.dtype = np.dtype(dtype)
+        self.dtype = self._state_dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.complex64)):
             raise TypeError("ResampleNode takes float32 or complex64 samples, not %s" % self.dtype)
         self.up, self.down, self.n_taps = int(up), int(down), taps.size
@@ -784,11 +837,6 @@ class ResampleNode(_Handle):
     def out_len(self, n):
         m = C.c_size_t()
         check(lib().comms_resample_out_len(n, self.up, self.down, C.byref(m)))
-        return m.value
-
-    def state_len(self):
-        m = C.c_size_t()
-        check(lib().comms_resample_state_len(self.n_taps, self.up, C.byref(m)))
         return m.value
 
     def kernel(self, n):
@@ -805,25 +853,15 @@ class ResampleNode(_Handle):
     def run_dev(self, in_ptr, n, out_ptr, stream=0):
         check(lib().comms_resample_run_dev(self._h, in_ptr, n, out_ptr, stream))
 
-    def get_state(self, n_state=None):
-        """The last n_state input samples (default: all state_len() of them), newest first."""
-        n_state = self.state_len() if n_state is None else int(n_state)
-        st = np.empty(n_state, self.dtype)
-        check(lib().comms_resample_get_state(self._h, _ptr(st), n_state))
-        return st
 
-    def set_state(self, state):
-        state = np.ascontiguousarray(state, dtype=self.dtype)
-        check(lib().comms_resample_set_state(self._h, _ptr(state), state.size))
-
-
-class ChannelizerNode(_Handle):
+class ChannelizerNode(_History, _Handle):
     """Polyphase channelizer (comms_channelizer_*): M chains MixerNode(0, -2 pi k / M) -> BatchFirNode(Complex(taps, 0)) ->
     DecimateNode(down), k = 0 .. M-1, over one Complex<f32> stream as one node -- a polyphase filter bank that reads every
     sample once and spends len(taps) multiply-adds per frame (one output of each channel).  Any batch length: ceil(n / down)
     frames per call, returned as an array [channels][frames] (layout "channel", each row a contiguous stream) or
     [frames][channels] (layout "frame").  State: the last len(taps) - 1 input samples and the stream index mod M."""
     _prefix = "comms_channelizer"
+    _state_args = ("n_taps",)
     LAYOUTS = {"channel": 0, "frame": 1, 0: 0, 1: 1}
 
     def __init__(self, taps, channels, down, layout="channel", device=0):
@@ -839,11 +877,6 @@ class ChannelizerNode(_Handle):
         """Frames of a call of n samples; the call writes out_len(n) * channels outputs."""
         m = C.c_size_t()
         check(lib().comms_channelizer_out_len(n, self.down, C.byref(m)))
-        return m.value
-
-    def state_len(self):
-        m = C.c_size_t()
-        check(lib().comms_channelizer_state_len(self.n_taps, C.byref(m)))
         return m.value
 
     def kernel(self, n):
@@ -863,18 +896,7 @@ class ChannelizerNode(_Handle):
     def run_dev(self, in_ptr, n, out_ptr, stream=0):
         check(lib().comms_channelizer_run_dev(self._h, in_ptr, n, out_ptr, stream))
 
-    def get_state(self, n_state=None):
-        """The last n_state input samples (default: all state_len() of them), newest first."""
-        n_state = self.state_len() if n_state is None else int(n_state)
-        st = np.empty(n_state, np.complex64)
-        check(lib().comms_channelizer_get_state(self._h, _ptr(st), n_state))
-        return st
-
-    def set_state(self, state):
-        state = np.ascontiguousarray(state, dtype=np.complex64)
-        check(lib().comms_channelizer_set_state(self._h, _ptr(state), state.size))
-
-    state = property(get_state, set_state)
+    state = property(_History.get_state, _History.set_state)
 
     def get_phase(self):
         """The stream index of the next input sample, mod channels."""
@@ -889,13 +911,14 @@ class ChannelizerNode(_Handle):
     phase = property(get_phase, set_phase)
 
 
-class SymbolSyncNode(_Handle):
+class SymbolSyncNode(_History, _Handle):
     """Symbol synchroniser (comms_symsync_*): matched filter with a fractional delay, symbol-rate sampler, rotation and
     (optionally) hard decision over a Complex<f32> stream as one node -- UpsampleNode(phases) -> BatchFirNode(Complex(taps,
     0)) -> skip mu -> DecimateNode(phases * sps) -> MixerNode -> decision, computing only the kept outputs.  taps are real,
     designed at `phases` times the input rate (rrc_taps(N, phases * sps, beta)); batches are multiples of sps samples and
     give n / sps outputs; the history -- (len(taps) - 1) // phases RAW input samples -- does not depend on the timing."""
     _prefix = "comms_symsync"
+    _state_args = ("n_taps", "phases")
     _out_bits = 0
 
     def __init__(self, taps, phases, sps, device=0):
@@ -954,11 +977,6 @@ class SymbolSyncNode(_Handle):
         n_sym = self.out_len(n)
         return (n_sym * self._out_bits + 7) // 8 if self._out_bits else n_sym * 8
 
-    def state_len(self):
-        m = C.c_size_t()
-        check(lib().comms_symsync_state_len(self.n_taps, self.phases, C.byref(m)))
-        return m.value
-
     def kernel(self, n):
         """What a batch of n samples is run by: "symsync_kernel<..> tile=.. wg=.. lds=.. tiles=.. grid=.. max_grid=.."."""
         return self._kernel_name(n)
@@ -972,18 +990,7 @@ class SymbolSyncNode(_Handle):
     def run_dev(self, in_ptr, n, out_ptr, stream=0):
         check(lib().comms_symsync_run_dev(self._h, in_ptr, n, out_ptr, stream))
 
-    def get_state(self, n_state=None):
-        """The last n_state input samples (default: all state_len() of them), newest first."""
-        n_state = self.state_len() if n_state is None else int(n_state)
-        st = np.empty(n_state, np.complex64)
-        check(lib().comms_symsync_get_state(self._h, _ptr(st), n_state))
-        return st
-
-    def set_state(self, state):
-        state = np.ascontiguousarray(state, dtype=np.complex64)
-        check(lib().comms_symsync_set_state(self._h, _ptr(state), state.size))
-
-    state = property(get_state, set_state)
+    state = property(_History.get_state, _History.set_state)
 
 
 def _taps(fn, n_taps, *args):
@@ -1381,7 +1388,7 @@ class FrameDetection:
         return "FrameDetection(index=%d, corr=%r, metric=%r, energy=%r)" % (self.index, self.corr, self.metric, self.energy)
 
 
-class FrameSyncNode(_Handle):
+class FrameSyncNode(_History, _Detector, _Handle):
     """Frame synchroniser (comms_framesync_*): normalised correlation of a Complex<f32> symbol stream (SymbolSyncNode's
     output) with a known `word`, peak search over +-`guard` positions and the `threshold` in one launch that returns only the
     detections.  A call on n symbols decides n positions (a word is reported `guard` symbols after its end); flush() ends a
@@ -1389,21 +1396,13 @@ class FrameSyncNode(_Handle):
     lowest indices); `found` is the true count of the last call.  With raw=True a call returns the structured array
     (FRAME_DETECTION_DTYPE) instead of FrameDetection values."""
     _prefix = "comms_framesync"
-    found = 0
+    _state_args = ("n_word", "guard")
 
     def __init__(self, word, threshold, guard, device=0):
         super().__init__()
         word = np.ascontiguousarray(word, dtype=np.complex64)
         self.n_word, self.guard = word.size, int(guard)
         check(lib().comms_framesync_create(_ptr(word), word.size, float(threshold), int(guard), device, C.byref(self._h)))
-
-    def _cap(self, n, cap):
-        return (n + self.guard) // (self.guard + 1) if cap is None else int(cap)
-
-    def _result(self, out, cap, found, raw):
-        self.found = found.value
-        out = out[: min(self.found, cap)]
-        return out if raw else [FrameDetection(d) for d in out]
 
     def run(self, symbols, cap=None, raw=False):
         x = np.ascontiguousarray(symbols, dtype=np.complex64)
@@ -1425,36 +1424,7 @@ class FrameSyncNode(_Handle):
         check(lib().comms_framesync_flush(self._h, _ptr(out) if cap else None, cap, C.byref(found)))
         return self._result(out, cap, found, raw)
 
-    def state_len(self):
-        m = C.c_size_t()
-        check(lib().comms_framesync_state_len(self.n_word, self.guard, C.byref(m)))
-        return m.value
-
-    def state(self, n_state=None):
-        """The last n_state symbols (default: all n_word + 2 guard - 1), newest first."""
-        n_state = self.state_len() if n_state is None else int(n_state)
-        st = np.empty(n_state, np.complex64)
-        check(lib().comms_framesync_get_state(self._h, _ptr(st), n_state))
-        return st
-
-    def set_state(self, state):
-        state = np.ascontiguousarray(state, dtype=np.complex64)
-        check(lib().comms_framesync_set_state(self._h, _ptr(state), state.size))
-        return self
-
-    def position(self):
-        """Stream index of the next symbol."""
-        t = C.c_uint64()
-        check(lib().comms_framesync_get_position(self._h, C.byref(t)))
-        return t.value
-
-    def set_position(self, position):
-        check(lib().comms_framesync_set_position(self._h, int(position)))
-        return self
-
-    def set_threshold(self, threshold):
-        check(lib().comms_framesync_set_threshold(self._h, float(threshold)))
-        return self
+    state = _History.get_state   # the last n_state symbols (default: all n_word + 2 guard - 1), newest first
 
     def kernel(self, n):
         """What a call on n symbols is run by: "framesync_kernel tile=.. wg=.. word=.. guard=.. lds=.. tiles=.. grid=.. max_grid=.."."""
@@ -1482,7 +1452,7 @@ def _as_detections(detections):
     return out
 
 
-class DeframeNode(_Handle):
+class DeframeNode(_History, _Position, _Handle):
     """Deframer (comms_deframe_*): takes the symbol stream FrameSyncNode takes, in the same calls, and the detections those
     calls return, and writes every frame that becomes complete in a call -- `n_payload` symbols from index + `offset`,
     derotated by the detection's correlation and, with normalise=True, scaled by word_energy / |corr| -- in one launch:
@@ -1492,6 +1462,7 @@ class DeframeNode(_Handle):
     of shape (n_frames, n_payload) complex64, (n_frames, frame_bytes) uint8 or (n_frames, n_payload * bits_per_sym) float32;
     `headers` holds the FRAME_HEADER_DTYPE records of the last call."""
     _prefix = "comms_deframe"
+    _state_args = ("n_payload", "lookback")
 
     def __init__(self, n_payload, offset, lookback, bits_per_sym=2, constellation=None, normalise=False, word_energy=None, device=0):
         super().__init__()
@@ -1566,33 +1537,9 @@ class DeframeNode(_Handle):
         check(lib().comms_deframe_flush(self._h, C.byref(dropped)))
         return dropped.value
 
-    def state_len(self):
-        m = C.c_size_t()
-        check(lib().comms_deframe_state_len(self.n_payload, self.lookback, C.byref(m)))
-        return m.value
+    state = _History.get_state   # the last n_state symbols (default: all max(lookback, n_payload - 1)), newest first
 
-    def state(self, n_state=None):
-        """The last n_state symbols (default: all max(lookback, n_payload - 1)), newest first."""
-        n_state = self.state_len() if n_state is None else int(n_state)
-        st = np.empty(n_state, np.complex64)
-        check(lib().comms_deframe_get_state(self._h, _ptr(st) if n_state else None, n_state))
-        return st
-
-    def set_state(self, state):
-        state = np.ascontiguousarray(state, dtype=np.complex64)
-        check(lib().comms_deframe_set_state(self._h, _ptr(state) if state.size else None, state.size))
-        return self
-
-    def position(self):
-        """Stream index of the next symbol."""
-        t = C.c_uint64()
-        check(lib().comms_deframe_get_position(self._h, C.byref(t)))
-        return t.value
-
-    def set_position(self, position):
-        """Also forgets the pending frames: restore a checkpoint as set_state, set_position, set_pending."""
-        check(lib().comms_deframe_set_position(self._h, int(position)))
-        return self
+    # (set_position also forgets the pending frames: restore a checkpoint as set_state, set_position, set_pending)
 
     def pending(self):
         """The frames admitted and not yet complete (FRAME_HEADER_DTYPE), ascending."""
@@ -2120,7 +2067,7 @@ class OfdmDemodNode(_Ofdm):
         check(lib().comms_ofdm_demod_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
 
 
-class OfdmSyncNode(_Handle):
+class OfdmSyncNode(_History, _Detector, _Handle):
     """OFDM stream synchroniser (comms_ofdmsync_*).  run() correlates the received sample stream with itself at `lag` over
     `window` samples, searches peaks of the normalised metric over +-`guard` positions above `threshold`, in one launch, and
     returns (detections, cfo): FrameDetection values whose `index` lies `advance` samples ahead of the peak, and the
@@ -2129,7 +2076,7 @@ class OfdmSyncNode(_Handle):
     DeframeNode(n_frame, 0, lookback >= window + lag + guard + advance - 1) in "c32"; correct() then multiplies record f by
     exp(-i cfo[f] n), all records in one launch, in front of OfdmDemodNode.  `found` is the true count of the last call."""
     _prefix = "comms_ofdmsync"
-    found = 0
+    _state_args = ("lag", "window", "guard")
 
     def __init__(self, lag, window, threshold, guard, advance=0, n_frame=0, device=0):
         super().__init__()
@@ -2149,13 +2096,9 @@ class OfdmSyncNode(_Handle):
         """The least `lookback` of the DeframeNode behind this node."""
         return self.window + self.lag + self.guard + self.advance - 1
 
-    def _cap(self, n, cap):
-        return (n + self.guard) // (self.guard + 1) if cap is None else int(cap)
-
     def _result(self, out, cfo, cap, found, raw):
-        self.found = found.value
-        k = min(self.found, cap)
-        return (out[:k] if raw else [FrameDetection(d) for d in out[:k]]), cfo[:k]
+        dets = super()._result(out, cap, found, raw)
+        return dets, cfo[: len(dets)]
 
     def run(self, samples, cap=None, raw=False):
         x = np.ascontiguousarray(samples, dtype=np.complex64)
@@ -2199,36 +2142,7 @@ class OfdmSyncNode(_Handle):
             raise ValueError("cfo holds one value per record")
         check(lib().comms_ofdmsync_correct_run_dev(self._h, in_ptr, int(n_frames), _ptr(w) if w.size else None, out_ptr, stream))
 
-    def state_len(self):
-        m = C.c_size_t()
-        check(lib().comms_ofdmsync_state_len(self.lag, self.window, self.guard, C.byref(m)))
-        return m.value
-
-    def state(self, n_state=None):
-        """The last n_state samples (default: all window + lag + 2 guard - 1), newest first."""
-        n_state = self.state_len() if n_state is None else int(n_state)
-        st = np.empty(n_state, np.complex64)
-        check(lib().comms_ofdmsync_get_state(self._h, _ptr(st), n_state))
-        return st
-
-    def set_state(self, state):
-        state = np.ascontiguousarray(state, dtype=np.complex64)
-        check(lib().comms_ofdmsync_set_state(self._h, _ptr(state), state.size))
-        return self
-
-    def position(self):
-        """Stream index of the next sample."""
-        t = C.c_uint64()
-        check(lib().comms_ofdmsync_get_position(self._h, C.byref(t)))
-        return t.value
-
-    def set_position(self, position):
-        check(lib().comms_ofdmsync_set_position(self._h, int(position)))
-        return self
-
-    def set_threshold(self, threshold):
-        check(lib().comms_ofdmsync_set_threshold(self._h, float(threshold)))
-        return self
+    state = _History.get_state   # the last n_state samples (default: all window + lag + 2 guard - 1), newest first
 
     def kernel(self, n):
         """What a call on n samples is run by: "ofdmsync_detect_kernel tile=.. wg=.. lag=.. window=.. guard=.. lds=.. tiles=.. grid=..".

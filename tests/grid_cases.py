@@ -35,14 +35,19 @@ ANCHORS = [
     (CSRC + "common.hpp", 'const int cap = diag_knob("COMMS_GRID_CAP", 0);'),
     (CSRC + "common.hpp", "return cap > 0 && static_cast<unsigned>(cap) < chip ? static_cast<unsigned>(cap) : chip;"),
     (CSRC + "syncest.hip", "constexpr int SE_TILE = SE_WG * SE_OPL;     // outputs per tile"),
-    (CSRC + "syncest.hip", "return tiles < h->max_grid ? tiles : h->max_grid;"),
+    (CSRC + "stream_call.hpp", "inline size_t tile_grid(size_t tiles, unsigned max_grid) { return tiles ? capped_grid(tiles, max_grid) : 0; }"),
+    (CSRC + "syncest.hip", "size_t syncest_tiles(size_t len) { return (len + SE_TILE - 1) / SE_TILE; }"),
+    (CSRC + "syncest.hip", "size_t syncest_grid(const comms_syncest* h, size_t len) { return tile_grid(syncest_tiles(len), h->max_grid); }"),
     (CSRC + "syncest.hip", "const int mt_step = static_cast<int>((static_cast<unsigned long long>(gridDim.x) * SE_TILE) % static_cast<unsigned>(n2));"),
-    (CSRC + "framesync.hip", "return tiles < h->max_grid ? tiles : h->max_grid;"),
+    (CSRC + "framesync.hip", "size_t framesync_tiles(size_t n) { return (n + FS_TILE - 1) / FS_TILE; }"),
+    (CSRC + "framesync.hip", "size_t framesync_grid(const comms_framesync* h, size_t n) { return tile_grid(framesync_tiles(n), h->max_grid); }"),
     (CSRC + "framesync.hip", "for (size_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {"),
     (CSRC + "symsync.hip", "for (int TO = 1024; TO >="),
-    (CSRC + "symsync.hip", "const unsigned grid = tiles < h->max_grid ? static_cast<unsigned>(tiles) : h->max_grid;"),
+    (CSRC + "symsync.hip", "size_t symsync_tiles(const comms_symsync* h, size_t n_out) { return (n_out + h->TO - 1) / h->TO; }"),
+    (CSRC + "symsync.hip", "size_t symsync_grid(const comms_symsync* h, size_t n_out) { return tile_grid(symsync_tiles(h, n_out), h->max_grid); }"),
     (CSRC + "resample.hip", "for (size_t TO = 1024; TO >="),
-    (CSRC + "resample.hip", "const unsigned grid = tiles < h->max_grid ? static_cast<unsigned>(tiles) : h->max_grid;"),
+    (CSRC + "resample.hip", "size_t resample_tiles(const comms_resample* h, size_t n_out) { return (n_out + h->TO - 1) / h->TO; }"),
+    (CSRC + "resample.hip", "size_t resample_grid(const comms_resample* h, size_t n_out) { return tile_grid(resample_tiles(h, n_out), h->max_grid); }"),
     (CSRC + "resample.hip", "const unsigned long long step = static_cast<unsigned long long>(grid) * h->TO * h->down;"),
     (CSRC + "channelizer.hip", "const size_t per = (tiles + h->max_grid - 1) / h->max_grid;"),
     (CSRC + "channelizer.hip", "return static_cast<unsigned>((tiles + per1 - 1) / per1);"),
