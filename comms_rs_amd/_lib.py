@@ -332,6 +332,19 @@ _PROTOS = {
     "comms_viterbi_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_viterbi_set_timer": [_vp, _vp],
     "comms_viterbi_destroy": [_vp],
+    "comms_ldpcenc_create": [_i32, _i32, _i32, _vp, _i32, _pp],
+    "comms_ldpcenc_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_ldpcenc_run": [_vp, _vp, _sz, _vp],
+    "comms_ldpcenc_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_ldpcenc_set_timer": [_vp, _vp],
+    "comms_ldpcenc_destroy": [_vp],
+    "comms_ldpcdec_create": [_i32, _i32, _i32, _vp, _i32, _i32, _sz, _i32, _pp],
+    "comms_ldpcdec_set_quant_scale": [_vp, C.c_float],
+    "comms_ldpcdec_run_dev": [_vp, _vp, _sz, _vp, _vp, _vp],
+    "comms_ldpcdec_run": [_vp, _vp, _sz, _vp, _vp],
+    "comms_ldpcdec_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_ldpcdec_set_timer": [_vp, _vp],
+    "comms_ldpcdec_destroy": [_vp],
     "comms_ratematch_create": [_sz, _vp, _sz, _sz, _vp, _vp, _sz, _i32, _pp],
     "comms_ratematch_get_map": [_vp, _vp, _sz],
     "comms_ratematch_tx_run_dev": [_vp, _vp, _sz, _vp, _vp],
@@ -411,6 +424,10 @@ _OTHER = {
     "comms_convenc_out_frame_bytes": (_sz, [_vp]),
     "comms_viterbi_in_frame_bytes": (_sz, [_vp]),
     "comms_viterbi_out_frame_bytes": (_sz, [_vp]),
+    "comms_ldpcenc_in_frame_bytes": (_sz, [_vp]),
+    "comms_ldpcenc_out_frame_bytes": (_sz, [_vp]),
+    "comms_ldpcdec_in_frame_bytes": (_sz, [_vp]),
+    "comms_ldpcdec_out_frame_bytes": (_sz, [_vp]),
     "comms_ratematch_n_tx_bits": (_sz, [_vp]),
     "comms_ratematch_tx_in_frame_bytes": (_sz, [_vp]),
     "comms_ratematch_tx_out_frame_bytes": (_sz, [_vp]),

@@ -776,6 +776,16 @@ inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintp
 // A record of `bits` packed bits: whole bytes, rounded up to 4
 inline size_t bit_record_bytes(size_t bits) { return ((bits + 7) / 8 + 3) / 4 * 4; }
 
+// The quantiser of the soft-input decoders (Viterbi, LDPC): q = clamp(rint(L * qscale), -127, 127), the product rounded to
+// f32 (no FMA), halves to even, NaN -> 0
+__device__ __forceinline__ int quantise_llr(float L, float qscale) {
+    const float x = __fmul_rn(L, qscale);
+    float r = rintf(x);                       // to nearest, halves to even
+    r = x != x ? 0.f : r;                     // NaN: an erasure
+    r = r < -127.f ? -127.f : r > 127.f ? 127.f : r;
+    return static_cast<int>(r);
+}
+
 // The body of every *_set_timer that only attaches the timer
 template <class H>
 comms_status_t set_handle_timer(H* h, comms_timer_t* t) {

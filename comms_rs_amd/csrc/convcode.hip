@@ -111,14 +111,6 @@ struct VtArgs {
     float qscale;
 };
 
-__device__ __forceinline__ int vt_quantise(float L, float qscale) {
-    const float x = __fmul_rn(L, qscale);
-    float r = rintf(x);                       // to nearest, halves to even
-    r = x != x ? 0.f : r;                     // NaN: an erasure
-    r = r < -127.f ? -127.f : r > 127.f ? 127.f : r;
-    return static_cast<int>(r);
-}
-
 template <int N, bool WS>
 __global__ __launch_bounds__(CC_WG) void viterbi_kernel(const VtArgs a) {
     extern __shared__ unsigned long long vt_lds[];
@@ -152,7 +144,7 @@ __global__ __launch_bounds__(CC_WG) void viterbi_kernel(const VtArgs a) {
         for (unsigned blk = 0; blk < a.blocks; ++blk) {
             int q[N];
 #pragma unroll
-            for (int j = 0; j < N; ++j) q[j] = vt_quantise(x[j], a.qscale);
+            for (int j = 0; j < N; ++j) q[j] = quantise_llr(x[j], a.qscale);
             if (blk + 1 < a.blocks) {
 #pragma unroll
                 for (int j = 0; j < N; ++j) {

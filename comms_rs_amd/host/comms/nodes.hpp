@@ -1481,6 +1481,94 @@ public:
     Result<FramesDev> run(const FramesDev& in) { return decode_dev(in, *this); }
 };
 
+// LDPC coding (comms_ldpcenc_*, comms_ldpcdec_*; additional nodes).  A code is its base matrix (mb x nb entries, row-major; -1 a
+// zero block, b >= 0 the identity shifted by b) and the lifting size Z.  One description per operation, two shells each.
+struct LdpcCodeSpec {
+    int mb, nb, Z;
+    std::vector<int16_t> base;   // mb * nb entries
+    const int16_t* b() const { return base.size() == static_cast<size_t>(mb) * static_cast<size_t>(nb) ? base.data() : nullptr; }
+};
+
+// Encoder: a message is whole records of (nb - mb) Z packed information bits (in_frame_bytes() each, LSB first), the output the
+// records of nb Z coded bits (out_frame_bytes() each) -- the bytes PulseBitsNode and the byte modulators take as they stand.
+struct LdpcEncOp {
+    using In = uint8_t;
+    using Out = uint8_t;
+    LdpcEncOp(const char* who, const LdpcCodeSpec& code, int device)
+        : h_(create<decltype(h_)>(who, comms_ldpcenc_create, code.mb, code.nb, code.Z, code.b(), device)) {}
+    size_t in_frame_bytes() const { return comms_ldpcenc_in_frame_bytes(h_.get()); }
+    size_t out_frame_bytes() const { return comms_ldpcenc_out_frame_bytes(h_.get()); }
+    std::string kernel(size_t n_frames) const { return kernel_name(comms_ldpcenc_get_kernel, h_.get(), n_frames); }  // "ldpc_encode_kernel ..."
+
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const {
+        if (n % in_frame_bytes()) return COMMS_ERR_ARG;
+        m = n / in_frame_bytes() * out_frame_bytes();
+        return COMMS_OK;
+    }
+    comms_status_t launch(const uint8_t* in, size_t n, uint8_t* out) { return comms_ldpcenc_run(h_.get(), in, n / in_frame_bytes(), out); }
+    comms_status_t launch_dev(const uint8_t* in, size_t n, uint8_t* out, void* s) {
+        return comms_ldpcenc_run_dev(h_.get(), in, n / in_frame_bytes(), out, s);
+    }
+    Owned<comms_ldpcenc_t, comms_ldpcenc_destroy> h_;
+};
+class LdpcEncoderNode : public HostNode<LdpcEncoderNode, LdpcEncOp> {
+public:
+    explicit LdpcEncoderNode(const LdpcCodeSpec& code, int device = 0) : HostNode("LdpcEncoderNode::new", code, device) {}
+};
+class LdpcEncoderNodeDev : public DevNode<LdpcEncoderNodeDev, LdpcEncOp> {
+public:
+    explicit LdpcEncoderNodeDev(const LdpcCodeSpec& code, int device = 0) : DevNode(device, "LdpcEncoderNodeDev::new", code, device) {}
+};
+
+// Decoder: takes DeframeNode's message in the COMMS_SYM_LLR format (records of frame_bytes / 4 >= nb Z values) and sends the
+// decoded records under the same headers: frame f at data[f * frame_bytes], frame_bytes = out_frame_bytes().  A message without
+// frames passes through empty.
+struct LdpcDecSpec {
+    int max_iters = 20, norm16 = 12;
+    size_t record_llrs = 0;      // values per input record (0: exactly nb Z)
+    float qscale = 1.0f;         // comms_ldpcdec_set_quant_scale
+};
+struct LdpcDecOp {
+    using Frames = DeframeOp::Frames;
+    using FramesDev = DeframeOp::FramesDev;
+    LdpcDecOp(const char* who, const LdpcCodeSpec& code, const LdpcDecSpec& dec, int device)
+        : h_(create<decltype(h_)>(who, comms_ldpcdec_create, code.mb, code.nb, code.Z, code.b(), dec.max_iters, dec.norm16, dec.record_llrs, device)) {
+        throw_on(comms_ldpcdec_set_quant_scale(h_.get(), dec.qscale), who);
+    }
+    size_t in_frame_bytes() const { return comms_ldpcdec_in_frame_bytes(h_.get()); }
+    size_t out_frame_bytes() const { return comms_ldpcdec_out_frame_bytes(h_.get()); }
+    std::string kernel(size_t n_frames) const { return kernel_name(comms_ldpcdec_get_kernel, h_.get(), n_frames); }  // "ldpc_decode_kernel ..."
+
+protected:
+    Result<Frames> decode(const Frames& in) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        Frames out{std::vector<uint8_t>(in.size() * out_frame_bytes()), in.headers, out_frame_bytes()};
+        return ok_or(comms_ldpcdec_run(h_.get(), reinterpret_cast<const float*>(in.data.data()), in.size(), out.data.data(), nullptr), out);
+    }
+    Result<FramesDev> decode_dev(const FramesDev& in, const DevStream& on) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        FramesDev out{DeviceBuf<uint8_t>(in.size() ? in.size() * out_frame_bytes() : 8, on.device()), in.headers, out_frame_bytes()};
+        return ok_or(on.submit(in.data, out.data, [&](void* s) {
+            return comms_ldpcdec_run_dev(h_.get(), reinterpret_cast<const float*>(in.data.ptr()), in.size(), out.data.ptr(), nullptr, s);
+        }), out);
+    }
+    Owned<comms_ldpcdec_t, comms_ldpcdec_destroy> h_;
+};
+class LdpcDecoderNode : public DeriveNode<LdpcDecoderNode>, public Ports<LdpcDecOp::Frames, LdpcDecOp::Frames>, public LdpcDecOp {
+public:
+    explicit LdpcDecoderNode(const LdpcCodeSpec& code, const LdpcDecSpec& dec = {}, int device = 0)
+        : LdpcDecOp("LdpcDecoderNode::new", code, dec, device) {}
+    Result<Frames> run(const Frames& in) { return decode(in); }
+};
+// on device-resident messages: DeframeNodeDev's records in, the decoded records in a DeviceBuf out (headers on the host)
+class LdpcDecoderNodeDev : public DeriveNode<LdpcDecoderNodeDev>, public Ports<LdpcDecOp::FramesDev, LdpcDecOp::FramesDev>, public OnStream<LdpcDecOp> {
+public:
+    explicit LdpcDecoderNodeDev(const LdpcCodeSpec& code, const LdpcDecSpec& dec = {}, int device = 0)
+        : OnStream(device, "LdpcDecoderNodeDev::new", code, dec, device) {}
+    Result<FramesDev> run(const FramesDev& in) { return decode_dev(in, *this); }
+};
+
 // Rate matching (comms_ratematch_*; additional nodes): puncturer, interleaver and scrambler of one frame format, the same
 // description on both sides of the link.  One description per direction, two shells each.
 struct RateMatchSpec {

@@ -1659,6 +1659,108 @@ class ViterbiNode(_Handle):
         return self._kernel_name(int(n_frames))
 
 
+# ------------------------------------------------------------------ LDPC coding
+def _ldpc_base(base, Z):
+    """The base matrix as a contiguous (mb, nb) int16 array: -1 is a zero block, b >= 0 the identity shifted by b."""
+    B = np.ascontiguousarray(base, dtype=np.int16)
+    if B.ndim != 2:
+        raise ValueError("base must be a matrix of mb x nb entries")
+    return B, int(Z)
+
+
+class LdpcEncoderNode(_Handle):
+    """Encoder of a quasi-cyclic LDPC code with a dual-diagonal parity part (comms_ldpcenc_*): `base` is the mb x nb base
+    matrix (-1: zero block; b >= 0: check z of block row i touches variable j Z + (z + b) mod Z), Z the lifting size.
+    Frame-major records of T = (nb - mb) Z packed bits (LSB first, each record ceil(bits / 8) bytes rounded up to 4) ->
+    records of N = nb Z coded bits [u | p_0 | ... | p_{mb-1}], all frames of a call in one launch, one wave per frame.
+    run() takes and returns uint8 arrays of shape (n_frames, frame bytes)."""
+    _prefix = "comms_ldpcenc"
+
+    def __init__(self, base, Z, device=0):
+        super().__init__()
+        B, self.Z = _ldpc_base(base, Z)
+        self.mb, self.nb = B.shape
+        self.n_info_bits, self.n_coded_bits = (self.nb - self.mb) * self.Z, self.nb * self.Z
+        check(lib().comms_ldpcenc_create(self.mb, self.nb, self.Z, _ptr(B), device, C.byref(self._h)))
+
+    @property
+    def in_frame_bytes(self):
+        return lib().comms_ldpcenc_in_frame_bytes(self._h)
+
+    @property
+    def out_frame_bytes(self):
+        return lib().comms_ldpcenc_out_frame_bytes(self._h)
+
+    def run(self, frames):
+        x = np.ascontiguousarray(frames, dtype=np.uint8)
+        if x.size % self.in_frame_bytes:
+            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
+        n_frames = x.size // self.in_frame_bytes
+        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
+        check(lib().comms_ldpcenc_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
+        return out
+
+    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
+        check(lib().comms_ldpcenc_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+
+    def kernel(self, n_frames):
+        """ "ldpc_encode_kernel wg=.. frames_per_wg=.. Z=.. grid=.. lds=.." for a call on n_frames frames."""
+        return self._kernel_name(int(n_frames))
+
+
+class LdpcDecoderNode(_Handle):
+    """Layered normalised min-sum decoder of LdpcEncoderNode's code family (comms_ldpcdec_*; any base matrix within the
+    limits): frame-major records of `record_llrs` f32 LLRs (positive = bit 0; the first N are used; 0 = exactly N) ->
+    records of T decoded bits, all frames of a call in one launch, one wave per frame, a frame's state in LDS.  Integer
+    arithmetic on q = clamp(rint(L * qscale), -127, 127) (NaN: 0) with a fixed schedule, messages scaled by norm16 / 16, at
+    most max_iters iterations with a stop at the first one whose hard decisions satisfy every check: the bits are those of
+    the definition exactly.  run() returns uint8 (n_frames, out_frame_bytes); with status=True also one int32 per frame:
+    the iterations run if the frame converged, -max_iters if it did not."""
+    _prefix = "comms_ldpcdec"
+
+    def __init__(self, base, Z, max_iters=20, norm16=12, record_llrs=0, qscale=1.0, device=0):
+        super().__init__()
+        B, self.Z = _ldpc_base(base, Z)
+        self.mb, self.nb = B.shape
+        self.n_info_bits, self.n_coded_bits, self.max_iters = (self.nb - self.mb) * self.Z, self.nb * self.Z, int(max_iters)
+        check(lib().comms_ldpcdec_create(self.mb, self.nb, self.Z, _ptr(B), self.max_iters, int(norm16), int(record_llrs), device,
+                                         C.byref(self._h)))
+        if qscale != 1.0:
+            self.set_quant_scale(qscale)
+
+    def set_quant_scale(self, qscale):
+        """q = clamp(rint(L * qscale), -127, 127), as ViterbiNode.set_quant_scale."""
+        check(lib().comms_ldpcdec_set_quant_scale(self._h, float(qscale)))
+        return self
+
+    @property
+    def in_frame_bytes(self):
+        return lib().comms_ldpcdec_in_frame_bytes(self._h)
+
+    @property
+    def out_frame_bytes(self):
+        return lib().comms_ldpcdec_out_frame_bytes(self._h)
+
+    def run(self, llr, status=False):
+        x = np.ascontiguousarray(llr, dtype=np.float32)
+        per = self.in_frame_bytes // 4
+        if x.size % per:
+            raise ValueError("the input must hold whole records of in_frame_bytes / 4 values")
+        n_frames = x.size // per
+        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
+        st = np.zeros(n_frames, np.int32)
+        check(lib().comms_ldpcdec_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None,
+                                      _ptr(st) if status and n_frames else None))
+        return (out, st) if status else out
+
+    def run_dev(self, llr_ptr, n_frames, bits_ptr, status_ptr=None, stream=0):
+        check(lib().comms_ldpcdec_run_dev(self._h, llr_ptr, int(n_frames), bits_ptr, status_ptr, stream))
+
+    def kernel(self, n_frames):
+        """ "ldpc_decode_kernel wg=.. waves=.. frames_per_wg=.. mb=.. nb=.. Z=.. edges=.. max_iters=.. grid=.. lds=.."."""
+        return self._kernel_name(int(n_frames))
+
+
 # ------------------------------------------------------------------ rate matching
 class _RateMatch(_Handle):
     """One frame format of comms_ratematch_*: n_coded coded bits, a puncturing `pattern` (0 / 1 per coded position, repeated;
