@@ -462,12 +462,18 @@ def _symmap():
     return maps + demaps
 
 
-# the pilot phase correction on and two training symbols everywhere; n64_long: two rounds of 64 symbols, the second ragged
+# the pilot phase correction on and two training symbols everywhere; n64_long: two rounds of 64 symbols, the second ragged.
+# n512_t17: 2 ROUND + 1 training symbols that all differ (ofdm_ref.training_case), so a workgroup that walks several items redoes
+# the training sum of three rounds per item, behind the top-of-loop barrier.  The demodulator alone: T + S = 26 symbols fill the
+# modulator's last wave, and its training symbols are the table's whatever the channel.
 OFDM_FORMATS = {
     "n64_long": ofdm_ref.Format(64, 16, ofdm_ref.map_80211a(), 70, 2, ofdm_ref.POLARITY, cpe=True, seed=11),
     "n512_cp36": ofdm_ref.FORMATS["n512_cp36"].but(cpe=True),
     "n1024_cp72": ofdm_ref.FORMATS["n1024_cp72"].but(cpe=True),
+    "n512_t17": ofdm_ref.TRAINING_FORMATS["n512_cp36_t17"].but(cpe=True),
 }
+OFDM_TRAINING = {"n512_t17": "n512_cp36_t17"}     # the formats whose input is ofdm_ref.training_case's, held to TRAINING_BOUND
+OFDM_DIRECTIONS = {"n512_t17": ("demod",)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -478,7 +484,7 @@ def _ofdm_frames(name, direction, cap):
 def _ofdm():
     # ofdm.hip takes its cap once for both directions: one label, the direction in `direction`
     return [Case("ofdm", "ofdm.hip", "%s-%s" % (d, name), dict(format=name, direction=d), functools.partial(_ofdm_frames, name, d))
-            for name in OFDM_FORMATS for d in ("mod", "demod")]
+            for name in OFDM_FORMATS for d in OFDM_DIRECTIONS.get(name, ("mod", "demod"))]
 
 
 CASES = _syncest() + _framesync() + _symsync() + _resample() + _channelizer() + _deframe() + _encoder() + _viterbi() + _ratematch() + _crc() + _symmap() + _ofdm()

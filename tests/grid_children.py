@@ -423,6 +423,9 @@ def ofdm(c):
             z = r.data_values(f, frames)
             if mod:
                 x, want, per, bound = z, r.ref_mod(f, z), f.sym_len, r.FFT_BOUND
+            elif cs.fmt["format"] in gc.OFDM_TRAINING:      # training symbols that all differ
+                x = r.training_case(gc.OFDM_TRAINING[cs.fmt["format"]], frames, cpe=True, rotate=True)[2]
+                want, per, bound = r.ref_demod(f, x), f.D, r.TRAINING_BOUND
             else:
                 x = r.through_channel(f, r.ref_mod(f, z), r.symbol_thetas(f))
                 want, per, bound = r.ref_demod(f, x), f.D, r.CHANNEL_BOUND

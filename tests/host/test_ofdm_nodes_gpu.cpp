@@ -5,7 +5,10 @@
 //      symbol's tail; OfdmModNodeDev gives the same bytes.
 //   2. source -> OfdmModNode -> OfdmDemodNode -> sink as a graph: the data values come back within the same bound (the training
 //      symbols see a flat channel, so H_k = N tx_scale); OfdmDemodNodeDev gives the same bytes.
+//   3. the two training symbols of every frame multiplied by different gains: H_k is their mean, so the data values come back
+//      divided by the mean gain -- which a sum that takes one training symbol twice does not give.
 // Needs an MI355X (libcomms_hip has no CPU fallback).
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -152,6 +155,38 @@ int main() {
         CHECK(back_dev.is_ok());
         if (back_dev.is_ok()) CHECK(back_dev.value().to_host() == *back);
     }
+    // 3. training symbols that differ: symbol t of every frame times g_t, so H_k = N tx_scale (g_0 + g_1) / 2 and the data values
+    //    come back divided by the mean gain (a sum that takes one of the two symbols twice gives 1 / g_0 or 1 / g_1 instead)
+    const Z gain[T] = {Z(1.3, 0.0), Z(1.0, 0.0) + 0.3 * std::polar(1.0, 2.4)};
+    std::vector<C> rx = *tx;
+    for (size_t f = 0; f < kFrames; ++f)
+        for (size_t t = 0; t < T; ++t)
+            for (size_t n = 0; n < SYM; ++n) {
+                C& v = rx[(f * (T + S) + t) * SYM + n];
+                const Z w = Z(v.real(), v.imag()) * gain[t];
+                v = C(static_cast<float>(w.real()), static_cast<float>(w.imag()));
+            }
+    const auto eq = OfdmDemodNode(spec).run(rx);
+    CHECK(eq.is_ok() && eq.value().size() == data.size());
+    if (!eq.is_ok() || eq.value().size() != data.size()) return 1;
+    const Z mean = (gain[0] + gain[1]) / 2.0;
+    worst = 0;
+    double twice = 1e9;   // how far the answer of a sum that takes one symbol twice would be
+    for (size_t i = 0; i < kFrames * S; ++i) {
+        std::vector<Z> want(D), w0(D), w1(D);
+        for (size_t d = 0; d < D; ++d) {
+            const Z v(data[i * D + d].real(), data[i * D + d].imag());
+            want[d] = v / mean;
+            w0[d] = v / gain[0];
+            w1[d] = v / gain[1];
+        }
+        const double e = rel_err(eq.value().data() + i * D, want);
+        worst = e > worst ? e : worst;
+        CHECK(e <= kBound);
+        twice = std::min(twice, std::min(rel_err(eq.value().data() + i * D, w0), rel_err(eq.value().data() + i * D, w1)));
+    }
+    std::printf("distinct training symbols: worst symbol %.3e (one symbol taken twice: %.3e)\n", worst, twice);
+    CHECK(twice >= 1e4 * kBound);
     CHECK(OfdmModNode(spec).run(std::vector<C>(S * D + 1)).is_err());   // not whole records
     bool threw = false;
     try {

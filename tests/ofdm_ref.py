@@ -94,6 +94,31 @@ CHANNEL_FORMATS = tuple(k for k, f in FORMATS.items() if f.n_train == 2 and f.n_
 CPE_FORMATS = tuple(k for k in CHANNEL_FORMATS if FORMATS[k].pilot_bins.size)               # check 4
 FRAME_COUNTS = (1, 5)
 
+
+def round_of(n_fft):
+    """Symbols ofdm_demod_kernel transforms at once: four waves of 1024 / N."""
+    return 4096 // n_fft
+
+
+def _training_formats():
+    """T = 1, 3, ROUND - 1, ROUND, ROUND + 1, 2 ROUND + 1 at every N (without duplicates), on the smallest S of that N: one slot,
+    a few, a round less one, a full round, a second round of one slot and a third.  n256_cp0 (prefix 0, no pilots) at ROUND + 1."""
+    out = {}
+    for base, s in (("n64_11a", 3), ("n128_cp9", 3), ("n256_cpN", 3), ("n512_cp36", 9), ("n1024_cp72", 2)):
+        rnd = round_of(FORMATS[base].n_fft)
+        for t in sorted({1, 3, rnd - 1, rnd, rnd + 1, 2 * rnd + 1}):
+            out["%s_t%d" % (base, t)] = FORMATS[base].but(n_syms=s, n_train=t)
+    out["n256_cp0_t17"] = FORMATS["n256_cp0"].but(n_syms=3, n_train=17)
+    return out
+
+
+# The training sum (tests/test_ofdm_ref.py, "sensitivity"): FORMATS has T = 2 everywhere and through_channel() gives both
+# training symbols of a frame the same samples, so no case above can tell which symbols the demodulator adds.  These can:
+# training_case() makes every received training symbol of a frame different from every other.
+TRAINING_FORMATS = _training_formats()
+TRAINING_CPE_FORMATS = tuple(k for k, f in TRAINING_FORMATS.items() if f.n_fft >= 512)   # also with the correction on, symbols rotated
+LONG_TRAINING_FORMATS = tuple(k for k, f in TRAINING_FORMATS.items() if f.n_train >= round_of(f.n_fft))   # the modulator's
+
 # ---------------------------------------------------------------- the definition, complex128
 
 
@@ -248,6 +273,104 @@ def channel_case(name, n_frames, cpe=False, rotate=False):
     return f, z, through_channel(f, ref_mod(f, z), symbol_thetas(f) if rotate else None)
 
 
+def training_gains(n_train):
+    """g_t = 1 + 0.3 e^{2.4 i t}: 0.7 <= |g_t| <= 1.3 and no two of a frame alike (2.4 t is no multiple of 2 pi)."""
+    return 1.0 + 0.3 * np.exp(2.4j * np.arange(n_train))
+
+
+TRAINING_NOISE = 10.0 ** (-30.0 / 20.0)   # the training symbols' noise, relative to their rms
+
+
+def training_case(name, n_frames, cpe=False, rotate=False, seed=0):
+    """(format, transmitted data values, received samples) behind the channel of channel_case, with training symbol t of every
+    frame multiplied by training_gains()[t] and seeded complex noise 30 dB below the training symbols added to them: the
+    received training symbols of a frame all differ.  Data symbols keep gain 1 and no noise; `seed` gives other frames."""
+    f = TRAINING_FORMATS[name].but(cpe=cpe)
+    z = data_values(f, n_frames, seed)
+    rx = through_channel(f, ref_mod(f, z), symbol_thetas(f) if rotate else None).astype(np.complex128)
+    tr = rx.reshape(n_frames, -1, f.sym_len)[:, : f.n_train, :]     # (a view: rx is contiguous)
+    rms = np.sqrt(np.mean(np.abs(tr) ** 2))
+    rng = np.random.default_rng(3000 + seed + f.n_fft + f.n_cp + f.n_train)
+    noise = (rng.standard_normal(tr.shape) + 1j * rng.standard_normal(tr.shape)) / np.sqrt(2)
+    tr[...] = tr * training_gains(f.n_train)[None, :, None] + TRAINING_NOISE * rms * noise
+    return f, z, rx.astype(np.complex64)
+
+
+def training_cases():
+    """[(name, cpe, rotate)] of the table: every format plain, N = 512 and 1024 also corrected and rotated as check 4 is."""
+    return [(k, False, False) for k in TRAINING_FORMATS] + [(k, True, True) for k in TRAINING_CPE_FORMATS]
+
+
+def training_mutants(f):
+    """[(label, slot, source)]: the wrong training sums a kernel could make.  Slot t (a) left out, (b) read from symbol t + 1,
+    (c) read from symbol t + 1024 / N, the same slot of the next wave's exchange buffer; both modulo T.  T = 1 has (a) alone."""
+    spw, T = 1024 // f.n_fft, f.n_train
+    out = [("omit", t, None) for t in range(T)]
+    out += [("next", t, (t + 1) % T) for t in range(T) if T > 1]
+    out += [("wave", t, (t + spw) % T) for t in range(T) if T > 1]
+    return out
+
+
+def mutant_samples(f, rx, slot, source):
+    """`rx` with training symbol `slot` of every frame replaced by symbol `source` (None: by zeros, which leaves it out of the
+    sum while the sum is still divided by T): the definition of a mutant is ref_demod of these samples."""
+    out = np.array(rx, np.complex64).reshape(rx.shape[0], -1, f.sym_len)
+    out[:, slot, :] = 0 if source is None else out[:, source, :]
+    return out.reshape(rx.shape)
+
+
+# Degenerate frames (the contract's "left as it is when |c| is 0 or not finite", and a training sum of zero): frame
+# DEGENERATE_FRAME of DEGENERATE_FRAMES is made degenerate, data symbol DEGENERATE_SYMBOL where it is one symbol's.
+DEGENERATE_FORMAT, DEGENERATE_FRAMES, DEGENERATE_FRAME, DEGENERATE_SYMBOL = "n64_11a_t3", 5, 2, 1
+DEGENERATE_KINDS = ("zero_symbol", "inf_sample", "zero_training")
+
+
+def degenerate_case(kind):
+    """(format, received samples) of training_case(DEGENERATE_FORMAT, correction on, symbols rotated) with one frame changed:
+    zero_symbol    every sample of one data symbol is 0: the pilot sum c is 0, the symbol stays unrotated, its values are 0;
+    inf_sample     one sample of one data symbol is +Inf: every bin of it, and c, is NaN or infinite, the rotation is skipped;
+    zero_training  every training sample is 0: the sum is 0 on every bin, Y / 0 is NaN or infinite in that frame."""
+    f, _, rx = training_case(DEGENERATE_FORMAT, DEGENERATE_FRAMES, cpe=True, rotate=True)
+    sym = rx.reshape(DEGENERATE_FRAMES, -1, f.sym_len)     # (a view)
+    if kind == "zero_symbol":
+        sym[DEGENERATE_FRAME, f.n_train + DEGENERATE_SYMBOL, :] = 0
+    elif kind == "inf_sample":
+        sym[DEGENERATE_FRAME, f.n_train + DEGENERATE_SYMBOL, f.n_cp + 5] = np.inf
+    elif kind == "zero_training":
+        sym[DEGENERATE_FRAME, : f.n_train, :] = 0
+    else:
+        raise ValueError(kind)
+    return f, rx
+
+
+def nonfinite(z):
+    """Per complex value: a part is NaN or infinite.  Whether a part is NaN or infinite depends on the order of the transform's
+    additions (Inf - Inf against Inf + x), so the definition and a kernel are compared by this mask, position by position."""
+    z = np.asarray(z)
+    return ~(np.isfinite(z.real) & np.isfinite(z.imag))
+
+
+def check_degenerate(f, kind, got, want, bound):
+    """The comparison of a degenerate call with ref_demod's `want`, shared by the CPU and the GPU test: NaN or infinite values at
+    the same positions, the degenerate symbol or frame as the contract says, and everything else within `bound` per symbol."""
+    n = DEGENERATE_FRAMES
+    g = np.asarray(got).reshape(n, f.n_syms, f.D)
+    w = np.asarray(want).reshape(n, f.n_syms, f.D)
+    bad = np.zeros((n, f.n_syms), bool)
+    if kind == "zero_training":
+        bad[DEGENERATE_FRAME, :] = True
+    else:
+        bad[DEGENERATE_FRAME, DEGENERATE_SYMBOL] = True
+    assert np.array_equal(nonfinite(g), nonfinite(w)), kind
+    if kind == "zero_symbol":
+        assert not nonfinite(g).any() and not g[bad].any() and not w[bad].any(), kind      # exactly zero, unrotated
+    else:
+        assert np.array_equal(nonfinite(g), np.broadcast_to(bad[:, :, None], g.shape)), kind
+    err = symbol_errors(g[~bad].reshape(1, -1), w[~bad].reshape(1, -1), f.D)
+    assert err.max() <= bound, (kind, worst(err))
+    return float(err.max())
+
+
 def symbol_errors(got, want, per_symbol):
     """||got - want||_2 / ||want||_2 per (frame, symbol) of `per_symbol` values each; float64 (n_frames, symbols)."""
     w = np.asarray(want, np.complex128)
@@ -269,6 +392,14 @@ FFT_BOUND = 1e-5
 # 2.65e-7 (n64_11a, 5 frames, correction on, symbols rotated).  The factor covers the kernels' different summation order; nothing here comes from a kernel.
 CHANNEL_MODEL_WORST = 2.66e-7
 CHANNEL_BOUND = 4 * CHANNEL_MODEL_WORST
+# The training-sum cases: the same measurement over training_cases() x FRAME_COUNTS (tests/test_ofdm_ref.py holds it likewise).
+# Measured worst: 2.706e-7 (n1024_cp72_t4, 5 frames, correction on, symbols rotated); n64_11a_t129, 129 f32 additions into
+# the sum, gives 2.69e-7: the sum's rounding errors average out in H, and the transform's error dominates at every T.
+TRAINING_MODEL_WORST = 2.71e-7
+TRAINING_BOUND = 4 * TRAINING_MODEL_WORST
+# Every mutant of training_mutants() moves ref_demod's output by at least this many bounds in some symbol (the issue's factor;
+# tests/test_ofdm_ref.py prints what each case achieves)
+TRAINING_SENSITIVITY = 10.0
 
 # ---------------------------------------------------------------- the link of check 5 (16-QAM)
 LINK_FORMAT = "n64_11a"

@@ -1,7 +1,9 @@
 """OfdmModNode and OfdmDemodNode (ofdm.hip) on an MI355X against tests/ofdm_ref.py, the complex128 definition of
 include/comms_hip.h's "OFDM modulator and demodulator".  Formats, inputs and bounds are ofdm_ref's (tests/test_ofdm_ref.py
 holds them to their rules); no bound here comes from a kernel's output.  Every figure is printed before it is asserted."""
+import functools
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -12,6 +14,11 @@ import ofdm_ref as r
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GUARD = 256   # bytes behind a device output, as in tests/test_gpu_symmap.py
+
+
+def fields(name):
+    return {a: int(b) for a, b in re.findall(r"(\w+)=(\d+)", name)}
 
 
 @pytest.fixture(scope="module")
@@ -95,6 +102,98 @@ def test_pilot_phase_correction(c, name, n_frames):
     th = r.symbol_thetas(g)[g.n_train:]
     want = z.reshape(n_frames, g.n_syms, g.D) * np.exp(1j * th)[None, :, None]
     assert r.symbol_errors(off, want.reshape(n_frames, -1), g.D).max() <= 1e-5
+
+
+@functools.lru_cache(maxsize=None)
+def training(name, n_frames, cpe, seed=0):
+    """(format, received samples, ref_demod of them) of a training-sum case, computed once and shared read-only."""
+    f, _, rx = r.training_case(name, n_frames, cpe, cpe, seed)
+    want = r.ref_demod(f, rx)
+    rx.setflags(write=False)
+    want.setflags(write=False)
+    return f, rx, want
+
+
+TRAINING_CASES = [(name, cpe) for name, cpe, _ in r.training_cases()]
+
+
+@pytest.mark.parametrize("n_frames", r.FRAME_COUNTS)
+@pytest.mark.parametrize("name,cpe", TRAINING_CASES)
+def test_demodulator_sums_every_training_symbol(c, name, cpe, n_frames):
+    """T = 1 ... 2 ROUND + 1 training symbols that all differ: tests/test_ofdm_ref.py shows that a sum which leaves a slot out,
+    or reads a neighbouring slot or the next wave's for it, is at least 10 bounds off in every one of these cases."""
+    f, rx, want = training(name, n_frames, cpe)
+    _, dem = nodes(c, f)
+    got = dem.run(rx)
+    err, frame, sym = r.worst(r.symbol_errors(got, want, f.D))
+    print("%s cpe %d frames %d: worst symbol %.3e (frame %d symbol %d), bound %.3e  [%s]" %
+          (name, cpe, n_frames, err, frame, sym, r.TRAINING_BOUND, dem.kernel(n_frames)))
+    assert err <= r.TRAINING_BOUND, (name, err, frame, sym)
+    if n_frames > 2:
+        assert split_runs(dem, rx).tobytes() == got.tobytes()
+    # other frames on the same handle, then the first again: nothing of a call (1 / H_k, the exchange buffers) reaches the next
+    _, rx2, want2 = training(name, n_frames, cpe, seed=1)
+    err2 = float(r.symbol_errors(dem.run(rx2), want2, f.D).max())
+    print("    other frames: worst symbol %.3e" % err2)
+    assert err2 <= r.TRAINING_BOUND, (name, err2)
+    assert dem.run(rx).tobytes() == got.tobytes()
+
+
+@pytest.mark.parametrize("n_frames", r.FRAME_COUNTS)
+@pytest.mark.parametrize("name,cpe", TRAINING_CASES)
+def test_demodulator_device_call_writes_its_records_and_no_more(c, name, cpe, n_frames):
+    f, rx, want = training(name, n_frames, cpe)
+    _, dem = nodes(c, f)
+    nbytes = 8 * n_frames * f.data_syms
+    d_in = c.DeviceBuf(rx.nbytes).upload(rx)
+    d_out = c.DeviceBuf(nbytes + GUARD).upload(np.full(nbytes + GUARD, 0xFF, np.uint8))
+    dem.run_dev(d_in.ptr, n_frames, d_out.ptr)
+    raw = d_out.download(np.uint8, nbytes + GUARD)
+    assert np.all(raw[nbytes:] == 0xFF), "the guard region was written"
+    assert not np.any(raw[:nbytes].view(np.uint32) == 0xFFFFFFFF), "an output value was not written"
+    got = raw[:nbytes].view(np.complex64).reshape(n_frames, -1)
+    err = float(r.symbol_errors(got, want, f.D).max())
+    print("%s cpe %d frames %d: worst symbol %.3e, bound %.3e" % (name, cpe, n_frames, err, r.TRAINING_BOUND))
+    assert err <= r.TRAINING_BOUND, (name, err)
+    assert dem.run(rx).tobytes() == got.tobytes()
+
+
+@pytest.mark.parametrize("n_frames", r.FRAME_COUNTS)
+@pytest.mark.parametrize("name", r.LONG_TRAINING_FORMATS)
+def test_modulator_with_long_training(c, name, n_frames):
+    """T of a round or more: the block rule gives a frame blocks of whole rounds, and the first of them holds training symbols
+    only (block <= T, asserted from kernel() for every call of one frame)."""
+    f = r.TRAINING_FORMATS[name]
+    mod, _ = nodes(c, f)
+    assert (mod.data_syms, mod.frame_samples) == (f.data_syms, f.frame_samples)
+    z = r.data_values(f, n_frames)
+    got = mod.run(z)
+    k = fields(mod.kernel(n_frames))
+    err, frame, sym = r.worst(r.symbol_errors(got, r.ref_mod(f, z), f.sym_len))
+    print("%s frames %d: worst symbol %.3e (frame %d symbol %d)  [%s]" % (name, n_frames, err, frame, sym, mod.kernel(n_frames)))
+    assert err <= r.FFT_BOUND, (name, err, frame, sym)
+    s = got.reshape(n_frames, -1, f.sym_len)
+    assert s[..., : f.n_cp].tobytes() == s[..., f.sym_len - f.n_cp:].tobytes()
+    assert (k["block"], k["blocks"]) == r.block_rule(f.n_fft, f.n_train + f.n_syms, n_frames, k["max_grid"]) and k["train"] == f.n_train
+    if n_frames == 1:
+        assert k["block"] == r.round_of(f.n_fft) <= f.n_train and k["blocks"] >= 2, k      # block 0: training symbols only
+    else:
+        assert split_runs(mod, z).tobytes() == got.tobytes()
+
+
+@pytest.mark.parametrize("kind", r.DEGENERATE_KINDS)
+def test_degenerate_frames_stay_in_their_frame(c, kind):
+    """include/comms_hip.h: a symbol whose pilot sum is 0 or not finite is left unrotated (all zeros; NaN or infinite values);
+    a frame whose training sum is 0 is NaN or infinite throughout.  One frame of five is degenerate: the others, and in the
+    first two kinds the frame's other symbols, are held to the bound."""
+    f, rx = r.degenerate_case(kind)
+    with np.errstate(all="ignore"):
+        want = r.ref_demod(f, rx)
+    _, dem = nodes(c, f)
+    got = dem.run(rx)
+    err = r.check_degenerate(f, kind, got, want, r.TRAINING_BOUND)
+    print("%s: every other symbol within %.3e, bound %.3e  [%s]" % (kind, err, r.TRAINING_BOUND, dem.kernel(r.DEGENERATE_FRAMES)))
+    assert split_runs(dem, rx).tobytes() == got.tobytes()
 
 
 def test_link_16qam_bits_are_exact(c):

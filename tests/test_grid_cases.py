@@ -123,6 +123,27 @@ def test_ofdm_cases_reach_every_transform_and_a_ragged_group():
         assert per_frame % (1024 // f.n_fft) or f.n_fft == 1024              # ... and the last group of a block within a wave
 
 
+def test_ofdm_training_case_redoes_a_sum_of_three_rounds_per_item():
+    """n512_t17: 2 ROUND + 1 training symbols that all differ, on the demodulator, whose workgroups walk four or more items and
+    sum the training spectra anew for each.  The conditions TRAINING_BOUND rests on hold on these calls: the f32 model is within
+    a quarter of the bound of the definition, and every wrong training sum moves a symbol by ten bounds or more."""
+    import ofdm_ref as r
+
+    assert gc.OFDM_TRAINING == {"n512_t17": "n512_cp36_t17"} and gc.OFDM_DIRECTIONS == {"n512_t17": ("demod",)}
+    (cs,) = [cs for cs in gc.cases_of("ofdm") if cs.fmt["format"] == "n512_t17"]
+    f = gc.OFDM_FORMATS["n512_t17"]
+    assert (f.n_fft, f.n_train, f.cpe) == (512, 2 * r.round_of(512) + 1, True) and cs.fmt["direction"] == "demod"
+    for cap in gc.CAPS:
+        frames = cs.size(cap)
+        g, _, rx = r.training_case("n512_cp36_t17", frames, cpe=True, rotate=True)
+        assert g.frame_samples == f.frame_samples and gc.walk(cs, cap).passes >= gc.MIN_PASSES
+        want = r.ref_demod(f, rx)
+        assert r.symbol_errors(r.model_demod(f, rx), want, f.D).max() <= r.TRAINING_MODEL_WORST, (cap, frames)
+        for _, t, src in r.training_mutants(f):
+            moved = r.symbol_errors(r.ref_demod(f, r.mutant_samples(f, rx, t, src)), want, f.D)
+            assert moved.max(axis=1).min() >= r.TRAINING_SENSITIVITY * r.TRAINING_BOUND, (cap, t, src)      # in every frame
+
+
 def test_rate_matching_walks_take_every_regime():
     """RmWalk by its additions equals the division at every item of every case, and the cases meet its four regimes: no whole
     frame per stride, whole frames and a remainder, no remainder, and a lane that carries on every step -- one of them on
