@@ -22,9 +22,10 @@ MAX_MB, MAX_NB, MAX_Z, MAX_ROW = 32, 64, 128, 32
 
 
 # ------------------------------------------------------------------ base matrices
-def make_base(mb, nb, Z, seed, colw=3):
+def make_base(mb, nb, Z, seed, colw=3, r=None, s=None, t=None):
     """(mb, nb) int16 of the encoder's form: every information column has min(colw, mb) random rows and shifts, every row at
-    least 2 information entries; column kb has s in rows 0 and mb-1 and t in a middle row r; then the double diagonal of 0."""
+    least 2 information entries; column kb has s in rows 0 and mb-1 and t in a middle row r; then the double diagonal of 0.
+    r, s and t are drawn unless given (the draws are made either way: the rest of the matrix does not depend on them)."""
     assert 3 <= mb <= MAX_MB and mb < nb <= MAX_NB and 2 <= Z <= MAX_Z
     rng = np.random.default_rng(seed)
     kb = nb - mb
@@ -36,8 +37,9 @@ def make_base(mb, nb, Z, seed, colw=3):
         while np.count_nonzero(B[i, :kb] >= 0) < 2:
             free = np.flatnonzero(B[i, :kb] < 0)
             B[i, rng.choice(free)] = rng.integers(0, Z)
-    r = int(rng.integers(1, mb - 1))
-    s, t = int(rng.integers(0, Z)), int(rng.integers(0, Z))
+    drawn = int(rng.integers(1, mb - 1)), int(rng.integers(0, Z)), int(rng.integers(0, Z))
+    r, s, t = (d if given is None else int(given) for given, d in zip((r, s, t), drawn))
+    assert 1 <= r <= mb - 2 and 0 <= s < Z and 0 <= t < Z
     B[0, kb] = B[mb - 1, kb] = s
     B[r, kb] = t
     for i in range(mb - 1):
@@ -46,13 +48,20 @@ def make_base(mb, nb, Z, seed, colw=3):
     return B
 
 
-def random_base(mb, nb, Z, seed):
-    """Any matrix within the limits, without the encoder's structure: 2 ... 6 entries per row at random columns."""
+def random_base(mb, nb, Z, seed, deg=None, full=None):
+    """Any matrix within the limits, without the encoder's structure: 2 ... 6 entries per row at random columns; or `deg`
+    entries (one number, or one per row, up to 32); with `full`, column `full` has an entry in every block row."""
     assert 1 <= mb <= MAX_MB and mb < nb <= MAX_NB and 2 <= Z <= MAX_Z
     rng = np.random.default_rng(seed)
     B = np.full((mb, nb), -1, np.int16)
     for i in range(mb):
-        cols = rng.choice(nb, size=int(rng.integers(2, min(nb, 6) + 1)), replace=False)
+        d = int(rng.integers(2, min(nb, 6) + 1)) if deg is None else int(deg if np.isscalar(deg) else deg[i])
+        assert 2 <= d <= min(nb, MAX_ROW)
+        if full is None:
+            cols = rng.choice(nb, size=d, replace=False)
+        else:
+            others = np.delete(np.arange(nb), full)
+            cols = np.concatenate([[full], rng.choice(others, size=d - 1, replace=False)])
         B[i, cols] = rng.integers(0, Z, cols.size)
     return B
 
@@ -127,8 +136,17 @@ def ref_encode(bits, B, Z):
 
 
 # ------------------------------------------------------------------ the decoder
-def ref_decode(q, B, Z, max_iters=20, norm16=12):
-    """Layered normalised min-sum of the header on quantised LLRs q (frames, >= N): (bits (frames, T) uint8, status int32)."""
+RULES = ("idx_last", "no_clamp", "mask32", "xor_passes")
+
+
+def ref_decode(q, B, Z, max_iters=20, norm16=12, rules=()):
+    """Layered normalised min-sum of the header on quantised LLRs q (frames, >= N): (bits (frames, T) uint8, status int32).
+    `rules` names deliberate departures from the header, each a mistake a kernel could make, for the tests that ask whether
+    the shared cases would see it (tests/test_ldpc_ref.py); no rule is the definition:
+      idx_last    idx is the LAST edge at the minimum         no_clamp    |Q| is not clamped at 127
+      mask32      a row of 32 edges flips no sign when its parity is odd (a sign mask built by a 32-bit shift by 32)
+      xor_passes  the stopping test XORs the parities of checks z and z + 64 (one lane's two passes) where it must OR them"""
+    assert set(rules) <= set(RULES)
     B = np.asarray(B)
     mb, nb = B.shape
     N, T = nb * Z, (nb - mb) * Z
@@ -144,14 +162,18 @@ def ref_decode(q, B, Z, max_iters=20, norm16=12):
         for i, v in enumerate(V):
             deg = v.shape[0]
             Q = P[act][:, v] - R[i][act]                                     # (act, deg, Z)
-            Qc = np.clip(Q, -127, 127)
+            Qc = Q if "no_clamp" in rules else np.clip(Q, -127, 127)
             a = np.abs(Qc)
             idx = np.argmin(a, axis=1)                                       # the first edge that attains the minimum
+            if "idx_last" in rules:
+                idx = deg - 1 - np.argmin(a[:, ::-1], axis=1)
             m1 = np.min(a, axis=1)
             first = np.arange(deg)[None, :, None] == idx[:, None, :]
             m2 = np.min(np.where(first, 1 << 20, a), axis=1)
             neg = Qc < 0
             par = np.bitwise_xor.reduce(neg, axis=1)
+            if "mask32" in rules and deg == 32:
+                par = np.zeros_like(par)
             mag = (int(norm16) * np.where(first, m2[:, None, :], m1[:, None, :])) >> 4
             Rn = np.where(par[:, None, :] ^ neg, -mag, mag)
             R[i][act] = Rn
@@ -161,10 +183,13 @@ def ref_decode(q, B, Z, max_iters=20, norm16=12):
         x = P[act] < 0
         ok = np.ones(act.size, bool)
         for v in V:
-            ok &= ~np.any(np.bitwise_xor.reduce(x[:, v], axis=1), axis=1)
+            odd = np.bitwise_xor.reduce(x[:, v], axis=1)                     # (act, Z)
+            if "xor_passes" in rules and Z > 64:
+                odd = odd[:, :64] ^ np.pad(odd[:, 64:], ((0, 0), (0, 128 - Z)))
+            ok &= ~np.any(odd, axis=1)
         status[act[ok]] = it
         act = act[~ok]
-    assert np.all(np.abs(P) <= 127 * 33)
+    assert rules or np.all(np.abs(P) <= 127 * 33)
     return (P[:, :T] < 0).astype(np.uint8), status
 
 
@@ -186,10 +211,96 @@ NOISY = {"A": (24, 0.5, 4.0), "B": (24, -0.5, 4.0), "C": (24, 2.5, 2.0), "D": (2
 NOISY_SEED = {"A": 0, "B": 0, "C": 0, "D": 0, "E": 0, "F": 0, "G": 0}
 
 
+# ------------------------------------------------------------------ the corner table: shapes off the formats above
+# The library's own sizes (ldpc.hip: comms_ldpcdec_create, ld_pack), restated: what decides the workgroup and the packing.
+WG_LDS, MAX_WAVES = 64 * 1024, 4
+
+
+def frame_lds(mb, nb, Z):
+    """Bytes of LDS of one frame in the decoder: P as int16, padded to 8, and one 8-byte record per check."""
+    return (2 * nb * Z + 7) // 8 * 8 + 8 * mb * Z
+
+
+def frames_per_wg(mb, nb, Z):
+    """As many frames as fit 64 KiB beside the edge table (128 bytes per block row), 1 ... 4: the waves of a workgroup."""
+    return max(1, min(MAX_WAVES, (WG_LDS - 128 * mb) // frame_lds(mb, nb, Z)))
+
+
+def out_words(bits):
+    return record_bytes(bits) // 4
+
+
+def chunks(bits):
+    """64-bit ballots of a record: a lane keeps one, the wave stores after chunk 63 (one full round) and after the last."""
+    return (out_words(bits) + 1) // 2
+
+
+def pack_model(bits, stale=False):
+    """ld_pack restated lane by lane: (frames, b) 0 / 1 -> (frames, out_words(b)) uint32.  stale=True is the mistake the
+    second round invites: a lane keeps only the ballot of chunk == lane, so words of later rounds repeat the first round's."""
+    bits = np.asarray(bits, np.uint8)
+    frames, b = bits.shape
+    words, n = out_words(b), chunks(b)
+    padded = np.zeros((frames, 64 * n), np.uint8)
+    padded[:, :b] = bits
+    out = np.zeros((frames, words), np.uint32)
+    keep = np.zeros((frames, 64), np.uint64)
+    weights = np.uint64(1) << np.arange(64, dtype=np.uint64)
+    for c in range(n):
+        ballot = (padded[:, 64 * c: 64 * c + 64].astype(np.uint64) * weights).sum(axis=1, dtype=np.uint64)
+        if not stale or c < 64:
+            keep[:, c & 63] = ballot
+        if (c & 63) == 63 or c + 1 == n:
+            for lane in range(64):
+                w = 2 * ((c & ~63) + lane)
+                if w < words:
+                    out[:, w] = (keep[:, lane] & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+                if w + 1 < words:
+                    out[:, w + 1] = (keep[:, lane] >> np.uint64(32)).astype(np.uint32)
+    return out
+
+
+# name, shape, seed, encoder form?, the builder's arguments, and the properties the format is in the table for: every one of
+# them is recomputed from the matrix and the formulas above by tests/test_ldpc_ref.py (test_corner_table_meets_its_properties)
+Corner = namedtuple("Corner", "name mb nb Z seed encoder build props")
+CORNERS = {f.name: f for f in (
+    # decoder only (random_base)
+    Corner("fpw3", 4, 64, 128, 31, False, dict(deg=32), ("fpw=3", "deg=32", "Z>64", "dec_partial_round")),   # T = 7680: 120 chunks
+    Corner("fpw2", 8, 64, 128, 32, False, dict(), ("fpw=2", "Z>64", "dec_second_round")),                   # T = 7168: 112 chunks
+    Corner("z65", 2, 64, 65, 33, False, dict(deg=32), ("fpw=4", "deg=32", "Z=65", "mb=2")),             # second pass: one live lane
+    Corner("mb1", 1, 33, 127, 34, False, dict(deg=32), ("deg=32", "Z=127", "mb=1", "dec_odd_words")),     # T = 4064: 127 words
+    Corner("least", 1, 2, 2, 35, False, dict(deg=2), ("deg=2", "Z=2", "mb=1", "nb=2", "dec_odd_words")),     # every limit at its minimum
+    Corner("col32", 32, 40, 16, 36, False, dict(full=3), ("fpw=4", "full_column", "mb=32")),                 # a variable in 32 layers
+    # encoder and decoder (make_base)
+    Corner("r1", 5, 12, 27, 41, True, dict(r=1, s=0, t=26), ("r=1", "s=0", "t=Z-1")),
+    Corner("rlast", 6, 14, 33, 42, True, dict(r=4, s=32, t=0), ("r=mb-2", "s=Z-1", "t=0")),
+    Corner("encz2", 4, 10, 2, 43, True, dict(), ("Z=2",)),
+    Corner("encz65", 4, 12, 65, 44, True, dict(), ("Z=65",)),
+    Corner("enc5080", 8, 40, 127, 45, True, dict(), ("Z=127", "enc_partial_round")),                          # N = 5080: 159 words
+)}
+ENCODER_CORNERS = [n for n, f in CORNERS.items() if f.encoder]
+# as NOISY: frames (more than a workgroup holds and no multiple of it), Es/N0 in dB, quantiser scale.  Dense rows do not
+# converge at the formats' Es/N0, so each point is placed where its call is mixed (test_corner_noisy_cases_are_mixed)
+NOISY.update({"fpw3": (7, 5.0, 2.0), "fpw2": (5, 5.0, 4.0), "z65": (9, 6.0, 2.0), "mb1": (9, 5.5, 2.0), "least": (9, -5.5, 4.0),
+              "col32": (9, -2.0, 4.0), "r1": (9, -1.0, 4.0), "rlast": (9, -1.0, 4.0), "encz2": (9, -2.0, 4.0), "encz65": (9, 0.0, 4.0),
+              "enc5080": (7, 2.0, 4.0)})
+NOISY_SEED.update({"fpw3": 2, "fpw2": 2, "z65": 0, "mb1": 2, "least": 2, "col32": 1, "r1": 0, "rlast": 1, "encz2": 1, "encz65": 1, "enc5080": 2})
+# the further message scales, and the longest run: planted errors that 255 iterations at norm16 = 1 never clear (Z = 2: cheap)
+CORNER_NORMS = {"z65": 5, "rlast": 11}
+CORNER_255 = "encz2"
+
+
+def format_of(name):
+    return FORMATS[name] if name in FORMATS else CORNERS[name]
+
+
 @functools.lru_cache(maxsize=None)
 def base_of(name):
-    f = FORMATS[name]
-    B = make_base(f.mb, f.nb, f.Z, f.seed) if f.encoder else random_base(f.mb, f.nb, f.Z, f.seed)
+    f = format_of(name)
+    if name in CORNERS:
+        B = (make_base if f.encoder else random_base)(f.mb, f.nb, f.Z, f.seed, **f.build)
+    else:
+        B = make_base(f.mb, f.nb, f.Z, f.seed) if f.encoder else random_base(f.mb, f.nb, f.Z, f.seed)
     B.setflags(write=False)
     return B
 
@@ -203,7 +314,9 @@ def planted_bits(fmt):
     One wrong bit, two in one block column, two in different block columns, two parity bits, none -- and, for Z > 64, pairs
     (v, (v + 64) mod Z) of block column 0: both wrong bits meet every block row of that column in checks 64 apart, the two
     checks one lane holds in its two passes, for every v at Z = 128 and for the v that do not wrap at Z = 81; two pairs on the
-    double diagonal, whose shifts are 0, do so at any Z > 64."""
+    double diagonal, whose shifts are 0, do so at any Z > 64.  The corner formats have corner_planted's frames."""
+    if fmt in CORNERS:
+        return corner_planted(fmt)
     f = FORMATS[fmt]
     Z, T = f.Z, (f.nb - f.mb) * f.Z
     frames = [(5 % Z,), (1, 1 + Z // 2), (2, Z + 3), (T + 1, T + Z - 1), ()]
@@ -215,22 +328,68 @@ def planted_bits(fmt):
     return frames
 
 
+def lane_mates(B, Z, most=3):
+    """Pairs of variables (v, w) of one block column whose unsatisfied checks are z and z + 64 of the same block row, in every
+    block row the column has an entry in: the two checks one lane holds in its two passes.  Found from the matrix, for any
+    shifts: with entry b the checks of variable j Z + a and of its partner 64 further on (mod Z) are (a - b) mod Z and that
+    plus 64 mod Z, lane mates when the first is below Z - 64."""
+    B = np.asarray(B)
+    pairs = []
+    for j in range(B.shape[1]):
+        shifts = B[:, j][B[:, j] >= 0].astype(int)
+        for a in range(Z if shifts.size and Z > 64 else 0):
+            if all(min((a - b) % Z, (a + 64 - b) % Z) < Z - 64 and abs((a - b) % Z - (a + 64 - b) % Z) == 64 for b in shifts):
+                pairs.append((j * Z + a, j * Z + (a + 64) % Z))
+                break
+        if len(pairs) == most:
+            break
+    return pairs
+
+
+def corner_planted(fmt):
+    """planted_bits for a corner format: the same five kinds of frame with every index inside the (possibly tiny) word, for
+    Z > 64 up to three lane_mates pairs, and single wrong bits until the count is more than a workgroup holds and no multiple of it."""
+    f = CORNERS[fmt]
+    Z, N, T = f.Z, f.nb * f.Z, (f.nb - f.mb) * f.Z
+    frames = [(5 % Z,), (1, 1 + max(Z // 2, 1)), (2 % Z, Z + 3 % Z), (T + 1, T + Z - 1), ()]
+    frames = [tuple(sorted({v % N for v in wrong})) for wrong in frames]
+    frames += [tuple(sorted(p)) for p in lane_mates(base_of(fmt), Z)]
+    fpw = frames_per_wg(f.mb, f.nb, Z)
+    while len(frames) <= fpw or len(frames) % fpw == 0:
+        frames.append(((7 * len(frames)) % N,))
+    return frames
+
+
 def make_case(fmt, kind, frames=None, qscale=None, max_iters=20, norm16=12):
-    f = FORMATS[fmt]
+    f = format_of(fmt)
     N = f.nb * f.Z
     n_noisy, _, q_noisy = NOISY[fmt]
     if kind == "planted":
         assert frames is None
         frames = len(planted_bits(fmt))
-    frames = (n_noisy if kind in ("noisy", "wide") else min(n_noisy, 3)) if frames is None else frames
+    few = n_noisy if fmt in CORNERS else min(n_noisy, 3)                    # a corner call never fits one workgroup
+    frames = (n_noisy if kind in ("noisy", "wide") else few) if frames is None else frames
     qscale = (q_noisy if kind in ("noisy", "wide") else 1.0) if qscale is None else qscale
     return Case(fmt, frames, kind, N + (37 if kind == "wide" else 0), float(qscale), max_iters, norm16)
+
+
+def corner_cases(fmt, kind):
+    """The cases of one corner format and kind, for the GPU test and for the tests that ask what these cases can see: the
+    formats' iteration limits and scales, the format's further scale, norm16 = 1 under planted errors (255 iterations once),
+    quantiser scales that move the clamp under the special values."""
+    norms = (12, 16) + ((CORNER_NORMS[fmt],) if fmt in CORNER_NORMS else ())
+    cases = [make_case(fmt, kind, max_iters=it, norm16=nm) for it in (1, 2, 20) for nm in norms]
+    if kind == "planted":
+        cases += [make_case(fmt, kind, max_iters=it, norm16=1) for it in (1, 2, 20) + ((255,) if fmt == CORNER_255 else ())]
+    if kind == "special":
+        cases += [make_case(fmt, kind, qscale=qs) for qs in (-2.5, 0.0, 0.03)]
+    return cases
 
 
 @functools.lru_cache(maxsize=None)
 def case_input(fmt, frames, kind):
     """(sent bits or None, LLR records f32 (frames, record_llrs)); fixed by the format, the frame count and the kind."""
-    f = FORMATS[fmt]
+    f = format_of(fmt)
     B, Z = base_of(fmt), f.Z
     N, T = f.nb * Z, (f.nb - f.mb) * Z
     rng = np.random.default_rng([f.seed, frames, KINDS.index(kind), NOISY_SEED[fmt]])
@@ -264,7 +423,7 @@ def case_input(fmt, frames, kind):
 @functools.lru_cache(maxsize=None)
 def case_data(cs):
     """(sent bits or None, LLR records, reference bits, reference status) of a case; fixed by the case."""
-    f = FORMATS[cs.fmt]
+    f = format_of(cs.fmt)
     sent, llr = case_input(cs.fmt, cs.frames, cs.kind)
     q = ref_quantise(llr[:, : f.nb * f.Z], cs.qscale)
     bits, status = ref_decode(q, base_of(cs.fmt), f.Z, cs.max_iters, cs.norm16)

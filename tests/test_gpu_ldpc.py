@@ -26,7 +26,7 @@ def c():
 
 
 def decoder_of(c, cs):
-    f = lr.FORMATS[cs.fmt]
+    f = lr.format_of(cs.fmt)
     return c.LdpcDecoderNode(lr.base_of(cs.fmt), f.Z, cs.max_iters, cs.norm16, cs.record_llrs, cs.qscale)
 
 
@@ -49,7 +49,7 @@ def decode_dev(c, node, llr):
 
 
 def check_case(c, cs, node=None):
-    f = lr.FORMATS[cs.fmt]
+    f = lr.format_of(cs.fmt)
     T = (f.nb - f.mb) * f.Z
     _, llr, bits, status = lr.case_data(cs)
     node = decoder_of(c, cs) if node is None else node
@@ -144,6 +144,68 @@ def test_a_second_call_on_the_handle_equals_a_fresh_handle(c, fmt):
     node = check_case(c, first)
     check_case(c, second, node)
     check_case(c, third, node)
+    check_case(c, first, node)
+
+
+# ------------------------------------------------------------------ 5b. the corner table: shapes off the formats A ... G
+@pytest.mark.parametrize("kind", lr.KINDS)
+@pytest.mark.parametrize("fmt", list(lr.CORNERS))
+def test_corner_decoder_is_the_reference_bit_for_bit(c, fmt, kind):
+    """Workgroups of 2 and 3 waves, records of more than 64 chunks, full sign masks over two passes, Z = 2, 65 and 127, one and
+    two block rows, a variable in 32 layers: tests/test_ldpc_ref.py says which format is which and what each can see."""
+    f = lr.CORNERS[fmt]
+    fpw = lr.frames_per_wg(f.mb, f.nb, f.Z)
+    assert {2, 3} <= {lr.frames_per_wg(g.mb, g.nb, g.Z) for g in lr.CORNERS.values()}
+    for cs in lr.corner_cases(fmt, kind):
+        node = check_case(c, cs)
+        k = fields(node.kernel(cs.frames))
+        assert k["frames_per_wg"] == fpw and k["wg"] == 64 * fpw and k["grid"] == -(-cs.frames // fpw) > 1, (cs, k)
+        assert cs.frames % fpw                                             # the last workgroup is partly empty
+    if kind == "planted" and fmt == lr.CORNER_255:
+        assert np.count_nonzero(lr.case_data(cs)[3] == -255) == cs.frames - 1
+
+
+@pytest.mark.parametrize("fmt", lr.ENCODER_CORNERS)
+def test_corner_encoder_is_the_reference_bit_for_bit(c, fmt):
+    """r = 1 and r = mb - 2, s and t at 0 and Z - 1, Z = 2 and 65, and a record of 159 words: a partial second round of the packing."""
+    f = lr.CORNERS[fmt]
+    B, Z = lr.base_of(fmt), f.Z
+    N, T = f.nb * Z, (f.nb - f.mb) * Z
+    node = c.LdpcEncoderNode(B, Z)
+    fin, fout = node.in_frame_bytes, node.out_frame_bytes
+    assert fin == lr.record_bytes(T) and fout == lr.record_bytes(N) == 4 * lr.out_words(N)
+    fpw = fields(node.kernel(1))["frames_per_wg"]
+    rng = np.random.default_rng(f.seed)
+    for frames in (2, fpw + 1, 2 * fpw + 3):
+        sent = rng.integers(0, 2, (frames, T), dtype=np.uint8)
+        records = lr.pack_records(sent)
+        dirty = records | ~lr.pack_records(np.ones((frames, T), np.uint8))   # bits from T on do not count
+        want = lr.pack_records(lr.ref_encode(sent, B, Z))
+        d_in = c.DeviceBuf(frames * fin).upload(dirty)
+        d_out = c.DeviceBuf(frames * fout + GUARD).upload(np.full(frames * fout + GUARD, 0xFF, np.uint8))
+        node.run_dev(d_in.ptr, frames, d_out.ptr)
+        raw = d_out.download(np.uint8, frames * fout + GUARD)
+        assert np.array_equal(raw[: frames * fout].reshape(frames, fout), want), (fmt, frames)
+        assert np.all(raw[frames * fout:] == 0xFF)
+        assert node.run(records).tobytes() == want.tobytes()               # host pointers
+        k = fields(node.kernel(frames))
+        assert k["grid"] * k["frames_per_wg"] >= frames and k["Z"] == Z and k["lds"] <= 160 * 1024
+
+
+@pytest.mark.parametrize("fmt", ["fpw2", "fpw3"])
+def test_a_second_call_on_a_corner_handle_equals_a_fresh_handle(c, fmt):
+    """As section 5 with workgroups of 2 and 3 waves: more frames first, then fewer and different ones, then the first again."""
+    first = lr.make_case(fmt, "planted", norm16=1)
+    second = lr.make_case(fmt, "noisy")
+    third = lr.make_case(fmt, "zeros", frames=2, qscale=second.qscale)
+    assert first.frames > second.frames > third.frames and (first.max_iters, first.record_llrs) == (second.max_iters, second.record_llrs)
+    f = lr.CORNERS[fmt]
+    node = c.LdpcDecoderNode(lr.base_of(fmt), f.Z, first.max_iters, first.norm16, first.record_llrs, first.qscale)
+    check_case(c, first, node)
+    node.set_quant_scale(second.qscale)
+    for cs in (second, third):
+        check_case(c, cs._replace(norm16=1), node)
+    node.set_quant_scale(first.qscale)
     check_case(c, first, node)
 
 

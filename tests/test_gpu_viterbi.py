@@ -14,7 +14,8 @@ import viterbi_ref as vr
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 GUARD = 256
-CODES = [(K, n, t) for K in (3, 5, 7) for n in (2, 3) for t in (True, False)]
+CODES = [(K, n, t) for K in (3, 4, 5, 6, 7) for n in (2, 3) for t in (True, False)]
+GEN_SETS = [pytest.param(K, n, name, id="%d-%d-%s" % (K, n, name)) for (K, n), sets in sorted(vr.GEN_CORNERS.items()) for name, _ in sets]
 
 
 @pytest.fixture(scope="module")
@@ -178,6 +179,44 @@ def test_encoder_past_the_grid_and_timers(c):
     ms = timer.read_ms()
     assert ms.size == 1 and 0 < ms[0] < 100
     timer.close()
+
+
+# ------------------------------------------------------------------ 2b. generators off the one set per (K, n)
+@pytest.mark.parametrize("K,n,name", GEN_SETS)
+def test_generator_corners_decode_bit_for_bit(c, K, n, name):
+    """Generators without the input bit, without the oldest register bit (the two branches into a state tie whenever their
+    metrics do), a single bit beside all ones, one generator n times, random sets: the tie rules decide most bits here."""
+    gens = dict(vr.GEN_CORNERS[(K, n)])[name]
+    for terminated in (True, False):
+        for steps in vr.corner_steps(K):
+            for cs, llr, bits, metric in vr.corner_data(K, n, gens, terminated, steps):
+                assert cs.gens == gens and cs.frames == llr.shape[0] == 3
+                got, met = decode_dev(c, decoder_of(c, cs), llr)
+                assert np.array_equal(met, metric), (cs, met, metric)
+                assert np.array_equal(got, vr.pack_records(bits)), (cs, int(np.count_nonzero(vr.unpack_records(got, cs.T) != bits)))
+
+
+@pytest.mark.parametrize("K,n", sorted(vr.GEN_CORNERS))
+def test_generator_corners_encode_bit_for_bit(c, K, n):
+    rng = np.random.default_rng(K * 10 + n)
+    for name, gens in vr.GEN_CORNERS[(K, n)]:
+        for terminated in (True, False):
+            for steps in vr.corner_steps(K)[:3]:
+                T, frames = steps - (K - 1 if terminated else 0), 3
+                node = c.ConvEncoderNode(T, K, gens, terminated=terminated)
+                fin, fout = node.in_frame_bytes, node.out_frame_bytes
+                assert fin == vr.record_bytes(T) and fout == vr.record_bytes(n * steps)
+                sent = rng.integers(0, 2, (frames, T), dtype=np.uint8)
+                records = vr.pack_records(sent)
+                dirty = records | ~vr.pack_records(np.ones((frames, T), np.uint8))   # bits from T on do not count
+                want = vr.pack_records(vr.ref_encode(sent, K, gens, terminated))
+                d_in = c.DeviceBuf(frames * fin).upload(dirty)
+                d_out = c.DeviceBuf(frames * fout + GUARD).upload(np.full(frames * fout + GUARD, 0xFF, np.uint8))
+                node.run_dev(d_in.ptr, frames, d_out.ptr)
+                raw = d_out.download(np.uint8, frames * fout + GUARD)
+                assert np.array_equal(raw[: frames * fout].reshape(frames, fout), want), (K, n, name, terminated, steps)
+                assert np.all(raw[frames * fout:] == 0xFF)
+                assert node.run(records).tobytes() == want.tobytes()               # host pointers
 
 
 # ------------------------------------------------------------------ 3. the loop on the device

@@ -1,6 +1,7 @@
 """The reference of the convolutional code (tests/viterbi_ref.py) checked against what does not depend on it: the known
 impulse response, brute force over every codeword, the code's free distance, the quantiser's corner values -- and the noisy
 point the GPU loop test runs at, pinned with tests/noise_ref.py's model of the generator.  No GPU."""
+import hashlib
 import itertools
 
 import numpy as np
@@ -114,7 +115,7 @@ def test_record_size_helpers():
 
 
 def test_shared_cases_are_what_the_gpu_tests_assume():
-    for K in (3, 5, 7):
+    for K in (3, 4, 5, 6, 7):
         counts = vr.step_counts(K)
         assert {1, 2, K - 1, K, 63, 64, 65, 127, 128, 129, 1000, vr.LDS_STEPS, vr.LDS_STEPS + 1} == set(counts)
     # the noisy input is noisy enough that the decoder itself errs: the GPU is compared with ref_decode, not with the sent bits
@@ -140,3 +141,90 @@ def test_the_noisy_point_of_the_device_loop():
     assert all(np.any(hard[f] != coded[f]) for f in range(vr.LOOP_FRAMES))
     assert np.array_equal(bits, sent)
     assert np.count_nonzero(np.abs(np.rint(llr * np.float32(vr.LOOP_QSCALE))) > 127) < 0.01 * llr.size   # the clamp is rare
+
+
+# ------------------------------------------------------------------ generators off the one set per (K, n) (vr.GEN_CORNERS)
+ALL_SETS = [(K, n, name, gens) for (K, n), sets in sorted(vr.GEN_CORNERS.items()) for name, gens in sets]
+
+
+def test_generator_corners_are_what_they_are_named():
+    assert sorted(vr.GEN_CORNERS) == [(K, n) for K in range(3, 8) for n in (2, 3)]
+    for (K, n), sets in vr.GEN_CORNERS.items():
+        top, ones = 1 << (K - 1), (1 << K) - 1
+        by = dict(sets)
+        assert len(by) == len(sets) == 7 and all(len(g) == n and all(0 < x <= ones for x in g) for g in by.values())
+        assert not by["input_clear"][0] & top and all(x & top for x in by["input_clear"][1:])
+        assert not by["oldest_clear"][0] & 1 and any(x & 1 for x in by["oldest_clear"][1:])
+        assert not any(x & 1 for x in by["oldest_clear_all"])
+        assert by["single_and_ones"][:2] == (top, ones) and all(bin(x).count("1") == 1 for x in by["single_and_ones"][2:])
+        assert len(set(by["equal"])) == 1
+        assert by["random0"] != by["random1"]
+        # without the oldest bit in any generator the two branches into a state carry the same coded bits
+        _, sign = vr.trellis(K, by["oldest_clear_all"])
+        assert np.array_equal(sign[0], sign[1])
+        _, sign = vr.trellis(K, vr.GENS[(K, n)])
+        assert not np.array_equal(sign[0], sign[1])
+    # the default argument is the table's set, and the seed of a case does not depend on the generators
+    cs = vr.make_case(5, 2, True, 65, 3, "noisy")
+    assert cs == vr.make_case(5, 2, True, 65, 3, "noisy", gens=vr.GENS[(5, 2)]) and cs.gens == vr.GENS[(5, 2)]
+    other = vr.make_case(5, 2, True, 65, 3, "noisy", gens=(0o22, 0o34))
+    assert np.array_equal(vr.case_input(cs)[0], vr.case_input(other)[0]) and not np.array_equal(vr.case_input(cs)[1], vr.case_input(other)[1])
+
+
+def test_pinned_cases_are_unchanged():
+    """sha256 over cases, sent bits, inputs, reference bits and metrics, taken before make_case and ref_decode gained arguments."""
+    g = hashlib.sha256()
+    for K, n, t, steps, frames, kind in ((7, 2, True, 300, 3, "noisy"), (5, 3, False, 129, 2, "wide"), (3, 2, False, 65, 3, "special"),
+                                         (7, 3, True, 64, 1, "zeros")):
+        cs = vr.make_case(K, n, t, steps, frames, kind)
+        sent, llr, bits, metric = vr.case_data(cs)
+        for part in (repr(tuple(cs)).encode(), sent.tobytes(), llr.tobytes(), bits.tobytes(), metric.tobytes()):
+            g.update(part)
+    assert g.hexdigest() == "c942a9931abfbe5efe1b2f8248dcdd3d09c3f64f086964d99a9c5239d7c76c84", g.hexdigest()
+
+
+@pytest.mark.parametrize("K,n", sorted(vr.GEN_CORNERS))
+def test_generator_corners_against_brute_force_and_the_register(K, n):
+    """Every set, both endings, T <= 10: the final metric is the maximum over all codewords, the decoded word attains it, and
+    the encoder is the register stepped bit by bit.  Inputs with few levels, so that many candidates tie."""
+    rng = np.random.default_rng(100 * K + n)
+    for name, gens in vr.GEN_CORNERS[(K, n)]:
+        for terminated in (True, False):
+            u = rng.integers(0, 2, (2, 23), dtype=np.uint8)
+            got = vr.ref_encode(u, K, gens, terminated)
+            for f in range(2):
+                s, out = 0, []
+                for b in list(u[f]) + [0] * (K - 1 if terminated else 0):
+                    r = (int(b) << (K - 1)) | s
+                    out += [bin(r & g).count("1") & 1 for g in gens]
+                    s = r >> 1
+                assert got[f].tolist() == out, (K, n, name, terminated)
+            for T in (1, 2, 5, 10):
+                steps = vr.n_steps(T, K, terminated)
+                for levels in (128, 2):
+                    q = rng.integers(-levels + 1, levels, n * steps)
+                    bits, metric = vr.ref_decode(q[None, :], K, gens, T, terminated)
+                    best, words = vr.brute_force_metric(q, K, gens, T, terminated)
+                    assert int(metric[0]) == best, (K, n, name, terminated, T)
+                    assert any(np.array_equal(bits[0], w) for w in words), (K, n, name, terminated, T)
+
+
+@pytest.mark.parametrize("rule", vr.RULES)
+def test_generator_corners_catch_the_tie_mutants(rule):
+    """b = 1 on equal candidates, and the highest state among equal final metrics, made in copies of the reference: in every K
+    some corner case of tests/test_gpu_viterbi.py changes bits or its metric."""
+    for K in range(3, 8):
+        caught = []
+        for n in (2, 3):
+            for name, gens in vr.GEN_CORNERS[(K, n)]:
+                for terminated in (True, False):
+                    for steps in (K, 65):
+                        ref = vr.corner_data(K, n, gens, terminated, steps)
+                        mut = vr.corner_data(K, n, gens, terminated, steps, (rule,))
+                        caught += ["%d-%s-%s-%d-%s" % (n, name, "term" if terminated else "trunc", steps, cs.kind)
+                                   for (cs, _, bits, metric), (_, _, mbits, mmetric) in zip(ref, mut)
+                                   if not (np.array_equal(bits, mbits) and np.array_equal(metric, mmetric))]
+        kinds = sorted({c.rsplit("-", 1)[1] for c in caught})
+        print(rule, "K = %d: %d cases, kinds %s, e.g. %s" % (K, len(caught), kinds, caught[:3]))
+        assert caught, (rule, K)
+        assert any(c.endswith("zeros") for c in caught)

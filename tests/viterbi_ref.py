@@ -85,7 +85,14 @@ def trellis(K, gens):
     return frm, sign
 
 
-def ref_decode(q, K, gens, T, terminated=True):
+RULES = ("ge", "highest")
+
+
+def ref_decode(q, K, gens, T, terminated=True, rules=()):
+    """`rules` names deliberate departures from the header's tie rules, for the tests that ask whether the shared cases would
+    see them (tests/test_viterbi_ref.py): "ge" takes b = 1 on equal candidates, "highest" ends a truncated frame in the
+    highest state among equal final metrics.  No rule is the definition."""
+    assert set(rules) <= set(RULES)
     q = np.asarray(q, np.int64)
     frames = q.shape[0]
     n, S = len(gens), 1 << (K - 1)
@@ -100,10 +107,12 @@ def ref_decode(q, K, gens, T, terminated=True):
         qt = qs[:, t, :]
         c0 = M[:, frm[0]] + qt @ sign[0]
         c1 = M[:, frm[1]] + qt @ sign[1]
-        D[t] = c1 > c0                                                   # b = 1 only when strictly greater
+        D[t] = c1 >= c0 if "ge" in rules else c1 > c0                    # b = 1 only when strictly greater
         M = np.where(D[t], c1, c0)
     assert np.all(np.abs(M) < (1 << 31))
     s = np.zeros(frames, np.int64) if terminated else np.argmax(M, axis=1)   # argmax: the lowest index among equals
+    if "highest" in rules and not terminated:
+        s = S - 1 - np.argmax(M[:, ::-1], axis=1)
     metric = M[np.arange(frames), s].astype(np.int32)
     bits = np.zeros((frames, steps), np.uint8)
     rows = np.arange(frames)
@@ -132,16 +141,17 @@ Case = namedtuple("Case", "K n gens terminated T steps frames kind record_llrs q
 KINDS = ("noisy", "zeros", "special", "wide")
 
 
-def make_case(K, n, terminated, steps, frames, kind, qscale=1.0):
+def make_case(K, n, terminated, steps, frames, kind, qscale=1.0, gens=None):
     T = steps - (K - 1 if terminated else 0)
     assert T >= 1
     record = n * steps + (37 if kind == "wide" else 0)
-    return Case(K, n, GENS[(K, n)], terminated, T, steps, frames, kind, record, qscale)
+    gens = GENS[(K, n)] if gens is None else tuple(int(g) for g in gens)
+    assert len(gens) == n and all(0 < g < (1 << K) for g in gens)
+    return Case(K, n, gens, terminated, T, steps, frames, kind, record, qscale)
 
 
-@functools.lru_cache(maxsize=None)
-def case_data(cs):
-    """(sent bits, LLR records f32 (frames, record_llrs), reference bits, reference metrics) of a case; fixed by the case."""
+def case_input(cs):
+    """(sent bits, LLR records f32 (frames, record_llrs)) of a case: the seed does not depend on the generators."""
     rng = np.random.default_rng(hash((cs.K, cs.n, cs.terminated, cs.steps, cs.frames, KINDS.index(cs.kind))) & 0xFFFFFFFF)
     sent = rng.integers(0, 2, (cs.frames, cs.T), dtype=np.uint8)
     coded = ref_encode(sent, cs.K, cs.gens, cs.terminated)
@@ -155,11 +165,53 @@ def case_data(cs):
         special = np.array([np.nan, np.inf, -np.inf, 1e30, -1e30, 126.5, 127.5, -127.5, 0.5, 1.5, 2.5, -0.5, -0.0, 3e38], np.float32)
         hit = rng.random((cs.frames, used)) < 0.2
         llr[:, :used][hit] = special[rng.integers(0, special.size, int(hit.sum()))]
-    q = ref_quantise(llr[:, :used], cs.qscale)
+    return sent, llr
+
+
+@functools.lru_cache(maxsize=None)
+def case_data(cs):
+    """(sent bits, LLR records f32 (frames, record_llrs), reference bits, reference metrics) of a case; fixed by the case."""
+    sent, llr = case_input(cs)
+    q = ref_quantise(llr[:, : cs.n * cs.steps], cs.qscale)
     bits, metric = ref_decode(q, cs.K, cs.gens, cs.T, cs.terminated)
     for a in (sent, llr, bits, metric):
         a.setflags(write=False)
     return sent, llr, bits, metric
+
+
+# ------------------------------------------------------------------ generators off the one set per (K, n)
+def _gen_corners(K, n):
+    """The sets the tie rules decide most bits in: a generator without the input bit; one without the oldest register bit;
+    every generator without it (both predecessors of a state then emit the same coded bits: the compare ties whenever their
+    metrics do); a single bit beside all ones; one generator n times; two seeded random sets."""
+    base, top, ones = GENS[(K, n)], 1 << (K - 1), (1 << K) - 1
+    sets = [("input_clear", (base[0] & ~top,) + base[1:]), ("oldest_clear", (base[0] & ~1,) + base[1:]),
+            ("oldest_clear_all", tuple(g & ~1 for g in base)), ("single_and_ones", (top, ones, 1)[:n]), ("equal", (base[0],) * n)]
+    for i in range(2):
+        rng = np.random.default_rng([K, n, i])
+        sets.append(("random%d" % i, tuple(int(g) for g in rng.integers(1, ones + 1, n))))
+    return sets
+
+
+GEN_CORNERS = {(K, n): _gen_corners(K, n) for K in range(3, 8) for n in (2, 3)}
+CORNER_KINDS, CORNER_FRAMES = ("noisy", "zeros", "special"), 3
+
+
+def corner_steps(K):
+    """A short frame, two block seams, the workspace form."""
+    return (K, 65, 129, LDS_STEPS + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def corner_data(K, n, gens, terminated, steps, rules=()):
+    """[(case, LLR records, reference bits, reference metrics)] per kind of CORNER_KINDS: the cases are make_case's and the
+    inputs case_input's; the kinds' frames go through ref_decode together, which decodes frame by frame."""
+    cases = [make_case(K, n, terminated, steps, CORNER_FRAMES, kind, gens=gens) for kind in CORNER_KINDS]
+    llrs = [case_input(cs)[1] for cs in cases]
+    q = np.concatenate([ref_quantise(llr[:, : n * steps]) for llr in llrs])
+    bits, metric = ref_decode(q, K, gens, cases[0].T, terminated, rules)
+    return [(cs, llr, bits[CORNER_FRAMES * i: CORNER_FRAMES * (i + 1)], metric[CORNER_FRAMES * i: CORNER_FRAMES * (i + 1)])
+            for i, (cs, llr) in enumerate(zip(cases, llrs))]
 
 
 # ------------------------------------------------------------------ the loop on the device, and its model
