@@ -276,6 +276,7 @@ _PROTOS = {
     "comms_timing_create": [_u32, _u32, _f64, _i32, _pp],
     "comms_timing_push": [_vp, _vp, _sz, C.POINTER(_f64)],
     "comms_timing_push_dev": [_vp, _vp, _sz, C.POINTER(_f64), _vp],
+    "comms_timing_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_timing_destroy": [_vp],
     "comms_qfilt_taps": [_u32, _f64, _u32, _vp],
     "comms_syncest_create": [_u32, _u32, _f64, _i32, _pp],
@@ -406,6 +407,7 @@ _PROTOS = {
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],
     "comms_nco_get_phase": [_vp, C.POINTER(_f64)],
+    "comms_nco_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_nco_destroy": [_vp],
     "comms_synth_iq_dev": [_vp, _sz, _u64, _u64, _i32, _vp],
     "comms_shard_range": [_sz, _u32, _u32, _psz, _psz],

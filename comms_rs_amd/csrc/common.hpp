@@ -862,12 +862,15 @@ constexpr int kNumCU = 256;  // MI355X: 8 XCD x 32 CU
 // eight per CU and as many as fit the CU's 160 KiB of LDS (a kernel below 1 KiB counts as 1 KiB).  The diagnostic build's
 // COMMS_GRID_CAP = c > 0 lowers it to at most c, so that every persistent loop makes many passes over a small call
 // (tests/test_gpu_small_grids.py); it is read at each call: a handle takes its cap at create, one process makes handles
-// under several.
-inline unsigned resident_workgroups(size_t lds) {
-    const size_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : lds);
-    const unsigned chip = static_cast<unsigned>(kNumCU * (per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu));
+// under several.  grid_cap() is the one place that reads the knob: the handles that size their grid by hand (demod.hip's
+// 4 and 8 workgroups per CU) pass their own `chip`.
+inline unsigned grid_cap(unsigned chip) {
     const int cap = diag_knob("COMMS_GRID_CAP", 0);
     return cap > 0 && static_cast<unsigned>(cap) < chip ? static_cast<unsigned>(cap) : chip;
+}
+inline unsigned resident_workgroups(size_t lds) {
+    const size_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : lds);
+    return grid_cap(static_cast<unsigned>(kNumCU * (per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu)));
 }
 // The grid of a persistent launch with `blocks` workgroups' worth of work: at least one, at most the handle's cap
 inline size_t capped_grid(size_t blocks, unsigned max_grid) { return blocks < 1 ? 1 : blocks < max_grid ? blocks : max_grid; }

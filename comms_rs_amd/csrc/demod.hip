@@ -386,7 +386,7 @@ struct comms_timing : Handle {
     uint32_t n = 0, d = 0, n_q = 0;
     DevBuf<double> d_taps;
     DevBuf<double2> d_part;
-    unsigned max_blocks = 4 * kNumCU;
+    unsigned max_blocks = 4 * kNumCU;  // four workgroups per CU (timing_kernel's launch bounds); the diagnostic cap lowers it at create
     Scratch qacc;  // running filter sums between the passes of a filter longer than TE_QMAX taps
 };
 static_assert(!std::is_copy_constructible_v<comms_timing>, "a handle is never copied");
@@ -396,6 +396,7 @@ struct comms_nco : Handle {
     DevBuf<uint64_t> d_phase;  // fixed-point turns, device resident
     DevBuf<double2> d_tab;     // (cos, sin)(2 pi k / 1024), f64
     Scratch tiles;
+    unsigned slots = 8 * kNumCU;  // persistent grids: the apply kernel stages a 16 KiB rotor table per workgroup (8 workgroups per CU); the diagnostic cap lowers it at create
 };
 static_assert(!std::is_copy_constructible_v<comms_nco>, "a handle is never copied");
 
@@ -446,6 +447,7 @@ comms_status_t comms_timing_create(uint32_t n, uint32_t d, double alpha, int32_t
     h->n_q = static_cast<uint32_t>(taps.size());
     taps.resize((taps.size() + 11) / 12 * 12, 0.0);  // the kernel walks the taps in blocks of 12; zero taps add nothing
     COMMS_HIP_TRY(h->d_taps.upload(taps));
+    h->max_blocks = grid_cap(h->max_blocks);
     COMMS_HIP_TRY(h->d_part.alloc(h->max_blocks));
     *out = h.release();
     return COMMS_OK;
@@ -510,6 +512,15 @@ comms_status_t comms_timing_push(comms_timing_t* h, const double* samples, size_
     return comms_timing_push_dev(h, static_cast<const double*>(h->in_scratch.p), len, estimate, COMMS_STREAM_HANDLE);
 }
 
+comms_status_t comms_timing_get_kernel(const comms_timing_t* h, size_t len, char* name, size_t name_len) {
+    COMMS_ARG(h && name && name_len, "NULL argument");
+    const size_t tiles = (len + TE_TILE - 1) / TE_TILE;
+    const uint32_t nq12 = (h->n_q + 11) / 12 * 12;
+    std::snprintf(name, name_len, "timing_kernel tile=%d wg=%d taps=%u filter_passes=%u tiles=%zu grid=%zu max_grid=%u", TE_TILE, TE_WG,
+                  h->n_q, (nq12 + TE_QMAX - 1) / TE_QMAX, tiles, tiles < h->max_blocks ? tiles : h->max_blocks, h->max_blocks);
+    return COMMS_OK;
+}
+
 comms_status_t comms_timing_destroy(comms_timing_t* h) { return destroy_handle(h); }
 
 // ---- NCO -------------------------------------------------------------------------
@@ -526,6 +537,7 @@ comms_status_t comms_nco_create(double dphase, double phase, int32_t device, com
         const long double a = 2.0L * 3.14159265358979323846264338327950288L * static_cast<long double>(k) / 1024.0L;
         tab[k] = make_double2(static_cast<double>(cosl(a)), static_cast<double>(sinl(a)));
     }
+    h->slots = grid_cap(h->slots);
     COMMS_HIP_TRY(h->d_phase.upload(&turns, 1));
     COMMS_HIP_TRY(h->d_tab.upload(tab));
     *out = h.release();
@@ -546,8 +558,7 @@ comms_status_t comms_nco_run_dev(comms_nco_t* h, const double* d_perr, size_t n,
     COMMS_ARG(ntiles <= 0x7fffffffu, "block too long");
     COMMS_TRY(h->tiles.reserve(ntiles * sizeof(uint64_t)));
     uint64_t* tiles = static_cast<uint64_t*>(h->tiles.p);
-    // persistent grids: the apply kernel stages a 16 KiB rotor table per workgroup (8 workgroups per CU)
-    const size_t slots = static_cast<size_t>(8) * kNumCU;
+    const size_t slots = h->slots;
     const unsigned blocks = static_cast<unsigned>(ntiles < slots ? ntiles : slots);
     h->tic(s);
     nco_sum_kernel<<<dim3(blocks), dim3(NCO_WG), 0, s>>>(d_perr, n, h->dphase, tiles, ntiles);
@@ -581,6 +592,14 @@ comms_status_t comms_nco_get_phase(comms_nco_t* h, double* phase) {
     COMMS_TRY(h->quiesce());
     COMMS_HIP_TRY(hipMemcpy(&turns, h->d_phase.get(), sizeof(uint64_t), hipMemcpyDeviceToHost));
     *phase = static_cast<double>(turns >> 11) * (kMixT * 0x1.0p-53);
+    return COMMS_OK;
+}
+
+comms_status_t comms_nco_get_kernel(const comms_nco_t* h, size_t n, char* name, size_t name_len) {
+    COMMS_ARG(h && name && name_len, "NULL argument");
+    const size_t tiles = (n + NCO_TILE - 1) / NCO_TILE;
+    std::snprintf(name, name_len, "nco_sum_kernel+nco_scan_kernel+nco_apply_kernel tile=%d wg=%d tiles=%zu scan_sweeps=%zu grid=%zu max_grid=%u",
+                  NCO_TILE, NCO_WG, tiles, (tiles + 8191) / 8192, tiles < h->slots ? tiles : static_cast<size_t>(h->slots), h->slots);
     return COMMS_OK;
 }
 

@@ -1283,6 +1283,10 @@ class TimingEstimatorNode(_Handle):
         check(lib().comms_timing_push_dev(self._h, in_ptr, n, C.byref(out), stream))
         return out.value
 
+    def kernel(self, n):
+        """What a block of n samples is run by: "timing_kernel tile=.. wg=.. taps=.. filter_passes=.. tiles=.. grid=.. max_grid=.."."""
+        return self._kernel_name(n)
+
 
 class _SyncEstimateStruct(C.Structure):
     _fields_ = [("timing", C.c_double), ("freq", C.c_double), ("timing_sum", C.c_double * 2), ("freq_sum", C.c_double * 2)]
@@ -2277,6 +2281,11 @@ class NcoNode(_Handle):
 
     def run_dev(self, in_ptr, n, out_ptr, stream=0):
         check(lib().comms_nco_run_dev(self._h, in_ptr, n, out_ptr, stream))
+
+    def kernel(self, n):
+        """What a block of n phase errors is run by: "nco_sum_kernel+nco_scan_kernel+nco_apply_kernel tile=.. wg=.. tiles=..
+        scan_sweeps=.. grid=.. max_grid=.."."""
+        return self._kernel_name(n)
 
     @property
     def phase(self):

@@ -1,12 +1,13 @@
 """Persistent kernels on capped grids: the case table of tests/test_gpu_small_grids.py and each node's pass count restated from
 its launch code (no GPU here; tests/test_grid_cases.py holds the table to the rules below).
 
-The diagnostic build reads COMMS_GRID_CAP in resident_workgroups() (csrc/common.hpp): a handle made under cap c has
+The diagnostic build reads COMMS_GRID_CAP in grid_cap() (csrc/common.hpp), through resident_workgroups() or -- the two handles
+of demod.hip, which size their grids by hand -- directly: a handle made under cap c has
 max_grid = c, so a call of a few tens of thousands of samples makes every workgroup, wave or lane walk many passes.  Every
 grid formula used here is listed in ANCHORS with the source text it restates.
 
 A case is Case(family, kernel, name, fmt, size): `fmt` the node's format (a dict), `size(cap)` the call's size in the unit of
-its family -- samples (syncest, framesync), tiles (symsync, resample, channelizer; their tile is planned per handle and read
+its family -- samples (syncest, framesync, demod), tiles (symsync, resample, channelizer; their tile is planned per handle and read
 from kernel() on the device), frames (the rest).  walk(case, cap) restates the launch: Walk(total, unit, grid, passes), `total`
 the items of the call, `unit` the items one workgroup takes per pass; the busiest workgroup, wave or lane makes `passes`
 passes (four or more: five in most cases, up to 17).  The rules: passes >= MIN_PASSES, grid == cap (the channelizer: its own formula's grid), total no multiple of
@@ -18,6 +19,7 @@ import numpy as np
 
 import crc_ref
 import deframe_ref as dr
+import demod_ref
 import framesync_ref as fr
 import ofdm_ref
 import ratematch_ref as rr
@@ -34,6 +36,18 @@ CSRC = "comms_rs_amd/csrc/"
 ANCHORS = [
     (CSRC + "common.hpp", 'const int cap = diag_knob("COMMS_GRID_CAP", 0);'),
     (CSRC + "common.hpp", "return cap > 0 && static_cast<unsigned>(cap) < chip ? static_cast<unsigned>(cap) : chip;"),
+    (CSRC + "common.hpp", "return grid_cap(static_cast<unsigned>(kNumCU * (per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu)));"),
+    (CSRC + "demod.hip", "constexpr int TE_TILE = TE_WG * TE_OPL;     // outputs per tile"),
+    (CSRC + "demod.hip", "constexpr int NCO_TILE = NCO_WG * NCO_PER;    // 2048 samples per workgroup"),
+    (CSRC + "demod.hip", "h->max_blocks = grid_cap(h->max_blocks);"),
+    (CSRC + "demod.hip", "size_t blocks = (len + TE_TILE - 1) / TE_TILE;"),
+    (CSRC + "demod.hip", "if (blocks > h->max_blocks) blocks = h->max_blocks;"),
+    (CSRC + "demod.hip", "for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {"),
+    (CSRC + "demod.hip", "h->slots = grid_cap(h->slots);"),
+    (CSRC + "demod.hip", "const size_t ntiles = (n + NCO_TILE - 1) / NCO_TILE;"),
+    (CSRC + "demod.hip", "const size_t slots = h->slots;"),
+    (CSRC + "demod.hip", "const unsigned blocks = static_cast<unsigned>(ntiles < slots ? ntiles : slots);"),
+    (CSRC + "demod.hip", "for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {"),
     (CSRC + "syncest.hip", "constexpr int SE_TILE = SE_WG * SE_OPL;     // outputs per tile"),
     (CSRC + "stream_call.hpp", "inline size_t tile_grid(size_t tiles, unsigned max_grid) { return tiles ? capped_grid(tiles, max_grid) : 0; }"),
     (CSRC + "syncest.hip", "size_t syncest_tiles(size_t len) { return (len + SE_TILE - 1) / SE_TILE; }"),
@@ -81,6 +95,7 @@ ANCHORS = [
 
 WG = 256                 # lanes per workgroup of every kernel here
 SE_TILE = FS_TILE = 2048
+TE_TILE = NCO_TILE = 2048   # demod.hip: the timing estimator's and the NCO's
 TILE_MAX = 1024          # symsync, resample: the largest tile their planners try
 CHZ_TILE_POINTS = 2048   # channelizer: F = 2048 / M frames per tile at most
 
@@ -258,6 +273,31 @@ def n_coded_for(n_tx):
 
 def _syncest_len(cap):
     return 4 * cap * SE_TILE + 1031
+
+
+def _demod_len(cap):
+    return 4 * cap * TE_TILE + 1031
+
+
+# (n, d): n d = 50 (101 taps: one pass of the filter), 509 (1019 -> 1020: exactly one full pass), 510 (1021: two), 1300 (2601: three)
+DEMOD_TIMING = ((10, 5), (509, 1), (10, 51), (2, 650))
+
+
+def _demod():
+    # tiles = 4 cap + 1, the last one 1031 samples.  The NCO: two calls of that size in a row on one handle.
+    nco = [Case("demod", "demod.hip", "nco-%s" % kind, dict(node="nco", errors=kind), _demod_len) for kind in demod_ref.KINDS]
+    timing = [Case("demod", "demod.hip", "timing-n%d-d%d" % (n, d), dict(node="timing", n=n, d=d, alpha=demod_ref.ALPHA), _demod_len)
+              for n, d in DEMOD_TIMING]
+    return nco + timing
+
+
+def demod_nco_stream(cs, cap):
+    """(dphase, phase0, errors) in demod_ref's grid integers: both calls' errors, one after the other."""
+    return demod_ref.D_POS, demod_ref.P_NEAR_TURN, demod_ref.nco_errors(cs.fmt["errors"], 2 * cs.size(cap), 600 + cap)
+
+
+def demod_timing_block(cs, cap):
+    return demod_ref.timing_block("qpsk", cs.fmt["n"], cs.fmt["d"], cs.size(cap))
 
 
 def _framesync_len(cap):
@@ -487,10 +527,11 @@ def _ofdm():
             for name in OFDM_FORMATS for d in OFDM_DIRECTIONS.get(name, ("mod", "demod"))]
 
 
-CASES = _syncest() + _framesync() + _symsync() + _resample() + _channelizer() + _deframe() + _encoder() + _viterbi() + _ratematch() + _crc() + _symmap() + _ofdm()
-FAMILIES = ("syncest", "framesync", "symsync", "resample", "channelizer", "deframe", "convcode", "ratematch", "crc", "symmap", "ofdm")
-# not bitwise equal to the uncapped run: the [gridDim.x][4] partial sums of syncest_kernel are a reduction across workgroups
-REDUCED_ACROSS_WORKGROUPS = ("syncest",)
+CASES = _syncest() + _demod() + _framesync() + _symsync() + _resample() + _channelizer() + _deframe() + _encoder() + _viterbi() + _ratematch() + _crc() + _symmap() + _ofdm()
+FAMILIES = ("syncest", "demod", "framesync", "symsync", "resample", "channelizer", "deframe", "convcode", "ratematch", "crc", "symmap", "ofdm")
+# not bitwise equal to the uncapped run: the [gridDim.x][4] partial sums of syncest_kernel are a reduction across workgroups, and
+# so are timing_kernel's (the demod family's timing cases; its NCO cases are bitwise equal)
+REDUCED_ACROSS_WORKGROUPS = ("syncest", "demod/timing")
 
 
 def cases_of(family):
@@ -503,6 +544,8 @@ def walk(cs, cap):
         return tiles_walk(cdiv(size, SE_TILE), cap)
     if cs.family == "framesync":
         return tiles_walk(cdiv(size, FS_TILE), cap)
+    if cs.family == "demod":
+        return tiles_walk(cdiv(size, NCO_TILE if f["node"] == "nco" else TE_TILE), cap)
     if cs.family in ("symsync", "resample"):
         return tiles_walk(size, cap)
     if cs.family == "channelizer":
@@ -523,10 +566,10 @@ def walk(cs, cap):
 
 
 def ragged(cs, cap):
-    """The last pass is partial: the call's total is no multiple of grid * unit.  The tile kernels count in samples: syncest
-    and framesync against cap * 2048 here; symsync, resample and channelizer cut their last tile short on the device, where
+    """The last pass is partial: the call's total is no multiple of grid * unit.  The tile kernels count in samples: syncest,
+    demod and framesync against cap * 2048 here; symsync, resample and channelizer cut their last tile short on the device, where
     the handle's tile is known (tests/grid_children.py asserts it), so they count as ragged here."""
-    if cs.family in ("syncest", "framesync"):
+    if cs.family in ("syncest", "framesync", "demod"):
         return cs.size(cap) % (cap * SE_TILE) != 0
     if cs.family in ("symsync", "resample", "channelizer"):
         return True
@@ -550,6 +593,8 @@ def bytes_moved(cs, cap):
     size, f = cs.size(cap), cs.fmt
     if cs.family in ("syncest", "framesync"):
         return 8 * size
+    if cs.family == "demod":
+        return (8 + 16) * size if f["node"] == "nco" else 16 * size
     if cs.family == "symsync":
         return 8 * size * TILE_MAX * (f["S"] + 1)
     if cs.family == "resample":

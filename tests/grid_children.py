@@ -1,8 +1,8 @@
 """The child processes of tests/test_gpu_small_grids.py: `python grid_children.py FAMILY` runs every case of one node family
 from tests/grid_cases.py on handles made under COMMS_GRID_CAP = 1, 3 and 7 (the diagnostic build, which the parent selects
 through COMMS_HIP_LIB).  Per case and cap: kernel() must report max_grid == grid == cap and the table's pass count; the outputs
-are held to the node's own reference at the bound of its own GPU test, and -- syncest excepted, whose partial sums are one per
-workgroup -- to the bits of the same calls on an uncapped handle of this process.  The first failure ends the process: an
+are held to the node's own reference at the bound of its own GPU test, and -- syncest and the f64 timing estimator excepted,
+whose partial sums are one per workgroup -- to the bits of the same calls on an uncapped handle of this process.  The first failure ends the process: an
 assertion or a CommsError is an uncaught exception, and nothing is launched behind it.  The last line is "ok"."""
 import os
 import re
@@ -71,6 +71,52 @@ def syncest(c):
                       % (cs.name, cap, dts, sr.TIMING_SUM_TOL, dt, sr.TIMING_TOL, dfs, sr.FREQ_SUM_TOL))
                 assert dts <= sr.TIMING_SUM_TOL and dt <= sr.TIMING_TOL, (cs.name, cap, dts, dt)
                 assert dfs <= sr.FREQ_SUM_TOL and abs(got.freq - freq) <= sr.ANGLE_TOL, (cs.name, cap, dfs)
+
+
+# ---------------------------------------------------------------- demod: the f64 timing estimator and the NCO
+def demod(c):
+    import demod_ref as dm
+    import oracle
+
+    for cs in gc.cases_of("demod"):
+        if cs.fmt["node"] == "nco":
+            for cap in gc.CAPS:
+                d, p0, e = gc.demod_nco_stream(cs, cap)
+                n = cs.size(cap)
+                new = lambda: c.NcoNode(float(dm.rad(d)), float(dm.rad(p0)))  # noqa: E731
+                node, plain = make(new, cap), make(new)
+                k = fields(node.kernel(n))
+                held(cs, cap, k, k["tiles"], 1)
+                assert k["tile"] == gc.NCO_TILE and n % gc.NCO_TILE != 0 and fields(plain.kernel(n))["max_grid"] == 8 * 256
+                want, k_end = dm.nco_exact(p0, d, e)
+                x = dm.rad(e)
+                # two calls in a row: the tile offsets, the apply kernel's wave totals and the carried phase are used again
+                got = np.concatenate([node.run(x[:n]), node.run(x[n:])])
+                err = float(np.max(np.abs(got - want)))
+                dp = abs(np.exp(1j * node.phase) - dm.rotor_exact(np.array([k_end]))[0])
+                print("demod %s cap %d: 2 x %d samples, %d passes, off the exact values by %.3e, the phase by %.3e (tolerance %.0e)"
+                      % (cs.name, cap, n, gc.walk(cs, cap).passes, err, dp, dm.NCO_TOL))
+                assert err <= dm.NCO_TOL and dp <= dm.NCO_TOL, (cs.name, cap, err, dp)
+                assert np.concatenate([plain.run(x[:n]), plain.run(x[n:])]).tobytes() == got.tobytes(), (cs.name, cap)
+                assert plain.phase == node.phase
+            continue
+        n, d, alpha = cs.fmt["n"], cs.fmt["d"], cs.fmt["alpha"]
+        plain = make(lambda: c.TimingEstimatorNode(n, d, alpha))
+        for cap in gc.CAPS:
+            x = gc.demod_timing_block(cs, cap)
+            node = make(lambda: c.TimingEstimatorNode(n, d, alpha), cap)
+            k = fields(node.kernel(x.size))
+            held(cs, cap, k, k["tiles"], 1)
+            assert k["tile"] == gc.TE_TILE and x.size % gc.TE_TILE != 0 and fields(plain.kernel(x.size))["max_grid"] == 4 * 256
+            assert k["taps"] == 2 * n * d + 1 and k["filter_passes"] == len(dm.pass_lengths(n, d))
+            want = oracle.timing_push(x, n, d, alpha)
+            got = node.run(x)
+            errs = [dm.angle_error(g, want, n) for g in (got, plain.run(x))]
+            print("demod %s cap %d: %d samples, %d filter passes, estimate %.6f off the oracle's by %.3e rad of the sum, uncapped %.3e (tolerance %.3e)"
+                  % (cs.name, cap, x.size, k["filter_passes"], got, errs[0], errs[1], dm.ANGLE_TOL))
+            assert max(errs) <= dm.ANGLE_TOL, (cs.name, cap, errs)
+            again = node.run(x)                                       # the second push: qacc and the partials are overwritten
+            assert np.float64(again).tobytes() == np.float64(got).tobytes(), (cs.name, cap, got, again)
 
 
 # ---------------------------------------------------------------- framesync
@@ -436,7 +482,7 @@ def ofdm(c):
             assert plain.run(x).tobytes() == got.tobytes(), (cs.name, cap)
 
 
-CHILDREN = dict(syncest=syncest, framesync=framesync, symsync=symsync, resample=resample, channelizer=channelizer, deframe=deframe,
+CHILDREN = dict(syncest=syncest, demod=demod, framesync=framesync, symsync=symsync, resample=resample, channelizer=channelizer, deframe=deframe,
                 convcode=convcode, ratematch=ratematch, crc=crc, symmap=symmap, ofdm=ofdm)
 
 if __name__ == "__main__":

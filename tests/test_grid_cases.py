@@ -27,21 +27,23 @@ def test_formulas_still_stand_in_the_source():
 
 
 def test_every_persistent_kernel_has_a_case():
-    """Every .hip file that sizes a grid by resident_workgroups( has a case per call of it."""
+    """Every .hip file that sizes a grid by resident_workgroups( -- or by grid_cap( itself: the two handles of demod.hip -- has a
+    case per call of it."""
     csrc = os.path.join(ROOT, "comms_rs_amd", "csrc")
     calls = {}
     for name in sorted(os.listdir(csrc)):
         if name.endswith(".hip"):
             with open(os.path.join(csrc, name)) as f:
-                n = len(re.findall(r"resident_workgroups\(", f.read()))
+                n = len(re.findall(r"\b(?:resident_workgroups|grid_cap)\(", f.read()))
             if n:
                 calls[name] = n
-    assert calls == {"syncest.hip": 1, "symsync.hip": 1, "framesync.hip": 1, "resample.hip": 1, "channelizer.hip": 1, "deframe.hip": 1,
+    assert calls == {"demod.hip": 2, "syncest.hip": 1, "symsync.hip": 1, "framesync.hip": 1, "resample.hip": 1, "channelizer.hip": 1, "deframe.hip": 1,
                      "convcode.hip": 2, "ratematch.hip": 2, "crc.hip": 1, "symmap.hip": 2, "ofdm.hip": 1}, calls
     have = {}
     for cs in gc.CASES:
         have.setdefault(cs.kernel, set()).add(cs.fmt.get("node") or cs.fmt.get("dir") or "")
     assert {k: len(v) for k, v in have.items()} == calls
+    assert have["demod.hip"] == {"timing", "nco"}
     assert have["convcode.hip"] == {"encoder", "viterbi"} and have["ratematch.hip"] == {"tx", "rx"} and have["symmap.hip"] == {"map", "demap"}
     assert {cs.fmt["direction"] for cs in gc.cases_of("ofdm")} == {"mod", "demod"}     # ofdm.hip takes its cap once for both
     assert {cs.family for cs in gc.CASES} == set(gc.FAMILIES)
@@ -272,6 +274,33 @@ def test_syncest_inputs_are_within_the_model_distance():
             assert abs(mts - ts) / ta <= sr.MODEL_SUM_DISTANCE, (cs.name, cap, abs(mts - ts) / ta)
             assert sr.circ(sr.timing_of(mts, n), sr.timing_of(ts, n), n) <= sr.MODEL_TIMING_DISTANCE, (cs.name, cap)
             assert abs(mfs - fs) <= sr.FREQ_SUM_TOL * fa
+
+
+def test_demod_inputs_meet_their_conditions():
+    """The demod family: the filter lengths of one, exactly one, two and three passes; timing blocks coherent enough to test an
+    angle on (tests/test_demod_ref.py's condition); NCO streams on which the oracle agrees with the exact reference, with tile
+    sums that all differ, in both error ranges."""
+    import demod_ref as dm
+
+    timing = [cs for cs in gc.cases_of("demod") if cs.fmt["node"] == "timing"]
+    assert [cs.fmt["n"] * cs.fmt["d"] for cs in timing] == [50, 509, 510, 1300]
+    assert [dm.pass_lengths(cs.fmt["n"], cs.fmt["d"]) for cs in timing] == [[108], [1020], [1020, 12], [1020, 1020, 564]]
+    for cs in timing:
+        for cap in gc.CAPS:
+            x = gc.demod_timing_block(cs, cap)
+            assert x.size == cs.size(cap) and dm.coherence(x, cs.fmt["n"], cs.fmt["d"], cs.fmt["alpha"]) >= sr.MIN_COHERENCE, (cs.name, cap)
+    nco = [cs for cs in gc.cases_of("demod") if cs.fmt["node"] == "nco"]
+    assert [cs.fmt["errors"] for cs in nco] == ["small", "large"]
+    for cs in nco:
+        for cap in gc.CAPS:
+            d, p0, e = gc.demod_nco_stream(cs, cap)
+            assert e.size == 2 * cs.size(cap)
+            sums = np.add.reduceat(d + e, np.arange(0, e.size, gc.NCO_TILE))
+            assert np.unique(sums).size == sums.size
+            got, phase = dm.oracle_nco(p0, d, e, (cs.size(cap),))
+            want, k_end = dm.nco_exact(p0, d, e)
+            assert np.max(np.abs(got - want)) <= dm.ORACLE_NCO_TOL, (cs.name, cap)
+            assert abs(np.exp(1j * phase) - dm.rotor_exact(np.array([k_end]))[0]) <= dm.ORACLE_NCO_TOL
 
 
 def test_deframe_inputs_keep_the_decision_margin():
