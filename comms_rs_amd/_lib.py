@@ -210,7 +210,7 @@ _PROTOS = {
     "comms_channelizer_run": [_vp, _vp, _sz, _vp],
     "comms_channelizer_get_state": [_vp, _vp, _sz],
     "comms_channelizer_set_state": [_vp, _vp, _sz],
-    "comms_channelizer_get_phase": [_vp, C.POINTER(C.c_uint64)],
+    "comms_channelizer_get_phase": [_vp, C.POINTER(_u64)],
     "comms_channelizer_set_phase": [_vp, _u64],
     "comms_channelizer_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_channelizer_set_timer": [_vp, _vp],
@@ -296,8 +296,8 @@ _PROTOS = {
     "comms_framesync_state_len": [_sz, _sz, _psz],
     "comms_framesync_get_state": [_vp, _vp, _sz],
     "comms_framesync_set_state": [_vp, _vp, _sz],
-    "comms_framesync_get_position": [_vp, C.POINTER(C.c_uint64)],
-    "comms_framesync_set_position": [_vp, C.c_uint64],
+    "comms_framesync_get_position": [_vp, C.POINTER(_u64)],
+    "comms_framesync_set_position": [_vp, _u64],
     "comms_framesync_set_threshold": [_vp, _f64],
     "comms_framesync_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_framesync_set_timer": [_vp, _vp],
@@ -313,8 +313,8 @@ _PROTOS = {
     "comms_deframe_state_len": [_sz, _sz, _psz],
     "comms_deframe_get_state": [_vp, _vp, _sz],
     "comms_deframe_set_state": [_vp, _vp, _sz],
-    "comms_deframe_get_position": [_vp, C.POINTER(C.c_uint64)],
-    "comms_deframe_set_position": [_vp, C.c_uint64],
+    "comms_deframe_get_position": [_vp, C.POINTER(_u64)],
+    "comms_deframe_set_position": [_vp, _u64],
     "comms_deframe_get_pending": [_vp, _vp, _sz, _psz],
     "comms_deframe_set_pending": [_vp, _vp, _sz],
     "comms_deframe_get_kernel": [_vp, _sz, C.c_char_p, _sz],
@@ -397,8 +397,8 @@ _PROTOS = {
     "comms_ofdmsync_state_len": [_sz, _sz, _sz, _psz],
     "comms_ofdmsync_get_state": [_vp, _vp, _sz],
     "comms_ofdmsync_set_state": [_vp, _vp, _sz],
-    "comms_ofdmsync_get_position": [_vp, C.POINTER(C.c_uint64)],
-    "comms_ofdmsync_set_position": [_vp, C.c_uint64],
+    "comms_ofdmsync_get_position": [_vp, C.POINTER(_u64)],
+    "comms_ofdmsync_set_position": [_vp, _u64],
     "comms_ofdmsync_set_threshold": [_vp, _f64],
     "comms_ofdmsync_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_ofdmsync_set_timer": [_vp, _vp],

@@ -37,10 +37,19 @@ def _as_input(a, fmt):
     return a, a.size // per
 
 
+def _get(ctype, fn, *args, tail=()):
+    """The scalar that fn(*args, &value, *tail) writes: every getter, out_len and estimate of the C ABI.  `tail` is what
+    follows the output in the handle-less entries: the device, and the stream of their device forms."""
+    v = ctype()
+    check(fn(*args, C.byref(v), *tail))
+    return v.value
+
+
 def device_count():
-    n = C.c_int32(0)
-    st = lib().comms_device_count(C.byref(n))
-    return n.value if st == 0 else 0
+    try:
+        return _get(C.c_int32, lib().comms_device_count)
+    except _lib.CommsError:
+        return 0
 
 
 class _Handle:
@@ -60,6 +69,10 @@ class _Handle:
         check(getattr(lib(), self._prefix + "_set_timer")(self._h, timer._h if timer is not None else None))
         return self
 
+    def _call(self, name, *args):
+        """check(comms_<prefix>_<name>(*args)): the call of a body that several prefixes share."""
+        check(getattr(lib(), self._prefix + "_" + name)(*args))
+
     def _kernel_name(self, *args, cap=240):
         """comms_*_get_kernel(handle, *args, name, cap), decoded."""
         buf = C.create_string_buffer(cap)
@@ -75,29 +88,31 @@ class _Handle:
 
 class _History:
     """The history accessors of a stream node (csrc/stream_call.hpp) over comms_<prefix>_{state_len, get_state, set_state}:
-    `_state_dtype` is the sample type, `_state_args` names the attributes comms_<prefix>_state_len takes.  The length is fixed
-    at create: the library is asked once per node."""
+    `_state_dtype` and `_state_shape` are the numpy type and shape of ONE sample, `_state_args` names the attributes
+    comms_<prefix>_state_len takes, `_state_get` / `_state_set` the C name stems where they differ (the chain's
+    "_get_fir_state").  The length is fixed at create: the library is asked once per node.  A node without a state_len entry
+    (the FIRs, the chain) passes its n_state."""
     _state_dtype = np.complex64
+    _state_shape = ()
     _state_args = ()
     _state_len = None
+    _state_get, _state_set = "_get_state", "_set_state"
 
     def state_len(self):
         if self._state_len is None:
-            m = C.c_size_t()
-            check(getattr(lib(), self._prefix + "_state_len")(*[getattr(self, a) for a in self._state_args], C.byref(m)))
-            self._state_len = m.value
+            self._state_len = _get(C.c_size_t, getattr(lib(), self._prefix + "_state_len"), *[getattr(self, a) for a in self._state_args])
         return self._state_len
 
     def get_state(self, n_state=None):
         """The last n_state input samples (default: all state_len() of them), newest first."""
         n_state = self.state_len() if n_state is None else int(n_state)
-        st = np.empty(n_state, self._state_dtype)
-        check(getattr(lib(), self._prefix + "_get_state")(self._h, _ptr(st), n_state))
+        st = np.empty((n_state,) + self._state_shape, self._state_dtype)
+        check(getattr(lib(), self._prefix + self._state_get)(self._h, _ptr(st), n_state))
         return st
 
     def set_state(self, state):
         state = np.ascontiguousarray(state, dtype=self._state_dtype)
-        check(getattr(lib(), self._prefix + "_set_state")(self._h, _ptr(state), state.size))
+        check(getattr(lib(), self._prefix + self._state_set)(self._h, _ptr(state), len(state.reshape((-1,) + self._state_shape))))
         return self
 
 
@@ -106,9 +121,7 @@ class _Position:
 
     def position(self):
         """Stream index of the next sample (symbol)."""
-        t = C.c_uint64()
-        check(getattr(lib(), self._prefix + "_get_position")(self._h, C.byref(t)))
-        return t.value
+        return _get(C.c_uint64, getattr(lib(), self._prefix + "_get_position"), self._h)
 
     def set_position(self, position):
         check(getattr(lib(), self._prefix + "_set_position")(self._h, int(position)))
@@ -117,8 +130,10 @@ class _Position:
 
 class _Detector(_Position):
     """What the two synchronisers share beside their history: the threshold, the default capacity of a call (detections are more
-    than `guard` positions apart) and the packing of its detections."""
+    than `guard` positions apart), the outputs of a call and the packing of its detections.  `_side` holds the dtypes of the
+    per-detection outputs beside the detections: the OFDM synchroniser's cfo."""
     found = 0
+    _side = ()
 
     def set_threshold(self, threshold):
         check(getattr(lib(), self._prefix + "_set_threshold")(self._h, float(threshold)))
@@ -127,10 +142,89 @@ class _Detector(_Position):
     def _cap(self, n, cap):
         return (n + self.guard) // (self.guard + 1) if cap is None else int(cap)
 
-    def _result(self, out, cap, found, raw):
+    def _detect(self, fn, n, cap, raw, *args, tail=()):
+        """fn(handle, *args, detections, *side outputs, cap, &found, *tail) with room for `cap` detections (None: as many as n
+        positions can hold): the detections, or with side outputs the tuple (detections, *side), each cut to what was found."""
+        cap = self._cap(n, cap)
+        outs = [np.zeros(cap, dtype) for dtype in (FRAME_DETECTION_DTYPE,) + self._side]
+        found = C.c_size_t()
+        check(fn(self._h, *args, *[_ptr(o) if cap else None for o in outs], cap, C.byref(found), *tail))
         self.found = found.value
-        out = out[: min(self.found, cap)]
-        return out if raw else [FrameDetection(d) for d in out]
+        dets = outs[0][: min(self.found, cap)]
+        dets = dets if raw else [FrameDetection(d) for d in dets]
+        return (dets, *[o[: len(dets)] for o in outs[1:]]) if self._side else dets
+
+
+def _record(accessor, unit=1):
+    """node -> the bytes of one record, from the handle's C accessor `accessor` (looked up at the first call), which counts
+    units of `unit` bytes."""
+    fn = []
+
+    def nbytes(node):
+        if not fn:
+            fn.append(getattr(lib(), accessor))
+        return fn[0](node._h) * unit
+    return nbytes
+
+
+class _FrameCall:
+    """One per-frame entry of the C ABI (csrc/common.hpp: FrameCall): `run`(handle, records in, n_frames, records out, ...)
+    and its device form `run`_dev(..., stream), looked up at the first call.  in_dtype / out_dtype are the numpy types of an
+    input and an output element, in_bytes / out_bytes give node -> bytes of a record (_record, or host arithmetic).  A node
+    holds one as data and calls it; a stream node with a per-frame entry beside its stream (OfdmSyncNode.correct) does the same."""
+
+    def __init__(self, run, in_dtype, out_dtype, in_bytes, out_bytes):
+        self._name, self._fns = run, None
+        self.in_dtype, self.out_dtype, self.in_bytes, self.out_bytes = np.dtype(in_dtype), np.dtype(out_dtype), in_bytes, out_bytes
+
+    def _c(self, dev):
+        if self._fns is None:
+            self._fns = getattr(lib(), self._name), getattr(lib(), self._name + "_dev")
+        return self._fns[dev]
+
+    def run(self, node, x, side=(), pre=(), tail=()):
+        """Host form on any array of whole records: run(handle, x, n_frames, *pre, out, *side outputs, *tail) with a zero-filled
+        output of shape (n_frames, elements per record) and one zero-filled side output of n_frames values per dtype of `side`;
+        `pre` holds further per-frame input arrays, `tail` goes as it is.  Returns out, or with side outputs (out, *side
+        outputs).  With no frames every array goes as NULL and nothing is launched."""
+        x = np.ascontiguousarray(x, dtype=self.in_dtype)
+        per = self.in_bytes(node) // self.in_dtype.itemsize
+        if not per or x.size % per:
+            raise ValueError("the input must hold whole records of %d values (%d bytes)" % (per, per * self.in_dtype.itemsize))
+        n_frames = x.size // per
+        out = np.zeros((n_frames, self.out_bytes(node) // self.out_dtype.itemsize), self.out_dtype)
+        outs = [out] + [np.zeros(n_frames, dtype) for dtype in side]
+        p_in, *ptrs = [_ptr(a) if n_frames else None for a in (x, *pre, *outs)]
+        check(self._c(0)(node._h, p_in, n_frames, *ptrs, *tail))
+        return tuple(outs) if side else out
+
+    def run_dev(self, node, in_ptr, n_frames, *rest):
+        """Device form: rest = the further pointers and the stream, as the C entry takes them."""
+        check(self._c(1)(node._h, in_ptr, int(n_frames), *rest))
+
+
+class _FrameNode:
+    """A node whose run is one _FrameCall, `_frame`: frame-major records in, records out, all frames of a call in one launch."""
+    _frame = None
+
+    @property
+    def in_frame_bytes(self):
+        return self._frame.in_bytes(self)
+
+    @property
+    def out_frame_bytes(self):
+        return self._frame.out_bytes(self)
+
+    def run(self, frames):
+        return self._frame.run(self, frames)
+
+    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
+        self._frame.run_dev(self, in_ptr, n_frames, out_ptr, stream)
+
+
+def _frame_call(prefix, in_dtype, out_dtype):
+    """The _FrameCall of comms_<prefix>_run with the accessors comms_<prefix>_{in,out}_frame_bytes: what most nodes have."""
+    return _FrameCall(prefix + "_run", in_dtype, out_dtype, _record(prefix + "_in_frame_bytes"), _record(prefix + "_out_frame_bytes"))
 
 
 # ------------------------------------------------------------------ device buffers
@@ -180,7 +274,7 @@ class DeviceBuf:
 
 
 # ------------------------------------------------------------------ FIR
-class BatchFirNode(_Handle):
+class BatchFirNode(_History, _Handle):
     """BatchFirNode::new(taps, state) / run (fir_node.rs:193-220)."""
     _prefix = "comms_fir"
 
@@ -198,9 +292,7 @@ class BatchFirNode(_Handle):
         return self
 
     def algo_for(self, n):
-        a = C.c_int32()
-        check(lib().comms_fir_get_algo(self._h, n, C.byref(a)))
-        return a.value
+        return _get(C.c_int32, lib().comms_fir_get_algo, self._h, n)
 
     def kernel_for(self, n):
         """Name of the kernel a batch of n samples is run by (diagnostics)."""
@@ -225,13 +317,10 @@ class BatchFirNode(_Handle):
         check(lib().comms_fir_run_dev(self._h, in_ptr, n, out_ptr, stream))
 
     def state(self, n_state):
-        st = np.empty(n_state, np.complex64)
-        check(lib().comms_fir_get_state(self._h, _ptr(st), n_state))
-        return st
+        return self.get_state(n_state)
 
     def set_state(self, state):
-        state = _as_c64(state)
-        check(lib().comms_fir_set_state(self._h, _ptr(state), state.size))
+        _History.set_state(self, state)
 
 
 class FirNode(BatchFirNode):
@@ -259,9 +348,7 @@ class PulseNode(_Handle):
     @property
     def phase(self):
         """Oscillator phase of the fused mixer for the next output sample."""
-        p = C.c_double()
-        check(lib().comms_pulse_get_phase(self._h, C.byref(p)))
-        return p.value
+        return _get(C.c_double, lib().comms_pulse_get_phase, self._h)
 
     _out_i16 = False
 
@@ -278,20 +365,9 @@ class PulseNode(_Handle):
         """"bits": run_bits() takes packed bits (LSB first, bits_per_sym = 1 or 2 per symbol) and the kernel maps
         value v to constellation[v] (2**bits_per_sym points; None = digital.rs's bpsk_bit_mod / qpsk_bit_mod tables);
         "c32" restores the default, run() on complex symbols.  The history carries across a switch."""
-        if fmt == "c32":
-            check(lib().comms_pulse_set_input_format(self._h, _lib.SYM_C32, 0, None))
-            self._in_bits = 0
-            return self
-        if fmt != "bits":
+        if fmt not in ("c32", "bits"):
             raise ValueError("input format must be 'c32' or 'bits' (got %r)" % (fmt,))
-        cons = None
-        if constellation is not None:
-            cons = _as_c64(constellation).ravel()
-            if cons.size != 1 << int(bits_per_sym):
-                raise ValueError("the constellation holds 2**bits_per_sym points")
-        check(lib().comms_pulse_set_input_format(self._h, _lib.SYM_BITS, int(bits_per_sym), None if cons is None else _ptr(cons)))
-        self._cons = cons  # (kept alive while the call copies it)
-        self._in_bits = int(bits_per_sym)
+        self._in_bits = _set_bits_format(lib().comms_pulse_set_input_format, self._h, bits_per_sym if fmt == "bits" else None, constellation)
         return self
 
     def _out_array(self, n_sym):
@@ -316,10 +392,7 @@ class PulseNode(_Handle):
         if self._in_bits:
             raise ValueError("the node reads packed bits (set_input_format): use run_bits")
         s = _as_c64(np.atleast_1d(sym))
-        if self._out_i16:
-            out = np.empty((s.size * self.sam_per_sym, 2), np.int16)
-        else:
-            out = np.empty(s.size * self.sam_per_sym, np.complex64)
+        out = self._out_array(s.size)
         check(lib().comms_pulse_run(self._h, _ptr(s), s.size, _ptr(out)))
         return out
 
@@ -342,9 +415,6 @@ class _Exact(_Handle):
     its ABI prefix `_abi`, the function `_arr` that makes a contiguous array of its sample type, and that type as the numpy
     `_dtype` and `_shape` of ONE sample: int16 (2,) for Complex<i16>, complex128 () for Complex<f64>."""
     _abi = _arr = _dtype = _shape = None
-
-    def _call(self, name, *args):
-        check(getattr(lib(), self._abi + name)(*args))
 
     def _n(self, a):
         """Samples in an array that _arr made."""
@@ -376,10 +446,13 @@ class _ExactFir(_Exact):
         self._call("run", self._h, _ptr(x), self._n(x), _ptr(out))
         return out[0] if single else out
 
+    # _History's bodies on the sample type of the subclass; no mixin, because the ABI backs them in part: only Complex<f64>
+    # has a set_state entry
+    _state_get, _state_set = _History._state_get, _History._state_set
+    _state_dtype, _state_shape = property(lambda self: self._dtype), property(lambda self: self._shape)
+
     def state(self, n_state):
-        st = self._out(int(n_state))
-        self._call("get_state", self._h, _ptr(st), int(n_state))
-        return st
+        return _History.get_state(self, n_state)
 
 
 class _ExactPulse(_Exact):
@@ -410,10 +483,7 @@ class BatchFirNodeF64(_ExactFir):
     _abi, _arr, _dtype, _shape = "comms_fir_f64_", staticmethod(_as_c128), np.complex128, ()
     _prefix = _abi[:-1]
 
-    def set_state(self, state):
-        st = self._arr(state)
-        self._call("set_state", self._h, _ptr(st), st.size)
-        return self
+    set_state = _History.set_state
 
 
 FirNodeI16 = BatchFirNodeI16
@@ -465,9 +535,7 @@ class MixerNode(_Handle):
 
     @property
     def phase(self):
-        p = C.c_double()
-        check(lib().comms_mixer_get_phase(self._h, C.byref(p)))
-        return p.value
+        return _get(C.c_double, lib().comms_mixer_get_phase, self._h)
 
     @phase.setter
     def phase(self, value):
@@ -476,200 +544,159 @@ class MixerNode(_Handle):
 
 
 # ------------------------------------------------------------------ resampling
-class DecimateNode:
+class _RateChange:
+    """What DecimateNode and UpsampleNode share: comms_<_name>_{out_len, run, run_dev} on elements of any size, handle-less,
+    the rate kept in the attribute that `_rate` names.  The C functions are looked up once per node."""
+    _name = _rate = None
+
+    def __init__(self, rate, device=0):
+        setattr(self, self._rate, int(rate))
+        self.device = device
+        self._out_len, self._run, self._run_dev = (getattr(lib(), "comms_%s_%s" % (self._name, f)) for f in ("out_len", "run", "run_dev"))
+
+    def out_len(self, n):
+        return _get(C.c_size_t, self._out_len, n, getattr(self, self._rate))
+
+    def run(self, x):
+        x = np.ascontiguousarray(x)
+        elem = x.dtype.itemsize * int(np.prod(x.shape[1:], dtype=np.int64))
+        out = np.empty((self.out_len(x.shape[0]),) + x.shape[1:], x.dtype)
+        m = _get(C.c_size_t, self._run, _ptr(x), x.shape[0], elem, getattr(self, self._rate), _ptr(out), tail=(self.device,))
+        assert m == out.shape[0]
+        return out
+
+    def run_dev(self, in_ptr, n, elem, out_ptr, stream=0):
+        return _get(C.c_size_t, self._run_dev, in_ptr, n, elem, getattr(self, self._rate), out_ptr, tail=(self.device, stream))
+
+
+class DecimateNode(_RateChange):
     """DecimateNode::new(dec_rate) / decimate (resample_node.rs:23, :53-65)."""
+    _name, _rate = "decimate", "dec_rate"
 
     def __init__(self, dec_rate, device=0):
-        self.dec_rate, self.device = int(dec_rate), device
+        super().__init__(dec_rate, device)
 
-    def out_len(self, n):
-        m = C.c_size_t()
-        check(lib().comms_decimate_out_len(n, self.dec_rate, C.byref(m)))
-        return m.value
-
-    def run(self, x):
-        x = np.ascontiguousarray(x)
-        elem = x.dtype.itemsize * int(np.prod(x.shape[1:], dtype=np.int64))
-        out = np.empty((self.out_len(x.shape[0]),) + x.shape[1:], x.dtype)
-        m = C.c_size_t()
-        check(lib().comms_decimate_run(_ptr(x), x.shape[0], elem, self.dec_rate, _ptr(out), C.byref(m), self.device))
-        assert m.value == out.shape[0]
-        return out
-
-    decimate = run
-
-    def run_dev(self, in_ptr, n, elem, out_ptr, stream=0):
-        m = C.c_size_t()
-        check(lib().comms_decimate_run_dev(in_ptr, n, elem, self.dec_rate, out_ptr, C.byref(m), self.device, stream))
-        return m.value
+    decimate = _RateChange.run
 
 
-class UpsampleNode:
+class UpsampleNode(_RateChange):
     """UpsampleNode::new(ups_rate) / upsample (resample_node.rs:87, :120-131)."""
+    _name, _rate = "upsample", "ups_rate"
 
     def __init__(self, ups_rate, device=0):
-        self.ups_rate, self.device = int(ups_rate), device
+        super().__init__(ups_rate, device)
 
-    def out_len(self, n):
-        m = C.c_size_t()
-        check(lib().comms_upsample_out_len(n, self.ups_rate, C.byref(m)))
-        return m.value
-
-    def run(self, x):
-        x = np.ascontiguousarray(x)
-        elem = x.dtype.itemsize * int(np.prod(x.shape[1:], dtype=np.int64))
-        out = np.empty((self.out_len(x.shape[0]),) + x.shape[1:], x.dtype)
-        m = C.c_size_t()
-        check(lib().comms_upsample_run(_ptr(x), x.shape[0], elem, self.ups_rate, _ptr(out), C.byref(m), self.device))
-        assert m.value == out.shape[0]
-        return out
-
-    upsample = run
-
-    def run_dev(self, in_ptr, n, elem, out_ptr, stream=0):
-        m = C.c_size_t()
-        check(lib().comms_upsample_run_dev(in_ptr, n, elem, self.ups_rate, out_ptr, C.byref(m), self.device, stream))
-        return m.value
+    upsample = _RateChange.run
 
 
 # ------------------------------------------------------------------ FM demod
-class FMDemodNode(_Handle):
-    """FMDemodNode::new() / run (analog_node.rs:43-51)."""
-    _prefix = "comms_fmdemod"
+def _flat_c128(a):
+    return np.ascontiguousarray(a, dtype=np.complex128).ravel()
+
+
+class _FMDemod(_Handle):
+    """FMDemodNode<T> over comms_<_prefix>_*: `_dtype` is the complex sample type, `_arr` makes a contiguous array of it; the
+    output is its real type."""
+    _dtype = _arr = None
 
     def __init__(self, device=0):
         super().__init__()
-        check(lib().comms_fmdemod_create(device, C.byref(self._h)))
+        self._call("create", device, C.byref(self._h))
 
     def run(self, x):
-        x = _as_c64(x)
-        out = np.empty(x.size, np.float32)
-        check(lib().comms_fmdemod_run(self._h, _ptr(x), x.size, _ptr(out)))
+        x = self._arr(x)
+        out = np.empty(x.size, x.real.dtype)
+        self._call("run", self._h, _ptr(x), x.size, _ptr(out))
         return out
 
     def run_dev(self, in_ptr, n, out_ptr, stream=0):
-        check(lib().comms_fmdemod_run_dev(self._h, in_ptr, n, out_ptr, stream))
+        self._call("run_dev", self._h, in_ptr, n, out_ptr, stream)
 
     @property
     def prev(self):
         """FM.prev (analog.rs:9,31): the last input sample of the previous batch."""
-        p = np.zeros(1, np.complex64)
-        check(lib().comms_fmdemod_get_prev(self._h, _ptr(p)))
+        p = np.zeros(1, self._dtype)
+        self._call("get_prev", self._h, _ptr(p))
         return p[0]
 
     @prev.setter
     def prev(self, value):
-        p = np.array([value], np.complex64)
-        check(lib().comms_fmdemod_set_prev(self._h, _ptr(p)))
+        p = np.array([value], self._dtype)
+        self._call("set_prev", self._h, _ptr(p))
+
+
+class FMDemodNode(_FMDemod):
+    """FMDemodNode::new() / run (analog_node.rs:43-51)."""
+    _prefix, _dtype, _arr = "comms_fmdemod", np.complex64, staticmethod(_as_c64)
+
+
+class FMDemodNodeF64(_FMDemod):
+    """FMDemodNode<f64>::new() / run (analog_node.rs:20-52; FM::demod analog.rs:22-35) on Complex<f64>."""
+    _prefix, _dtype, _arr = "comms_fmdemod_f64", np.complex128, staticmethod(_flat_c128)
 
 
 # ------------------------------------------------------------------ FFT
-class FFTBatchNode(_Handle):
-    """FFTBatchNode::new(fft_size, ifft) / run (fft_node.rs:65-83)."""
-    _prefix = "comms_fft"
+class _FFTBatch(_Handle):
+    """FFTBatchNode<T> over comms_<_prefix>_*: `_dtype` is the sample type, `_arr` makes a contiguous array of it."""
+    _dtype = _arr = None
 
     def __init__(self, fft_size, ifft, device=0):
         super().__init__()
         self.fft_size = int(fft_size)
-        check(lib().comms_fft_create(self.fft_size, 1 if ifft else 0, device, C.byref(self._h)))
+        self._call("create", self.fft_size, 1 if ifft else 0, device, C.byref(self._h))
 
     def run(self, x):
-        x = _as_c64(x)
+        x = self._arr(x)
         out = np.empty_like(x)
-        check(lib().comms_fft_run(self._h, _ptr(x), x.size, _ptr(out)))
+        self._call("run", self._h, _ptr(x), x.size, _ptr(out))
         return out
 
     def run_dev(self, in_ptr, n, out_ptr, stream=0):
-        check(lib().comms_fft_run_dev(self._h, in_ptr, n, out_ptr, stream))
+        self._call("run_dev", self._h, in_ptr, n, out_ptr, stream)
 
 
-class FFTBatchNodeF64(_Handle):
-    """FFTBatchNode<f64>::new(fft_size, ifft) / run (fft_node.rs:65-83) on Complex<f64> = numpy complex128 (comms_fft_f64_*):
-    the instantiation of the reference's doc examples; correct to f64 rounding."""
-    _prefix = "comms_fft_f64"
-
-    def __init__(self, fft_size, ifft, device=0):
-        super().__init__()
-        self.fft_size = int(fft_size)
-        check(lib().comms_fft_f64_create(self.fft_size, 1 if ifft else 0, device, C.byref(self._h)))
-
-    def run(self, x):
-        x = np.ascontiguousarray(x, dtype=np.complex128).ravel()
-        out = np.empty_like(x)
-        check(lib().comms_fft_f64_run(self._h, _ptr(x), x.size, _ptr(out)))
-        return out
-
-    def run_dev(self, in_ptr, n, out_ptr, stream=0):
-        check(lib().comms_fft_f64_run_dev(self._h, in_ptr, n, out_ptr, stream))
-
-
-class FFTSampleNodeF64(FFTBatchNodeF64):
-    """FFTSampleNode<f64> (fft_node.rs:142-167), #[aggregate]: a sample per call, the spectrum every fft_size samples."""
+class _FFTSample:
+    """The #[aggregate] form over an _FFTBatch: a sample per call, None until fft_size samples arrived, then their transform."""
 
     def __init__(self, fft_size, ifft, device=0):
         super().__init__(fft_size, ifft, device)
         self._samples = []
 
     def run(self, sample):
-        self._samples.append(np.complex128(sample))
+        self._samples.append(self._dtype(sample))
         if len(self._samples) == self.fft_size:
-            res = FFTBatchNodeF64.run(self, np.array(self._samples, np.complex128))
+            res = _FFTBatch.run(self, np.array(self._samples, self._dtype))
             self._samples = []
             return res
         return None
 
 
-class FMDemodNodeF64(_Handle):
-    """FMDemodNode<f64>::new() / run (analog_node.rs:20-52; FM::demod analog.rs:22-35) on Complex<f64>."""
-    _prefix = "comms_fmdemod_f64"
-
-    def __init__(self, device=0):
-        super().__init__()
-        check(lib().comms_fmdemod_f64_create(device, C.byref(self._h)))
-
-    def run(self, x):
-        x = np.ascontiguousarray(x, dtype=np.complex128).ravel()
-        out = np.empty(x.size, np.float64)
-        check(lib().comms_fmdemod_f64_run(self._h, _ptr(x), x.size, _ptr(out)))
-        return out
-
-    def run_dev(self, in_ptr, n, out_ptr, stream=0):
-        check(lib().comms_fmdemod_f64_run_dev(self._h, in_ptr, n, out_ptr, stream))
-
-    @property
-    def prev(self):
-        p = np.zeros(1, np.complex128)
-        check(lib().comms_fmdemod_f64_get_prev(self._h, _ptr(p)))
-        return p[0]
-
-    @prev.setter
-    def prev(self, value):
-        p = np.array([value], np.complex128)
-        check(lib().comms_fmdemod_f64_set_prev(self._h, _ptr(p)))
+class FFTBatchNode(_FFTBatch):
+    """FFTBatchNode::new(fft_size, ifft) / run (fft_node.rs:65-83)."""
+    _prefix, _dtype, _arr = "comms_fft", np.complex64, staticmethod(_as_c64)
 
 
-class FFTSampleNode(FFTBatchNode):
+class FFTBatchNodeF64(_FFTBatch):
+    """FFTBatchNode<f64>::new(fft_size, ifft) / run (fft_node.rs:65-83) on Complex<f64> = numpy complex128 (comms_fft_f64_*):
+    the instantiation of the reference's doc examples; correct to f64 rounding."""
+    _prefix, _dtype, _arr = "comms_fft_f64", np.complex128, staticmethod(_flat_c128)
+
+
+class FFTSampleNode(_FFTSample, FFTBatchNode):
     """FFTSampleNode::new(fft_size, ifft) / run (fft_node.rs:142-167), #[aggregate]:
     push one sample; returns None until fft_size samples arrived, then the FFT."""
 
-    def __init__(self, fft_size, ifft, device=0):
-        super().__init__(fft_size, ifft, device)
-        self._samples = []
 
-    def run(self, sample):
-        self._samples.append(np.complex64(sample))
-        if len(self._samples) == self.fft_size:
-            res = FFTBatchNode.run(self, np.array(self._samples, np.complex64))
-            self._samples = []
-            return res
-        return None
+class FFTSampleNodeF64(_FFTSample, FFTBatchNodeF64):
+    """FFTSampleNode<f64> (fft_node.rs:142-167), #[aggregate]: a sample per call, the spectrum every fft_size samples."""
 
 
 # ------------------------------------------------------------------ fused chain
-class ChainNode(_Handle):
+class ChainNode(_History, _Handle):
     """mixer / FIR / decimate [/ FM demod] as one node (comms_chain_*), an additional node.
     mixer_after_fir=False: mixer -> FIR -> decimate [-> FM]; True: FIR -> mixer -> decimate."""
     _prefix = "comms_chain"
+    _state_get, _state_set = "_get_fir_state", "_set_fir_state"
 
     def __init__(self, dphase, phase, taps, rate, fm_demod, device=0, mixer_after_fir=False, unfused=False,
                  kernel="auto"):
@@ -684,20 +711,19 @@ class ChainNode(_Handle):
         check(lib().comms_chain_create_ex(float(dphase), float(phase), _ptr(taps), taps.size, self.rate,
                                           flags, device, C.byref(self._h)))
 
+    def _is_fused(self):
+        return _get(C.c_int32, lib().comms_chain_is_fused, self._h)
+
     @property
     def fused(self):
-        f = C.c_int32()
-        check(lib().comms_chain_is_fused(self._h, C.byref(f)))
-        return bool(f.value)
+        return bool(self._is_fused())
 
     @property
     def kernel(self):
         """"unfused", "freq" (fir_os1024_kernel; fir_os4096_kernel / fir_os16k_kernel in their decimating form for 258 ... 4097
         taps), "time" (fir_decim_kernel / fir_decim_wave_kernel), "time_any" (fir_decim_any_kernel) or "poly" (fir_poly8_kernel:
         forced, picked at creation for 258 ... 513 taps, or what the chain's last call ran on)."""
-        f = C.c_int32()
-        check(lib().comms_chain_is_fused(self._h, C.byref(f)))
-        return ("unfused", "freq", "time", "time_any", "poly")[f.value]
+        return ("unfused", "freq", "time", "time_any", "poly")[self._is_fused()]
 
     _fmt = "c32"
 
@@ -715,15 +741,9 @@ class ChainNode(_Handle):
         ceil(n / rate * bits_per_sym / 8) bytes; the inverse of PulseNode.set_input_format("bits", ...)), nearest of
         the 2**bits_per_sym points of `constellation` (None = digital.rs's tables; see comms_sym_to_bits for the rule);
         "c32" restores the default.  No FM chains.  History and phase carry across a switch."""
-        if fmt == "c32":
-            check(lib().comms_chain_set_output_format(self._h, _lib.SYM_C32, 0, None))
-            self._out_bits = 0
-            return self
-        if fmt != "bits":
+        if fmt not in ("c32", "bits"):
             raise ValueError("output format must be 'c32' or 'bits' (got %r)" % (fmt,))
-        cons = _constellation(constellation, bits_per_sym)
-        check(lib().comms_chain_set_output_format(self._h, _lib.SYM_BITS, int(bits_per_sym), None if cons is None else _ptr(cons)))
-        self._out_bits = int(bits_per_sym)
+        self._out_bits = _set_bits_format(lib().comms_chain_set_output_format, self._h, bits_per_sym if fmt == "bits" else None, constellation)
         return self
 
     def out_bytes(self, n):
@@ -747,21 +767,15 @@ class ChainNode(_Handle):
 
     def set_fir_state(self, state):
         """FIR history, reference layout (newest first) -- e.g. the halo of a sharded stream."""
-        st = _as_c64(state)
-        check(lib().comms_chain_set_fir_state(self._h, _ptr(st), st.size))
-        return self
+        return self.set_state(state)
 
     def fir_state(self, n_state):
-        st = np.empty(int(n_state), np.complex64)
-        check(lib().comms_chain_get_fir_state(self._h, _ptr(st), st.size))
-        return st
+        return self.get_state(n_state)
 
     @property
     def phase(self):
         """Oscillator phase of the next input sample."""
-        p = C.c_double()
-        check(lib().comms_chain_get_phase(self._h, C.byref(p)))
-        return p.value
+        return _get(C.c_double, lib().comms_chain_get_phase, self._h)
 
     @phase.setter
     def phase(self, value):
@@ -780,7 +794,7 @@ class ChainNode(_Handle):
         check(lib().comms_chain_set_fm_prev(self._h, _ptr(p)))
 
 
-# ------------------------------------------------------------------ tap design
+# ------------------------------------------------------------------ stream nodes with a device history
 class RealFirDecimNode(_History, _Handle):
     """Real FIR with decimation (comms_rfir_*): the audio stage of examples/fm_radio.rs:98-164 -- Convert2Node ->
     BatchFirNode<f32> -> Convert3Node -> DecimateNode<f32>(rate) -- as one node over an f32 stream.  Any batch length:
@@ -799,9 +813,7 @@ class RealFirDecimNode(_History, _Handle):
             check(lib().comms_rfir_create(_ptr(taps), taps.size, _ptr(state), state.size, self.rate, device, C.byref(self._h)))
 
     def out_len(self, n):
-        m = C.c_size_t()
-        check(lib().comms_rfir_out_len(n, self.rate, C.byref(m)))
-        return m.value
+        return _get(C.c_size_t, lib().comms_rfir_out_len, n, self.rate)
 
     def kernel(self, n):
         """What a batch of n samples is run by: "rfir_decim_kernel<..>", or "series: ..." (the four launches)."""
@@ -835,9 +847,7 @@ class ResampleNode(_History, _Handle):
         check(lib().comms_resample_create(_ptr(taps), taps.size, self.up, self.down, self.dtype.itemsize, device, C.byref(self._h)))
 
     def out_len(self, n):
-        m = C.c_size_t()
-        check(lib().comms_resample_out_len(n, self.up, self.down, C.byref(m)))
-        return m.value
+        return _get(C.c_size_t, lib().comms_resample_out_len, n, self.up, self.down)
 
     def kernel(self, n):
         """What a batch of n samples is run by: "resample_kernel<..> tile=.. lds=.. tiles=.. grid=.. max_grid=..", or "series: ..."
@@ -875,9 +885,7 @@ class ChannelizerNode(_History, _Handle):
 
     def out_len(self, n):
         """Frames of a call of n samples; the call writes out_len(n) * channels outputs."""
-        m = C.c_size_t()
-        check(lib().comms_channelizer_out_len(n, self.down, C.byref(m)))
-        return m.value
+        return _get(C.c_size_t, lib().comms_channelizer_out_len, n, self.down)
 
     def kernel(self, n):
         """What a batch of n samples is run by: "channelizer_kernel<..> ...", or "series: ..." (the launches)."""
@@ -900,9 +908,7 @@ class ChannelizerNode(_History, _Handle):
 
     def get_phase(self):
         """The stream index of the next input sample, mod channels."""
-        t = C.c_uint64()
-        check(lib().comms_channelizer_get_phase(self._h, C.byref(t)))
-        return t.value
+        return _get(C.c_uint64, lib().comms_channelizer_get_phase, self._h)
 
     def set_phase(self, t):
         """Any stream index t >= 0 (reduced mod channels): where a shard starts."""
@@ -933,9 +939,7 @@ class SymbolSyncNode(_History, _Handle):
 
     def get_timing(self):
         """mu, in steps of 1 / phases input samples: 0 <= mu < sps * phases."""
-        mu = C.c_uint32()
-        check(lib().comms_symsync_get_timing(self._h, C.byref(mu)))
-        return mu.value
+        return _get(C.c_uint32, lib().comms_symsync_get_timing, self._h)
 
     timing = property(get_timing, set_timing)
 
@@ -948,9 +952,7 @@ class SymbolSyncNode(_History, _Handle):
 
     def get_rotation(self):
         """(dphase as given, phase of the next output in [0, 2 pi))."""
-        ph = C.c_double()
-        check(lib().comms_symsync_get_phase(self._h, C.byref(ph)))
-        return self._dphase, ph.value
+        return self._dphase, _get(C.c_double, lib().comms_symsync_get_phase, self._h)
 
     rotation = property(get_rotation, lambda self, v: self.set_rotation(*v))
 
@@ -958,20 +960,12 @@ class SymbolSyncNode(_History, _Handle):
         """bits_per_sym 1 or 2: run() returns hard decisions as packed bits (np.uint8, LSB first, ceil(n / sps *
         bits_per_sym / 8) bytes), nearest of the 2**bits_per_sym points of `constellation` (None = digital.rs's tables; see
         comms_sym_to_bits for the rule); None restores Complex<f32>.  State, phase and timing carry across a switch."""
-        if bits_per_sym is None:
-            check(lib().comms_symsync_set_output_format(self._h, _lib.SYM_C32, 0, None))
-            self._out_bits = 0
-            return self
-        cons = _constellation(constellation, bits_per_sym)
-        check(lib().comms_symsync_set_output_format(self._h, _lib.SYM_BITS, int(bits_per_sym), None if cons is None else _ptr(cons)))
-        self._out_bits = int(bits_per_sym)
+        self._out_bits = _set_bits_format(lib().comms_symsync_set_output_format, self._h, bits_per_sym, constellation)
         return self
 
     def out_len(self, n):
         """Symbols of a call of n samples."""
-        m = C.c_size_t()
-        check(lib().comms_symsync_out_len(n, self.sps, C.byref(m)))
-        return m.value
+        return _get(C.c_size_t, lib().comms_symsync_out_len, n, self.sps)
 
     def out_bytes(self, n):
         n_sym = self.out_len(n)
@@ -993,6 +987,7 @@ class SymbolSyncNode(_History, _Handle):
     state = property(_History.get_state, _History.set_state)
 
 
+# ------------------------------------------------------------------ tap design
 def _taps(fn, n_taps, *args):
     out = np.empty(int(n_taps), np.complex64)
     check(fn(int(n_taps), *args, _ptr(out)))
@@ -1089,6 +1084,18 @@ def _constellation(constellation, bits_per_sym):
     return cons
 
 
+def _set_bits_format(fn, h, bits_per_sym, constellation):
+    """The comms_*_set_{input,output}_format of a node that reads or writes packed bits beside Complex<f32>: bits_per_sym bits
+    per symbol against `constellation` (None = digital.rs's tables), or Complex<f32> with bits_per_sym None.  Returns the bits
+    per symbol now set (0: Complex<f32>)."""
+    if bits_per_sym is None:
+        check(fn(h, _lib.SYM_C32, 0, None))
+        return 0
+    cons = _constellation(constellation, bits_per_sym)
+    check(fn(h, _lib.SYM_BITS, int(bits_per_sym), None if cons is None else _ptr(cons)))
+    return int(bits_per_sym)
+
+
 def sym_to_bits(sym, bits_per_sym, constellation=None, device=0):
     """Complex<f32> symbols -> packed hard-decision bits (np.uint8, LSB first, ceil(n * bits_per_sym / 8) bytes):
     nearest of the 2**bits_per_sym points of `constellation` (None = digital.rs's tables), by comms_sym_to_bits's rule."""
@@ -1112,18 +1119,22 @@ def bit_errors(a, b, n_bits, device=0):
     n_bits = int(n_bits)
     if min(a.size, b.size) * 8 < n_bits:
         raise ValueError("the arrays hold fewer than n_bits bits")
-    out = C.c_uint64()
-    check(lib().comms_bit_errors(_ptr(a), _ptr(b), n_bits, C.byref(out), device))
-    return out.value
+    return _get(C.c_uint64, lib().comms_bit_errors, _ptr(a), _ptr(b), n_bits, tail=(device,))
 
 
 def bit_errors_dev(a_ptr, b_ptr, n_bits, device=0, stream=0):
-    out = C.c_uint64()
-    check(lib().comms_bit_errors_dev(a_ptr, b_ptr, int(n_bits), C.byref(out), device, stream))
-    return out.value
+    return _get(C.c_uint64, lib().comms_bit_errors_dev, a_ptr, b_ptr, int(n_bits), tail=(device, stream))
 
 
 # ------------------------------------------------------------------ PRNS source
+def _bits_out(fn, h, n, packed):
+    """The next n bits of a bit source's host entry: uint8 0 / 1 per bit, or packed LSB first."""
+    n = int(n)
+    out = np.empty((n + 7) // 8 if packed else n, np.uint8)
+    check(fn(h, n, _lib.BITS_PACKED if packed else _lib.BITS_U8, _ptr(out)))
+    return out
+
+
 class PrnsNode(_Handle):
     """PrnsNode::new(poly_mask, state) (prns.rs:93-137) on an unsigned register of `width` = 8, 16, 32 or 64 bits:
     run() returns the next bit, as the reference; run_batch(n) the next n bits (uint8 0/1 per bit, or packed LSB
@@ -1139,19 +1150,14 @@ class PrnsNode(_Handle):
         return int(self.run_batch(1)[0])
 
     def run_batch(self, n, packed=False):
-        n = int(n)
-        out = np.empty((n + 7) // 8 if packed else n, np.uint8)
-        check(lib().comms_prns_run(self._h, n, _lib.BITS_PACKED if packed else _lib.BITS_U8, _ptr(out)))
-        return out
+        return _bits_out(lib().comms_prns_run, self._h, n, packed)
 
     def run_dev(self, n, out_ptr, packed=False, stream=0):
         check(lib().comms_prns_run_dev(self._h, int(n), _lib.BITS_PACKED if packed else _lib.BITS_U8, out_ptr, stream))
 
     @property
     def state(self):
-        v = C.c_uint64()
-        check(lib().comms_prns_get_state(self._h, C.byref(v)))
-        return v.value
+        return _get(C.c_uint64, lib().comms_prns_get_state, self._h)
 
     @state.setter
     def state(self, value):
@@ -1177,9 +1183,7 @@ class NoiseSource(_Handle):
 
     @property
     def pos(self):
-        v = C.c_uint64()
-        check(lib().comms_noise_get_pos(self._h, C.byref(v)))
-        return v.value
+        return _get(C.c_uint64, lib().comms_noise_get_pos, self._h)
 
     @pos.setter
     def pos(self, value):
@@ -1191,10 +1195,7 @@ class NoiseSource(_Handle):
 
     def bits(self, n, packed=False):
         """The next n bits: uint8 0 / 1 per bit, or packed LSB first (the PRNS layout)."""
-        n = int(n)
-        out = np.empty((n + 7) // 8 if packed else n, np.uint8)
-        check(lib().comms_noise_bits_run(self._h, n, _lib.BITS_PACKED if packed else _lib.BITS_U8, _ptr(out)))
-        return out
+        return _bits_out(lib().comms_noise_bits_run, self._h, n, packed)
 
     def bits_dev(self, n, out_ptr, packed=False, stream=0):
         check(lib().comms_noise_bits_run_dev(self._h, int(n), _lib.BITS_PACKED if packed else _lib.BITS_U8, out_ptr, stream))
@@ -1242,25 +1243,19 @@ class NoiseSource(_Handle):
 def frequency_offset_estimate(samples, device=0):
     """frequency_estimator.rs:27-42 on Complex<f64> samples."""
     x = np.ascontiguousarray(samples, dtype=np.complex128)
-    out = C.c_double()
-    check(lib().comms_frequency_offset_estimate(_ptr(x), x.size, C.byref(out), device))
-    return out.value
+    return _get(C.c_double, lib().comms_frequency_offset_estimate, _ptr(x), x.size, tail=(device,))
 
 
 def psk_phase_estimate(symbols, m, device=0):
     """phase_estimator.rs:26-33."""
     x = np.ascontiguousarray(symbols, dtype=np.complex128)
-    out = C.c_double()
-    check(lib().comms_psk_phase_estimate(_ptr(x), x.size, int(m), C.byref(out), device))
-    return out.value
+    return _get(C.c_double, lib().comms_psk_phase_estimate, _ptr(x), x.size, int(m), tail=(device,))
 
 
 def qam_phase_estimate(symbols, device=0):
     """phase_estimator.rs:58-65."""
     x = np.ascontiguousarray(symbols, dtype=np.complex128)
-    out = C.c_double()
-    check(lib().comms_qam_phase_estimate(_ptr(x), x.size, C.byref(out), device))
-    return out.value
+    return _get(C.c_double, lib().comms_qam_phase_estimate, _ptr(x), x.size, tail=(device,))
 
 
 class TimingEstimatorNode(_Handle):
@@ -1274,14 +1269,10 @@ class TimingEstimatorNode(_Handle):
 
     def run(self, samples):
         x = np.ascontiguousarray(samples, dtype=np.complex128)
-        out = C.c_double()
-        check(lib().comms_timing_push(self._h, _ptr(x), x.size, C.byref(out)))
-        return out.value
+        return _get(C.c_double, lib().comms_timing_push, self._h, _ptr(x), x.size)
 
     def run_dev(self, in_ptr, n, stream=0):
-        out = C.c_double()
-        check(lib().comms_timing_push_dev(self._h, in_ptr, n, C.byref(out), stream))
-        return out.value
+        return _get(C.c_double, lib().comms_timing_push_dev, self._h, in_ptr, n, tail=(stream,))
 
     def kernel(self, n):
         """What a block of n samples is run by: "timing_kernel tile=.. wg=.. taps=.. filter_passes=.. tiles=.. grid=.. max_grid=.."."""
@@ -1336,29 +1327,21 @@ class SyncEstimatorNode(_Handle):
 def psk_phase_estimate_c32(symbols, m, device=0):
     """phase_estimator.rs:26-33 on Complex<f32> symbols (widened in the kernel's load)."""
     x = np.ascontiguousarray(symbols, dtype=np.complex64)
-    out = C.c_double()
-    check(lib().comms_psk_phase_estimate_c32(_ptr(x), x.size, int(m), C.byref(out), device))
-    return out.value
+    return _get(C.c_double, lib().comms_psk_phase_estimate_c32, _ptr(x), x.size, int(m), tail=(device,))
 
 
 def qam_phase_estimate_c32(symbols, device=0):
     """phase_estimator.rs:58-65 on Complex<f32> symbols."""
     x = np.ascontiguousarray(symbols, dtype=np.complex64)
-    out = C.c_double()
-    check(lib().comms_qam_phase_estimate_c32(_ptr(x), x.size, C.byref(out), device))
-    return out.value
+    return _get(C.c_double, lib().comms_qam_phase_estimate_c32, _ptr(x), x.size, tail=(device,))
 
 
 def psk_phase_estimate_c32_dev(in_ptr, n, m, device=0, stream=0):
-    out = C.c_double()
-    check(lib().comms_psk_phase_estimate_c32_dev(in_ptr, n, int(m), C.byref(out), device, stream))
-    return out.value
+    return _get(C.c_double, lib().comms_psk_phase_estimate_c32_dev, in_ptr, n, int(m), tail=(device, stream))
 
 
 def qam_phase_estimate_c32_dev(in_ptr, n, device=0, stream=0):
-    out = C.c_double()
-    check(lib().comms_qam_phase_estimate_c32_dev(in_ptr, n, C.byref(out), device, stream))
-    return out.value
+    return _get(C.c_double, lib().comms_qam_phase_estimate_c32_dev, in_ptr, n, tail=(device, stream))
 
 
 class _FrameDetectionStruct(C.Structure):
@@ -1410,23 +1393,14 @@ class FrameSyncNode(_History, _Detector, _Handle):
 
     def run(self, symbols, cap=None, raw=False):
         x = np.ascontiguousarray(symbols, dtype=np.complex64)
-        cap = self._cap(x.size, cap)
-        out, found = np.zeros(cap, FRAME_DETECTION_DTYPE), C.c_size_t()
-        check(lib().comms_framesync_run(self._h, _ptr(x), x.size, _ptr(out) if cap else None, cap, C.byref(found)))
-        return self._result(out, cap, found, raw)
+        return self._detect(lib().comms_framesync_run, x.size, cap, raw, _ptr(x), x.size)
 
     def run_dev(self, in_ptr, n, cap=None, stream=0, raw=False):
-        cap = self._cap(n, cap)
-        out, found = np.zeros(cap, FRAME_DETECTION_DTYPE), C.c_size_t()
-        check(lib().comms_framesync_run_dev(self._h, in_ptr, n, _ptr(out) if cap else None, cap, C.byref(found), stream))
-        return self._result(out, cap, found, raw)
+        return self._detect(lib().comms_framesync_run_dev, n, cap, raw, in_ptr, n, tail=(stream,))
 
     def flush(self, cap=None, raw=False):
         """The positions still undecided, as if n_word + guard zero symbols followed; history zero afterwards, position kept."""
-        cap = self._cap(self.n_word + self.guard, cap)
-        out, found = np.zeros(cap, FRAME_DETECTION_DTYPE), C.c_size_t()
-        check(lib().comms_framesync_flush(self._h, _ptr(out) if cap else None, cap, C.byref(found)))
-        return self._result(out, cap, found, raw)
+        return self._detect(lib().comms_framesync_flush, self.n_word + self.guard, cap, raw)
 
     state = _History.get_state   # the last n_state symbols (default: all n_word + 2 guard - 1), newest first
 
@@ -1500,14 +1474,12 @@ class DeframeNode(_History, _Position, _Handle):
         check(lib().comms_deframe_set_llr_scale(self._h, float(scale)))
         return self
 
-    def frame_bytes(self):
-        return lib().comms_deframe_frame_bytes(self._h)
+    frame_bytes = _record("comms_deframe_frame_bytes")      # frame_bytes(): bytes of one output record in the format set
 
     def frames_ready(self, n, detections=None):
         """How many frames a call on n symbols with these detections would emit (host arithmetic)."""
-        det, count = _as_detections(detections), C.c_size_t()
-        check(lib().comms_deframe_frames_ready(self._h, int(n), _ptr(det) if det.size else None, det.size, C.byref(count)))
-        return count.value
+        det = _as_detections(detections)
+        return _get(C.c_size_t, lib().comms_deframe_frames_ready, self._h, int(n), _ptr(det) if det.size else None, det.size)
 
     def _shape(self, raw, n_frames):
         dtype = {"c32": np.complex64, "bits": np.uint8, "llr": np.float32}[self.format]
@@ -1537,9 +1509,7 @@ class DeframeNode(_History, _Position, _Handle):
 
     def flush(self):
         """Drops the pending (incomplete) frames and returns how many; history zero afterwards, position kept."""
-        dropped = C.c_size_t()
-        check(lib().comms_deframe_flush(self._h, C.byref(dropped)))
-        return dropped.value
+        return _get(C.c_size_t, lib().comms_deframe_flush, self._h)
 
     state = _History.get_state   # the last n_state symbols (default: all max(lookback, n_payload - 1)), newest first
 
@@ -1547,10 +1517,9 @@ class DeframeNode(_History, _Position, _Handle):
 
     def pending(self):
         """The frames admitted and not yet complete (FRAME_HEADER_DTYPE), ascending."""
-        n = C.c_size_t()
-        check(lib().comms_deframe_get_pending(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, FRAME_HEADER_DTYPE)
-        check(lib().comms_deframe_get_pending(self._h, _ptr(out) if n.value else None, n.value, C.byref(n)))
+        n = _get(C.c_size_t, lib().comms_deframe_get_pending, self._h, None, 0)
+        out = np.zeros(n, FRAME_HEADER_DTYPE)
+        _get(C.c_size_t, lib().comms_deframe_get_pending, self._h, _ptr(out) if n else None, n)
         return out
 
     def set_pending(self, pending):
@@ -1573,12 +1542,13 @@ def _conv_args(K, n, gens, terminated):
     return int(K), n, g, _lib.CONV_TERMINATED if terminated else _lib.CONV_TRUNCATED
 
 
-class ConvEncoderNode(_Handle):
+class ConvEncoderNode(_FrameNode, _Handle):
     """Rate-1/n convolutional encoder (comms_convenc_*): frame-major records of `n_info_bits` packed bits (LSB first, each
     record ceil(bits / 8) bytes rounded up to 4) -> records of n * steps coded bits, coded bit j of step t at t * n + j, all
     frames of a call in one launch.  terminated=True appends K - 1 zero bits (steps = n_info_bits + K - 1).  Stateless:
     every frame starts in state 0.  run() takes and returns uint8 arrays of shape (n_frames, frame bytes)."""
     _prefix = "comms_convenc"
+    _frame = _frame_call(_prefix, np.uint8, np.uint8)
 
     def __init__(self, n_info_bits, K=7, gens=None, n=None, terminated=True, device=0):
         super().__init__()
@@ -1586,32 +1556,12 @@ class ConvEncoderNode(_Handle):
         self.n_info_bits, self.K, self.n = int(n_info_bits), K, n
         check(lib().comms_convenc_create(K, n, None if g is None else _ptr(g), flags, self.n_info_bits, device, C.byref(self._h)))
 
-    @property
-    def in_frame_bytes(self):
-        return lib().comms_convenc_in_frame_bytes(self._h)
-
-    @property
-    def out_frame_bytes(self):
-        return lib().comms_convenc_out_frame_bytes(self._h)
-
-    def run(self, frames):
-        x = np.ascontiguousarray(frames, dtype=np.uint8)
-        if x.size % self.in_frame_bytes:
-            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
-        n_frames = x.size // self.in_frame_bytes
-        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
-        check(lib().comms_convenc_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
-        return out
-
-    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
-        check(lib().comms_convenc_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
-
     def kernel(self, n_frames):
         """ "conv_encode_kernel wg=.. K=.. n=.. steps=.. words=.. grid=.. max_grid=.. lds=0" for a call on n_frames frames."""
         return self._kernel_name(int(n_frames))
 
 
-class ViterbiNode(_Handle):
+class ViterbiNode(_FrameNode, _Handle):
     """Viterbi decoder of ConvEncoderNode's code (comms_viterbi_*): frame-major records of `record_llrs` f32 LLRs (positive =
     bit 0; the first n * steps are used; None = exactly that many) -> records of `n_info_bits` decoded bits, all frames of a
     call in one launch, one wave per frame.  The decisions are integer arithmetic on q = clamp(rint(L * qscale), -127, 127)
@@ -1619,6 +1569,7 @@ class ViterbiNode(_Handle):
     valid input as it stands.  run() returns uint8 (n_frames, out_frame_bytes); with metrics=True also the final int32
     path metric of every frame."""
     _prefix = "comms_viterbi"
+    _frame = _frame_call(_prefix, np.float32, np.uint8)
 
     def __init__(self, n_info_bits, K=7, gens=None, n=None, terminated=True, record_llrs=None, qscale=None, device=0):
         super().__init__()
@@ -1635,28 +1586,11 @@ class ViterbiNode(_Handle):
         check(lib().comms_viterbi_set_quant_scale(self._h, float(qscale)))
         return self
 
-    @property
-    def in_frame_bytes(self):
-        return lib().comms_viterbi_in_frame_bytes(self._h)
-
-    @property
-    def out_frame_bytes(self):
-        return lib().comms_viterbi_out_frame_bytes(self._h)
-
     def run(self, llr, metrics=False):
-        x = np.ascontiguousarray(llr, dtype=np.float32)
-        per = self.in_frame_bytes // 4
-        if x.size % per:
-            raise ValueError("the input must hold whole records of in_frame_bytes / 4 values")
-        n_frames = x.size // per
-        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
-        m = np.zeros(n_frames, np.int32)
-        check(lib().comms_viterbi_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None,
-                                      _ptr(m) if metrics and n_frames else None))
-        return (out, m) if metrics else out
+        return self._frame.run(self, llr, side=(np.int32,)) if metrics else self._frame.run(self, llr, tail=(None,))
 
     def run_dev(self, llr_ptr, n_frames, bits_ptr, metrics_ptr=None, stream=0):
-        check(lib().comms_viterbi_run_dev(self._h, llr_ptr, int(n_frames), bits_ptr, metrics_ptr, stream))
+        self._frame.run_dev(self, llr_ptr, n_frames, bits_ptr, metrics_ptr, stream)
 
     def kernel(self, n_frames):
         """ "viterbi_kernel<n,lds|workspace> wg=.. waves=.. K=.. steps=.. seam=.. grid=.. max_grid=.. lds=.. workspace=.."."""
@@ -1672,13 +1606,14 @@ def _ldpc_base(base, Z):
     return B, int(Z)
 
 
-class LdpcEncoderNode(_Handle):
+class LdpcEncoderNode(_FrameNode, _Handle):
     """Encoder of a quasi-cyclic LDPC code with a dual-diagonal parity part (comms_ldpcenc_*): `base` is the mb x nb base
     matrix (-1: zero block; b >= 0: check z of block row i touches variable j Z + (z + b) mod Z), Z the lifting size.
     Frame-major records of T = (nb - mb) Z packed bits (LSB first, each record ceil(bits / 8) bytes rounded up to 4) ->
     records of N = nb Z coded bits [u | p_0 | ... | p_{mb-1}], all frames of a call in one launch, one wave per frame.
     run() takes and returns uint8 arrays of shape (n_frames, frame bytes)."""
     _prefix = "comms_ldpcenc"
+    _frame = _frame_call(_prefix, np.uint8, np.uint8)
 
     def __init__(self, base, Z, device=0):
         super().__init__()
@@ -1687,32 +1622,12 @@ class LdpcEncoderNode(_Handle):
         self.n_info_bits, self.n_coded_bits = (self.nb - self.mb) * self.Z, self.nb * self.Z
         check(lib().comms_ldpcenc_create(self.mb, self.nb, self.Z, _ptr(B), device, C.byref(self._h)))
 
-    @property
-    def in_frame_bytes(self):
-        return lib().comms_ldpcenc_in_frame_bytes(self._h)
-
-    @property
-    def out_frame_bytes(self):
-        return lib().comms_ldpcenc_out_frame_bytes(self._h)
-
-    def run(self, frames):
-        x = np.ascontiguousarray(frames, dtype=np.uint8)
-        if x.size % self.in_frame_bytes:
-            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
-        n_frames = x.size // self.in_frame_bytes
-        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
-        check(lib().comms_ldpcenc_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
-        return out
-
-    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
-        check(lib().comms_ldpcenc_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
-
     def kernel(self, n_frames):
         """ "ldpc_encode_kernel wg=.. frames_per_wg=.. Z=.. grid=.. lds=.." for a call on n_frames frames."""
         return self._kernel_name(int(n_frames))
 
 
-class LdpcDecoderNode(_Handle):
+class LdpcDecoderNode(_FrameNode, _Handle):
     """Layered normalised min-sum decoder of LdpcEncoderNode's code family (comms_ldpcdec_*; any base matrix within the
     limits): frame-major records of `record_llrs` f32 LLRs (positive = bit 0; the first N are used; 0 = exactly N) ->
     records of T decoded bits, all frames of a call in one launch, one wave per frame, a frame's state in LDS.  Integer
@@ -1721,6 +1636,7 @@ class LdpcDecoderNode(_Handle):
     the definition exactly.  run() returns uint8 (n_frames, out_frame_bytes); with status=True also one int32 per frame:
     the iterations run if the frame converged, -max_iters if it did not."""
     _prefix = "comms_ldpcdec"
+    _frame = _frame_call(_prefix, np.float32, np.uint8)
 
     def __init__(self, base, Z, max_iters=20, norm16=12, record_llrs=0, qscale=1.0, device=0):
         super().__init__()
@@ -1737,28 +1653,11 @@ class LdpcDecoderNode(_Handle):
         check(lib().comms_ldpcdec_set_quant_scale(self._h, float(qscale)))
         return self
 
-    @property
-    def in_frame_bytes(self):
-        return lib().comms_ldpcdec_in_frame_bytes(self._h)
-
-    @property
-    def out_frame_bytes(self):
-        return lib().comms_ldpcdec_out_frame_bytes(self._h)
-
     def run(self, llr, status=False):
-        x = np.ascontiguousarray(llr, dtype=np.float32)
-        per = self.in_frame_bytes // 4
-        if x.size % per:
-            raise ValueError("the input must hold whole records of in_frame_bytes / 4 values")
-        n_frames = x.size // per
-        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
-        st = np.zeros(n_frames, np.int32)
-        check(lib().comms_ldpcdec_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None,
-                                      _ptr(st) if status and n_frames else None))
-        return (out, st) if status else out
+        return self._frame.run(self, llr, side=(np.int32,)) if status else self._frame.run(self, llr, tail=(None,))
 
     def run_dev(self, llr_ptr, n_frames, bits_ptr, status_ptr=None, stream=0):
-        check(lib().comms_ldpcdec_run_dev(self._h, llr_ptr, int(n_frames), bits_ptr, status_ptr, stream))
+        self._frame.run_dev(self, llr_ptr, n_frames, bits_ptr, status_ptr, stream)
 
     def kernel(self, n_frames):
         """ "ldpc_decode_kernel wg=.. waves=.. frames_per_wg=.. mb=.. nb=.. Z=.. edges=.. max_iters=.. grid=.. lds=.."."""
@@ -1766,7 +1665,7 @@ class LdpcDecoderNode(_Handle):
 
 
 # ------------------------------------------------------------------ rate matching
-class _RateMatch(_Handle):
+class _RateMatch(_FrameNode, _Handle):
     """One frame format of comms_ratematch_*: n_coded coded bits, a puncturing `pattern` (0 / 1 per coded position, repeated;
     None keeps everything), an interleaver over the n_tx_bits kept bits (`cols` columns of the pruned block interleaver, or an
     explicit `perm` with perm[k] the kept-bit index transmitted k-th) and `scramble`, n_tx_bits bits packed LSB first (uint8)
@@ -1810,29 +1709,10 @@ class RateMatchNode(_RateMatch):
     bits (the encoder's records) -> records of n_tx_bits bits, tx_bit[k] = in_bit[map()[k]] ^ scramble_bit[k], all frames of a
     call in one launch.  Stateless.  run() takes and returns uint8 arrays of shape (n_frames, frame bytes)."""
     _direction = _lib.RATEMATCH_TX
+    _frame = _frame_call("comms_ratematch_tx", np.uint8, np.uint8)
 
     def __init__(self, n_coded, pattern=None, cols=0, perm=None, scramble=None, device=0):
         super().__init__(n_coded, pattern, cols, perm, scramble, 0, device)
-
-    @property
-    def in_frame_bytes(self):
-        return lib().comms_ratematch_tx_in_frame_bytes(self._h)
-
-    @property
-    def out_frame_bytes(self):
-        return lib().comms_ratematch_tx_out_frame_bytes(self._h)
-
-    def run(self, frames):
-        x = np.ascontiguousarray(frames, dtype=np.uint8)
-        if x.size % self.in_frame_bytes:
-            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
-        n_frames = x.size // self.in_frame_bytes
-        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
-        check(lib().comms_ratematch_tx_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
-        return out
-
-    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
-        check(lib().comms_ratematch_tx_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
 
 
 class RateDematchNode(_RateMatch):
@@ -1841,31 +1721,17 @@ class RateDematchNode(_RateMatch):
     positions and elsewhere the input value with its sign bit toggled where the scramble bit is 1: a ViterbiNode input as it
     stands.  Stateless.  run() takes float32 and returns float32 (n_frames, n_coded)."""
     _direction = _lib.RATEMATCH_RX
-
-    @property
-    def in_frame_bytes(self):
-        return lib().comms_ratematch_rx_in_frame_bytes(self._h)
-
-    @property
-    def out_frame_bytes(self):
-        return lib().comms_ratematch_rx_out_frame_bytes(self._h)
+    _frame = _frame_call("comms_ratematch_rx", np.float32, np.float32)
 
     def run(self, llr):
-        x = np.ascontiguousarray(llr, dtype=np.float32)
-        per = self.in_frame_bytes // 4
-        if x.size % per:
-            raise ValueError("the input must hold whole records of in_frame_bytes / 4 values")
-        n_frames = x.size // per
-        out = np.zeros((n_frames, self.n_coded), np.float32)
-        check(lib().comms_ratematch_rx_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
-        return out
+        return self._frame.run(self, llr)
 
     def run_dev(self, llr_ptr, n_frames, out_ptr, stream=0):
-        check(lib().comms_ratematch_rx_run_dev(self._h, llr_ptr, int(n_frames), out_ptr, stream))
+        self._frame.run_dev(self, llr_ptr, n_frames, out_ptr, stream)
 
 
 # ------------------------------------------------------------------ frame check (CRC)
-class _Crc(_Handle):
+class _Crc(_FrameNode, _Handle):
     """One frame check of comms_crc_*: a `width`-bit CRC (1 ... 32) with polynomial `poly` (normal form, no x^width term),
     register `init` and final `xorout`, no reflection, over frames of `n_payload_bits` bits; the CRC follows the payload with
     its x^(width-1) coefficient first.  Records are packed LSB first, so (32, 0x04C11DB7, 0xFFFFFFFF, 0xFFFFFFFF) is the
@@ -1881,24 +1747,13 @@ class _Crc(_Handle):
                 raise ValueError("poly, init and xorout are unsigned 32-bit values")
         check(lib().comms_crc_create(self.width, int(poly), int(init), int(xorout), self.n_payload_bits, device, C.byref(self._h)))
 
-    @property
-    def payload_frame_bytes(self):
-        return lib().comms_crc_payload_frame_bytes(self._h)
-
-    @property
-    def coded_frame_bytes(self):
-        return lib().comms_crc_coded_frame_bytes(self._h)
+    _payload_bytes, _coded_bytes = _record("comms_crc_payload_frame_bytes"), _record("comms_crc_coded_frame_bytes")
+    payload_frame_bytes, coded_frame_bytes = property(_payload_bytes), property(_coded_bytes)
 
     def kernel(self, n_frames):
         """ "crc_attach_kernel | crc_check_kernel wg=.. group=.. rounds=.. width=.. words=.. frames=.. grid=.. max_grid=.. lds=0"
         for a call on n_frames frames."""
         return self._kernel_name(self._direction, int(n_frames))
-
-    def _frames(self, frames):
-        x = np.ascontiguousarray(frames, dtype=np.uint8)
-        if x.size % self.in_frame_bytes:
-            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
-        return x, x.size // self.in_frame_bytes
 
 
 class CrcAttachNode(_Crc):
@@ -1906,23 +1761,7 @@ class CrcAttachNode(_Crc):
     n_payload_bits + width bits, all frames of a call in one launch.  Stateless.  run() takes and returns uint8 arrays of shape
     (n_frames, frame bytes)."""
     _direction = _lib.CRC_ATTACH
-
-    @property
-    def in_frame_bytes(self):
-        return self.payload_frame_bytes
-
-    @property
-    def out_frame_bytes(self):
-        return self.coded_frame_bytes
-
-    def run(self, frames):
-        x, n_frames = self._frames(frames)
-        out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
-        check(lib().comms_crc_attach_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
-        return out
-
-    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
-        check(lib().comms_crc_attach_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+    _frame = _FrameCall("comms_crc_attach_run", np.uint8, np.uint8, _Crc._payload_bytes, _Crc._coded_bytes)
 
 
 class CrcCheckNode(_Crc):
@@ -1933,28 +1772,16 @@ class CrcCheckNode(_Crc):
     pointer per output, each may be None; the launch ADDS the call's failed frames to the uint32 at n_failed_ptr."""
     _direction = _lib.CRC_CHECK
     n_failed = 0
-
-    @property
-    def in_frame_bytes(self):
-        return self.coded_frame_bytes
-
-    @property
-    def out_frame_bytes(self):
-        return self.payload_frame_bytes
+    _frame = _FrameCall("comms_crc_check_run", np.uint8, np.uint8, _Crc._coded_bytes, _Crc._payload_bytes)
 
     def run(self, frames):
-        x, n_frames = self._frames(frames)
-        payload = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
-        passed = np.zeros(n_frames, np.int32)
-        crc = np.zeros(n_frames, np.uint32)
         failed = C.c_size_t(0)
-        p = (lambda a: _ptr(a) if n_frames else None)
-        check(lib().comms_crc_check_run(self._h, p(x), n_frames, p(payload), p(passed), p(crc), C.byref(failed)))
+        payload, passed, crc = self._frame.run(self, frames, side=(np.int32, np.uint32), tail=(C.byref(failed),))
         self.n_failed = failed.value
         return payload, passed, crc
 
     def run_dev(self, in_ptr, n_frames, payload_ptr=None, pass_ptr=None, crc_ptr=None, n_failed_ptr=None, stream=0):
-        check(lib().comms_crc_check_run_dev(self._h, in_ptr, int(n_frames), payload_ptr, pass_ptr, crc_ptr, n_failed_ptr, stream))
+        self._frame.run_dev(self, in_ptr, n_frames, payload_ptr, pass_ptr, crc_ptr, n_failed_ptr, stream)
 
 
 # ------------------------------------------------------------------ symbol mapper and soft demapper
@@ -1977,7 +1804,7 @@ def psk_table(bits_per_sym, scale=1.0):
     return _table("comms_constellation_psk", bits_per_sym, scale)
 
 
-class SymbolMapNode(_Handle):
+class SymbolMapNode(_FrameNode, _Handle):
     """Packed bit records -> frames of Complex<f32> symbols (comms_symmap_*), behind RateMatchNode and in front of PulseNode in
     "c32" input format: every record of n_bits bits (RateMatchNode's output record) becomes `word` (the known word a
     FrameSyncNode looks for, or None), ceil(n_bits / bits_per_sym) payload symbols table[v] -- v the record's next
@@ -1985,6 +1812,7 @@ class SymbolMapNode(_Handle):
     in one launch.  constellation: 2**bits_per_sym points (qam_table, psk_table, or any), None = digital.rs's tables at 1 or 2
     bits.  Stateless.  run() takes uint8 (n_frames, in_frame_bytes) and returns complex64 (n_frames, out_frame_syms)."""
     _prefix = "comms_symmap"
+    _frame = _FrameCall("comms_symmap_run", np.uint8, np.complex64, _record("comms_symmap_in_frame_bytes"), _record("comms_symmap_out_frame_syms", 8))
 
     def __init__(self, bits_per_sym, constellation, n_bits, word=None, gap=0, device=0):
         super().__init__()
@@ -1998,35 +1826,15 @@ class SymbolMapNode(_Handle):
                                         C.byref(self._h)))
 
     @property
-    def in_frame_bytes(self):
-        return lib().comms_symmap_in_frame_bytes(self._h)
-
-    @property
     def out_frame_syms(self):
-        return lib().comms_symmap_out_frame_syms(self._h)
-
-    @property
-    def out_frame_bytes(self):
-        return 8 * self.out_frame_syms
-
-    def run(self, frames):
-        x = np.ascontiguousarray(frames, dtype=np.uint8)
-        if x.size % self.in_frame_bytes:
-            raise ValueError("the input must hold whole records of in_frame_bytes bytes")
-        n_frames = x.size // self.in_frame_bytes
-        out = np.zeros((n_frames, self.out_frame_syms), np.complex64)
-        check(lib().comms_symmap_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
-        return out
-
-    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
-        check(lib().comms_symmap_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+        return self.out_frame_bytes // 8
 
     def kernel(self, n_frames):
         """ "symmap_kernel wg=.. bits=.. n_bits=.. word=.. payload=.. gap=.. syms=.. frames=.. grid=.. max_grid=.. lds=.."."""
         return self._kernel_name(int(n_frames))
 
 
-class DemapNode(_Handle):
+class DemapNode(_FrameNode, _Handle):
     """Records of n_payload Complex<f32> symbols -> max-log LLRs ("llr", the default: bits_per_sym float32 per symbol, positive
     = bit 0, scaled by llr_scale = 1 / (2 sigma^2)) or packed hard bits ("bits") against a table of 2**bits_per_sym points
     (comms_demap_*), all frames of a call in one launch: behind DeframeNode in "c32" format with normalise=True, in front of
@@ -2035,6 +1843,8 @@ class DemapNode(_Handle):
     keeps the general form.  Stateless.  run() takes complex64 and returns float32 (n_frames, n_payload * bits_per_sym) or
     uint8 (n_frames, out_frame_bytes)."""
     _prefix = "comms_demap"
+    _formats = {"llr": _frame_call(_prefix, np.complex64, np.float32), "bits": _frame_call(_prefix, np.complex64, np.uint8)}
+    _frame = property(lambda self: self._formats[self.format])
 
     def __init__(self, bits_per_sym, constellation, n_payload, force_table=False, device=0):
         super().__init__()
@@ -2058,28 +1868,11 @@ class DemapNode(_Handle):
         check(lib().comms_demap_set_llr_scale(self._h, float(scale)))
         return self
 
-    @property
-    def in_frame_bytes(self):
-        return lib().comms_demap_in_frame_bytes(self._h)
-
-    @property
-    def out_frame_bytes(self):
-        return lib().comms_demap_out_frame_bytes(self._h)
-
     def run(self, symbols):
-        x = _as_c64(symbols).ravel()
-        if x.size % self.n_payload:
-            raise ValueError("the input must hold whole records of n_payload symbols")
-        n_frames = x.size // self.n_payload
-        if self.format == "llr":
-            out = np.zeros((n_frames, self.n_payload * self.bits_per_sym), np.float32)
-        else:
-            out = np.zeros((n_frames, self.out_frame_bytes), np.uint8)
-        check(lib().comms_demap_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
-        return out
+        return self._frame.run(self, symbols)
 
     def run_dev(self, sym_ptr, n_frames, out_ptr, stream=0):
-        check(lib().comms_demap_run_dev(self._h, sym_ptr, int(n_frames), out_ptr, stream))
+        self._frame.run_dev(self, sym_ptr, n_frames, out_ptr, stream)
 
     def kernel(self, n_frames):
         """ "demap_table_kernel<m,fmt> form=table ..." or "demap_axis_kernel<mI,mQ,fmt> form=axis ...", then "wg=.. bits=..
@@ -2088,7 +1881,7 @@ class DemapNode(_Handle):
 
 
 # ------------------------------------------------------------------ OFDM modulator and demodulator
-class _Ofdm(_Handle):
+class _Ofdm(_FrameNode, _Handle):
     """One OFDM frame format of comms_ofdm_*: n_fft (64 ... 1024) bins, a cyclic prefix of n_cp samples, carrier_kind[n_fft]
     (0 null, 1 data, 2 pilot; bin 0 is DC), the base `pilots` in increasing bin order, `polarity` (floats that multiply the
     pilots of data symbol s by polarity[s mod len]; None = 1), n_train identical training symbols of frequency values
@@ -2121,29 +1914,22 @@ class _Ofdm(_Handle):
         check(lib().comms_ofdm_set_scale(self._h, float(tx_scale)))
         return self
 
+    _data_bytes, _sample_bytes = _record("comms_ofdm_data_syms", 8), _record("comms_ofdm_frame_samples", 8)
+
     @property
     def data_syms(self):
         """Data-carrier values per record: n_syms * (data carriers)."""
-        return lib().comms_ofdm_data_syms(self._h)
+        return self._data_bytes() // 8
 
     @property
     def frame_samples(self):
         """(n_train + n_syms) * (n_fft + n_cp)."""
-        return lib().comms_ofdm_frame_samples(self._h)
+        return self._sample_bytes() // 8
 
     def kernel(self, n_frames):
         """ "ofdm_mod_kernel<N> | ofdm_demod_kernel<N> form=wave16 wg=.. n_fft=.. cp=.. data=.. pilots=.. train=.. syms=.. cpe=..
         lanes_per_sym=.. syms_per_wave=.. block=.. blocks=.. frames=.. items=.. grid=.. max_grid=.. lds=.." for a call on n_frames."""
         return self._kernel_name(self._direction, int(n_frames), cap=320)
-
-    def _run(self, fn, x, in_len, out_len):
-        x = _as_c64(x).ravel()
-        if not in_len or x.size % in_len:
-            raise ValueError("the input must hold whole records of %d values" % in_len)
-        n_frames = x.size // in_len
-        out = np.zeros((n_frames, out_len), np.complex64)
-        check(getattr(lib(), fn)(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(out) if n_frames else None))
-        return out
 
 
 class OfdmModNode(_Ofdm):
@@ -2151,12 +1937,10 @@ class OfdmModNode(_Ofdm):
     training symbols, inverse transform scaled by tx_scale, cyclic prefix; all frames of a call in one launch.  Stateless.  run()
     takes complex64 (n_frames, data_syms), symbol-major, and returns complex64 (n_frames, frame_samples)."""
     _direction = _lib.OFDM_MOD
+    _frame = _FrameCall("comms_ofdm_mod_run", np.complex64, np.complex64, _Ofdm._data_bytes, _Ofdm._sample_bytes)
 
     def run(self, symbols):
-        return self._run("comms_ofdm_mod_run", symbols, self.data_syms, self.frame_samples)
-
-    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
-        check(lib().comms_ofdm_mod_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+        return self._frame.run(self, symbols)
 
 
 class OfdmDemodNode(_Ofdm):
@@ -2165,12 +1949,10 @@ class OfdmDemodNode(_Ofdm):
     n_fft * tx_scale), one multiply per carrier, with cpe=True the pilots' common phase removed per symbol; all frames of a call
     in one launch.  Stateless.  run() takes complex64 (n_frames, frame_samples) and returns complex64 (n_frames, data_syms)."""
     _direction = _lib.OFDM_DEMOD
+    _frame = _FrameCall("comms_ofdm_demod_run", np.complex64, np.complex64, _Ofdm._sample_bytes, _Ofdm._data_bytes)
 
     def run(self, samples):
-        return self._run("comms_ofdm_demod_run", samples, self.frame_samples, self.data_syms)
-
-    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0):
-        check(lib().comms_ofdm_demod_run_dev(self._h, in_ptr, int(n_frames), out_ptr, stream))
+        return self._frame.run(self, samples)
 
 
 class OfdmSyncNode(_History, _Detector, _Handle):
@@ -2183,6 +1965,12 @@ class OfdmSyncNode(_History, _Detector, _Handle):
     exp(-i cfo[f] n), all records in one launch, in front of OfdmDemodNode.  `found` is the true count of the last call."""
     _prefix = "comms_ofdmsync"
     _state_args = ("lag", "window", "guard")
+    _side = (np.float64,)
+
+    def _record_bytes(self):
+        return 8 * self.n_frame
+
+    _correct = _FrameCall("comms_ofdmsync_correct_run", np.complex64, np.complex64, _record_bytes, _record_bytes)   # correct()
 
     def __init__(self, lag, window, threshold, guard, advance=0, n_frame=0, device=0):
         super().__init__()
@@ -2202,51 +1990,30 @@ class OfdmSyncNode(_History, _Detector, _Handle):
         """The least `lookback` of the DeframeNode behind this node."""
         return self.window + self.lag + self.guard + self.advance - 1
 
-    def _result(self, out, cfo, cap, found, raw):
-        dets = super()._result(out, cap, found, raw)
-        return dets, cfo[: len(dets)]
-
     def run(self, samples, cap=None, raw=False):
         x = np.ascontiguousarray(samples, dtype=np.complex64)
-        cap = self._cap(x.size, cap)
-        out, cfo, found = np.zeros(cap, FRAME_DETECTION_DTYPE), np.zeros(cap, np.float64), C.c_size_t()
-        check(lib().comms_ofdmsync_run(self._h, _ptr(x), x.size, _ptr(out) if cap else None, _ptr(cfo) if cap else None, cap,
-                                       C.byref(found)))
-        return self._result(out, cfo, cap, found, raw)
+        return self._detect(lib().comms_ofdmsync_run, x.size, cap, raw, _ptr(x), x.size)
 
     def run_dev(self, in_ptr, n, cap=None, stream=0, raw=False):
-        cap = self._cap(n, cap)
-        out, cfo, found = np.zeros(cap, FRAME_DETECTION_DTYPE), np.zeros(cap, np.float64), C.c_size_t()
-        check(lib().comms_ofdmsync_run_dev(self._h, in_ptr, n, _ptr(out) if cap else None, _ptr(cfo) if cap else None, cap,
-                                           C.byref(found), stream))
-        return self._result(out, cfo, cap, found, raw)
+        return self._detect(lib().comms_ofdmsync_run_dev, n, cap, raw, in_ptr, n, tail=(stream,))
 
     def flush(self, cap=None, raw=False):
         """The positions still undecided, as if window + lag + guard zero samples followed; history zero afterwards, position kept."""
-        cap = self._cap(self.window + self.lag + self.guard, cap)
-        out, cfo, found = np.zeros(cap, FRAME_DETECTION_DTYPE), np.zeros(cap, np.float64), C.c_size_t()
-        check(lib().comms_ofdmsync_flush(self._h, _ptr(out) if cap else None, _ptr(cfo) if cap else None, cap, C.byref(found)))
-        return self._result(out, cfo, cap, found, raw)
+        return self._detect(lib().comms_ofdmsync_flush, self.window + self.lag + self.guard, cap, raw)
 
     def correct(self, records, cfo):
         """complex64 (n_frames, n_frame) records and one cfo per record -> the records times exp(-i cfo n)."""
         x = _as_c64(records)
-        if not self.n_frame or x.size % self.n_frame:
-            raise ValueError("the input must hold whole records of n_frame = %d samples" % self.n_frame)
-        n_frames = x.size // self.n_frame
         w = np.ascontiguousarray(cfo, dtype=np.float64).ravel()
-        if w.size != n_frames:
-            raise ValueError("cfo holds one value per record")
-        out = np.zeros((n_frames, self.n_frame), np.complex64)
-        check(lib().comms_ofdmsync_correct_run(self._h, _ptr(x) if n_frames else None, n_frames, _ptr(w) if n_frames else None,
-                                               _ptr(out) if n_frames else None))
-        return out
+        if w.size * self.n_frame != x.size:
+            raise ValueError("records holds n_frame = %d samples, and cfo one value, per record" % self.n_frame)
+        return self._correct.run(self, x, pre=(w,))
 
     def correct_dev(self, in_ptr, n_frames, cfo, out_ptr, stream=0):
         w = np.ascontiguousarray(cfo, dtype=np.float64).ravel()
         if w.size != int(n_frames):
             raise ValueError("cfo holds one value per record")
-        check(lib().comms_ofdmsync_correct_run_dev(self._h, in_ptr, int(n_frames), _ptr(w) if w.size else None, out_ptr, stream))
+        self._correct.run_dev(self, in_ptr, n_frames, _ptr(w) if w.size else None, out_ptr, stream)
 
     state = _History.get_state   # the last n_state samples (default: all window + lag + 2 guard - 1), newest first
 
@@ -2289,9 +2056,7 @@ class NcoNode(_Handle):
 
     @property
     def phase(self):
-        out = C.c_double()
-        check(lib().comms_nco_get_phase(self._h, C.byref(out)))
-        return out.value
+        return _get(C.c_double, lib().comms_nco_get_phase, self._h)
 
 
 # ------------------------------------------------------------------ synthetic IQ
@@ -2343,16 +2108,12 @@ class KernelTimer:
 
     def read_ms(self):
         out = np.zeros(self.n, np.float32)
-        m = C.c_size_t()
-        check(lib().comms_timer_read(self._h, _ptr(out), self.n, C.byref(m)))
-        return out[:m.value].copy()
+        return out[: _get(C.c_size_t, lib().comms_timer_read, self._h, _ptr(out), self.n)].copy()
 
     def read_stamps_ms(self):
         """In-stream kernel durations of the stamped launches (0.0 where the launched kernel does not stamp)."""
         out = np.zeros(self.n, np.float32)
-        m = C.c_size_t()
-        check(lib().comms_timer_read_stamps(self._h, _ptr(out), self.n, C.byref(m)))
-        return out[:m.value].copy()
+        return out[: _get(C.c_size_t, lib().comms_timer_read_stamps, self._h, _ptr(out), self.n)].copy()
 
     def close(self):
         if self._h:

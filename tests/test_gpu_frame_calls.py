@@ -2,13 +2,16 @@
 node's smallest format and 3 frames, all through run_dev on DeviceBufs: n_frames = 0 with NULL pointers is a no-op; NULL
 pointers, misaligned pointers and overlapping input and output records with n_frames = 3 are refused with COMMS_ERR_ARG and
 launch nothing (a KernelTimer on the handle counts the launches); after every refusal a correct call on the same handle
-returns the records of the node's own reference (tests/*_ref.py).  No call here passes an unmapped pointer."""
+returns the records of the node's own reference (tests/*_ref.py).  No call here passes an unmapped pointer.
+test_frame_run_shell holds the host form, run(), of the same rows to the same references: any shape of whole records, no
+frames, and an input that is no whole number of records."""
 import collections
 
 import numpy as np
 import pytest
 
 import crc_ref as cr
+import ldpc_ref as lr
 import ofdm_ref as orf
 import ratematch_ref as rr
 import symmap_ref as sm
@@ -47,6 +50,27 @@ def viterbi(c):
     _, llr, bits, _ = vr.case_data(vc)
     node = c.ViterbiNode(vc.T, vc.K, vc.gens, terminated=vc.terminated, record_llrs=vc.record_llrs, qscale=vc.qscale)
     return Row(node, np.ascontiguousarray(llr, np.float32), node.out_frame_bytes, (4, 4), exact(vr.pack_records(bits)))
+
+
+LDPC_Z = 2
+LDPC_B = lr.make_base(3, 5, LDPC_Z, 51)             # the smallest base matrix of the encoder's form: T = 4, N = 10 bits
+
+
+def ldpcenc(c):
+    bits = np.random.default_rng(8).integers(0, 2, (FRAMES, 2 * LDPC_Z), dtype=np.uint8)
+    node = c.LdpcEncoderNode(LDPC_B, LDPC_Z)
+    return Row(node, lr.pack_records(bits), node.out_frame_bytes, (4, 4), exact(lr.pack_records(lr.ref_encode(bits, LDPC_B, LDPC_Z))))
+
+
+def ldpcdec(c):
+    """LLRs of random codewords, one of them with a wrong bit; the statuses are the decoder's own output and not in the row"""
+    rng = np.random.default_rng(9)
+    coded = lr.ref_encode(rng.integers(0, 2, (FRAMES, 2 * LDPC_Z), dtype=np.uint8), LDPC_B, LDPC_Z)
+    llr = ((1.0 - 2.0 * coded) * rng.uniform(2.0, 9.0, coded.shape)).astype(np.float32)
+    llr[1, 3] *= -0.25
+    bits, _ = lr.ref_decode(lr.ref_quantise(llr, 4.0), LDPC_B, LDPC_Z)
+    node = c.LdpcDecoderNode(LDPC_B, LDPC_Z, qscale=4.0)
+    return Row(node, llr, node.out_frame_bytes, (4, 4), exact(lr.pack_records(bits)))
 
 
 RM_N, RM_PATTERN = 8, rr.PATTERNS["3/4"]           # 6 of 8 coded bits are transmitted
@@ -117,16 +141,18 @@ def within(want, per, bound):
 def ofdm_mod(c):
     args, kw = OFDM.node_args()
     z = orf.data_values(OFDM, FRAMES)
-    return Row(c.OfdmModNode(*args, **kw), z, 8 * OFDM.frame_samples, (8, 8), within(orf.ref_mod(OFDM, z), OFDM.sym_len, orf.FFT_BOUND))
+    node = c.OfdmModNode(*args, **kw)
+    return Row(node, z, node.out_frame_bytes, (8, 8), within(orf.ref_mod(OFDM, z), OFDM.sym_len, orf.FFT_BOUND))
 
 
 def ofdm_demod(c):
     args, kw = OFDM.node_args()
     rx = orf.samples(OFDM, FRAMES)
-    return Row(c.OfdmDemodNode(*args, **kw), rx, 8 * OFDM.data_syms, (8, 8), within(orf.ref_demod(OFDM, rx), OFDM.D, orf.FFT_BOUND))
+    node = c.OfdmDemodNode(*args, **kw)
+    return Row(node, rx, node.out_frame_bytes, (8, 8), within(orf.ref_demod(OFDM, rx), OFDM.D, orf.FFT_BOUND))
 
 
-ROWS = {"convenc": convenc, "viterbi": viterbi, "ratematch-tx": ratematch_tx, "ratematch-rx": ratematch_rx, "crc-attach": crc_attach,
+ROWS = {"convenc": convenc, "viterbi": viterbi, "ldpcenc": ldpcenc, "ldpcdec": ldpcdec, "ratematch-tx": ratematch_tx, "ratematch-rx": ratematch_rx, "crc-attach": crc_attach,
         "crc-check": crc_check, "symmap": symmap, "demap-llr": lambda c: demap(c, "llr"), "demap-bits": lambda c: demap(c, "bits"),
         "ofdm-mod": ofdm_mod, "ofdm-demod": ofdm_demod}
 
@@ -178,3 +204,35 @@ def test_frame_call_shell(c, name):
     for args in bad:
         refused(*args)
         correct()
+
+
+# the element type of run()'s records where it is not uint8
+OUT_DTYPES = {"ratematch-rx": np.float32, "demap-llr": np.float32, "symmap": np.complex64, "ofdm-mod": np.complex64, "ofdm-demod": np.complex64}
+
+
+@pytest.mark.parametrize("name", sorted(ROWS))
+def test_frame_run_shell(c, name):
+    """The host form: run() on the row's records in their (FRAMES, record) shape and flat gives the reference; no frames give
+    the empty 2-D array of the node's output type and an input one element short of whole records is a ValueError, neither
+    with a launch."""
+    row = ROWS[name](c)
+    node, x = row.node, np.ascontiguousarray(row.x)
+    assert node.in_frame_bytes * FRAMES == x.nbytes and node.out_frame_bytes == row.out_bytes
+    timer = c.KernelTimer(8).attach(node)
+
+    def primary(got):
+        return got[0] if isinstance(got, tuple) else got
+
+    dtype = np.dtype(OUT_DTYPES.get(name, np.uint8))
+    out = primary(node.run(x))
+    assert timer.read_ms().size == 1
+    assert out.dtype == dtype and out.shape == (FRAMES, row.out_bytes // dtype.itemsize), (name, out.dtype, out.shape)
+    assert row.same(np.ascontiguousarray(out).view(np.uint8).ravel()), name
+    flat = primary(node.run(x.ravel()))
+    assert timer.read_ms().size == 2
+    assert flat.dtype == out.dtype and flat.tobytes() == out.tobytes(), name
+    none = primary(node.run(x[:0]))
+    assert none.shape == (0, row.out_bytes // dtype.itemsize) and none.dtype == dtype, (name, none.shape, none.dtype)
+    with pytest.raises(ValueError):
+        node.run(x.ravel()[:-1])
+    assert timer.read_ms().size == 2, name                             # neither launched anything
