@@ -22,6 +22,7 @@ import deframe_ref as dr
 import demod_ref
 import framesync_ref as fr
 import ofdm_ref
+import plan_cases
 import ratematch_ref as rr
 import rx_ref
 import symmap_ref as sm
@@ -372,11 +373,17 @@ def _tiles(cap):
     return 4 * cap + 1
 
 
+# the first two: tiles of 1024 outputs, four per lane in flight; (4, 5, 132): 512, two in flight; (4, 63, 132): 128 outputs on a workgroup
+# of 128 lanes whose staging steps across S = 63 phase arrays that do not divide it (tests/plan_cases.py restates the planner)
+SYMSYNC_FORMATS = ((32, 4, 1025), (7, 3, 50), (4, 5, 132), (4, 63, 132))
+
+
 def _symsync():
-    return [Case("symsync", "symsync.hip", "L%d-S%d-N%d" % f, dict(L=f[0], S=f[1], N=f[2], mu=5), _tiles) for f in ((32, 4, 1025), (7, 3, 50))]
+    return [Case("symsync", "symsync.hip", "L%d-S%d-N%d" % f, dict(L=f[0], S=f[1], N=f[2], mu=5), _tiles) for f in SYMSYNC_FORMATS]
 
 
-RESAMPLE_FORMATS = ((3, 2, 64, "f32"), (3, 2, 64, "c32"), (147, 152, 1000, "c32"), (160, 147, 1601, "f32"))
+# (3, 31, 16, "c32"): a tile of 256 outputs, one per lane (tests/plan_cases.py)
+RESAMPLE_FORMATS = ((3, 2, 64, "f32"), (3, 2, 64, "c32"), (147, 152, 1000, "c32"), (160, 147, 1601, "f32"), (3, 31, 16, "c32"))
 
 
 def _resample():
@@ -589,17 +596,18 @@ def never_ragged(cs, cap):
 
 
 def bytes_moved(cs, cap):
-    """Input plus output bytes of one call, from above (tile-planned nodes at their largest tile)."""
+    """Input plus output bytes of one call, from above (symsync and resample at the tile tests/plan_cases.py plans, which
+    tests/grid_children.py asserts on the device; the channelizer at its largest)."""
     size, f = cs.size(cap), cs.fmt
     if cs.family in ("syncest", "framesync"):
         return 8 * size
     if cs.family == "demod":
         return (8 + 16) * size if f["node"] == "nco" else 16 * size
     if cs.family == "symsync":
-        return 8 * size * TILE_MAX * (f["S"] + 1)
+        return 8 * size * plan_cases.symsync_tile(f["L"], f["S"], f["N"]).plan.TO * (f["S"] + 1)
     if cs.family == "resample":
         e = 8 if f["dtype"] == "c32" else 4
-        return e * size * TILE_MAX * (cdiv(f["M"], f["L"]) + 1)
+        return e * size * plan_cases.resample_tile(f["L"], f["M"], f["N"], f["dtype"]).plan.TO * (cdiv(f["M"], f["L"]) + 1)
     if cs.family == "channelizer":
         frames = size * max(CHZ_TILE_POINTS // f["M"], 1)
         return 8 * frames * (f["D"] + f["M"])

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 
 import grid_cases as gc  # noqa: E402
+import plan_cases  # noqa: E402
 
 KNOB = "COMMS_GRID_CAP"
 
@@ -170,7 +171,7 @@ def symsync(c):
             node, plain, ref = make(new, cap), make(new), SymSyncRef(taps, L, S)
             ref.mu = mu
             TO, worst = fields(node.kernel(S))["tile"], 0.0
-            assert TO <= gc.TILE_MAX
+            assert TO == plan_cases.symsync_tile(L, S, N).plan.TO <= gc.TILE_MAX        # the tile gc.bytes_moved counts with
             for call, cut in enumerate((TO // 2 + 1, 1)):             # the second call ends one output into its last tile
                 n_out = (cs.size(cap) - 1) * TO + cut
                 x = rand_c(rng, S * n_out)
@@ -198,7 +199,7 @@ def resample(c):
             node, plain, ref = make(lambda: c.ResampleNode(taps, L, M, dtype), cap), make(lambda: c.ResampleNode(taps, L, M, dtype)), ResampleRef(taps, L, M, dtype)
             k0 = fields(node.kernel(1))
             TO, worst = k0["tile"], 0.0
-            assert TO <= gc.TILE_MAX and "resample_kernel" in node.kernel(1)
+            assert TO == plan_cases.resample_tile(L, M, N, cs.fmt["dtype"]).plan.TO <= gc.TILE_MAX and "resample_kernel" in node.kernel(1)
             print("resample %s cap %d: tile %d, (cap tile M) mod L = %d" % (cs.name, cap, TO, cap * TO * M % L))
             for call, cut in enumerate((TO // 3 + 1, 1)):
                 n = ((cs.size(cap) - 1) * TO + cut) * M // L

@@ -81,6 +81,18 @@ def test_grid_dependent_steps_take_nonzero_residues():
     assert any(L & (L - 1) for L, _, _, _ in gc.RESAMPLE_FORMATS)
 
 
+def test_tile_planned_cases_reach_more_than_the_largest_tile():
+    """symsync: four, two and one output per lane in flight, the last on a tile narrower than 256 lanes; resample: a tile of 256
+    outputs, one trip per lane, beside the larger ones (the plans are tests/plan_cases.py's, pinned to the source there)."""
+    import plan_cases as pc
+
+    ss = [pc.symsync_tile(cs.fmt["L"], cs.fmt["S"], cs.fmt["N"]).plan for cs in gc.cases_of("symsync")]
+    assert {p.U for p in ss} == {4, 2, 1} and any(p.TO <= 128 and p.WG == p.TO for p in ss)
+    assert all(cs.fmt["mu"] < cs.fmt["S"] * cs.fmt["L"] for cs in gc.cases_of("symsync"))
+    rs = [pc.resample_tile(cs.fmt["L"], cs.fmt["M"], cs.fmt["N"], cs.fmt["dtype"]).plan for cs in gc.cases_of("resample")]
+    assert {p.TO for p in rs} >= {1024, 256} and all(p.tab_lds for p in rs)
+
+
 def test_seam_cases_sit_on_both_sides():
     rx = [cs.fmt["n_coded"] for cs in gc.cases_of("ratematch") if cs.fmt["dir"] == "rx"]
     tx = [cs.fmt["n_tx"] for cs in gc.cases_of("ratematch") if cs.fmt["dir"] == "tx"]
