@@ -376,6 +376,8 @@ _PROTOS = {
     "comms_demap_set_llr_scale": [_vp, C.c_float],
     "comms_demap_run_dev": [_vp, _vp, _sz, _vp, _vp],
     "comms_demap_run": [_vp, _vp, _sz, _vp],
+    "comms_demap_run_weighted_dev": [_vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "comms_demap_run_weighted": [_vp, _vp, _vp, _sz, _sz, _vp],
     "comms_demap_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_demap_set_timer": [_vp, _vp],
     "comms_demap_destroy": [_vp],
@@ -385,6 +387,8 @@ _PROTOS = {
     "comms_ofdm_mod_run": [_vp, _vp, _sz, _vp],
     "comms_ofdm_demod_run_dev": [_vp, _vp, _sz, _vp, _vp],
     "comms_ofdm_demod_run": [_vp, _vp, _sz, _vp],
+    "comms_ofdm_demod_csi_run_dev": [_vp, _vp, _sz, _vp, _vp, _vp],
+    "comms_ofdm_demod_csi_run": [_vp, _vp, _sz, _vp, _vp],
     "comms_ofdm_get_kernel": [_vp, _i32, _sz, C.c_char_p, _sz],
     "comms_ofdm_set_timer": [_vp, _vp],
     "comms_ofdm_destroy": [_vp],

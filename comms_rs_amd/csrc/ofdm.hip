@@ -26,6 +26,10 @@
 //                 them in symbol order and leaves T train[k] / sum_t Y_{t,k} = 1 / H_k in LDS.  ofdm_block() chooses the
 //                 block: one per frame when the call has at least as many frames as the grid has workgroups, otherwise
 //                 just enough blocks per frame to give every workgroup an item.
+//   channel state ofdm_demod_kernel<N, true> (comms_ofdm_demod_csi_run_dev) is the same launch with one store more behind the
+//                 1 / H_k step: den = |sum_t Y_{t,k}|^2 is in a register there, and g = den / |T train[k]|^2 = |H_k|^2 goes to
+//                 the frame's record of D floats, data carriers in bin order.  Every item of a frame forms 1 / H_k; the item
+//                 whose block starts at symbol 0 writes the record.  The divisor is a host-built table (f64, rounded once).
 // Both kernels walk their items grid-stride under the library's grid cap.
 #include <cmath>
 
@@ -48,6 +52,8 @@ struct OfdmArgs {
     const float2* pilots;  // Q
     const float* pol;      // n_pol >= 1
     const float2* train;   // modulator: train[k]; demodulator: T train[k]
+    const float* tt2;      // demodulator with channel state: |T train[k]|^2
+    float* csi;            // ... and its records of D floats
     size_t items;          // n_frames * nblk
     unsigned n_pol, T, S, D, CP;
     unsigned blk, nblk;    // symbols per block, blocks per frame
@@ -200,7 +206,7 @@ __global__ __launch_bounds__(OF_WG) void ofdm_mod_kernel(const OfdmArgs a) {
     }
 }
 
-template <int N>
+template <int N, bool CSI = false>
 __global__ __launch_bounds__(OF_WG) void ofdm_demod_kernel(const OfdmArgs a) {
     using G = OfGeom<N>;
     extern __shared__ __align__(16) unsigned char of_smem[];
@@ -247,6 +253,9 @@ __global__ __launch_bounds__(OF_WG) void ofdm_demod_kernel(const OfdmArgs a) {
                 const float den = __fmaf_rn(h.x, h.x, __fmul_rn(h.y, h.y));
                 const cf num = cmulcf(to_cf(a.train[k]), h);   // T train[k] conj(sum)
                 inv[k] = map[k] == -1 ? cf{0.f, 0.f} : cf{__fdiv_rn(num.x, den), __fdiv_rn(num.y, den)};
+                if constexpr (CSI) {
+                    if (s0 == 0 && map[k] >= 0) a.csi[frame * a.D + map[k]] = __fdiv_rn(den, a.tt2[k]);   // (D > map[k])
+                }
             }
         }
         __syncthreads();
@@ -297,7 +306,7 @@ struct comms_ofdm : Handle {
     int flags = 0;
     float tx_scale = 0.f;
     DevBuf<float2> tw, pilots, train, train_t;   // train_t: T train[k]
-    DevBuf<float> pol;
+    DevBuf<float> pol, tt2;                      // tt2: |train_t[k]|^2
     DevBuf<int> map;
     unsigned max_grid = 1;
 };
@@ -330,11 +339,23 @@ template <int N>
 comms_status_t of_launch_n(comms_ofdm* h, int direction, const OfdmArgs& a, dim3 grid, hipStream_t s) {
     if (direction == COMMS_OFDM_MOD)
         return launch_kernel<ofdm_mod_kernel<N>>("ofdm_mod_kernel", grid, dim3(OF_WG), ofdm_lds(N), s, h->take_events(), a);
+    if (a.csi) return launch_kernel<ofdm_demod_kernel<N, true>>("ofdm_demod_kernel", grid, dim3(OF_WG), ofdm_lds(N), s, h->take_events(), a);
     return launch_kernel<ofdm_demod_kernel<N>>("ofdm_demod_kernel", grid, dim3(OF_WG), ofdm_lds(N), s, h->take_events(), a);
 }
 
-comms_status_t of_run_dev(comms_ofdm* h, int direction, const comms_c32* d_in, size_t n_frames, comms_c32* d_out, void* stream) {
+// `with_csi`: the demodulator's channel-state form, d_csi its n_frames records of D floats
+comms_status_t of_run_dev(comms_ofdm* h, int direction, const comms_c32* d_in, size_t n_frames, comms_c32* d_out, void* stream,
+                          bool with_csi = false, float* d_csi = nullptr) {
     COMMS_TRY(check_frame_call(h, [&](const comms_ofdm* o) { return of_call(o, direction); }, d_in, n_frames, d_out, true));
+    if (with_csi) {
+        COMMS_ARG(h->T >= 1, "the channel state comes from the training symbols: the handle has none");
+        COMMS_ARG(!n_frames || d_csi, "NULL pointer");
+        COMMS_ARG(aligned(d_csi, 4), "the channel-state records must be aligned to 4 bytes");
+        const size_t csi_bytes = n_frames * h->D * sizeof(float);
+        COMMS_ARG(!n_frames || (!ranges_overlap(d_csi, csi_bytes, d_in, n_frames * of_call(h, direction).in_bytes) &&
+                                !ranges_overlap(d_csi, csi_bytes, d_out, n_frames * of_call(h, direction).out_bytes)),
+                  "the channel-state records overlap the input or the output records");
+    }
     if (!n_frames) return COMMS_OK;
     COMMS_TRY(use_device(h->device));
     const bool mod = direction == COMMS_OFDM_MOD;
@@ -346,6 +367,8 @@ comms_status_t of_run_dev(comms_ofdm* h, int direction, const comms_c32* d_in, s
     a.pilots = h->pilots.get();
     a.pol = h->pol.get();
     a.train = mod ? h->train.get() : h->train_t.get();
+    a.tt2 = h->tt2.get();
+    a.csi = with_csi ? d_csi : nullptr;
     a.n_pol = h->n_pol;
     a.T = h->T;
     a.S = h->S;
@@ -407,6 +430,7 @@ comms_status_t comms_ofdm_create(int32_t n_fft, int32_t n_cp, const uint8_t* car
               "a frame has n_syms >= 1 and at most 2^24 samples (got n_train %zu, n_syms %zu)", n_train, n_syms);
     COMMS_ARG(train || !n_train, "train is NULL with n_train > 0");
     std::vector<float2> tr(N, make_float2(0.f, 0.f)), tr_t(N, make_float2(0.f, 0.f));
+    std::vector<float> tt2(N, 0.f);
     if (n_train) {
         for (size_t k = 0; k < N; ++k) {
             COMMS_ARG(std::isfinite(train[k].re) && std::isfinite(train[k].im), "train[%zu] is not finite", k);
@@ -414,6 +438,8 @@ comms_status_t comms_ofdm_create(int32_t n_fft, int32_t n_cp, const uint8_t* car
             tr[k] = make_float2(train[k].re, train[k].im);
             tr_t[k] = make_float2(static_cast<float>(static_cast<double>(n_train) * train[k].re),
                                   static_cast<float>(static_cast<double>(n_train) * train[k].im));
+            const double re = tr_t[k].x, im = tr_t[k].y;   // from the stored, rounded values: what the kernel multiplies by
+            tt2[k] = static_cast<float>(re * re + im * im);
         }
     }
     std::vector<float2> tw(N);
@@ -437,6 +463,7 @@ comms_status_t comms_ofdm_create(int32_t n_fft, int32_t n_cp, const uint8_t* car
     COMMS_HIP_TRY(h->pol.upload(pol));
     COMMS_HIP_TRY(h->train.upload(tr));
     COMMS_HIP_TRY(h->train_t.upload(tr_t));
+    COMMS_HIP_TRY(h->tt2.upload(tt2));
     if (Q) COMMS_HIP_TRY(h->pilots.upload(reinterpret_cast<const float2*>(pilots), Q));
     h->max_grid = resident_workgroups(ofdm_lds(n_fft));
     *out = h.release();
@@ -464,6 +491,31 @@ comms_status_t comms_ofdm_demod_run_dev(comms_ofdm_t* h, const comms_c32* d_in, 
 }
 comms_status_t comms_ofdm_demod_run(comms_ofdm_t* h, const comms_c32* in, size_t n_frames, comms_c32* out) {
     return of_run(h, COMMS_OFDM_DEMOD, in, n_frames, out);
+}
+
+comms_status_t comms_ofdm_demod_csi_run_dev(comms_ofdm_t* h, const comms_c32* d_in, size_t n_frames, comms_c32* d_out, float* d_csi,
+                                           void* stream) {
+    return of_run_dev(h, COMMS_OFDM_DEMOD, d_in, n_frames, d_out, stream, true, d_csi);
+}
+comms_status_t comms_ofdm_demod_csi_run(comms_ofdm_t* h, const comms_c32* in, size_t n_frames, comms_c32* out, float* csi) {
+    COMMS_TRY(check_frame_call(h, [&](const comms_ofdm* o) { return of_call(o, COMMS_OFDM_DEMOD); }, in, n_frames, out, false));
+    COMMS_ARG(h->T >= 1, "the channel state comes from the training symbols: the handle has none");
+    COMMS_ARG(!n_frames || csi, "NULL pointer");
+    if (!n_frames) return COMMS_OK;
+    COMMS_TRY(use_device(h->device));
+    // one device block for the outputs: the records, then the channel state
+    const FrameCall c = of_call(h, COMMS_OFDM_DEMOD);
+    const size_t in_b = n_frames * c.in_bytes, rec_b = n_frames * c.out_bytes, csi_b = n_frames * h->D * sizeof(float);
+    COMMS_TRY(h->in_scratch.reserve(in_b));
+    COMMS_TRY(h->out_scratch.reserve(rec_b + csi_b));
+    char* d_out = static_cast<char*>(h->out_scratch.p);
+    COMMS_HIP_TRY(hipMemcpyAsync(h->in_scratch.p, in, in_b, hipMemcpyHostToDevice, h->stream));
+    COMMS_TRY(of_run_dev(h, COMMS_OFDM_DEMOD, static_cast<const comms_c32*>(h->in_scratch.p), n_frames, reinterpret_cast<comms_c32*>(d_out),
+                         COMMS_STREAM_HANDLE, true, reinterpret_cast<float*>(d_out + rec_b)));
+    COMMS_HIP_TRY(hipMemcpyAsync(out, d_out, rec_b, hipMemcpyDeviceToHost, h->stream));
+    COMMS_HIP_TRY(hipMemcpyAsync(csi, d_out + rec_b, csi_b, hipMemcpyDeviceToHost, h->stream));
+    COMMS_HIP_TRY(hipStreamSynchronize(h->stream));
+    return COMMS_OK;
 }
 
 comms_status_t comms_ofdm_get_kernel(const comms_ofdm_t* h, int32_t direction, size_t n_frames, char* name, size_t name_len) {

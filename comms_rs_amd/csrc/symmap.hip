@@ -19,6 +19,10 @@
 //   minima               with a finite table a distance is NaN for one point only if it is NaN for all of them, so the
 //                        definition's strict-replace scan equals an IEEE minimum (fminf); every minimum starts from the first
 //                        point of its class, not from +inf, so that a NaN symbol gives NaN values.
+//   weighted LLRs        comms_demap_run_weighted: both forms again with FMT = SM_LLR_WEIGHTED.  A lane loads its symbol's weight
+//                        w (4 bytes beside the symbol's 8), multiplies by c = fl(scale * w) where the plain form multiplies by
+//                        scale, and writes +0.0 for a weight that is not finite and positive.  (frame, position) are carried
+//                        from pass to pass, one 64-bit division per lane; P = F and P = 1 need no position at all.
 //   LLR stores           a lane writes its symbol's 4 m bytes directly: 16-byte stores at m = 4 and 8, 8-byte stores at m = 2
 //                        and 6, 4-byte stores at odd m.
 //   BITS words           a wave takes 64 consecutive symbols of ONE frame, which are exactly 2 m whole 32-bit words of its
@@ -98,7 +102,10 @@ struct DemapArgs {
     unsigned F, chunks;     // BITS: chunks = ceil(F / 64) per frame
     unsigned rec_words;     // BITS: 32-bit words per output record
     float scale;
+    const float* weight;    // weighted LLR: n_frames records of P floats, symbol j of a frame takes weight[j mod P]
+    unsigned P;
 };
+constexpr int SM_LLR_WEIGHTED = -1;   // the kernels' FMT of comms_demap_run_weighted: COMMS_SYM_LLR with a weight per symbol
 
 __device__ __forceinline__ float sq_diff(float z, float p) {
     const float d = __fsub_rn(z, p);
@@ -247,17 +254,51 @@ __device__ __forceinline__ bool wave_words(unsigned v, unsigned lane, unsigned& 
 
 // FORM 0: the table form (M = MI, MQ unused); FORM 1: the per-axis form (M = MI + MQ)
 template <int FORM, int MI, int MQ>
-__device__ __forceinline__ void demap_llr_items(const DemapArgs& a) {
+__device__ __forceinline__ void demap_llr_one(const DemapArgs& a, size_t at, float scale, bool erase) {
     constexpr int M = FORM ? MI + MQ : MI;
+    const float2 z = a.sym[at];
+    float L[M];
+    if constexpr (FORM)
+        llr_axis<MI, MQ>(z, a.pI, a.pQ, scale, L);
+    else
+        llr_table<M>(z, a.table, scale, L);
+    if (erase) {
+#pragma unroll
+        for (int b = 0; b < M; ++b) L[b] = 0.f;
+    }
+    llr_store<M>(static_cast<float*>(a.out), at, L);
+}
+
+template <int FORM, int MI, int MQ>
+__device__ __forceinline__ void demap_llr_items(const DemapArgs& a) {
     const size_t stride = static_cast<size_t>(gridDim.x) * SM_WG;
-    for (size_t at = static_cast<size_t>(blockIdx.x) * SM_WG + threadIdx.x; at < a.items; at += stride) {
-        const float2 z = a.sym[at];
-        float L[M];
-        if constexpr (FORM)
-            llr_axis<MI, MQ>(z, a.pI, a.pQ, a.scale, L);
-        else
-            llr_table<M>(z, a.table, a.scale, L);
-        llr_store<M>(static_cast<float*>(a.out), at, L);
+    for (size_t at = static_cast<size_t>(blockIdx.x) * SM_WG + threadIdx.x; at < a.items; at += stride)
+        demap_llr_one<FORM, MI, MQ>(a, at, a.scale, false);
+}
+
+// The weighted form: symbol `at` = frame * F + pos takes w = weight[frame * P + pos mod P] and c = fl(scale * w) in place of
+// the scale; a weight that is not finite and positive erases the symbol (every LLR +0.0, whatever the symbol is).  P = F
+// reads weight[at] and P = 1 weight[frame]; only the periods between need pos mod P (32-bit).  A lane divides once, by F,
+// in front of its loop, and carries (frame, pos) from pass to pass as symmap_kernel does.
+template <int FORM, int MI, int MQ>
+__device__ __forceinline__ void demap_weighted_items(const DemapArgs& a) {
+    const unsigned stride = gridDim.x * SM_WG;
+    const size_t l0 = static_cast<size_t>(blockIdx.x) * SM_WG + threadIdx.x;
+    if (l0 >= a.items) return;
+    const unsigned dq = stride / a.F, dr = stride % a.F;
+    size_t frame = l0 / a.F;
+    unsigned pos = static_cast<unsigned>(l0 % a.F);
+    for (size_t at = l0; at < a.items; at += stride) {
+        const size_t wi = a.P == a.F ? at : a.P == 1u ? frame : frame * a.P + pos % a.P;
+        const float w = a.weight[wi];
+        const bool ok = w > 0.f && w <= 3.402823466e38f;   // (false for NaN)
+        demap_llr_one<FORM, MI, MQ>(a, at, __fmul_rn(a.scale, w), !ok);
+        frame += dq;
+        pos += dr;
+        if (pos >= a.F) {
+            pos -= a.F;
+            ++frame;
+        }
     }
 }
 
@@ -290,6 +331,8 @@ template <int M, int FMT>
 __global__ __launch_bounds__(SM_WG) void demap_table_kernel(const DemapArgs a) {
     if constexpr (FMT == COMMS_SYM_BITS)
         demap_bits_items<0, M, 0>(a);
+    else if constexpr (FMT == SM_LLR_WEIGHTED)
+        demap_weighted_items<0, M, 0>(a);
     else
         demap_llr_items<0, M, 0>(a);
 }
@@ -298,6 +341,8 @@ template <int MI, int MQ, int FMT>
 __global__ __launch_bounds__(SM_WG) void demap_axis_kernel(const DemapArgs a) {
     if constexpr (FMT == COMMS_SYM_BITS)
         demap_bits_items<1, MI, MQ>(a);
+    else if constexpr (FMT == SM_LLR_WEIGHTED)
+        demap_weighted_items<1, MI, MQ>(a);
     else
         demap_llr_items<1, MI, MQ>(a);
 }
@@ -586,10 +631,8 @@ comms_status_t comms_demap_set_llr_scale(comms_demap_t* h, float scale) {
 size_t comms_demap_in_frame_bytes(const comms_demap_t* h) { return h ? static_cast<size_t>(h->F) * sizeof(comms_c32) : 0; }
 size_t comms_demap_out_frame_bytes(const comms_demap_t* h) { return h ? demap_out_bytes(h) : 0; }
 
-comms_status_t comms_demap_run_dev(comms_demap_t* h, const comms_c32* d_sym, size_t n_frames, void* d_out, void* stream) {
-    COMMS_TRY(check_frame_call(h, demap_call, d_sym, n_frames, d_out, true));
-    if (!n_frames) return COMMS_OK;
-    COMMS_TRY(use_device(h->device));
+// the arguments of either device form behind its checks
+static DemapArgs demap_args(const comms_demap* h, const comms_c32* d_sym, size_t n_frames, void* d_out) {
     DemapArgs a{};
     a.sym = reinterpret_cast<const float2*>(d_sym);
     a.out = d_out;
@@ -602,9 +645,60 @@ comms_status_t comms_demap_run_dev(comms_demap_t* h, const comms_c32* d_sym, siz
     a.chunks = static_cast<unsigned>(demap_chunks(h));
     a.rec_words = static_cast<unsigned>(bit_record_bytes(static_cast<size_t>(h->F) * h->m) / 4);
     a.scale = h->scale;
+    return a;
+}
+
+comms_status_t comms_demap_run_dev(comms_demap_t* h, const comms_c32* d_sym, size_t n_frames, void* d_out, void* stream) {
+    COMMS_TRY(check_frame_call(h, demap_call, d_sym, n_frames, d_out, true));
+    if (!n_frames) return COMMS_OK;
+    COMMS_TRY(use_device(h->device));
+    const DemapArgs a = demap_args(h, d_sym, n_frames, d_out);
     const dim3 grid(static_cast<unsigned>(demap_grid(h, n_frames)));
     hipStream_t s = h->pick(stream);
     return h->format == COMMS_SYM_BITS ? demap_launch<COMMS_SYM_BITS>(h, a, grid, s) : demap_launch<COMMS_SYM_LLR>(h, a, grid, s);
+}
+
+// what both weighted forms check behind check_frame_call
+static comms_status_t check_weights(const comms_demap* h, const float* weight, size_t weight_period, size_t n_frames) {
+    COMMS_ARG(h->format == COMMS_SYM_LLR, "weighted demapping gives LLRs: the handle's output format is COMMS_SYM_BITS");
+    COMMS_ARG(weight_period >= 1 && weight_period <= h->F, "weight_period must be 1 ... n_payload = %u (got %zu)", h->F, weight_period);
+    COMMS_ARG(!n_frames || weight, "NULL pointer");
+    return COMMS_OK;
+}
+
+comms_status_t comms_demap_run_weighted_dev(comms_demap_t* h, const comms_c32* d_sym, const float* d_weight, size_t weight_period,
+                                            size_t n_frames, void* d_out, void* stream) {
+    COMMS_TRY(check_frame_call(h, demap_call, d_sym, n_frames, d_out, true));
+    COMMS_TRY(check_weights(h, d_weight, weight_period, n_frames));
+    COMMS_ARG(aligned(d_weight, 4), "the weights must be aligned to 4 bytes");
+    if (!n_frames) return COMMS_OK;
+    COMMS_ARG(!ranges_overlap(d_weight, n_frames * weight_period * sizeof(float), d_out, n_frames * demap_out_bytes(h)),
+              "the weights and the output records overlap");
+    COMMS_TRY(use_device(h->device));
+    DemapArgs a = demap_args(h, d_sym, n_frames, d_out);
+    a.weight = d_weight;
+    a.P = static_cast<unsigned>(weight_period);
+    return demap_launch<SM_LLR_WEIGHTED>(h, a, dim3(static_cast<unsigned>(demap_grid(h, n_frames))), h->pick(stream));
+}
+
+comms_status_t comms_demap_run_weighted(comms_demap_t* h, const comms_c32* sym, const float* weight, size_t weight_period, size_t n_frames,
+                                        void* out) {
+    COMMS_TRY(check_frame_call(h, demap_call, sym, n_frames, out, false));
+    COMMS_TRY(check_weights(h, weight, weight_period, n_frames));
+    if (!n_frames) return COMMS_OK;
+    COMMS_TRY(use_device(h->device));
+    // one device block for the inputs: the symbol records, then the weights
+    const size_t sym_b = n_frames * h->F * sizeof(comms_c32), w_b = n_frames * weight_period * sizeof(float), out_b = n_frames * demap_out_bytes(h);
+    COMMS_TRY(h->in_scratch.reserve(sym_b + w_b));
+    COMMS_TRY(h->out_scratch.reserve(out_b));
+    char* d_in = static_cast<char*>(h->in_scratch.p);
+    COMMS_HIP_TRY(hipMemcpyAsync(d_in, sym, sym_b, hipMemcpyHostToDevice, h->stream));
+    COMMS_HIP_TRY(hipMemcpyAsync(d_in + sym_b, weight, w_b, hipMemcpyHostToDevice, h->stream));
+    COMMS_TRY(comms_demap_run_weighted_dev(h, reinterpret_cast<const comms_c32*>(d_in), reinterpret_cast<const float*>(d_in + sym_b),
+                                           weight_period, n_frames, h->out_scratch.p, COMMS_STREAM_HANDLE));
+    COMMS_HIP_TRY(hipMemcpyAsync(out, h->out_scratch.p, out_b, hipMemcpyDeviceToHost, h->stream));
+    COMMS_HIP_TRY(hipStreamSynchronize(h->stream));
+    return COMMS_OK;
 }
 
 comms_status_t comms_demap_run(comms_demap_t* h, const comms_c32* sym, size_t n_frames, void* out) {

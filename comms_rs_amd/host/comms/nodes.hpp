@@ -1970,6 +1970,108 @@ public:
     explicit OfdmDemodNodeDev(const OfdmSpec& format, int device = 0) : DevNode(device, "OfdmDemodNodeDev::new", format, device) {}
 };
 
+// OfdmDemodCsi: the demodulator behind OfdmCfoCorrectNode with its channel state (comms_ofdm_demod_csi_run; n_train >= 1).  Takes
+// the frame message (records of frame_samples() samples) and sends the equalised records under the same headers together with
+// one record of data_carriers() floats per frame, |H_k|^2 of every data carrier -- WeightedDemapNode's input.  A message without
+// frames passes through empty.
+template <class Store, class Csi>
+struct EqualisedOf {
+    FramesOf<Store> frames;   // the equalised records, frame_bytes = data_syms() * sizeof(Complex32)
+    Csi csi;                  // csi_period floats per frame
+    size_t csi_period = 0;
+    size_t size() const { return frames.size(); }
+};
+struct OfdmDemodCsiOp : OfdmOp<false> {
+    using Frames = DeframeOp::Frames;
+    using FramesDev = DeframeOp::FramesDev;
+    using Equalised = EqualisedOf<std::vector<uint8_t>, std::vector<float>>;
+    using EqualisedDev = EqualisedOf<DeviceBuf<uint8_t>, DeviceBuf<float>>;
+    OfdmDemodCsiOp(const char* who, const OfdmSpec& f, int device) : OfdmOp<false>(who, f, device) {
+        for (uint8_t k : f.carrier_kind) carriers_ += k == COMMS_OFDM_DATA;
+        if (!f.n_train) throw std::runtime_error(std::string(who) + ": the channel state needs a training symbol");
+    }
+    size_t data_carriers() const { return carriers_; }
+    size_t in_frame_bytes() const { return frame_samples() * sizeof(Complex32); }
+    size_t out_frame_bytes() const { return data_syms() * sizeof(Complex32); }
+
+protected:
+    Result<Equalised> demod(const Frames& in) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        Equalised out{{std::vector<uint8_t>(in.size() * out_frame_bytes()), in.headers, out_frame_bytes()}, std::vector<float>(in.size() * carriers_), carriers_};
+        return ok_or(comms_ofdm_demod_csi_run(h_.get(), reinterpret_cast<const comms_c32*>(in.data.data()), in.size(),
+                                              reinterpret_cast<comms_c32*>(out.frames.data.data()), out.csi.data()), out);
+    }
+    Result<EqualisedDev> demod_dev(const FramesDev& in, const DevStream& on) {
+        if (in.frame_bytes != in_frame_bytes() || in.data.size() < in.size() * in.frame_bytes) return NodeError::DataError;
+        const size_t n = in.size();
+        EqualisedDev out{{DeviceBuf<uint8_t>(n ? n * out_frame_bytes() : 8, on.device()), in.headers, out_frame_bytes()},
+                         DeviceBuf<float>(n ? n * carriers_ : 2, on.device()), carriers_};
+        comms_status_t st = on.submit(in.data, out.frames.data, [&](void* s) {
+            return comms_ofdm_demod_csi_run_dev(h_.get(), reinterpret_cast<const comms_c32*>(in.data.ptr()), n,
+                                                reinterpret_cast<comms_c32*>(out.frames.data.ptr()), out.csi.ptr(), s);
+        });
+        if (st == COMMS_OK) st = comms_buf_record_ready(out.csi.raw(), on.get());   // the same launch wrote the channel state
+        return ok_or(st, out);
+    }
+    size_t carriers_ = 0;
+};
+class OfdmDemodCsiNode : public DeriveNode<OfdmDemodCsiNode>, public Ports<OfdmDemodCsiOp::Frames, OfdmDemodCsiOp::Equalised>, public OfdmDemodCsiOp {
+public:
+    explicit OfdmDemodCsiNode(const OfdmSpec& format, int device = 0) : OfdmDemodCsiOp("OfdmDemodCsiNode::new", format, device) {}
+    Result<Equalised> run(const Frames& in) { return demod(in); }
+};
+class OfdmDemodCsiNodeDev : public DeriveNode<OfdmDemodCsiNodeDev>, public Ports<OfdmDemodCsiOp::FramesDev, OfdmDemodCsiOp::EqualisedDev>, public OnStream<OfdmDemodCsiOp> {
+public:
+    explicit OfdmDemodCsiNodeDev(const OfdmSpec& format, int device = 0) : OnStream(device, "OfdmDemodCsiNodeDev::new", format, device) {}
+    Result<EqualisedDev> run(const FramesDev& in) { return demod_dev(in, *this); }
+};
+
+// WeightedDemap: takes OfdmDemodCsiNode's message -- symbol records and csi_period weights per frame -- and sends the LLR records
+// of comms_demap_run_weighted under the same headers: symbol j of a frame is scaled by llr_scale * csi[j mod csi_period] and
+// erased (+0.0) where that weight is not finite and positive.  The spec's format stays COMMS_SYM_LLR.
+struct WeightedDemapOp : DemapOp {
+    using Equalised = OfdmDemodCsiOp::Equalised;
+    using EqualisedDev = OfdmDemodCsiOp::EqualisedDev;
+    WeightedDemapOp(const char* who, const DemapSpec& f, int device) : DemapOp(who, f, device) {
+        if (f.format != COMMS_SYM_LLR) throw std::runtime_error(std::string(who) + ": weighted demapping gives LLRs");
+    }
+
+protected:
+    template <class E>
+    bool fits(const E& in) const {
+        return in.frames.frame_bytes == in_frame_bytes() && in.frames.data.size() >= in.size() * in.frames.frame_bytes && in.csi_period >= 1 &&
+               in.csi.size() >= in.size() * in.csi_period;
+    }
+    Result<Frames> demap_weighted(const Equalised& in) {
+        if (!fits(in)) return NodeError::DataError;
+        Frames out{std::vector<uint8_t>(in.size() * out_frame_bytes()), in.frames.headers, out_frame_bytes()};
+        return ok_or(comms_demap_run_weighted(h_.get(), reinterpret_cast<const comms_c32*>(in.frames.data.data()), in.csi.data(), in.csi_period,
+                                              in.size(), out.data.data()), out);
+    }
+    Result<FramesDev> demap_weighted_dev(const EqualisedDev& in, const DevStream& on) {
+        if (!fits(in)) return NodeError::DataError;
+        FramesDev out{DeviceBuf<uint8_t>(in.size() ? in.size() * out_frame_bytes() : 16, on.device()), in.frames.headers, out_frame_bytes()};
+        comms_status_t st = on.wait(in.csi);   // the weights' producer, beside the symbols' (submit waits for that one)
+        if (st == COMMS_OK)
+            st = on.submit(in.frames.data, out.data, [&](void* s) {
+                return comms_demap_run_weighted_dev(h_.get(), reinterpret_cast<const comms_c32*>(in.frames.data.ptr()), in.csi.ptr(), in.csi_period,
+                                                    in.size(), out.data.ptr(), s);
+            });
+        if (st == COMMS_OK) st = comms_buf_record_use(in.csi.raw(), on.get());
+        return ok_or(st, out);
+    }
+};
+class WeightedDemapNode : public DeriveNode<WeightedDemapNode>, public Ports<WeightedDemapOp::Equalised, WeightedDemapOp::Frames>, public WeightedDemapOp {
+public:
+    explicit WeightedDemapNode(const DemapSpec& format, int device = 0) : WeightedDemapOp("WeightedDemapNode::new", format, device) {}
+    Result<Frames> run(const Equalised& in) { return demap_weighted(in); }
+};
+class WeightedDemapNodeDev : public DeriveNode<WeightedDemapNodeDev>, public Ports<WeightedDemapOp::EqualisedDev, WeightedDemapOp::FramesDev>, public OnStream<WeightedDemapOp> {
+public:
+    explicit WeightedDemapNodeDev(const DemapSpec& format, int device = 0) : OnStream(device, "WeightedDemapNodeDev::new", format, device) {}
+    Result<FramesDev> run(const EqualisedDev& in) { return demap_weighted_dev(in, *this); }
+};
+
 // OFDM stream synchroniser (comms_ofdmsync_*; additional nodes): what stands between a received sample stream and OfdmDemodNode.
 //   stream -> OfdmSyncNode -+- detections -> DeframeNode (COMMS_SYM_C32, n_payload = frame_samples, offset 0, lookback())
 //                            +- output ----------------------+-> OfdmCfoCorrectNode -> OfdmDemodNode

@@ -1841,7 +1841,9 @@ class DemapNode(_FrameNode, _Handle):
     RateDematchNode(record_llrs = n_payload * bits_per_sym).  The rule is sym_to_bits's and DeframeNode's over the whole table.
     A separable table (any square or rectangular QAM) runs per axis, the same bits from far fewer distances; force_table=True
     keeps the general form.  Stateless.  run() takes complex64 and returns float32 (n_frames, n_payload * bits_per_sym) or
-    uint8 (n_frames, out_frame_bytes)."""
+    uint8 (n_frames, out_frame_bytes).  With weights= (float32 (n_frames, P), 1 <= P <= n_payload, "llr" only) symbol j of a
+    frame is scaled by llr_scale * weights[frame, j mod P] and erased (+0.0) where that weight is not finite and positive:
+    OfdmDemodNode.run(..., csi=True)'s channel state with P = its data carriers, or one 1 / (2 sigma^2) per frame with P = 1."""
     _prefix = "comms_demap"
     _formats = {"llr": _frame_call(_prefix, np.complex64, np.float32), "bits": _frame_call(_prefix, np.complex64, np.uint8)}
     _frame = property(lambda self: self._formats[self.format])
@@ -1868,11 +1870,27 @@ class DemapNode(_FrameNode, _Handle):
         check(lib().comms_demap_set_llr_scale(self._h, float(scale)))
         return self
 
-    def run(self, symbols):
-        return self._frame.run(self, symbols)
+    def run(self, symbols, weights=None):
+        if weights is None:
+            return self._frame.run(self, symbols)
+        # (comms_demap_run_weighted takes its weights in front of n_frames: not the shell's order of arguments)
+        x = _as_c64(symbols)
+        if x.size % self.n_payload:
+            raise ValueError("the input must hold whole records of %d symbols" % self.n_payload)
+        n_frames = x.size // self.n_payload
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.ndim != 2 or w.shape[0] != n_frames:
+            raise ValueError("weights holds one record per frame: shape (n_frames, P)")
+        out = np.zeros((n_frames, self.n_payload * self.bits_per_sym), np.float32)
+        p_x, p_w, p_out = [_ptr(a) if n_frames else None for a in (x, w, out)]
+        check(lib().comms_demap_run_weighted(self._h, p_x, p_w, w.shape[1], n_frames, p_out))
+        return out
 
-    def run_dev(self, sym_ptr, n_frames, out_ptr, stream=0):
-        self._frame.run_dev(self, sym_ptr, n_frames, out_ptr, stream)
+    def run_dev(self, sym_ptr, n_frames, out_ptr, stream=0, weight_ptr=None, weight_period=0):
+        if weight_ptr is None:
+            self._frame.run_dev(self, sym_ptr, n_frames, out_ptr, stream)
+        else:
+            check(lib().comms_demap_run_weighted_dev(self._h, sym_ptr, weight_ptr, int(weight_period), int(n_frames), out_ptr, stream))
 
     def kernel(self, n_frames):
         """ "demap_table_kernel<m,fmt> form=table ..." or "demap_axis_kernel<mI,mQ,fmt> form=axis ...", then "wg=.. bits=..
@@ -1947,12 +1965,28 @@ class OfdmDemodNode(_Ofdm):
     """Frames of received samples -> records of equalised data-carrier values, in front of DemapNode(n_payload = data_syms):
     prefix removal, transform, least-squares channel estimate from the n_train training symbols (without them: division by
     n_fft * tx_scale), one multiply per carrier, with cpe=True the pilots' common phase removed per symbol; all frames of a call
-    in one launch.  Stateless.  run() takes complex64 (n_frames, frame_samples) and returns complex64 (n_frames, data_syms)."""
+    in one launch.  Stateless.  run() takes complex64 (n_frames, frame_samples) and returns complex64 (n_frames, data_syms); with
+    csi=True (n_train >= 1) it returns (records, csi), csi float32 (n_frames, data carriers): |H_k|^2 of every data carrier in bin
+    order, the same launch with one store more -- DemapNode.run(records, weights=csi) weighs every carrier's LLRs by it."""
     _direction = _lib.OFDM_DEMOD
     _frame = _FrameCall("comms_ofdm_demod_run", np.complex64, np.complex64, _Ofdm._sample_bytes, _Ofdm._data_bytes)
+    _frame_csi = _FrameCall("comms_ofdm_demod_csi_run", np.complex64, np.complex64, _Ofdm._sample_bytes, _Ofdm._data_bytes)
 
-    def run(self, samples):
-        return self._frame.run(self, samples)
+    @property
+    def data_carriers(self):
+        return self.data_syms // self.n_syms
+
+    def run(self, samples, csi=False):
+        if not csi:
+            return self._frame.run(self, samples)
+        # the side output is one record of data_carriers floats per frame: a sub-array dtype gives it that shape
+        return self._frame_csi.run(self, samples, side=(np.dtype((np.float32, (self.data_carriers,))),))
+
+    def run_dev(self, in_ptr, n_frames, out_ptr, stream=0, csi_ptr=None):
+        if csi_ptr is None:
+            self._frame.run_dev(self, in_ptr, n_frames, out_ptr, stream)
+        else:
+            self._frame_csi.run_dev(self, in_ptr, n_frames, out_ptr, csi_ptr, stream)
 
 
 class OfdmSyncNode(_History, _Detector, _Handle):
