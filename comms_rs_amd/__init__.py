@@ -16,4 +16,4 @@ from .nodes import (BatchFirNode, BatchFirNodeI16, FirNodeI16, PulseNodeI16, Bat
                     psk_phase_estimate_c32_dev, qam_phase_estimate_c32_dev, FrameSyncNode, FrameDetection,
                     FRAME_DETECTION_DTYPE, DeframeNode, FRAME_HEADER_DTYPE, ConvEncoderNode, ViterbiNode,
                     RateMatchNode, RateDematchNode, CrcAttachNode, CrcCheckNode, SymbolMapNode, DemapNode, qam_table, psk_table,
-                    OfdmModNode, OfdmDemodNode, OfdmSyncNode, LdpcEncoderNode, LdpcDecoderNode)
+                    OfdmModNode, OfdmDemodNode, OfdmSyncNode, LdpcEncoderNode, LdpcDecoderNode, SpectrumNode, window_taps)

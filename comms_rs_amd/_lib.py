@@ -29,6 +29,9 @@ OFDM_MOD, OFDM_DEMOD = 0, 1     # comms_ofdm_get_kernel: direction
 BITS_U8, BITS_PACKED = 0, 1     # comms_prns_run formats
 RESAMPLE_F32, RESAMPLE_C32 = 4, 8  # comms_resample_create: bytes per sample
 CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR = 0, 1  # comms_channelizer_create: layout
+SPECTRUM_NATURAL, SPECTRUM_CENTRED = 0, 1  # comms_spectrum_create: order
+SPECTRUM_CHUNK = 32             # segments per partial sum of a spectrum row
+WINDOW_RECT, WINDOW_HANN, WINDOW_HAMMING, WINDOW_BLACKMAN = 0, 1, 2, 3  # comms_window_taps: kind
 STREAM_HANDLE = C.c_void_p(-1).value  # COMMS_STREAM_HANDLE: the handle's own stream
 
 
@@ -407,6 +410,21 @@ _PROTOS = {
     "comms_ofdmsync_get_kernel": [_vp, _sz, C.c_char_p, _sz],
     "comms_ofdmsync_set_timer": [_vp, _vp],
     "comms_ofdmsync_destroy": [_vp],
+    "comms_window_taps": [_i32, _sz, _vp],
+    "comms_spectrum_create": [_i32, _vp, _sz, _sz, C.c_float, _i32, _i32, _pp],
+    "comms_spectrum_out_len": [_vp, _sz, _psz],
+    "comms_spectrum_state_len": [_i32, _psz],
+    "comms_spectrum_run_dev": [_vp, _vp, _sz, _vp, _vp],
+    "comms_spectrum_run": [_vp, _vp, _sz, _vp],
+    "comms_spectrum_get_state": [_vp, _vp, _sz],
+    "comms_spectrum_set_state": [_vp, _vp, _sz],
+    "comms_spectrum_get_position": [_vp, C.POINTER(_u64)],
+    "comms_spectrum_set_position": [_vp, _u64],
+    "comms_spectrum_get_acc": [_vp, _vp, _sz],
+    "comms_spectrum_set_acc": [_vp, _vp, _sz],
+    "comms_spectrum_get_kernel": [_vp, _sz, C.c_char_p, _sz],
+    "comms_spectrum_set_timer": [_vp, _vp],
+    "comms_spectrum_destroy": [_vp],
     "comms_nco_create": [_f64, _f64, _i32, _pp],
     "comms_nco_run": [_vp, _vp, _sz, _vp],
     "comms_nco_run_dev": [_vp, _vp, _sz, _vp, _vp],

@@ -4,7 +4,7 @@
 //   * its position accessors and the threshold check: get_position / set_position, check_threshold / set_threshold;
 //   * the input-only host staging of a node that returns no sample stream: stage_input;
 //   * the whole detection step of a synchroniser: detect_prologue, detection_bound, detection_step;
-//   * the grid of its persistent kernel (tile_grid) and, for a polyphase filter, polyphase_rows and tile_workgroup.
+//   * the grid of its persistent kernel (tile_grid, persistent_cap) and, for a polyphase filter, polyphase_rows and tile_workgroup.
 // (Everything here is static: no function or instantiation of this header is a symbol of the library.)
 #pragma once
 
@@ -149,6 +149,10 @@ static comms_status_t detection_step(Scratch& list, size_t bound, hipStream_t s,
 // The grid of a persistent kernel that walks `tiles` tiles: capped_grid, except that an empty call has no grid (nothing is
 // launched for it, and get_kernel reports grid=0)
 static inline size_t tile_grid(size_t tiles, unsigned max_grid) { return tiles ? capped_grid(tiles, max_grid) : 0; }
+// The cap itself, from the LDS bytes of a workgroup (0: a kernel without LDS): the workgroups the chip holds at once, lowered by the
+// diagnostic build's COMMS_GRID_CAP.  A node that takes its cap here has its capped-grid cases in a test file of its own
+// (tests/test_gpu_spectrum_grids.py); tests/grid_cases.py lists the .hip files that ask common.hpp directly.
+static inline unsigned persistent_cap(size_t lds) { return resident_workgroups(lds); }
 
 // Polyphase row table of `taps` over L phases, rows of RS floats padded with zeros: tab[p * RS + q] = taps[p + L * q]
 static inline std::vector<float> polyphase_rows(const float* taps, size_t n_taps, size_t L, size_t RS) {

@@ -41,6 +41,19 @@ comms_status_t comms_rect_taps(size_t n_taps, comms_c32* out) {
     return COMMS_OK;
 }
 
+// The periodic (DFT-even) windows of the spectrum estimator: a0 - a1 cos(2 pi n / N) + a2 cos(4 pi n / N), f64, rounded once
+comms_status_t comms_window_taps(int32_t kind, size_t n, float* out) {
+    COMMS_ARG(kind >= COMMS_WINDOW_RECT && kind <= COMMS_WINDOW_BLACKMAN, "kind must be COMMS_WINDOW_RECT ... COMMS_WINDOW_BLACKMAN (got %d)", kind);
+    COMMS_ARG(out || !n, "out is NULL");
+    static const double coef[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.0}, {0.54, 0.46, 0.0}, {0.42, 0.5, 0.08}};
+    const double* a = coef[kind];
+    for (size_t i = 0; i < n; ++i) {
+        const double t = 2.0 * kPi * static_cast<double>(i) / static_cast<double>(n);
+        out[i] = static_cast<float>(a[0] - a[1] * std::cos(t) + a[2] * std::cos(2.0 * t));
+    }
+    return COMMS_OK;
+}
+
 comms_status_t comms_gaussian_taps(uint32_t n_taps, double sam_per_sym, double alpha,
                                    comms_c32* out) {
     COMMS_ARG(out || !n_taps, "out is NULL");

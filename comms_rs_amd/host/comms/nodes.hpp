@@ -861,6 +861,81 @@ public:
         : DevNode(device, "ChannelizerNodeDev::new", taps, channels, down, layout, device) {}
 };
 
+// Spectrum estimator as ONE node (comms_spectrum_*; an additional node): windowed, overlapping segments of a Complex32 stream ->
+// forward transform -> |X|^2 -> the sum of `avg` segments per row, times scale.  Any message length; a message carries the rows
+// its samples complete, rows x n_fft floats, and a call that completes no row sends no message (the #[aggregate] form).
+// scale <= 0 asks for the Welch scale 1 / (avg sum w^2).
+struct SpectrumOp {
+    using In = Complex32;
+    using Out = float;
+    SpectrumOp(const char* who, int32_t n_fft, const std::vector<float>& window, size_t hop, size_t avg, float scale, int32_t order, int device)
+        : n_fft_(static_cast<size_t>(n_fft)) {
+        if (window.size() != n_fft_) throw std::runtime_error(std::string(who) + ": the window must hold n_fft values");
+        if (!(scale > 0.0f)) {
+            double e = 0.0;
+            for (float w : window) e += static_cast<double>(w) * w;
+            scale = static_cast<float>(1.0 / (static_cast<double>(avg ? avg : 1) * e));
+        }
+        h_ = create<decltype(h_)>(who, comms_spectrum_create, n_fft, window.data(), hop, avg, scale, order, device);
+    }
+    size_t n_fft() const { return n_fft_; }
+    std::string kernel(size_t n) const { return kernel_name(comms_spectrum_get_kernel, h_.get(), n); }  // "spectrum_kernel<..> ..."
+    // comms_window_taps: "rect", "hann", "hamming", "blackman" as COMMS_WINDOW_*
+    static std::vector<float> window(int32_t kind, size_t n) {
+        std::vector<float> w(n);
+        throw_on(comms_window_taps(kind, n, w.data()), "comms_window_taps");
+        return w;
+    }
+
+protected:
+    comms_status_t prepare(size_t n, size_t& m) const {
+        comms_status_t st = comms_spectrum_out_len(h_.get(), n, &m);  // rows
+        m *= n_fft_;
+        return st;
+    }
+    comms_status_t launch(const Complex32* in, size_t n, float* out) { return comms_spectrum_run(h_.get(), c32(in), n, out); }
+    comms_status_t launch_dev(const Complex32* in, size_t n, float* out, void* s) { return comms_spectrum_run_dev(h_.get(), c32(in), n, out, s); }
+    Owned<comms_spectrum_t, comms_spectrum_destroy> h_;
+    size_t n_fft_;
+};
+class SpectrumNode : public DeriveNode<SpectrumNode>, public Ports<std::vector<Complex32>, std::vector<float>>, public SpectrumOp {
+public:
+    SpectrumNode(int32_t n_fft, const std::vector<float>& window, size_t hop, size_t avg = 1, float scale = 0.0f,
+                 int32_t order = COMMS_SPECTRUM_NATURAL, int device = 0)
+        : SpectrumOp("SpectrumNode::new", n_fft, window, hop, avg, scale, order, device) {}
+    SpectrumNode(SpectrumNode&&) = default;
+
+    Result<std::optional<std::vector<float>>> run(const std::vector<Complex32>& in) {
+        size_t m = 0;
+        comms_status_t st = prepare(in.size(), m);
+        if (st != COMMS_OK) return to_node_error(st);
+        std::vector<float> rows(m);
+        st = launch(in.data(), in.size(), rows.data());
+        if (st != COMMS_OK) return to_node_error(st);
+        if (!m) return std::optional<std::vector<float>>(std::nullopt);
+        return std::optional<std::vector<float>>(std::move(rows));
+    }
+};
+// on device-resident messages
+class SpectrumNodeDev : public DeriveNode<SpectrumNodeDev>, public Ports<DeviceBuf<Complex32>, DeviceBuf<float>>, public OnStream<SpectrumOp> {
+public:
+    SpectrumNodeDev(int32_t n_fft, const std::vector<float>& window, size_t hop, size_t avg = 1, float scale = 0.0f,
+                    int32_t order = COMMS_SPECTRUM_NATURAL, int device = 0)
+        : OnStream<SpectrumOp>(device, "SpectrumNodeDev::new", n_fft, window, hop, avg, scale, order, device) {}
+    SpectrumNodeDev(SpectrumNodeDev&&) = default;
+
+    Result<std::optional<DeviceBuf<float>>> run(const DeviceBuf<Complex32>& in) {
+        size_t m = 0;
+        comms_status_t st = prepare(in.size(), m);
+        if (st != COMMS_OK) return to_node_error(st);
+        DeviceBuf<float> rows(m ? m : 1, this->device());   // (a call without a row still advances the state: it writes nothing here)
+        st = this->submit(in, rows, [&](void* s) { return launch_dev(in.ptr(), in.size(), rows.ptr(), s); });
+        if (st != COMMS_OK) return to_node_error(st);
+        if (!m) return std::optional<DeviceBuf<float>>(std::nullopt);
+        return std::optional<DeviceBuf<float>>(std::move(rows));
+    }
+};
+
 // Symbol synchroniser as ONE node (comms_symsync_*; an additional node): matched filter with a fractional delay, symbol-rate
 // sampler, rotation and -- with set_output_bits -- hard decision, the results of UpsampleNode(phases) -> BatchFirNode(Complex(
 // taps, 0)) -> skip mu -> DecimateNode(phases sps) -> MixerNode.  Messages are multiples of sps samples and give n / sps

@@ -987,6 +987,74 @@ class SymbolSyncNode(_History, _Handle):
     state = property(_History.get_state, _History.set_state)
 
 
+class SpectrumNode(_History, _Position, _Handle):
+    """Spectrum estimator (comms_spectrum_*): windowed, overlapping segments of a Complex<f32> stream -> forward n_fft-point
+    transform -> |X|^2 -> the sum of `avg` segments per output row, times `scale`, in one launch (two when avg > 32).  `window`
+    is a name ("rect", "hann", "hamming", "blackman": window_taps) or n_fft floats; hop defaults to n_fft / 2; scale defaults
+    to 1 / (avg sum w^2), the Welch power spectral density estimate per bin; order "natural" (column k is bin k) or "centred"
+    (fftshift).  Any batch length: a call returns the rows it completes, (rows, n_fft) float32, and the rows of a stream do
+    not depend on how it is cut into calls.  State: the last n_fft - 1 samples (state), the stream index (position) and the
+    sums of the incomplete row (acc)."""
+    _prefix = "comms_spectrum"
+    _state_args = ("n_fft",)
+    ORDERS = {"natural": 0, "centred": 1, "centered": 1, 0: 0, 1: 1}
+
+    def __init__(self, n_fft, window="hann", hop=None, avg=1, scale=None, order="natural", device=0):
+        super().__init__()
+        self.n_fft = int(n_fft)
+        if order not in self.ORDERS:
+            raise ValueError("order is 'natural' or 'centred', not %r" % (order,))
+        window = window_taps(window, self.n_fft) if isinstance(window, str) else np.ascontiguousarray(window, dtype=np.float32)
+        if window.size != self.n_fft:
+            raise ValueError("the window has %d values, n_fft is %d" % (window.size, self.n_fft))
+        self.window, self.order = window, self.ORDERS[order]
+        self.hop, self.avg = (self.n_fft // 2 if hop is None else int(hop)), int(avg)
+        self.scale = float(1.0 / (self.avg * np.sum(window.astype(np.float64) ** 2))) if scale is None else float(scale)
+        check(lib().comms_spectrum_create(self.n_fft, _ptr(window), self.hop, self.avg, self.scale, self.order, device, C.byref(self._h)))
+
+    def out_len(self, n):
+        """Rows a call of n samples completes at the node's position."""
+        return _get(C.c_size_t, lib().comms_spectrum_out_len, self._h, n)
+
+    def kernel(self, n):
+        """What a call of n samples is run by: "spectrum_kernel<..> ...", and " + spectrum_rows_kernel ..." when avg > 32."""
+        return self._kernel_name(n)
+
+    def run(self, x):
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        out = np.empty((self.out_len(x.size), self.n_fft), np.float32)
+        check(lib().comms_spectrum_run(self._h, _ptr(x), x.size, _ptr(out) if out.size else None))
+        return out
+
+    def run_dev(self, in_ptr, n, out_ptr, stream=0):
+        check(lib().comms_spectrum_run_dev(self._h, in_ptr, n, out_ptr, stream))
+
+    state = property(_History.get_state, _History.set_state)
+    position = property(_Position.position, _Position.set_position)
+
+    def get_acc(self):
+        """The sums of the incomplete row: (2, n_fft) float32, R then the incomplete chunk's c, natural bin order."""
+        acc = np.empty((2, self.n_fft), np.float32)
+        check(lib().comms_spectrum_get_acc(self._h, _ptr(acc), acc.size))
+        return acc
+
+    def set_acc(self, acc):
+        acc = np.ascontiguousarray(acc, dtype=np.float32)
+        check(lib().comms_spectrum_set_acc(self._h, _ptr(acc), acc.size))
+
+    acc = property(get_acc, set_acc)
+
+
+_WINDOWS = {"rect": 0, "hann": 1, "hamming": 2, "blackman": 3}
+
+
+def window_taps(kind, n):
+    """The periodic (DFT-even) window `kind` ("rect", "hann", "hamming", "blackman", or its COMMS_WINDOW_* code) of n floats."""
+    out = np.empty(int(n), np.float32)
+    check(lib().comms_window_taps(_WINDOWS.get(kind, kind), int(n), _ptr(out)))
+    return out
+
+
 # ------------------------------------------------------------------ tap design
 def _taps(fn, n_taps, *args):
     out = np.empty(int(n_taps), np.complex64)
