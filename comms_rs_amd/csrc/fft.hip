@@ -25,8 +25,10 @@
 #include <vector>
 
 #include "common.hpp"
+#include "fft_plan.hpp"  // which kernels a length runs on
 #include "fft_radix.hpp"
 #include "fir_handle.hpp"  // make_rsrc: buffer-addressed rows
+#include "roots.hpp"
 
 namespace comms {
 
@@ -1173,48 +1175,46 @@ __global__ void blu_post_kernel(const cf* __restrict__ a, const cf* __restrict__
 
 using namespace comms;
 
-static const double kPiF = 3.14159265358979323846264338327950288;
-
-static int ilog2(size_t v) {
-    int l = 0;
-    while ((static_cast<size_t>(1) << l) < v) ++l;
-    return l;
+// The diagnostic build's selectors, read once (the product build has their defaults at compile time)
+static const FftKnobs& fft_knobs() {
+    static const FftKnobs knobs = [] {
+        FftKnobs k;
+        k.no_rx = diag_knob("COMMS_FFT_NO_RX", k.no_rx) != 0;
+        k.no_rx32k = diag_knob("COMMS_FFT_NO_RX32K", k.no_rx32k) != 0;
+        k.no_cols = diag_knob("COMMS_FFT_NO_COLS", k.no_cols) != 0;
+        k.large_gather = diag_knob("COMMS_FFT_LARGE_GATHER", k.large_gather);
+        k.direct_max = static_cast<size_t>(diag_knob("COMMS_FFT_DIRECT_MAX", static_cast<int>(k.direct_max)));
+        k.blu_unfused = diag_knob("COMMS_FFT_BLU_UNFUSED", k.blu_unfused) != 0;
+        return k;
+    }();
+    return knobs;
 }
 
-// Power-of-two plan: one tile pass (N <= 4096) or two (four-step).
+// A power-of-two plan: the form its length runs on (fft_plan.hpp) and the tables that form reads.
 struct Pow2Plan {
     size_t N = 0;
-    int n_pass = 0;
-    FftTileParams pass[2];
-    DevBuf<float2> d_tw[4];  // twL(pass0), twL(pass1), tw_lo, tw_hi
-    DevBuf<float2> d_fw1;  // fast 16x1024 kernel: W1024^{lane*k0} [16][64]
-    DevBuf<float2> d_fw2;  //                       W64^{c*k1}     [16][4]
-    int rx_rad = 0;           // N = rx_rad * 1024 (2, 4, 8, 16): single-pass fft_rx1024_kernel
-    DevBuf<float2> d_rxa;  //   W_N^{64*wave*k1} [rad][16]
-    DevBuf<float2> d_rxb;  //   W_N^{lane*k1}    [rad][64]
-    DevBuf<float2> d_rx32;  // N = 32768 in one pass (fft_rx32k_kernel): W_N^{t}, W_N^{4 t}, W_N^{16 t}, t < 1024
-    int col_kind = -1;         // four-step pass 1 on fft_cols_kernel: 0 (N1 = 64), 128, 256, 512; -1: tile kernel
-    DevBuf<float2> d_colw1; //   the core's stage table (W256^{b*ka} for the 256-point form, else unused)
-    DevBuf<float2> d_colr;  //   W_N1^{r}, r < N1/2 (radix-2 front stage of 128 / 512)
-    int threads[2] = {0, 0};
-    size_t lds[2] = {0, 0};
-    std::unique_ptr<Pow2Plan> rows;  // N = 2^21 ... 2^24: the plan of the N2-point row transforms (columns: pass[0]; then the transpose)
-
-    bool fast(int i) const { return pass[i].L == 1024 && (pass[i].C == 16 || pass[i].C == 8) && d_fw1; }
+    Pow2Choice choice{Pow2Form::Tile, 0, 0, false};
+    // the two-pass forms and Tile: the passes' geometry (Cols reads pass[0] for tw_lo / tw_hi only, Gather likewise)
+    FftTileParams pass[2] = {};
+    DevBuf<float2> d_tw[4];          // twL(pass 0), twL(pass 1), tw_lo, tw_hi
+    DevBuf<float2> d_fw1;            // fft1024x16_kernel and the 1024-point wave core: W1024^{lane*k0} [16][64]
+    DevBuf<float2> d_fw2;            //                                                 W64^{c*k1}     [16][4]
+    DevBuf<float2> d_w256;           // the 256-point wave core's stage W256^{b*ka} at [ka*16 + b], ones up to 1024 entries
+                                     // (Rx at N = 256 / 512, where it takes d_fw1's argument; Cols)
+    DevBuf<float2> d_front;          // radix-2 front stage W_L^r, r < L/2, then ones (Tiny at 32, Rx at 128 / 512: L = N, in
+                                     // d_rxb's argument; Cols: L = N / 1024)
+    DevBuf<float2> d_rxa;            // Tiny, Rx: W_N^{64*wave*k1} [rad][16], rad = N / 1024 (all ones below 1024 points)
+    DevBuf<float2> d_rxb;            //           W_N^{lane*k1}    [rad][64]
+    DevBuf<float2> d_w32k;           // Rx32k: W_N^{t}, W_N^{4 t}, W_N^{16 t}, t < 1024
+    std::unique_ptr<Pow2Plan> rows;  // Gather, Three: the plan of the N / 1024-point row transforms (form Rx)
 };
 static_assert(!std::is_copy_constructible_v<Pow2Plan>, "a plan owns its tables: never copied");
 
-static comms_status_t upload_tw(size_t count, size_t denom, size_t mult, DevBuf<float2>& d_out) {
-    // table[m] = exp(-2 pi i * (m * mult) / denom), m < count   (forward sign)
-    std::vector<float2> t(count);
-    for (size_t m = 0; m < count; ++m) {
-        size_t e = (m * mult) % denom;
-        double a = -2.0 * kPiF * static_cast<double>(e) / static_cast<double>(denom);
-        t[m] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-    }
-    COMMS_HIP_TRY(d_out.upload(t));
+static comms_status_t upload(DevBuf<float2>& d, const std::vector<float2>& table) {
+    COMMS_HIP_TRY(d.upload(table));
     return COMMS_OK;
 }
+static const cf* dev(const DevBuf<float2>& d) { return reinterpret_cast<const cf*>(d.get()); }
 
 static void tile_geometry(FftTileParams& p, int L, size_t want_c) {
     p.L = L;
@@ -1226,263 +1226,200 @@ static void tile_geometry(FftTileParams& p, int L, size_t want_c) {
     p.logC = ilog2(C);
 }
 
-static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N) {
+// Tile, N <= 4096: one pass
+static comms_status_t one_pass_geometry(Pow2Plan& pl) {
+    const size_t N = pl.N;
+    FftTileParams& p = pl.pass[0];
+    // 1024-point batches: two 8-wave workgroups per CU overlap load/compute/store (measured
+    // 258 vs 226 Gpoints/s); four-step passes keep 16 columns = 128-B row pieces
+    // short transforms: full 16384-point tiles (1024 lanes, 128 KiB of LDS) -- with 16 transforms
+    // per tile a 64-point batch ran one wave per workgroup (74 -> 173 Gpoints/s)
+    static const size_t tile_pts = static_cast<size_t>(diag_knob("COMMS_FFT_TILE_PTS", 16384));
+    tile_geometry(p, static_cast<int>(N), N == 1024 ? 8 : (N < 1024 ? tile_pts / N : 16));
+    // rows mode: tile = C consecutive transforms; the "transform" seen by the
+    // kernel is the tile itself (distance C*N), one tile per transform
+    p.in_cs = N;
+    p.in_ls = 1;
+    p.out_cs = N;
+    p.out_ks = 1;
+    p.tiles_per_xform = 1;
+    p.N = static_cast<size_t>(p.C) * N;
+    COMMS_TRY(upload(pl.d_tw[0], roots<float2>(N, N)));
+    p.twL = dev(pl.d_tw[0]);
+    return COMMS_OK;
+}
+
+// The column pass of every two-pass form: columns n2, FFT over the N1 points n1 (stride N2), twiddle, same positions
+static comms_status_t column_pass(Pow2Plan& pl, size_t N1, size_t want_c) {
+    const size_t N = pl.N, N2 = N / N1;
+    FftTileParams& a = pl.pass[0];
+    tile_geometry(a, static_cast<int>(N1), want_c);
+    a.in_c_fast = 1;
+    a.out_c_fast = 1;
+    a.in_cs = 1;
+    a.in_ls = N2;
+    a.out_cs = 1;
+    a.out_ks = N2;
+    a.tiles_per_xform = N2 / a.C;
+    a.tile_step_in = a.tile_step_out = a.C;
+    a.N = N;
+    a.apply_tw = 1;
+    COMMS_TRY(upload(pl.d_tw[0], roots<float2>(N1, N1)));
+    COMMS_TRY(upload(pl.d_tw[2], roots<float2>(4096, N)));
+    COMMS_TRY(upload(pl.d_tw[3], roots<float2>(N / 4096, N, 4096)));
+    a.twL = dev(pl.d_tw[0]);
+    a.tw_lo = dev(pl.d_tw[2]);
+    a.tw_hi = dev(pl.d_tw[3]);
+    return COMMS_OK;
+}
+
+// 2^13 ... 2^20 in two passes (four-step)
+static comms_status_t four_step_geometry(Pow2Plan& pl) {
+    // 2^15 .. 2^20: N2 = 1024 so that pass 2 (and for 2^20 pass 1 too) runs on fft1024x16_kernel;
+    // the short column pass takes wide tiles (2-KiB row pieces at N1 = 64)
+    const int logN = ilog2(pl.N), log1 = logN >= 15 ? logN - 10 : logN / 2;
+    const size_t N1 = static_cast<size_t>(1) << log1, N2 = pl.N >> log1;
+    COMMS_TRY(column_pass(pl, N1, N1 < 1024 ? (FT_MAX_POINTS / N1 < N2 ? FT_MAX_POINTS / N1 : N2) : 16));
+    // pass 2: rows k1, FFT over n2, transposed store -> X[k1 + N1*k2]
+    FftTileParams& b = pl.pass[1];
+    tile_geometry(b, static_cast<int>(N2), 16);
+    b.in_c_fast = 0;
+    b.out_c_fast = 1;
+    b.in_cs = N2;
+    b.in_ls = 1;
+    b.out_cs = 1;
+    b.out_ks = N1;
+    b.tiles_per_xform = N1 / b.C;
+    b.tile_step_in = static_cast<size_t>(b.C) * N2;
+    b.tile_step_out = b.C;
+    b.N = pl.N;
+    COMMS_TRY(upload(pl.d_tw[1], roots<float2>(N2, N2)));
+    b.twL = dev(pl.d_tw[1]);
+    return COMMS_OK;
+}
+
+// 2^21 ... 2^24: N2 = N / 1024-point rows.  pass[0] is the 1024-point column pass (stride N2) that Three launches and
+// whose tw_lo / tw_hi Gather's column kernel reads; pass[1] is Gather's row pass: tile t = the 16 adjacent outputs k of
+// every column, as the column kernel left them ([k / 16][column][k % 16]); 1024-point transforms over the columns;
+// X[k + N2 k2] in 128-byte pieces
+static comms_status_t large_geometry(Pow2Plan& pl) {
+    const size_t N2 = pl.N >> 10;
+    COMMS_TRY(column_pass(pl, 1024, 16));
+    FftTileParams& b = pl.pass[1];
+    tile_geometry(b, 1024, 16);
+    b.in_c_fast = 1;
+    b.out_c_fast = 1;
+    b.in_cs = 1;
+    b.in_ls = 16;
+    b.out_cs = 1;
+    b.out_ks = N2;
+    b.tiles_per_xform = N2 / 16;
+    b.tile_step_in = 16384;
+    b.tile_step_out = 16;
+    b.N = pl.N;
+    b.twL = pl.pass[0].twL;
+    return COMMS_OK;
+}
+
+static comms_status_t fast_tables(Pow2Plan& pl) {
+    COMMS_TRY(upload(pl.d_fw1, root_grid<float2>(16, 64, 1024)));
+    return upload(pl.d_fw2, root_grid<float2>(16, 4, 64));
+}
+static std::vector<float2> w256_table() { return root_grid<float2>(16, 16, 256, 1, 1024); }
+
+static comms_status_t pow2_plan_build(Pow2Plan& pl, size_t N, const Pow2Choice& choice) {
     pl.N = N;
-    const int logN = ilog2(N);
-    COMMS_ARG(logN <= 24, "power-of-two FFT supports up to 2^24 points (got 2^%d)", logN);
-    if (N <= 4096) {
-        pl.n_pass = 1;
-        FftTileParams& p = pl.pass[0];
-        memset(&p, 0, sizeof(p));
-        // 1024-point batches: two 8-wave workgroups per CU overlap load/compute/store (measured
-        // 258 vs 226 Gpoints/s); four-step passes keep 16 columns = 128-B row pieces
-        // short transforms: full 16384-point tiles (1024 lanes, 128 KiB of LDS) -- with 16 transforms
-        // per tile a 64-point batch ran one wave per workgroup (74 -> 173 Gpoints/s)
-        static const size_t tile_pts = static_cast<size_t>(diag_knob("COMMS_FFT_TILE_PTS", 16384));
-        tile_geometry(p, static_cast<int>(N), N == 1024 ? 8 : (N < 1024 ? tile_pts / N : 16));
-        // rows mode: tile = C consecutive transforms; the "transform" seen by the
-        // kernel is the tile itself (distance C*N), one tile per transform
-        p.in_c_fast = 0;
-        p.out_c_fast = 0;
-        p.in_cs = N;
-        p.in_ls = 1;
-        p.out_cs = N;
-        p.out_ks = 1;
-        p.tiles_per_xform = 1;
-        p.tile_step_in = p.tile_step_out = 0;
-        p.N = static_cast<size_t>(p.C) * N;
-        COMMS_TRY(upload_tw(N, N, 1, pl.d_tw[0]));
-        p.twL = reinterpret_cast<const cf*>(pl.d_tw[0].get());
-    } else if (logN > 20) {
-        // 2^21 .. 2^24: columns of 1024 points (stride N2) -> rows of N2 = N / 1024 points -> transpose
-        pl.n_pass = 2;  // (pass[1] is unused; the row transforms have a plan of their own)
-        const size_t N2 = N >> 10;
-        FftTileParams& a = pl.pass[0];
-        memset(&a, 0, sizeof(a));
-        memset(&pl.pass[1], 0, sizeof(pl.pass[1]));
-        tile_geometry(a, 1024, 16);
-        a.in_c_fast = 1;
-        a.out_c_fast = 1;
-        a.in_cs = 1;
-        a.in_ls = N2;
-        a.out_cs = 1;
-        a.out_ks = N2;
-        a.tiles_per_xform = N2 / a.C;
-        a.tile_step_in = a.tile_step_out = a.C;
-        a.N = N;
-        a.apply_tw = 1;
-        COMMS_TRY(upload_tw(1024, 1024, 1, pl.d_tw[0]));
-        COMMS_TRY(upload_tw(4096, N, 1, pl.d_tw[2]));
-        COMMS_TRY(upload_tw(N / 4096, N, 4096, pl.d_tw[3]));
-        a.twL = reinterpret_cast<const cf*>(pl.d_tw[0].get());
-        a.tw_lo = reinterpret_cast<const cf*>(pl.d_tw[2].get());
-        a.tw_hi = reinterpret_cast<const cf*>(pl.d_tw[3].get());
-        // row pass of the two-pass form: tile t = the 16 adjacent outputs k of every column, as the column pass left them
-        // ([k / 16][column][k % 16]); 1024-point transforms over the columns; X[k + N2 k2] in 128-byte pieces
-        FftTileParams& b = pl.pass[1];
-        tile_geometry(b, 1024, 16);
-        b.in_c_fast = 1;
-        b.out_c_fast = 1;
-        b.in_cs = 1;
-        b.in_ls = 16;
-        b.out_cs = 1;
-        b.out_ks = N2;
-        b.tiles_per_xform = N2 / 16;
-        b.tile_step_in = 16384;
-        b.tile_step_out = 16;
-        b.N = N;
-        b.twL = a.twL;
-        pl.rows.reset(new (std::nothrow) Pow2Plan);
-        COMMS_ARG(pl.rows != nullptr, "out of host memory");
-        COMMS_TRY(pow2_plan_build(*pl.rows, N2));
-    } else {
-        pl.n_pass = 2;
-        // 2^15 .. 2^20: N2 = 1024 so that pass 2 (and for 2^20 pass 1 too) runs on fft1024x16_kernel;
-        // the short column pass takes wide tiles (2-KiB row pieces at N1 = 64)
-        const int log1 = (logN >= 15 && logN <= 20) ? logN - 10 : logN / 2, log2v = logN - log1;
-        const size_t N1 = static_cast<size_t>(1) << log1, N2 = static_cast<size_t>(1) << log2v;
-        // pass 1: columns n2, FFT over n1 (stride N2), twiddle, in place
-        FftTileParams& a = pl.pass[0];
-        memset(&a, 0, sizeof(a));
-        tile_geometry(a, static_cast<int>(N1), N1 < 1024 ? (FT_MAX_POINTS / N1 < N2 ? FT_MAX_POINTS / N1 : N2) : 16);
-        a.in_c_fast = 1;
-        a.out_c_fast = 1;
-        a.in_cs = 1;
-        a.in_ls = N2;
-        a.out_cs = 1;
-        a.out_ks = N2;
-        a.tiles_per_xform = N2 / a.C;
-        a.tile_step_in = a.tile_step_out = a.C;
-        a.N = N;
-        a.apply_tw = 1;
-        COMMS_TRY(upload_tw(N1, N1, 1, pl.d_tw[0]));
-        COMMS_TRY(upload_tw(4096, N, 1, pl.d_tw[2]));
-        COMMS_TRY(upload_tw(N / 4096, N, 4096, pl.d_tw[3]));
-        a.twL = reinterpret_cast<const cf*>(pl.d_tw[0].get());
-        a.tw_lo = reinterpret_cast<const cf*>(pl.d_tw[2].get());
-        a.tw_hi = reinterpret_cast<const cf*>(pl.d_tw[3].get());
-        // pass 2: rows k1, FFT over n2, transposed store -> X[k1 + N1*k2]
-        FftTileParams& b = pl.pass[1];
-        memset(&b, 0, sizeof(b));
-        tile_geometry(b, static_cast<int>(N2), 16);
-        b.in_c_fast = 0;
-        b.out_c_fast = 1;
-        b.in_cs = N2;
-        b.in_ls = 1;
-        b.out_cs = 1;
-        b.out_ks = N1;
-        b.tiles_per_xform = N1 / b.C;
-        b.tile_step_in = static_cast<size_t>(b.C) * N2;
-        b.tile_step_out = b.C;
-        b.N = N;
-        COMMS_TRY(upload_tw(N2, N2, 1, pl.d_tw[1]));
-        b.twL = reinterpret_cast<const cf*>(pl.d_tw[1].get());
-    }
-    for (int i = 0; i < pl.n_pass; ++i) {
-        const int npts = pl.pass[i].L * pl.pass[i].C;
-        int T = npts / FT_PTS;
-        if (T < 64) T = 64;
-        if (T > 1024) T = 1024;
-        pl.threads[i] = T;
-        pl.lds[i] = static_cast<size_t>(npts) * sizeof(float2);
-    }
-    const bool rx = (N >= 2 && N <= 32) || N == 64 || N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048 || N == 4096 || N == 8192 || N == 16384;
-    if (pl.pass[0].L == 1024 || (pl.n_pass == 2 && pl.pass[1].L == 1024) || rx) {
-        std::vector<float2> t1(1024), t2(64);
-        for (int k0 = 0; k0 < 16; ++k0)
-            for (int t = 0; t < 64; ++t) {
-                const double a = -2.0 * kPiF * static_cast<double>((t * k0) % 1024) / 1024.0;
-                t1[k0 * 64 + t] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-            }
-        for (int k1 = 0; k1 < 16; ++k1)
-            for (int c = 0; c < 4; ++c) {
-                const double a = -2.0 * kPiF * static_cast<double>((c * k1) % 64) / 64.0;
-                t2[k1 * 4 + c] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-            }
-        COMMS_HIP_TRY(pl.d_fw1.alloc(t1.size()));
-        COMMS_HIP_TRY(pl.d_fw2.alloc(t2.size()));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_fw1.get(), t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_fw2.get(), t2.data(), t2.size() * sizeof(float2), hipMemcpyHostToDevice));
-    }
-    if (rx) {
-        const int rad = N < 1024 ? 1 : static_cast<int>(N / 1024);  // (N = 64, 256: tables unused, kept for the common signature)
-        std::vector<float2> ta(rad * 16), tb(rad * 64);
-        for (int k = 0; k < rad; ++k) {
-            for (int w = 0; w < 16; ++w) {
-                const double a = -2.0 * kPiF * static_cast<double>((64ull * w * k) % N) / static_cast<double>(N);
-                ta[k * 16 + w] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-            }
-            for (int l = 0; l < 64; ++l) {
-                const double a = -2.0 * kPiF * static_cast<double>((static_cast<size_t>(l) * k) % N) / static_cast<double>(N);
-                tb[k * 64 + l] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-            }
+    pl.choice = choice;
+    switch (choice.form) {
+        case Pow2Form::Tiny:
+        case Pow2Form::Rx: {
+            const size_t rad = N < 1024 ? 1 : N / 1024;
+            const bool c256 = N == 256 || N == 512, front = N == 32 || N == 128 || N == 512;
+            COMMS_TRY(c256 ? upload(pl.d_w256, w256_table()) : upload(pl.d_fw1, root_grid<float2>(16, 64, 1024)));
+            COMMS_TRY(upload(pl.d_fw2, root_grid<float2>(16, 4, 64)));
+            COMMS_TRY(upload(pl.d_rxa, root_grid<float2>(rad, 16, N, 64)));
+            return front ? upload(pl.d_front, roots<float2>(N / 2, N, 1, 64)) : upload(pl.d_rxb, root_grid<float2>(rad, 64, N));
         }
-        COMMS_HIP_TRY(pl.d_rxa.alloc(ta.size()));
-        COMMS_HIP_TRY(pl.d_rxb.alloc(tb.size()));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_rxa.get(), ta.data(), ta.size() * sizeof(float2), hipMemcpyHostToDevice));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_rxb.get(), tb.data(), tb.size() * sizeof(float2), hipMemcpyHostToDevice));
-        pl.rx_rad = N == 64 ? -1 : N == 256 ? -2 : N == 128 ? -3 : N == 512 ? -4 : N <= 32 ? -static_cast<int>(N) - 100 : rad;  // < 0: the short forms (-100 - N: the tiny ones)
-        if (N == 128 || N == 512 || N == 32) {  // W_N^{n2}, n2 < N/2, for the radix-2 front stage
-            std::vector<float2> t(N / 2 < 64 ? 64 : N / 2, make_float2(1.f, 0.f));
-            for (size_t j = 0; j < N / 2; ++j) {
-                const double a = -2.0 * kPiF * static_cast<double>(j) / static_cast<double>(N);
-                t[j] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
+        case Pow2Form::Rx32k: {  // three twiddle values per thread
+            std::vector<float2> t;
+            for (size_t mult : {1, 4, 16}) {
+                const std::vector<float2> w = roots<float2>(1024, N, mult);
+                t.insert(t.end(), w.begin(), w.end());
             }
-            COMMS_HIP_TRY(pl.d_rxb.alloc(t.size()));
-            COMMS_HIP_TRY(hipMemcpy(pl.d_rxb.get(), t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
+            COMMS_TRY(fast_tables(pl));
+            return upload(pl.d_w32k, t);
         }
-        if (N == 256 || N == 512) {  // its stage twiddle W256^{b*ka} at [ka*16 + b] takes the place of the W1024 table
-            std::vector<float2> t1(1024, make_float2(1.f, 0.f));
-            for (int k = 0; k < 16; ++k)
-                for (int bq = 0; bq < 16; ++bq) {
-                    const double a = -2.0 * kPiF * static_cast<double>((bq * k) % 256) / 256.0;
-                    t1[k * 16 + bq] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-                }
-            COMMS_HIP_TRY(hipMemcpy(pl.d_fw1.get(), t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
-        }
-    }
-    if (pl.n_pass == 2 && pl.pass[1].L == 1024 && pl.d_fw1 &&
-        (pl.pass[0].L == 64 || pl.pass[0].L == 128 || pl.pass[0].L == 256 || pl.pass[0].L == 512)) {
-        // (N1 = 32, i.e. N = 32768, runs in one pass on fft_rx32k_kernel since round 4; its 16-point column form --
-        // half of its LDS cycles bank conflicts -- is retired, COMMS_FFT_NO_RX32K falls back to the generic tile kernel)
-        const int n1 = pl.pass[0].L;
-        std::vector<float2> t1(1024, make_float2(1.f, 0.f)), tr(256, make_float2(1.f, 0.f));
-        for (int k = 0; k < 16; ++k)
-            for (int bq = 0; bq < 16; ++bq) {
-                const double a = -2.0 * kPiF * static_cast<double>((bq * k) % 256) / 256.0;
-                t1[k * 16 + bq] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-            }
-        for (int r = 0; r < n1 / 2; ++r) {
-            const double a = -2.0 * kPiF * static_cast<double>(r) / static_cast<double>(n1);
-            tr[r] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-        }
-        COMMS_HIP_TRY(pl.d_colw1.alloc(t1.size()));
-        COMMS_HIP_TRY(pl.d_colr.alloc(tr.size()));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_colw1.get(), t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_colr.get(), tr.data(), tr.size() * sizeof(float2), hipMemcpyHostToDevice));
-        pl.col_kind = n1 == 64 ? 0 : n1;
-    }
-    if (N == 32768 && pl.d_fw1) {  // the single-pass form: three twiddle values per thread
-        std::vector<float2> t(3 * 1024);
-        const size_t mult[3] = {1, 4, 16};
-        for (int i = 0; i < 3; ++i)
-            for (size_t n2 = 0; n2 < 1024; ++n2) {
-                const double a = -2.0 * kPiF * static_cast<double>((n2 * mult[i]) % N) / static_cast<double>(N);
-                t[i * 1024 + n2] = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-            }
-        COMMS_HIP_TRY(pl.d_rx32.alloc(t.size()));
-        COMMS_HIP_TRY(hipMemcpy(pl.d_rx32.get(), t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
+        case Pow2Form::Cols:
+            // (32-point columns, i.e. N = 32768, run in one pass on fft_rx32k_kernel; their 16-point column form -- half of
+            // its LDS cycles bank conflicts -- is retired, COMMS_FFT_NO_RX32K falls back to the generic tile kernel)
+            COMMS_TRY(four_step_geometry(pl));
+            COMMS_TRY(fast_tables(pl));
+            COMMS_TRY(upload(pl.d_w256, w256_table()));
+            return upload(pl.d_front, roots<float2>(pl.pass[0].L / 2, pl.pass[0].L, 1, 256));
+        case Pow2Form::Fast20:
+            COMMS_TRY(four_step_geometry(pl));
+            return fast_tables(pl);
+        case Pow2Form::Gather:
+        case Pow2Form::Three:
+            COMMS_TRY(large_geometry(pl));
+            COMMS_TRY(fast_tables(pl));
+            pl.rows.reset(new (std::nothrow) Pow2Plan);
+            COMMS_ARG(pl.rows != nullptr, "out of host memory");
+            // (the rows are on the single-pass kernel whatever the selectors say: both forms launch it themselves)
+            return pow2_plan_build(*pl.rows, N >> 10, pow2_form(N >> 10, FftKnobs{}));
+        case Pow2Form::Tile:
+            COMMS_TRY(N <= kTileOnePassMax ? one_pass_geometry(pl) : four_step_geometry(pl));
+            return N == 1024 || N >= 32768 ? fast_tables(pl) : COMMS_OK;  // the passes that stay on fft1024x16_kernel
     }
     return COMMS_OK;
 }
 
-// Runs `batch` transforms of length pl.N.  In-place (in == out) is fine: every
-// tile is fully read before it is written and tiles do not overlap; pass 2
-// reads what pass 1 wrote to `out`.
-static comms_status_t launch_fast(Pow2Plan& pl, const float2* src, float2* dst, const FftTileParams& p,
-                                  bool inverse, hipStream_t s) {
-    const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1.get());
-    const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
-    const cf* a = reinterpret_cast<const cf*>(src);
-    cf* d = reinterpret_cast<cf*>(dst);
+// ---- launchers: one kernel each; `inverse` picks DIR = +1, else -1 ------------------------------------------------------
+template <class F>
+static auto with_dir(bool inverse, F&& f) {
+    return inverse ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, -1>{});
+}
+// The grid of a persistent kernel with n units of work: one workgroup per unit, at most `slots`
+static unsigned persistent_grid(size_t n, size_t slots = kNumCU) { return static_cast<unsigned>(n < slots ? n : slots); }
+
+static comms_status_t launch_fast(const Pow2Plan& pl, const cf* a, cf* d, const FftTileParams& p, bool inverse, hipStream_t s) {
+    const cf* t1 = dev(pl.d_fw1);
+    const cf* t2 = dev(pl.d_fw2);
     if (p.C == 16) {  // one 16-wave workgroup per CU
         const size_t lds = (1024 + 64 + 16 * FW_BUF + 256) * sizeof(float2);
-        const dim3 grid(static_cast<unsigned>(p.n_tiles < static_cast<size_t>(kNumCU) ? p.n_tiles : kNumCU));
+        const dim3 grid(persistent_grid(p.n_tiles));
         if (p.apply_tw && p.out_c_fast)
-            return inverse ? launch_kernel<fft1024x16_kernel<1, 16, true>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2)
-                           : launch_kernel<fft1024x16_kernel<-1, 16, true>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2);
-        return inverse ? launch_kernel<fft1024x16_kernel<1, 16>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2)
-                       : launch_kernel<fft1024x16_kernel<-1, 16>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2);
+            return with_dir(inverse, [&](auto dir) {
+                return launch_kernel<fft1024x16_kernel<dir(), 16, true>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2);
+            });
+        return with_dir(inverse, [&](auto dir) {
+            return launch_kernel<fft1024x16_kernel<dir(), 16>>("fft1024x16_kernel", grid, dim3(1024), lds, s, {}, a, d, p, t1, t2);
+        });
     }
     // two 8-wave workgroups per CU: one loads/stores while the other computes
     const size_t lds = (1024 + 64 + 8 * FW_BUF + 256) * sizeof(float2);
-    const size_t slots = 2 * static_cast<size_t>(kNumCU);
-    const dim3 grid(static_cast<unsigned>(p.n_tiles < slots ? p.n_tiles : slots));
-    return inverse ? launch_kernel<fft1024x16_kernel<1, 8>>("fft1024x16_kernel", grid, dim3(512), lds, s, {}, a, d, p, t1, t2)
-                   : launch_kernel<fft1024x16_kernel<-1, 8>>("fft1024x16_kernel", grid, dim3(512), lds, s, {}, a, d, p, t1, t2);
+    const dim3 grid(persistent_grid(p.n_tiles, 2 * static_cast<size_t>(kNumCU)));
+    return with_dir(inverse, [&](auto dir) {
+        return launch_kernel<fft1024x16_kernel<dir(), 8>>("fft1024x16_kernel", grid, dim3(512), lds, s, {}, a, d, p, t1, t2);
+    });
 }
 
 template <int RAD>
-static comms_status_t launch_rx(Pow2Plan& pl, const float2* src, float2* dst, size_t n_points, bool inverse,
-                                hipStream_t s, const BluArgs& blu = BluArgs{0, 0, 0, nullptr, nullptr}) {
-    const size_t n_full = n_points / 16384, rem = n_points % 16384;
-    const cf* a = reinterpret_cast<const cf*>(src);
-    cf* d = reinterpret_cast<cf*>(dst);
-    const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1.get());
-    const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
-    const cf* ta = reinterpret_cast<const cf*>(pl.d_rxa.get());
-    const cf* tb = reinterpret_cast<const cf*>(pl.d_rxb.get());
+static comms_status_t launch_rx(const Pow2Plan& pl, const cf* a, cf* d, size_t n_points, bool inverse, hipStream_t s, const BluArgs& blu) {
+    const size_t n_full = n_points / kRxTilePoints, rem = n_points % kRxTilePoints;
+    const cf* t1 = dev(RxGeom<RAD>::C256 ? pl.d_w256 : pl.d_fw1);
+    const cf* t2 = dev(pl.d_fw2);
+    const cf* ta = dev(pl.d_rxa);
+    const cf* tb = dev(RxGeom<RAD>::PRE2 ? pl.d_front : pl.d_rxb);
     constexpr size_t lds = RxGeom<RAD>::LDS;
     // full tiles on the persistent grid; a partly filled last tile as one more workgroup.  In the
     // Bluestein modes the two launches address in / out by the global element index, so the second
     // one simply starts at tile n_full.
     auto go = [&](auto dir, auto mode) -> comms_status_t {
         constexpr int DIR = decltype(dir)::value, MODE = decltype(mode)::value;
-        if (n_full) {
-            const unsigned blocks = static_cast<unsigned>(n_full < static_cast<size_t>(kNumCU) ? n_full : kNumCU);
-            COMMS_TRY((launch_kernel<fft_rx1024_kernel<DIR, RAD, MODE>>("fft_rx1024_kernel", dim3(blocks), dim3(1024), lds, s, {}, a, d, n_full, 0,
-                                                                        n_full * 16384, t1, t2, ta, tb, blu)));
-        }
+        if (n_full)
+            COMMS_TRY((launch_kernel<fft_rx1024_kernel<DIR, RAD, MODE>>("fft_rx1024_kernel", dim3(persistent_grid(n_full)), dim3(1024), lds, s, {}, a, d,
+                                                                        n_full, 0, n_full * kRxTilePoints, t1, t2, ta, tb, blu)));
         if (rem)
             COMMS_TRY((launch_kernel<fft_rx1024_kernel<DIR, RAD, MODE, true>>("fft_rx1024_kernel", dim3(1), dim3(1024), lds, s, {}, a, d, n_full + 1,
                                                                               n_full, n_points, t1, t2, ta, tb, blu)));
@@ -1495,177 +1432,164 @@ static comms_status_t launch_rx(Pow2Plan& pl, const float2* src, float2* dst, si
     return go(integral_constant<int, -1>{}, integral_constant<int, 0>{});
 }
 
-// Column pass of N = 2^21 ... 2^24 (BluArgs mode 3) on the row plan's tables: `rows` is the plan of the N / 1024-point transforms.
+// Column pass of Gather (BluArgs mode 3) on the row plan's tables: `rows` is the plan of the N / 1024-point transforms.
 template <int RAD>
-static comms_status_t launch_rx_cols(Pow2Plan& rows, const float2* src, float2* dst, size_t n_points, bool inverse, hipStream_t s,
+static comms_status_t launch_rx_cols(const Pow2Plan& rows, const cf* a, cf* d, size_t n_points, bool inverse, hipStream_t s,
                                      const cf* tw_lo, const cf* tw_hi) {
     constexpr size_t lds = rx_cols_lds(RAD);
-    BluArgs blu{3, 0, 0, nullptr, nullptr, tw_lo, tw_hi};
-    const size_t n_tiles = n_points / 16384;  // whole transforms of at least 2^21 points: no partial tile
-    const dim3 grid(static_cast<unsigned>(n_tiles < static_cast<size_t>(kNumCU) ? n_tiles : kNumCU));
-    const cf* a = reinterpret_cast<const cf*>(src);
-    cf* d = reinterpret_cast<cf*>(dst);
-    const cf* t1 = reinterpret_cast<const cf*>(rows.d_fw1.get());
-    const cf* t2 = reinterpret_cast<const cf*>(rows.d_fw2.get());
-    const cf* ta = reinterpret_cast<const cf*>(rows.d_rxa.get());
-    const cf* tb = reinterpret_cast<const cf*>(rows.d_rxb.get());
-    const char* name = "fft_rx1024_kernel (columns)";
-    return inverse ? launch_kernel<fft_rx1024_kernel<1, RAD, 3>>(name, grid, dim3(1024), lds, s, {}, a, d, n_tiles, 0, n_points, t1, t2, ta, tb, blu)
-                   : launch_kernel<fft_rx1024_kernel<-1, RAD, 3>>(name, grid, dim3(1024), lds, s, {}, a, d, n_tiles, 0, n_points, t1, t2, ta, tb, blu);
+    const BluArgs blu{3, 0, 0, nullptr, nullptr, tw_lo, tw_hi};
+    const size_t n_tiles = n_points / kRxTilePoints;  // whole transforms of at least 2^21 points: no partial tile
+    const dim3 grid(persistent_grid(n_tiles));
+    const cf* t1 = dev(rows.d_fw1);
+    const cf* t2 = dev(rows.d_fw2);
+    const cf* ta = dev(rows.d_rxa);
+    const cf* tb = dev(rows.d_rxb);
+    return with_dir(inverse, [&](auto dir) {
+        return launch_kernel<fft_rx1024_kernel<dir(), RAD, 3>>("fft_rx1024_kernel (columns)", grid, dim3(1024), lds, s, {}, a, d, n_tiles, 0, n_points,
+                                                               t1, t2, ta, tb, blu);
+    });
 }
 
 template <int KIND>
-static comms_status_t launch_cols(Pow2Plan& pl, const float2* src, float2* dst, size_t batch, bool inverse,
-                                  hipStream_t s) {
+static comms_status_t launch_cols(const Pow2Plan& pl, const cf* a, cf* d, size_t batch, bool inverse, hipStream_t s, KStamp ks) {
     constexpr size_t lds = ColGeom<KIND>::LDS;
     const size_t n_tiles = batch * (1024 / ColGeom<KIND>::C);
-    const dim3 grid(static_cast<unsigned>(n_tiles < static_cast<size_t>(kNumCU) ? n_tiles : kNumCU));
-    const cf* a = reinterpret_cast<const cf*>(src);
-    cf* d = reinterpret_cast<cf*>(dst);
-    const cf* t1 = reinterpret_cast<const cf*>(pl.d_colw1.get());
-    const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
-    const cf* tr = reinterpret_cast<const cf*>(pl.d_colr.get());
+    const dim3 grid(persistent_grid(n_tiles));
+    const cf* t1 = dev(pl.d_w256);
+    const cf* t2 = dev(pl.d_fw2);
+    const cf* tr = dev(pl.d_front);
     const FftTileParams& p = pl.pass[0];
     const unsigned N = static_cast<unsigned>(pl.N);
-    return inverse ? launch_kernel<fft_cols_kernel<1, KIND>>("fft_cols_kernel", grid, dim3(1024), lds, s, {}, a, d, n_tiles, N, t1, t2, tr, p.tw_lo, p.tw_hi, p.ks)
-                   : launch_kernel<fft_cols_kernel<-1, KIND>>("fft_cols_kernel", grid, dim3(1024), lds, s, {}, a, d, n_tiles, N, t1, t2, tr, p.tw_lo, p.tw_hi, p.ks);
+    return with_dir(inverse, [&](auto dir) {
+        return launch_kernel<fft_cols_kernel<dir(), KIND>>("fft_cols_kernel", grid, dim3(1024), lds, s, {}, a, d, n_tiles, N, t1, t2, tr, p.tw_lo, p.tw_hi, ks);
+    });
 }
 
-// The generic tile kernel (tiles above 64 KiB need the dynamic-LDS limit raised: 160 KiB per CU on gfx950)
-static comms_status_t launch_tile(bool inverse, unsigned blocks, int threads, size_t lds, hipStream_t s, const float2* src, float2* dst,
-                                  const FftTileParams& p) {
-    const cf* a = reinterpret_cast<const cf*>(src);
-    cf* d = reinterpret_cast<cf*>(dst);
-    return inverse ? launch_kernel<fft_tile_kernel<1>>("fft_tile_kernel", dim3(blocks), dim3(threads), lds, s, {}, a, d, p)
-                   : launch_kernel<fft_tile_kernel<-1>>("fft_tile_kernel", dim3(blocks), dim3(threads), lds, s, {}, a, d, p);
+// The generic tile kernel, a lane per FT_PTS points of the tile (tiles above 64 KiB need the dynamic-LDS limit raised:
+// 160 KiB per CU on gfx950)
+static comms_status_t launch_tile(bool inverse, unsigned blocks, hipStream_t s, const cf* a, cf* d, const FftTileParams& p) {
+    const int npts = p.L * p.C;
+    const int threads = npts / FT_PTS < 64 ? 64 : npts / FT_PTS > 1024 ? 1024 : npts / FT_PTS;
+    const size_t lds = static_cast<size_t>(npts) * sizeof(float2);
+    return with_dir(inverse, [&](auto dir) {
+        return launch_kernel<fft_tile_kernel<dir()>>("fft_tile_kernel", dim3(blocks), dim3(threads), lds, s, {}, a, d, p);
+    });
 }
 
-// All of a batch on the single-pass kernel (plain, or as one half of a Bluestein pair).
-static comms_status_t run_rx(Pow2Plan& pl, const float2* in, float2* out, size_t n_points, bool inverse, hipStream_t s,
+// All of a batch on the single-pass kernel (plain, or as one half of a Bluestein pair): the plan's RAD to its instantiation
+static comms_status_t run_rx(const Pow2Plan& pl, const cf* in, cf* out, size_t n_points, bool inverse, hipStream_t s,
                              const BluArgs& blu = BluArgs{0, 0, 0, nullptr, nullptr}) {
-    switch (pl.rx_rad) {
-            case -1: COMMS_TRY(launch_rx<0>(pl, in, out, n_points, inverse, s, blu)); break;
-            case -2: COMMS_TRY(launch_rx<256>(pl, in, out, n_points, inverse, s, blu)); break;
-            case -3: COMMS_TRY(launch_rx<128>(pl, in, out, n_points, inverse, s, blu)); break;
-            case -4: COMMS_TRY(launch_rx<512>(pl, in, out, n_points, inverse, s, blu)); break;
-            case -102: COMMS_TRY(launch_rx<-2>(pl, in, out, n_points, inverse, s, blu)); break;
-            case -104: COMMS_TRY(launch_rx<-4>(pl, in, out, n_points, inverse, s, blu)); break;
-            case -108: COMMS_TRY(launch_rx<-8>(pl, in, out, n_points, inverse, s, blu)); break;
-            case -116: COMMS_TRY(launch_rx<-16>(pl, in, out, n_points, inverse, s, blu)); break;
-            case -132: COMMS_TRY(launch_rx<-32>(pl, in, out, n_points, inverse, s, blu)); break;
-            case 1: COMMS_TRY(launch_rx<1>(pl, in, out, n_points, inverse, s, blu)); break;
-            case 2: COMMS_TRY(launch_rx<2>(pl, in, out, n_points, inverse, s, blu)); break;
-            case 4: COMMS_TRY(launch_rx<4>(pl, in, out, n_points, inverse, s, blu)); break;
-            case 8: COMMS_TRY(launch_rx<8>(pl, in, out, n_points, inverse, s, blu)); break;
-            default: COMMS_TRY(launch_rx<16>(pl, in, out, n_points, inverse, s, blu)); break;
+    switch (pl.choice.rad) {
+        case 0: return launch_rx<0>(pl, in, out, n_points, inverse, s, blu);
+        case 256: return launch_rx<256>(pl, in, out, n_points, inverse, s, blu);
+        case 128: return launch_rx<128>(pl, in, out, n_points, inverse, s, blu);
+        case 512: return launch_rx<512>(pl, in, out, n_points, inverse, s, blu);
+        case -2: return launch_rx<-2>(pl, in, out, n_points, inverse, s, blu);
+        case -4: return launch_rx<-4>(pl, in, out, n_points, inverse, s, blu);
+        case -8: return launch_rx<-8>(pl, in, out, n_points, inverse, s, blu);
+        case -16: return launch_rx<-16>(pl, in, out, n_points, inverse, s, blu);
+        case -32: return launch_rx<-32>(pl, in, out, n_points, inverse, s, blu);
+        case 1: return launch_rx<1>(pl, in, out, n_points, inverse, s, blu);
+        case 2: return launch_rx<2>(pl, in, out, n_points, inverse, s, blu);
+        case 4: return launch_rx<4>(pl, in, out, n_points, inverse, s, blu);
+        case 8: return launch_rx<8>(pl, in, out, n_points, inverse, s, blu);
+        default: return launch_rx<16>(pl, in, out, n_points, inverse, s, blu);
     }
-    return COMMS_OK;
 }
 
-static comms_status_t pow2_run(Pow2Plan& pl, const float2* in, float2* out, size_t batch,
-                               bool inverse, hipStream_t s, float2* scratch, KStamp ks = KStamp{nullptr, nullptr}) {
-    // only the four-step passes of N = 2^15 ... 2^20 stamp (both of them: the call from its first workgroup in to its last
-    // wave out); the column pass of the larger lengths does not, so those stay unstamped altogether
-    pl.pass[0].ks = pl.pass[1].ks = pl.rows ? KStamp{nullptr, nullptr} : ks;
-    static const bool no_rx = diag_knob("COMMS_FFT_NO_RX", 0) != 0;
-    if (pl.rx_rad && !no_rx) return run_rx(pl, in, out, batch * pl.N, inverse, s);
-    static const bool no_rx32k = diag_knob("COMMS_FFT_NO_RX32K", 0) != 0;
-    if (pl.d_rx32 && !no_rx32k) {  // N = 32768: one pass, a transform per workgroup and step
-        const dim3 grid(static_cast<unsigned>(batch < static_cast<size_t>(kNumCU) ? batch : kNumCU));
-        const cf* a = reinterpret_cast<const cf*>(in);
-        cf* d = reinterpret_cast<cf*>(out);
-        const cf* t1 = reinterpret_cast<const cf*>(pl.d_fw1.get());
-        const cf* t2 = reinterpret_cast<const cf*>(pl.d_fw2.get());
-        const cf* tt = reinterpret_cast<const cf*>(pl.d_rx32.get());
-        return inverse ? launch_kernel<fft_rx32k_kernel<1>>("fft_rx32k_kernel", grid, dim3(1024), R32_LDS, s, {}, a, d, batch, t1, t2, tt, ks)
-                       : launch_kernel<fft_rx32k_kernel<-1>>("fft_rx32k_kernel", grid, dim3(1024), R32_LDS, s, {}, a, d, batch, t1, t2, tt, ks);
-    }
-    if (pl.rows) {
-        // N = 2^21 ... 2^24 in two passes: N / 1024-point columns gathered in pieces of 64 ... 8 B (small pieces cost far less
-        // on the read side than on the write side: scripts/probes/strided_tiles.hip), spectra out in runs of 1 KiB ... 128 B;
-        // then 1024-point rows, sixteen adjacent ones per tile, stored transposed in 128-byte pieces.
-        static const int gather_max = diag_knob("COMMS_FFT_LARGE_GATHER", 23);
-        if (ilog2(pl.N) <= gather_max && pl.rows->rx_rad >= 2) {
+// Runs `batch` transforms of length pl.N.  In-place (in == out) is fine: every tile is fully read before it is written
+// and tiles do not overlap; a second pass reads what the first wrote to `scratch`.
+static comms_status_t pow2_run(const Pow2Plan& pl, const cf* in, cf* out, size_t batch, bool inverse, hipStream_t s, cf* scratch,
+                               KStamp ks = KStamp{nullptr, nullptr}) {
+    // pass i of this call.  Only the passes of Cols, Fast20 and Tile stamp (both of them: the call from its first workgroup
+    // in to its last wave out), and Rx32k; the larger lengths stay unstamped altogether.
+    auto pass = [&](int i) {
+        FftTileParams p = pl.pass[i];
+        p.n_tiles = batch * p.tiles_per_xform;
+        return p;
+    };
+    auto stamped = [&](FftTileParams p) {
+        p.ks = ks;
+        return p;
+    };
+    switch (pl.choice.form) {
+        case Pow2Form::Tiny:
+        case Pow2Form::Rx: return run_rx(pl, in, out, batch * pl.N, inverse, s);
+        case Pow2Form::Rx32k: {  // one pass, a transform per workgroup and step
+            const dim3 grid(persistent_grid(batch));
+            const cf* t1 = dev(pl.d_fw1);
+            const cf* t2 = dev(pl.d_fw2);
+            const cf* tt = dev(pl.d_w32k);
+            return with_dir(inverse, [&](auto dir) {
+                return launch_kernel<fft_rx32k_kernel<dir()>>("fft_rx32k_kernel", grid, dim3(1024), R32_LDS, s, {}, in, out, batch, t1, t2, tt, ks);
+            });
+        }
+        case Pow2Form::Gather: {
+            // N / 1024-point columns gathered in pieces of 64 ... 8 B (small pieces cost far less on the read side than on
+            // the write side: scripts/probes/strided_tiles.hip), spectra out in runs of 1 KiB ... 128 B; then 1024-point rows,
+            // sixteen adjacent ones per tile, stored transposed in 128-byte pieces.
             const cf* lo = pl.pass[0].tw_lo;
             const cf* hi = pl.pass[0].tw_hi;
-            switch (pl.rows->rx_rad) {
+            switch (pl.choice.rad) {
                 case 2: COMMS_TRY(launch_rx_cols<2>(*pl.rows, in, scratch, batch * pl.N, inverse, s, lo, hi)); break;
                 case 4: COMMS_TRY(launch_rx_cols<4>(*pl.rows, in, scratch, batch * pl.N, inverse, s, lo, hi)); break;
                 case 8: COMMS_TRY(launch_rx_cols<8>(*pl.rows, in, scratch, batch * pl.N, inverse, s, lo, hi)); break;
                 default: COMMS_TRY(launch_rx_cols<16>(*pl.rows, in, scratch, batch * pl.N, inverse, s, lo, hi)); break;
             }
-            FftTileParams q = pl.pass[1];
-            q.n_tiles = batch * q.tiles_per_xform;
-            return launch_fast(pl, scratch, out, q, inverse, s);
+            return launch_fast(pl, scratch, out, pass(1), inverse, s);
         }
-        // N = 2^24 (8-byte pieces): three launches on 128-byte pieces throughout -- 1024-point columns (in -> scratch), rows (in
-        // place), transpose (scratch -> out) -- are faster (0.78 against 0.82 ms per 2^26 points)
-        FftTileParams p = pl.pass[0];
-        p.n_tiles = batch * p.tiles_per_xform;
-        COMMS_TRY(launch_fast(pl, in, scratch, p, inverse, s));
-        COMMS_TRY(run_rx(*pl.rows, scratch, scratch, batch * pl.N, inverse, s));
-        const unsigned cols = static_cast<unsigned>(pl.N >> 10);
-        const size_t n_tiles = batch * (1024 / TR_T) * (cols / TR_T);
-        const size_t slots = static_cast<size_t>(16) * kNumCU;
-        const unsigned blocks = static_cast<unsigned>(n_tiles < slots ? n_tiles : slots);
-        fft_transpose_kernel<<<dim3(blocks), dim3(256), 0, s>>>(reinterpret_cast<const cf*>(scratch), reinterpret_cast<cf*>(out), 1024u,
-                                                               cols, n_tiles);
-        return launch_ok("fft_transpose_kernel");
-    }
-    for (int i = 0; i < pl.n_pass; ++i) {
-        FftTileParams p = pl.pass[i];
-        const float2* src = in;
-        float2* dst = out;
-        if (pl.n_pass == 1) {
-            // group C transforms per tile; a ragged tail runs with C = 1 tiles
-            const size_t full = batch / p.C;
-            p.n_tiles = full;
-            if (full && pl.fast(i)) {
-                COMMS_TRY(launch_fast(pl, src, dst, p, inverse, s));
-            } else if (full) {
-                static const unsigned wgs = static_cast<unsigned>(diag_knob("COMMS_FFT_TILE_WGS", 4));
-                unsigned blocks = static_cast<unsigned>(full < wgs * kNumCU ? full : wgs * kNumCU);
-                COMMS_TRY(launch_tile(inverse, blocks, pl.threads[i], pl.lds[i], s, src, dst, p));
-            }
-            const size_t rem = batch - full * p.C;
-            if (rem) {
-                FftTileParams q = p;
-                q.C = 1;
-                q.logC = 0;
-                q.N = pl.N;
-                q.n_tiles = rem;
-                const size_t off = full * p.C * pl.N;
-                int T = static_cast<int>(pl.N) / FT_PTS;
-                if (T < 64) T = 64;
-                unsigned blocks = static_cast<unsigned>(rem < 4u * kNumCU ? rem : 4u * kNumCU);
-                COMMS_TRY(launch_tile(inverse, blocks, T, pl.N * sizeof(float2), s, src + off, dst + off, q));
-            }
-        } else {
-            // pass 1: in -> scratch (same positions, twiddled); pass 2: scratch -> out
-            // (transposed).  in == out is therefore fine.
-            if (i == 0) {
-                dst = scratch;
-            } else {
-                src = scratch;
-            }
-            p.n_tiles = batch * p.tiles_per_xform;
-            static const bool no_cols = diag_knob("COMMS_FFT_NO_COLS", 0) != 0;
-            if (i == 0 && pl.col_kind >= 0 && !no_cols) {
-                switch (pl.col_kind) {
-                    case 0: COMMS_TRY(launch_cols<0>(pl, src, dst, batch, inverse, s)); break;
-                    case 128: COMMS_TRY(launch_cols<128>(pl, src, dst, batch, inverse, s)); break;
-                    case 256: COMMS_TRY(launch_cols<256>(pl, src, dst, batch, inverse, s)); break;
-                    default: COMMS_TRY(launch_cols<512>(pl, src, dst, batch, inverse, s)); break;
+        case Pow2Form::Three: {
+            // N = 2^24 (8-byte pieces on the Gather form): three launches on 128-byte pieces throughout -- 1024-point columns
+            // (in -> scratch), rows (in place), transpose (scratch -> out) -- are faster (0.78 against 0.82 ms per 2^26 points)
+            COMMS_TRY(launch_fast(pl, in, scratch, pass(0), inverse, s));
+            COMMS_TRY(run_rx(*pl.rows, scratch, scratch, batch * pl.N, inverse, s));
+            const unsigned cols = static_cast<unsigned>(pl.N >> 10);
+            const size_t n_tiles = batch * (1024 / TR_T) * (cols / TR_T);
+            const unsigned blocks = persistent_grid(n_tiles, static_cast<size_t>(16) * kNumCU);
+            fft_transpose_kernel<<<dim3(blocks), dim3(256), 0, s>>>(scratch, out, 1024u, cols, n_tiles);
+            return launch_ok("fft_transpose_kernel");
+        }
+        case Pow2Form::Tile: {
+            if (pl.N <= kTileOnePassMax) {
+                // group C transforms per tile; a ragged tail runs with C = 1 tiles
+                FftTileParams p = stamped(pl.pass[0]);
+                const size_t full = batch / p.C;
+                p.n_tiles = full;
+                if (full && pl.N == 1024) {
+                    COMMS_TRY(launch_fast(pl, in, out, p, inverse, s));
+                } else if (full) {
+                    static const unsigned wgs = static_cast<unsigned>(diag_knob("COMMS_FFT_TILE_WGS", 4));
+                    COMMS_TRY(launch_tile(inverse, persistent_grid(full, wgs * kNumCU), s, in, out, p));
                 }
-                continue;
+                const size_t rem = batch - full * p.C;
+                if (rem) {
+                    FftTileParams q = p;
+                    q.C = 1;
+                    q.logC = 0;
+                    q.N = pl.N;
+                    q.n_tiles = rem;
+                    const size_t off = full * p.C * pl.N;
+                    COMMS_TRY(launch_tile(inverse, persistent_grid(rem, 4u * kNumCU), s, in + off, out + off, q));
+                }
+                return COMMS_OK;
             }
-            if (pl.fast(i)) {
-                COMMS_TRY(launch_fast(pl, src, dst, p, inverse, s));
-                continue;
-            }
-            unsigned blocks = static_cast<unsigned>(p.n_tiles < 4u * kNumCU ? p.n_tiles : 4u * kNumCU);
-            COMMS_TRY(launch_tile(inverse, blocks, pl.threads[i], pl.lds[i], s, src, dst, p));
+            // pass 1: in -> scratch (same positions, twiddled); pass 2: scratch -> out (transposed)
+            const FftTileParams p = stamped(pass(0)), q = stamped(pass(1));
+            COMMS_TRY(launch_tile(inverse, persistent_grid(p.n_tiles, 4u * kNumCU), s, in, scratch, p));
+            if (pl.N >= 32768) return launch_fast(pl, scratch, out, q, inverse, s);  // 1024-point rows
+            return launch_tile(inverse, persistent_grid(q.n_tiles, 4u * kNumCU), s, scratch, out, q);
         }
+        case Pow2Form::Cols:
+            switch (pl.choice.kind) {
+                case 0: COMMS_TRY(launch_cols<0>(pl, in, scratch, batch, inverse, s, ks)); break;
+                case 128: COMMS_TRY(launch_cols<128>(pl, in, scratch, batch, inverse, s, ks)); break;
+                case 256: COMMS_TRY(launch_cols<256>(pl, in, scratch, batch, inverse, s, ks)); break;
+                default: COMMS_TRY(launch_cols<512>(pl, in, scratch, batch, inverse, s, ks)); break;
+            }
+            return launch_fast(pl, scratch, out, stamped(pass(1)), inverse, s);
+        case Pow2Form::Fast20:
+            COMMS_TRY(launch_fast(pl, in, scratch, stamped(pass(0)), inverse, s));
+            return launch_fast(pl, scratch, out, stamped(pass(1)), inverse, s);
     }
     return COMMS_OK;
 }
@@ -1673,10 +1597,9 @@ static comms_status_t pow2_run(Pow2Plan& pl, const float2* in, float2* out, size
 struct comms_fft : Handle {
     size_t N = 0;
     bool inverse = false;
-    int kind = 0;  // 0 pow2, 1 direct O(N^2), 2 Bluestein
-    Pow2Plan plan;           // pow2: length N;  Bluestein: length M
+    FftChoice choice{FftKind::Refused, 0, {0}};  // what runs (fft_plan.hpp), and Bluestein's padded length M
+    Pow2Plan plan;           // Pow2: length N;  Bluestein: length M
     DevBuf<float2> d_twN;     // direct: W_N^m
-    size_t M = 0;                // Bluestein padded length
     DevBuf<float2> d_chirp;   // exp(-/+ i pi n^2 / N)
     DevBuf<float2> d_bspec;   // FFT_M(conj chirp, wrapped) / M
     Scratch work;                // four-step transpose buffer / Bluestein work
@@ -1687,33 +1610,27 @@ static_assert(!std::is_copy_constructible_v<comms_fft>, "a handle is never copie
 
 static comms_status_t fft_setup(comms_fft* h) {
     const size_t N = h->N;
-    if ((N & (N - 1)) == 0) {
-        h->kind = 0;
-        if (N >= 2) COMMS_TRY(pow2_plan_build(h->plan, N));
-        return COMMS_OK;
-    }
-    // short odd lengths: the exact-index O(N^2) DFT (f64 accumulation); above that Bluestein on the
-    // power-of-two kernels is faster by far (N = 1000: 2.3 -> 20 Gpoints/s) -- measured crossover ~64
-    static const size_t direct_max = static_cast<size_t>(diag_knob("COMMS_FFT_DIRECT_MAX", 64));
-    if (N <= direct_max && N <= 4096) {
-        h->kind = 1;
-        return upload_tw(N, N, 1, h->d_twN);
+    h->choice = fft_form(N, fft_knobs());
+    switch (h->choice.kind) {
+        case FftKind::Refused: return fail(COMMS_ERR_ARG, "%s", h->choice.why);
+        case FftKind::Copy: return COMMS_OK;
+        case FftKind::Pow2: return pow2_plan_build(h->plan, N, pow2_form(N, fft_knobs()));
+        case FftKind::DirectSmall:
+        case FftKind::Direct: return upload(h->d_twN, roots<float2>(N, N));
+        case FftKind::BluFused:
+        case FftKind::BluUnfused: break;
     }
     // Bluestein: with chirp[n] = W^{n^2/2} (W = e^{-/+ 2 pi i/N} by direction),
     //   X[k] = chirp[k] * sum_n (x[n] chirp[n]) * conj(chirp)[k-n]
     // i.e. one circular convolution of length M >= 2N-1 on the power-of-two path.
-    h->kind = 2;
-    COMMS_ARG(N <= (static_cast<size_t>(1) << 23), "FFT length %zu too large", N);
-    size_t M = 1;
-    while (M < 2 * N - 1) M <<= 1;
-    h->M = M;
-    COMMS_TRY(pow2_plan_build(h->plan, M));
+    const size_t M = h->choice.M;
+    COMMS_TRY(pow2_plan_build(h->plan, M, pow2_form(M, fft_knobs())));
     const double sgn = h->inverse ? 1.0 : -1.0;
     std::vector<float2> chirp(N);
     std::vector<double> cr(N), ci(N);
     for (size_t n = 0; n < N; ++n) {
         const size_t e = (n * n) % (2 * N);  // n^2 mod 2N keeps the angle exact
-        const double a = sgn * kPiF * static_cast<double>(e) / static_cast<double>(N);
+        const double a = sgn * 3.14159265358979323846264338327950288 * static_cast<double>(e) / static_cast<double>(N);
         cr[n] = std::cos(a);
         ci[n] = std::sin(a);
         chirp[n] = make_float2(static_cast<float>(cr[n]), static_cast<float>(ci[n]));
@@ -1725,12 +1642,11 @@ static comms_status_t fft_setup(comms_fft* h) {
         bvec[n] = v;
         if (n) bvec[M - n] = v;
     }
-    COMMS_HIP_TRY(h->d_chirp.alloc(N));
-    COMMS_HIP_TRY(hipMemcpy(h->d_chirp.get(), chirp.data(), N * sizeof(float2), hipMemcpyHostToDevice));
-    COMMS_HIP_TRY(h->d_bspec.alloc(M));
-    COMMS_HIP_TRY(hipMemcpy(h->d_bspec.get(), bvec.data(), M * sizeof(float2), hipMemcpyHostToDevice));
+    COMMS_TRY(upload(h->d_chirp, chirp));
+    COMMS_TRY(upload(h->d_bspec, bvec));
     COMMS_TRY(h->work.reserve(M * sizeof(float2)));
-    COMMS_TRY(pow2_run(h->plan, h->d_bspec.get(), h->d_bspec.get(), 1, false, h->stream, static_cast<float2*>(h->work.p)));
+    cf* bspec = reinterpret_cast<cf*>(h->d_bspec.get());
+    COMMS_TRY(pow2_run(h->plan, bspec, bspec, 1, false, h->stream, static_cast<cf*>(h->work.p)));
     COMMS_HIP_TRY(hipStreamSynchronize(h->stream));
     // fold the 1/M of the inverse transform into the spectrum
     std::vector<float2> spec(M);
@@ -1770,97 +1686,98 @@ comms_status_t comms_fft_run_dev(comms_fft_t* h, const comms_c32* d_in, size_t n
     COMMS_TRY(use_device(h->device));
     hipStream_t s = nullptr;
     COMMS_TRY(h->enter(stream, &s));
-    const float2* in = reinterpret_cast<const float2*>(d_in);
-    float2* o = reinterpret_cast<float2*>(d_out);
-    const size_t batch = n / h->N;
-    if (h->N == 1) {
-        if (d_in != d_out) COMMS_HIP_TRY(hipMemcpyAsync(o, in, n * sizeof(float2), hipMemcpyDefault, s));
-        return COMMS_OK;
-    }
-    if (h->kind == 0) {
-        if (h->plan.n_pass == 1) {
-            h->tic(s);
-            comms_status_t st = pow2_run(h->plan, in, o, batch, h->inverse, s, nullptr);
-            h->toc(s);
-            return st;
-        }
-        // four-step: pass 1 -> scratch -> pass 2, in groups that bound the scratch buffer.
-        // (Small groups, sized so the intermediate stays in the 256 MiB Infinity Cache, were
-        // measured and lose: 2^20 x 64 runs 0.56 ms ungrouped, 0.66 ms at 64 MiB, 2.3 ms at 8 MiB.)
-        static const size_t group_bytes = static_cast<size_t>(diag_knob("COMMS_FFT_GROUP_MB", 2048)) << 20;
-        size_t group = group_bytes / (h->N * sizeof(float2));
-        if (group < 1) group = 1;
-        if (group > batch) group = batch;
-        COMMS_TRY(h->work.reserve(group * h->N * sizeof(float2)));
-        float2* scratch = static_cast<float2*>(h->work.p);
-        h->tic(s);
-        const KStamp ks = h->next_stamp();
-        for (size_t b0 = 0; b0 < batch; b0 += group) {
-            const size_t nb = batch - b0 < group ? batch - b0 : group;
-            COMMS_TRY(pow2_run(h->plan, in + b0 * h->N, o + b0 * h->N, nb, h->inverse, s, scratch, ks));
-        }
-        h->toc(s);
-        return COMMS_OK;
-    }
-    if (h->kind == 1) {
-        COMMS_ARG(!ranges_overlap(d_in, n * 8, d_out, n * 8) , "this fft_size cannot run in place");
-        if (h->N <= 128) {
-            const size_t groups = (batch + 256 / h->N - 1) / (256 / h->N);
-            const unsigned gb = static_cast<unsigned>(groups < 8u * kNumCU ? groups : 8u * kNumCU);
-            h->tic(s);
-            dft_small_kernel<<<dim3(gb), dim3(256), 0, s>>>(reinterpret_cast<const cf*>(in), reinterpret_cast<cf*>(o),
-                                                            static_cast<int>(h->N), batch,
-                                                            reinterpret_cast<const cf*>(h->d_twN.get()), h->inverse ? 1 : 0);
-            h->toc(s);
-            return launch_ok("dft_small_kernel");
-        }
-        unsigned blocks = static_cast<unsigned>(batch < 4u * kNumCU ? batch : 4u * kNumCU);
-        h->tic(s);
-        dft_direct_kernel<<<dim3(blocks), dim3(256), 2 * h->N * sizeof(float2), s>>>(
-            reinterpret_cast<const cf*>(in), reinterpret_cast<cf*>(o), static_cast<int>(h->N), batch,
-            reinterpret_cast<const cf*>(h->d_twN.get()), h->inverse ? 1 : 0);
-        h->toc(s);
-        return launch_ok("dft_direct_kernel");
-    }
-    // Bluestein, in chunks that bound the work buffer
-    const size_t M = h->M;
-    size_t chunk = (static_cast<size_t>(1) << 24) / M;
-    if (chunk < 1) chunk = 1;
-    if (chunk > batch) chunk = batch;
-    COMMS_TRY(h->work.reserve(chunk * M * sizeof(float2)));
-    if (h->plan.n_pass == 2) COMMS_TRY(h->work2.reserve(chunk * M * sizeof(float2)));
-    float2* a = static_cast<float2*>(h->work.p);
-    float2* sc = static_cast<float2*>(h->work2.p);
-    static const bool no_fuse = diag_knob("COMMS_FFT_BLU_UNFUSED", 0) != 0;
-    const bool fuse = h->plan.rx_rad != 0 && !no_fuse;  // padded length on the single-pass kernel (M <= 16384)
-    unsigned logM = 0;
-    while ((static_cast<size_t>(1) << logM) < M) ++logM;
-    // (a timer brackets all the launches of the call, as on the power-of-two paths; the pair is closed on every exit)
+    const cf* in = reinterpret_cast<const cf*>(d_in);
+    cf* o = reinterpret_cast<cf*>(d_out);
+    const cf* twN = dev(h->d_twN);
+    const cf* chirp = dev(h->d_chirp);
+    const cf* bspec = dev(h->d_bspec);
+    const size_t N = h->N, M = h->choice.M, batch = n / N;
+    // (a timer brackets all the launches of the call; the pair is closed on every exit)
     struct Bracket {
         comms_fft* h;
         hipStream_t s;
         Bracket(comms_fft* hh, hipStream_t ss) : h(hh), s(ss) { h->tic(s); }
         ~Bracket() { h->toc(s); }
-    } bracket(h, s);
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-        if (fuse) {
-            // two launches: [x * chirp, pad, forward, * bspec] -> work;  [inverse, * chirp, first N] -> out
-            const cf* chirp = reinterpret_cast<const cf*>(h->d_chirp.get());
-            COMMS_TRY(run_rx(h->plan, in + b0 * h->N, a, nb * M, false, s,
-                             BluArgs{1, static_cast<unsigned>(h->N), logM, chirp, reinterpret_cast<const cf*>(h->d_bspec.get())}));
-            COMMS_TRY(run_rx(h->plan, a, o + b0 * h->N, nb * M, true, s,
-                             BluArgs{2, static_cast<unsigned>(h->N), logM, chirp, nullptr}));
-            continue;
+    };
+    // Bluestein runs in chunks that bound the work buffers (work2: the scratch of a two-pass plan)
+    size_t chunk = 0;
+    if (h->choice.kind == FftKind::BluFused || h->choice.kind == FftKind::BluUnfused) {
+        chunk = kBluChunkPoints / M;
+        if (chunk < 1) chunk = 1;
+        if (chunk > batch) chunk = batch;
+        COMMS_TRY(h->work.reserve(chunk * M * sizeof(float2)));
+        if (h->plan.choice.scratch) COMMS_TRY(h->work2.reserve(chunk * M * sizeof(float2)));
+    }
+    cf* a = static_cast<cf*>(h->work.p);
+    cf* sc = static_cast<cf*>(h->work2.p);
+    switch (h->choice.kind) {
+        case FftKind::Refused: break;  // (comms_fft_create has refused it)
+        case FftKind::Copy:
+            if (d_in != d_out) COMMS_HIP_TRY(hipMemcpyAsync(o, in, n * sizeof(float2), hipMemcpyDefault, s));
+            return COMMS_OK;
+        case FftKind::Pow2: {
+            if (N <= kTileOnePassMax) {
+                Bracket bracket(h, s);
+                return pow2_run(h->plan, in, o, batch, h->inverse, s, nullptr);
+            }
+            // longer transforms in groups that bound the scratch buffer of the two-pass forms: pass 1 -> scratch -> pass 2.
+            // (Small groups, sized so the intermediate stays in the 256 MiB Infinity Cache, were
+            // measured and lose: 2^20 x 64 runs 0.56 ms ungrouped, 0.66 ms at 64 MiB, 2.3 ms at 8 MiB.)
+            static const size_t group_bytes = static_cast<size_t>(diag_knob("COMMS_FFT_GROUP_MB", 2048)) << 20;
+            size_t group = group_bytes / (N * sizeof(float2));
+            if (group < 1) group = 1;
+            if (group > batch) group = batch;
+            if (h->plan.choice.scratch) COMMS_TRY(h->work.reserve(group * N * sizeof(float2)));
+            cf* scratch = static_cast<cf*>(h->work.p);
+            Bracket bracket(h, s);
+            const KStamp ks = h->next_stamp();
+            for (size_t b0 = 0; b0 < batch; b0 += group) {
+                const size_t nb = batch - b0 < group ? batch - b0 : group;
+                COMMS_TRY(pow2_run(h->plan, in + b0 * N, o + b0 * N, nb, h->inverse, s, scratch, ks));
+            }
+            return COMMS_OK;
         }
-        blu_pre_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(reinterpret_cast<const cf*>(in + b0 * h->N), reinterpret_cast<const cf*>(h->d_chirp.get()), reinterpret_cast<cf*>(a), h->N, M, nb);
-        COMMS_TRY(launch_ok("blu_pre_kernel"));
-        COMMS_TRY(pow2_run(h->plan, a, a, nb, false, s, sc));
-        blu_mul_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(reinterpret_cast<cf*>(a), reinterpret_cast<const cf*>(h->d_bspec.get()), M, nb);
-        COMMS_TRY(launch_ok("blu_mul_kernel"));
-        COMMS_TRY(pow2_run(h->plan, a, a, nb, true, s, sc));
-        blu_post_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(reinterpret_cast<const cf*>(a), reinterpret_cast<const cf*>(h->d_chirp.get()), reinterpret_cast<cf*>(o + b0 * h->N), h->N, M, nb);
-        COMMS_TRY(launch_ok("blu_post_kernel"));
+        case FftKind::DirectSmall: {
+            COMMS_ARG(d_in != d_out, "this fft_size cannot run in place");
+            const size_t per_wg = kSmallDftLanes / N, groups = (batch + per_wg - 1) / per_wg;
+            Bracket bracket(h, s);
+            dft_small_kernel<<<dim3(persistent_grid(groups, small_dft_grid_cap(kNumCU))), dim3(256), 0, s>>>(in, o, static_cast<int>(N), batch, twN,
+                                                                                                          h->inverse ? 1 : 0);
+            return launch_ok("dft_small_kernel");
+        }
+        case FftKind::Direct: {
+            COMMS_ARG(d_in != d_out, "this fft_size cannot run in place");
+            Bracket bracket(h, s);
+            dft_direct_kernel<<<dim3(persistent_grid(batch, 4u * kNumCU)), dim3(256), 2 * N * sizeof(float2), s>>>(in, o, static_cast<int>(N), batch, twN,
+                                                                                                                  h->inverse ? 1 : 0);
+            return launch_ok("dft_direct_kernel");
+        }
+        case FftKind::BluFused: {
+            // two launches: [x * chirp, pad, forward, * bspec] -> work;  [inverse, * chirp, first N] -> out
+            const unsigned logM = static_cast<unsigned>(ilog2(M));
+            Bracket bracket(h, s);
+            for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+                const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+                COMMS_TRY(run_rx(h->plan, in + b0 * N, a, nb * M, false, s, BluArgs{1, static_cast<unsigned>(N), logM, chirp, bspec}));
+                COMMS_TRY(run_rx(h->plan, a, o + b0 * N, nb * M, true, s, BluArgs{2, static_cast<unsigned>(N), logM, chirp, nullptr}));
+            }
+            return COMMS_OK;
+        }
+        case FftKind::BluUnfused: {
+            Bracket bracket(h, s);
+            for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+                const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+                blu_pre_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(in + b0 * N, chirp, a, N, M, nb);
+                COMMS_TRY(launch_ok("blu_pre_kernel"));
+                COMMS_TRY(pow2_run(h->plan, a, a, nb, false, s, sc));
+                blu_mul_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(a, bspec, M, nb);
+                COMMS_TRY(launch_ok("blu_mul_kernel"));
+                COMMS_TRY(pow2_run(h->plan, a, a, nb, true, s, sc));
+                blu_post_kernel<<<dim3(4 * kNumCU), dim3(256), 0, s>>>(a, chirp, o + b0 * N, N, M, nb);
+                COMMS_TRY(launch_ok("blu_post_kernel"));
+            }
+            return COMMS_OK;
+        }
     }
     return COMMS_OK;
 }
@@ -1882,3 +1799,4 @@ comms_status_t comms_fft_set_timer(comms_fft_t* h, comms_timer_t* t) { return se
 comms_status_t comms_fft_destroy(comms_fft_t* h) { return destroy_handle(h); }
 
 }  // extern "C"
+

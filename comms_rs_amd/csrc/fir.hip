@@ -33,6 +33,7 @@
 #include "common.hpp"
 #include "fft_radix.hpp"
 #include "fir_handle.hpp"
+#include "roots.hpp"
 #include "sgpr_mac.hpp"
 
 namespace comms {
@@ -1407,12 +1408,6 @@ static comms_status_t launch_os1024_dyn(hipStream_t s, In in, const float2* hist
 
 static const double kPi = 3.14159265358979323846264338327950288;
 
-static float2 unit_root_os(long long e, int denom) {
-    e %= denom;
-    const double a = -2.0 * kPi * static_cast<double>(e) / denom;
-    return make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-}
-
 // Tuning knobs (scripts/bench_fir.py sweeps them in the diagnostic build; compile-time defaults in the product: common.hpp)
 static int tune_int(const char* name, int dflt) { return diag_knob(name, dflt); }
 
@@ -1434,13 +1429,9 @@ static comms_status_t fir_prepare_os(comms_fir* h) {
     }
     h->hblk = (per - 1 + 255) / 256;
     if (h->hblk < 1) h->hblk = 1;
-    std::vector<float2> tw1(16 * 256), tw2(16 * 16), hdev(16 * 256);
-    for (int k0 = 0; k0 < 16; ++k0)
-        for (int t = 0; t < 256; ++t) tw1[k0 * 256 + t] = unit_root_os(static_cast<long long>(t) * k0, OSF);
-    for (int j = 0; j < 16; ++j)
-        for (int lo = 0; lo < 16; ++lo) tw2[j * 16 + lo] = unit_root_os(lo * j, 256);
-    COMMS_HIP_TRY(h->d_tw1.upload(tw1));
-    COMMS_HIP_TRY(h->d_tw2.upload(tw2));
+    std::vector<float2> hdev(16 * 256);
+    COMMS_HIP_TRY(h->d_tw1.upload(root_grid<float2>(16, 256, OSF)));  // W4096^{t*k0} at [k0][t]
+    COMMS_HIP_TRY(h->d_tw2.upload(root_grid<float2>(16, 16, 256)));   // W256^{lo*j} at [j][lo]
     std::vector<double> re, im;
     for (int pt = 0; pt < h->n_part; ++pt) {
         const int first = pt * per;
@@ -1502,20 +1493,10 @@ static void tap_spectrum(const comms_fir* h, int F, std::vector<double>& re, std
     tap_spectrum_range(h, 0, h->n_eff, F, re, im);
 }
 
-static float2 unit_root(long long e, int denom) {
-    e %= denom;
-    double a = -2.0 * kPi * static_cast<double>(e) / denom;
-    return make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-}
-
 static comms_status_t fir_prepare_os1024(comms_fir* h) {
     if (h->w_ready) return COMMS_OK;
     COMMS_ARG(h->n_eff <= 257, "the 1024-point overlap-save kernel supports at most 257 taps, got %d", h->n_eff);
-    std::vector<float2> tw1(16 * 64), tw2(16 * 4), hdev(16 * 64);
-    for (int k0 = 0; k0 < 16; ++k0)
-        for (int t = 0; t < 64; ++t) tw1[k0 * 64 + t] = unit_root(static_cast<long long>(t) * k0, 1024);
-    for (int k1 = 0; k1 < 16; ++k1)
-        for (int c = 0; c < 4; ++c) tw2[k1 * 4 + c] = unit_root(c * k1, 64);
+    std::vector<float2> hdev(16 * 64);
     std::vector<double> re, im;
     tap_spectrum(h, WF, re, im);
     // register 4t + m of lane k0 + 16g + 32h holds Z[k0 + 16 (2m + 8g + h) + 256 t] (os1024_core, stage 3)
@@ -1527,8 +1508,8 @@ static comms_status_t fir_prepare_os1024(comms_fir* h) {
                 hdev[(4 * t + m) * 64 + l] =
                     make_float2(static_cast<float>(re[k] / WF), static_cast<float>(im[k] / WF));
             }
-    COMMS_HIP_TRY(h->d_wtw1.upload(tw1));
-    COMMS_HIP_TRY(h->d_wtw2.upload(tw2));
+    COMMS_HIP_TRY(h->d_wtw1.upload(root_grid<float2>(16, 64, 1024)));  // W1024^{t*k0} at [k0][t]
+    COMMS_HIP_TRY(h->d_wtw2.upload(root_grid<float2>(16, 4, 64)));     // W64^{c*k1} at [k1][c]
     COMMS_HIP_TRY(h->d_whdev.upload(hdev));
     h->w_ready = true;
     return COMMS_OK;
@@ -1544,20 +1525,11 @@ static comms_status_t fir_prepare_os16k(comms_fir* h) {
     }
     const int N = h->n_eff;
     h->x_part = (N + X_PART - 1) / X_PART;
-    std::vector<float2> tw1(16 * 64), tw2(16 * 4), ta(16 * 16), tb(16 * 64), hdev(16 * 1024);
-    for (int k = 0; k < 16; ++k)
-        for (int t = 0; t < 64; ++t) {
-            tw1[k * 64 + t] = unit_root(static_cast<long long>(t) * k, 1024);
-            tb[k * 64 + t] = unit_root(static_cast<long long>(t) * k, XF);
-        }
-    for (int k1 = 0; k1 < 16; ++k1)
-        for (int c = 0; c < 4; ++c) tw2[k1 * 4 + c] = unit_root(c * k1, 64);
-    for (int w = 0; w < 16; ++w)
-        for (int k = 0; k < 16; ++k) ta[w * 16 + k] = unit_root(w * k, 256);
-    COMMS_HIP_TRY(h->d_xt[0].upload(tw1));
-    COMMS_HIP_TRY(h->d_xt[1].upload(tw2));
-    COMMS_HIP_TRY(h->d_xt[2].upload(ta));
-    COMMS_HIP_TRY(h->d_xt[3].upload(tb));
+    std::vector<float2> hdev(16 * 1024);
+    COMMS_HIP_TRY(h->d_xt[0].upload(root_grid<float2>(16, 64, 1024)));  // W1024^{t*k} at [k][t]
+    COMMS_HIP_TRY(h->d_xt[1].upload(root_grid<float2>(16, 4, 64)));     // W64^{c*k1} at [k1][c]
+    COMMS_HIP_TRY(h->d_xt[2].upload(root_grid<float2>(16, 16, 256)));   // W256^{w*k} at [w][k]
+    COMMS_HIP_TRY(h->d_xt[3].upload(root_grid<float2>(16, 64, XF)));    // W16384^{t*k} at [k][t]
     std::vector<double> re, im;
     for (int pt = 0; pt < h->x_part; ++pt) {
         const int first = pt * X_PART;

@@ -45,6 +45,7 @@
 #include "common.hpp"
 #include "fft_radix.hpp"
 #include "fir_handle.hpp"
+#include "roots.hpp"
 
 namespace comms {
 
@@ -432,12 +433,6 @@ using namespace comms;
 namespace {
 
 const double kPi8 = 3.14159265358979323846264338327950288;
-float2 root(long long e, int denom, int sign) {  // e^{sign 2 pi i e / denom}
-    e %= denom;
-    if (e < 0) e += denom;
-    const double a = 2.0 * kPi8 * static_cast<double>(e) / denom;
-    return make_float2(static_cast<float>(std::cos(a)), static_cast<float>(sign * std::sin(a)));
-}
 
 }  // namespace
 
@@ -489,15 +484,15 @@ static comms_status_t poly8_prepare(comms_fir* h, bool pre, uint64_t frac, hipSt
                 }
         }
     for (int k1 = 0; k1 < 16; ++k1)
-        for (int d = 0; d < 8; ++d) tw[k1 * 8 + d] = root(static_cast<long long>(d) * k1, 128, -1);
-    for (int i = 0; i < 64; ++i) sc[i] = root(i, 64, +1);
+        for (int d = 0; d < 8; ++d) tw[k1 * 8 + d] = root<float2>(d * k1, 128);
+    for (int i = 0; i < 64; ++i) sc[i] = root_conj<float2>(i, 64);
     for (int lane = 0; lane < 64; ++lane) {
         const int k1 = lane & 15, j = lane >> 4, j0 = j & 1, j1 = j >> 1, q1 = 2 * j0 + j1, ka = (lane & 31) >> 3;
-        ln[0 * 64 + lane] = root(j, 8, +1);
+        ln[0 * 64 + lane] = root_conj<float2>(j, 8);
         ln[1 * 64 + lane] = j0 ? make_float2(0.f, 1.f) : make_float2(1.f, 0.f);
-        ln[2 * 64 + lane] = root(static_cast<long long>(q1) * k1, 128, +1);
-        ln[3 * 64 + lane] = root(static_cast<long long>(q1 + 4) * k1, 128, +1);
-        for (int tq = 1; tq < 4; ++tq) ln[(3 + tq) * 64 + lane] = root(static_cast<long long>(tq) * ka, 16, +1);
+        ln[2 * 64 + lane] = root_conj<float2>(q1 * k1, 128);
+        ln[3 * 64 + lane] = root_conj<float2>((q1 + 4) * k1, 128);
+        for (int tq = 1; tq < 4; ++tq) ln[(3 + tq) * 64 + lane] = root_conj<float2>(tq * ka, 16);
     }
     if (!h->d_p8) COMMS_HIP_TRY(h->d_p8.alloc(t.size()));
     // (in stream order behind the launches that still read the old tables; the source is pageable memory, so the call returns

@@ -1,54 +1,39 @@
 """Which kernels an FFT length runs on, restated from the dispatch code, and the case tables of tests/test_gpu_fft_lengths.py
 drawn from that rule (no GPU here; tests/test_fft_cases.py holds the tables to the rule).
 
-`family_f32(n)` restates fft_setup / pow2_plan_build / pow2_run / comms_fft_run_dev (csrc/fft.hip), `family_f64(n)` restates
-fft_f64_prepare / pow2_run / comms_fft_f64_run_dev (csrc/fft_f64.hip).  Every threshold used here is listed in ANCHORS with the
-source text it restates; the CPU test looks each text up in the source, so a threshold that moves in the code fails there
-rather than leaving a table that no longer crosses its seam.
+`family_f32(n)` restates fft_form / pow2_form (csrc/fft_plan.hpp, the rule csrc/fft.hip builds its plans from): the CPU test
+runs that rule itself (tests/fft_plan_test.cpp) at every length up to 70000 and at every power of two +- 1 and compares the
+labels, and the header's batching constants with the F32_* values below.  `family_f64(n)` restates fft_f64_prepare / pow2_run /
+comms_fft_f64_run_dev (csrc/fft_f64.hip): every threshold of it is listed in ANCHORS with the source text it restates, and the
+CPU test looks each text up in the source.  Either way a threshold that moves in the code fails there rather than leaving a
+table that no longer crosses its seam.
 
 A case is (n, batches, in_place): transform length, the batch counts to run it at, and whether the in-place run is checked
 too (bitwise against the out-of-place one)."""
 
-# ---------------------------------------------------------------- thresholds (see ANCHORS for the source text of each)
+# ---------------------------------------------------------------- thresholds (f32: fft_plan.hpp's constants; f64: see ANCHORS)
 NUM_CU = 256                 # common.hpp: kNumCU
-F32_DIRECT_MAX = 64          # fft_setup: default of COMMS_FFT_DIRECT_MAX
-F32_BLU_MAX_N = 1 << 23      # fft_setup: Bluestein refuses longer transforms
-F32_BLU_CHUNK_POINTS = 1 << 24   # comms_fft_run_dev: chunk = 2^24 / M padded transforms per pass of the Bluestein loop
-F32_TILE_POINTS = 16384      # launch_rx: points per tile of fft_rx1024_kernel
-F32_RX_GRID = NUM_CU         # launch_rx: full tiles run on at most kNumCU workgroups
-F32_DIRECT_GROUP_CAP = 8 * NUM_CU  # comms_fft_run_dev: dft_small_kernel's grid, in groups of G = 256 / N transforms
+F32_DIRECT_MAX = 64          # FftKnobs::direct_max: default of COMMS_FFT_DIRECT_MAX
+F32_DIRECT_MAX_CAP = 4096    # kDirectMaxCap: the longest direct DFT whatever the selector says
+F32_SMALL_DFT_MAX = 128      # kSmallDftMax: dft_small_kernel up to here, dft_direct_kernel above
+F32_SMALL_DFT_LANES = 256    # kSmallDftLanes: dft_small_kernel runs G = 256 / N transforms per workgroup
+F32_BLU_MAX_N = 1 << 23      # kBluMaxN: Bluestein refuses longer transforms
+F32_BLU_CHUNK_POINTS = 1 << 24   # kBluChunkPoints: chunk = 2^24 / M padded transforms per pass of the Bluestein loop
+F32_TILE_POINTS = 16384      # kRxTilePoints: points per tile of fft_rx1024_kernel
+F32_RX_GRID = NUM_CU         # launch_rx: full tiles run on at most kNumCU workgroups (persistent_grid)
+F32_DIRECT_GROUP_CAP = 8 * NUM_CU  # small_dft_grid_cap(kNumCU): dft_small_kernel's grid, in groups of G transforms
 F64_LDS_POINTS = 4096        # fft_f64.hip: one pass through LDS up to here; the DFT sum up to here
 F64_MAX_P = 1 << 24          # fft_f64_prepare: the largest power-of-two transform
 F64_FOUR_STEP_PIECE = 64     # pow2_run: transforms per column + row pass pair
 F64_ONE_PASS_PIECE = 1 << 20  # pow2_run: transforms per launch of the one-pass form
 F64_DFT_PIECE = 32768        # comms_fft_f64_run_dev: transforms per launch of the DFT sum
 
-FFT_HIP = "comms_rs_amd/csrc/fft.hip"
 FFT_F64_HIP = "comms_rs_amd/csrc/fft_f64.hip"
 COMMON_HPP = "comms_rs_amd/csrc/common.hpp"
 
-# (file, function the text stands in, text) -- the source lines the rules below restate
+# (file, function the text stands in, text) -- the source lines the f64 rule and NUM_CU restate
 ANCHORS = [
     (COMMON_HPP, "kNumCU", "constexpr int kNumCU = 256;"),
-    (FFT_HIP, "fft_setup", 'diag_knob("COMMS_FFT_DIRECT_MAX", 64)'),
-    (FFT_HIP, "fft_setup", "if (N <= direct_max && N <= 4096) {"),
-    (FFT_HIP, "fft_setup", 'COMMS_ARG(N <= (static_cast<size_t>(1) << 23), "FFT length %zu too large", N);'),
-    (FFT_HIP, "fft_setup", "while (M < 2 * N - 1) M <<= 1;"),
-    (FFT_HIP, "pow2_plan_build", "COMMS_ARG(logN <= 24,"),
-    (FFT_HIP, "pow2_plan_build", "const bool rx = (N >= 2 && N <= 32) || N == 64 || N == 128 || N == 256 || N == 512 || N == 1024 || "
-                                 "N == 2048 || N == 4096 || N == 8192 || N == 16384;"),
-    (FFT_HIP, "pow2_plan_build", "if (N == 32768 && pl.d_fw1) {"),
-    (FFT_HIP, "pow2_plan_build", "} else if (logN > 20) {"),
-    (FFT_HIP, "pow2_plan_build", "const int log1 = (logN >= 15 && logN <= 20) ? logN - 10 : logN / 2, log2v = logN - log1;"),
-    (FFT_HIP, "pow2_plan_build", "(pl.pass[0].L == 64 || pl.pass[0].L == 128 || pl.pass[0].L == 256 || pl.pass[0].L == 512)) {"),
-    (FFT_HIP, "pow2_run", 'diag_knob("COMMS_FFT_LARGE_GATHER", 23)'),
-    (FFT_HIP, "launch_rx", "const size_t n_full = n_points / 16384, rem = n_points % 16384;"),
-    (FFT_HIP, "launch_rx", "n_full < static_cast<size_t>(kNumCU) ? n_full : kNumCU"),
-    (FFT_HIP, "comms_fft_run_dev", "size_t chunk = (static_cast<size_t>(1) << 24) / M;"),
-    (FFT_HIP, "comms_fft_run_dev", "const bool fuse = h->plan.rx_rad != 0 && !no_fuse;"),
-    (FFT_HIP, "comms_fft_run_dev", "if (h->N <= 128) {"),
-    (FFT_HIP, "comms_fft_run_dev", "groups < 8u * kNumCU ? groups : 8u * kNumCU"),
-    (FFT_HIP, "comms_fft_run_dev", "(batch + 256 / h->N - 1) / (256 / h->N)"),
     (FFT_F64_HIP, "F64_LDS_POINTS", "constexpr int F64_LDS_POINTS = 4096;"),
     (FFT_F64_HIP, "fft_f64_prepare", "h->kind = pow2 ? (N <= 4096 ? 0 : 1) : (N <= 4096 ? 2 : 3);"),
     (FFT_F64_HIP, "fft_f64_prepare", "while (P < 2 * N - 1) P <<= 1;"),
@@ -72,7 +57,7 @@ def ilog2(n):
 
 
 def padded(n):
-    """Bluestein's power-of-two length (fft_setup: `while (M < 2 * N - 1) M <<= 1`; fft_f64_prepare: the same for P)."""
+    """Bluestein's power-of-two length (fft_form: `while (c.M < 2 * N - 1) c.M <<= 1`; fft_f64_prepare: the same for P)."""
     m = 1
     while m < 2 * n - 1:
         m <<= 1
@@ -82,38 +67,38 @@ def padded(n):
 def _pow2_form_f32(length):
     """The form a power-of-two transform of `length` points runs on, with or without Bluestein around it."""
     log = ilog2(length)
-    if length <= 32:          # pow2_plan_build: `rx = (N >= 2 && N <= 32) || ...` -> rx_rad = -100 - N, the in-register forms
+    if length <= 32:          # Pow2Form::Tiny, Pow2Choice::rad = -N: the in-register forms of fft_rx1024_kernel
         return "tiny"
-    if length <= 16384:       # pow2_plan_build: `rx = ... N == 64 || ... || N == 16384`; pow2_run: `if (pl.rx_rad && !no_rx)`
-        return "rx%d" % length  # (one instantiation of fft_rx1024_kernel per length: RAD 0, 128, 256, 512, 1, 2, 4, 8, 16)
-    if length == 32768:       # pow2_plan_build: `if (N == 32768 && pl.d_fw1)`; pow2_run: `if (pl.d_rx32 && !no_rx32k)`
+    if length <= 16384:       # Pow2Form::Rx
+        return "rx%d" % length  # (one instantiation of fft_rx1024_kernel per length: Pow2Choice::rad 0, 128, 256, 512, 1, 2, 4, 8, 16)
+    if length == 32768:       # Pow2Form::Rx32k
         return "rx32k"
-    if log <= 19:             # pow2_plan_build: log1 = logN - 10 -> N1 = 64 ... 512 -> col_kind set: fft_cols_kernel + 1024-point rows
+    if log <= 19:             # Pow2Form::Cols, Pow2Choice::kind by the column length 64 ... 512: fft_cols_kernel + 1024-point rows
         return "cols_2p%d" % log
-    if log == 20:             # N1 = N2 = 1024: both passes on fft1024x16_kernel (pl.fast(i)), no column kernel
+    if log == 20:             # Pow2Form::Fast20: N1 = N2 = 1024, both passes on fft1024x16_kernel, no column kernel
         return "fast_2p20"
-    if log <= 23:             # pow2_plan_build: `else if (logN > 20)`; pow2_run: `ilog2(pl.N) <= gather_max` (23): gathered columns + rows
+    if log <= 23:             # Pow2Form::Gather up to FftKnobs::large_gather (23): gathered columns + rows
         return "gather_2p%d" % log
-    if log == 24:             # pow2_run: columns, rows in place, transpose
+    if log == 24:             # Pow2Form::Three: columns, rows in place, transpose
         return "three_2p24"
-    raise ValueError("power-of-two FFT supports up to 2^24 points")  # pow2_plan_build: COMMS_ARG(logN <= 24, ...)
+    raise ValueError("power-of-two FFT supports up to 2^24 points")  # fft_form: kPow2MaxLog
 
 
 def family_f32(n):
     """Label of the kernels FFTBatchNode(n) runs; ValueError where comms_fft_create refuses."""
     if n < 1:                 # comms_fft_create: COMMS_ARG(fft_size >= 1, ...)
         raise ValueError("fft_size must be >= 1")
-    if is_pow2(n):            # fft_setup: `if ((N & (N - 1)) == 0)` -> kind 0
-        if n == 1:            # comms_fft_run_dev: `if (h->N == 1)`: a copy
+    if is_pow2(n):            # fft_form: FftKind::Pow2
+        if n == 1:            # FftKind::Copy
             return "pow2_copy"
         return "pow2_" + _pow2_form_f32(n)
-    if n <= F32_DIRECT_MAX:   # fft_setup: `if (N <= direct_max && N <= 4096)` -> kind 1; run_dev: `if (h->N <= 128)`: dft_small_kernel
+    if n <= F32_DIRECT_MAX:   # fft_form: `N <= k.direct_max && N <= kDirectMaxCap` -> FftKind::DirectSmall (N <= 128): dft_small_kernel
         return "direct"
-    if n > F32_BLU_MAX_N:     # fft_setup: COMMS_ARG(N <= (1 << 23), "FFT length %zu too large")
+    if n > F32_BLU_MAX_N:     # fft_form: `N > kBluMaxN`: "FFT length %zu too large"
         raise ValueError("FFT length too large")
     m = padded(n)
-    form = _pow2_form_f32(m)  # fft_setup: pow2_plan_build(h->plan, M)
-    if form.startswith("rx") and form != "rx32k":  # run_dev: `fuse = h->plan.rx_rad != 0`: two launches of fft_rx1024_kernel, modes 1 and 2
+    form = _pow2_form_f32(m)  # fft_setup: pow2_plan_build(h->plan, M, pow2_form(M, ...))
+    if form.startswith("rx") and form != "rx32k":  # FftKind::BluFused (the plan's form is Rx): two launches of fft_rx1024_kernel, modes 1 and 2
         return "blu_fused_M%d" % m
     if form == "rx32k":
         return "blu_rx32k"
@@ -163,7 +148,7 @@ def all_families(family, limit=1 << 25):
 
 def direct_group(n):
     """Transforms per workgroup of dft_small_kernel (`const int G = 256 / N`)."""
-    return 256 // n
+    return F32_SMALL_DFT_LANES // n
 
 
 def tile_xforms(n):

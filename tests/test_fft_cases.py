@@ -1,6 +1,8 @@
 """The FFT case tables (tests/fft_cases.py) held to the rule they are drawn from: a case for every kernel family, every seam
-case across its seam, and every threshold of the rule still in the source it restates.  No GPU."""
+case across its seam, the f32 rule equal to the one the library runs (csrc/fft_plan.hpp, executed at every length), and every
+threshold of the f64 rule still in the source it restates.  No GPU."""
 import os
+import subprocess
 
 import pytest
 
@@ -9,8 +11,80 @@ import fft_cases as fc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+@pytest.fixture(scope="module")
+def plan(tmp_path_factory):
+    """tests/fft_plan_test.cpp -- the library's own rule (csrc/fft_plan.hpp) and table builder (csrc/roots.hpp), nothing else of
+    it -- built with AddressSanitizer and UBSan and run once as a program of its own: ({name: value}, {section: {n: label}})."""
+    exe = str(tmp_path_factory.mktemp("fft_plan") / "fft_plan_test")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-Wall", "-Wextra",
+                           "-Werror", "-I", os.path.join(ROOT, "comms_rs_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "fft_plan_test.cpp"), "-o", exe], timeout=300)
+    out = subprocess.run([exe, str(fc.NUM_CU)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    consts, forms, roots = {}, {}, None
+    for line in out.stdout.splitlines():
+        f = line.split("\t")
+        if f[0] == "const":
+            consts[f[1]] = int(f[2])
+        elif f[0] == "form":
+            forms.setdefault(f[1], {})[int(f[2])] = f[3]
+        elif f[0] == "roots":
+            roots = (int(f[1]), int(f[2]))
+    assert roots is not None and roots[0] > 40000 and roots[1] == 0, (roots, out.stderr[-4000:])
+    return consts, forms
+
+
+def test_family_f32_is_the_rule_the_library_runs(plan):
+    """family_f32(n) against fft_form / pow2_form themselves, at every length 1 ... 70000 and around every power of two up to
+    2^25: the same label, and a refusal exactly where family_f32 raises."""
+    _, forms = plan
+    default = forms["default"]
+    assert set(range(1, 70001)) <= set(default)
+    assert {(1 << k) + d for k in range(1, 26) for d in (-1, 0, 1)} <= set(default)
+    for n, label in default.items():
+        try:
+            want = fc.family_f32(n)
+        except ValueError:
+            want = "refused"
+        assert label == want or (want == "refused" and label.startswith("refused: ")), (n, label, want)
+    assert default[1 << 25] == "refused: power-of-two FFT supports up to 2^24 points (got 2^25)"
+    assert default[fc.F32_REFUSED] == "refused: FFT length %d too large" % fc.F32_REFUSED
+
+
+def test_batching_constants_are_the_headers(plan):
+    consts, _ = plan
+    assert consts == {"tile_points": fc.F32_TILE_POINTS, "blu_chunk_points": fc.F32_BLU_CHUNK_POINTS, "blu_max_n": fc.F32_BLU_MAX_N,
+                      "small_dft_grid_cap": fc.F32_DIRECT_GROUP_CAP, "small_dft_lanes": fc.F32_SMALL_DFT_LANES,
+                      "small_dft_max": fc.F32_SMALL_DFT_MAX, "direct_max": fc.F32_DIRECT_MAX, "direct_max_cap": fc.F32_DIRECT_MAX_CAP}
+
+
+def test_selectors_move_their_cases_to_the_forms_they_name(plan):
+    """Under each selector of FALLBACKS every one of its cases leaves its default form, for the form the comment beside the
+    selector names."""
+    _, forms = plan
+    assert set(forms) == {"default"} | {"%s=%s" % (name, value) for name, (value, _) in fc.FALLBACKS.items()}
+    named = {
+        # the generic tile kernel; Bluestein unfused on it
+        "COMMS_FFT_NO_RX": lambda n: "pow2_tile_2p%d" % fc.ilog2(n) if fc.is_pow2(n) else "blu_tile_M2p%d" % fc.ilog2(fc.padded(n)),
+        "COMMS_FFT_NO_RX32K": lambda n: "pow2_tile_2p15",                     # 32 x 1024 on the tile kernel + rows
+        "COMMS_FFT_NO_COLS": lambda n: "pow2_tile_2p%d" % fc.ilog2(n),        # column pass on the tile kernel
+        "COMMS_FFT_BLU_UNFUSED": lambda n: "blu_unfused_rx_M%d" % fc.padded(n),  # pre / mul / post around the single-pass kernel
+        # dft_small_kernel at 65 ... 128, dft_direct_kernel above
+        "COMMS_FFT_DIRECT_MAX": lambda n: "direct" if n <= fc.F32_SMALL_DFT_MAX else "direct_large",
+    }
+    assert set(named) == set(fc.FALLBACKS)
+    for name, (value, cases) in fc.FALLBACKS.items():
+        under = forms["%s=%s" % (name, value)]
+        for n, _ in cases:
+            assert under[n] != forms["default"][n], (name, n)
+            assert under[n] == named[name](n), (name, n, under[n])
+        # ... and moves nothing but what it names: every other length keeps its label's family
+        moved = {n for n in under if under[n] != forms["default"][n]}
+        assert all("tile" in under[n] or "unfused" in under[n] or under[n].startswith("direct") for n in moved), name
+
+
 def test_thresholds_still_stand_in_the_source():
-    """Each rule of family_f32 / family_f64 names the source text it restates; a threshold that moves takes its text along."""
+    """Each rule of family_f64 (and NUM_CU) names the source text it restates; a threshold that moves takes its text along."""
     texts = {}
     for path, where, text in fc.ANCHORS:
         if path not in texts:
